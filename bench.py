@@ -7,21 +7,27 @@ already resident in HBM (BASELINE config 2, SURVEY.md 8d). One process per GPU; 
 one block per rank with no data-path collective; each step ends with ONE gather of the decoded
 bits to rank 0 over RCCL (torch.distributed backend "nccl"), inside the timed region.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--samples S]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--streams B] [--samples S] [--dump-outputs DIR] [--full]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 Both forms work at every N: started WITHOUT a torchrun environment (no WORLD_SIZE) and asked for N > 1 (or for
 --exercise-gather), the script counts the visible GPUs, refuses if there are fewer than N ("N GPUs requested, V visible"),
-and otherwise replaces itself (exec) with the torch.distributed.run command line above on a free port of 127.0.0.1 --
-the driver's N = 1 invocation and an N = 8 invocation are then the same command with a different number.
+and otherwise starts the torch.distributed.run command line above on a free port of 127.0.0.1 as a child process and exits
+with its exit code -- the driver's N = 1 invocation and an N = 8 invocation are then the same command with a different number.
 
 Prints ONE JSON line on rank 0 (see the field notes in DESIGN.md "Measurement"). This file is the timed path, top to bottom: synthetic
 batch -> handle -> step() -> clock -> JSON; the checker and the side figures live in tools/bench_checks.py, the launcher logic in
 tools/bench_launch.py.
+
+A plain run does only what the headline needs: set up, warm up, time --steps steps, write the outputs of the last timed step if
+--dump-outputs is given, print the line. --full adds everything else after the clock has stopped: the CPU leg (cpu_baseline),
+the oracle replay of the device's bits (bit_check, bit_errors_vs_*, gather_check), the side figures and the other BASELINE
+configurations (extra_configs); --no-cpu-baseline, --no-extra and --check-streams trim a --full run.
 """
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -59,7 +65,6 @@ def synth_base_streams(nsamp):
     L.fsk_mod_c.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.fsk_destroy.argtypes = [C.c_void_p]
     bin_path = os.path.join(ROOT, "pirip_amd", "bin", "fsk_get_test_bits")
-    import subprocess
     nsym = (nsamp + TS) // TS + NSYM
     nsym -= nsym % NSYM
     bits = np.frombuffer(subprocess.run([bin_path, "-", str(nsym)], capture_output=True, check=True).stdout,
@@ -76,6 +81,41 @@ def synth_base_streams(nsamp):
         q = np.clip(np.rint(127.0 + 32.0 * x[:nsamp + TS].astype(np.float64)), 0, 255).astype(np.uint8)
         out[k] = q
     return out, bits
+
+
+DUMP_BITS_BYTES = 48 << 20                    # --dump-outputs: budget of the sampled bits (the whole dump stays below 64 MB)
+DUMP_SEED = 0x5eed                            # fixed sample of streams, the same in every run with the same arguments
+
+
+def dump_outputs(outdir, msgs, B, maxf, nbits, consumed):
+    """--dump-outputs DIR: what a caller of the timed path receives from its last timed step, as .npy files --
+      bits.npy          float32 [S, maxf', nbits]  decoded bits (0/1) of S streams drawn with DUMP_SEED, slots past the frame count 0
+      stream_index.npy  float64 [S]                which streams bits.npy holds (global index, rank-major)
+      frames.npy        float32 [world * B]        frames decoded per stream
+      consumed.npy      float64 [B]                input samples consumed per stream (rank 0's streams)
+    msgs: the packed-bit messages rank 0 holds after the step (its own at N = 1, the gathered ones otherwise)."""
+    import torch
+    from pirip_amd.shard import _payload_layout, unpack_bits
+    nb, off, _ = _payload_layout(B, maxf, nbits)
+    nby = (nbits + 7) // 8
+    nfr = np.concatenate([m[off:off + 4 * B].view(torch.int32).cpu().numpy() for m in msgs]).astype(np.int64)
+    total = len(nfr)
+    fmax = min(maxf, DUMP_BITS_BYTES // (nbits * 4))
+    n = max(1, min(total, DUMP_BITS_BYTES // (fmax * nbits * 4)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(total, size=n, replace=False))
+    parts = []
+    for r, m in enumerate(msgs):
+        loc = idx[(idx >= r * B) & (idx < (r + 1) * B)] - r * B
+        if len(loc):
+            packed = m[:nb].view(B, maxf, nby)[torch.from_numpy(loc).to(m.device), :fmax]
+            parts.append(unpack_bits(packed, nbits).cpu().numpy())
+    bits = np.concatenate(parts).astype(np.float32)
+    bits[np.arange(fmax)[None, :] >= nfr[idx][:, None]] = 0.0
+    os.makedirs(outdir, exist_ok=True)
+    np.save(os.path.join(outdir, "bits.npy"), bits)
+    np.save(os.path.join(outdir, "stream_index.npy"), idx.astype(np.float64))
+    np.save(os.path.join(outdir, "frames.npy"), nfr.astype(np.float32))
+    np.save(os.path.join(outdir, "consumed.npy"), consumed.cpu().numpy().astype(np.float64))
 
 
 def main():
@@ -101,10 +141,17 @@ def main():
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="compute time per core of the CPU leg")
     ap.add_argument("--cpu-baseline-only", action="store_true",
                     help="time the CPU leg on this host, print its JSON object and exit (no GPU touched): what the "
-                         "self-launcher runs before it becomes torch.distributed.run")
+                         "self-launcher runs before it starts torch.distributed.run")
     ap.add_argument("--cpu-leg-only", action="store_true",
                     help="run this rank's part of the CPU-leg hand-over (measure / wait / quote) and exit: CPU test hook")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed to DIR/*.npy (see dump_outputs)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: CPU leg, oracle replay of the bits, side figures, "
+                         "other BASELINE configurations")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.cpu_baseline_only:
         base, _ = synth_base_streams(args.samples)
@@ -120,23 +167,24 @@ def main():
         env = dict(os.environ)
         env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # dmabuf IPC only on these hosts (RCCL needs it)
         env.setdefault("OMP_NUM_THREADS", "1")
-        if not args.no_cpu_baseline and args.ebno_db is None and CPU_ENV not in env:
+        if args.full and not args.no_cpu_baseline and args.ebno_db is None and CPU_ENV not in env:
             # the CPU leg of an N-rank job: timed NOW, while this is the only process of the job, in a child of its own (this
             # process has already asked the HIP runtime for the device count), and handed to rank 0 through the environment
-            import subprocess
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--cpu-baseline-only", "--cpu-seconds",
                                 str(args.cpu_seconds), "--samples", str(args.samples)], capture_output=True, text=True)
             lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
             env[CPU_ENV] = lines[-1] if r.returncode == 0 and lines else json.dumps({"error": (r.stderr or "no output")[-400:]})
         print("bench.py: starting " + " ".join(argv[1:]), file=sys.stderr, flush=True)
-        os.execve(argv[0], argv, env)                          # this process BECOMES the launcher: one JSON line, one exit code
+        # a child, not an exec: this process has opened the device to count it. Its exit code is this process's
+        rc = subprocess.run(argv, env=env).returncode
+        raise SystemExit(rc if rc >= 0 else 128 - rc)
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
 
     B, nsamp = args.streams, args.samples
-    cpu_how, cpu_arg = cpu_leg_plan(rank, world, os.environ, args.no_cpu_baseline or args.ebno_db is not None)
+    cpu_how, cpu_arg = cpu_leg_plan(rank, world, os.environ, not args.full or args.no_cpu_baseline or args.ebno_db is not None)
     waited = None
     if cpu_how == "wait":                             # rank 0 is timing the oracle on this host's cores: stay off them
         waited = wait_for_cpu_leg(cpu_arg, args.cpu_seconds * 2 + 180.0)
@@ -328,22 +376,25 @@ def main():
             "rccl": ({"world_size": rccl_world, "backend": rccl_backend, "exchange": "one gather of the packed-bit message to rank 0 per step"}
                      if dist else None),
         }
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, gather_out if dist else [payloads[(nstep - 1) % 2][0]], B, maxf, h.Nbits, cons)
         # everything below runs after the clock has stopped: the checker (oracle replay), the CPU leg's figure, the side figures
         ctx = {"torch": torch, "pirip_amd": pirip_amd, "h": h, "dev": dev, "payloads": payloads, "nstep": nstep, "cons": cons, "maxf": maxf,
                "nsamp": nsamp, "B": B, "args": args, "stream": stream, "dist": dist, "gather_out": gather_out, "frames_first": frames_first,
                "world": world, "local_rank": local_rank}
         chk = None
-        try:
-            chk = bench_checks.bit_checks(out, ctx)
-        except Exception as e:  # the oracle is a checker; its absence must not hide the GPU number
-            out["bit_check"] = f"unavailable: {e!r}"
-        if world == 1 and not args.no_extra:
+        if args.full:
+            try:
+                chk = bench_checks.bit_checks(out, ctx)
+            except Exception as e:  # the oracle is a checker; its absence must not hide the GPU number
+                out["bit_check"] = f"unavailable: {e!r}"
+        if args.full and world == 1 and not args.no_extra:
             bench_checks.side_figures(out, ctx, chk, khash, ALGO_BYTES_PER_SAMPLE, HBM_PEAK_GBPS)
             if isinstance(out.get("exact_order_kernel"), dict):
                 out["exact_order_kernel"]["of_the_default_kernels_rate"] = out["exact_order_kernel"]["Msamples_per_s"] / value
         if cpu_res is not None:
             out["cpu_baseline"] = cpu_res
-        if world == 1 and not args.no_extra:
+        if args.full and world == 1 and not args.no_extra:
             # the other BASELINE configurations, as side keys with their own roofline fractions (not the metric)
             del dev, payloads, ctx, chk
             torch.cuda.empty_cache()

@@ -92,7 +92,7 @@ def test_cpu_leg_hand_over_between_two_ranks():
     oracle, rank 1 does nothing until rank 0 has published, then both go on. --cpu-leg-only stops them before the GPU part."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", _bench().CPU_ENV)}
     port = str(_bench().free_port())
-    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-leg-only", "--cpu-seconds", "1", "--samples", "120000"]
+    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--cpu-leg-only", "--full", "--cpu-seconds", "1", "--samples", "120000"]
     ps = [subprocess.Popen(common, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True,
                            env=dict(env, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE="2", MASTER_ADDR="127.0.0.1", MASTER_PORT=port))
           for r in (1, 0)]
@@ -110,21 +110,25 @@ def test_cpu_leg_hand_over_between_two_ranks():
 
 
 def test_launcher_times_the_cpu_leg_before_exec(monkeypatch, tmp_path):
-    """The "spawn" branch: the CPU leg runs in a child BEFORE this process becomes torch.distributed.run, and travels in the environment."""
+    """The "spawn" branch: the CPU leg runs in a child BEFORE this process starts torch.distributed.run, and travels in the environment."""
     b = _bench()
     seen = {}
+    real_run = subprocess.run
 
-    def fake_execve(path, argv, env):
-        seen["argv"], seen["env"] = argv, env
-        raise SystemExit(0)
+    def fake_run(argv, *a, **kw):
+        if "torch.distributed.run" not in argv:
+            return real_run(argv, *a, **kw)          # the CPU leg's child
+        seen["argv"], seen["env"] = argv, kw["env"]
+        return subprocess.CompletedProcess(argv, 0)
 
-    monkeypatch.setattr(b.os, "execve", fake_execve)
+    monkeypatch.setattr(b.subprocess, "run", fake_run)
     monkeypatch.setattr(b, "visible_gpus", lambda: 2)
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--cpu-seconds", "0.2", "--samples", "120000"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "2", "--full", "--cpu-seconds", "0.2", "--samples", "120000"])
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", b.CPU_ENV):
         monkeypatch.delenv(k, raising=False)
-    with pytest.raises(SystemExit):
+    with pytest.raises(SystemExit) as ex:
         b.main()
+    assert ex.value.code == 0                    # the launcher's exit code
     assert "--nproc-per-node=2" in seen["argv"]
     o = json.loads(seen["env"][b.CPU_ENV])
     assert o["value"] > 0 and o["cores"] >= 1
@@ -132,11 +136,11 @@ def test_launcher_times_the_cpu_leg_before_exec(monkeypatch, tmp_path):
 
 @pytest.mark.gpu
 def test_self_launched_gather_run_prints_one_line():
-    """The N > 1 code path end to end on one GPU: bench.py re-execs itself under torch.distributed.run (1 rank), RCCL
+    """The N > 1 code path end to end on one GPU: bench.py starts itself under torch.distributed.run (1 rank) as a child, RCCL
     world of 1, packed message written in place, asynchronous gather every step, the line parsed like the driver does."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--exercise-gather", "--streams", "96",
-                        "--samples", "240000", "--steps", "2", "--warmup", "1", "--no-extra", "--cpu-seconds", "1",
+                        "--samples", "240000", "--steps", "2", "--warmup", "1", "--full", "--no-extra", "--cpu-seconds", "1",
                         "--check-streams", "8"], capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "starting -m torch.distributed.run" in r.stderr
@@ -161,7 +165,7 @@ def test_driver_launched_rank_carries_the_cpu_leg():
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", b.CPU_ENV)}
     argv = b.launcher_argv(1, b.free_port(), os.path.join(ROOT, "bench.py"),
                            ["--gpus", "1", "--exercise-gather", "--streams", "96", "--samples", "240000", "--steps", "2", "--warmup", "1",
-                            "--no-extra", "--cpu-seconds", "1", "--check-streams", "8"])
+                            "--full", "--no-extra", "--cpu-seconds", "1", "--check-streams", "8"])
     r = subprocess.run(argv, capture_output=True, text=True, env=env, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -5,7 +5,7 @@
 R=${GRAFT_REPO_ROOT:-/root/repo}
 echo "# streams  G samples/s  ms per launch (HIP events)  fraction of HBM roofline (2.0058 B/sample)"
 for B in 64 256 1024 3072 4096 6144 16384; do
-  python $R/bench.py --streams $B --steps 20 --warmup 3 --no-cpu-baseline --no-extra --check-streams 8 2>/dev/null | python3 -c "
+  python $R/bench.py --streams $B --steps 20 --warmup 3 --full --no-cpu-baseline --no-extra --check-streams 8 2>/dev/null | python3 -c "
 import sys, json
 j = json.loads(sys.stdin.read())
 print('%8d  %10.1f  %10.3f  %8.4f  bit_errors_vs_cpu_ref %d' % ($B, j['value'] / 1e3, j['roofline']['kernel_ms'], j['roofline']['frac'], j['bit_errors_vs_cpu_ref']))"

@@ -10,7 +10,7 @@ import time
 
 def visible_gpus():
     """HIP devices this process can open, counted through the product library (hipGetDeviceCount): no torch import, no
-    context created in a process that is about to exec. 0 when there is no device or no driver."""
+    context created in a process that is about to start the launcher. 0 when there is no device or no driver."""
     try:
         import pirip_amd
         return max(int(pirip_amd.device_count()), 0)
@@ -28,8 +28,8 @@ def free_port():
 def launch_plan(gpus, exercise_gather, environ, visible):
     """What a bench.py process started with these arguments has to do before anything else:
       ("run", None)      -- it is a rank (torchrun environment present) or a plain single-GPU run: go on in this process
-      ("spawn", None)    -- no torchrun environment, but N > 1 ranks (or the gather path at N = 1) are wanted: re-exec
-                            under torch.distributed.run with N local ranks
+      ("spawn", None)    -- no torchrun environment, but N > 1 ranks (or the gather path at N = 1) are wanted: start
+                            torch.distributed.run with N local ranks as a child process
       ("refuse", reason) -- the request cannot be met on this box
     `visible` is a callable so that the GPU count is only taken when it matters."""
     if gpus < 1:

@@ -36,28 +36,28 @@ pmc() { rm -rf /tmp/pm; timeout $1 rocprofv3 --kernel-trace --pmc $2 -d /tmp/pm 
 
 if has headline; then
   O=$R/gpurun_out/${tag}_headline_stats.txt
-  echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra --check-streams 16" > $O
-  stats $ST python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra --check-streams 16
+  echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra --check-streams 16" > $O
+  stats $ST python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra --check-streams 16
   python $R/tools/rocprof_summary.py /tmp/pr | head -6 >> $O
   echo "# bench line under the profiler:" >> $O; grep '^{' /tmp/pr.log | cut -c1-1600 >> $O
   O=$R/gpurun_out/${tag}_headline_pmc.txt
-  echo "# PMC passes, each its own run of: rocprofv3 --kernel-trace --pmc <set> -- python bench.py --streams 6144 --steps 2 --warmup 1 --no-cpu-baseline --no-extra --check-streams 4" > $O
+  echo "# PMC passes, each its own run of: rocprofv3 --kernel-trace --pmc <set> -- python bench.py --streams 6144 --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra --check-streams 4" > $O
   echo "# kernel_source_hash $(khash)" >> $O
   echo "# (6144 streams = two rounds of the 3072 resident waves; packed-bit output, the bench's mode at every N; values are means per shader engine (x32 for the chip) except FETCH/WRITE_SIZE (KiB, chip))" >> $O
   for set in "${SETS[@]}"; do
-    pmc $ST "$set" python $R/bench.py --streams 6144 --steps 2 --warmup 1 --no-cpu-baseline --no-extra --check-streams 4
+    pmc $ST "$set" python $R/bench.py --streams 6144 --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra --check-streams 4
     python $R/tools/pmc_extract.py /tmp/pm fsk_demod | cut -c1-24,52-140 >> $O
   done
 fi
 if has band; then
   O=$R/gpurun_out/${tag}_band_only_stats_pmc.txt
-  echo "# PIRIP_EST_BAND=1 rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra --check-streams 16" > $O
-  PIRIP_EST_BAND=1 stats $ST python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra --check-streams 16
+  echo "# PIRIP_EST_BAND=1 rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra --check-streams 16" > $O
+  PIRIP_EST_BAND=1 stats $ST python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra --check-streams 16
   python $R/tools/rocprof_summary.py /tmp/pr | head -6 >> $O
   echo "# bench line under the profiler:" >> $O; grep '^{' /tmp/pr.log | cut -c1-1200 >> $O
   echo "# PMC passes (6144 streams), each its own run: FETCH_SIZE, WRITE_SIZE, instruction counts" >> $O
   for set in "FETCH_SIZE" "WRITE_SIZE" "$SQ1"; do
-    PIRIP_EST_BAND=1 pmc $ST "$set" python $R/bench.py --streams 6144 --steps 2 --warmup 1 --no-cpu-baseline --no-extra --check-streams 4
+    PIRIP_EST_BAND=1 pmc $ST "$set" python $R/bench.py --streams 6144 --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra --check-streams 4
     python $R/tools/pmc_extract.py /tmp/pm fsk_demod | cut -c1-24,52-140 >> $O
   done
 fi
