@@ -13,6 +13,8 @@
  *              fsk_demod / fsk_demod_sd ... with codec2's own names and calling convention
  *              [UPSTREAM-RECALLED codec2 src/fsk.h], so `rtl_fsk` and `fsk_demod` link
  *              against libpirip_hip.so instead of libcodec2.so.
+ *   section G  streaming receiver (pirip_hip_rx_*)         : sections A, B and E as a live
+ *              N-channel receiver, each channel's tail carried on the device.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -373,6 +375,52 @@ int pirip_hip_ldpc_rx_host(pirip_hip_ldpc *h, const float *rx_filt, int ncalls, 
  * the decoder on ncw codewords of LLRs ([ncw][n] -> hard codeword bits [ncw][n], {iterations, parity checks ok} [ncw][2]) */
 int pirip_hip_ldpc_llr(pirip_hip_ldpc *h, const float *d_rx_filt, int ncalls, float *d_llr, void *hip_stream);
 int pirip_hip_ldpc_decode_llr(pirip_hip_ldpc *h, const float *d_llr, int ncw, uint8_t *d_bits, int32_t *d_iter_pcc, void *hip_stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* section G : streaming receiver (N live channels, block after block)                 */
+/*   Composes the handles above: a demodulator of nstreams channels, optionally the     */
+/*   FSK_LDPC receivers of the same channels and a csdr front end. Each channel's       */
+/*   unconsumed tail stays on the device, right-aligned in front of the landing zone    */
+/*   of the next block: no host round trip, no repacking, and every     */
+/*   channel carries fewer than nin_max samples from one call into the next.           */
+/*   Bit packing, estimator settings, burst mode, eye, get_Sf, get_stream_state and the  */
+/*   LDPC info stay on the handles the caller owns; the receiver does not own them.     */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_rx pirip_hip_rx;
+/* dem: the demodulator (nstreams channels). ldpc: NULL for bits / soft magnitudes / stats out, else FSK_LDPC records out (same
+ * nstreams / M / Nsym / device as dem). dec: NULL when the caller's samples are modem-rate samples of dem's in_format; else tuner-rate
+ * u8 IQ through csdr's convert_u8_f | fir_decimate_cc D (dec created with out_s16 == (in_format == PIRIP_IN_CS16), dem's in_format
+ * PIRIP_IN_CF32 or PIRIP_IN_CS16 -- rtl_fsk -a and the README.md:109 pipe). block: input samples per channel per call at the input
+ * rate. PIRIP_ERR_BAD_ARG unless block % D == 0 and every call hands the demodulator >= nin_max new samples (with dec the first call
+ * hands it fewer than the others: the filter's first output needs ntaps inputs); PIRIP_ERR_UNSUPPORTED when the demodulator's kernel
+ * cannot take calls of that size. The handles must outlive the receiver; create synchronises the device. */
+int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *dec, int64_t block, pirip_hip_rx **out);
+int pirip_hip_rx_destroy(pirip_hip_rx *rx);
+/* output rows per channel per call: floor((nin_max - 1 + m) / nin_min) + 1, m = modem-rate samples per call, nin_min = 2 N - nin_max */
+int64_t pirip_hip_rx_max_frames(const pirip_hip_rx *rx);
+/* zero-copy ingest: where the next call's block of channel s goes (*d_block + s * *stride_bytes, block samples of the input format:
+ * u8 IQ with dec, else dem's in_format); free to be written once the previous call's work on the same HIP stream has run */
+int pirip_hip_rx_input(pirip_hip_rx *rx, void **d_block, size_t *stride_bytes);
+/* One block per channel (already in the input) -> outputs. Without ldpc: the demodulator's outputs as pirip_hip_demod_batch writes them
+ * (d_bits / d_rx_filt / d_stats, strides in elements, each may be NULL); d_status / d_payload / d_info must be NULL. With ldpc: FSK_LDPC
+ * records as pirip_hip_fsk_ldpc_rx_batch writes them ([s][max_frames][...], one row per demodulator call, rows beyond d_nframes[s] as
+ * documented there; d_stats optional); d_bits / d_rx_filt must be NULL. d_nframes [s]: frames of this call (required with ldpc, else
+ * may be NULL). Rows per channel: pirip_hip_rx_max_frames. Enqueued on hip_stream (NULL = default stream); never synchronises. */
+int pirip_hip_rx_process(pirip_hip_rx *rx, uint8_t *d_bits, size_t bits_stride, float *d_rx_filt, size_t filt_stride,
+                         uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, float *d_stats, size_t stats_stride,
+                         int32_t *d_nframes, void *hip_stream);
+/* The same after copying channel s's block from d_in + s * in_stride_bytes (DEVICE pointer, block samples of the input format) into
+ * the input, on hip_stream. */
+int pirip_hip_rx_push(pirip_hip_rx *rx, const void *d_in, size_t in_stride_bytes,
+                      uint8_t *d_bits, size_t bits_stride, float *d_rx_filt, size_t filt_stride,
+                      uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, float *d_stats, size_t stats_stride,
+                      int32_t *d_nframes, void *hip_stream);
+/* Host copies (synchronises the device), per channel [nstreams], either may be NULL: modem-rate samples consumed since create / reset,
+ * and samples carried into the next call (< nin_max). PIRIP_ERR_HIP if a carry ever reached nin_max (only possible if the frame budget
+ * bound, which its sizing rules out; that carry was dropped). */
+int pirip_hip_rx_get_counters(pirip_hip_rx *rx, int64_t *consumed_total, int32_t *backlog);
+/* Drops the carries and resets dem (and ldpc): the next call is the first after create. */
+int pirip_hip_rx_reset(pirip_hip_rx *rx, void *hip_stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

@@ -115,6 +115,15 @@ def lib():
     L.pirip_hip_fsk_ldpc_last_path.argtypes = [vp]
     L.pirip_hip_ldpc_llr.argtypes = [vp, vp, i32, vp, vp]
     L.pirip_hip_ldpc_decode_llr.argtypes = [vp, vp, i32, vp, vp, vp]
+    L.pirip_hip_rx_create.argtypes = [vp, vp, vp, i64, C.POINTER(vp)]
+    L.pirip_hip_rx_destroy.argtypes = [vp]
+    L.pirip_hip_rx_max_frames.restype = i64
+    L.pirip_hip_rx_max_frames.argtypes = [vp]
+    L.pirip_hip_rx_input.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
+    L.pirip_hip_rx_process.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+    L.pirip_hip_rx_push.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
+    L.pirip_hip_rx_get_counters.argtypes = [vp, vp, vp]
+    L.pirip_hip_rx_reset.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -407,3 +416,55 @@ class HipLdpc:
         _chk(self.L.pirip_hip_ldpc_rx_host(self.h, r.ctypes.data, n, status.ctypes.data, payload.ctypes.data, info.ctypes.data),
              "pirip_hip_ldpc_rx_host")
         return status, payload, info
+
+
+class HipRx:
+    """Streaming receiver over live channels (include/pirip_hip.h section G): one block per channel per call, each channel's unconsumed
+    tail carried on the device. dem: HipDemod; ldpc: HipLdpc or None (records out instead of bits); dec: HipDecim or None (u8 IQ at
+    the tuner rate in instead of modem-rate samples); block: input samples per channel per call. The handles must outlive the receiver."""
+
+    def __init__(self, dem, ldpc=None, dec=None, block=None):
+        self.L = lib()
+        self.dem, self.ldpc, self.dec = dem, ldpc, dec
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_rx_create(dem.h, ldpc.h if ldpc is not None else None, dec.h if dec is not None else None, int(block),
+                                        C.byref(h)), "pirip_hip_rx_create")
+        self.h = h
+        self.block, self.nstreams = int(block), dem.nstreams
+        self.max_frames = int(self.L.pirip_hip_rx_max_frames(self.h))
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_rx_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def input(self):
+        """(device pointer of channel 0's next block, stride in bytes): the zero-copy landing zone (pirip_hip_rx_input)."""
+        p, st = C.c_void_p(), C.c_size_t(0)
+        _chk(self.L.pirip_hip_rx_input(self.h, C.byref(p), C.byref(st)), "pirip_hip_rx_input")
+        return int(p.value), int(st.value)
+
+    def process(self, d_bits=0, bits_stride=0, d_filt=0, filt_stride=0, d_status=0, d_payload=0, d_info=0, d_stats=0, stats_stride=0,
+                d_nframes=0, stream=0):
+        """Raw device pointers (ints); enqueues on `stream`, does not synchronise."""
+        _chk(self.L.pirip_hip_rx_process(self.h, d_bits, bits_stride, d_filt, filt_stride, d_status, d_payload, d_info, d_stats,
+                                         stats_stride, d_nframes, stream), "pirip_hip_rx_process")
+
+    def push(self, d_in, in_stride, d_bits=0, bits_stride=0, d_filt=0, filt_stride=0, d_status=0, d_payload=0, d_info=0, d_stats=0,
+             stats_stride=0, d_nframes=0, stream=0):
+        """process() after copying channel s's block from d_in + s * in_stride (device) into the input."""
+        _chk(self.L.pirip_hip_rx_push(self.h, d_in, in_stride, d_bits, bits_stride, d_filt, filt_stride, d_status, d_payload, d_info,
+                                      d_stats, stats_stride, d_nframes, stream), "pirip_hip_rx_push")
+
+    def counters(self):
+        """(consumed_total int64[nstreams], backlog int32[nstreams]) -- synchronises."""
+        import numpy as np
+        tot = np.zeros(self.nstreams, dtype=np.int64)
+        bl = np.zeros(self.nstreams, dtype=np.int32)
+        _chk(self.L.pirip_hip_rx_get_counters(self.h, tot.ctypes.data, bl.ctypes.data), "pirip_hip_rx_get_counters")
+        return tot, bl
+
+    def reset(self, stream=0):
+        _chk(self.L.pirip_hip_rx_reset(self.h, stream), "pirip_hip_rx_reset")

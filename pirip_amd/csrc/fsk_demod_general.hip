@@ -345,6 +345,14 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
     const int tid = threadIdx.x;
     const int NT = blockDim.x;
     const int sid = blockIdx.x;
+    // a segment (SegDesc: capture.hip, stream_rx.hip): own first sample, output row and frame budget, as the wave and block kernels
+    // honour it; max_frames < 0: this stream slot sits the launch out, its state untouched. (The exact prologue is descriptor-free.)
+    int64_t seg_in = 0, out0 = 0, seg_frames = a.io.max_frames;
+    if (!EXACT0 && a.io.seg) {
+        const SegDesc sd = a.io.seg[sid];
+        if (sd.max_frames < 0) return;                     // (workgroup-uniform: no barrier has been reached)
+        seg_in = sd.in_off; out0 = sd.out_frame0; seg_frames = sd.max_frames;
+    }
     Lds L;
     float *red = (float *)smem;                            // 2 * kMaxWaves words of reduction scratch
     carve(d, &L, smem + kRedBytes);
@@ -398,7 +406,9 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
     for (int m = 0; m < kMaxTones; m++) theta[m] = EXACT0 ? 0u : a.s.theta[(size_t)sid * kMaxTones + m];
     __syncthreads();
 
-    const uint8_t *in_base = a.io.in + (size_t)sid * a.io.in_stride;
+    const int in_bps = in_u8 ? 2 : in_s16 ? 4 : 8;
+    const uint8_t *in_base = a.io.in + (size_t)sid * a.io.in_stride + (size_t)seg_in * in_bps;
+    const int64_t nsamp = a.io.nsamp - seg_in;
     constexpr int kPre = 12;                              // input read-ahead registers per thread (12 x NT samples)
     const int nin_max = d.N + d.nin_step;
     const bool can_pre = !EXACTM && !direct && (in_u8 || in_s16) && nin_max <= kPre * NT;
@@ -413,9 +423,9 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
     uint32_t x0_dth[kMaxTones] = {0u, 0u, 0u, 0u};       // EXACT0: the frame's tone estimates as the wave kernel's state block names them
     int x0_tix[kMaxTones] = {0, 0, 0, 0};
     if (!EXACT0 && a.io.first) { pos = a.io.first[sid]; frame = pos ? 1 : 0; }      // an exact-first-frame prologue ran in this call
-    const int64_t frame_limit = EXACT0 ? (a.io.max_frames < 1 ? a.io.max_frames : 1) : a.io.max_frames;
+    const int64_t frame_limit = EXACT0 ? (a.io.max_frames < 1 ? a.io.max_frames : 1) : seg_frames;
 
-    while (frame < frame_limit && pos + nin <= a.io.nsamp) {
+    while (frame < frame_limit && pos + nin <= nsamp) {
         // ---- a-1: convert nin samples to complex float -----------------------------------
         // The u8 / s16 input of the NEXT frame is requested into registers right after this frame's input has
         // landed in LDS (nin_max samples from pos + nin: the next nin is not known yet) and written to LDS at the
@@ -447,7 +457,7 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
             for (int u = 0; u < kPre; u++) {
                 const int i = tid + u * NT;
                 if (u * NT < nin_max) {                     // wave-uniform
-                    const int64_t gi = (p1 + i < a.io.nsamp) ? p1 + i : a.io.nsamp - 1;
+                    const int64_t gi = (p1 + i < nsamp) ? p1 + i : nsamp - 1;
                     pre[u] = in_u8 ? (uint32_t)((const uint16_t *)in_base)[gi] : ((const uint32_t *)in_base)[gi];
                 }
             }
@@ -662,10 +672,10 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
         } else { tcr = block_sum(tcr, red, tid, NT); tci = block_sum(tci, red, tid, NT); }
 
         const int frame_bytes = d.pack_bits ? (d.Nbits + 7) / 8 : d.Nbits;
-        uint8_t *bits_o = a.io.bits ? a.io.bits + (size_t)sid * a.io.bits_stride + (size_t)frame * frame_bytes : nullptr;
+        uint8_t *bits_o = a.io.bits ? a.io.bits + (size_t)sid * a.io.bits_stride + (size_t)(out0 + frame) * frame_bytes : nullptr;
         uint8_t *bits_l = (uint8_t *)L.X;            // FFT work array is free here: staging for packed output (Nbits <= 8*Ndft)
-        float *filt_o = a.io.filt ? a.io.filt + (size_t)sid * a.io.filt_stride + (size_t)frame * M * Nsym : nullptr;
-        float *stats_o = a.io.stats ? a.io.stats + (size_t)sid * a.io.stats_stride + (size_t)frame * PIRIP_STATS_PER_FRAME : nullptr;
+        float *filt_o = a.io.filt ? a.io.filt + (size_t)sid * a.io.filt_stride + (size_t)(out0 + frame) * M * Nsym : nullptr;
+        float *stats_o = a.io.stats ? a.io.stats + (size_t)sid * a.io.stats_stride + (size_t)(out0 + frame) * PIRIP_STATS_PER_FRAME : nullptr;
 
         const bool bad = isnan(tcr) || isnan(tci);
         if (!bad) {

@@ -127,6 +127,16 @@ struct DemodArgs {
     float tw_s2[18];            // wave-uniform FFT twiddles of the wave kernel (Ndft 256: stage 2; Ndft 512: tw[64], tw[128], tw[192])
 };
 
+// pirip_hip_demod_batch with per-stream segment descriptors (pirip_capi.hip; seg == nullptr: the public call itself)
+int demod_batch_seg(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp, uint8_t *d_bits, size_t bits_stride,
+                    float *d_rx_filt, size_t filt_stride, float *d_stats, size_t stats_stride, int32_t *d_nframes, int64_t *d_consumed,
+                    int64_t max_frames, const SegDesc *seg, hipStream_t st);
+// pirip_hip_fsk_ldpc_rx_batch with per-stream segment descriptors (ldpc_kernels.hip)
+int fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp,
+                          uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, float *d_stats, size_t stats_stride,
+                          int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, const SegDesc *seg, hipStream_t st);
+int ldpc_handle_shape(const pirip_hip_ldpc *h, int *M, int *Nsym, int *nstreams, int *device);   // (ldpc_kernels.hip)
+
 // launchers (fsk_demod_kernels.hip)
 size_t demod_general_lds_bytes(const FskDims &d);
 hipError_t launch_demod_general(const DemodArgs &a, int nstreams, hipStream_t stream);

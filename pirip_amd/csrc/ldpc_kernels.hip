@@ -35,7 +35,8 @@ using namespace pirip;
 // pirip_capi.hip: the demodulator's side of the fused hand-over
 namespace pirip {
 int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp, const SoftOut &so, float *d_stats, size_t stats_stride,
-                     int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, hipStream_t st, int s0 = 0, int n = -1);
+                     int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, hipStream_t st, int s0 = 0, int n = -1,
+                     const SegDesc *seg = nullptr);
 int demod_handle_shape(const pirip_hip_demod *h, int *M, int *Nsym, int *nstreams, int *device);
 int demod_streams_per_cu(const pirip_hip_demod *h);                     // streams of the handle's wave instance that one CU holds at a time (0: another kernel)
 bool demod_soft_capable(const pirip_hip_demod *h, int64_t nsamp);      // the handle's kernel instance can write the fused hand-over for calls of nsamp samples
@@ -1583,6 +1584,18 @@ int pirip_hip_fsk_ldpc_rx_batch(pirip_hip_demod *dem, pirip_hip_ldpc *h, const v
                                 uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, float *d_stats, size_t stats_stride,
                                 int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, void *hip_stream)
 {
+    return pirip::fsk_ldpc_rx_batch_seg(dem, h, d_in, in_stride_bytes, nsamp, d_status, d_payload, d_info, d_stats, stats_stride, d_nframes, d_consumed,
+                                        max_frames, nullptr, (hipStream_t)hip_stream);
+}
+
+}  // extern "C"
+
+// seg: per-stream segment descriptors of the demodulator (stream_rx.hip; nullptr: the public call); each stream range of a split call
+// takes its own slice of them, like every other per-stream array
+int pirip::fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp,
+                                 uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, float *d_stats, size_t stats_stride,
+                                 int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, const SegDesc *seg, hipStream_t hip_stream)
+{
     if (!dem || !h || !d_in || !d_status || !d_payload || !d_info || !d_nframes || nsamp < 0 || max_frames <= 0 || max_frames > (1 << 24)) return PIRIP_ERR_BAD_ARG;
     int M = 0, Nsym = 0, ns = 0, dev = 0;
     if (demod_handle_shape(dem, &M, &Nsym, &ns, &dev) != PIRIP_OK) return PIRIP_ERR_BAD_ARG;
@@ -1604,7 +1617,7 @@ int pirip_hip_fsk_ldpc_rx_batch(pirip_hip_demod *dem, pirip_hip_ldpc *h, const v
             hipLaunchKernelGGL(hist_prepare_kernel, dim3((2 * c.bpf + 255) / 256, n), dim3(256), 0, sg, c.bpf, h->d_llr_hist + (size_t)s0 * (size_t)(2 * c.bpf),
                                h->d_llr_all + (size_t)s0 * bd.llr_stride, bd.llr_stride, h->d_words + (size_t)s0 * bd.nwords, bd.nwords);
             LCHK(hipGetLastError());
-            const int r = demod_batch_soft(dem, d_in, in_stride_bytes, nsamp, so, d_stats, stats_stride, d_nframes, d_consumed, max_frames, sg, s0, n);
+            const int r = demod_batch_soft(dem, d_in, in_stride_bytes, nsamp, so, d_stats, stats_stride, d_nframes, d_consumed, max_frames, sg, s0, n, seg);
             if (r != PIRIP_OK) return r;
             return stages_after_llr(h, d_nframes, ncalls, d_status, d_payload, d_info, sg, s0, n, beside, sdec, ev);
         };
@@ -1688,11 +1701,20 @@ int pirip_hip_fsk_ldpc_rx_batch(pirip_hip_demod *dem, pirip_hip_ldpc *h, const v
         LCHK(hipMalloc((void **)&h->d_filt_work, sizeof(float) * (size_t)h->nstreams * ncalls * per));
         h->filt_cap = (size_t)ncalls;
     }
-    rc = pirip_hip_demod_batch(dem, d_in, in_stride_bytes, nsamp, nullptr, 0, h->d_filt_work, (size_t)ncalls * per, d_stats, stats_stride, d_nframes, d_consumed,
-                               max_frames, hip_stream);
+    rc = demod_batch_seg(dem, d_in, in_stride_bytes, nsamp, nullptr, 0, h->d_filt_work, (size_t)ncalls * per, d_stats, stats_stride, d_nframes, d_consumed,
+                         max_frames, seg, st);
     if (rc != PIRIP_OK) return rc;
     return pirip_hip_ldpc_rx_batch(h, h->d_filt_work, (size_t)ncalls * per, d_nframes, ncalls, d_status, d_payload, d_info, hip_stream);
 }
+
+int pirip::ldpc_handle_shape(const pirip_hip_ldpc *h, int *M, int *Nsym, int *nstreams, int *device)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    *M = h->dev.M; *Nsym = h->dev.Nsym; *nstreams = h->nstreams; *device = h->device;
+    return PIRIP_OK;
+}
+
+extern "C" {
 
 int pirip_hip_fsk_ldpc_last_path(const pirip_hip_ldpc *h) { return h ? h->last_path_fused : PIRIP_ERR_BAD_ARG; }
 

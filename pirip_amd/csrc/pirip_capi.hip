@@ -347,12 +347,28 @@ int pirip_hip_demod_batch(pirip_hip_demod *h, const void *d_in, size_t in_stride
                           float *d_stats, size_t stats_stride, int32_t *d_nframes, int64_t *d_consumed,
                           int64_t max_frames, void *hip_stream)
 {
+    return pirip::demod_batch_seg(h, d_in, in_stride_bytes, nsamp, d_bits, bits_stride, d_rx_filt, filt_stride, d_stats, stats_stride,
+                                  d_nframes, d_consumed, max_frames, nullptr, (hipStream_t)hip_stream);
+}
+
+}  // extern "C"
+
+namespace pirip {
+// pirip_hip_demod_batch with per-stream segment descriptors (seg: device array [nstreams] or nullptr; stream_rx.hip): stream s reads from
+// d_in + s * in_stride_bytes + seg[s].in_off samples, nsamp - seg[s].in_off of them, and writes seg[s].max_frames frames at most from
+// output row seg[s].out_frame0 on. With descriptors the exact-first-frame prologue does not run (it only notes that the streams started).
+int demod_batch_seg(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp,
+                    uint8_t *d_bits, size_t bits_stride, float *d_rx_filt, size_t filt_stride,
+                    float *d_stats, size_t stats_stride, int32_t *d_nframes, int64_t *d_consumed,
+                    int64_t max_frames, const SegDesc *seg, hipStream_t hip_stream)
+{
     if (!h || !d_in || nsamp < 0 || max_frames < 0) return PIRIP_ERR_BAD_ARG;
     if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
     DemodArgs a;
     fill_args(h, &a);
     a.io = DemodIO{(const uint8_t *)d_in, in_stride_bytes, nsamp, d_bits, bits_stride, d_rx_filt, filt_stride,
                    d_stats, stats_stride, d_nframes, d_consumed, max_frames, SoftOut{nullptr, 0, nullptr, 0, nullptr, 0}};
+    a.io.seg = seg;
     a.io.eye = (h->kernel == PIRIP_KERNEL_GENERAL || h->kernel == PIRIP_KERNEL_EXACT) ? h->d_eye : nullptr;
     hipError_t e;
     if (h->kernel == 2 && nsamp > demod_wave_max_samples(a.d)) return PIRIP_ERR_UNSUPPORTED;   // present the batch in smaller pieces (before anything runs)
@@ -367,14 +383,11 @@ int pirip_hip_demod_batch(pirip_hip_demod *h, const void *d_in, size_t in_stride
     return PIRIP_OK;
 }
 
-}  // extern "C"
-
 // internal (ldpc_kernels.hip): one batch with the fused FSK_LDPC hand-over instead of bits / magnitudes
-namespace pirip {
 // s0 / n (n < 0: all): streams [s0, s0 + n) of the handle only -- every per-stream array of the argument block is advanced to stream s0, the
 // pointers the caller passes are those of stream 0 (pirip_hip_fsk_ldpc_rx_batch runs two ranges on two HIP streams)
 int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp, const SoftOut &so, float *d_stats, size_t stats_stride,
-                     int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, hipStream_t st, int s0, int n)
+                     int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, hipStream_t st, int s0, int n, const SegDesc *seg)
 {
     if (!h || !d_in || nsamp < 0 || max_frames < 0 || !so.llr || !so.words || !so.lnI0 || (so.bit0 & 31)) return PIRIP_ERR_BAD_ARG;
     if (h->kernel != 2 || !demod_wave_soft_capable(h->plan.d) || nsamp > demod_wave_max_samples(h->plan.d)) return PIRIP_ERR_UNSUPPORTED;
@@ -382,6 +395,7 @@ int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_byte
     DemodArgs a;
     fill_args(h, &a);
     a.io = DemodIO{(const uint8_t *)d_in, in_stride_bytes, nsamp, nullptr, 0, nullptr, 0, d_stats, stats_stride, d_nframes, d_consumed, max_frames, so};
+    a.io.seg = seg;
     (void)exact0_prologue(h, &a, st);                    // (the fused hand-over has no prologue: this only notes that the streams have started)
     int nrun = h->nstreams;
     if (n >= 0) {
@@ -394,6 +408,7 @@ int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_byte
         if (a.io.stats) a.io.stats += z * stats_stride;
         a.io.nframes += z;
         if (a.io.consumed) a.io.consumed += z;
+        if (a.io.seg) a.io.seg += z;
         a.io.soft.llr += z * so.llr_stride; a.io.soft.words += z * so.words_stride;
         nrun = n;
     }
