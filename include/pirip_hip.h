@@ -15,6 +15,9 @@
  *              against libpirip_hip.so instead of libcodec2.so.
  *   section G  streaming receiver (pirip_hip_rx_*)         : sections A, B and E as a live
  *              N-channel receiver, each channel's tail carried on the device.
+ *   section H  channelizer (pirip_hip_chan_*)              : K channels out of W wideband u8 IQ
+ *              captures (shift_addition_cc | fir_decimate_cc D per channel), one pass over
+ *              the input; also the front end of a section G receiver.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -421,6 +424,47 @@ int pirip_hip_rx_push(pirip_hip_rx *rx, const void *d_in, size_t in_stride_bytes
 int pirip_hip_rx_get_counters(pirip_hip_rx *rx, int64_t *consumed_total, int32_t *backlog);
 /* Drops the carries and resets dem (and ldpc): the next call is the first after create. */
 int pirip_hip_rx_reset(pirip_hip_rx *rx, void *hip_stream);
+
+/* ----------------------------------------------------------------------------------- */
+/* section H : channelizer (K channels out of W wideband u8 IQ captures)                */
+/*   csdr shift_addition_cc (-f_c/Fs) | fir_decimate_cc D [| convert_f_s16] per channel, */
+/*   every channel of a capture computed from one read of it.           */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_chan pirip_hip_chan;
+typedef struct pirip_chan_info {
+    int Fs, D, ntaps, ntaps_padded, ninputs, nchan, out_s16, device;
+} pirip_chan_info;
+/* ninputs wideband u8 IQ captures at Fs samples/s; nchan channels, channel c = (capture chan_input[c], centre offset chan_offset_hz[c]).
+ * Taps: section B's prototype for the same D / transition_bw (csdr Hamming low-pass, cutoff 0.5/D, padded with zeros to Lp taps).
+ * out_s16 != 0 appends convert_f_s16 (interleaved s16 IQ, y * 32767 truncated, clamped to the s16 range), else complex float out.
+ * For channel c, with x[n] = convert_u8_f(byte) = b/127.5 - 1 and t0 the absolute index of the call's first input sample:
+ *     y_c[j] = sum_{i=0}^{Lp-1} h[i] x[jD+i] e^{-j 2 pi f_c (t0 + jD + i) / Fs}
+ * -- the direct form and tap order of section B; a tone at f_c + a Hz in the capture comes out at +a Hz in channel c.
+ * Computed as g_c[i] = h[i] e^{-j 2 pi f_c i / Fs} (host, double, rounded to float) and one rotation per output whose phase is the exact
+ * integer (f_c mod Fs)(t0 + jD) mod Fs: a function of the absolute sample index only, so consecutive calls on overlapping windows give
+ * the one-shot output bit for bit, and a channel's output does not depend on which other channels the handle has. csdr's own
+ * shift_addition_cc runs a recursive cos/sin phasor restarted every buffer (its rounding depends on csdr's buffer size): that recursion
+ * is deliberately not reproduced. PIRIP_ERR_BAD_ARG for nchan < 1, ninputs < 1, D < 1, a chan_input outside [0, ninputs) or an offset
+ * outside -Fs/2 < f_c < Fs/2; PIRIP_ERR_UNSUPPORTED for Fs > 2^24. */
+int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s16, int ninputs, int nchan, const int32_t *chan_input,
+                          const int32_t *chan_offset_hz, int device, pirip_hip_chan **out);
+int pirip_hip_chan_destroy(pirip_hip_chan *ch);
+int pirip_hip_chan_get_info(const pirip_hip_chan *ch, pirip_chan_info *info);
+int pirip_hip_chan_taps(const pirip_hip_chan *ch, float *taps, int *ntaps);      /* host copy of the prototype h (ntaps, unpadded) */
+/* outputs per channel for n_in input samples: floor((n_in - Lp)/D) + 1, or 0 (= pirip_hip_decim_nout for the same D / transition_bw) */
+int64_t pirip_hip_chan_nout(const pirip_hip_chan *ch, int64_t n_in);
+/* Capture i: n_in u8 IQ samples at d_in + i*in_stride_bytes (d_in and the stride even), whose first sample has absolute index t0.
+ * Channel c: pirip_hip_chan_nout(n_in) samples at (char*)d_out + c*out_stride_bytes (aligned to the output sample: 8 or 4 bytes).
+ * Stateless; enqueued on hip_stream (NULL = default stream), never synchronises. */
+int pirip_hip_chan_batch(pirip_hip_chan *ch, const uint8_t *d_in, size_t in_stride_bytes, int64_t n_in, int64_t t0,
+                         void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* Section G with the channelizer as its front end: one wideband capture row per input (ninputs rows at pirip_hip_rx_input, block u8 IQ
+ * samples each), the channelizer writing straight into the nchan channels' modem-rate landing zones. dem must have nstreams == nchan and
+ * in_format PIRIP_IN_CF32 (out_s16 == 0) or PIRIP_IN_CS16 (out_s16 != 0); ldpc optional as in pirip_hip_rx_create; block: wideband samples
+ * per input per call, a multiple of D. Each input row keeps the channelizer's history of Lp - D samples right-aligned in front of its
+ * block; the receiver tracks t0 on the host (no synchronisation). pirip_hip_rx_input / _push / _process / _get_counters / _reset then
+ * work as documented above with ninputs input rows (push copies ninputs rows); _reset also restarts t0 at 0. */
+int pirip_hip_rx_create_chan(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_chan *chan, int64_t block, pirip_hip_rx **out);
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

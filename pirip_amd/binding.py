@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A and B).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G and H).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -34,6 +34,10 @@ class FskInfo(C.Structure):
 class CaptureReport(C.Structure):
     _fields_ = [("segments", C.c_int32), ("segment_frames", C.c_int32), ("passes", C.c_int32), ("segments_rerun", C.c_int32),
                 ("frames_demodulated", C.c_int64)]
+
+
+class ChanInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("Fs", "D", "ntaps", "ntaps_padded", "ninputs", "nchan", "out_s16", "device")]
 
 
 class LdpcInfo(C.Structure):
@@ -124,6 +128,14 @@ def lib():
     L.pirip_hip_rx_push.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
     L.pirip_hip_rx_get_counters.argtypes = [vp, vp, vp]
     L.pirip_hip_rx_reset.argtypes = [vp, vp]
+    L.pirip_hip_rx_create_chan.argtypes = [vp, vp, vp, i64, C.POINTER(vp)]
+    L.pirip_hip_chan_create.argtypes = [i32, i32, C.c_float, i32, i32, i32, vp, vp, i32, C.POINTER(vp)]
+    L.pirip_hip_chan_destroy.argtypes = [vp]
+    L.pirip_hip_chan_get_info.argtypes = [vp, C.POINTER(ChanInfo)]
+    L.pirip_hip_chan_taps.argtypes = [vp, vp, C.POINTER(i32)]
+    L.pirip_hip_chan_nout.restype = i64
+    L.pirip_hip_chan_nout.argtypes = [vp, i64]
+    L.pirip_hip_chan_batch.argtypes = [vp, vp, sz, i64, i64, vp, sz, vp]
     _lib = L
     return L
 
@@ -337,6 +349,56 @@ class HipDecim:
              "pirip_hip_decim_batch")
 
 
+class HipChan:
+    """Channelizer (include/pirip_hip.h section H): channel c = csdr shift_addition_cc (-offsets[c]/Fs) | fir_decimate_cc D of capture
+    inputs[c] (all 0 when inputs is None), for every channel of every capture in one pass over the u8 IQ. out_s16: interleaved s16 IQ out
+    (convert_f_s16), else complex float."""
+
+    def __init__(self, Fs, D, offsets, inputs=None, transition_bw=0.05, out_s16=False, device=-1):
+        import numpy as np
+        self.L = lib()
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        inp = np.zeros(off.size, dtype=np.int32) if inputs is None else np.ascontiguousarray(inputs, dtype=np.int32).reshape(-1)
+        if inp.size != off.size:
+            raise ValueError("inputs and offsets must have the same length")
+        ninputs = int(inp.max()) + 1 if inp.size else 1
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_chan_create(int(Fs), int(D), transition_bw, 1 if out_s16 else 0, ninputs, int(off.size),
+                                          inp.ctypes.data if inp.size else None, off.ctypes.data if off.size else None, device, C.byref(h)),
+             "pirip_hip_chan_create")
+        self.h = h
+        self.info = ChanInfo()
+        _chk(self.L.pirip_hip_chan_get_info(self.h, C.byref(self.info)), "pirip_hip_chan_get_info")
+        self.Fs, self.D, self.out_s16 = int(Fs), int(D), bool(out_s16)
+        self.offsets, self.inputs = off.copy(), inp.copy()
+        self.ninputs, self.nchan, self.Lp = self.info.ninputs, self.info.nchan, self.info.ntaps_padded
+        self.bytes_per_sample = 4 if out_s16 else 8
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_chan_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def taps(self):
+        """the prototype low-pass h (section B's taps for the same D / transition_bw, unpadded)"""
+        import numpy as np
+        n = C.c_int(0)
+        self.L.pirip_hip_chan_taps(self.h, None, C.byref(n))
+        t = np.zeros(n.value, dtype=np.float32)
+        self.L.pirip_hip_chan_taps(self.h, t.ctypes.data, C.byref(n))
+        return t
+
+    def nout(self, n_in):
+        return int(self.L.pirip_hip_chan_nout(self.h, int(n_in)))
+
+    def batch(self, d_in, in_stride, n_in, d_out, out_stride, t0=0, stream=0):
+        """capture i at d_in + i * in_stride (n_in u8 IQ samples, the first at absolute index t0) -> channel c at d_out + c * out_stride
+        (nout(n_in) samples); raw device pointers, enqueued on `stream`, does not synchronise"""
+        _chk(self.L.pirip_hip_chan_batch(self.h, d_in, in_stride, int(n_in), int(t0), d_out, out_stride, stream), "pirip_hip_chan_batch")
+
+
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,
               amp=32.0, sigma=0.0, seed=1, skip=None, stream=0):
     """Device-side fsk_mod -c | u8 quantiser [| AWGN] for len(f1_hz) streams (include/pirip_hip.h B2).
@@ -421,16 +483,25 @@ class HipLdpc:
 class HipRx:
     """Streaming receiver over live channels (include/pirip_hip.h section G): one block per channel per call, each channel's unconsumed
     tail carried on the device. dem: HipDemod; ldpc: HipLdpc or None (records out instead of bits); dec: HipDecim or None (u8 IQ at
-    the tuner rate in instead of modem-rate samples); block: input samples per channel per call. The handles must outlive the receiver."""
+    the tuner rate in instead of modem-rate samples); chan: HipChan or None (wideband u8 IQ captures in, one row per capture, each
+    channel of the channelizer a channel of dem; exclusive with dec); block: input samples per channel (per capture with chan) per call.
+    The handles must outlive the receiver."""
 
-    def __init__(self, dem, ldpc=None, dec=None, block=None):
+    def __init__(self, dem, ldpc=None, dec=None, block=None, chan=None):
         self.L = lib()
-        self.dem, self.ldpc, self.dec = dem, ldpc, dec
+        if dec is not None and chan is not None:
+            raise ValueError("HipRx: dec and chan are mutually exclusive")
+        self.dem, self.ldpc, self.dec, self.chan = dem, ldpc, dec, chan
         h = C.c_void_p()
-        _chk(self.L.pirip_hip_rx_create(dem.h, ldpc.h if ldpc is not None else None, dec.h if dec is not None else None, int(block),
-                                        C.byref(h)), "pirip_hip_rx_create")
+        if chan is not None:
+            _chk(self.L.pirip_hip_rx_create_chan(dem.h, ldpc.h if ldpc is not None else None, chan.h, int(block), C.byref(h)),
+                 "pirip_hip_rx_create_chan")
+        else:
+            _chk(self.L.pirip_hip_rx_create(dem.h, ldpc.h if ldpc is not None else None, dec.h if dec is not None else None, int(block),
+                                            C.byref(h)), "pirip_hip_rx_create")
         self.h = h
         self.block, self.nstreams = int(block), dem.nstreams
+        self.ninputs = chan.ninputs if chan is not None else dem.nstreams
         self.max_frames = int(self.L.pirip_hip_rx_max_frames(self.h))
 
     def close(self):

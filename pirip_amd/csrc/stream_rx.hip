@@ -9,6 +9,9 @@
 // With a decimator, a tuner-rate row per channel:  [Hpad | block]   (Hpad = H u8 samples rounded up to 256 bytes)
 //   the decimator's history of H samples (the same H for every channel and every call: block % D == 0) right-aligned in front of the
 //   block; the decimator writes straight into the modem rows at C_pre through its output stride.
+// With a channelizer (section H), the same tuner-rate rows, one per wideband INPUT instead of one per channel; the channelizer writes
+// every channel of an input into that channel's modem row at C_pre, and the absolute index of each call's first input sample (t0) is
+// tracked here on the host: it only depends on the number of calls.
 #include <hip/hip_runtime.h>
 
 #include <cstring>
@@ -106,7 +109,10 @@ struct pirip_hip_rx {
     pirip_hip_demod *dem = nullptr;
     pirip_hip_ldpc *ldpc = nullptr;
     pirip_hip_decim *dec = nullptr;
+    pirip_hip_chan *chan = nullptr;
     int nstreams = 0, bps = 0, nin_max = 0;
+    int nraw = 0;                          // tuner-rate rows: nstreams with a decimator, the channelizer's inputs with a channelizer
+    int64_t t_in = 0;                      // channelizer: input samples per input before this call's block
     int64_t block = 0;                     // input samples per channel per call
     int64_t m = 0, m_first = 0;            // modem-rate samples per call (the first call after create / reset: m_first)
     int64_t c_pre = 0, budget = 0;
@@ -136,6 +142,7 @@ int rx_clear(pirip_hip_rx *rx, hipStream_t st)
         hipMemsetAsync(rx->d_total, 0, sizeof(int64_t) * ns, st) != hipSuccess ||
         hipMemsetAsync(rx->d_flag, 0, sizeof(int32_t), st) != hipSuccess) return PIRIP_ERR_HIP;
     rx->first = true;
+    rx->t_in = 0;
     return PIRIP_OK;
 }
 
@@ -172,14 +179,15 @@ int rx_run(pirip_hip_rx *rx, uint8_t *d_bits, size_t bits_stride, float *d_rx_fi
     const int64_t mc = rx->first ? rx->m_first : rx->m;
     uint8_t *land = rx->d_rows + (size_t)rx->c_pre * rx->bps;
     // 1. front end: decimate into the modem rows at C_pre, then keep the last H tuner-rate samples in front of the next block
-    if (rx->dec) {
+    if (rx->dec || rx->chan) {
         const uint8_t *in = rx->d_raw + rx->raw_pre - (rx->first ? 0 : (size_t)rx->H * 2);
         const int64_t n_in = rx->block + (rx->first ? 0 : rx->H);
-        int rc = pirip_hip_decim_batch(rx->dec, in, rx->raw_row_bytes, n_in, land, rx->row_bytes, rx->nstreams, st);
+        int rc = rx->dec ? pirip_hip_decim_batch(rx->dec, in, rx->raw_row_bytes, n_in, land, rx->row_bytes, rx->nstreams, st)
+                         : pirip_hip_chan_batch(rx->chan, in, rx->raw_row_bytes, n_in, rx->first ? 0 : rx->t_in - rx->H, land, rx->row_bytes, st);
         if (rc != PIRIP_OK) return rc;
         if (rx->H > 0 && hipMemcpy2DAsync(rx->d_raw + rx->raw_pre - (size_t)rx->H * 2, rx->raw_row_bytes,
                                           rx->d_raw + rx->raw_pre + (size_t)(rx->block - rx->H) * 2, rx->raw_row_bytes,
-                                          (size_t)rx->H * 2, (size_t)rx->nstreams, hipMemcpyDeviceToDevice, st) != hipSuccess) return PIRIP_ERR_HIP;
+                                          (size_t)rx->H * 2, (size_t)rx->nraw, hipMemcpyDeviceToDevice, st) != hipSuccess) return PIRIP_ERR_HIP;
     }
     // 2. demodulator (or the FSK_LDPC chain): the first call on row + C_pre without descriptors -- the exact-first-frame prologue then
     //    applies as in pirip_hip_demod_batch --, every later one from each channel's carried tail
@@ -197,14 +205,11 @@ int rx_run(pirip_hip_rx *rx, uint8_t *d_bits, size_t bits_stride, float *d_rx_fi
     hipLaunchKernelGGL(rx_advance_kernel, dim3((rx->nstreams + kChannelsPerBlock - 1) / kChannelsPerBlock), dim3(kWave * kChannelsPerBlock), 0, st, a);
     if (hipGetLastError() != hipSuccess) return PIRIP_ERR_HIP;
     rx->first = false;
+    rx->t_in += rx->block;
     return PIRIP_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *dec, int64_t block, pirip_hip_rx **out)
+int rx_create_impl(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *dec, pirip_hip_chan *chan, int64_t block, pirip_hip_rx **out)
 {
     if (!out) return PIRIP_ERR_BAD_ARG;
     *out = nullptr;
@@ -216,7 +221,7 @@ int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_de
         if (ldpc_handle_shape(ldpc, &M, &Nsym, &ns, &dev) != PIRIP_OK) return PIRIP_ERR_BAD_ARG;
         if (M != d.M || Nsym != d.Nsym || ns != dem->nstreams || dev != dem->device) return PIRIP_ERR_BAD_ARG;
     }
-    int Lp = 0, D = 1, out_s16 = 0;
+    int Lp = 0, D = 1, out_s16 = 0, nraw = dem->nstreams;
     if (dec) {
         if (d.in_format != PIRIP_IN_CF32 && d.in_format != PIRIP_IN_CS16) return PIRIP_ERR_BAD_ARG;
         const int rc = decim_shape(dec, &Lp, &D, &out_s16);
@@ -224,20 +229,30 @@ int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_de
         if (out_s16 != (d.in_format == PIRIP_IN_CS16)) return PIRIP_ERR_BAD_ARG;
         if (block % D != 0) return PIRIP_ERR_BAD_ARG;
     }
+    if (chan) {
+        pirip_chan_info ci{};
+        if (d.in_format != PIRIP_IN_CF32 && d.in_format != PIRIP_IN_CS16) return PIRIP_ERR_BAD_ARG;
+        if (pirip_hip_chan_get_info(chan, &ci) != PIRIP_OK) return PIRIP_ERR_BAD_ARG;
+        if (ci.out_s16 != (d.in_format == PIRIP_IN_CS16) || ci.nchan != dem->nstreams || ci.device != dem->device) return PIRIP_ERR_BAD_ARG;
+        D = ci.D; Lp = ci.ntaps_padded; nraw = ci.ninputs;
+        if (block % D != 0) return PIRIP_ERR_BAD_ARG;
+    }
+    auto fe_nout = [&](int64_t n) { return dec ? pirip_hip_decim_nout(dec, n) : pirip_hip_chan_nout(chan, n); };
     pirip_hip_rx *rx = new (std::nothrow) pirip_hip_rx();
     if (!rx) return PIRIP_ERR_NOMEM;
-    rx->dem = dem; rx->ldpc = ldpc; rx->dec = dec; rx->block = block; rx->D = D;
+    rx->dem = dem; rx->ldpc = ldpc; rx->dec = dec; rx->chan = chan; rx->block = block; rx->D = D;
     rx->nstreams = dem->nstreams;
+    rx->nraw = nraw;
     rx->bps = bytes_per_sample(d.in_format);
     rx->nin_max = d.N + d.nin_step;
     const int nin_min = 2 * d.N - rx->nin_max;
     rx->m = block / D;
     rx->m_first = rx->m;
-    if (dec) {
+    if (dec || chan) {
         // the first call's D-spaced outputs stop where the filter runs out of input; from then on the leftover H is the same every call
-        rx->m_first = pirip_hip_decim_nout(dec, block);
+        rx->m_first = fe_nout(block);
         rx->H = block - rx->m_first * D;
-        if (rx->H < 0 || rx->H > block || pirip_hip_decim_nout(dec, block + rx->H) != rx->m) { delete rx; return PIRIP_ERR_BAD_ARG; }
+        if (rx->H < 0 || rx->H > block || fe_nout(block + rx->H) != rx->m) { delete rx; return PIRIP_ERR_BAD_ARG; }
     }
     // every call hands the demodulator at least nin_max new samples: the carry (< nin_max) is then never overwritten by its own move
     if (rx->m_first < rx->nin_max || nin_min <= 0) { delete rx; return PIRIP_ERR_BAD_ARG; }
@@ -248,10 +263,10 @@ int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_de
     rx->row_bytes = round_up((size_t)(rx->c_pre + rx->m) * rx->bps, 256);
     const size_t ns = (size_t)rx->nstreams;
     bool ok = hipMalloc((void **)&rx->d_rows, rx->row_bytes * ns) == hipSuccess;
-    if (dec) {
+    if (dec || chan) {
         rx->raw_pre = round_up((size_t)rx->H * 2, 256);
         rx->raw_row_bytes = round_up(rx->raw_pre + (size_t)block * 2, 256);
-        ok &= hipMalloc((void **)&rx->d_raw, rx->raw_row_bytes * ns) == hipSuccess;
+        ok &= hipMalloc((void **)&rx->d_raw, rx->raw_row_bytes * (size_t)nraw) == hipSuccess;
     }
     ok &= hipMalloc((void **)&rx->d_consumed, sizeof(int64_t) * ns) == hipSuccess;
     ok &= hipMalloc((void **)&rx->d_total, sizeof(int64_t) * ns) == hipSuccess;
@@ -261,13 +276,28 @@ int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_de
     if (!ok) { rx_free(rx); delete rx; return PIRIP_ERR_NOMEM; }
     // (rows start zeroed: nothing reads bytes the caller or the decimator did not write, but a fresh buffer is not left to chance)
     ok = hipMemset(rx->d_rows, 0, rx->row_bytes * ns) == hipSuccess;
-    if (rx->d_raw) ok &= hipMemset(rx->d_raw, 0, rx->raw_row_bytes * ns) == hipSuccess;
+    if (rx->d_raw) ok &= hipMemset(rx->d_raw, 0, rx->raw_row_bytes * (size_t)nraw) == hipSuccess;
     ok &= hipMemset(rx->d_seg, 0, sizeof(SegDesc) * ns) == hipSuccess;
     ok &= rx_clear(rx, nullptr) == PIRIP_OK;
     ok &= hipDeviceSynchronize() == hipSuccess;
     if (!ok) { rx_free(rx); delete rx; return PIRIP_ERR_HIP; }
     *out = rx;
     return PIRIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *dec, int64_t block, pirip_hip_rx **out)
+{
+    return rx_create_impl(dem, ldpc, dec, nullptr, block, out);
+}
+
+int pirip_hip_rx_create_chan(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_chan *chan, int64_t block, pirip_hip_rx **out)
+{
+    if (!chan) { if (out) *out = nullptr; return PIRIP_ERR_BAD_ARG; }
+    return rx_create_impl(dem, ldpc, nullptr, chan, block, out);
 }
 
 int pirip_hip_rx_destroy(pirip_hip_rx *rx)
@@ -285,7 +315,7 @@ int64_t pirip_hip_rx_max_frames(const pirip_hip_rx *rx) { return rx ? rx->budget
 int pirip_hip_rx_input(pirip_hip_rx *rx, void **d_block, size_t *stride_bytes)
 {
     if (!rx || !d_block || !stride_bytes) return PIRIP_ERR_BAD_ARG;
-    if (rx->dec) { *d_block = rx->d_raw + rx->raw_pre; *stride_bytes = rx->raw_row_bytes; }
+    if (rx->dec || rx->chan) { *d_block = rx->d_raw + rx->raw_pre; *stride_bytes = rx->raw_row_bytes; }
     else { *d_block = rx->d_rows + (size_t)rx->c_pre * rx->bps; *stride_bytes = rx->row_bytes; }
     return PIRIP_OK;
 }
@@ -307,9 +337,10 @@ int pirip_hip_rx_push(pirip_hip_rx *rx, const void *d_in, size_t in_stride_bytes
     if (!demod_bind(rx->dem)) return PIRIP_ERR_NO_DEVICE;
     void *dst = nullptr; size_t dpitch = 0;
     (void)pirip_hip_rx_input(rx, &dst, &dpitch);
-    const size_t width = (size_t)rx->block * (rx->dec ? 2 : rx->bps);
-    if (in_stride_bytes < width && rx->nstreams > 1) return PIRIP_ERR_BAD_ARG;
-    if (hipMemcpy2DAsync(dst, dpitch, d_in, in_stride_bytes ? in_stride_bytes : width, width, (size_t)rx->nstreams, hipMemcpyDeviceToDevice,
+    const size_t width = (size_t)rx->block * (rx->dec || rx->chan ? 2 : rx->bps);
+    const int rows = rx->chan ? rx->nraw : rx->nstreams;
+    if (in_stride_bytes < width && rows > 1) return PIRIP_ERR_BAD_ARG;
+    if (hipMemcpy2DAsync(dst, dpitch, d_in, in_stride_bytes ? in_stride_bytes : width, width, (size_t)rows, hipMemcpyDeviceToDevice,
                          (hipStream_t)hip_stream) != hipSuccess) return PIRIP_ERR_HIP;
     return rx_run(rx, d_bits, bits_stride, d_rx_filt, filt_stride, d_status, d_payload, d_info, d_stats, stats_stride, d_nframes, (hipStream_t)hip_stream);
 }

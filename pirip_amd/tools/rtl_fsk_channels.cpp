@@ -1,0 +1,197 @@
+// rtl_fsk_channels -- K FSK channels out of ONE wideband u8 IQ capture: the channelizer (include/pirip_hip.h section H) as the front end
+// of the streaming receiver (section G), every channel demodulated -- or FSK_LDPC-decoded with --code -- on the device, block after block.
+//
+//   rtl_fsk_channels -s rtlFs -a modemFs -r Rs [-m M] [--mask S] [--fsk_lower Hz] [--fsk_upper Hz] [--code NAME|FILE]
+//                    -c OFF1,OFF2,... [-i FILE|-] -o PREFIX [-q]
+//
+// Channel k is centred at OFFk Hz from the capture's centre (integer, -rtlFs/2 < OFFk < rtlFs/2) and is what
+// `csdr shift_addition_cc (-OFFk/rtlFs) | fir_decimate_cc (rtlFs/modemFs)` would hand `rtl_fsk -a modemFs`: the same modem settings as
+// rtl_fsk's (P halved while it is above 10 and even, the estimator from Rs/2 to modemFs/2 unless given), and rtlFs must be a multiple of
+// modemFs. The capture is read in blocks of a quarter second (rounded down to a multiple of the decimation); a partial last block is not
+// processed. Output, one file per channel, PREFIX.<k>:
+//   uncoded        one byte per bit, as rtl_fsk writes to stdout
+//   --code NAME    the packed payload bytes of every frame whose CRC16 matches, as rtl_fsk --code
+#include <getopt.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include <hip/hip_runtime_api.h>
+
+#include "../../include/pirip_hip.h"
+
+static void usage()
+{
+    fprintf(stderr,
+            "rtl_fsk_channels (pirip_hip): -s rtlFs -a modemFs -r Rs [-m M] [--mask spacing] [--fsk_lower Hz] [--fsk_upper Hz]\n"
+            "        [--code NAME|FILE] -c off1,off2,... [-i <u8 IQ file|->] -o PREFIX [-q]\n"
+            "        writes PREFIX.<k> per channel: bits one per byte, or with --code the payload bytes of every CRC-ok frame\n");
+}
+
+static bool file_exists(const std::string &p) { struct stat st; return !p.empty() && stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
+
+// --code NAME: NAME as a file path, then $PIRIP_CODE_DIR/NAME.code, then <exe>/../data/NAME.code (as rtl_fsk resolves it)
+static std::string resolve_code(const std::string &name, const char *argv0)
+{
+    if (file_exists(name)) return name;
+    if (const char *d = getenv("PIRIP_CODE_DIR")) { const std::string p = std::string(d) + "/" + name + ".code"; if (file_exists(p)) return p; }
+    char exe[4096];
+    const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1);
+    std::string base = n > 0 ? std::string(exe, (size_t)n) : std::string(argv0);
+    const size_t s = base.rfind('/');
+    base = s == std::string::npos ? "." : base.substr(0, s);
+    const std::string p = base + "/../data/" + name + ".code";
+    return file_exists(p) ? p : std::string();
+}
+
+static bool parse_offsets(const char *s, std::vector<int32_t> &out)
+{
+    std::string all(s);
+    for (size_t pos = 0; pos <= all.size();) {
+        size_t end = all.find(',', pos);
+        if (end == std::string::npos) end = all.size();
+        const std::string tok = all.substr(pos, end - pos);
+        if (tok.empty()) return false;
+        char *e = nullptr;
+        const long v = strtol(tok.c_str(), &e, 10);
+        if (*e) return false;
+        out.push_back((int32_t)v);
+        pos = end + 1;
+    }
+    return !out.empty();
+}
+
+#define HIPOK(expr) do { if ((expr) != hipSuccess) { fprintf(stderr, "rtl_fsk_channels: HIP error at %s:%d\n", __FILE__, __LINE__); return 2; } } while (0)
+#define PIRIPOK(expr, what) do { const int rc_ = (expr); if (rc_ != PIRIP_OK) { fprintf(stderr, "rtl_fsk_channels: %s: %s\n", what, pirip_hip_strerror(rc_)); return 2; } } while (0)
+
+int main(int argc, char **argv)
+{
+    if (!pirip_hip_abi_check(PIRIP_HIP_ABI_VERSION, PIRIP_STATS_PER_FRAME, sizeof(pirip_stream_state))) {
+        fprintf(stderr, "%s: built against a different pirip_hip.h than %s\n", argv[0], pirip_hip_version()); return 2;
+    }
+    long rtlFs = 0, modemFs = 0, Rs = 0;
+    int M = 2, mask = 0, quiet = 0, fsk_lower = 0, fsk_upper = 0, user_lower = 0, user_upper = 0;
+    std::string in_name = "-", prefix, code;
+    std::vector<int32_t> offsets;
+    static struct option lopts[] = {{"code", required_argument, 0, 1000}, {"mask", required_argument, 0, 1001},
+                                    {"fsk_lower", required_argument, 0, 1002}, {"fsk_upper", required_argument, 0, 1003},
+                                    {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
+    int o, oi;
+    while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:qh", lopts, &oi)) != -1) {
+        switch (o) {
+        case 's': rtlFs = (long)atof(optarg); break;
+        case 'a': modemFs = (long)atof(optarg); break;
+        case 'r': Rs = (long)atof(optarg); break;
+        case 'm': M = atoi(optarg); break;
+        case 'c': if (!parse_offsets(optarg, offsets)) { fprintf(stderr, "rtl_fsk_channels: -c wants integer offsets in Hz, comma separated\n"); return 1; } break;
+        case 'i': in_name = optarg; break;
+        case 'o': prefix = optarg; break;
+        case 'q': quiet = 1; break;
+        case 1000: code = optarg; break;
+        case 1001: mask = atoi(optarg); break;
+        case 1002: fsk_lower = atoi(optarg); user_lower = 1; break;
+        case 1003: fsk_upper = atoi(optarg); user_upper = 1; break;
+        default: usage(); return 1;
+        }
+    }
+    if (rtlFs <= 0 || modemFs <= 0 || Rs <= 0 || offsets.empty() || prefix.empty() || (M != 2 && M != 4)) { usage(); return 1; }
+    if (rtlFs % modemFs) { fprintf(stderr, "rtl_fsk_channels: rtl rate %ld must be a multiple of the modem rate %ld\n", rtlFs, modemFs); return 1; }
+    if (modemFs % Rs) { fprintf(stderr, "rtl_fsk_channels: modem rate must be a multiple of the symbol rate\n"); return 1; }
+    const int D = (int)(rtlFs / modemFs), Fs = (int)modemFs, K = (int)offsets.size();
+    const int Ts = Fs / (int)Rs;
+    int P = Ts;
+    while (P > 10 && (P % 2) == 0) P /= 2;                       // rtl_fsk's oversample rule
+    if (P < 4) P = Ts;
+    if (!user_lower) fsk_lower = (int)Rs / 2;
+    if (!user_upper) fsk_upper = Fs / 2;
+    std::string code_path;
+    if (!code.empty() && (code_path = resolve_code(code, argv[0])).empty()) {
+        fprintf(stderr, "rtl_fsk_channels: no table for --code %s (format: pirip_amd/csrc/fsk_ldpc.hpp; $PIRIP_CODE_DIR or a file path)\n", code.c_str());
+        return 2;
+    }
+    FILE *fin = in_name == "-" ? stdin : fopen(in_name.c_str(), "rb");
+    if (!fin) { fprintf(stderr, "rtl_fsk_channels: can't open %s\n", in_name.c_str()); return 1; }
+    std::vector<FILE *> fout((size_t)K);
+    for (int k = 0; k < K; k++) {
+        const std::string name = prefix + "." + std::to_string(k);
+        if (!(fout[(size_t)k] = fopen(name.c_str(), "wb"))) { fprintf(stderr, "rtl_fsk_channels: can't open %s\n", name.c_str()); return 1; }
+    }
+
+    // handles: K channels of one capture -> K complex-float modem streams -> bits, or FSK_LDPC records
+    std::vector<int32_t> inputs((size_t)K, 0);
+    pirip_hip_chan *chan = nullptr;
+    pirip_hip_demod *dem = nullptr;
+    pirip_hip_ldpc *ldpc = nullptr;
+    pirip_hip_rx *rx = nullptr;
+    PIRIPOK(pirip_hip_chan_create((int)rtlFs, D, 0.05f, 0, 1, K, inputs.data(), offsets.data(), -1, &chan), "channelizer");
+    pirip_fsk_params prm{Fs, (int)Rs, M, P, PIRIP_FSK_DEFAULT_NSYM, fsk_lower, fsk_upper, mask ? 1 : 0, mask ? mask : 100, PIRIP_IN_CF32};
+    PIRIPOK(pirip_hip_create(&prm, K, -1, &dem), "demodulator");
+    pirip_ldpc_info li{};
+    if (!code_path.empty()) {
+        PIRIPOK(pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, K, -1, &ldpc), "--code");
+        pirip_hip_ldpc_get_info(ldpc, &li);
+    }
+    const int64_t block = (int64_t)(rtlFs / 4) / D * D;
+    PIRIPOK(pirip_hip_rx_create_chan(dem, ldpc, chan, block, &rx), "receiver");
+    pirip_fsk_info info;
+    pirip_hip_get_info(dem, &info);
+    if (!quiet)
+        fprintf(stderr, "rtl_fsk_channels: rtl rate %ld Fs %d Rs %ld M %d P %d decimation %d channels %d estimator %d..%d Hz%s%s\n", rtlFs, Fs, Rs,
+                M, P, D, K, fsk_lower, fsk_upper, ldpc ? " code " : "", ldpc ? li.name : "");
+
+    const int64_t R = pirip_hip_rx_max_frames(rx);
+    void *d_block = nullptr;
+    size_t in_stride = 0;
+    PIRIPOK(pirip_hip_rx_input(rx, &d_block, &in_stride), "receiver input");
+    uint8_t *d_bits = nullptr, *d_status = nullptr, *d_payload = nullptr;
+    int32_t *d_info = nullptr, *d_nfr = nullptr;
+    const size_t rows = (size_t)K * (size_t)R;
+    if (ldpc) {
+        HIPOK(hipMalloc((void **)&d_status, rows));
+        HIPOK(hipMalloc((void **)&d_payload, rows * (size_t)li.data_bytes));
+        HIPOK(hipMalloc((void **)&d_info, sizeof(int32_t) * rows * PIRIP_LDPC_INFO_PER_CALL));
+    } else {
+        HIPOK(hipMalloc((void **)&d_bits, rows * (size_t)info.Nbits));
+    }
+    HIPOK(hipMalloc((void **)&d_nfr, sizeof(int32_t) * (size_t)K));
+    std::vector<uint8_t> raw((size_t)block * 2), bits(ldpc ? 0 : rows * (size_t)info.Nbits), status(ldpc ? rows : 0),
+        payload(ldpc ? rows * (size_t)li.data_bytes : 0);
+    std::vector<int32_t> nfr((size_t)K);
+    long blocks = 0;
+    for (;;) {
+        const size_t got = fread(raw.data(), 2, (size_t)block, fin);
+        if (got < (size_t)block) break;
+        HIPOK(hipMemcpy(d_block, raw.data(), raw.size(), hipMemcpyHostToDevice));
+        if (ldpc) PIRIPOK(pirip_hip_rx_process(rx, nullptr, 0, nullptr, 0, d_status, d_payload, d_info, nullptr, 0, d_nfr, nullptr), "receiver");
+        else PIRIPOK(pirip_hip_rx_process(rx, d_bits, (size_t)R * info.Nbits, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, d_nfr, nullptr), "receiver");
+        HIPOK(hipMemcpy(nfr.data(), d_nfr, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost));
+        if (ldpc) {
+            HIPOK(hipMemcpy(status.data(), d_status, rows, hipMemcpyDeviceToHost));
+            HIPOK(hipMemcpy(payload.data(), d_payload, rows * (size_t)li.data_bytes, hipMemcpyDeviceToHost));
+        } else {
+            HIPOK(hipMemcpy(bits.data(), d_bits, bits.size(), hipMemcpyDeviceToHost));
+        }
+        for (int k = 0; k < K; k++)
+            for (int32_t f = 0; f < nfr[(size_t)k]; f++) {
+                const size_t row = (size_t)k * (size_t)R + (size_t)f;
+                if (!ldpc) fwrite(&bits[row * (size_t)info.Nbits], 1, (size_t)info.Nbits, fout[(size_t)k]);
+                else if (status[row] & PIRIP_RX_BITS) fwrite(&payload[row * (size_t)li.data_bytes], 1, (size_t)li.data_bytes, fout[(size_t)k]);
+            }
+        blocks++;
+    }
+    if (!quiet) fprintf(stderr, "rtl_fsk_channels: %ld blocks of %lld samples\n", blocks, (long long)block);
+    for (FILE *f : fout) fclose(f);
+    if (fin != stdin) fclose(fin);
+    pirip_hip_rx_destroy(rx);
+    if (ldpc) pirip_hip_ldpc_destroy(ldpc);
+    pirip_hip_destroy(dem);
+    pirip_hip_chan_destroy(chan);
+    void *ptrs[] = {d_bits, d_status, d_payload, d_info, d_nfr};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+    return 0;
+}
