@@ -335,6 +335,10 @@ int pirip_hip_ldpc_create(const char *code_path, int M, int Nsym, int nstreams, 
 int pirip_hip_ldpc_destroy(pirip_hip_ldpc *h);
 int pirip_hip_ldpc_get_info(const pirip_hip_ldpc *h, pirip_ldpc_info *info);
 int pirip_hip_ldpc_reset(pirip_hip_ldpc *h, void *hip_stream);
+/* The soft bits receiver s carries into its next call (synchronous copy): the last 2 * bits_per_frame bit LLRs it was handed, oldest first,
+ * as IEEE binary16 -- written by the LLR stage or by the demodulator's fused hand-over alike. A checking aid: the fused path keeps no
+ * other copy of them. */
+int pirip_hip_ldpc_get_llr_history(pirip_hip_ldpc *h, int s, uint16_t *host_llr);
 /* Stream s consumes `ncalls` demodulator frames of soft decisions d_rx_filt + s*filt_stride (floats; each frame is
  * M*Nsym magnitudes in fsk_demod_sd() layout [m][sym] = pirip_hip_demod_batch's d_rx_filt); d_ncalls[s] (or NULL = all)
  * says how many of them are valid (d_nframes of the demodulator): the receiver advances by exactly that many calls -- the

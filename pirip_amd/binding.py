@@ -155,8 +155,9 @@ def selftest_sqrt():
 
 
 def selftest_div():
-    """Mismatches of the fused hand-over's x / 3 and x / 50 (pirip_hip_selftest_div) against the device's IEEE quotient over x = 0 and
-    every float in [2^-125, FLT_MAX]: (count for / 50 << 32) | count for / 3."""
+    """Mismatches of the fused hand-over's x / 3 and x / 50 (pirip_hip_selftest_div) against the device's IEEE quotient over their measured
+    domains -- x / 3: every finite x >= 0, denormals included; x / 50: x = 0 and every float in [2^-125, FLT_MAX]:
+    (count for / 50 << 32) | count for / 3."""
     L = lib()
     m = C.c_uint64(0)
     L.pirip_hip_selftest_div.argtypes = [C.POINTER(C.c_uint64)]
@@ -443,6 +444,14 @@ class HipLdpc:
 
     def reset(self, stream=0):
         _chk(self.L.pirip_hip_ldpc_reset(self.h, stream), "pirip_hip_ldpc_reset")
+
+    def llr_history(self, s=0):
+        """The 2 * bits_per_frame binary16 soft bits receiver s carries into its next call, oldest first (pirip_hip_ldpc_get_llr_history)."""
+        import numpy as np
+        out = np.zeros(2 * self.info.bits_per_frame, dtype=np.float16)
+        self.L.pirip_hip_ldpc_get_llr_history.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _chk(self.L.pirip_hip_ldpc_get_llr_history(self.h, s, out.ctypes.data), "pirip_hip_ldpc_get_llr_history")
+        return out
 
     def rx_batch(self, d_rx_filt, filt_stride, d_ncalls, ncalls, d_status, d_payload, d_info, stream=0):
         _chk(self.L.pirip_hip_ldpc_rx_batch(self.h, d_rx_filt, filt_stride, d_ncalls, ncalls, d_status, d_payload, d_info, stream),

@@ -163,6 +163,7 @@ __device__ __forceinline__ float llr_frame_gain_quick(int llr_map, float sig, fl
 __device__ __forceinline__ unsigned sqrt_key(float x) { return __builtin_bit_cast(unsigned, x) - 1u; }
 __device__ __forceinline__ unsigned fbits(float x) { return __builtin_bit_cast(unsigned, x); }
 constexpr unsigned kSqrtLo = 0x0f800000u;                           // 2^-96
+constexpr unsigned kQuickHi = 0x7c000000u;                          // 2^121: the fused hand-over's quick path (its frame sums stay finite)
 __device__ __forceinline__ unsigned umin2(unsigned a, unsigned b) { return a < b ? a : b; }
 __device__ __forceinline__ unsigned umin3(unsigned a, unsigned b, unsigned c)
 {
@@ -1474,14 +1475,16 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                 // them from rx_filt (ldpc_kernels.hip: llr_tile_kernel; the checker (ldpc_oracle.c): oracle_ldpc_llr): per-symbol terms on
                 // every lane, the frame's two sums by the wave reduction, ln I0 by table + linear interpolation, 4-FSK bits by max-log.
                 // Square roots and the divisions by constants are IEEE operations: any correctly rounded form gives the same words. When every
-                // |f|^2 of the frame is zero or >= 2^-96 (one wave-uniform test: always, short of denormal inputs) the roots are the estimator's
-                // rsq form (6 instructions instead of sqrtf's 20) and x / 3, x / Nsym are x * (1/c) corrected once (3 instead of 11: exact
-                // for every x >= 2^-125, tools/div_const_check.c; pirip_hip_selftest_div repeats it on the device).
+                // |f|^2 of the frame is zero or in [2^-96, 2^121] (one wave-uniform test: always, short of denormal or huge cf32 inputs) the roots
+                // are the estimator's rsq form (6 instructions instead of sqrtf's 20) and x / 3, x / Nsym are x * (1/c) corrected once (3 instead
+                // of 11: the IEEE quotient for x = 0 and every finite x >= 2^-125, tools/div_const_check.c; pirip_hip_selftest_div repeats it on
+                // the device). The upper bound keeps every sum finite (a symbol's 4 tones: <= 2^123, a frame's 50 terms: < 2^127): the corrected
+                // product turns +inf into NaN where the quotient is +inf.
                 float mag[M], sum2 = 0.f, mx2 = 0.f;
-                unsigned kmin = 0xffffffffu;
+                unsigned kmin = 0xffffffffu, kmax = 0u;
 #pragma unroll
-                for (int m = 0; m < M; m++) kmin = umin2(kmin, sqrt_key(tmax[m]));
-                const bool quick = __all(!act || kmin >= 0x0f800000u - 1u);
+                for (int m = 0; m < M; m++) { kmin = umin2(kmin, sqrt_key(tmax[m])); kmax = kmax > fbits(tmax[m]) ? kmax : fbits(tmax[m]); }
+                const bool quick = __all(!act || (kmin >= 0x0f800000u - 1u && kmax <= kQuickHi));
                 float ssig, snse;
                 // (the receiver's defined summation order IS this kernel's wave reduction: ldpc_kernels.hip wave_order_sum)
                 if (quick) {
@@ -1685,8 +1688,7 @@ hipError_t selftest_div(unsigned long long *mismatches)
     if (e != hipSuccess) return e;
     e = hipMemset(d, 0, 2 * sizeof(*d));
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(div_selftest_kernel<3>, dim3(4096), dim3(256), 0, 0, d, 0u, 0u);                          // x = 0
-        hipLaunchKernelGGL(div_selftest_kernel<3>, dim3(4096), dim3(256), 0, 0, d, 0x01000000u, 0x7f7fffffu);        // [2^-125, FLT_MAX]
+        hipLaunchKernelGGL(div_selftest_kernel<3>, dim3(4096), dim3(256), 0, 0, d, 0u, 0x7f7fffffu);                 // every finite x >= 0
         hipLaunchKernelGGL(div_selftest_kernel<50>, dim3(4096), dim3(256), 0, 0, d + 1, 0u, 0u);
         hipLaunchKernelGGL(div_selftest_kernel<50>, dim3(4096), dim3(256), 0, 0, d + 1, 0x01000000u, 0x7f7fffffu);
         unsigned long long h[2] = {0, 0};

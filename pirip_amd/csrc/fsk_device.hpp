@@ -73,8 +73,12 @@ __device__ __forceinline__ float logbesseli0_upstream(float x)
     if (x >= 20.0f) { c2 = 0.0f; c1 = 0.9867f; c0 = -2.2053f; }
     return (((c2 * x) * x) + (c1 * x)) + c0;
 }
-// x / C correctly rounded for x = 0 or x >= 2^-125 (C = 3, 50: compared with the IEEE quotient for every such float on the CPU,
-// tools/div_const_check.c, and on the device, pirip_hip_selftest_div): q = x * RN(1/C), one residual correction.
+// x / C correctly rounded (q = x * RN(1/C), one residual correction) on a measured domain -- compared with the IEEE quotient for every such
+// float on the CPU (tools/div_const_check.c) and on the device (pirip_hip_selftest_div):
+//   C = 3:  every finite x >= 0, the denormals included;
+//   C = 50: x = 0 and every finite x >= 2^-125 (167 772 denormals and floats below 2^-125 round the other way).
+// Not in either domain: +inf (the residual fma is inf - inf: NaN, where the quotient is +inf) and NaN (NaN either way). Callers guard both
+// ends with a wave-uniform range test.
 template <int C>
 __device__ __forceinline__ float div_rn_const(float x)
 {
@@ -168,7 +172,8 @@ inline hipError_t launch_demod_kind(int kind, const DemodArgs &a, int nstreams, 
 const char *demod_wave_source_hash();                              // Makefile: sha256 prefix of the gfx950 code object in fsk_demod_wave.o
 // exhaustive device-side check of the wave kernel's correctly rounded square roots (x = 0 and every float in [2^-96, FLT_MAX])
 hipError_t selftest_sqrt(unsigned long long *mismatches);
-// the fused FSK_LDPC hand-over's x / 3 and x / 50 (x * RN(1/c) corrected once) against the IEEE quotient: x = 0 and every float in [2^-125, FLT_MAX]
+// the fused FSK_LDPC hand-over's x / 3 and x / 50 (x * RN(1/c) corrected once) against the IEEE quotient on their domains (div_rn_const):
+// x / 3 for every finite x >= 0, x / 50 for x = 0 and every float in [2^-125, FLT_MAX]
 hipError_t selftest_div(unsigned long long *mismatches);       // (count for / 50, saturated) << 32 | count for / 3
 
 }  // namespace pirip

@@ -205,7 +205,8 @@ __global__ __launch_bounds__(kLlrThreads) void llr_tile_kernel(LdpcDev c, const 
 #pragma unroll
             for (int m = 0; m < 4; m++) if (m < c.M) { const float p = vreg[q][m] * vreg[q][m]; sum = sum + p; mx = p > mx ? p : mx; }
             const bool on = cl < ncl && lane < c.Nsym;                                     // (vreg is zero elsewhere, the terms too)
-            // (x / 3 as x * RN(1/3) corrected once: the IEEE quotient for every finite x >= 0 -- fsk_device.hpp: div_rn_const; wave-uniform test for the rest)
+            // (x / 3 as x * RN(1/3) corrected once: the IEEE quotient for every finite x >= 0, denormals included -- fsk_device.hpp: div_rn_const,
+            //  measured by tools/div_const_check.c and pirip_hip_selftest_div; +inf would give NaN: the wave-uniform test sends the top end to the quotient)
             const float oth = sum - mx;
             float mean_oth;
             if (c.M == 4 && __all(!(oth > 3.0e38f))) mean_oth = div_rn_const<3>(oth);
@@ -1527,6 +1528,15 @@ int pirip_hip_ldpc_get_info(const pirip_hip_ldpc *h, pirip_ldpc_info *info)
     info->n = h->code.n; info->k = h->code.k; info->bits_per_frame = h->code.bits_per_frame(); info->data_bytes = h->code.data_bytes();
     info->nbits_per_call = h->dev.Nbits; info->max_iter = h->code.max_iter; info->nstreams = h->nstreams;
     std::strncpy(info->name, h->code.name.c_str(), sizeof(info->name) - 1);
+    return PIRIP_OK;
+}
+
+int pirip_hip_ldpc_get_llr_history(pirip_hip_ldpc *h, int s, uint16_t *host_llr)
+{
+    if (!h || !host_llr || s < 0 || s >= h->nstreams) return PIRIP_ERR_BAD_ARG;
+    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    const size_t n = 2 * (size_t)h->dev.bpf;
+    LCHK(hipMemcpy(host_llr, h->d_llr_hist + (size_t)s * n, sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
     return PIRIP_OK;
 }
 

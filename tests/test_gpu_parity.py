@@ -117,7 +117,8 @@ def test_estimator_sqrt_is_correctly_rounded_on_this_device(built_lib):
 
 def test_hand_over_constant_divisions_are_the_ieee_quotients_on_this_device(built_lib):
     """The fused FSK_LDPC hand-over divides the frame's sums by Nsym = 50 and by M - 1 = 3 as x * RN(1/c) + one residual correction
-    (3 instructions instead of the quotient's 11): equal to x / c for x = 0 and every float in [2^-125, FLT_MAX], counted on the device."""
+    (3 instructions instead of the quotient's 11): equal to x / c on its measured domain, counted on the device -- x / 3 for every finite
+    x >= 0 (denormals included), x / 50 for x = 0 and every float in [2^-125, FLT_MAX]."""
     import pirip_amd
     m = pirip_amd.selftest_div()
     assert (m & 0xffffffff, m >> 32) == (0, 0), "mismatches (x / 3, x / 50)"
