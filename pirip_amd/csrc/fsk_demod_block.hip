@@ -35,6 +35,7 @@
 #include <type_traits>
 
 #include "../../include/pirip_hip.h"
+#include "demod_simd.hpp"
 #include "fsk_device.hpp"
 
 namespace pirip {
@@ -56,33 +57,9 @@ static_assert(NSTEP * STEP == NMEM && CSTEPS * NT <= NSTEP && CEXTRA >= 0 && CEX
 static_assert(NINT + P - 1 <= NSTEP, "the last window ends inside the memory");
 constexpr int XA_CF = 16 * 272;         // exchange array, complex floats (34 816 bytes)
 
-typedef float v2f __attribute__((ext_vector_type(2)));
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
 typedef u32x4 u32x4_a2 __attribute__((aligned(2)));      // 16 bytes at the alignment of an (I, Q) byte pair
 
-// ---- packed-f32 complex helpers (as in fsk_demod_wave.hip: kiss_fft's arithmetic, every product and sum rounded once) ----------
-__device__ __forceinline__ v2f cmul_x(v2f a, v2f t)
-{
-    v2f p2, r;
-    asm("v_pk_mul_f32 %0, %2, %3 op_sel_hi:[0,1]\n\t"
-        "v_pk_mul_f32 %1, %2, %3 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-        "v_pk_add_f32 %0, %0, %1 neg_lo:[0,1]"
-        : "=&v"(r), "=&v"(p2) : "v"(a), "v"(t));
-    return r;
-}
-__device__ __forceinline__ v2f add_rot(v2f a, v2f b) { v2f r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ v2f sub_rot(v2f a, v2f b) { v2f r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r; }
-__device__ __forceinline__ void bfly4(v2f &f0, v2f &f1, v2f &f2, v2f &f3)
-{
-    const v2f s5 = f0 - f2;
-    f0 = f0 + f2;
-    const v2f s3 = f1 + f3;
-    const v2f s4 = f1 - f3;
-    f2 = f0 - s3;
-    f0 = f0 + s3;
-    f1 = add_rot(s5, s4);
-    f3 = sub_rot(s5, s4);
-}
 // two radix-4 stages over 16 register values X[c + 4 dd]: first over dd for every c (twiddles t1[0..2], the same for every c; nullptr:
 // trivial), results at X[c + 4 k]; then over c for every k with twiddles t2[3 k + 0..2], results k' at X[k' + 4 k]
 __device__ __forceinline__ void radix16(v2f *X, const v2f *t1, const v2f *t2, bool first_trivial)
@@ -101,55 +78,6 @@ __device__ __forceinline__ void radix16(v2f *X, const v2f *t1, const v2f *t2, bo
         bfly4(f0, f1, f2, f3);
         X[4 * k] = f0; X[4 * k + 1] = f1; X[4 * k + 2] = f2; X[4 * k + 3] = f3;
     }
-}
-__device__ __forceinline__ v2f mix_conj(v2f x, v2f ph)
-{
-    v2f r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
-        : "=&v"(r) : "v"(x), "v"(ph));
-    return r;
-}
-// acc + x * conj(ph): the down-conversion folded into the running sum, 2 packed fma (round 5)
-__device__ __forceinline__ v2f mix_conj_acc(v2f x, v2f ph, v2f acc)
-{
-    v2f r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
-        : "=&v"(r) : "v"(x), "v"(ph), "v"(acc));
-    return r;
-}
-__device__ __forceinline__ v2f rot_step(v2f ph, v2f d)
-{
-    v2f r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
-        : "=&v"(r) : "v"(ph), "v"(d));
-    return r;
-}
-// correctly rounded sqrt for x = 0 or x >= 2^-96 (fsk_demod_wave.hip: measured on the device over every float; pirip_hip_selftest_sqrt)
-// NZ: every value of the batch >= 2^-96 (none zero): the clamp is a no-op there and is left out
-template <bool NZ = false>
-__device__ __forceinline__ float sqrt_rn_fast(float x)
-{
-    float q = __builtin_amdgcn_rsqf(x);
-    if (!NZ) asm("v_min_f32 %0, %0, %1" : "+v"(q) : "v"(0x1p60f));
-    const float y = x * q, h = 0.5f * q;
-    return __builtin_fmaf(__builtin_fmaf(-y, y, x), h, y);
-}
-template <int FMT>
-__device__ __forceinline__ float cvt_u8(float b)
-{
-    if (FMT == PIRIP_IN_CU8_FSKDEMOD) return __builtin_fmaf(b, 0.0078125f, -0.9921875f);
-    return __builtin_fmaf(b, -1.187418e-07f, __builtin_fmaf(b, 0.007843255996704102f, -1.0f));
-}
-// the same maps on an (I, Q) pair of byte values: one v_pk_fma_f32 per fma (round 5, as in fsk_demod_wave.hip)
-template <int FMT>
-__device__ __forceinline__ v2f cvt_u8_pair(v2f b)
-{
-    if (FMT == PIRIP_IN_CU8_FSKDEMOD) return __builtin_elementwise_fma(b, v2f{0.0078125f, 0.0078125f}, v2f{-0.9921875f, -0.9921875f});
-    return __builtin_elementwise_fma(b, v2f{-1.187418e-07f, -1.187418e-07f},
-                                     __builtin_elementwise_fma(b, v2f{0.007843255996704102f, 0.007843255996704102f}, v2f{-1.0f, -1.0f}));
 }
 template <int FMT>
 __device__ __forceinline__ v2f cvt_sample_hi(uint32_t v)  // high 16 bits: (I, Q) bytes
@@ -187,32 +115,13 @@ __device__ __forceinline__ PIRIP_GLOBAL T *gl(PIRIP_GLOBAL T *p)     // a global
 }
 // element idx of a global array. (Measured, interleaved A/B on one box: forming the byte offset in 32 bits -- scalar base + 32-bit lane
 // offset for EVERY access of the kernel -- ran 13 % slower than plain indexing, 205 against 235 G samples/s, with fewer instructions; the
-// row-base form below is used where the row is wave-uniform and kept because it measured faster there. -DPIRIP_BLOCK_LDG32 selects it.)
+// row-base form below is used where the row is wave-uniform and kept because it measured faster there: DESIGN_NOTES.md 4.2b.)
 template <class T>
-__device__ __forceinline__ T ldg(const PIRIP_GLOBAL T *base, unsigned idx)
-{
-#ifdef PIRIP_BLOCK_LDG32
-    return *(const PIRIP_GLOBAL T *)((const PIRIP_GLOBAL char *)base + idx * (unsigned)sizeof(T));
-#else
-    return base[(int)idx];
-#endif
-}
+__device__ __forceinline__ T ldg(const PIRIP_GLOBAL T *base, unsigned idx) { return base[(int)idx]; }
 // the same with a wave-uniform row base: base and row advance in scalar registers, the lane's own offset is the only vector operand
 template <class T>
 __device__ __forceinline__ T ldrow(const PIRIP_GLOBAL T *row_base, unsigned lane_elem) { return *(const PIRIP_GLOBAL T *)((const PIRIP_GLOBAL char *)row_base + lane_elem * (unsigned)sizeof(T)); }
 
-#define PIRIP_DPP_F(old, src, ctrl, rmask) \
-    __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (float)(old)), __builtin_bit_cast(int, (float)(src)), ctrl, rmask, 0xf, false))
-__device__ __forceinline__ float wave_sum(float v)
-{
-    v += PIRIP_DPP_F(0.f, v, 0x111, 0xf);
-    v += PIRIP_DPP_F(0.f, v, 0x112, 0xf);
-    v += PIRIP_DPP_F(0.f, v, 0x114, 0xf);
-    v += PIRIP_DPP_F(0.f, v, 0x118, 0xf);
-    v += PIRIP_DPP_F(0.f, v, 0x142, 0xa);
-    v += PIRIP_DPP_F(0.f, v, 0x143, 0xc);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
 // Workgroup barrier that orders LDS traffic only: __syncthreads() also waits for every global load in flight (vmcnt(0)), which would
 // put the latency of the twiddle loads issued in front of an exchange back on the critical path.
 __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -257,25 +166,11 @@ __device__ __forceinline__ void block_argmax(float &v, int &idx, float *red, int
 
 }  // namespace
 
-// timing experiments only (results wrong): fewer FFTs / no correlator threads -- what a phase costs is the time its removal saves
-#ifndef PIRIP_BLOCK_T_NFFT
-#define PIRIP_BLOCK_T_NFFT NFFT
-#endif
-#ifndef PIRIP_BLOCK_T_NCORR
-#define PIRIP_BLOCK_T_NCORR NT
-#endif
-#ifndef PIRIP_BLOCK_PREFETCH
-#define PIRIP_BLOCK_PREFETCH 1
-#endif
-#ifndef PIRIP_BLOCK_WPB2
-#define PIRIP_BLOCK_WPB2 3     // workgroups per CU the 2-FSK instances are compiled for (36 KB of LDS each, <= 168 VGPR)
-#endif
-#ifndef PIRIP_BLOCK_WPB4
-#define PIRIP_BLOCK_WPB4 3     // ... and the 4-FSK instances (51 KB of LDS; tones two at a time in the correlator). Round 5: with the down-conversion
-                               // folded into the running sums the peak instances need 156 VGPR (were 216) and run at three as well
-#endif
+// Compiled for three workgroups per CU: the 2-FSK instances hold 36 KB of LDS each and <= 168 VGPR, the 4-FSK ones 51 KB (tones two at a
+// time in the correlator). Round 5: with the down-conversion folded into the running sums the 4-FSK peak instances need 156 VGPR (were 216)
+// and run at three as well.
 template <int M, int FMT, bool MASK>
-__global__ __launch_bounds__(NT, M == 2 ? PIRIP_BLOCK_WPB2 : PIRIP_BLOCK_WPB4) void fsk_demod_block_kernel(DemodArgs a_by_value)
+__global__ __launch_bounds__(NT, 3) void fsk_demod_block_kernel(DemodArgs a_by_value)
 {
     // The argument block is copied to LDS once; every phase re-derives what it needs through a pointer that is made opaque per phase, so
     // nothing of the block stays live in registers across the frame loop (by value it cost the general kernel 223 SGPR spills).
@@ -292,9 +187,7 @@ __global__ __launch_bounds__(NT, M == 2 ? PIRIP_BLOCK_WPB2 : PIRIP_BLOCK_WPB4) v
     float2 (*s_step)[NSTEP] = (float2 (*)[NSTEP])s_xa;
     __shared__ __attribute__((aligned(16))) uint16_t s_tail[HIST + 4];      // last frame's raw tail (I, Q bytes per sample)
     __shared__ float s_red[16];
-#if PIRIP_BLOCK_PREFETCH
     __shared__ uint32_t s_dump[kWave];      // where the line-touching prefetch of the next frame lands (a wave writes lane-linear: 64 dwords)
-#endif
     __shared__ uint32_t s_prev[2 * kMaxTones + 1];   // last frame's phase steps [M], oscillator-table rows [M], nin: read once per frame by the correlator
     __shared__ float s_sc[6];               // SNRest, snr_est, EbNodB, v_est, rx_sig_pow, rx_nse_pow: stream state that only wave 0 touches, on observable frames
     __shared__ float s_fest[kMaxTones];     // the latest frame's tone estimates (thread 0 writes them, and reads them back when the state is saved)
@@ -372,7 +265,7 @@ __global__ __launch_bounds__(NT, M == 2 ? PIRIP_BLOCK_WPB2 : PIRIP_BLOCK_WPB4) v
             //  prefetches the kernel held 252 VGPR = two workgroups per CU and ran 193 G samples/s (2-FSK); at <= 168 VGPR a third
             //  workgroup fits and its waves hide the same latencies: 228 G)
 #pragma unroll 1
-            for (int j = 0; j < PIRIP_BLOCK_T_NFFT; j++) {
+            for (int j = 0; j < NFFT; j++) {
                 // (an opaque copy of the thread index per FFT: the twiddle loads below are loop-invariant, and hoisted out of this
                 //  loop they are 54 more live registers for the whole frame)
                 int tq = tid; asm volatile("" : "+v"(tq));
@@ -447,14 +340,14 @@ __global__ __launch_bounds__(NT, M == 2 ? PIRIP_BLOCK_WPB2 : PIRIP_BLOCK_WPB4) v
                 }
                 if (__all(kmin >= 0x0f800000u)) {                                   // every |X|^2 >= 2^-96: roots without the zero guard
 #pragma unroll
-                    for (int r = 0; r < 16; r++) mg[r] = sqrt_rn_fast<true>(mg[r]);
+                    for (int r = 0; r < 16; r++) mg[r] = sqrt_rn_normal<true, true>(mg[r]);
                 } else {
                     kmin = 0xffffffffu;
 #pragma unroll
                     for (int r = 0; r < 16; r++) { const unsigned key = __builtin_bit_cast(unsigned, mg[r]) - 1u; kmin = key < kmin ? key : kmin; }
                     if (__all(kmin >= 0x0f800000u - 1u)) {                          // zeros among them (a silent input)
 #pragma unroll
-                        for (int r = 0; r < 16; r++) mg[r] = sqrt_rn_fast(mg[r]);
+                        for (int r = 0; r < 16; r++) mg[r] = sqrt_rn_normal<true>(mg[r]);
                     } else {
 #pragma unroll
                         for (int r = 0; r < 16; r++) mg[r] = sqrtf(mg[r]);
@@ -531,7 +424,7 @@ __global__ __launch_bounds__(NT, M == 2 ? PIRIP_BLOCK_WPB2 : PIRIP_BLOCK_WPB4) v
         }
         // ================= a-6: down-convert, sums over the 16-sample window steps ========================================
         __syncthreads();                                   // (the linear spectrum in s_xa has been read)
-        if (tid < PIRIP_BLOCK_T_NCORR) {
+        if (tid < NT) {
             PIRIP_ARGS();
             const PIRIP_GLOBAL v2f *__restrict__ g_tw = gl((const v2f *)a.t.tw);
             const PIRIP_GLOBAL v2f *__restrict__ g_step = gl((const v2f *)a.t.osc_step), *__restrict__ g_drift = gl((const v2f *)a.t.osc_drift);
@@ -642,7 +535,6 @@ __global__ __launch_bounds__(NT, M == 2 ? PIRIP_BLOCK_WPB2 : PIRIP_BLOCK_WPB4) v
             }
         }
         __syncthreads();
-#if PIRIP_BLOCK_PREFETCH
         // (issued right after the FFTs instead, a whole correlator pass earlier, it measured the same)
         // touch the next frame's cache lines (one dword of each 128-byte line, landing in a dump row of LDS nobody reads): they are on their
         // way to L2 while the window sums, the timing estimate and the decisions run, instead of being fetched from HBM by the next FFT
@@ -653,7 +545,6 @@ __global__ __launch_bounds__(NT, M == 2 ? PIRIP_BLOCK_WPB2 : PIRIP_BLOCK_WPB4) v
                 __builtin_amdgcn_global_load_lds((const PIRIP_GLOBAL void *)((const PIRIP_GLOBAL char *)gin + 2u * (unsigned)nin + off),
                                                  (__attribute__((address_space(3))) void *)s_dump, 4, 0, 0);
         }
-#endif
         // the frame's last HIST raw samples are the next frame's old positions
         for (int i = tid; i < HIST; i += NT) s_tail[i] = ldg(gin, (unsigned)(nin - HIST + i));
         if (tid == 0) {                                    // (the correlator's reads are behind the barrier above; the next ones are a frame away)

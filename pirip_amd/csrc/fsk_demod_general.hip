@@ -30,6 +30,7 @@
 #include <cmath>
 
 #include "../../include/pirip_hip.h"
+#include "demod_simd.hpp"
 #include "fsk_device.hpp"
 
 namespace pirip {
@@ -37,53 +38,16 @@ namespace pirip {
 namespace {
 
 constexpr int kWave = 64;
-#ifndef PIRIP_GEN_U
-#define PIRIP_GEN_U 2
-#endif
-constexpr int kU = PIRIP_GEN_U;   // independent items per thread per pass in the batched loops (reads first, then arithmetic)
+constexpr int kU = 2;   // independent items per thread per pass in the batched loops (reads first, then arithmetic)
 
-// Wave reductions on the VALU's DPP paths (row shifts, then row broadcasts; lane 63 ends up with the result, one v_readlane
-// hands it to every lane) -- no LDS round trips (__shfl_xor is ds_bpermute: six of them and their waits per reduction).
-#define PIRIP_GEN_DPP(op) \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-        "s_nop 1\n\tv_readlane_b32 %1, %0, 63"
-__device__ __forceinline__ float wave_sum(float v)
+// wave_sum (demod_simd.hpp) as one asm statement: the same additions in the same order, but v_add_f32_dpp on the partial sum itself
+// (lanes whose DPP source is outside the row / masked keep their own partial sum: the row_shr steps build inclusive prefix sums inside
+// each row of 16, the broadcasts add the preceding rows' totals -- lane 63 holds the wave total)
+__device__ __forceinline__ float wave_sum_asm(float v)
 {
-    // lanes whose DPP source is outside the row / masked keep their own partial sum: the row_shr steps build inclusive
-    // prefix sums inside each row of 16, the broadcasts add the preceding rows' totals -- lane 63 holds the wave total
     int tot;
-    asm(PIRIP_GEN_DPP("v_add_f32_dpp") : "+v"(v), "=s"(tot));
+    asm(PIRIP_DPP_REDUCE("v_add_f32_dpp") : "+v"(v), "=s"(tot));
     return __builtin_bit_cast(float, tot);
-}
-
-// Ordering point for LDS traffic inside ONE wave (the streams of a workgroup never exchange data, and they
-// run different numbers of frames, so a workgroup barrier inside the frame loop would be wrong): LDS
-// instructions of a wave execute in order, only the compiler has to be kept from moving accesses across.
-__device__ __forceinline__ void wave_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// arg-max with codec2's tie rule (first maximum wins, only values > 0 count)
-// (v >= 0 and never NaN here: a candidate only ever replaces "best" by being larger than it, and best starts at 0 -- so the
-//  maximum is six v_max_f32 with a DPP source, the winner the smallest index among the lanes that hold it)
-__device__ __forceinline__ void wave_argmax(float &v, int &idx)
-{
-    float red = v;
-    int smax, smin;
-    asm(PIRIP_GEN_DPP("v_max_f32_dpp") : "+v"(red), "=s"(smax));
-    int cand = (__builtin_bit_cast(int, v) == smax) ? idx : 0x7fffffff;
-    asm(PIRIP_GEN_DPP("v_min_i32_dpp") : "+v"(cand), "=s"(smin));
-    v = __builtin_bit_cast(float, smax);
-    idx = smin;
 }
 
 // LDS, per stream (= per workgroup; the read-only tables -- twiddles, Hann, digit-reversal -- are read from
@@ -232,7 +196,7 @@ constexpr int kMaxWaves = 16;
 constexpr int kRedBytes = 2 * kMaxWaves * 4;
 __device__ __forceinline__ float block_sum(float v, float *red, int tid, int NT)
 {
-    v = wave_sum(v);
+    v = wave_sum_asm(v);
     if (NT == kWave) return v;
     __syncthreads();
     if ((tid & (kWave - 1)) == 0) red[tid >> 6] = v;

@@ -42,6 +42,7 @@
 #include <cstdlib>
 
 #include "../../include/pirip_hip.h"
+#include "demod_simd.hpp"
 #include "fsk_device.hpp"
 
 namespace pirip {
@@ -51,17 +52,6 @@ namespace {
 constexpr int kWave = 64;
 
 struct cf { float x, y; };
-typedef float v2f __attribute__((ext_vector_type(2)));
-
-// Ordering point for LDS traffic inside ONE wavefront: LDS instructions of a wave execute in issue order, so only the
-// compiler has to be kept from reordering (see fsk_demod_general.hip for why __syncthreads() is the wrong tool here).
-__device__ __forceinline__ void wave_lds_sync()
-{
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    asm volatile("" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
 
 // b + (a of lane + 1): one VALU instruction with a DPP source (hipcc does not fold wave_shl moves into the consumer)
 __device__ __forceinline__ float add_lane_up(float a, float b)
@@ -71,9 +61,6 @@ __device__ __forceinline__ float add_lane_up(float a, float b)
     return r;
 }
 
-#define PIRIP_DPP_F(old, src, ctrl, rmask) \
-    __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(__builtin_bit_cast(int, (float)(old)), __builtin_bit_cast(int, (float)(src)), ctrl, rmask, 0xf, false))
-#define PIRIP_DPP_I(old, src, ctrl, rmask) __builtin_amdgcn_update_dpp((int)(old), (int)(src), ctrl, rmask, 0xf, false)
 // value of lane + 1 (lane 63 reads 0: bound_ctrl, so the instruction has no tied "old" operand and hipcc can fold it
 // into the consuming VALU op as a DPP source instead of v_mov + v_mov_dpp)
 __device__ __forceinline__ float lane_up(float v)
@@ -81,76 +68,11 @@ __device__ __forceinline__ float lane_up(float v)
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
 }
 
-__device__ __forceinline__ float wsum(float v)
-{
-    v += PIRIP_DPP_F(0.f, v, 0x111, 0xf);   // row_shr:1
-    v += PIRIP_DPP_F(0.f, v, 0x112, 0xf);   // row_shr:2
-    v += PIRIP_DPP_F(0.f, v, 0x114, 0xf);   // row_shr:4
-    v += PIRIP_DPP_F(0.f, v, 0x118, 0xf);   // row_shr:8
-    v += PIRIP_DPP_F(0.f, v, 0x142, 0xa);   // row_bcast:15
-    v += PIRIP_DPP_F(0.f, v, 0x143, 0xc);   // row_bcast:31 -> lane 63 holds the total
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-
-// arg-max with codec2's tie rule (first maximum wins): larger value, then smaller index. v >= 0 and never NaN (a lane's
-// candidate is only ever replaced by "w > best" with best starting at 0), so the wave maximum is six v_max_f32 with a DPP
-// source and the winning index is the minimum index among the lanes that hold the maximum (six v_min_i32). A lane whose
-// DPP source is outside its row, or whose row is masked out, is not written and keeps its own value; lane 63 ends up with
-// the reduction over the wave. s_nop 1: VALU write -> DPP read needs two wait states and hipcc does not look inside asm.
-#define PIRIP_DPP_REDUCE(op) \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:1 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:2 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:4 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_shr:8 row_mask:0xf bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_bcast:15 row_mask:0xa bank_mask:0xf\n\t" \
-        "s_nop 1\n\t" op " %0, %0, %0 row_bcast:31 row_mask:0xc bank_mask:0xf\n\t" \
-        "s_nop 1\n\tv_readlane_b32 %1, %0, 63"
-__device__ __forceinline__ void wargmax(float &v, int &idx)
-{
-    float red = v;
-    int smax, smin;
-    asm(PIRIP_DPP_REDUCE("v_max_f32_dpp") : "+v"(red), "=s"(smax));
-    int cand = (__builtin_bit_cast(int, v) == smax) ? idx : 0x7fffffff;      // v >= 0: equal values <=> equal bit patterns
-    asm(PIRIP_DPP_REDUCE("v_min_i32_dpp") : "+v"(cand), "=s"(smin));
-    v = __builtin_bit_cast(float, smax);
-    idx = smin;
-}
-#undef PIRIP_DPP_REDUCE
-
 __device__ __forceinline__ float ubyte0(uint32_t v) { return (float)(v & 0xffu); }
 __device__ __forceinline__ float ubyte1(uint32_t v) { return (float)((v >> 8) & 0xffu); }
 __device__ __forceinline__ float ubyte2(uint32_t v) { return (float)((v >> 16) & 0xffu); }
 __device__ __forceinline__ float ubyte3(uint32_t v) { return (float)(v >> 24); }
 
-// Correctly rounded sqrt for x that is zero or >= 2^-96; the caller takes this path only when every value of the batch
-// qualifies (one wave-uniform test), sqrtf() otherwise.
-//   FINITE: q = min(rsq(x), 2^60); y = x q; result = fma(fma(-y, y, x), q/2, y) -- one transcendental + 5 VALU. Correct
-//           rounding is not a theorem but a measurement: tools/compiler_checks.hip and the library's self-test
-//           (pirip_hip_selftest_sqrt, run by the GPU tests) compare it with (float)sqrt((double)x) for x = 0 and EVERY float in
-//           [2^-96, FLT_MAX] on the device; the clamp makes x = 0 give 0 and is a no-op elsewhere. +inf would give NaN,
-//           so the f32 input format (the only one that can produce an infinite |X|^2) keeps
-//   general: v_sqrt_f32 (within 1 ulp) plus the neighbour-residual test -- one transcendental + 8 VALU, inf/NaN as sqrtf.
-//   NZ (every value of the batch >= 2^-96, none zero: what a live receiver sees): the FINITE form without the clamp, which is a no-op
-//           there (rsq(2^-96) = 2^48) -- 4 instead of 5 VALU; and the batch's range test is then the minimum of the raw bit patterns
-//           (non-negative floats order as unsigned integers), without the "- 1" per value that lets zero pass (sqrt_key).
-template <bool FINITE, bool NZ = false>
-__device__ __forceinline__ float sqrt_rn_normal(float x)
-{
-    if (FINITE) {
-        float q = __builtin_amdgcn_rsqf(x);
-        if (!NZ) asm("v_min_f32 %0, %0, %1" : "+v"(q) : "v"(0x1p60f));
-        const float y = x * q, h = 0.5f * q;
-        return __builtin_fmaf(__builtin_fmaf(-y, y, x), h, y);
-    }
-    const float y = __builtin_amdgcn_sqrtf(x);
-    const float ym = __builtin_bit_cast(float, __builtin_bit_cast(int, y) - 1);
-    const float yp = __builtin_bit_cast(float, __builtin_bit_cast(int, y) + 1);
-    const float rm = __builtin_fmaf(-ym, y, x);
-    const float rp = __builtin_fmaf(-yp, y, x);
-    float r = (rm <= 0.0f) ? ym : y;
-    r = (rp > 0.0f) ? yp : r;
-    return r;
-}
 // llr_frame_gain (fsk_device.hpp) with its square root in the v_sqrt + neighbour-residual form where the argument allows it (wave-uniform)
 __device__ __forceinline__ float llr_frame_gain_quick(int llr_map, float sig, float nse)
 {
@@ -161,7 +83,6 @@ __device__ __forceinline__ float llr_frame_gain_quick(int llr_map, float sig, fl
     return (2.0f * (sig / nse)) / amp;
 }
 __device__ __forceinline__ unsigned sqrt_key(float x) { return __builtin_bit_cast(unsigned, x) - 1u; }
-__device__ __forceinline__ unsigned fbits(float x) { return __builtin_bit_cast(unsigned, x); }
 constexpr unsigned kSqrtLo = 0x0f800000u;                           // 2^-96
 constexpr unsigned kQuickHi = 0x7c000000u;                          // 2^121: the fused hand-over's quick path (its frame sums stay finite)
 __device__ __forceinline__ unsigned umin2(unsigned a, unsigned b) { return a < b ? a : b; }
@@ -172,21 +93,7 @@ __device__ __forceinline__ unsigned umin3(unsigned a, unsigned b, unsigned c)
     return r;
 }
 
-// ---- packed-f32 complex helpers ------------------------------------------------------------------------------------
-// A complex value is one VGPR pair (x = re in the low half). gfx950's v_pk_*_f32 take per-operand half selectors
-// (op_sel / op_sel_hi) and per-half negation (neg_lo / neg_hi), so kiss_fft's complex multiply is 3 instructions and the
-// +-j rotation inside the radix-4 butterfly is free; hipcc builds those operand swizzles with v_mov/v_xor copies, hence the
-// inline asm (one asm statement per helper: hipcc pads adjacent asm statements that feed each other with s_nop).
-// kiss_fft C_MUL: (a.x*t.x - a.y*t.y, a.x*t.y + a.y*t.x): three instructions, each product/sum rounded once (no fma)
-__device__ __forceinline__ v2f cmul_x(v2f a, v2f t)
-{
-    v2f p2, r;
-    asm("v_pk_mul_f32 %0, %2, %3 op_sel_hi:[0,1]\n\t"
-        "v_pk_mul_f32 %1, %2, %3 op_sel:[1,1] op_sel_hi:[1,0]\n\t"
-        "v_pk_add_f32 %0, %0, %1 neg_lo:[0,1]"
-        : "=&v"(r), "=&v"(p2) : "v"(a), "v"(t));
-    return r;
-}
+// ---- packed-f32 helpers of this kernel (the complex arithmetic it shares with the other demodulators: demod_simd.hpp) ------------
 // real window sample (low / high half of a table pair) times a complex sample: one packed multiply with a broadcast selector
 // (written as scalar code hipcc moves the odd-numbered window samples into low halves first)
 __device__ __forceinline__ v2f scale_lo(v2f h, v2f x)
@@ -218,58 +125,10 @@ __device__ __forceinline__ v2f smooth2(v2f sf, v2f mag, v2f k)
         : "+v"(sf), "=&v"(t) : "v"(mag), "v"(k));
     return sf;
 }
-__device__ __forceinline__ v2f add_rot(v2f a, v2f b)   // a + (b.y, -b.x)
-{
-    v2f r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_hi:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-__device__ __forceinline__ v2f sub_rot(v2f a, v2f b)   // a - (b.y, -b.x)
-{
-    v2f r; asm("v_pk_add_f32 %0, %1, %2 op_sel:[0,1] op_sel_hi:[1,0] neg_lo:[0,1]" : "=v"(r) : "v"(a), "v"(b)); return r;
-}
-// down-conversion x * conj(ph): 2 packed ops (fma allowed here)
-__device__ __forceinline__ v2f mix_conj(v2f x, v2f ph)
-{
-    v2f r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[1,0]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
-        : "=&v"(r) : "v"(x), "v"(ph));
-    return r;
-}
-// acc + x * conj(ph): the down-conversion folded into the running sum, 2 packed fma (round 5: was mix_conj + one packed add)
-__device__ __forceinline__ v2f mix_conj_acc(v2f x, v2f ph, v2f acc)
-{
-    v2f r;
-    asm("v_pk_fma_f32 %0, %1, %2, %3 op_sel_hi:[1,0,1]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[0,1,1] neg_hi:[1,0,0]"
-        : "=&v"(r) : "v"(x), "v"(ph), "v"(acc));
-    return r;
-}
-// oscillator step ph * d: 2 packed ops
-__device__ __forceinline__ v2f rot_step(v2f ph, v2f d)
-{
-    v2f r;
-    asm("v_pk_mul_f32 %0, %1, %2 op_sel_hi:[0,1]\n\t"
-        "v_pk_fma_f32 %0, %1, %2, %0 op_sel:[1,1,0] op_sel_hi:[1,0,1] neg_lo:[0,1,0]"
-        : "=&v"(r) : "v"(ph), "v"(d));
-    return r;
-}
-// kiss_fft radix-4 butterfly (forward) on operands already multiplied by their twiddles
-__device__ __forceinline__ void bfly4(v2f &f0, v2f &f1, v2f &f2, v2f &f3)
-{
-    const v2f s5 = f0 - f2;
-    f0 = f0 + f2;
-    const v2f s3 = f1 + f3;
-    const v2f s4 = f1 - f3;
-    f2 = f0 - s3;
-    f0 = f0 + s3;
-    f1 = add_rot(s5, s4);
-    f3 = sub_rot(s5, s4);
-}
 
 // ---- input formats ------------------------------------------------------------------------------------------------
-// Exact conversions (each checked against the defining expression for every input value in tests/test_boundary_cpu.py):
-//   fsk_demod -d   (x - 127)/128              = fma(x, 2^-7, -127/128)
-//   csdr / rtl_fsk x/127.5 - 1 (double, rounded) = fma(x, c_lo, fma(x, c_hi, -1)), c_hi a multiple of 2^-22
+// Exact conversions (each checked against the defining expression for every input value in tests/test_boundary_cpu.py; the 8-bit maps
+// on (I, Q) pairs, cvt_u8_pair: demod_simd.hpp):
 //   fsk_demod -c   x/750                       = fma(x, c_lo, x*c_hi), c_hi = 175/2^17 (x*c_hi exact for every int16)
 template <int FMT> struct InFmt;
 template <> struct InFmt<PIRIP_IN_CU8_FSKDEMOD> { static constexpr int BPS = 2; static constexpr bool NEUTRAL_OK = true; static constexpr uint32_t NEUTRAL = 0x7F7F7F7Fu; };
@@ -277,20 +136,6 @@ template <> struct InFmt<PIRIP_IN_CU8_CSDR> { static constexpr int BPS = 2; stat
 template <> struct InFmt<PIRIP_IN_CS16> { static constexpr int BPS = 4; static constexpr bool NEUTRAL_OK = true; static constexpr uint32_t NEUTRAL = 0u; };
 template <> struct InFmt<PIRIP_IN_CF32> { static constexpr int BPS = 8; static constexpr bool NEUTRAL_OK = true; static constexpr uint32_t NEUTRAL = 0u; };
 
-template <int FMT>
-__device__ __forceinline__ float cvt_u8(float b)
-{
-    if (FMT == PIRIP_IN_CU8_FSKDEMOD) return __builtin_fmaf(b, 0.0078125f, -0.9921875f);
-    return __builtin_fmaf(b, -1.187418e-07f, __builtin_fmaf(b, 0.007843255996704102f, -1.0f));
-}
-// the same maps on an (I, Q) pair of byte values: one v_pk_fma_f32 per fma instead of two scalar ones (round 5)
-template <int FMT>
-__device__ __forceinline__ v2f cvt_u8_pair(v2f b)
-{
-    if (FMT == PIRIP_IN_CU8_FSKDEMOD) return __builtin_elementwise_fma(b, v2f{0.0078125f, 0.0078125f}, v2f{-0.9921875f, -0.9921875f});
-    return __builtin_elementwise_fma(b, v2f{-1.187418e-07f, -1.187418e-07f},
-                                     __builtin_elementwise_fma(b, v2f{0.007843255996704102f, 0.007843255996704102f}, v2f{-1.0f, -1.0f}));
-}
 __device__ __forceinline__ float cvt_s16(float x)
 {
     const float hi = x * 0.00133514404296875f;                    // exact (16-bit x 8-bit significands)
@@ -387,22 +232,6 @@ __device__ int g_wave_stop_phase = -1;
 #define PIRIP_T_MARK(i) do { } while (0)
 #endif
 
-
-#ifndef PIRIP_XPS256            // (build-time experiment knobs: bytes per 16x16 transpose group, waves per SIMD of the Ts = 24 4-FSK instances)
-#define PIRIP_XPS256 2176
-#endif
-#ifndef PIRIP_M4_WPS
-#define PIRIP_M4_WPS 3
-#endif
-#ifndef PIRIP_S16_DIRECT        // the same for the complex-s16 instances (Ts = 40: 8.5 KB of staging per stream, two blocks per CU): measured, interleaved
-#define PIRIP_S16_DIRECT 0      // A/B: 254 against 261 G samples/s (2-FSK), 196 against 209 G (4-FSK mask) -- staged stays
-#endif
-#ifndef PIRIP_F32_PREFETCH
-#define PIRIP_F32_PREFETCH 1
-#endif
-#ifndef PIRIP_F32_DIRECT        // 1: complex-float instances read their samples from global memory instead of staging the frame in LDS
-#define PIRIP_F32_DIRECT 1
-#endif
 template <int M, int TS, int P, int NSYM, int NDFT, int FMT>
 struct WaveCfg {
     static constexpr int BPS = InFmt<FMT>::BPS;
@@ -422,13 +251,16 @@ struct WaveCfg {
     // at 6 waves per CU. Its FFT inputs and the correlator blocks come straight from global memory (L2); LDS keeps the guard and, behind
     // it, the HEAD: the first Ts + Ts/4 new samples, so that the three blocks that contain last frame's positions (lanes 0..2) read one
     // linear piece of LDS exactly as in the staged layout. DUMP: where the line-touching prefetch of the next frame lands.
-    // (Ndft = 128 shapes -- Ts = 8, 10: 4 KB frames -- stay staged: measured 3-10 % slower unstaged)
-    static constexpr bool DIRECT = (PIRIP_F32_DIRECT != 0) && (FMT == PIRIP_IN_CF32 || (FMT == PIRIP_IN_CS16 && PIRIP_S16_DIRECT != 0)) && NDFT >= 256;
+    // (Ndft = 128 shapes -- Ts = 8, 10: 4 KB frames -- stay staged: measured 3-10 % slower unstaged. So do the complex-s16 instances -- Ts = 40:
+    // 8.5 KB of staging per stream, two blocks per CU -- measured, interleaved A/B: unstaged 254 against 261 G samples/s (2-FSK), 196 against
+    // 209 G (4-FSK mask), DESIGN_NOTES.md 4.1)
+    static constexpr bool DIRECT = FMT == PIRIP_IN_CF32 && NDFT >= 256;
     static constexpr int HEAD_B = 1024, DUMP_B = 256;
     static_assert(!DIRECT || ((TS + Q) * BPS <= HEAD_B && 3 * TS >= 2 * TS + Q), "the head holds blocks 0..2's new samples");
     static constexpr int RAW_B = DIRECT ? GUARD_B + HEAD_B + DUMP_B : GUARD_B + NDMA16 * 1024 + NDMA4 * 256;
     // FFT exchange area (also the |X|^2 hand-over and the mask estimator's linear spectrum)
-    static constexpr int XP_FFT_B = NDFT == 256 ? 4 * PIRIP_XPS256 : NDFT == 512 ? 4480 : 8 * 72 * 8;    // Ndft 128: eight FFTs x (8 groups x 9) complex, two passes
+    static constexpr int XPS256 = 16 * 17 * 8;                 // Ndft = 256: bytes per FFT group, 16 rows x 17 cf
+    static constexpr int XP_FFT_B = NDFT == 256 ? 4 * XPS256 : NDFT == 512 ? 4480 : 8 * 72 * 8;    // Ndft 128: eight FFTs x (8 groups x 9) complex, two passes
     static constexpr int XP_B = cmax(cmax(XP_FFT_B, NDFT * 4), NDFT == 256 ? 64 * 20 * 4 : NDFT == 128 ? 8 * 136 * 4 : 0);
     // carried between launches in the stream's DemodState::hist block (M * HIST float2 = room to spare): the guard area as it stands
     // (the raw tail, right-aligned), then per tone last frame's phase step and oscillator-table row, then last frame's nin (0: no tail yet)
@@ -472,12 +304,8 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     // into the kernarg segment that is made opaque twice per frame: no instance then spills more than 8 SGPRs (most: none) -- and all
     // but three shapes are SLOWER by 0.1 .. 2.7 % (interleaved A/B on one box, profiles/r06_b_ab_kernarg_instances.txt: a scalar load's
     // latency at the point of use costs more than a lane write and a lane read). So: by value, except Ts = 10 (`rtl_fsk -a 100000 -r 10000`,
-    // README.md:196: + 1.9 % / + 4.1 %). -DPIRIP_WAVE_KERNARG_INPLACE=0 / 1 force one way for every instance (A/B builds).
-#ifdef PIRIP_WAVE_KERNARG_INPLACE
-    constexpr bool INPLACE = PIRIP_WAVE_KERNARG_INPLACE != 0;
-#else
+    // README.md:196: + 1.9 % / + 4.1 %).
     constexpr bool INPLACE = TS == 10;
-#endif
     static_assert(offsetof(DemodArgs, d) == 0, "the argument block is the first kernel argument");
     auto ap = [&]() {
         if constexpr (INPLACE) return (const __attribute__((address_space(4))) DemodArgs *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -622,11 +450,9 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             // the head behind the guard (one 16-byte-per-lane copy covers it), then one dword of every 128-byte line of the superset
             // into the dump row: the lines are on their way to L2 while this frame's window sums, timing and decisions run
             __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(raw + GUARD_B), 16, lane0 * 16, goff, 0, 0);
-#if PIRIP_F32_PREFETCH
 #pragma unroll
             for (int i = 0; i < (C::SUP_B + 8191) / 8192; i++)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (lds_ptr)(raw + GUARD_B + C::HEAD_B), 4, lane0 * 128, goff + i * 8192, 0, 0);
-#endif
             return;
         }
 #pragma unroll
@@ -684,7 +510,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             PIRIP_PHASE_LANE(lane);
             const int grp = lane >> 4, e16 = lane & 15;    // 4 FFTs x 16 lanes
             const float4 *ftab = (const float4 *)s_tab + e16;
-            constexpr int XPS = PIRIP_XPS256;              // bytes per FFT group: 16 rows x 17 cf
+            constexpr int XPS = C::XPS256;
             // this lane's FFT constants, fetched once per frame (48 VGPRs that are free until the correlator starts):
             // chunks 0..3 Hann samples of its 16 inputs, 4..5 stage-3 twiddles, 5..11 stage-4 twiddles
             float4 tabv[12];
@@ -1133,7 +959,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                 for (int k = 0; k < d.n_teeth; k++) corr += sfl[b + a.t.teeth[k]];    // tooth sums in ascending order
                 if (corr > best) { best = corr; ib = b; }
             }
-            wargmax(best, ib);
+            wave_argmax(best, ib);
             bb = ib;
             wave_lds_sync();
         } else {
@@ -1153,7 +979,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
 #pragma unroll
                 for (int b = 0; b < NB; b++)
                     if (w[b] > best) { best = w[b]; ib = sfi[b]; }
-                wargmax(best, ib);
+                wave_argmax(best, ib);
                 int f_min = ib - d.f_zero; f_min = f_min < 0 ? 0 : f_min;
                 int f_max = ib + d.f_zero; f_max = f_max > NDFT ? NDFT : f_max;
 #pragma unroll
@@ -1359,7 +1185,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                 tcr = pr * tgain.x - pi * tgain.y;
                 tci = pr * tgain.y + pi * tgain.x;
             }
-            tcr = wsum(tcr); tci = wsum(tci);
+            tcr = wave_sum(tcr); tci = wave_sum(tci);
         }
 
         PIRIP_T_MARK(4);                                   // DMA issue, hist copy, window sums, timing reduction
@@ -1486,17 +1312,17 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                 for (int m = 0; m < M; m++) { kmin = umin2(kmin, sqrt_key(tmax[m])); kmax = kmax > fbits(tmax[m]) ? kmax : fbits(tmax[m]); }
                 const bool quick = __all(!act || (kmin >= 0x0f800000u - 1u && kmax <= kQuickHi));
                 float ssig, snse;
-                // (the receiver's defined summation order IS this kernel's wave reduction: ldpc_kernels.hip wave_order_sum)
+                // (the receiver's defined summation order IS this kernel's wave reduction: ldpc_kernels.hip sums with the same wave_sum)
                 if (quick) {
 #pragma unroll
                     for (int m = 0; m < M; m++) { mag[m] = sqrt_rn_normal<FMT != PIRIP_IN_CF32>(tmax[m]); const float p2 = mag[m] * mag[m]; sum2 = sum2 + p2; mx2 = p2 > mx2 ? p2 : mx2; }
-                    ssig = wsum(act ? mx2 : 0.f); snse = wsum(act ? div_rn_const<M - 1>(sum2 - mx2) : 0.f);
+                    ssig = wave_sum(act ? mx2 : 0.f); snse = wave_sum(act ? div_rn_const<M - 1>(sum2 - mx2) : 0.f);
                     ssig = div_rn_const<NSYM>(ssig);
                     snse = div_rn_const<NSYM>(snse) + 1e-12f;
                 } else {
 #pragma unroll
                     for (int m = 0; m < M; m++) { mag[m] = sqrtf(tmax[m]); const float p2 = mag[m] * mag[m]; sum2 = sum2 + p2; mx2 = p2 > mx2 ? p2 : mx2; }
-                    ssig = wsum(act ? mx2 : 0.f); snse = wsum(act ? (sum2 - mx2) / (float)(M - 1) : 0.f);
+                    ssig = wave_sum(act ? mx2 : 0.f); snse = wave_sum(act ? (sum2 - mx2) / (float)(M - 1) : 0.f);
                     ssig = ssig / (float)NSYM;
                     snse = (snse / (float)NSYM) + 1e-12f;
                 }
@@ -1551,12 +1377,12 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             const bool last_frame = (frame + 1 >= max_frames) || (pos + nin + nin_next > nsamp);
             if (stats_o || last_frame) {
                 float sig = act ? mx : 0.f, nse = act ? (sum - mx) / (float)(M - 1) : 0.f;
-                sig = wsum(sig); nse = wsum(nse) + 1e-12f;
+                sig = wave_sum(sig); nse = wave_sum(nse) + 1e-12f;
                 sig = sig / (float)NSYM; nse = nse / (float)NSYM;
                 sc_SNRest = sig / nse;
                 // codec2's other by-products (v_est, EbNodB and its smoothed form, MODEM_STATS.snr_est): kept in LDS between
                 // observable frames so they cost no registers on the frames that skip this block
-                float mean_e = wsum(act ? sqrtf(mx) : 0.f), std_e = wsum(act ? mx : 0.f);
+                float mean_e = wave_sum(act ? sqrtf(mx) : 0.f), std_e = wave_sum(act ? mx : 0.f);
                 mean_e = mean_e / (float)NSYM;
                 std_e = (std_e / (float)NSYM) - (mean_e * mean_e);
                 // (single-precision throughout: (float)sqrt((double)x) == sqrtf(x) and .5*a + .5*b rounds the same either way;
@@ -1730,29 +1556,9 @@ hipError_t launch_inst(const DemodArgs &a, int nstreams, hipStream_t stream)
 #define PIRIP_WAVE_INST_FMA(M, TS, P, NDFT, FMT, WPB, WPS) {M, TS, P, 50, NDFT, FMT, 1, 0, WPB, WPS, 0, launch_inst<M, TS, P, 50, NDFT, FMT, WPB, WPS, true, false>}
 #define PIRIP_WAVE_INST_MASK(M, TS, P, NDFT, FMT, WPB, WPS) {M, TS, P, 50, NDFT, FMT, 0, 1, WPB, WPS, 0, launch_inst<M, TS, P, 50, NDFT, FMT, WPB, WPS, false, true>}
 #define PIRIP_WAVE_INST_BAND(M, TS, P, NDFT, FMT, WPB, WPS, B) {M, TS, P, 50, NDFT, FMT, 0, 0, WPB, WPS, B, launch_inst<M, TS, P, 50, NDFT, FMT, WPB, WPS, false, false, B>}
-#ifndef PIRIP_N128_WPB          // (build-time experiment knobs for the Ndft = 128 2-FSK instances: streams per block, waves per SIMD)
-// complex-float instances: unstaged (PIRIP_F32_DIRECT) they are no longer bound by LDS: four streams per block, as many waves as the registers allow
-#if PIRIP_F32_DIRECT
-#define PIRIP_F32_WPB 4
-#define PIRIP_F32_WPS(M) ((M) == 2 ? 3 : 2)      /* Ts = 40; 4-FSK at three waves per SIMD spills 3-9 registers */
-#define PIRIP_F32_WPS256(M) 3                     /* Ts = 18, 20: every instance fits 168 VGPR */
-#else
-#define PIRIP_F32_WPB 2
-#define PIRIP_F32_WPS(M) 1
-#define PIRIP_F32_WPS256(M) 1
-#endif
-#if PIRIP_F32_DIRECT && PIRIP_S16_DIRECT
-#define PIRIP_S16_WPS(M) ((M) == 2 ? 3 : 2)
-#else
-#define PIRIP_S16_WPS(M) 2
-#endif
-#define PIRIP_N128_WPB 4
-#define PIRIP_N128_WPS 4
-#endif
+// Complex-float instances with Ndft >= 256 are unstaged (WaveCfg::DIRECT) and so no longer bound by LDS: four streams per block, as many
+// waves per SIMD as the registers allow.
 const WaveInst kInst[] = {
-#ifdef PIRIP_WAVE_PROBE      // compile-time experiments: one instance only
-    PIRIP_WAVE_INST(2, 24, PIRIP_WAVE_PROBE_P, 256, PIRIP_IN_CU8_FSKDEMOD, 4, PIRIP_WAVE_PROBE),
-#else
     // Ts = 24 (Fs 240k / Rs 10k), both 8-bit front ends. P = 24: `fsk_demod -p 24` (README.md:105); P = 8: fsk_demod's default;
     // P = 6: what rtl_fsk derives from Ts = 24. _MASK: the `--mask` comb estimator (README.md:239-297)
     PIRIP_WAVE_INST(2, 24, 24, 256, PIRIP_IN_CU8_FSKDEMOD, 4, 3),
@@ -1761,34 +1567,33 @@ const WaveInst kInst[] = {
     // opt-in band-only estimator (pirip_hip_set_estimator_band_only): the `fsk_demod -p 24` shape, both 8-bit front ends
     PIRIP_WAVE_INST_BAND(2, 24, 24, 256, PIRIP_IN_CU8_FSKDEMOD, 4, 3, 2), PIRIP_WAVE_INST_BAND(2, 24, 24, 256, PIRIP_IN_CU8_CSDR, 4, 3, 2),
     // ... and the 4-FSK P = 8 shape with a search range inside bins 0 .. 63 (BASELINE configs[3] as bench_configs.py sets it up: 500 .. 60000 Hz)
-    PIRIP_WAVE_INST_BAND(4, 24, 8, 256, PIRIP_IN_CU8_FSKDEMOD, 4, PIRIP_M4_WPS, 4), PIRIP_WAVE_INST_BAND(4, 24, 8, 256, PIRIP_IN_CU8_CSDR, 4, PIRIP_M4_WPS, 4),
+    PIRIP_WAVE_INST_BAND(4, 24, 8, 256, PIRIP_IN_CU8_FSKDEMOD, 4, 3, 4), PIRIP_WAVE_INST_BAND(4, 24, 8, 256, PIRIP_IN_CU8_CSDR, 4, 3, 4),
 #define PIRIP_TS24(M, P, WPB, WPS) \
     PIRIP_WAVE_INST(M, 24, P, 256, PIRIP_IN_CU8_FSKDEMOD, WPB, WPS), PIRIP_WAVE_INST(M, 24, P, 256, PIRIP_IN_CU8_CSDR, WPB, WPS), \
     PIRIP_WAVE_INST_MASK(M, 24, P, 256, PIRIP_IN_CU8_FSKDEMOD, WPB, WPS), PIRIP_WAVE_INST_MASK(M, 24, P, 256, PIRIP_IN_CU8_CSDR, WPB, WPS)
-    PIRIP_TS24(2, 8, 4, 3), PIRIP_TS24(2, 6, 4, 3), PIRIP_TS24(4, 8, 4, PIRIP_M4_WPS), PIRIP_TS24(4, 6, 4, PIRIP_M4_WPS),    // (4-FSK at 9, 10 or 11 waves per CU -- blocks of 3, 5 or 11 streams, 168 VGPR -- measured slower per stream than 8: two waves already keep a SIMD's issue port busy)
+    PIRIP_TS24(2, 8, 4, 3), PIRIP_TS24(2, 6, 4, 3), PIRIP_TS24(4, 8, 4, 3), PIRIP_TS24(4, 6, 4, 3),    // (4-FSK at 9, 10 or 11 waves per CU -- blocks of 3, 5 or 11 streams, 168 VGPR -- measured slower per stream than 8: two waves already keep a SIMD's issue port busy)
 #undef PIRIP_TS24
     // Ts = 40 (Fs 40k / Rs 1k): s16 behind the csdr decimator (README.md:109), f32 inside rtl_fsk (-a 40000 -r 1000: script/ping:47,
     // script/frame_repeater:36; 4-FSK with --mask: README.md:239). P = 8: fsk_demod's default, P = 10: rtl_fsk's.
-    // (s16: 5 waves per block, 10 per CU, measured slower than 4 / 8: uneven SIMD load)
+    // (s16: 5 waves per block, 10 per CU, measured slower than 4 / 8: uneven SIMD load. f32 4-FSK at three waves per SIMD spills 3-9 registers)
 #define PIRIP_TS40(M, P) \
-    PIRIP_WAVE_INST(M, 40, P, 512, PIRIP_IN_CS16, 4, PIRIP_S16_WPS(M)), PIRIP_WAVE_INST(M, 40, P, 512, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS(M)), \
-    PIRIP_WAVE_INST_MASK(M, 40, P, 512, PIRIP_IN_CS16, 4, PIRIP_S16_WPS(M)), PIRIP_WAVE_INST_MASK(M, 40, P, 512, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS(M))
+    PIRIP_WAVE_INST(M, 40, P, 512, PIRIP_IN_CS16, 4, 2), PIRIP_WAVE_INST(M, 40, P, 512, PIRIP_IN_CF32, 4, ((M) == 2 ? 3 : 2)), \
+    PIRIP_WAVE_INST_MASK(M, 40, P, 512, PIRIP_IN_CS16, 4, 2), PIRIP_WAVE_INST_MASK(M, 40, P, 512, PIRIP_IN_CF32, 4, ((M) == 2 ? 3 : 2))
     PIRIP_TS40(2, 8), PIRIP_TS40(2, 10), PIRIP_TS40(4, 8), PIRIP_TS40(4, 10),
 #undef PIRIP_TS40
     // Ts = 20 (rtl_fsk -a 200000 -r 10000 [-m 4] [--mask 10000]: README.md:262,292,297), float samples from the in-process decimator;
-    // 6 FFTs of 256 per frame = one full batch of four and a half-empty one
-    PIRIP_WAVE_INST(2, 20, 10, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(2)), PIRIP_WAVE_INST_MASK(2, 20, 10, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(2)),
-    PIRIP_WAVE_INST(4, 20, 10, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(4)), PIRIP_WAVE_INST_MASK(4, 20, 10, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(4)),
+    // 6 FFTs of 256 per frame = one full batch of four and a half-empty one. Ts = 20 and 18: every instance fits 168 VGPR (three waves per SIMD)
+    PIRIP_WAVE_INST(2, 20, 10, 256, PIRIP_IN_CF32, 4, 3), PIRIP_WAVE_INST_MASK(2, 20, 10, 256, PIRIP_IN_CF32, 4, 3),
+    PIRIP_WAVE_INST(4, 20, 10, 256, PIRIP_IN_CF32, 4, 3), PIRIP_WAVE_INST_MASK(4, 20, 10, 256, PIRIP_IN_CF32, 4, 3),
     // Ts = 18 (rtl_fsk -a 180000 -r 10000 -m 4 --mask 10000: README.md:286); nin moves in steps of Ts/4 = 4 samples
-    PIRIP_WAVE_INST(2, 18, 9, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(2)), PIRIP_WAVE_INST_MASK(2, 18, 9, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(2)),
-    PIRIP_WAVE_INST(4, 18, 9, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(4)), PIRIP_WAVE_INST_MASK(4, 18, 9, 256, PIRIP_IN_CF32, PIRIP_F32_WPB, PIRIP_F32_WPS256(4)),
+    PIRIP_WAVE_INST(2, 18, 9, 256, PIRIP_IN_CF32, 4, 3), PIRIP_WAVE_INST_MASK(2, 18, 9, 256, PIRIP_IN_CF32, 4, 3),
+    PIRIP_WAVE_INST(4, 18, 9, 256, PIRIP_IN_CF32, 4, 3), PIRIP_WAVE_INST_MASK(4, 18, 9, 256, PIRIP_IN_CF32, 4, 3),
     // Ts = 10 / Ndft = 128 (rtl_fsk -a 100000 -r 10000: README.md:196) and Ts = 8 / Ndft = 128 (rtl_fsk -s 2400000 -a 80000 -r 10000 on a
     // Pi: README.md:172), float samples from the in-process decimator; all of a frame's 6 / 5 FFTs in one batch of eight
-    PIRIP_WAVE_INST(2, 10, 10, 128, PIRIP_IN_CF32, PIRIP_N128_WPB, PIRIP_N128_WPS), PIRIP_WAVE_INST_MASK(2, 10, 10, 128, PIRIP_IN_CF32, PIRIP_N128_WPB, PIRIP_N128_WPS),
+    PIRIP_WAVE_INST(2, 10, 10, 128, PIRIP_IN_CF32, 4, 4), PIRIP_WAVE_INST_MASK(2, 10, 10, 128, PIRIP_IN_CF32, 4, 4),
     PIRIP_WAVE_INST(4, 10, 10, 128, PIRIP_IN_CF32, 2, 2), PIRIP_WAVE_INST_MASK(4, 10, 10, 128, PIRIP_IN_CF32, 2, 2),
-    PIRIP_WAVE_INST(2, 8, 8, 128, PIRIP_IN_CF32, PIRIP_N128_WPB, PIRIP_N128_WPS), PIRIP_WAVE_INST_MASK(2, 8, 8, 128, PIRIP_IN_CF32, PIRIP_N128_WPB, PIRIP_N128_WPS),
+    PIRIP_WAVE_INST(2, 8, 8, 128, PIRIP_IN_CF32, 4, 4), PIRIP_WAVE_INST_MASK(2, 8, 8, 128, PIRIP_IN_CF32, 4, 4),
     PIRIP_WAVE_INST(4, 8, 8, 128, PIRIP_IN_CF32, 2, 2), PIRIP_WAVE_INST_MASK(4, 8, 8, 128, PIRIP_IN_CF32, 2, 2),
-#endif
 };
 #undef PIRIP_WAVE_INST
 #undef PIRIP_WAVE_INST_FMA

@@ -27,6 +27,7 @@
 #include <vector>
 
 #include "../../include/pirip_hip.h"
+#include "demod_simd.hpp"
 #include "fsk_device.hpp"
 #include "fsk_ldpc.hpp"
 
@@ -104,30 +105,15 @@ __device__ __forceinline__ float phi_lookup(const float *tab, float x)
     return tab[idx];
 }
 
-// Sum over a wave in the receiver's DEFINED order (the checker (ldpc_oracle.c): wave_order_sum): row_shr 1, 2, 4, 8 inside rows of 16 lanes,
-// then row 1 += row 0's total and row 3 += row 2's, then rows 2 and 3 += lane 31's; lane 63 holds the result. The same DPP steps as
-// the demodulator's wsum() -- that is the point: the frame's signal / noise sums of the LLR stage cost the fused hand-over 14
-// instructions instead of 100 dependent adds. Terms are >= 0 (adding the +0 of an absent source lane changes nothing).
-#define LDPC_DPP_F(src, ctrl, rmask) \
-    __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, (float)(src)), ctrl, rmask, 0xf, false))
-__device__ __forceinline__ float wave_order_sum(float v)
-{
-    v = v + LDPC_DPP_F(v, 0x111, 0xf);
-    v = v + LDPC_DPP_F(v, 0x112, 0xf);
-    v = v + LDPC_DPP_F(v, 0x114, 0xf);
-    v = v + LDPC_DPP_F(v, 0x118, 0xf);
-    v = v + LDPC_DPP_F(v, 0x142, 0xa);
-    v = v + LDPC_DPP_F(v, 0x143, 0xc);
-    return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63));
-}
-#undef LDPC_DPP_F
-
 // ---- stage 1: LLRs ----------------------------------------------------------------------------------------------------
 // grid (ceil(ncalls / kLlrTile), nstreams), block 256: a workgroup turns kLlrTile consecutive demodulator calls of one stream
 // (a contiguous run of rx_filt, read as rows of Nsym consecutive floats) into soft bits. llr_all[s] = [2*bpf history | ncalls*Nbits
 // new]; tile 0 also brings the history in. The frame statistics (codec2's fsk_demod_core: sig and nse, sums over the symbols) are
-// summed in the receiver's defined wave order (wave_order_sum above; the oracle states the same order in C): cheap here and in the
-// demodulator's fused hand-over, and a last-bit difference from a serial sum vanishes in the binary16 rounding of the soft bits.
+// summed in the receiver's DEFINED wave order, demod_simd.hpp's wave_sum (the checker, ldpc_oracle.c, states it in C: wave_order_sum): row_shr
+// 1, 2, 4, 8 inside rows of 16 lanes, then row 1 += row 0's total and row 3 += row 2's, then rows 2 and 3 += lane 31's; lane 63 holds the
+// result. The demodulator's fused hand-over sums with the same function -- that is the point: there the frame's signal / noise sums cost
+// 14 instructions instead of 100 dependent adds. Terms are >= 0 (adding the +0 of an absent source lane changes nothing), and a last-bit
+// difference from a serial sum vanishes in the binary16 rounding of the soft bits.
 // When `words` is given the tile also packs its hard decisions 32 per word (first bit in the MSB) -- it covers whole words
 // because the host only asks for that when 2*bpf is a multiple of 32 (kLlrTile * Nbits always is).
 constexpr int kLlrTile = 32;
@@ -190,11 +176,11 @@ __global__ __launch_bounds__(kLlrThreads) void llr_tile_kernel(LdpcDev c, const 
         }
     }
     // per (call, symbol): the largest tone power and the mean of the others (codec2's per-symbol terms); the frame's two sums in
-    // wave order: lane l adds its symbols l, l + 64, ... in index order, then the lanes combine (wave_order_sum)
+    // wave order: lane l adds its symbols l, l + 64, ... in index order, then the lanes combine (wave_sum)
     // (the sums of a call are wave-uniform; the gain -- two divisions and a square root -- is formed afterwards, one call per lane, instead of
     //  by all 64 lanes once per call)
     auto frame_gain = [&](int cl, float sig_l, float nse_l) {
-        const float sig = wave_order_sum(sig_l), nse = wave_order_sum(nse_l);
+        const float sig = wave_sum(sig_l), nse = wave_sum(nse_l);
         if (lane == 0) { s_sn[2 * cl] = sig; s_sn[2 * cl + 1] = nse; }
     };
     if constexpr (REG) {
@@ -765,13 +751,11 @@ __global__ __launch_bounds__(kWave * WPB, MAXDEG > 6 ? 3 : 4) void decode_fast_k
     };
     // The kernel is bound by the LDS pipe (PMC, profiles/r05_o_configs_pmc.txt: SQ_LDS_IDX_ACTIVE 90 % of the cycles, 41 % of them
     // bank conflicts -- the data-dependent phi look-ups: 32 lanes of a group on 32 banks, the bank is the argument's top five
-    // mantissa bits), the vector-memory path is idle. The first PIRIP_PHI_VMEM slots of a row's first-stage look-ups read the SAME
+    // mantissa bits), the vector-memory path is idle. The first kPhiVmem slots of a row's first-stage look-ups read the SAME
     // table from global memory (2.3 KB, L1-resident): same values, LDS pipe relieved. Measured (profiles/r05_q_phi_vmem_ab.txt):
     // receive stage at 3.5 dB 9.64 ms -> 9.35 / 9.28 / 9.26 / 9.23 for 3 / 4 / 5 / 6 slots, second-stage look-ups as well 10.4 (2nd only)
     // and 13.1 ms (all 48: the texture path then is the bottleneck); at 7 dB (1.2 iterations per frame) 4.13 -> 4.19 ms.
-#ifndef PIRIP_PHI_VMEM
-#define PIRIP_PHI_VMEM 4
-#endif
+    constexpr int kPhiVmem = 4;
     const __amdgpu_buffer_rsrc_t phi_rsrc = __builtin_amdgcn_make_buffer_rsrc((void *)((const char *)c.phi - kPhiFirst), 0, (int)(kPhiFirst + (uint32_t)kPhiN * 4u), 0x00020000);
     auto phi_vm = [&](float x) {
         x = __builtin_fminf(__builtin_fmaxf(__builtin_fabsf(x), kPhiXLo), kPhiXHi);
@@ -846,7 +830,7 @@ __global__ __launch_bounds__(kWave * WPB, MAXDEG > 6 ? 3 : 4) void decode_fast_k
 #pragma unroll
                     for (int j = 0; j < MAXDEG; j++) {
                         const uint32_t qb = a[i][j];
-                        const float ph = j < PIRIP_PHI_VMEM ? phi_vm(__builtin_bit_cast(float, qb)) : phi_at(__builtin_bit_cast(float, qb));
+                        const float ph = j < kPhiVmem ? phi_vm(__builtin_bit_cast(float, qb)) : phi_at(__builtin_bit_cast(float, qb));
                         sg[i] ^= qb;
                         S[i] = S[i] + ph;
                         a[i][j] = __builtin_bit_cast(uint32_t, ph) | (qb & 0x80000000u);
@@ -974,8 +958,6 @@ constexpr int kBankChunk = 16;
 //   * ors its status bits into the status byte's word with one no-return atomic instead of load / or / store.
 struct BankDev { const uint16_t *vcrc; uint32_t crc0, cps, cps_magic; };   // cps: chunks per stream; cps_magic = ceil(2^32 / cps): unit / cps = mulhi(unit, magic)
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-// (by value: __builtin_bit_cast applied directly to a vector element expression `v.y` reads element 0 with this hipcc)
-__device__ __forceinline__ uint32_t fbits(float v) { return __builtin_bit_cast(uint32_t, v); }
 // xor of N words, three at a time (v_bitop3_b32 with the table of a ^ b ^ c)
 template <int N> __device__ __forceinline__ uint32_t xor_all(const uint32_t (&x)[N])
 {

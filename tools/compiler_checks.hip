@@ -4,14 +4,17 @@
 //      second read back as the first (why the Ndft = 512 instances use inline asm)?
 //   2. v_sqrt_f32 against the correctly rounded square root over EVERY positive float: the histogram of its error in ulps
 //      (why the estimator does not use the bare instruction: Sf has to be bit-identical to sqrtf on the CPU).
-//   3. the kernel's replacement, q = min(rsq(x), 2^60); y = x q; fma(fma(-y, y, x), q/2, y), over x = 0 and [2^-96, FLT_MAX], and the
-//      v_sqrt + neighbour-residual form: number of wrong results (the library's own self-test, pirip_hip_selftest_sqrt, repeats this).
+//   3. the kernels' replacement, sqrt_rn_normal<true> of pirip_amd/csrc/demod_simd.hpp (q = min(rsq(x), 2^60); y = x q;
+//      fma(fma(-y, y, x), q/2, y)), over x = 0 and [2^-96, FLT_MAX], and its v_sqrt + neighbour-residual form sqrt_rn_normal<false>:
+//      number of wrong results (the library's own self-test, pirip_hip_selftest_sqrt, repeats this).
 //   hipcc --offload-arch=gfx950 -O3 -o tools/bin/compiler_checks tools/compiler_checks.hip && tools/bin/compiler_checks > profiles/r04_compiler_checks.txt
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstdint>
 #include <cstdio>
+
+#include "../pirip_amd/csrc/demod_simd.hpp"
 
 __global__ void swap_kernel(unsigned *out)
 {
@@ -24,22 +27,6 @@ __global__ void swap_kernel(unsigned *out)
     out[lane] = r[0]; out[64 + lane] = r[1]; out[128 + lane] = x; out[192 + lane] = y;
 }
 
-__device__ __forceinline__ float sqrt_rsq(float x)
-{
-    float q = __builtin_amdgcn_rsqf(x);
-    q = fminf(q, 0x1p60f);
-    const float y = x * q, h = 0.5f * q;
-    return __builtin_fmaf(__builtin_fmaf(-y, y, x), h, y);
-}
-__device__ __forceinline__ float sqrt_fix(float x)
-{
-    const float y = __builtin_amdgcn_sqrtf(x);
-    const float ym = __builtin_bit_cast(float, __builtin_bit_cast(int, y) - 1), yp = __builtin_bit_cast(float, __builtin_bit_cast(int, y) + 1);
-    const float rm = __builtin_fmaf(-ym, y, x), rp = __builtin_fmaf(-yp, y, x);
-    float r = (rm <= 0.0f) ? ym : y;
-    return (rp > 0.0f) ? yp : r;
-}
-
 // hist[0..4]: v_sqrt_f32 - RN(sqrt) in ulps (<= -2, -1, 0, +1, >= +2); hist[5], hist[6]: wrong results of the rsq form / the v_sqrt + fix-up form
 __global__ void sqrt_kernel(unsigned long long *hist, unsigned lo, unsigned hi)
 {
@@ -50,8 +37,8 @@ __global__ void sqrt_kernel(unsigned long long *hist, unsigned lo, unsigned hi)
         const float want = (float)sqrt((double)x);                 // double rounding is innocuous for sqrt
         const int d = __builtin_bit_cast(int, __builtin_amdgcn_sqrtf(x)) - __builtin_bit_cast(int, want);
         h[d <= -2 ? 0 : d == -1 ? 1 : d == 0 ? 2 : d == 1 ? 3 : 4]++;
-        h[5] += __builtin_bit_cast(unsigned, sqrt_rsq(x)) != __builtin_bit_cast(unsigned, want);
-        h[6] += __builtin_bit_cast(unsigned, sqrt_fix(x)) != __builtin_bit_cast(unsigned, want);
+        h[5] += __builtin_bit_cast(unsigned, pirip::sqrt_rn_normal<true>(x)) != __builtin_bit_cast(unsigned, want);
+        h[6] += __builtin_bit_cast(unsigned, pirip::sqrt_rn_normal<false>(x)) != __builtin_bit_cast(unsigned, want);
     }
     for (int i = 0; i < 7; i++) if (h[i]) atomicAdd(&hist[i], h[i]);
 }
