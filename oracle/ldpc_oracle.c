@@ -1,6 +1,6 @@
 /* oracle/ldpc_oracle.c -- TEST INFRASTRUCTURE ONLY (CPU oracle; parity unpinned).
  *
- * CPU restatement of the FSK_LDPC receive chain the HIP path implements (pirip_amd/csrc/ldpc_kernels.hip):
+ * CPU restatement of the FSK_LDPC receive chain the HIP path implements (pirip_amd/csrc/ldpc_stages.hip, ldpc_decode.hip, ldpc_rx.hip):
  * soft decisions -> bit LLRs -> unique-word sync state machine -> sum-product LDPC decode -> CRC16 -> payload + rx_status.
  * What the reference pins is the framing and the record/flag protocol (/root/reference/tx/rpitx_fsk.cpp:75-83,313-336,
  * 382-395,427-509; tx/frame_repeater.c:55-62,71,80,88; README.md:176-212); the decoder arithmetic, the LLR mapping, the

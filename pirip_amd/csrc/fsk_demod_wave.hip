@@ -195,7 +195,7 @@ __device__ __forceinline__ float atan2_turns(float y, float x)
     return __builtin_copysignf(r, y);
 }
 
-// ---- fused FSK_LDPC hand-over (SoftOut): the arithmetic of ldpc_kernels.hip's LLR stage / the checker (ldpc_oracle.c), operation for operation
+// ---- fused FSK_LDPC hand-over (SoftOut): the arithmetic of ldpc_stages.hip's LLR stage / the checker (ldpc_oracle.c), operation for operation
 constexpr float kLlrMax = 24.0f;
 // ln I0(x), x >= 0: table at multiples of 1/8 up to 32 with linear interpolation, slope 1 beyond
 // (branch-free, so that a lane's four look-ups are in flight together: beyond 32 the argument is held at 32, where the
@@ -1298,7 +1298,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             }
             if constexpr (SOFT_OK) if (a.io.soft.llr) {
                 // Bit LLRs from the soft magnitudes fsk_demod_sd would have handed over, computed exactly as the LLR stage computes
-                // them from rx_filt (ldpc_kernels.hip: llr_tile_kernel; the checker (ldpc_oracle.c): oracle_ldpc_llr): per-symbol terms on
+                // them from rx_filt (ldpc_stages.hip: llr_tile_kernel; the checker (ldpc_oracle.c): oracle_ldpc_llr): per-symbol terms on
                 // every lane, the frame's two sums by the wave reduction, ln I0 by table + linear interpolation, 4-FSK bits by max-log.
                 // Square roots and the divisions by constants are IEEE operations: any correctly rounded form gives the same words. When every
                 // |f|^2 of the frame is zero or in [2^-96, 2^121] (one wave-uniform test: always, short of denormal or huge cf32 inputs) the roots
@@ -1312,7 +1312,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                 for (int m = 0; m < M; m++) { kmin = umin2(kmin, sqrt_key(tmax[m])); kmax = kmax > fbits(tmax[m]) ? kmax : fbits(tmax[m]); }
                 const bool quick = __all(!act || (kmin >= 0x0f800000u - 1u && kmax <= kQuickHi));
                 float ssig, snse;
-                // (the receiver's defined summation order IS this kernel's wave reduction: ldpc_kernels.hip sums with the same wave_sum)
+                // (the receiver's defined summation order IS this kernel's wave reduction: ldpc_stages.hip sums with the same wave_sum)
                 if (quick) {
 #pragma unroll
                     for (int m = 0; m < M; m++) { mag[m] = sqrt_rn_normal<FMT != PIRIP_IN_CF32>(tmax[m]); const float p2 = mag[m] * mag[m]; sum2 = sum2 + p2; mx2 = p2 > mx2 ? p2 : mx2; }

@@ -46,7 +46,7 @@ struct DemodState {
     float2 *phic;               // [nstreams][kMaxTones] the exact kernel's carried oscillators phi_c (0, 0 = created state); nullptr elsewhere
 };
 
-// Fused FSK_LDPC hand-over (ldpc_kernels.hip): instead of soft magnitudes the demodulator writes, per frame, the
+// Fused FSK_LDPC hand-over (ldpc_rx.hip): instead of soft magnitudes the demodulator writes, per frame, the
 // Nbits bit log-likelihood ratios and their hard decisions packed 32 per word (first bit in the MSB) straight into the LDPC
 // receiver's work buffers -- the magnitudes never travel through HBM.
 struct SoftOut {
@@ -61,7 +61,7 @@ struct SoftOut {
 // piecewise-quadratic fit of ln I0]: metric = logbesseli0(2 * SNRest * |r| / v_est). Here the frame's factor k = (2 * SNRest) / v_est is
 // formed once and the argument is k * |r| (upstream forms sqrt(r^2 / v_est^2) per value: the same number up to the last float bits,
 // far below the binary16 rounding of the soft bits); the polynomial in float32, every product and sum rounded once, in this order --
-// the LLR stage (ldpc_kernels.hip), the demodulator's fused hand-over (fsk_demod_wave.hip) and the checker restate exactly this.
+// the LLR stage (ldpc_stages.hip), the demodulator's fused hand-over (fsk_demod_wave.hip) and the checker restate exactly this.
 constexpr int kLlrUpstream = 0, kLlrRician = 1;
 constexpr float kLlrMaxUpstream = 1000.0f;  // keeps the binary16 soft bits finite when v_est is tiny (any |LLR| >= 32 saturates the decoder)
 __device__ __forceinline__ float logbesseli0_upstream(float x)
@@ -135,11 +135,18 @@ struct DemodArgs {
 int demod_batch_seg(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp, uint8_t *d_bits, size_t bits_stride,
                     float *d_rx_filt, size_t filt_stride, float *d_stats, size_t stats_stride, int32_t *d_nframes, int64_t *d_consumed,
                     int64_t max_frames, const SegDesc *seg, hipStream_t st);
-// pirip_hip_fsk_ldpc_rx_batch with per-stream segment descriptors (ldpc_kernels.hip)
+// pirip_hip_fsk_ldpc_rx_batch with per-stream segment descriptors (ldpc_rx.hip)
 int fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp,
                           uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, float *d_stats, size_t stats_stride,
                           int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, const SegDesc *seg, hipStream_t st);
-int ldpc_handle_shape(const pirip_hip_ldpc *h, int *M, int *Nsym, int *nstreams, int *device);   // (ldpc_kernels.hip)
+int ldpc_handle_shape(const pirip_hip_ldpc *h, int *M, int *Nsym, int *nstreams, int *device);   // (ldpc_rx.hip)
+// pirip_capi.hip: the demodulator's side of the fused hand-over
+int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp, const SoftOut &so, float *d_stats, size_t stats_stride,
+                     int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, hipStream_t st, int s0 = 0, int n = -1,
+                     const SegDesc *seg = nullptr);
+int demod_handle_shape(const pirip_hip_demod *h, int *M, int *Nsym, int *nstreams, int *device);
+int demod_streams_per_cu(const pirip_hip_demod *h);                     // streams of the handle's wave instance that one CU holds at a time (0: another kernel)
+bool demod_soft_capable(const pirip_hip_demod *h, int64_t nsamp);      // the handle's kernel instance can write the fused hand-over for calls of nsamp samples
 
 // launchers (fsk_demod_kernels.hip)
 size_t demod_general_lds_bytes(const FskDims &d);

@@ -383,7 +383,7 @@ int demod_batch_seg(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes
     return PIRIP_OK;
 }
 
-// internal (ldpc_kernels.hip): one batch with the fused FSK_LDPC hand-over instead of bits / magnitudes
+// internal (ldpc_rx.hip): one batch with the fused FSK_LDPC hand-over instead of bits / magnitudes
 // s0 / n (n < 0: all): streams [s0, s0 + n) of the handle only -- every per-stream array of the argument block is advanced to stream s0, the
 // pointers the caller passes are those of stream 0 (pirip_hip_fsk_ldpc_rx_batch runs two ranges on two HIP streams)
 int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp, const SoftOut &so, float *d_stats, size_t stats_stride,

@@ -421,12 +421,13 @@ def _write_random_code(path, n, k, wcol, seed, max_iter=15):
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("decoder", DECODERS)
-@pytest.mark.parametrize("n,k,wcol", [(200, 104, 3), (136, 104, 3)])
+@pytest.mark.parametrize("n,k,wcol", [(200, 104, 3), (136, 104, 3), (600, 296, 3)])
 def test_other_code_shapes_take_the_generic_paths(oracle, built_lib, tmp_path, monkeypatch, n, k, wcol, decoder):
     """Nothing in the receiver is specific to the (512,256) stand-in: a (200,104) code whose two-frame window is not a whole
     number of 32-bit words (the hard-decision words then come from their own kernel) and a (136,104) code with check rows of
     degree > 8 (the decoder's two-pass check loop) give the oracle's records, payloads and info columns, through chunked
-    single-stream calls."""
+    single-stream calls. A (600,296) code has more check rows (304) than the generic decoder keeps in registers and none of
+    weight > 8: its check pass reads the rows' edge lists from LDS; it has no fast layout, so both decoder settings reach it."""
     import pirip_amd
     monkeypatch.setenv("PIRIP_LDPC_DECODER", decoder)       # ((200,104): row weight 7-8, the decoders' wider build; (136,104) fits neither fast one)
     path = str(tmp_path / "test.code")

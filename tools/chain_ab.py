@@ -92,8 +92,10 @@ def main():
             env.update(kv.split("=", 1) for kv in extra.split(",") if "=" in kv)
             r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", ebnos], env=env, capture_output=True, text=True)
             ln = [l for l in r.stdout.splitlines() if l.startswith("ABCHAIN ")]
-            if not ln:
-                print(tag, "failed", r.stderr[-600:]); continue
+            if r.returncode != 0 or not ln:
+                # nothing more is started on the GPU after a child that failed: it may have left the device in a bad state
+                print(tag, f"failed (exit status {r.returncode}), stopping", r.stderr[-600:])
+                sys.exit(1)
             d = json.loads(ln[0][8:])
             print(f"{tag} {os.path.basename(os.path.dirname(lib)) + (' ' + extra if extra else ''):8s} " + "   ".join(
                 f"{e} dB: chain {v['chain_ms']:6.2f} ms ({v['G']:5.1f} G) rx_batch {v['ldpc_rx_batch_ms']:5.2f} ms ok {v['frames_ok']} it {v['mean_it']:.2f} rec {v['records']}"
