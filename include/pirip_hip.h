@@ -18,6 +18,8 @@
  *   section H  channelizer (pirip_hip_chan_*)              : K channels out of W wideband u8 IQ
  *              captures (shift_addition_cc | fir_decimate_cc D per channel), one pass over
  *              the input; also the front end of a section G receiver.
+ *   section I  FSK_LDPC transmit (pirip_hip_tx_*)           : rpitx_fsk --code's record protocol ->
+ *              channel symbols -> continuous-phase M-FSK IQ for a batch of streams.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -469,6 +471,76 @@ int pirip_hip_chan_batch(pirip_hip_chan *ch, const uint8_t *d_in, size_t in_stri
  * block; the receiver tracks t0 on the host (no synchronisation). pirip_hip_rx_input / _push / _process / _get_counters / _reset then
  * work as documented above with ninputs input rows (push copies ninputs rows); _reset also restarts t0 at 0. */
 int pirip_hip_rx_create_chan(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_chan *chan, int64_t block, pirip_hip_rx **out);
+
+/* ----------------------------------------------------------------------------------- */
+/* section I : FSK_LDPC transmit (records -> channel symbols -> IQ, a batch of streams)  */
+/*   The Tx half of section E: what `rpitx_fsk --code NAME --packed` does to its stdin    */
+/*   (/root/reference/tx/rpitx_fsk.cpp:427-509) up to the modulator, and a continuous-    */
+/*   phase M-FSK modulator, as two device stages. Every buffer the stages */
+/*   need is owned by the handle (grown when a call is larger than any before it); the    */
+/*   calls are enqueued on hip_stream (NULL = default stream) and do not synchronise.     */
+/* ----------------------------------------------------------------------------------- */
+#define PIRIP_TX_CARRIER_OFF 0xFF   /* symbol value: nothing is sent for this symbol time, the phase stays where it was */
+typedef struct pirip_hip_tx pirip_hip_tx;
+typedef struct pirip_tx_info {
+    int Fs, Rs, M, Ts, n, k, bits_per_frame, data_bytes, preamble_syms, frame_syms, nstreams, device;
+} pirip_tx_info;
+/* nstreams transmitters of one code file and one modem shape (Fs % Rs == 0, M 2 or 4). PIRIP_ERR_BAD_CONFIG for a code file without the
+ * accumulator (dual-diagonal) parity part -- fsk_ldpc_framer's refusal --, PIRIP_ERR_UNSUPPORTED for Fs > 2^24 or a frame that is not a
+ * whole number of symbols (32 + n odd with M = 4), PIRIP_ERR_BAD_ARG for a file that does not load. Tones, lead and gap start at 0. */
+int pirip_hip_tx_create(const char *code_path, int Fs, int Rs, int M, int nstreams, int device, pirip_hip_tx **out);
+int pirip_hip_tx_destroy(pirip_hip_tx *h);
+int pirip_hip_tx_get_info(const pirip_hip_tx *h, pirip_tx_info *info);
+/* Stream s sends symbol m on f1_hz[s] + m * tone_spacing_hz (host array, integer Hz, negative allowed). Synchronises the device. */
+int pirip_hip_tx_set_tones(pirip_hip_tx *h, const int32_t *f1_hz, int tone_spacing_hz);
+/* Carrier-off symbols of stream s in front of its first record (lead_syms[s]) and for each of its `2` records (gap_syms[s]: the framer
+ * tool's --gap, in symbols). Host arrays, NULL = zeros. Synchronises the device. */
+int pirip_hip_tx_set_gaps(pirip_hip_tx *h, const int32_t *lead_syms, const int32_t *gap_syms);
+/* Phase and sample count (the noise key) of every stream back to zero: the next pirip_hip_tx_modulate is the first after create. */
+int pirip_hip_tx_reset(pirip_hip_tx *h, void *hip_stream);
+/* symbols a row of max_rec records can need with the handle's lead / gap: the capacity pirip_hip_tx_frame asks of its rows */
+int64_t pirip_hip_tx_max_syms(const pirip_hip_tx *h, int max_rec);
+/* Stage 1. Stream s: d_nrec[s] (NULL = max_rec; clamped to [0, max_rec]) records at d_records + s * rec_stride, each one burst-control
+ * byte + k/8 packed data bytes: 1 = preamble then a frame, 0 = a frame, 2 = end of burst (its data ignored, gap symbols of carrier off),
+ * any other value sends nothing. A frame is UW | data | parity with the last 16 data bits replaced by the CRC16 of the packed bytes
+ * before them, bit for bit fsk_ldpc_framer --packed (CPU: fsk_ldpc.cpp). Writes one symbol per byte (0 .. M-1, bit pairs MSB first for
+ * M = 4, PIRIP_TX_CARRIER_OFF over lead and gaps) to d_syms + s * sym_stride and the symbol count to d_nsym[s] (may be NULL); with d_bits
+ * also the frame bits one per byte at d_bits + s * bits_stride (nsym * log2(M) of them, zeros where the carrier is off: the framer
+ * tool's output). Rows hold max_syms >= pirip_hip_tx_max_syms(h, max_rec) symbols, else PIRIP_ERR_BAD_ARG. */
+int pirip_hip_tx_frame(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_stride, const int32_t *d_nrec, int max_rec,
+                       uint8_t *d_syms, size_t sym_stride, int64_t max_syms, int32_t *d_nsym, uint8_t *d_bits, size_t bits_stride,
+                       void *hip_stream);
+/* Stage 2. Every stream sends nsym symbol times = nsym * Ts samples: the symbols at d_syms + s * sym_stride, those from d_nsym[s] on
+ * (NULL = none) carrier off. Sample r of symbol i is x = 2 e^{j 2 pi p / Fs} with the exact integer p = (A_i + (r + 1) f_i) mod Fs,
+ * A_i = (phase carried in + Ts * sum_{q<i} f_q) mod Fs, f the symbol's tone; carrier off gives x = 0 and moves no phase. sigma > 0 adds
+ * sigma * N(0,1) per component from pirip_hip_synth_cu8's generator, keyed by (seed, stream, samples sent since create / reset).
+ * out_format PIRIP_IN_CU8_FSKDEMOD: u8 IQ, clamp(rintf(127 + amp * x)); PIRIP_IN_CF32: complex float x (amp unused). Row s at
+ * (char*)d_out + s * out_stride_bytes, aligned to the sample (16-byte aligned rows get 16-byte stores). The handle carries each stream's
+ * phase and the sample count: a row sent in several calls gives the bytes of one call. Numerics: DESIGN.md 4.9 (every component within
+ * 1e-6 of the formula in float64). nsym * Ts < 2^31. */
+int pirip_hip_tx_modulate(pirip_hip_tx *h, const uint8_t *d_syms, size_t sym_stride, const int32_t *d_nsym, int64_t nsym,
+                          int out_format, void *d_out, size_t out_stride_bytes, float amp, float sigma, uint64_t seed, void *hip_stream);
+/* Both stages over the handle's own symbol rows: records in, nsym symbol times of IQ out per stream (carrier off behind a stream's last
+ * record; a row that needs more than nsym symbols is cut there). d_nsym (may be NULL): the symbols each stream's records made. */
+int pirip_hip_tx_records_to_iq(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_stride, const int32_t *d_nrec, int max_rec,
+                               int64_t nsym, int out_format, void *d_out, size_t out_stride_bytes, float amp, float sigma, uint64_t seed,
+                               int32_t *d_nsym, void *hip_stream);
+
+/* The repeater's record conversion (tx/frame_repeater.c:68-107 without its sleeps and logging), on the device, one wave per stream: the
+ * records pirip_hip_fsk_ldpc_rx_batch wrote for stream s -- d_ncalls[s] (NULL = ncalls) status bytes at d_status + s * status_stride and
+ * payloads of k/8 bytes at d_payload + s * payload_stride -- become Tx records at d_records + s * rec_stride, their count in d_nrec[s]. A
+ * burst starts at a record whose status is exactly SYNC | BITS, takes every later record with BITS, and ends at the first record without
+ * SYNC: only then are its frames written, burst control 1, 0, ... and byte 0 replaced by source_byte, followed by one `2` record of zeros.
+ * Frames of a burst that has not ended wait in the handle (at most PIRIP_TX_REPEAT_MAX_FRAMES per burst, the original's MAX_FRAMES; further
+ * frames of that burst are dropped where the original asserts) and come out in the call in which it ends; pirip_hip_tx_reset forgets them.
+ * Rows hold max_rec >= pirip_hip_tx_repeat_max_records(h, ncalls) records, else PIRIP_ERR_BAD_ARG; ncalls <= 4096. */
+#define PIRIP_TX_REPEAT_MAX_FRAMES 100
+int pirip_hip_tx_repeat_max_records(const pirip_hip_tx *h, int ncalls);
+int pirip_hip_tx_repeat_records(pirip_hip_tx *h, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                                const int32_t *d_ncalls, int ncalls, int source_byte, uint8_t *d_records, size_t rec_stride, int max_rec,
+                                int32_t *d_nrec, void *hip_stream);
+/* One HIP stream per handle: the phase, the repeater's state and the work buffers are device state advanced in stream order, the sample
+ * count of the noise key is host state advanced when a call is enqueued. Calls on one handle from several streams must be ordered by the caller. */
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

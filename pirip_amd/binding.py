@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G and H).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H and I).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -38,6 +38,11 @@ class CaptureReport(C.Structure):
 
 class ChanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("Fs", "D", "ntaps", "ntaps_padded", "ninputs", "nchan", "out_s16", "device")]
+
+
+class TxInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("Fs", "Rs", "M", "Ts", "n", "k", "bits_per_frame", "data_bytes", "preamble_syms", "frame_syms",
+                                       "nstreams", "device")]
 
 
 class LdpcInfo(C.Structure):
@@ -136,6 +141,19 @@ def lib():
     L.pirip_hip_chan_nout.restype = i64
     L.pirip_hip_chan_nout.argtypes = [vp, i64]
     L.pirip_hip_chan_batch.argtypes = [vp, vp, sz, i64, i64, vp, sz, vp]
+    L.pirip_hip_tx_create.argtypes = [C.c_char_p, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    L.pirip_hip_tx_destroy.argtypes = [vp]
+    L.pirip_hip_tx_get_info.argtypes = [vp, C.POINTER(TxInfo)]
+    L.pirip_hip_tx_set_tones.argtypes = [vp, vp, i32]
+    L.pirip_hip_tx_set_gaps.argtypes = [vp, vp, vp]
+    L.pirip_hip_tx_reset.argtypes = [vp, vp]
+    L.pirip_hip_tx_max_syms.restype = i64
+    L.pirip_hip_tx_max_syms.argtypes = [vp, i32]
+    L.pirip_hip_tx_frame.argtypes = [vp, vp, sz, vp, i32, vp, sz, i64, vp, vp, sz, vp]
+    L.pirip_hip_tx_modulate.argtypes = [vp, vp, sz, vp, i64, i32, vp, sz, C.c_float, C.c_float, C.c_uint64, vp]
+    L.pirip_hip_tx_records_to_iq.argtypes = [vp, vp, sz, vp, i32, i64, i32, vp, sz, C.c_float, C.c_float, C.c_uint64, vp, vp]
+    L.pirip_hip_tx_repeat_max_records.argtypes = [vp, i32]
+    L.pirip_hip_tx_repeat_records.argtypes = [vp, vp, sz, vp, sz, vp, i32, i32, vp, sz, i32, vp, vp]
     _lib = L
     return L
 
@@ -398,6 +416,87 @@ class HipChan:
         """capture i at d_in + i * in_stride (n_in u8 IQ samples, the first at absolute index t0) -> channel c at d_out + c * out_stride
         (nout(n_in) samples); raw device pointers, enqueued on `stream`, does not synchronise"""
         _chk(self.L.pirip_hip_chan_batch(self.h, d_in, in_stride, int(n_in), int(t0), d_out, out_stride, stream), "pirip_hip_chan_batch")
+
+
+TX_CARRIER_OFF = 0xFF
+
+
+class HipTx:
+    """nstreams FSK_LDPC transmitters (include/pirip_hip.h section I): records of rpitx_fsk --code's stdin protocol -> channel symbols ->
+    continuous-phase M-FSK IQ. f1: one first-tone frequency for all streams or one per stream (Hz); lead / gap: carrier-off symbols in
+    front of a stream's first record and for each of its `2` records (scalars or one per stream)."""
+
+    def __init__(self, code_path, Fs, Rs, M, nstreams=1, f1=None, shift=None, lead=0, gap=0, device=-1):
+        self.L = lib()
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_tx_create(code_path.encode(), int(Fs), int(Rs), int(M), int(nstreams), device, C.byref(h)), "pirip_hip_tx_create")
+        self.h = h
+        self.info = TxInfo()
+        _chk(self.L.pirip_hip_tx_get_info(self.h, C.byref(self.info)), "pirip_hip_tx_get_info")
+        self.Fs, self.Rs, self.M, self.Ts, self.nstreams = int(Fs), int(Rs), int(M), self.info.Ts, int(nstreams)
+        self.k, self.data_bytes, self.record_bytes = self.info.k, self.info.data_bytes, 1 + self.info.data_bytes
+        self.bits_per_frame, self.frame_syms, self.preamble_syms = self.info.bits_per_frame, self.info.frame_syms, self.info.preamble_syms
+        self.bps = 1 if M == 2 else 2
+        if f1 is not None:
+            self.set_tones(f1, shift if shift is not None else Rs)
+        self.set_gaps(lead, gap)
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_tx_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def _per_stream(self, v):
+        import numpy as np
+        a = np.ascontiguousarray(v, dtype=np.int32).reshape(-1)
+        if a.size == 1:
+            a = np.full(self.nstreams, int(a[0]), dtype=np.int32)
+        if a.size != self.nstreams:
+            raise ValueError("one value, or one per stream")
+        return a
+
+    def set_tones(self, f1, shift):
+        a = self._per_stream(f1)
+        _chk(self.L.pirip_hip_tx_set_tones(self.h, a.ctypes.data, int(shift)), "pirip_hip_tx_set_tones")
+
+    def set_gaps(self, lead=0, gap=0):
+        a, b = self._per_stream(lead), self._per_stream(gap)
+        _chk(self.L.pirip_hip_tx_set_gaps(self.h, a.ctypes.data, b.ctypes.data), "pirip_hip_tx_set_gaps")
+
+    def reset(self, stream=0):
+        _chk(self.L.pirip_hip_tx_reset(self.h, stream), "pirip_hip_tx_reset")
+
+    def max_syms(self, max_rec):
+        return int(self.L.pirip_hip_tx_max_syms(self.h, int(max_rec)))
+
+    def frame(self, d_records, rec_stride, max_rec, d_syms, sym_stride, max_syms, d_nrec=0, d_nsym=0, d_bits=0, bits_stride=0, stream=0):
+        """records -> symbol rows (and the framer's bits); raw device pointers, enqueued on `stream`, does not synchronise"""
+        _chk(self.L.pirip_hip_tx_frame(self.h, d_records, rec_stride, d_nrec, int(max_rec), d_syms, sym_stride, int(max_syms), d_nsym,
+                                       d_bits, bits_stride, stream), "pirip_hip_tx_frame")
+
+    def modulate(self, d_syms, sym_stride, nsym, d_out, out_stride, out_format=IN_CU8_FSKDEMOD, d_nsym=0, amp=32.0, sigma=0.0, seed=1,
+                 stream=0):
+        """nsym symbol times (nsym * Ts samples) per stream -> IQ rows; continues where the previous call stopped"""
+        _chk(self.L.pirip_hip_tx_modulate(self.h, d_syms, sym_stride, d_nsym, int(nsym), out_format, d_out, out_stride, amp, sigma, seed,
+                                          stream), "pirip_hip_tx_modulate")
+
+    def repeat_max_records(self, ncalls):
+        return int(self.L.pirip_hip_tx_repeat_max_records(self.h, int(ncalls)))
+
+    def repeat_records(self, d_status, status_stride, d_payload, payload_stride, ncalls, source_byte, d_records, rec_stride, max_rec,
+                       d_ncalls=0, d_nrec=0, stream=0):
+        """receiver records (HipLdpc.chain_batch's status / payload rows) -> Tx records by frame_repeater's state machine, on the device;
+        a burst still being received waits in the handle for the call in which it ends"""
+        _chk(self.L.pirip_hip_tx_repeat_records(self.h, d_status, status_stride, d_payload, payload_stride, d_ncalls, int(ncalls),
+                                                int(source_byte), d_records, rec_stride, int(max_rec), d_nrec, stream),
+             "pirip_hip_tx_repeat_records")
+
+    def records_to_iq(self, d_records, rec_stride, max_rec, nsym, d_out, out_stride, out_format=IN_CU8_FSKDEMOD, d_nrec=0, d_nsym=0,
+                      amp=32.0, sigma=0.0, seed=1, stream=0):
+        _chk(self.L.pirip_hip_tx_records_to_iq(self.h, d_records, rec_stride, d_nrec, int(max_rec), int(nsym), out_format, d_out, out_stride,
+                                               amp, sigma, seed, d_nsym, stream), "pirip_hip_tx_records_to_iq")
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

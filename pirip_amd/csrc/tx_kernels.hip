@@ -1,0 +1,708 @@
+// pirip_amd/csrc/tx_kernels.hip -- include/pirip_hip.h section I: the batch FSK_LDPC transmitter.
+//
+//   records (rpitx_fsk --code's stdin protocol)  --frame-->  channel symbols  --modulate-->  IQ (u8 or complex float)
+//
+// Stage 1, the framer: what fsk_ldpc_framer --packed does to a record stream, for every stream of the batch. A record is one burst-control
+// byte and k/8 packed data bytes (1: preamble + frame, 0: frame, 2: carrier off for the stream's gap, nothing sent). tx_layout_kernel
+// (one wave per stream) turns the control bytes into each record's place in the symbol row by a wave prefix sum; tx_frame_kernel
+// (one wave per (stream, record)) forms UW | data + CRC16 | parity in LDS and writes symbols (and, on request, the framer's bits).
+// The arithmetic is fsk_ldpc.cpp's: crc16_ccitt over the k/8 - 2 packed bytes (one lane: 30 bytes for the (512,256) code), and
+// LdpcCode::encode -- parity[p] = parity[p-1] ^ (XOR of row p's data columns). Lane l forms the data-column XOR of rows 64c + l from the
+// CSR; the running XOR across rows is then a prefix XOR inside the wave: one ballot per 64 rows, each lane takes the popcount parity of
+// the lanes at or below it, and the carry into the next 64 rows is the ballot's own parity. No LDS round trip per row.
+//
+// Stage 2, the modulator: continuous-phase M-FSK, parallel in the samples. With f_i the tone of symbol i in Hz (an integer mod Fs) the
+// phase after sample r of symbol i is 2 pi p / Fs with the exact integer
+//     p = (A_i + (r + 1) f_i) mod Fs,      A_i = (phase carried in + Ts * sum_{q < i} f_q) mod Fs
+// (the advance comes before the output, as in fsk_mod_c: the first sample is one step in). tx_prefix_kernel (one workgroup per stream)
+// forms A_i by an exclusive scan of (Ts f_q mod Fs) in wave and across waves, in 32-bit integers, and leaves the row's final phase in
+// the handle; tx_mod_kernel gives each lane one 16-byte unit of output (8 u8 samples or 2 complex floats): one exact (r + 1) f mod Fs
+// in double, then p += f (mod Fs) from sample to sample, x = 2 (cospi, sinpi)(2p/Fs). Carrier-off symbols (0xFF) add nothing to the
+// phase and give x = 0. No float recursion: a sample is a function of the symbols before it and of nothing else, so a row sent in one
+// call or in several gives the same bytes. Optional AWGN is synth_kernels.hip's counter generator with its key (seed, stream, sample).
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <string>
+#include <vector>
+
+#include "../../include/pirip_hip.h"
+#include "fsk_ldpc.hpp"
+
+using namespace pirip;
+
+namespace {
+
+constexpr int kMaxFs = 1 << 24;            // p, f < 2^24: exact in float and in the 32-bit sums below
+constexpr int kFrameWaves = 4;             // records per workgroup of the framer
+constexpr int kScanThreads = 256;
+constexpr int kModThreads = 256;
+constexpr uint8_t kOff = 0xFF;             // carrier off
+
+struct FrameArgs {
+    const uint8_t *rec; size_t rec_stride; const int32_t *nrec; int max_rec;
+    int32_t *off;                          // [nstreams][max_rec] first symbol of each record
+    uint8_t *syms; size_t sym_stride; int64_t max_syms; int32_t *nsym;
+    uint8_t *bits; size_t bits_stride;     // optional: one bit per byte, zeros over the gaps (fsk_ldpc_framer's output)
+    const int32_t *row_ptr, *col_idx;      // CSR of H
+    const int32_t *lead, *gap;             // [nstreams] carrier-off symbols in front of the first burst / for every `2` record
+    uint32_t uw;                           // unique word, first bit in bit 31
+    int k, m, kb, bpf, bps, pre_bits, nstreams, wave_lds, frame_lds;
+};
+
+__device__ __forceinline__ int rec_count(const FrameArgs &a, int s)
+{
+    int n = a.nrec ? a.nrec[s] : a.max_rec;
+    return n < 0 ? 0 : (n > a.max_rec ? a.max_rec : n);
+}
+
+// carrier off over symbols [from, from + n) of stream s, clipped to the row
+__device__ __forceinline__ void write_off(const FrameArgs &a, int s, int64_t from, int64_t n, int lane)
+{
+    uint8_t *sy = a.syms + (size_t)s * a.sym_stride;
+    for (int64_t i = from + lane; i < from + n && i < a.max_syms; i += 64) sy[i] = kOff;
+    if (a.bits) {
+        uint8_t *b = a.bits + (size_t)s * a.bits_stride;
+        const int64_t b0 = from * a.bps, b1 = (from + n) * a.bps, bmax = a.max_syms * a.bps;
+        for (int64_t i = b0 + lane; i < b1 && i < bmax; i += 64) b[i] = 0;
+    }
+}
+
+__global__ __launch_bounds__(64) void tx_layout_kernel(FrameArgs a)
+{
+    const int s = blockIdx.x, lane = threadIdx.x;
+    const int nrec = rec_count(a, s);
+    const int lead = a.lead[s] > 0 ? a.lead[s] : 0, gap = a.gap[s] > 0 ? a.gap[s] : 0;
+    const int fsyms = a.bpf / a.bps, psyms = a.pre_bits / a.bps;
+    write_off(a, s, 0, lead, lane);
+    const uint8_t *rec = a.rec + (size_t)s * a.rec_stride;
+    int64_t carry = lead;
+    for (int base = 0; base < nrec; base += 64) {
+        const int r = base + lane;
+        int len = 0;
+        if (r < nrec) {
+            const uint8_t ctl = rec[(size_t)r * (size_t)(1 + a.kb)];
+            len = ctl == 1 ? psyms + fsyms : ctl == 0 ? fsyms : ctl == 2 ? gap : 0;
+        }
+        int64_t incl = len;
+        for (int d = 1; d < 64; d <<= 1) {
+            const int64_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        const int64_t o = carry + incl - len;
+        if (r < nrec) a.off[(size_t)s * a.max_rec + r] = (int32_t)(o < a.max_syms ? o : a.max_syms);
+        carry += __shfl(incl, 63, 64);
+    }
+    if (lane == 0 && a.nsym) a.nsym[s] = (int32_t)(carry < a.max_syms ? carry : a.max_syms);
+}
+
+__device__ __forceinline__ uint16_t crc16_step(uint16_t crc, uint8_t byte)   // fsk_ldpc.cpp: crc16_ccitt
+{
+    uint8_t x = (uint8_t)((uint8_t)(crc >> 8) ^ byte);
+    x ^= x >> 4;
+    return (uint16_t)((crc << 8) ^ ((uint16_t)x << 12) ^ ((uint16_t)x << 5) ^ (uint16_t)x);
+}
+
+// bits [0, nbits) at `src` (one per byte, LDS or generated) -> symbols from `sym0` on and bits from sym0 * bps on, clipped to the row
+template <typename F>
+__device__ __forceinline__ void emit(const FrameArgs &a, int s, int64_t sym0, int nbits, int lane, F bit)
+{
+    uint8_t *sy = a.syms + (size_t)s * a.sym_stride;
+    const int ns = nbits / a.bps;
+    for (int i = lane; i < ns && sym0 + i < a.max_syms; i += 64)
+        sy[sym0 + i] = a.bps == 1 ? bit(i) : (uint8_t)((bit(2 * i) << 1) | bit(2 * i + 1));
+    if (a.bits) {
+        uint8_t *b = a.bits + (size_t)s * a.bits_stride;
+        const int64_t b0 = sym0 * a.bps, bmax = a.max_syms * a.bps;
+        for (int i = lane; i < nbits && b0 + i < bmax; i += 64) b[b0 + i] = bit(i);
+    }
+}
+
+__global__ __launch_bounds__(kFrameWaves * 64) void tx_frame_kernel(FrameArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int s = blockIdx.y, r = blockIdx.x * kFrameWaves + wave;
+    uint8_t *s_frame = smem + (size_t)wave * a.wave_lds;    // [bpf] UW | data | parity, one bit per byte
+    uint8_t *s_bytes = s_frame + a.frame_lds;               // [kb] the record's packed data
+    const bool live = r < rec_count(a, s);
+    const uint8_t *rec = a.rec + (size_t)s * a.rec_stride + (size_t)(live ? r : 0) * (size_t)(1 + a.kb);
+    const uint8_t ctl = live ? rec[0] : 3;
+    const bool frame = ctl == 0 || ctl == 1;
+    if (frame) for (int i = lane; i < a.kb; i += 64) s_bytes[i] = rec[1 + i];
+    __syncthreads();
+    if (frame && lane == 0) {                               // insert_crc: the last 16 data bits are the CRC16 of the bytes before them
+        uint16_t crc = 0xFFFF;
+        for (int i = 0; i < a.kb - 2; i++) crc = crc16_step(crc, s_bytes[i]);
+        s_bytes[a.kb - 2] = (uint8_t)(crc >> 8);
+        s_bytes[a.kb - 1] = (uint8_t)(crc & 0xff);
+    }
+    __syncthreads();
+    if (frame)
+        for (int i = lane; i < kUwBits + a.k; i += 64)
+            s_frame[i] = i < kUwBits ? (uint8_t)((a.uw >> (31 - i)) & 1u)
+                                     : (uint8_t)((s_bytes[(i - kUwBits) >> 3] >> (7 - ((i - kUwBits) & 7))) & 1);
+    __syncthreads();
+    if (frame) {                                            // LdpcCode::encode
+        const uint8_t *data = s_frame + kUwBits;
+        uint8_t *par = s_frame + kUwBits + a.k;
+        unsigned carry = 0;
+        for (int base = 0; base < a.m; base += 64) {
+            const int p = base + lane;
+            unsigned d = 0;
+            if (p < a.m)
+                for (int e = a.row_ptr[p]; e < a.row_ptr[p + 1]; e++) {
+                    const int c = a.col_idx[e];
+                    if (c < a.k) d ^= data[c];
+                }
+            const unsigned long long mask = __ballot(d & 1u);
+            const unsigned long long below = lane == 63 ? mask : (mask & ((2ull << lane) - 1ull));
+            if (p < a.m) par[p] = (uint8_t)((carry ^ (unsigned)__popcll(below)) & 1u);
+            carry ^= (unsigned)__popcll(mask) & 1u;
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const int64_t o = a.off[(size_t)s * a.max_rec + r];
+    if (ctl == 2) {
+        write_off(a, s, o, a.gap[s] > 0 ? a.gap[s] : 0, lane);
+    } else if (frame) {
+        int64_t at = o;
+        if (ctl == 1) {                                     // preamble_bits(M): symbols 0, 1, 2, 3, 0, ... two bits each
+            emit(a, s, at, a.pre_bits, lane, [](int i) { const int sym = i >> 1; return (uint8_t)((i & 1) ? (sym & 1) : ((sym >> 1) & 1)); });
+            at += a.pre_bits / a.bps;
+        }
+        emit(a, s, at, a.bpf, lane, [&](int i) { return s_frame[i]; });
+    }
+}
+
+// ---------------------------------------------------------------- modulator
+
+struct ModArgs {
+    const uint8_t *syms; size_t sym_stride; const int32_t *nsym;
+    int64_t total;                         // symbols sent per stream in this call (symbols from nsym[s] on are carrier off)
+    uint32_t *prefix;                      // [nstreams][total] A_i
+    uint32_t *phase;                       // [nstreams] phase integer carried from call to call
+    const uint32_t *fm, *tm;               // [nstreams][4] tone m mod Fs, (Ts * tone m) mod Fs
+    void *out; size_t out_stride;
+    int64_t n0;                            // samples sent per stream before this call (the noise key)
+    int Fs, Ts, M, nstreams, aligned16;
+    float two_over_fs, amp, sigma;
+    double inv_fs_d;
+    uint64_t seed;
+};
+
+__device__ __forceinline__ int sym_at(const ModArgs &a, const uint8_t *sy, int valid, int64_t i)
+{
+    const int v = i < valid ? sy[i] : kOff;
+    return v < a.M ? v : -1;               // -1: carrier off
+}
+
+__global__ __launch_bounds__(kScanThreads) void tx_prefix_kernel(ModArgs a)
+{
+    __shared__ uint32_t s_tot[kScanThreads / 64];
+    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const uint8_t *sy = a.syms + (size_t)s * a.sym_stride;
+    int64_t valid = a.nsym ? a.nsym[s] : a.total;
+    if (valid > a.total) valid = a.total;
+    const uint32_t Fs = (uint32_t)a.Fs;
+    uint32_t tm[4];
+    for (int m = 0; m < 4; m++) tm[m] = a.tm[(size_t)s * 4 + m];
+    uint32_t carry = a.phase[s];
+    uint32_t *pre = a.prefix + (size_t)s * (size_t)a.total;
+    for (int64_t base = 0; base < a.total; base += kScanThreads) {
+        const int64_t i = base + tid;
+        const int sym = i < a.total ? sym_at(a, sy, (int)valid, i) : -1;
+        const uint32_t v = sym < 0 ? 0u : tm[sym];
+        uint32_t incl = v;                                   // < 64 * 2^24
+        for (int d = 1; d < 64; d <<= 1) {
+            const uint32_t up = __shfl_up(incl, d, 64);
+            if (lane >= d) incl += up;
+        }
+        if (lane == 63) s_tot[wave] = incl % Fs;
+        __syncthreads();
+        uint32_t before = carry, all = carry;                // carry + the waves in front: < 5 * 2^24
+        for (int w = 0; w < kScanThreads / 64; w++) { if (w < wave) before += s_tot[w]; all += s_tot[w]; }
+        if (i < a.total) pre[i] = (before + (incl - v)) % Fs;
+        carry = all % Fs;
+        __syncthreads();
+    }
+    if (tid == 0) a.phase[s] = carry;
+}
+
+__device__ __forceinline__ uint64_t splitmix(uint64_t z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+// (a b) mod Fs for 0 <= a, b <= 2^24: the product is exact in double, the quotient right or one off, the remainder exact
+__device__ __forceinline__ uint32_t mulmod(uint32_t x, uint32_t y, int Fs, double inv_fs)
+{
+    const double p = (double)x * (double)y;
+    const double q = floor(p * inv_fs);
+    double r = fma(-q, (double)Fs, p);
+    if (r < 0.0) r += (double)Fs;
+    if (r >= (double)Fs) r -= (double)Fs;
+    return (uint32_t)r;
+}
+
+// One sample: x = 2 e^{j 2 pi p / Fs} (0 when the carrier is off), plus the noise of (stream, absolute sample)
+__device__ __forceinline__ float2 sample(const ModArgs &a, bool on, uint32_t p, int s, int64_t nabs)
+{
+    float xr = 0.f, xi = 0.f;
+    if (on) {
+        int32_t pc = (int32_t)p;
+        if (2 * pc > a.Fs) pc -= a.Fs;                       // the angle as a fraction of pi in (-1, 1]
+        float sn, cs;
+        sincospif((float)pc * a.two_over_fs, &sn, &cs);
+        xr = 2 * cs; xi = 2 * sn;
+    }
+    if (a.sigma > 0.f) {                                    // synth_kernels.hip's generator and key
+        const uint64_t r = splitmix(a.seed ^ splitmix(((uint64_t)s << 40) ^ (uint64_t)nabs));
+        const float u1 = ((float)(uint32_t)(r >> 40) + 1.0f) * (1.0f / 16777216.0f);     // (0,1]
+        const float u2 = (float)(uint32_t)((r >> 8) & 0xffffffu) * (1.0f / 16777216.0f); // [0,1)
+        const float mag = a.sigma * sqrtf(-2.0f * logf(u1));
+        float sn, cs;
+        sincosf(6.2831853071795865f * u2, &sn, &cs);
+        xr += mag * cs; xi += mag * sn;
+    }
+    return make_float2(xr, xi);
+}
+
+__device__ __forceinline__ uint32_t quant(float v, float amp)
+{
+    const float q = rintf(127.0f + amp * v);
+    return (uint32_t)fminf(fmaxf(q, 0.f), 255.f);
+}
+
+// SPU samples per 16-byte unit: 8 (u8 IQ) or 2 (complex float)
+template <int SPU>
+__global__ __launch_bounds__(kModThreads) void tx_mod_kernel(ModArgs a)
+{
+    const int s = blockIdx.y + blockIdx.z * 65535;
+    if (s >= a.nstreams) return;
+    const int64_t nsamp = a.total * a.Ts;
+    const int64_t first = ((int64_t)blockIdx.x * kModThreads + threadIdx.x) * SPU;
+    if (first >= nsamp) return;
+    const uint8_t *sy = a.syms + (size_t)s * a.sym_stride;
+    const uint32_t *pre = a.prefix + (size_t)s * (size_t)a.total;
+    int64_t valid = a.nsym ? a.nsym[s] : a.total;
+    if (valid > a.total) valid = a.total;
+    const uint32_t Fs = (uint32_t)a.Fs;
+    int64_t i = first / a.Ts;
+    int r = (int)(first - i * a.Ts);
+    int sym = sym_at(a, sy, (int)valid, i);
+    uint32_t f = sym < 0 ? 0u : a.fm[(size_t)s * 4 + sym];
+    uint32_t p = pre[i] + mulmod((uint32_t)r, f, a.Fs, a.inv_fs_d);     // the phase after r samples of symbol i
+    if (p >= Fs) p -= Fs;
+    float2 x[SPU];
+    const int cnt = (int)(nsamp - first < SPU ? nsamp - first : SPU);
+#pragma unroll
+    for (int j = 0; j < SPU; j++) {
+        if (j < cnt) {
+            if (r == a.Ts) {
+                i++; r = 0;
+                sym = sym_at(a, sy, (int)valid, i);
+                f = sym < 0 ? 0u : a.fm[(size_t)s * 4 + sym];
+                p = pre[i];
+            }
+            p += f;
+            if (p >= Fs) p -= Fs;
+            r++;
+            x[j] = sample(a, sym >= 0, p, s, a.n0 + first + j);
+        } else {
+            x[j] = make_float2(0.f, 0.f);
+        }
+    }
+    char *row = (char *)a.out + (size_t)s * a.out_stride;
+    if (SPU == 8) {
+        uint32_t w[4];
+#pragma unroll
+        for (int q = 0; q < 4; q++)
+            w[q] = quant(x[2 * q].x, a.amp) | (quant(x[2 * q].y, a.amp) << 8) | (quant(x[2 * q + 1].x, a.amp) << 16) | (quant(x[2 * q + 1].y, a.amp) << 24);
+        if (a.aligned16 && cnt == SPU) {
+            *(uint4 *)(row + 2 * first) = make_uint4(w[0], w[1], w[2], w[3]);
+        } else {
+#pragma unroll
+            for (int j = 0; j < SPU; j++) if (j < cnt) *(uint16_t *)(row + 2 * (first + j)) = (uint16_t)(w[j >> 1] >> (16 * (j & 1)));
+        }
+    } else {
+        if (a.aligned16 && cnt == SPU) {
+            *(float4 *)(row + 8 * first) = make_float4(x[0].x, x[0].y, x[SPU - 1].x, x[SPU - 1].y);
+        } else {
+#pragma unroll
+            for (int j = 0; j < SPU; j++) if (j < cnt) *(float2 *)(row + 8 * (first + j)) = x[j];
+        }
+    }
+}
+
+
+// ---------------------------------------------------------------- receiver records -> Tx records (tx/frame_repeater.c:68-107)
+
+struct RepeatArgs {
+    const uint8_t *status; size_t status_stride; const uint8_t *payload; size_t payload_stride; const int32_t *ncalls_s; int ncalls;
+    uint8_t *rec; size_t rec_stride; int max_rec; int32_t *nrec;
+    int32_t *state;                        // [nstreams][2] receiving, frames buffered
+    uint8_t *held;                         // [nstreams][max_burst][kb] the frames of a burst that is still being received
+    int kb, max_burst, source;
+};
+
+// One wave per stream. Lane 0 walks the status bytes (staged in LDS) through the state machine and notes, per call, where its frame goes;
+// the wave then copies the payloads. A burst is written out only when SYNC drops: until then its frames wait in the handle.
+__global__ __launch_bounds__(64) void tx_repeat_kernel(RepeatArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    int32_t *s_act = (int32_t *)smem;                        // [ncalls] -1, or (burst << 16) | slot of the call's frame
+    int32_t *s_base = s_act + a.ncalls;                      // [ncalls + 1] first output record of a burst, -1: still open at the end
+    int32_t *s_n = s_base + a.ncalls + 1;                    // [ncalls + 1] frames of the burst
+    uint8_t *s_st = (uint8_t *)(s_n + a.ncalls + 1);         // [ncalls]
+    __shared__ int32_t s_hdr[4];                             // bursts, records out, receiving, frames held at the end
+    const int s = blockIdx.x, lane = threadIdx.x;
+    int nc = a.ncalls_s ? a.ncalls_s[s] : a.ncalls;
+    nc = nc < 0 ? 0 : (nc > a.ncalls ? a.ncalls : nc);
+    const uint8_t *st = a.status + (size_t)s * a.status_stride;
+    const uint8_t *pl = a.payload + (size_t)s * a.payload_stride;
+    uint8_t *held = a.held + (size_t)s * a.max_burst * a.kb;
+    uint8_t *out = a.rec + (size_t)s * a.rec_stride;
+    const int rl = 1 + a.kb;
+    const int held0 = a.state[2 * s + 1];
+    for (int c = lane; c < nc; c += 64) s_st[c] = st[c];
+    __syncthreads();
+    if (lane == 0) {
+        int receiving = a.state[2 * s], n = held0, b = 0, nout = 0;
+        for (int c = 0; c < nc; c++) {
+            const int v = s_st[c];
+            int act = -1;
+            if (!receiving) {
+                if (v == (PIRIP_RX_SYNC | PIRIP_RX_BITS)) { receiving = 1; n = 1; act = (b << 16) | 0; }
+            } else {
+                if ((v & PIRIP_RX_BITS) && n < a.max_burst) { act = (b << 16) | n; n++; }
+                if (!(v & PIRIP_RX_SYNC)) { s_base[b] = nout; s_n[b] = n; nout += n + 1; b++; receiving = 0; n = 0; }
+            }
+            s_act[c] = act;
+        }
+        s_base[b] = -1; s_n[b] = n;
+        s_hdr[0] = b; s_hdr[1] = nout; s_hdr[2] = receiving; s_hdr[3] = receiving ? n : 0;
+    }
+    __syncthreads();
+    const int nb = s_hdr[0];
+    // frames that were held from earlier calls belong to burst 0: out they go if it ended here (else they stay where they are)
+    if (held0 > 0 && nb > 0)
+        for (int i = lane; i < held0 * a.kb; i += 64) {
+            const int j = i / a.kb, o = i - j * a.kb;
+            if (j < a.max_rec) {
+                out[(size_t)j * rl + 1 + o] = o == 0 ? (uint8_t)a.source : held[i];
+                if (o == 0) out[(size_t)j * rl] = j == 0 ? 1 : 0;
+            }
+        }
+    __syncthreads();
+    for (int i = lane; i < nc * a.kb; i += 64) {
+        const int c = i / a.kb, o = i - c * a.kb;
+        const int act = s_act[c];
+        if (act < 0) continue;
+        const int b = act >> 16, slot = act & 0xffff;
+        const uint8_t v = pl[(size_t)c * a.kb + o];
+        if (s_base[b] >= 0) {
+            const int j = s_base[b] + slot;
+            if (j < a.max_rec) {
+                out[(size_t)j * rl + 1 + o] = o == 0 ? (uint8_t)a.source : v;      // the repeater's own source address
+                if (o == 0) out[(size_t)j * rl] = slot == 0 ? 1 : 0;
+            }
+        } else {
+            held[(size_t)slot * a.kb + o] = v;
+        }
+    }
+    for (int i = lane; i < nb * rl; i += 64) {                                    // end of burst: control byte 2, zero data
+        const int b = i / rl, o = i - b * rl;
+        const int j = s_base[b] + s_n[b];
+        if (j < a.max_rec) out[(size_t)j * rl + o] = o == 0 ? 2 : 0;
+    }
+    if (lane == 0) {
+        a.state[2 * s] = s_hdr[2]; a.state[2 * s + 1] = s_hdr[3];
+        if (a.nrec) a.nrec[s] = s_hdr[1];
+    }
+}
+
+}  // namespace
+
+struct pirip_hip_tx {
+    LdpcCode code;
+    int Fs = 0, Rs = 0, M = 0, Ts = 0, bps = 1, nstreams = 0, device = 0, last_hip = 0;
+    int pre_bits = 0;
+    int64_t samples_sent = 0;              // per stream since create / reset (every stream sends the same count per call)
+    int max_lead = 0, max_gap = 0;
+    int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr, *d_lead = nullptr, *d_gap = nullptr, *d_nsym = nullptr;
+    uint32_t *d_fm = nullptr, *d_tm = nullptr, *d_phase = nullptr;
+    // work buffers, grown on demand
+    int32_t *d_off = nullptr; size_t off_cap = 0;
+    uint32_t *d_prefix = nullptr; size_t prefix_cap = 0;
+    uint8_t *d_syms = nullptr; size_t syms_cap = 0;
+    // record conversion (the repeater): per stream {receiving, frames held} and the held frames, made on first use
+    int32_t *d_rep_state = nullptr; uint8_t *d_rep_held = nullptr;
+};
+
+namespace {
+
+#define TCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { h->last_hip = (int)e_; return PIRIP_ERR_HIP; } } while (0)
+
+void tx_free(pirip_hip_tx *h)
+{
+    void *ptrs[] = {h->d_row_ptr, h->d_col_idx, h->d_lead, h->d_gap, h->d_nsym, h->d_fm, h->d_tm, h->d_phase, h->d_off, h->d_prefix, h->d_syms, h->d_rep_state, h->d_rep_held};
+    for (void *p : ptrs) if (p) (void)hipFree(p);
+}
+
+bool tx_bind(const pirip_hip_tx *h)
+{
+    int cur = -1;
+    if (hipGetDevice(&cur) == hipSuccess && cur == h->device) return true;
+    return hipSetDevice(h->device) == hipSuccess;
+}
+
+template <typename T>
+int tx_grow(pirip_hip_tx *h, T **buf, size_t *cap, size_t want)
+{
+    if (want <= *cap) return PIRIP_OK;
+    if (*buf) { TCHK(hipDeviceSynchronize()); (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
+    if (hipMalloc((void **)buf, want * sizeof(T)) != hipSuccess) return PIRIP_ERR_NOMEM;
+    *cap = want;
+    return PIRIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pirip_hip_tx_create(const char *code_path, int Fs, int Rs, int M, int nstreams, int device, pirip_hip_tx **out)
+{
+    if (!out) return PIRIP_ERR_BAD_ARG;
+    *out = nullptr;
+    if (!code_path || nstreams <= 0) return PIRIP_ERR_BAD_ARG;
+    if (Fs <= 0 || Rs <= 0 || Fs % Rs || (M != 2 && M != 4)) return PIRIP_ERR_BAD_CONFIG;
+    pirip_hip_tx *h = new (std::nothrow) pirip_hip_tx();
+    if (!h) return PIRIP_ERR_NOMEM;
+    const std::string err = h->code.load(code_path);
+    if (!err.empty()) { fprintf(stderr, "pirip_hip_tx_create: %s: %s\n", code_path, err.c_str()); delete h; return PIRIP_ERR_BAD_ARG; }
+    if (!h->code.accumulator) { delete h; return PIRIP_ERR_BAD_CONFIG; }             // no linear-time encoder: the framer tool's refusal
+    h->Fs = Fs; h->Rs = Rs; h->M = M; h->Ts = Fs / Rs; h->bps = M == 2 ? 1 : 2; h->nstreams = nstreams;
+    h->pre_bits = (int)preamble_bits(M).size();
+    // the kernels' tiling: whole symbols per frame and per preamble, 32-bit sample counts in the phase integers
+    if (Fs > kMaxFs || h->code.bits_per_frame() % h->bps || h->pre_bits % h->bps) { delete h; return PIRIP_ERR_UNSUPPORTED; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { delete h; return PIRIP_ERR_NO_DEVICE; }
+    if (device >= 0 && (device >= ndev || hipSetDevice(device) != hipSuccess)) { delete h; return PIRIP_ERR_NO_DEVICE; }
+    if (hipGetDevice(&h->device) != hipSuccess) { delete h; return PIRIP_ERR_NO_DEVICE; }
+    const size_t S = (size_t)nstreams, nr = h->code.row_ptr.size(), ne = h->code.col_idx.size();
+    bool ok = hipMalloc((void **)&h->d_row_ptr, sizeof(int32_t) * nr) == hipSuccess &&
+              hipMalloc((void **)&h->d_col_idx, sizeof(int32_t) * ne) == hipSuccess &&
+              hipMalloc((void **)&h->d_lead, sizeof(int32_t) * S) == hipSuccess &&
+              hipMalloc((void **)&h->d_gap, sizeof(int32_t) * S) == hipSuccess &&
+              hipMalloc((void **)&h->d_nsym, sizeof(int32_t) * S) == hipSuccess &&
+              hipMalloc((void **)&h->d_fm, sizeof(uint32_t) * 4 * S) == hipSuccess &&
+              hipMalloc((void **)&h->d_tm, sizeof(uint32_t) * 4 * S) == hipSuccess &&
+              hipMalloc((void **)&h->d_phase, sizeof(uint32_t) * S) == hipSuccess;
+    if (!ok) { tx_free(h); delete h; return PIRIP_ERR_NOMEM; }
+    ok = hipMemcpy(h->d_row_ptr, h->code.row_ptr.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(h->d_col_idx, h->code.col_idx.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemset(h->d_lead, 0, sizeof(int32_t) * S) == hipSuccess && hipMemset(h->d_gap, 0, sizeof(int32_t) * S) == hipSuccess &&
+         hipMemset(h->d_fm, 0, sizeof(uint32_t) * 4 * S) == hipSuccess && hipMemset(h->d_tm, 0, sizeof(uint32_t) * 4 * S) == hipSuccess &&
+         hipMemset(h->d_phase, 0, sizeof(uint32_t) * S) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
+    if (!ok) { tx_free(h); delete h; return PIRIP_ERR_HIP; }
+    *out = h;
+    return PIRIP_OK;
+}
+
+int pirip_hip_tx_destroy(pirip_hip_tx *h)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    (void)hipSetDevice(h->device);
+    (void)hipDeviceSynchronize();
+    tx_free(h);
+    delete h;
+    return PIRIP_OK;
+}
+
+int pirip_hip_tx_get_info(const pirip_hip_tx *h, pirip_tx_info *info)
+{
+    if (!h || !info) return PIRIP_ERR_BAD_ARG;
+    std::memset(info, 0, sizeof(*info));
+    info->Fs = h->Fs; info->Rs = h->Rs; info->M = h->M; info->Ts = h->Ts;
+    info->n = h->code.n; info->k = h->code.k; info->bits_per_frame = h->code.bits_per_frame(); info->data_bytes = h->code.data_bytes();
+    info->preamble_syms = h->pre_bits / h->bps; info->frame_syms = h->code.bits_per_frame() / h->bps;
+    info->nstreams = h->nstreams; info->device = h->device;
+    return PIRIP_OK;
+}
+
+int pirip_hip_tx_set_tones(pirip_hip_tx *h, const int32_t *f1_hz, int tone_spacing_hz)
+{
+    if (!h || !f1_hz) return PIRIP_ERR_BAD_ARG;
+    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    std::vector<uint32_t> fm((size_t)h->nstreams * 4, 0), tm((size_t)h->nstreams * 4, 0);
+    for (int s = 0; s < h->nstreams; s++)
+        for (int m = 0; m < h->M; m++) {
+            const int64_t f = (((int64_t)f1_hz[s] + (int64_t)m * tone_spacing_hz) % h->Fs + h->Fs) % h->Fs;
+            fm[(size_t)s * 4 + m] = (uint32_t)f;
+            tm[(size_t)s * 4 + m] = (uint32_t)((f * h->Ts) % h->Fs);
+        }
+    TCHK(hipDeviceSynchronize());                            // calls in flight still read the old tones
+    TCHK(hipMemcpy(h->d_fm, fm.data(), sizeof(uint32_t) * fm.size(), hipMemcpyHostToDevice));
+    TCHK(hipMemcpy(h->d_tm, tm.data(), sizeof(uint32_t) * tm.size(), hipMemcpyHostToDevice));
+    return PIRIP_OK;
+}
+
+int pirip_hip_tx_set_gaps(pirip_hip_tx *h, const int32_t *lead_syms, const int32_t *gap_syms)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    std::vector<int32_t> lead((size_t)h->nstreams, 0), gap((size_t)h->nstreams, 0);
+    int ml = 0, mg = 0;
+    for (int s = 0; s < h->nstreams; s++) {
+        if ((lead_syms && lead_syms[s] < 0) || (gap_syms && gap_syms[s] < 0)) return PIRIP_ERR_BAD_ARG;
+        if (lead_syms) { lead[(size_t)s] = lead_syms[s]; if (lead_syms[s] > ml) ml = lead_syms[s]; }
+        if (gap_syms) { gap[(size_t)s] = gap_syms[s]; if (gap_syms[s] > mg) mg = gap_syms[s]; }
+    }
+    TCHK(hipDeviceSynchronize());
+    TCHK(hipMemcpy(h->d_lead, lead.data(), sizeof(int32_t) * lead.size(), hipMemcpyHostToDevice));
+    TCHK(hipMemcpy(h->d_gap, gap.data(), sizeof(int32_t) * gap.size(), hipMemcpyHostToDevice));
+    h->max_lead = ml; h->max_gap = mg;
+    return PIRIP_OK;
+}
+
+int pirip_hip_tx_reset(pirip_hip_tx *h, void *hip_stream)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    TCHK(hipMemsetAsync(h->d_phase, 0, sizeof(uint32_t) * (size_t)h->nstreams, (hipStream_t)hip_stream));
+    if (h->d_rep_state) TCHK(hipMemsetAsync(h->d_rep_state, 0, sizeof(int32_t) * 2 * (size_t)h->nstreams, (hipStream_t)hip_stream));
+    h->samples_sent = 0;
+    return PIRIP_OK;
+}
+
+int64_t pirip_hip_tx_max_syms(const pirip_hip_tx *h, int max_rec)
+{
+    if (!h || max_rec < 0) return 0;
+    const int64_t per_frame = (h->pre_bits + h->code.bits_per_frame()) / h->bps;
+    return (int64_t)h->max_lead + (int64_t)max_rec * (per_frame > h->max_gap ? per_frame : (int64_t)h->max_gap);
+}
+
+int pirip_hip_tx_frame(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_stride, const int32_t *d_nrec, int max_rec,
+                       uint8_t *d_syms, size_t sym_stride, int64_t max_syms, int32_t *d_nsym, uint8_t *d_bits, size_t bits_stride,
+                       void *hip_stream)
+{
+    if (!h || !d_records || !d_syms || max_rec < 0 || max_syms < 0) return PIRIP_ERR_BAD_ARG;
+    const int64_t need = pirip_hip_tx_max_syms(h, max_rec);
+    if (max_syms < need || sym_stride < (size_t)max_syms || (d_bits && bits_stride < (size_t)max_syms * h->bps)) return PIRIP_ERR_BAD_ARG;
+    if (rec_stride < (size_t)max_rec * (size_t)(1 + h->code.data_bytes())) return PIRIP_ERR_BAD_ARG;
+    if (max_syms > 0x7fffffff || (max_rec + kFrameWaves - 1) / kFrameWaves > 65535 || h->nstreams > 65535) return PIRIP_ERR_UNSUPPORTED;
+    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    const int rc = tx_grow(h, &h->d_off, &h->off_cap, (size_t)h->nstreams * (size_t)(max_rec > 0 ? max_rec : 1));
+    if (rc != PIRIP_OK) return rc;
+    FrameArgs a{};
+    a.rec = d_records; a.rec_stride = rec_stride; a.nrec = d_nrec; a.max_rec = max_rec; a.off = h->d_off;
+    a.syms = d_syms; a.sym_stride = sym_stride; a.max_syms = max_syms; a.nsym = d_nsym ? d_nsym : h->d_nsym;
+    a.bits = d_bits; a.bits_stride = bits_stride;
+    a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.lead = h->d_lead; a.gap = h->d_gap;
+    a.uw = 0;
+    for (int i = 0; i < kUwBits; i++) a.uw |= (uint32_t)(h->code.uw[i] & 1) << (31 - i);
+    a.k = h->code.k; a.m = h->code.m; a.kb = h->code.data_bytes(); a.bpf = h->code.bits_per_frame(); a.bps = h->bps;
+    a.pre_bits = h->pre_bits; a.nstreams = h->nstreams;
+    a.frame_lds = (a.bpf + 15) & ~15;
+    a.wave_lds = a.frame_lds + ((a.kb + 15) & ~15);
+    hipStream_t st = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(tx_layout_kernel, dim3((unsigned)h->nstreams), dim3(64), 0, st, a);
+    if (max_rec > 0)
+        hipLaunchKernelGGL(tx_frame_kernel, dim3((unsigned)((max_rec + kFrameWaves - 1) / kFrameWaves), (unsigned)h->nstreams), dim3(kFrameWaves * 64),
+                           (size_t)kFrameWaves * a.wave_lds, st, a);
+    TCHK(hipGetLastError());
+    return PIRIP_OK;
+}
+
+int pirip_hip_tx_modulate(pirip_hip_tx *h, const uint8_t *d_syms, size_t sym_stride, const int32_t *d_nsym, int64_t nsym,
+                          int out_format, void *d_out, size_t out_stride_bytes, float amp, float sigma, uint64_t seed, void *hip_stream)
+{
+    if (!h || !d_syms || !d_out || nsym < 0) return PIRIP_ERR_BAD_ARG;
+    if (out_format != PIRIP_IN_CU8_FSKDEMOD && out_format != PIRIP_IN_CF32) return PIRIP_ERR_UNSUPPORTED;
+    const int bsamp = out_format == PIRIP_IN_CF32 ? 8 : 2, spu = 16 / bsamp;
+    if (((uintptr_t)d_out | out_stride_bytes) & (size_t)(bsamp - 1)) return PIRIP_ERR_BAD_ARG;
+    const int64_t nsamp = nsym * h->Ts;
+    if (nsamp > 0x7fffffff) return PIRIP_ERR_UNSUPPORTED;
+    if (out_stride_bytes < (size_t)nsamp * bsamp && h->nstreams > 1) return PIRIP_ERR_BAD_ARG;
+    if (nsym == 0) return PIRIP_OK;
+    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    const int rc = tx_grow(h, &h->d_prefix, &h->prefix_cap, (size_t)h->nstreams * (size_t)nsym);
+    if (rc != PIRIP_OK) return rc;
+    ModArgs a{};
+    a.syms = d_syms; a.sym_stride = sym_stride; a.nsym = d_nsym; a.total = nsym;
+    a.prefix = h->d_prefix; a.phase = h->d_phase; a.fm = h->d_fm; a.tm = h->d_tm;
+    a.out = d_out; a.out_stride = out_stride_bytes; a.n0 = h->samples_sent;
+    a.Fs = h->Fs; a.Ts = h->Ts; a.M = h->M; a.nstreams = h->nstreams;
+    a.aligned16 = (((uintptr_t)d_out | out_stride_bytes) & 15) == 0;
+    a.two_over_fs = 2.0f / (float)h->Fs; a.amp = amp; a.sigma = sigma; a.inv_fs_d = 1.0 / (double)h->Fs; a.seed = seed;
+    hipStream_t st = (hipStream_t)hip_stream;
+    hipLaunchKernelGGL(tx_prefix_kernel, dim3((unsigned)h->nstreams), dim3(kScanThreads), 0, st, a);
+    const int64_t units = (nsamp + spu - 1) / spu;
+    const dim3 grid((unsigned)((units + kModThreads - 1) / kModThreads), (unsigned)(h->nstreams < 65535 ? h->nstreams : 65535),
+                    (unsigned)((h->nstreams + 65534) / 65535));
+    if (spu == 8) hipLaunchKernelGGL(tx_mod_kernel<8>, grid, dim3(kModThreads), 0, st, a);
+    else hipLaunchKernelGGL(tx_mod_kernel<2>, grid, dim3(kModThreads), 0, st, a);
+    TCHK(hipGetLastError());
+    h->samples_sent += nsamp;
+    return PIRIP_OK;
+}
+
+int pirip_hip_tx_records_to_iq(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_stride, const int32_t *d_nrec, int max_rec,
+                               int64_t nsym, int out_format, void *d_out, size_t out_stride_bytes, float amp, float sigma, uint64_t seed,
+                               int32_t *d_nsym, void *hip_stream)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    int64_t cap = pirip_hip_tx_max_syms(h, max_rec);
+    if (cap < 1) cap = 1;
+    int rc = tx_grow(h, &h->d_syms, &h->syms_cap, (size_t)h->nstreams * (size_t)cap);
+    if (rc != PIRIP_OK) return rc;
+    int32_t *ns = d_nsym ? d_nsym : h->d_nsym;
+    rc = pirip_hip_tx_frame(h, d_records, rec_stride, d_nrec, max_rec, h->d_syms, (size_t)cap, cap, ns, nullptr, 0, hip_stream);
+    if (rc != PIRIP_OK) return rc;
+    return pirip_hip_tx_modulate(h, h->d_syms, (size_t)cap, ns, nsym, out_format, d_out, out_stride_bytes, amp, sigma, seed, hip_stream);
+}
+
+int pirip_hip_tx_repeat_max_records(const pirip_hip_tx *h, int ncalls)
+{
+    if (!h || ncalls < 0) return 0;
+    return PIRIP_TX_REPEAT_MAX_FRAMES + 2 * ncalls;          // held frames + a frame and (at worst) an end per call
+}
+
+int pirip_hip_tx_repeat_records(pirip_hip_tx *h, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                                const int32_t *d_ncalls, int ncalls, int source_byte, uint8_t *d_records, size_t rec_stride, int max_rec,
+                                int32_t *d_nrec, void *hip_stream)
+{
+    if (!h || !d_status || !d_payload || !d_records || ncalls < 0 || max_rec < 0 || source_byte < 0 || source_byte > 255) return PIRIP_ERR_BAD_ARG;
+    const int kb = h->code.data_bytes();
+    if (status_stride < (size_t)ncalls || payload_stride < (size_t)ncalls * kb || rec_stride < (size_t)max_rec * (size_t)(1 + kb)) return PIRIP_ERR_BAD_ARG;
+    if (max_rec < pirip_hip_tx_repeat_max_records(h, ncalls)) return PIRIP_ERR_BAD_ARG;
+    if (ncalls > 4096) return PIRIP_ERR_UNSUPPORTED;         // the call table lives in LDS
+    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!h->d_rep_state) {
+        const size_t S = (size_t)h->nstreams;
+        if (hipMalloc((void **)&h->d_rep_state, sizeof(int32_t) * 2 * S) != hipSuccess ||
+            hipMalloc((void **)&h->d_rep_held, S * PIRIP_TX_REPEAT_MAX_FRAMES * (size_t)kb) != hipSuccess) return PIRIP_ERR_NOMEM;
+        TCHK(hipMemset(h->d_rep_state, 0, sizeof(int32_t) * 2 * S));
+    }
+    RepeatArgs a{};
+    a.status = d_status; a.status_stride = status_stride; a.payload = d_payload; a.payload_stride = payload_stride; a.ncalls_s = d_ncalls; a.ncalls = ncalls;
+    a.rec = d_records; a.rec_stride = rec_stride; a.max_rec = max_rec; a.nrec = d_nrec;
+    a.state = h->d_rep_state; a.held = h->d_rep_held; a.kb = kb; a.max_burst = PIRIP_TX_REPEAT_MAX_FRAMES; a.source = source_byte;
+    const size_t lds = sizeof(int32_t) * (3 * (size_t)ncalls + 2) + (size_t)ncalls + 16;
+    hipLaunchKernelGGL(tx_repeat_kernel, dim3((unsigned)h->nstreams), dim3(64), lds, (hipStream_t)hip_stream, a);
+    TCHK(hipGetLastError());
+    return PIRIP_OK;
+}
+
+}  // extern "C"

@@ -11,6 +11,10 @@ and every receiver is scored against the TRANSMITTED payloads: frame error rate 
 the right bytes), undetected errors (CRC good, bytes wrong), bit error rate of all decoded payloads, mean iterations.
 
   python tools/ldpc_fer.py [--streams 1088] [--frames 104] [--ebno 3.5,5,7] > profiles/r04_ldpc_fer.txt
+  python tools/ldpc_fer.py --device-tx [--streams 16384] ...
+--device-tx (opt-in): every stream sends its OWN random payloads (source byte and sequence number kept), framed and modulated on the
+device by pirip_amd.HipTx (include/pirip_hip.h section I) instead of one host-framed burst played on every stream; the expected
+payloads are read back from the transmitter's own frame bits. Tones, timing offsets, noise level and scoring are the default path's.
 Eb/N0 is per CHANNEL bit (Es / log2 M), the convention of tools/bench_configs.py and tests/test_ldpc.py. Checker only."""
 import argparse
 import multiprocessing as mp
@@ -55,6 +59,7 @@ def _worker(s):
     g = _G
     code, M = g["code"], g["M"]
     filt = g["filt"][s, :g["nfr"][s]]
+    expected = g["expected"] if g["expected"].ndim == 2 else g["expected"][s]     # one burst for all streams, or each stream's own
     out = {}
     rx = {"mirror": ob.OracleLdpc(code, M), "indep": ob.IndepLdpc(code, M, mode=1), "recalled": ob.IndepLdpc(code, M, mode=2),
           "recalled_phi0": ob.IndepLdpc(code, M, mode=3)}
@@ -62,13 +67,13 @@ def _worker(s):
     n = g["nfr"][s]
     recs["gpu"] = (g["st"][s, :n], g["pl"][s, :n], g["inf"][s, :n])
     for k, (st, pl, inf) in recs.items():
-        out[k] = _score(st, pl, inf, g["expected"], g["lo"], g["hi"])
+        out[k] = _score(st, pl, inf, expected, g["lo"], g["hi"])
     out["gpu_equals_mirror"] = bool(np.array_equal(recs["gpu"][0], recs["mirror"][0]) and np.array_equal(recs["gpu"][1], recs["mirror"][1])
                                     and np.array_equal(recs["gpu"][2][:, :9], recs["mirror"][2][:, :9]))
     return out
 
 
-def run(ebno_db, streams=1024, frames=104, M=4, P=8, seed=0xfec, procs=None, llr_map=None):
+def run(ebno_db, streams=1024, frames=104, M=4, P=8, seed=0xfec, procs=None, llr_map=None, device_tx=False):
     import torch
     import pirip_amd
     from pirip_amd.binding import synth_cu8
@@ -96,9 +101,37 @@ def run(ebno_db, streams=1024, frames=104, M=4, P=8, seed=0xfec, procs=None, llr
     skips = ((gsi // 5) % TS).astype(np.int32)
     sigma = float(np.sqrt((4.0 * TS / bps) / (10 ** (ebno_db / 10.0)) / 2.0))
     dev = torch.empty((B, nsamp, 2), dtype=torch.uint8, device="cuda")
-    dtx = torch.from_numpy(fb.copy()).cuda()
-    synth_cu8(FS, RS, M, f1s, 10000, dtx.data_ptr(), 0, nsym, dev.data_ptr(), nsamp * 2, nsamp, amp=14.0, sigma=sigma, seed=seed,
-              skip=skips, stream=torch.cuda.current_stream().cuda_stream)
+    if device_tx:
+        # a distinct payload per (stream, frame): byte 0 the source address, byte 1 the sequence number as in the default path
+        assert frames <= 255, "--device-tx keeps the one-byte sequence number: at most 255 frames"
+        tx = pirip_amd.HipTx(pirip_amd.STANDIN_CODE, FS, RS, M, nstreams=B, f1=f1s, shift=10000)
+        kb = code["k"] // 8
+        rec = np.random.default_rng(seed).integers(0, 256, (B, frames, 1 + kb)).astype(np.uint8)
+        rec[:, :, 0] = 0; rec[:, 0, 0] = 1
+        rec[:, :, 1] = 1; rec[:, :, 2] = (np.arange(frames) + 1) & 0xff
+        assert tx.max_syms(frames) >= nsym
+        cap = tx.max_syms(frames)
+        d_rec = torch.from_numpy(rec).cuda()
+        syms = torch.empty((B, cap), dtype=torch.uint8, device="cuda")
+        bits = torch.empty((B, cap * bps), dtype=torch.uint8, device="cuda")
+        cs0 = torch.cuda.current_stream().cuda_stream
+        tx.frame(d_rec.data_ptr(), rec[0].size, frames, syms.data_ptr(), cap, cap, d_bits=bits.data_ptr(), bits_stride=cap * bps, stream=cs0)
+        full = torch.empty((B, nsym * TS, 2), dtype=torch.uint8, device="cuda")
+        tx.modulate(syms.data_ptr(), cap, nsym, full.data_ptr(), nsym * TS * 2, amp=14.0, sigma=sigma, seed=seed, stream=cs0)
+        torch.cuda.synchronize()
+        hb = bits[:, :nsym * bps].cpu().numpy()
+        expected = np.stack([np.packbits(hb[:, pre + f * bpf + 32:][:, :code["k"]], axis=1) for f in range(frames)], axis=1)   # [B, frames, kb]
+        assert np.array_equal(expected[:, :, :kb - 2], rec[:, :, 1:kb - 1]) and np.array_equal(hb[0, :pre], fb[:pre])
+        tsk = torch.from_numpy(skips).cuda()
+        for k in range(TS):                       # the timing offsets of the default path: stream s starts skips[s] samples in
+            rows = torch.nonzero(tsk == k).flatten()
+            if rows.numel():
+                dev[rows] = full[rows, k:k + nsamp]
+        del full, syms, bits, tx
+    else:
+        dtx = torch.from_numpy(fb.copy()).cuda()
+        synth_cu8(FS, RS, M, f1s, 10000, dtx.data_ptr(), 0, nsym, dev.data_ptr(), nsamp * 2, nsamp, amp=14.0, sigma=sigma, seed=seed,
+                  skip=skips, stream=torch.cuda.current_stream().cuda_stream)
     torch.cuda.synchronize()
     est_max = 25000 if M == 2 else 60000
     h = pirip_amd.HipDemod(FS, RS, M, P=P, est_min=500, est_max=est_max, nstreams=B)
@@ -157,17 +190,20 @@ def main():
     ap.add_argument("--ebno", default="3.5,5,7")
     ap.add_argument("--M", type=int, default=4)
     ap.add_argument("--P", type=int, default=8)
+    ap.add_argument("--device-tx", action="store_true", help="a distinct payload per stream, framed and modulated on the device through HipTx (default: one host-framed burst on every stream)")
     ap.add_argument("--llr-map", default=None, help="upstream | rician: the product's (and the mirror's) soft-decision mapping; default: the code file's (upstream)")
     a = ap.parse_args()
     print("# tools/ldpc_fer.py: FSK_LDPC receive, stand-in (512,256) code, %d-FSK Fs=240k Rs=10k P=%d, %d streams x %d frames "
           "(the first and last 4 of a stream are not scored: acquisition / tail)" % (a.M, a.P, a.streams, a.frames))
+    if a.device_tx:
+        print("# --device-tx: every stream sends its own random payloads, framed and modulated on the device (pirip_amd.HipTx)")
     print("# product llr_map: %s (upstream = codec2's fsk_rx_filt_to_llrs as recalled [UPSTREAM-RECALLED], the default since round 5; rician = exact ln I0, rounds 2-4)" % (a.llr_map or "code file default = upstream"))
     print("# receivers: gpu = product (its llr_map, binary16 soft bits, wave-order sums, table phi); mirror = CPU statement of the same arithmetic; "
           "indep = float32 soft bits, serial sums, exact ln I0, double sum-product; recalled = codec2's fsk_rx_filt_to_llrs as recalled "
           "[UPSTREAM-RECALLED] + the same double sum-product; recalled_phi0 = that with the decoder's phi limited to codec2's phi0() range as recalled (x < 9.08e-5 -> 10, x > 10 -> 0): what the product's decoder range follows since round 5")
     print("# Eb/N0(dB,channel bit) receiver frames_scored frame_errors FER undetected decoded_BER mean_iterations")
     for e in a.ebno.split(","):
-        r = run(float(e), a.streams, a.frames, a.M, a.P, llr_map=a.llr_map)
+        r = run(float(e), a.streams, a.frames, a.M, a.P, llr_map=a.llr_map, device_tx=a.device_tx)
         for k in ("gpu", "mirror", "indep", "recalled", "recalled_phi0"):
             v = r[k]
             print(f"{e} {k:13s} {r['frames_scored']} {v['frame_errors']} {v['fer']:.3e} {v['undetected']} {v['ber_decoded']:.3e} {v['mean_iter']:.2f}")
