@@ -298,23 +298,7 @@ def test_loopback_into_the_receive_chain(oracle, built_lib, M, P):
     assert a >= b - 3.0 * sd
 
 
-def _repeater_replay(status, data, source):
-    """tx/frame_repeater.c:68-107 on one stream's records -> the Tx records it writes (uint8 [n, 1 + kb])"""
-    out, buf, receiving = [], [], False
-    for st, d in zip(status, data):
-        if not receiving:
-            if st == (RX_SYNC | RX_BITS):
-                buf, receiving = [d.copy()], True
-        else:
-            if st & RX_BITS:
-                buf.append(d.copy())
-            if not (st & RX_SYNC):
-                for i, fr in enumerate(buf):
-                    fr[0] = source
-                    out.append(np.concatenate([[1 if i == 0 else 0], fr]))
-                out.append(np.concatenate([[2], np.zeros(data.shape[1], dtype=np.uint8)]))
-                receiving = False
-    return np.array(out, dtype=np.uint8).reshape(-1, 1 + data.shape[1])
+_repeater_replay = txref.repeater_replay
 
 
 @pytest.mark.gpu

@@ -396,6 +396,86 @@ def decim_one(seed, ob, A):
             return "FAIL", f"decimator D {D} tbw {tbw} ({ntaps} taps) n_in {n_in} B {B} byte_off {byte_off} stride {stride}: stream {s} differs"
     return "exact", ""
 
+TX_TS = [1, 2, 3, 5, 7, 8, 9, 10, 16, 24, 24, 40, 100, 1024]
+
+
+def tx_draw(seed):
+    """one transmit draw -> (cfg, discarded): code shape, M, Fs / Rs, first tones and shift, symbols with carrier-off runs, call split,
+    format, sigma. A (shape, tones) pair on which the float64 formula alone puts more than a quarter of tests/test_tx.py's 1e-3 cap of u8
+    samples within the bound of a rounding tie is discarded and drawn again (the filter sees no device output); `discarded` counts them."""
+    import test_tx_shapes as shp
+    import txref
+    rng = np.random.default_rng(seed)
+    discarded = 0
+    while True:
+        Ts = int(rng.choice(TX_TS))
+        Fs = (1 << 24) if rng.random() < 0.15 and (1 << 24) % Ts == 0 else Ts * int(rng.choice([600, 1000, 2400, 9600, 10000, 16000]))
+        Rs = Fs // Ts
+        M = int(rng.choice([2, 4]))
+        B = int(rng.integers(1, 5))
+        edge = [0, 1, -1, Fs // 2 - 1, -(Fs // 2 - 1), Rs + 1, 2 * Rs - 1]
+        f1 = [int(rng.choice(edge)) if rng.random() < 0.3 else int(rng.integers(-Fs // 2, Fs // 2)) for _ in range(B)]
+        shift = int(rng.choice([Rs, Rs + 1, max(Rs - 1, 1), 2 * Rs, int(rng.integers(1, max(Fs // 4, 2)))]))
+        nsym = int(rng.integers(1, max(2, min(3000, 400000 // Ts))))
+        amp = float(rng.choice([32.0, 20.0, 14.0]))
+        syms = rng.integers(0, M, (B, nsym)).astype(np.uint8)
+        for s in range(B):
+            if rng.random() < 0.5:
+                a = int(rng.integers(0, nsym)); syms[s, a:a + int(rng.integers(1, 80))] = txref.OFF
+        share = max(float(np.mean(txref.near_tie(txref.quantise(txref.mod_f64(syms[s], f1[s], shift, Fs, Ts), amp)[1], amp))) for s in range(B))
+        if share > 1e-3 / 4:
+            discarded += 1
+            continue
+        cuts = np.sort(rng.integers(0, nsym + 1, int(rng.integers(0, 5))))
+        blocks = [int(v) for v in np.diff(np.concatenate([[0], cuts, [nsym]]))]
+        n, k = shp.CODE_SHAPES[int(rng.integers(0, len(shp.CODE_SHAPES)))]
+        return dict(seed=seed, n=n, k=k, M=M, Fs=Fs, Rs=Rs, Ts=Ts, f1=f1, shift=shift, nsym=nsym, amp=amp, syms=syms, blocks=blocks,
+                    fmt="cf32" if rng.random() < 0.5 else "u8", sigma=0.0 if rng.random() < 0.5 else float(rng.uniform(0.05, 3.0)),
+                    nseed=int(rng.integers(1, 1 << 40))), discarded
+
+
+def tx_one(seed, ob, A):
+    """the batch transmitter (section I) on one draw of tx_draw: the framer on the drawn code shape against fsk_ldpc_framer, H, the CRC16
+    and the UW (tests/test_tx_shapes.py's checks); the modulator on the drawn shape, tones, symbols and call split against the float64
+    formula plus, with sigma > 0, the float64 restatement of the noise at the same key (tests/txref.py), cf32 within the derived bounds,
+    u8 equal to the float64 quantiser outside the bound of a rounding tie"""
+    import tempfile
+    import torch
+    import test_tx_shapes as shp
+    import txref
+    c, _ = tx_draw(seed)
+    rng = np.random.default_rng(seed + 1)
+    tag = f"tx ({c['n']},{c['k']}) M {c['M']} Fs {c['Fs']} Ts {c['Ts']} f1 {c['f1']} shift {c['shift']} nsym {c['nsym']} blocks {c['blocks']} {c['fmt']} sigma {c['sigma']:.3f}"
+    with tempfile.TemporaryDirectory() as tmp:
+        code = shp.write_code(tmp, c["n"], c["k"])
+        try:
+            frames = shp.framer_case(ob, code, c["M"], c["n"], c["k"], rng, B=4)
+            Fs, Ts, B, amp, sigma = c["Fs"], c["Ts"], len(c["f1"]), c["amp"], c["sigma"]
+            tx = A.HipTx(code, Fs, c["Rs"], c["M"], nstreams=B, f1=c["f1"], shift=c["shift"])
+            fmt = A.IN_CF32 if c["fmt"] == "cf32" else A.IN_CU8_FSKDEMOD
+            d = torch.from_numpy(c["syms"]).cuda()
+            got = shp.modulate_rows(tx, d, c["nsym"], fmt, blocks=c["blocks"], amp=amp, sigma=sigma, seed=c["nseed"])
+            tx.reset()
+            again = shp.modulate_rows(tx, d, c["nsym"], fmt, amp=amp, sigma=sigma, seed=c["nseed"])
+            assert np.array_equal(got.view(np.uint8), again.view(np.uint8)), "split calls and one call after reset differ"
+            for s in range(B):
+                y = txref.mod_f64(c["syms"][s], c["f1"][s], c["shift"], Fs, Ts)
+                z = txref.noise_f64(c["nseed"], s, np.arange(y.size), sigma) if sigma > 0 else np.zeros(y.size, dtype=np.complex128)
+                tol = txref.BOUND * (np.abs(y) > 0) + txref.NOISE_REL_BOUND * np.abs(z) + 2.0 ** -24 * np.abs(y + z) * (sigma > 0)   # (the sum of signal and noise rounds once)
+                w = y + z
+                if c["fmt"] == "cf32":
+                    err = np.maximum(np.abs(got[s, :, 0] - w.real), np.abs(got[s, :, 1] - w.imag))
+                    assert (err <= tol).all(), f"stream {s}: cf32 off the formula by {float(np.max(err - tol)):.3e} beyond its bound"
+                else:
+                    q, v = txref.quantise(w, amp)
+                    diff = np.abs(got[s].astype(np.int64) - q)
+                    # (with noise the quantiser's own float roundings join the window: amp * x 2^-24 relative, 127 + amp * x 2^-17; DESIGN.md 4.9)
+                    tie = np.abs(np.abs(v - np.floor(v)) - 0.5) <= (tol * amp + (sigma > 0) * (2.0 ** -24 * amp * np.abs(w) + 2.0 ** -17))[:, None]
+                    assert diff.max() <= 1 and not diff[~tie].any(), f"stream {s}: {int(np.count_nonzero(diff[~tie]))} u8 samples differ away from a tie"
+        except AssertionError as e:
+            return "FAIL", f"{tag}: {str(e)[:300]}"
+    return "exact", dict(shape=(c["n"], c["k"]), M=c["M"], fmt=c["fmt"], Ts=c["Ts"], frames=frames)
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -404,6 +484,7 @@ def main():
     ap.add_argument("--chain", action="store_true", help="fuzz pirip_hip_fsk_ldpc_rx_batch (IQ -> FSK_LDPC records, several streams) against demodulator + oracle receiver")
     ap.add_argument("--ldpc", action="store_true", help="fuzz the FSK_LDPC receiver (records bit-exact against the mirror oracle) instead of the demodulator")
     ap.add_argument("--decimator", action="store_true", help="fuzz the csdr front end (u8 -> decimated f32 / s16, bit-exact) instead of the demodulator")
+    ap.add_argument("--tx", action="store_true", help="fuzz the batch transmitter (section I): framer against the tool and H, modulator and noise against their float64 statements")
     ap.add_argument("--minutes", type=float, default=10.0)
     ap.add_argument("--seed0", type=int, default=1)
     ap.add_argument("--max-draws", type=int, default=1 << 30)
@@ -421,6 +502,8 @@ def main():
         try:
             if a.decimator:
                 res, msg = decim_one(seed, ob, A); kern = "decim"
+            elif a.tx:
+                res, msg = tx_one(seed, ob, A); kern = "tx"; msg = "" if res == "exact" else msg
             elif a.capture:
                 res, msg = capture_one(seed, ob, A, sigutil); kern = "capture"; msg = "" if res == "exact" else msg
             elif a.chain:
