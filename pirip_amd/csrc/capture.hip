@@ -41,6 +41,7 @@
 using namespace pirip;
 
 struct CaptureWork {
+    DevMem mem;                                  // owns every device pointer below
     int slots = 0;
     // snapshot of every slot's state after its warm-up (same layouts as the handle's state arrays)
     float *d_Sf = nullptr; uint32_t *d_theta = nullptr; float2 *d_hist = nullptr; StreamScalars *d_scal = nullptr;
@@ -48,7 +49,7 @@ struct CaptureWork {
     int64_t *d_consA = nullptr, *d_consB = nullptr, *d_posB = nullptr;
     int32_t *d_nfA = nullptr, *d_nfB = nullptr, *d_ok = nullptr, *d_mode = nullptr, *d_src = nullptr, *d_from = nullptr;
     // the replicas' own output rows (passes after the first: several candidates per segment, the verified one is copied out)
-    uint8_t *r_bits = nullptr; float *r_filt = nullptr, *r_stats = nullptr; size_t r_rows = 0; bool r_has_filt = false;
+    uint8_t *r_bits = nullptr; float *r_filt = nullptr, *r_stats = nullptr; size_t r_rows = 0;   // (r_filt: only once a caller has asked for magnitudes)
     float *d_stats = nullptr; size_t stats_rows = 0;
     float *d_warm_stats = nullptr; size_t warm_rows = 0;   // statistics rows of the warm-up frames (never read: they make every warm-up frame
                                                            // an observable one, so that snr_est's average runs through them)
@@ -62,15 +63,7 @@ namespace {
 
 // Host-to-device copy whose source is a stack variable or a vector that the next pass rewrites: complete before returning, whatever
 // the runtime does with pageable sources
-#define CAP_H2D(dst, src, bytes, st) do { CAPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); CAPCHK(hipStreamSynchronize(st)); } while (0)
-#define CAPCHK(expr)                                              \
-    do {                                                          \
-        hipError_t e_ = (expr);                                   \
-        if (e_ != hipSuccess) {                                   \
-            h->last_hip = (int)e_;                                \
-            return PIRIP_ERR_HIP;                                 \
-        }                                                         \
-    } while (0)
+#define CAP_H2D(dst, src, bytes, st) do { PIRIP_HIPCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, st)); PIRIP_HIPCHK(hipStreamSynchronize(st)); } while (0)
 
 constexpr int kThreads = 256;
 
@@ -243,44 +236,39 @@ __global__ __launch_bounds__(256) void ppm_kernel(float *stats, int64_t nframes,
     if (t == 0) final_sc->ppm = s_carry_ppm;
 }
 
-void release(CaptureWork *w)
+int alloc_work(CaptureWork *w, const FskDims &d, size_t ns)
 {
-    if (!w) return;
-    void *ptrs[] = {w->d_Sf, w->d_theta, w->d_hist, w->d_scal, w->d_segA, w->d_segA2, w->d_segB, w->d_consA, w->d_consB, w->d_posB, w->d_nfA, w->d_nfB,
-                    w->d_ok, w->d_mode, w->d_src, w->d_from, w->r_bits, w->r_filt, w->r_stats, w->d_stats, w->d_warm_stats, w->d_scal0, w->d_in, w->d_bits, w->d_filt, w->d_ostats};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-    delete w;
+    DevMem &m = w->mem;
+    PIRIP_TRY(m.alloc(&w->d_Sf, sizeof(float) * ns * d.Ndft));
+    PIRIP_TRY(m.alloc(&w->d_theta, sizeof(uint32_t) * ns * kMaxTones));
+    PIRIP_TRY(m.alloc(&w->d_hist, sizeof(float2) * ns * d.M * d.hist_len));
+    PIRIP_TRY(m.alloc(&w->d_scal, sizeof(StreamScalars) * ns));
+    PIRIP_TRY(m.alloc(&w->d_segA, sizeof(SegDesc) * ns));
+    PIRIP_TRY(m.alloc(&w->d_segB, sizeof(SegDesc) * ns));
+    PIRIP_TRY(m.alloc(&w->d_consA, sizeof(int64_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_consB, sizeof(int64_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_posB, sizeof(int64_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_nfA, sizeof(int32_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_nfB, sizeof(int32_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_ok, sizeof(int32_t) * ns * 4));     // pair list (2 ints per link), then the verdicts
+    PIRIP_TRY(m.alloc(&w->d_src, sizeof(int32_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_from, sizeof(int32_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_segA2, sizeof(SegDesc) * ns));
+    PIRIP_TRY(m.alloc(&w->d_mode, sizeof(int32_t) * ns));
+    PIRIP_TRY(m.alloc(&w->d_scal0, sizeof(StreamScalars)));
+    return PIRIP_OK;
 }
 
 int ensure_work(pirip_hip_demod *h)
 {
     if (h->capture && h->capture->slots == h->nstreams) return PIRIP_OK;
-    release(h->capture);
+    delete h->capture;
     h->capture = nullptr;
     CaptureWork *w = new (std::nothrow) CaptureWork();
     if (!w) return PIRIP_ERR_NOMEM;
-    const FskDims &d = h->plan.d;
-    const size_t ns = (size_t)h->nstreams;
     w->slots = h->nstreams;
-    bool ok = true;
-    ok &= hipMalloc((void **)&w->d_Sf, sizeof(float) * ns * d.Ndft) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_theta, sizeof(uint32_t) * ns * kMaxTones) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_hist, sizeof(float2) * ns * d.M * d.hist_len) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_scal, sizeof(StreamScalars) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_segA, sizeof(SegDesc) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_segB, sizeof(SegDesc) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_consA, sizeof(int64_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_consB, sizeof(int64_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_posB, sizeof(int64_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_nfA, sizeof(int32_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_nfB, sizeof(int32_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_ok, sizeof(int32_t) * ns * 4) == hipSuccess;     // pair list (2 ints per link), then the verdicts
-    ok &= hipMalloc((void **)&w->d_src, sizeof(int32_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_from, sizeof(int32_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_segA2, sizeof(SegDesc) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_mode, sizeof(int32_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&w->d_scal0, sizeof(StreamScalars)) == hipSuccess;
-    if (!ok) { release(w); return PIRIP_ERR_NOMEM; }
+    const int rc = alloc_work(w, h->plan.d, (size_t)h->nstreams);
+    if (rc != PIRIP_OK) { delete w; return rc; }
     h->capture = w;
     return PIRIP_OK;
 }
@@ -290,7 +278,7 @@ int gcd_int(int a, int b) { while (b) { const int t = a % b; a = b; b = t; } ret
 }  // namespace
 
 namespace pirip {
-void capture_release(pirip_hip_demod *h) { if (h) { release(h->capture); h->capture = nullptr; } }
+void capture_release(pirip_hip_demod *h) { if (h) { delete h->capture; h->capture = nullptr; } }
 }
 
 static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uint8_t *d_bits, float *d_rx_filt, float *d_stats,
@@ -316,13 +304,12 @@ extern "C" int pirip_hip_demod_capture(pirip_hip_demod *h, const void *d_in, int
     a.io = DemodIO{(const uint8_t *)d_in, 0, nsamp, d_bits, 0, d_rx_filt, 0, d_stats, 0, nullptr, nullptr, 1, SoftOut{nullptr, 0, nullptr, 0, nullptr, 0}, nullptr};
     a.io.first_out = h->d_first;
     a.io.exact0_fmt = h->kernel == PIRIP_KERNEL_WAVE ? PIRIP_KERNEL_WAVE : PIRIP_KERNEL_GENERAL;
-    const hipError_t e = launch_demod_exact0(a, 1, st);               // stream slot 0 is the capture's stream
-    if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+    PIRIP_HIPCHK(launch_demod_exact0(a, 1, st));                      // stream slot 0 is the capture's stream
     int32_t n0 = 0;
-    CAPCHK(hipMemcpyAsync(&n0, h->d_first, sizeof(n0), hipMemcpyDeviceToHost, st));
-    CAPCHK(hipStreamSynchronize(st));
+    PIRIP_HIPCHK(hipMemcpyAsync(&n0, h->d_first, sizeof(n0), hipMemcpyDeviceToHost, st));
+    PIRIP_HIPCHK(hipStreamSynchronize(st));
     if (n0 <= 0) return capture_impl(h, d_in, nsamp, d_bits, d_rx_filt, d_stats, max_frames, nframes_out, consumed_out, rep, hip_stream);
-    const size_t bps = d.in_format == PIRIP_IN_CF32 ? 8 : d.in_format == PIRIP_IN_CS16 ? 4 : 2;
+    const size_t bps = (size_t)bytes_per_sample(d.in_format);
     const size_t fb = d.pack_bits ? (size_t)(d.Nbits + 7) / 8 : (size_t)d.Nbits;
     int64_t nf = 0, cons = 0;
     pirip_capture_report r;
@@ -363,9 +350,9 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
 
     // the stream's state at entry: nin decides how many frames fit; ppm / timing seed the ppm recomputation
     StreamScalars sc0;
-    CAPCHK(hipMemcpyAsync(&sc0, h->d_scal, sizeof(sc0), hipMemcpyDeviceToHost, st));
-    CAPCHK(hipMemcpyAsync(w->d_scal0, h->d_scal, sizeof(sc0), hipMemcpyDeviceToDevice, st));
-    CAPCHK(hipStreamSynchronize(st));
+    PIRIP_HIPCHK(hipMemcpyAsync(&sc0, h->d_scal, sizeof(sc0), hipMemcpyDeviceToHost, st));
+    PIRIP_HIPCHK(hipMemcpyAsync(w->d_scal0, h->d_scal, sizeof(sc0), hipMemcpyDeviceToDevice, st));
+    PIRIP_HIPCHK(hipStreamSynchronize(st));
     int64_t est_frames = nsamp >= sc0.nin ? 1 + (nsamp - sc0.nin) / N : 0;
     est_frames = std::min(est_frames, max_frames);
 
@@ -393,22 +380,14 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
     if (!stats) {
         // (no more rows than the samples can make frames of, whatever room the caller claims to have)
         const size_t rows = (size_t)std::min<int64_t>(max_frames, nsamp / (N - d.nin_step) + 2);
-        if (w->stats_rows < rows) {
-            if (w->d_stats) (void)hipFree(w->d_stats);
-            w->d_stats = nullptr; w->stats_rows = 0;
-            CAPCHK(hipMalloc((void **)&w->d_stats, sizeof(float) * rows * PIRIP_STATS_PER_FRAME + 16));
-            w->stats_rows = rows;
-        }
+        if (w->stats_rows < rows)
+            PIRIP_TRY(grow_dev(w->mem, &w->stats_rows, rows, GrowSync::none, nullptr, {grow_buf(&w->d_stats, sizeof(float) * rows * PIRIP_STATS_PER_FRAME + 16)}));
         stats = w->d_stats;
     }
 
     const size_t rrows = (size_t)h->nstreams * (size_t)F;                  // one row block of F frames per stream slot
-    if (parallel && w->warm_rows < rrows) {
-        if (w->d_warm_stats) (void)hipFree(w->d_warm_stats);
-        w->d_warm_stats = nullptr; w->warm_rows = 0;
-        CAPCHK(hipMalloc((void **)&w->d_warm_stats, sizeof(float) * rrows * PIRIP_STATS_PER_FRAME + 16));
-        w->warm_rows = rrows;
-    }
+    if (parallel && w->warm_rows < rrows)
+        PIRIP_TRY(grow_dev(w->mem, &w->warm_rows, rrows, GrowSync::none, nullptr, {grow_buf(&w->d_warm_stats, sizeof(float) * rrows * PIRIP_STATS_PER_FRAME + 16)}));
 
     if (!parallel) {
         // the sequential read loop on stream slot 0 (any kernel, any length)
@@ -420,11 +399,11 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
             if (nsamp > demod_wave_max_samples(d)) return PIRIP_ERR_UNSUPPORTED;
             e = launch_demod_wave(a, 1, st);
         } else e = launch_demod_kind(h->kernel, a, 1, st);
-        if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+        PIRIP_HIPCHK(e);
         int32_t nf = 0; int64_t cons = 0;
-        CAPCHK(hipMemcpyAsync(&nf, w->d_nfB, sizeof(nf), hipMemcpyDeviceToHost, st));
-        CAPCHK(hipMemcpyAsync(&cons, w->d_consB, sizeof(cons), hipMemcpyDeviceToHost, st));
-        CAPCHK(hipStreamSynchronize(st));
+        PIRIP_HIPCHK(hipMemcpyAsync(&nf, w->d_nfB, sizeof(nf), hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipMemcpyAsync(&cons, w->d_consB, sizeof(cons), hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipStreamSynchronize(st));
         r.passes = 1; r.frames_demodulated = nf;
         if (nframes_out) *nframes_out = nf;
         if (consumed_out) *consumed_out = cons;
@@ -451,15 +430,10 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
         for (int q = 0; q < h->nstreams; q++) { segA[q] = SegDesc{0, 0, -1, 0}; segA2[q] = SegDesc{0, 0, -1, 0}; segB[q] = SegDesc{0, 0, -1, 0}; mode[q] = 0; }
     };
     // output rows of the slots (every pass writes there; the rows of the verified segments are copied to the caller's arrays)
-    if (w->r_rows < rrows || (d_rx_filt && !w->r_has_filt)) {
-        void *olds[] = {w->r_bits, w->r_filt, w->r_stats};
-        for (void *o : olds) if (o) (void)hipFree(o);
-        w->r_bits = nullptr; w->r_filt = nullptr; w->r_stats = nullptr; w->r_rows = 0; w->r_has_filt = false;
-        CAPCHK(hipMalloc((void **)&w->r_bits, rrows * fb + 16));
-        CAPCHK(hipMalloc((void **)&w->r_stats, sizeof(float) * rrows * PIRIP_STATS_PER_FRAME + 16));
-        if (d_rx_filt) { CAPCHK(hipMalloc((void **)&w->r_filt, sizeof(float) * rrows * filt_floats + 16)); w->r_has_filt = true; }
-        w->r_rows = rrows;
-    }
+    if (w->r_rows < rrows || (d_rx_filt && !w->r_filt))
+        PIRIP_TRY(grow_dev(w->mem, &w->r_rows, rrows, GrowSync::none, nullptr,
+                           {grow_buf(&w->r_bits, rrows * fb + 16), grow_buf(&w->r_stats, sizeof(float) * rrows * PIRIP_STATS_PER_FRAME + 16),
+                            grow_buf(&w->r_filt, d_rx_filt ? sizeof(float) * rrows * filt_floats + 16 : 0)}));
 
     // the stream's true state is the chain's first end state (of "segment -1", ending at sample 0)
     hipLaunchKernelGGL(copy_state_kernel, dim3(1), dim3(kThreads), 0, st, state, KEEP, 0, Ndft, hist_elems);
@@ -478,11 +452,11 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
         a.io = DemodIO{(const uint8_t *)d_in, 0, nsamp, nullptr, 0, nullptr, 0, nullptr, 0, w->d_nfA, w->d_consA, Kp,
                        SoftOut{nullptr, 0, nullptr, 0, nullptr, 0}, w->d_segA};
         hipError_t e = launch_demod_wave(a, 1, st);
-        if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+        PIRIP_HIPCHK(e);
         int64_t c = 0; int32_t nf = 0;
-        CAPCHK(hipMemcpyAsync(&c, w->d_consA, sizeof(c), hipMemcpyDeviceToHost, st));
-        CAPCHK(hipMemcpyAsync(&nf, w->d_nfA, sizeof(nf), hipMemcpyDeviceToHost, st));
-        CAPCHK(hipStreamSynchronize(st));
+        PIRIP_HIPCHK(hipMemcpyAsync(&c, w->d_consA, sizeof(c), hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipMemcpyAsync(&nf, w->d_nfA, sizeof(nf), hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipStreamSynchronize(st));
         if (nf == Kp) grid0 = c - (int64_t)Kp * N;
         r.frames_demodulated += nf;
     }
@@ -541,7 +515,7 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
         CAP_H2D(w->d_src, src.data(), sizeof(int32_t) * src.size(), st);
         {   // where the chain ends, for the head's first sample
             CAP_H2D(w->d_posB + KEEP, &chain_pos, sizeof(int64_t), st);
-            CAPCHK(hipMemsetAsync(w->d_consB + KEEP, 0, sizeof(int64_t), st));
+            PIRIP_HIPCHK(hipMemsetAsync(w->d_consB + KEEP, 0, sizeof(int64_t), st));
         }
         hipError_t e = hipSuccess;
         if (nslots > 1) {
@@ -553,12 +527,12 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
                 ap.io = DemodIO{(const uint8_t *)d_in, 0, nsamp, nullptr, 0, nullptr, 0, w->d_warm_stats, 0, w->d_nfA, w->d_consA, F,
                                 SoftOut{nullptr, 0, nullptr, 0, nullptr, 0}, w->d_segA};
                 e = launch_demod_wave(ap, nslots, st);
-                if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+                PIRIP_HIPCHK(e);
             }
             a.io = DemodIO{(const uint8_t *)d_in, 0, nsamp, nullptr, 0, nullptr, 0, w->d_warm_stats, 0, w->d_nfA, w->d_consA, F,
                            SoftOut{nullptr, 0, nullptr, 0, nullptr, 0}, w->d_segA2};
             e = launch_demod_wave(a, nslots, st);
-            if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+            PIRIP_HIPCHK(e);
             hipLaunchKernelGGL(after_warmup_kernel, dim3(nslots), dim3(kThreads), 0, st, state, snap, (const SegDesc *)w->d_segA2, w->d_segB,
                                (const int64_t *)w->d_consA, w->d_posB, Ndft, hist_elems);
         }
@@ -568,14 +542,14 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
         a.io = DemodIO{(const uint8_t *)d_in, 0, nsamp, d_bits ? w->r_bits : nullptr, 0, d_rx_filt ? w->r_filt : nullptr, 0, w->r_stats, 0,
                        w->d_nfB, w->d_consB, F, SoftOut{nullptr, 0, nullptr, 0, nullptr, 0}, w->d_segB};
         e = launch_demod_wave(a, nslots, st);
-        if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
-        CAPCHK(hipGetLastError());
+        PIRIP_HIPCHK(e);
+        PIRIP_HIPCHK(hipGetLastError());
         std::vector<int64_t> pos((size_t)nslots), len((size_t)nslots);
         std::vector<int32_t> nfr((size_t)nslots);
-        CAPCHK(hipMemcpyAsync(pos.data(), w->d_posB, sizeof(int64_t) * nslots, hipMemcpyDeviceToHost, st));
-        CAPCHK(hipMemcpyAsync(len.data(), w->d_consB, sizeof(int64_t) * nslots, hipMemcpyDeviceToHost, st));
-        CAPCHK(hipMemcpyAsync(nfr.data(), w->d_nfB, sizeof(int32_t) * nslots, hipMemcpyDeviceToHost, st));
-        CAPCHK(hipStreamSynchronize(st));
+        PIRIP_HIPCHK(hipMemcpyAsync(pos.data(), w->d_posB, sizeof(int64_t) * nslots, hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipMemcpyAsync(len.data(), w->d_consB, sizeof(int64_t) * nslots, hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipMemcpyAsync(nfr.data(), w->d_nfB, sizeof(int32_t) * nslots, hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipStreamSynchronize(st));
         for (int q = 0; q < nslots; q++) r.frames_demodulated += nfr[q] + (mode[q] == 1 ? F : 0);
         if (r.passes > 1) r.segments_rerun += nslots;
         // walk the chain by sample position: from the head through the replica of each next segment that starts where this one ended
@@ -599,9 +573,9 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
             hipLaunchKernelGGL(verify_kernel, dim3(np), dim3(kThreads), 0, st, state, snap, (const int64_t *)w->d_posB, (const int64_t *)w->d_consB,
                                (const int32_t *)w->d_ok, w->d_ok + pq.size(), Ndft, hist_elems, d.M,
                                d.est_band ? Ndft / 2 : 0, d.est_band ? Ndft / 2 + 16 * d.est_band : Ndft);
-            CAPCHK(hipGetLastError());
-            CAPCHK(hipMemcpyAsync(okv.data(), w->d_ok + pq.size(), sizeof(int32_t) * np, hipMemcpyDeviceToHost, st));
-            CAPCHK(hipStreamSynchronize(st));
+            PIRIP_HIPCHK(hipGetLastError());
+            PIRIP_HIPCHK(hipMemcpyAsync(okv.data(), w->d_ok + pq.size(), sizeof(int32_t) * np, hipMemcpyDeviceToHost, st));
+            PIRIP_HIPCHK(hipStreamSynchronize(st));
             for (int i = 0; i < np; i++) if (okv[i]) { why = okv[i]; chain.resize((size_t)i + 1); break; }
         }
         const int na = (int)chain.size(), nv = v + na;
@@ -625,7 +599,7 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
                            (int)fb, filt_floats, (const uint8_t *)w->r_bits, d_bits, (const float *)w->r_filt, d_rx_filt, (const float *)w->r_stats, stats);
         const int ql = chain.back();
         hipLaunchKernelGGL(copy_state_kernel, dim3(1), dim3(kThreads), 0, st, state, KEEP, ql, Ndft, hist_elems);
-        CAPCHK(hipGetLastError());
+        PIRIP_HIPCHK(hipGetLastError());
         chain_pos = pos[ql] + len[ql];
         if (nv == S || nfr[ql] < F) {                      // the last segment, or the one the samples (or the output rows) ran out in
             total_frames = (int64_t)(nv - 1) * F + nfr[ql];
@@ -646,19 +620,19 @@ static int capture_impl(pirip_hip_demod *h, const void *d_in, int64_t nsamp, uin
         a.io = DemodIO{(const uint8_t *)d_in, 0, nsamp, d_bits, 0, d_rx_filt, 0, stats, 0, w->d_nfB, w->d_consB, F,
                        SoftOut{nullptr, 0, nullptr, 0, nullptr, 0}, w->d_segB};
         hipError_t e = launch_demod_wave(a, 1, st);
-        if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+        PIRIP_HIPCHK(e);
         hipLaunchKernelGGL(copy_state_kernel, dim3(1), dim3(kThreads), 0, st, state, KEEP, 0, Ndft, hist_elems);
         int32_t nf = 0; int64_t c = 0;
-        CAPCHK(hipMemcpyAsync(&nf, w->d_nfB, sizeof(nf), hipMemcpyDeviceToHost, st));
-        CAPCHK(hipMemcpyAsync(&c, w->d_consB, sizeof(c), hipMemcpyDeviceToHost, st));
-        CAPCHK(hipStreamSynchronize(st));
+        PIRIP_HIPCHK(hipMemcpyAsync(&nf, w->d_nfB, sizeof(nf), hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipMemcpyAsync(&c, w->d_consB, sizeof(c), hipMemcpyDeviceToHost, st));
+        PIRIP_HIPCHK(hipStreamSynchronize(st));
         total_frames += nf; total_consumed += c; r.frames_demodulated += nf;
     }
     // the capture's end state becomes the stream's (slot 0), with ppm recomputed in frame order
     hipLaunchKernelGGL(copy_state_kernel, dim3(1), dim3(kThreads), 0, st, state, 0, final_slot, Ndft, hist_elems);
     hipLaunchKernelGGL(ppm_kernel, dim3(1), dim3(256), 0, st, stats, total_frames, (const StreamScalars *)w->d_scal0, h->d_scal, d.Nsym);
-    CAPCHK(hipGetLastError());
-    CAPCHK(hipStreamSynchronize(st));
+    PIRIP_HIPCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipStreamSynchronize(st));
     if (nframes_out) *nframes_out = total_frames;
     if (consumed_out) *consumed_out = total_consumed;
     if (rep) *rep = r;
@@ -675,33 +649,23 @@ extern "C" int pirip_hip_demod_capture_host(pirip_hip_demod *h, const void *in, 
     if (rc != PIRIP_OK) return rc;
     CaptureWork *w = h->capture;
     const FskDims &d = h->plan.d;
-    const size_t bps = d.in_format == PIRIP_IN_CF32 ? 8 : d.in_format == PIRIP_IN_CS16 ? 4 : 2;
-    const size_t in_bytes = (size_t)nsamp * bps;
-    if (in_bytes > w->in_bytes || !w->d_in) {
-        if (w->d_in) (void)hipFree(w->d_in);
-        w->d_in = nullptr; w->in_bytes = 0;
-        CAPCHK(hipMalloc(&w->d_in, in_bytes + 64));
-        w->in_bytes = in_bytes;
-    }
+    const size_t in_bytes = (size_t)nsamp * (size_t)bytes_per_sample(d.in_format);
+    if (in_bytes > w->in_bytes || !w->d_in)
+        PIRIP_TRY(grow_dev(w->mem, &w->in_bytes, in_bytes, GrowSync::none, nullptr, {grow_buf(&w->d_in, in_bytes + 64)}));
     const size_t fb = d.pack_bits ? (size_t)(d.Nbits + 7) / 8 : (size_t)d.Nbits;
-    if (max_frames > w->out_frames) {
-        void *olds[] = {w->d_bits, w->d_filt, w->d_ostats};
-        for (void *p : olds) if (p) (void)hipFree(p);
-        w->d_bits = nullptr; w->d_filt = nullptr; w->d_ostats = nullptr; w->out_frames = 0;
-        CAPCHK(hipMalloc((void **)&w->d_bits, (size_t)max_frames * fb + 16));
-        CAPCHK(hipMalloc((void **)&w->d_filt, sizeof(float) * (size_t)max_frames * d.M * d.Nsym + 16));
-        CAPCHK(hipMalloc((void **)&w->d_ostats, sizeof(float) * (size_t)max_frames * PIRIP_STATS_PER_FRAME + 16));
-        w->out_frames = max_frames;
-    }
-    if (in_bytes) CAPCHK(hipMemcpy(w->d_in, in, in_bytes, hipMemcpyHostToDevice));
+    if (max_frames > w->out_frames)
+        PIRIP_TRY(grow_dev(w->mem, &w->out_frames, max_frames, GrowSync::none, nullptr,
+                           {grow_buf(&w->d_bits, (size_t)max_frames * fb + 16), grow_buf(&w->d_filt, sizeof(float) * (size_t)max_frames * d.M * d.Nsym + 16),
+                            grow_buf(&w->d_ostats, sizeof(float) * (size_t)max_frames * PIRIP_STATS_PER_FRAME + 16)}));
+    if (in_bytes) PIRIP_HIPCHK(hipMemcpy(w->d_in, in, in_bytes, hipMemcpyHostToDevice));
     int64_t nf = 0, cons = 0;
     rc = pirip_hip_demod_capture(h, w->d_in, nsamp, w->d_bits, rx_filt ? w->d_filt : nullptr, w->d_ostats, max_frames, &nf, &cons, rep, nullptr);
     if (rc != PIRIP_OK) return rc;
-    if (nf) CAPCHK(hipMemcpy(bits, w->d_bits, (size_t)nf * fb, hipMemcpyDeviceToHost));
-    if (rx_filt && nf) CAPCHK(hipMemcpy(rx_filt, w->d_filt, sizeof(float) * (size_t)nf * d.M * d.Nsym, hipMemcpyDeviceToHost));
-    if (stats && nf) CAPCHK(hipMemcpy(stats, w->d_ostats, sizeof(float) * (size_t)nf * PIRIP_STATS_PER_FRAME, hipMemcpyDeviceToHost));
+    if (nf) PIRIP_HIPCHK(hipMemcpy(bits, w->d_bits, (size_t)nf * fb, hipMemcpyDeviceToHost));
+    if (rx_filt && nf) PIRIP_HIPCHK(hipMemcpy(rx_filt, w->d_filt, sizeof(float) * (size_t)nf * d.M * d.Nsym, hipMemcpyDeviceToHost));
+    if (stats && nf) PIRIP_HIPCHK(hipMemcpy(stats, w->d_ostats, sizeof(float) * (size_t)nf * PIRIP_STATS_PER_FRAME, hipMemcpyDeviceToHost));
     StreamScalars sc;
-    CAPCHK(hipMemcpy(&sc, h->d_scal, sizeof(sc), hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(&sc, h->d_scal, sizeof(sc), hipMemcpyDeviceToHost));
     h->nin0 = sc.nin;
     if (nframes_out) *nframes_out = nf;
     if (consumed_out) *consumed_out = cons;

@@ -28,6 +28,7 @@
 
 #include "../../include/pirip_hip.h"
 #include "fsk_plan.hpp"
+#include "hip_host.hpp"
 
 using namespace pirip;
 
@@ -226,18 +227,13 @@ struct pirip_hip_chan {
     float c_hi = 0.f, c_lo = 0.f;
     std::vector<float> h;                  // prototype taps (L)
     std::vector<int32_t> input, offset;    // per channel
+    DevMem mem;
     dv4f *d_taps = nullptr;
     ChanGroup *d_groups = nullptr;
     int32_t *d_in_groups = nullptr, *d_fcm = nullptr, *d_sc = nullptr;
 };
 
 namespace {
-
-void chan_free(pirip_hip_chan *ch)
-{
-    void *ptrs[] = {ch->d_taps, ch->d_groups, ch->d_in_groups, ch->d_fcm, ch->d_sc};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-}
 
 // outputs per tile (T), its padding to whole waves (Tpad) and the staged window's LDS bytes
 size_t chan_lds(int Tpad, int D, int Lp, int P) { return ((size_t)Tpad + (Lp + D - 1) / D) * (size_t)P * sizeof(dv2f); }
@@ -257,12 +253,11 @@ int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s
         if (2 * (int64_t)chan_offset_hz[c] <= -(int64_t)Fs || 2 * (int64_t)chan_offset_hz[c] >= (int64_t)Fs) return PIRIP_ERR_BAD_ARG;
     }
     if (Fs > kMaxFs) return PIRIP_ERR_UNSUPPORTED;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PIRIP_ERR_NO_DEVICE;
-    if (device >= 0 && (device >= ndev || hipSetDevice(device) != hipSuccess)) return PIRIP_ERR_NO_DEVICE;
+    int dev = 0;
+    PIRIP_TRY(select_device(device, &dev));
     pirip_hip_chan *ch = new (std::nothrow) pirip_hip_chan();
     if (!ch) return PIRIP_ERR_NOMEM;
-    if (hipGetDevice(&ch->device) != hipSuccess) { delete ch; return PIRIP_ERR_NO_DEVICE; }
+    ch->device = dev;
     ch->Fs = Fs; ch->D = decimation; ch->out_s16 = out_s16 ? 1 : 0; ch->ninputs = ninputs; ch->nchan = nchan;
     // section B's prototype: csdr's Hamming low-pass, cutoff 0.5 / D, padded with zeros to a multiple of 4
     ch->L = csdr_filter_len(transition_bw);
@@ -320,21 +315,18 @@ int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s
                 taps[((size_t)g * Lp + i) * kMaxGroup + m] = dv4f{gr, gi, -gi, gr};
             }
         }
-    const size_t ngr = groups.size();
-    bool ok = hipMalloc((void **)&ch->d_taps, sizeof(dv4f) * taps.size()) == hipSuccess &&
-              hipMalloc((void **)&ch->d_groups, sizeof(ChanGroup) * ngr) == hipSuccess &&
-              hipMalloc((void **)&ch->d_in_groups, sizeof(int32_t) * in_groups.size()) == hipSuccess &&
-              hipMalloc((void **)&ch->d_fcm, sizeof(int32_t) * nchan) == hipSuccess &&
-              hipMalloc((void **)&ch->d_sc, sizeof(int32_t) * nchan) == hipSuccess;
-    if (!ok) { chan_free(ch); delete ch; return PIRIP_ERR_NOMEM; }
-    ok = hipMemcpy(ch->d_taps, taps.data(), sizeof(dv4f) * taps.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ch->d_groups, groups.data(), sizeof(ChanGroup) * ngr, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ch->d_in_groups, in_groups.data(), sizeof(int32_t) * in_groups.size(), hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ch->d_fcm, fcm.data(), sizeof(int32_t) * nchan, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(ch->d_sc, sc.data(), sizeof(int32_t) * nchan, hipMemcpyHostToDevice) == hipSuccess;
-    if (ok && ch->lds > 64 * 1024)
-        ok = hipFuncSetAttribute((const void *)chan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ch->lds) == hipSuccess;
-    if (!ok) { chan_free(ch); delete ch; return PIRIP_ERR_HIP; }
+    auto tables = [&]() -> int {
+        DevMem &m = ch->mem;
+        PIRIP_TRY(m.upload(&ch->d_taps, taps.data(), sizeof(dv4f) * taps.size()));
+        PIRIP_TRY(m.upload(&ch->d_groups, groups.data(), sizeof(ChanGroup) * groups.size()));
+        PIRIP_TRY(m.upload(&ch->d_in_groups, in_groups.data(), sizeof(int32_t) * in_groups.size()));
+        PIRIP_TRY(m.upload(&ch->d_fcm, fcm.data(), sizeof(int32_t) * nchan));
+        PIRIP_TRY(m.upload(&ch->d_sc, sc.data(), sizeof(int32_t) * nchan));
+        if (ch->lds > 64 * 1024) PIRIP_HIPCHK(hipFuncSetAttribute((const void *)chan_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)ch->lds));
+        return PIRIP_OK;
+    };
+    const int rc = tables();
+    if (rc != PIRIP_OK) { delete ch; return rc; }
     *out = ch;
     return PIRIP_OK;
 }
@@ -342,9 +334,8 @@ int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s
 int pirip_hip_chan_destroy(pirip_hip_chan *ch)
 {
     if (!ch) return PIRIP_ERR_BAD_ARG;
-    (void)hipSetDevice(ch->device);
+    (void)bind_device(ch->device);
     (void)hipDeviceSynchronize();
-    chan_free(ch);
     delete ch;
     return PIRIP_OK;
 }
@@ -379,8 +370,7 @@ int pirip_hip_chan_batch(pirip_hip_chan *ch, const uint8_t *d_in, size_t in_stri
     if (((uintptr_t)d_out | out_stride_bytes) & (bps - 1)) return PIRIP_ERR_BAD_ARG;
     const int64_t n_out = pirip_hip_chan_nout(ch, n_in);
     if (n_out <= 0) return PIRIP_OK;
-    int cur = -1;
-    if ((hipGetDevice(&cur) != hipSuccess || cur != ch->device) && hipSetDevice(ch->device) != hipSuccess) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(ch->device)) return PIRIP_ERR_NO_DEVICE;
     const int64_t ntiles = (n_out + ch->T - 1) / ch->T;
     if (ntiles > 0x7fffffff || (2 * n_in) > ((int64_t)1 << 46)) return PIRIP_ERR_UNSUPPORTED;
     ChanArgs a{};

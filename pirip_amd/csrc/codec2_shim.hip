@@ -22,6 +22,7 @@
 #include "../../include/pirip_hip.h"
 #include "fsk_ldpc.hpp"
 #include "fsk_plan.hpp"
+#include "hip_host.hpp"
 
 using namespace pirip;
 
@@ -281,6 +282,7 @@ struct freedv {
     LdpcCode code;                              // host copy: Tx framer, frame sizes, the test-frame payload
     std::string code_path;
     std::vector<uint8_t> tf_bytes;
+    DevMem mem;                                 // owns the staging buffers below
     void *d_in = nullptr; size_t d_in_bytes = 0;
     uint8_t *d_status = nullptr, *d_payload = nullptr; int32_t *d_info = nullptr, *d_nfr = nullptr; int64_t *d_cons = nullptr; float *d_stats = nullptr;
     long frame_periods = 0, period_bits = 0, period_rem = 0;   // freedv_set_verbose: upstream's cycling bit counter (rtl_fsk.cpp does the same)
@@ -302,10 +304,16 @@ std::string find_code(const char *name)
     }
     return "";
 }
-void free_dev(struct freedv *f)
+// the one-frame staging buffers behind freedv_rawdatacomprx
+int alloc_staging(struct freedv *f)
 {
-    void *ptrs[] = {f->d_in, f->d_status, f->d_payload, f->d_info, f->d_nfr, f->d_cons, f->d_stats};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
+    DevMem &m = f->mem;
+    PIRIP_TRY(m.alloc(&f->d_status, 16));
+    PIRIP_TRY(m.alloc(&f->d_payload, (size_t)f->li.data_bytes + 16));
+    PIRIP_TRY(m.alloc(&f->d_info, sizeof(int32_t) * PIRIP_LDPC_INFO_PER_CALL));
+    PIRIP_TRY(m.alloc(&f->d_nfr, 16));
+    PIRIP_TRY(m.alloc(&f->d_cons, 16));
+    return m.alloc(&f->d_stats, sizeof(float) * PIRIP_STATS_PER_FRAME);
 }
 }  // namespace
 
@@ -357,7 +365,7 @@ void freedv_close(struct freedv *f)
 {
     if (!f) return;
     if (f->ldpc) pirip_hip_ldpc_destroy(f->ldpc);
-    free_dev(f);
+    f->mem.free_all();
     if (f->fsk) fsk_destroy(f->fsk);
     delete f;
 }
@@ -394,18 +402,15 @@ int freedv_rawdatacomprx(struct freedv *f, unsigned char *packed_payload_bits, C
         rc = pirip_hip_ldpc_create(f->code_path.c_str(), f->M, fsk->Nsym, 1, -1, &f->ldpc);
         if (rc != PIRIP_OK) die("pirip_hip_ldpc_create", rc);
         pirip_hip_ldpc_get_info(f->ldpc, &f->li);
-        bool ok = hipMalloc((void **)&f->d_status, 16) == hipSuccess && hipMalloc((void **)&f->d_payload, (size_t)f->li.data_bytes + 16) == hipSuccess &&
-                  hipMalloc((void **)&f->d_info, sizeof(int32_t) * PIRIP_LDPC_INFO_PER_CALL) == hipSuccess && hipMalloc((void **)&f->d_nfr, 16) == hipSuccess &&
-                  hipMalloc((void **)&f->d_cons, 16) == hipSuccess && hipMalloc((void **)&f->d_stats, sizeof(float) * PIRIP_STATS_PER_FRAME) == hipSuccess;
-        if (!ok) die("hipMalloc", PIRIP_ERR_NOMEM);
+        rc = alloc_staging(f);
+        if (rc != PIRIP_OK) die("hipMalloc", rc);
     }
     const int nin = fsk->nin;
     const size_t bytes = sizeof(COMP) * (size_t)nin;
     if (bytes > f->d_in_bytes) {
-        if (f->d_in) (void)hipFree(f->d_in);
-        f->d_in = nullptr; f->d_in_bytes = 0;
-        if (hipMalloc(&f->d_in, sizeof(COMP) * (size_t)freedv_get_n_max_modem_samples(f) + 64) != hipSuccess) die("hipMalloc", PIRIP_ERR_NOMEM);
-        f->d_in_bytes = sizeof(COMP) * (size_t)freedv_get_n_max_modem_samples(f);
+        const size_t most = sizeof(COMP) * (size_t)freedv_get_n_max_modem_samples(f);
+        rc = grow_dev(f->mem, &f->d_in_bytes, most, GrowSync::none, nullptr, {grow_buf(&f->d_in, most + 64)});
+        if (rc != PIRIP_OK) die("hipMalloc", rc);
     }
     if (hipMemcpy(f->d_in, demod_in, bytes, hipMemcpyHostToDevice) != hipSuccess) die("hipMemcpy", PIRIP_ERR_HIP);
     rc = pirip_hip_fsk_ldpc_rx_batch(p->dev, f->ldpc, f->d_in, 0, nin, f->d_status, f->d_payload, f->d_info, f->d_stats, 0, f->d_nfr, f->d_cons, 1, nullptr);

@@ -44,6 +44,7 @@
 
 #include "../../include/pirip_hip.h"
 #include "fsk_plan.hpp"
+#include "hip_host.hpp"
 
 using namespace pirip;
 
@@ -430,6 +431,8 @@ void host_elementwise(const char *name, const TI *in, TO *out, int n, F launch)
 
 }  // namespace
 
+// (hidden: a handle's implicit destructor is no dynamic symbol of the library)
+#pragma GCC visibility push(hidden)
 struct pirip_hip_decim {
     int D = 0, L = 0, Lp = 0, out_s16 = 0, tile = 0, device = 0;
     size_t lds = 0;
@@ -440,8 +443,10 @@ struct pirip_hip_decim {
     int tile_sh = 0; size_t lds_sh = 0;
     float tap_sum = 0.f;
     std::vector<float> taps;
+    DevMem mem;
     float *d_taps = nullptr, *d_lut = nullptr;
 };
+#pragma GCC visibility pop
 
 extern "C" {
 
@@ -449,13 +454,11 @@ int pirip_hip_decim_create(int decimation, float transition_bw, int out_s16, int
 {
     if (!out || decimation < 1 || !(transition_bw > 0.f)) return PIRIP_ERR_BAD_ARG;
     *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PIRIP_ERR_NO_DEVICE;
-    if (device >= 0 && (device >= ndev || hipSetDevice(device) != hipSuccess)) return PIRIP_ERR_NO_DEVICE;
+    int dev = 0;
+    PIRIP_TRY(select_device(device, &dev));
     pirip_hip_decim *d = new (std::nothrow) pirip_hip_decim();
     if (!d) return PIRIP_ERR_NOMEM;
-    d->D = decimation; d->out_s16 = out_s16 ? 1 : 0;
-    if (hipGetDevice(&d->device) != hipSuccess) { delete d; return PIRIP_ERR_NO_DEVICE; }
+    d->D = decimation; d->out_s16 = out_s16 ? 1 : 0; d->device = dev;
     d->L = csdr_filter_len(transition_bw);
     // csdr pads the taps with zeros to a multiple of 4 and uses the padded length in the
     // "enough input left" test; zero taps add +0 and are skipped in the kernel.
@@ -471,11 +474,9 @@ int pirip_hip_decim_create(int decimation, float transition_bw, int out_s16, int
              ((2 * ((size_t)(tile - 1) * d->D + d->L) + 47) & ~(size_t)15);
     std::vector<float> lut(256);
     for (int x = 0; x < 256; x++) lut[x] = ((float)x) / (UCHAR_MAX / 2.0) - 1.0;   // convert_u8_f
-    bool ok = hipMalloc((void **)&d->d_taps, sizeof(float) * d->L) == hipSuccess &&
-              hipMalloc((void **)&d->d_lut, sizeof(float) * 256) == hipSuccess &&
-              hipMemcpy(d->d_taps, d->taps.data(), sizeof(float) * d->L, hipMemcpyHostToDevice) == hipSuccess &&
-              hipMemcpy(d->d_lut, lut.data(), sizeof(float) * 256, hipMemcpyHostToDevice) == hipSuccess;
-    if (!ok) { if (d->d_taps) (void)hipFree(d->d_taps); if (d->d_lut) (void)hipFree(d->d_lut); delete d; return PIRIP_ERR_NOMEM; }
+    int rc = d->mem.upload(&d->d_taps, d->taps.data(), sizeof(float) * d->L);
+    if (rc == PIRIP_OK) rc = d->mem.upload(&d->d_lut, lut.data(), sizeof(float) * 256);
+    if (rc != PIRIP_OK) { delete d; return rc; }
     // arithmetic u8->float must reproduce csdr's double formula for every byte value, else keep the table
     {
         d->c_hi = (float)(std::nearbyint((1.0 / 127.5) * 4194304.0) / 4194304.0);
@@ -503,7 +504,7 @@ int pirip_hip_decim_create(int decimation, float transition_bw, int out_s16, int
     }
     if (d->lds > 64 * 1024 &&
         hipFuncSetAttribute((const void *)decim_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)d->lds) != hipSuccess) {
-        (void)hipFree(d->d_taps); (void)hipFree(d->d_lut); delete d; return PIRIP_ERR_HIP;
+        delete d; return PIRIP_ERR_HIP;
     }
     *out = d;
     return PIRIP_OK;
@@ -512,8 +513,8 @@ int pirip_hip_decim_create(int decimation, float transition_bw, int out_s16, int
 int pirip_hip_decim_destroy(pirip_hip_decim *d)
 {
     if (!d) return PIRIP_ERR_BAD_ARG;
+    (void)bind_device(d->device);
     (void)hipDeviceSynchronize();
-    (void)hipFree(d->d_taps); (void)hipFree(d->d_lut);
     delete d;
     return PIRIP_OK;
 }
@@ -547,8 +548,7 @@ int pirip_hip_decim_batch(pirip_hip_decim *d, const uint8_t *d_in, size_t in_str
     if (!d || !d_in || !d_out || nstreams <= 0 || n_in < 0) return PIRIP_ERR_BAD_ARG;
     const int64_t n_out = pirip_hip_decim_nout(d, n_in);
     if (n_out <= 0) return PIRIP_OK;
-    int cur = -1;   // run on the device the stage was created on
-    if ((hipGetDevice(&cur) != hipSuccess || cur != d->device) && hipSetDevice(d->device) != hipSuccess) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(d->device)) return PIRIP_ERR_NO_DEVICE;   // run on the device the stage was created on
     // the shape-specialised kernel (every sample converted once per wave) where it exists: exact arithmetic, 16-bit aligned windows
     const bool sh = d->shared && d->mode == kDecimExact && !(((uintptr_t)d_in | (uintptr_t)in_stride_bytes) & 1);
     const int tile = sh ? d->tile_sh : d->tile;

@@ -6,14 +6,17 @@
 
 #include "fsk_device.hpp"
 #include "fsk_plan.hpp"
+#include "hip_host.hpp"
 
 struct CaptureWork;
 
+// (hidden: a handle's implicit destructor is no dynamic symbol of the library)
+#pragma GCC visibility push(hidden)
 struct pirip_hip_demod {
     pirip::FskPlan plan;
     int nstreams = 0;
     int device = 0;
-    int last_hip = 0;
+    pirip::DevMem mem;                          // owns every d_* below
     // Kernel of this handle, chosen ONCE at create (the kernels keep the integrator-memory tail in different layouts,
     // so a handle never switches): 2 = wave-per-stream (fsk_demod_wave.hip), 0 = general (fsk_demod_general.hip).
     // PIRIP_KERNEL=general (or the older PIRIP_FORCE_GENERAL) forces the general kernel: the on-device cross-check.
@@ -37,6 +40,7 @@ struct pirip_hip_demod {
     float *d_eye = nullptr;                     // pirip_hip_enable_eye: [nstreams][8][160] |f_int| eye traces of each stream's latest frame
     struct CaptureWork *capture = nullptr;      // capture.hip: work area of pirip_hip_demod_capture, allocated on first use
 };
+#pragma GCC visibility pop
 
 namespace pirip {
 void demod_fill_args(const pirip_hip_demod *h, DemodArgs *a);   // dims, tables, state pointers (io left to the caller)

@@ -738,9 +738,9 @@ int launch_decode(pirip_hip_ldpc *h, int slots, int nstreams_y, const int32_t *j
         const FastDev fd{h->d_rcol, h->d_vedge, h->d_vsrc, h->layout.maxdeg};
         const BankDev bk{h->d_vcrc, h->crc0, (uint32_t)cps, (uint32_t)((((uint64_t)1 << 32) + (uint64_t)cps - 1) / (uint64_t)cps)};
         const auto kern = deg == 6 ? decode_bank_kernel<8, 6, kFastColDeg> : decode_bank_kernel<8, kFastRowDeg, kFastColDeg>;
-        LCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        PIRIP_HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, g, b, lds, st, h->dev, fd, bk, slots, nstreams_y, jobs, njobs, llr, llr_stride, direct, status, ncalls, payload, info, cw, ip);
-        LCHK(hipGetLastError());
+        PIRIP_HIPCHK(hipGetLastError());
         return PIRIP_OK;
     }
     if (h->layout.ok && h->decoder_pref != kDecGeneric && h->fast_static_lds == 0) {
@@ -754,9 +754,9 @@ int launch_decode(pirip_hip_ldpc *h, int slots, int nstreams_y, const int32_t *j
 #define PIRIP_FAST(W) (h->fast_deg() == 6 ? decode_fast_kernel<W, 6, kFastColDeg> : decode_fast_kernel<W, kFastRowDeg, kFastColDeg>)
         const auto kern = wpb == 4 ? PIRIP_FAST(4) : wpb == 2 ? PIRIP_FAST(2) : PIRIP_FAST(1);
 #undef PIRIP_FAST
-        if (lds > 48 * 1024) LCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        if (lds > 48 * 1024) PIRIP_HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
         hipLaunchKernelGGL(kern, g, b, lds, st, h->dev, fd, slots, jobs, njobs, llr, llr_stride, direct, status, ncalls, payload, info, cw, ip);
-        LCHK(hipGetLastError());
+        PIRIP_HIPCHK(hipGetLastError());
         return PIRIP_OK;
     }
     int wpb = 8;
@@ -770,9 +770,9 @@ int launch_decode(pirip_hip_ldpc *h, int slots, int nstreams_y, const int32_t *j
 #define PIRIP_DEC(W) (regidx ? decode_kernel<W, true> : decode_kernel<W, false>)
     const auto kern = wpb == 8 ? PIRIP_DEC(8) : wpb == 4 ? PIRIP_DEC(4) : wpb == 2 ? PIRIP_DEC(2) : PIRIP_DEC(1);
 #undef PIRIP_DEC
-    if (lds > 48 * 1024) LCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    if (lds > 48 * 1024) PIRIP_HIPCHK(hipFuncSetAttribute((const void *)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL(kern, g, b, lds, st, h->dev, slots, jobs, njobs, llr, llr_stride, direct, status, ncalls, payload, info, cw, ip);
-    LCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;
 }
 

@@ -8,18 +8,20 @@
 
 #include "fsk_device.hpp"
 #include "fsk_ldpc.hpp"
+#include "hip_host.hpp"
 #include "ldpc_device.hpp"
 
 enum { kDecAuto = 0, kDecGeneric = 1, kDecFast = 2, kDecBank = 3 };
 struct pirip_hip_ldpc {
     pirip::LdpcCode code;
     LdpcDev dev{};
+    pirip::DevMem mem;                         // owns every d_* below
     pirip::DecoderLayout layout;               // fast decoder's storage layout (host), device copies below
     uint16_t *d_rcol = nullptr, *d_vedge = nullptr, *d_vsrc = nullptr;
     uint16_t *d_vcrc = nullptr; uint32_t crc0 = 0;   // persistent decoder: CRC term of the bit at each storage index, CRC of the all-zero word
     // two builds of the fast decoder: row weight <= 6 (the FSK_LDPC code's shape: 4 data ones + the accumulator's 2), or the limit 8
     int fast_deg() const { return layout.maxdeg <= 6 ? 6 : pirip::kFastRowDeg; }
-    int nstreams = 0, device = 0, last_hip = 0;
+    int nstreams = 0, device = 0;
     // internal HIP streams and events of the fork / join paths (this handle's own: two receivers driven from two host threads do not
     // meet on them; made on first use, destroyed with the handle). Slots 0 / 1: the two stream ranges of one call (low / high
     // priority); slots 2 ..: the groups of pirip_hip_fsk_ldpc_rx_batch_groups (2: the last group, low priority; the others high) --
@@ -47,18 +49,9 @@ struct pirip_hip_ldpc {
     // host staging for the one-stream convenience entry
     float *d_h_filt = nullptr; uint8_t *d_h_status = nullptr, *d_h_payload = nullptr; int32_t *d_h_info = nullptr; size_t h_cap = 0;
     // direct-decode staging
-    uint16_t *d_dd_llr = nullptr; uint8_t *d_dd_bits = nullptr; int32_t *d_dd_ip = nullptr; size_t dd_cap = 0;
+    uint16_t *d_dd_llr = nullptr; size_t dd_cap = 0;
     size_t lds_bytes(int wpb) const { return dec_lds_bytes(code.m, code.n, (int)code.col_idx.size(), wpb); }   // of the generic decoder
 };
-
-#define LCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { h->last_hip = (int)e_; return PIRIP_ERR_HIP; } } while (0)
-
-static inline bool bind_dev(const pirip_hip_ldpc *h)
-{
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur == h->device) return true;
-    return hipSetDevice(h->device) == hipSuccess;
-}
 
 // Launches, on stream st, for receivers that the caller has already sliced its per-receiver arrays to. The void ones leave the launch's
 // error to the caller's hipGetLastError(). (Hidden: not part of the library's dynamic symbols.)

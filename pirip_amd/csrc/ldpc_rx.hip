@@ -7,38 +7,12 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <initializer_list>
 #include <new>
 #include <vector>
 
 #include "ldpc_handle.hpp"
 
 using namespace pirip;
-
-namespace {
-
-template <typename T>
-bool up(T **dst, const void *src, size_t bytes)
-{
-    if (hipMalloc((void **)dst, bytes ? bytes : 16) != hipSuccess) return false;
-    return !bytes || hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice) == hipSuccess;
-}
-
-// Grow-on-demand device buffers to a capacity of `want`: wait for the work that may still use the old ones (sync: st), free them, null
-// them and the capacity, allocate anew, then record the capacity -- a failed allocation leaves the capacity at 0 and the rest null.
-struct GrowBuf { void **p; size_t bytes; };
-template <typename T> GrowBuf grow_buf(T **p, size_t bytes) { return GrowBuf{(void **)p, bytes}; }
-int grow_dev(pirip_hip_ldpc *h, size_t *cap, size_t want, bool sync, hipStream_t st, std::initializer_list<GrowBuf> bufs)
-{
-    if (sync) LCHK(hipStreamSynchronize(st));
-    for (const GrowBuf &b : bufs) { if (*b.p) (void)hipFree(*b.p); *b.p = nullptr; }
-    *cap = 0;
-    for (const GrowBuf &b : bufs) LCHK(hipMalloc(b.p, b.bytes));
-    *cap = want;
-    return PIRIP_OK;
-}
-
-}  // namespace
 
 // (C linkage: the library has always exported these five names -- batch_dims, ensure_work, stages_after_llr, side_stream, side_events --
 //  and its dynamic symbol table stays as it is here)
@@ -61,7 +35,7 @@ int ensure_work(pirip_hip_ldpc *h, int ncalls, hipStream_t st)
     if ((size_t)ncalls <= h->cap_calls) return PIRIP_OK;
     const size_t ns = (size_t)h->nstreams;
     const BatchDims bd = batch_dims(h->dev, ncalls);
-    return grow_dev(h, &h->cap_calls, (size_t)ncalls, true, st,
+    return grow_dev(h->mem, &h->cap_calls, (size_t)ncalls, GrowSync::stream, st,
                     {grow_buf(&h->d_llr_all, sizeof(uint16_t) * ns * bd.nbits_total + 16), grow_buf(&h->d_words, sizeof(uint32_t) * ns * bd.nwords),
                      grow_buf(&h->d_best, sizeof(uint32_t) * ns * ncalls), grow_buf(&h->d_jobs, sizeof(int32_t) * ns * bd.max_jobs * 2),
                      grow_buf(&h->d_njobs, sizeof(int32_t) * ns)});
@@ -85,14 +59,14 @@ int stages_after_llr(pirip_hip_ldpc *h, const int32_t *d_ncalls, int ncalls, uin
     uint16_t *llr_all = h->d_llr_all + z * llr_stride, *llr_hist = h->d_llr_hist + z * (size_t)(2 * c.bpf);
     if (d_ncalls) d_ncalls += z;
     d_status += z * ncalls; d_payload += z * ncalls * (size_t)(c.k / 8); d_info += z * ncalls * kInfoPerCall;
-    LCHK(hipMemsetAsync(d_payload, 0, ns * ncalls * (size_t)(c.k / 8), st));
+    PIRIP_HIPCHK(hipMemsetAsync(d_payload, 0, ns * ncalls * (size_t)(c.k / 8), st));
     int rc = launch_sync(h, s0, n, st, ncalls, d_ncalls, words, nwords, nbits_total, best, d_status, d_info, jobs, njobs, max_jobs);
     if (rc != PIRIP_OK) return rc;
-    if (sdec && ev) { LCHK(hipEventRecord(ev, st)); LCHK(hipStreamWaitEvent(sdec, ev, 0)); st = sdec; }
+    if (sdec && ev) { PIRIP_HIPCHK(hipEventRecord(ev, st)); PIRIP_HIPCHK(hipStreamWaitEvent(sdec, ev, 0)); st = sdec; }
     rc = launch_decode(h, max_jobs, n, jobs, njobs, llr_all, llr_stride, 0, d_status, ncalls, d_payload, d_info, nullptr, nullptr, st, beside_demod);
     if (rc != PIRIP_OK) return rc;
     launch_save_hist(n, st, llr_all, llr_stride, ncalls, d_ncalls, c.Nbits, c.bpf, llr_hist);
-    LCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;
 }
 
@@ -139,9 +113,7 @@ int pirip_hip_ldpc_create(const char *code_path, int M, int Nsym, int nstreams, 
     const int Nbits = Nsym * (M == 2 ? 1 : 2);
     if (Nbits > c.bits_per_frame()) { delete h; return PIRIP_ERR_BAD_CONFIG; }   // the sync logic assumes < one frame of bits per call
     if (c.col_idx.size() > 65535 || h->lds_bytes(1) > 160 * 1024) { delete h; return PIRIP_ERR_UNSUPPORTED; }
-    if (pirip_hip_device_count() <= 0) { delete h; return PIRIP_ERR_NO_DEVICE; }
-    if (device >= 0 && hipSetDevice(device) != hipSuccess) { delete h; return PIRIP_ERR_NO_DEVICE; }
-    if (hipGetDevice(&h->device) != hipSuccess) { delete h; return PIRIP_ERR_NO_DEVICE; }
+    if (select_device(device, &h->device) != PIRIP_OK) { delete h; return PIRIP_ERR_NO_DEVICE; }
     h->nstreams = nstreams;
     {
         int cus = 0;
@@ -183,22 +155,15 @@ int pirip_hip_ldpc_create(const char *code_path, int M, int Nsym, int nstreams, 
         if (x0 >= (double)kPhiXHi) phi[i] = 0.0f;                                     // phi0(x > 10) = 0
         if (x0 <= (double)kPhiXLo) phi[i] = 10.0f;                                    // phi0(x < 9.08e-5) = 10 (the clamp's own bin and everything below it)
     }
-    bool ok = up(&h->d_row_ptr, rp.data(), rp.size() * 2) && up(&h->d_col_idx, ci.data(), ci.size() * 2) &&
-              up(&h->d_col_ptr, cp.data(), cp.size() * 2) && up(&h->d_col_edge, ce.data(), ce.size() * 2) &&
-              up(&h->d_lnI0, lnI0.data(), lnI0.size() * 4) && up(&h->d_phi, phi.data(), phi.size() * 4);
-    ok = ok && hipMalloc((void **)&h->d_llr_hist, sizeof(uint16_t) * (size_t)nstreams * 2 * c.bits_per_frame()) == hipSuccess;
-    ok = ok && hipMalloc((void **)&h->d_fsm, sizeof(FsmState) * (size_t)nstreams) == hipSuccess;
     h->layout = make_decoder_layout(c);
-    if (h->layout.ok)
-        ok = ok && up(&h->d_rcol, h->layout.rcol.data(), h->layout.rcol.size() * 2) && up(&h->d_vedge, h->layout.vedge.data(), h->layout.vedge.size() * 2) &&
-             up(&h->d_vsrc, h->layout.vsrc.data(), h->layout.vsrc.size() * 2);
-    if (h->layout.ok && ok) {
+    std::vector<uint16_t> vcrc;
+    if (h->layout.ok) {
         // CRC-16/CCITT-FALSE (fsk_ldpc.cpp: crc16_ccitt; ldpc_device.hpp: crc16_tail_ok) over the k/8 payload bytes is an affine map of the
         // bits: the CRC of the all-zero word, and per bit the linear term = (CRC of the word with only that bit set) ^ (CRC of zero)
         const int nbytes = c.k / 8;
         std::vector<uint8_t> msg((size_t)nbytes, 0);
         h->crc0 = crc16_ccitt(msg.data(), nbytes);
-        std::vector<uint16_t> vcrc((size_t)kFastVars, 0);
+        vcrc.assign((size_t)kFastVars, 0);
         for (int q = 0; q < kFastVars; q++) {
             const int v = h->layout.vsrc[(size_t)q];
             if (v == 0xFFFF || v >= 8 * nbytes) continue;
@@ -206,9 +171,25 @@ int pirip_hip_ldpc_create(const char *code_path, int M, int Nsym, int nstreams, 
             vcrc[(size_t)q] = (uint16_t)(crc16_ccitt(msg.data(), nbytes) ^ h->crc0);
             msg[(size_t)(v / 8)] = 0;
         }
-        ok = up(&h->d_vcrc, vcrc.data(), vcrc.size() * 2);
     }
-    if (!ok) { pirip_hip_ldpc_destroy(h); return PIRIP_ERR_NOMEM; }
+    auto tables = [&]() -> int {
+        DevMem &m = h->mem;
+        PIRIP_TRY(m.upload(&h->d_row_ptr, rp.data(), rp.size() * 2));
+        PIRIP_TRY(m.upload(&h->d_col_idx, ci.data(), ci.size() * 2));
+        PIRIP_TRY(m.upload(&h->d_col_ptr, cp.data(), cp.size() * 2));
+        PIRIP_TRY(m.upload(&h->d_col_edge, ce.data(), ce.size() * 2));
+        PIRIP_TRY(m.upload(&h->d_lnI0, lnI0.data(), lnI0.size() * 4));
+        PIRIP_TRY(m.upload(&h->d_phi, phi.data(), phi.size() * 4));
+        PIRIP_TRY(m.alloc(&h->d_llr_hist, sizeof(uint16_t) * (size_t)nstreams * 2 * c.bits_per_frame()));
+        PIRIP_TRY(m.alloc(&h->d_fsm, sizeof(FsmState) * (size_t)nstreams));
+        if (!h->layout.ok) return PIRIP_OK;
+        PIRIP_TRY(m.upload(&h->d_rcol, h->layout.rcol.data(), h->layout.rcol.size() * 2));
+        PIRIP_TRY(m.upload(&h->d_vedge, h->layout.vedge.data(), h->layout.vedge.size() * 2));
+        PIRIP_TRY(m.upload(&h->d_vsrc, h->layout.vsrc.data(), h->layout.vsrc.size() * 2));
+        return m.upload(&h->d_vcrc, vcrc.data(), vcrc.size() * 2);
+    };
+    int rc = tables();
+    if (rc != PIRIP_OK) { delete h; return rc; }
     if (h->layout.ok) h->fast_static_lds = decode_fast_static_lds(h->fast_deg());     // (must be 0 for the fast decoder to serve)
     uint32_t uw = 0;
     for (int i = 0; i < kUwBits; i++) uw |= (uint32_t)(c.uw[i] & 1) << (31 - i);
@@ -216,8 +197,8 @@ int pirip_hip_ldpc_create(const char *code_path, int M, int Nsym, int nstreams, 
     for (int i = 0; i < c.m; i++) max_row_deg = std::max(max_row_deg, (int)(c.row_ptr[i + 1] - c.row_ptr[i]));
     h->dev = LdpcDev{c.n, c.k, c.m, (int)c.col_idx.size(), c.max_iter, c.uw_thresh1, c.uw_thresh2, c.bad_uw_thresh, M, Nsym, Nbits,
                      c.bits_per_frame(), max_row_deg, uw, h->d_row_ptr, h->d_col_idx, h->d_col_ptr, h->d_col_edge, h->d_lnI0, h->d_phi, c.llr_map};
-    const int rc = pirip_hip_ldpc_reset(h, nullptr);
-    if (rc != PIRIP_OK) { pirip_hip_ldpc_destroy(h); return rc; }
+    rc = pirip_hip_ldpc_reset(h, nullptr);
+    if (rc != PIRIP_OK) { delete h; return rc; }
     *out = h;
     return PIRIP_OK;
 }
@@ -225,12 +206,8 @@ int pirip_hip_ldpc_create(const char *code_path, int M, int Nsym, int nstreams, 
 int pirip_hip_ldpc_destroy(pirip_hip_ldpc *h)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
-    (void)bind_dev(h);
+    (void)bind_device(h->device);
     (void)hipDeviceSynchronize();
-    void *ptrs[] = {h->d_rcol, h->d_vedge, h->d_vsrc, h->d_vcrc, h->d_row_ptr, h->d_col_idx, h->d_col_ptr, h->d_col_edge, h->d_lnI0, h->d_phi, h->d_llr_hist, h->d_fsm, h->d_llr_all,
-                    h->d_words, h->d_best, h->d_jobs, h->d_njobs, h->d_filt_work, h->d_h_filt, h->d_h_status, h->d_h_payload, h->d_h_info,
-                    h->d_dd_llr, h->d_dd_bits, h->d_dd_ip};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     for (hipStream_t st : h->side) if (st) (void)hipStreamDestroy(st);
     if (h->ev_fork) (void)hipEventDestroy(h->ev_fork);
     if (h->ev_gfork) (void)hipEventDestroy(h->ev_gfork);
@@ -253,19 +230,19 @@ int pirip_hip_ldpc_get_info(const pirip_hip_ldpc *h, pirip_ldpc_info *info)
 int pirip_hip_ldpc_get_llr_history(pirip_hip_ldpc *h, int s, uint16_t *host_llr)
 {
     if (!h || !host_llr || s < 0 || s >= h->nstreams) return PIRIP_ERR_BAD_ARG;
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     const size_t n = 2 * (size_t)h->dev.bpf;
-    LCHK(hipMemcpy(host_llr, h->d_llr_hist + (size_t)s * n, sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(host_llr, h->d_llr_hist + (size_t)s * n, sizeof(uint16_t) * n, hipMemcpyDeviceToHost));
     return PIRIP_OK;
 }
 
 int pirip_hip_ldpc_reset(pirip_hip_ldpc *h, void *hip_stream)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)hip_stream;
-    LCHK(hipMemsetAsync(h->d_llr_hist, 0, sizeof(uint16_t) * (size_t)h->nstreams * 2 * h->dev.bpf, st));
-    LCHK(hipMemsetAsync(h->d_fsm, 0, sizeof(FsmState) * (size_t)h->nstreams, st));
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_llr_hist, 0, sizeof(uint16_t) * (size_t)h->nstreams * 2 * h->dev.bpf, st));
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_fsm, 0, sizeof(FsmState) * (size_t)h->nstreams, st));
     return PIRIP_OK;
 }
 
@@ -274,14 +251,14 @@ int pirip_hip_ldpc_rx_batch(pirip_hip_ldpc *h, const float *d_rx_filt, size_t fi
 {
     if (!h || !d_rx_filt || !d_status || !d_payload || !d_info || ncalls < 0) return PIRIP_ERR_BAD_ARG;
     if (ncalls == 0) return PIRIP_OK;
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)hip_stream;
     const LdpcDev &c = h->dev;
     const BatchDims bd = batch_dims(c, ncalls);
     int rc = ensure_work(h, ncalls, st);
     if (rc != PIRIP_OK) return rc;
     const bool fused_words = (2 * c.bpf) % 32 == 0;        // every LLR tile then covers whole hard-decision words
-    LCHK(launch_llr<h16>(h, h->nstreams, st, d_rx_filt, filt_stride, d_ncalls, ncalls, h->d_llr_all, bd.llr_stride,
+    PIRIP_HIPCHK(launch_llr<h16>(h, h->nstreams, st, d_rx_filt, filt_stride, d_ncalls, ncalls, h->d_llr_all, bd.llr_stride,
                          h->d_llr_hist, fused_words ? h->d_words : (uint32_t *)nullptr, bd.nwords));
     if (!fused_words) launch_hard(h->nstreams, st, h->d_llr_all, bd.llr_stride, bd.nbits_total, h->d_words, bd.nwords);
     return stages_after_llr(h, d_ncalls, ncalls, d_status, d_payload, d_info, st);
@@ -311,7 +288,7 @@ int pirip::fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const 
     if (demod_handle_shape(dem, &M, &Nsym, &ns, &dev) != PIRIP_OK) return PIRIP_ERR_BAD_ARG;
     const LdpcDev &c = h->dev;
     if (M != c.M || Nsym != c.Nsym || ns != h->nstreams || dev != h->device) return PIRIP_ERR_BAD_ARG;   // the two handles describe the same streams
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)hip_stream;
     const int ncalls = (int)max_frames;
     const BatchDims bd = batch_dims(c, ncalls);
@@ -323,10 +300,10 @@ int pirip::fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const 
         // (sdec / ev: the decode on another stream, ordered behind the range's earlier stages by the event)
         auto run_range = [&](int s0, int n, hipStream_t sg, bool beside = false, hipStream_t sdec = nullptr, hipEvent_t ev = nullptr) -> int {
             if (n <= 0) return PIRIP_OK;
-            LCHK(hipMemsetAsync(h->d_words + (size_t)s0 * bd.nwords, 0, sizeof(uint32_t) * (size_t)n * bd.nwords, sg));
+            PIRIP_HIPCHK(hipMemsetAsync(h->d_words + (size_t)s0 * bd.nwords, 0, sizeof(uint32_t) * (size_t)n * bd.nwords, sg));
             launch_hist_prepare(n, sg, c.bpf, h->d_llr_hist + (size_t)s0 * (size_t)(2 * c.bpf), h->d_llr_all + (size_t)s0 * bd.llr_stride, bd.llr_stride,
                                 h->d_words + (size_t)s0 * bd.nwords, bd.nwords);
-            LCHK(hipGetLastError());
+            PIRIP_HIPCHK(hipGetLastError());
             const int r = demod_batch_soft(dem, d_in, in_stride_bytes, nsamp, so, d_stats, stats_stride, d_nframes, d_consumed, max_frames, sg, s0, n, seg);
             if (r != PIRIP_OK) return r;
             return stages_after_llr(h, d_nframes, ncalls, d_status, d_payload, d_info, sg, s0, n, beside, sdec, ev);
@@ -380,9 +357,9 @@ int pirip::fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const 
         if (nr == 2 && first_end > 0) end[0] = first_end;
         if (nr == 2 && end[0] >= h->nstreams) end[0] = h->nstreams / 2;
         // fork: nothing has been launched on the side streams if one of these fails
-        LCHK(hipEventRecord(h->ev_fork, st));
-        for (int i = 0; i < nr; i++) LCHK(hipStreamWaitEvent(sr[i], h->ev_fork, 0));
-        if (sdec) LCHK(hipStreamWaitEvent(sdec, h->ev_fork, 0));
+        PIRIP_HIPCHK(hipEventRecord(h->ev_fork, st));
+        for (int i = 0; i < nr; i++) PIRIP_HIPCHK(hipStreamWaitEvent(sr[i], h->ev_fork, 0));
+        if (sdec) PIRIP_HIPCHK(hipStreamWaitEvent(sdec, h->ev_fork, 0));
         rc = PIRIP_OK;
         for (int i = 0; i < nr && rc == PIRIP_OK; i++) {
             const int s0 = i ? end[i - 1] : 0;
@@ -398,14 +375,14 @@ int pirip::fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const 
             if (e != hipSuccess) jerr = e;
         }
         if (rc != PIRIP_OK) return rc;
-        LCHK(jerr);
+        PIRIP_HIPCHK(jerr);
         return PIRIP_OK;
     }
     // no fused instance for this shape (general kernel, fsk_demod -p 24, a code whose window is not a whole number of words)
     h->last_path_fused = 0;
     const size_t per = (size_t)c.M * c.Nsym;
     if ((size_t)ncalls > h->filt_cap) {
-        rc = grow_dev(h, &h->filt_cap, (size_t)ncalls, true, st, {grow_buf(&h->d_filt_work, sizeof(float) * (size_t)h->nstreams * ncalls * per)});
+        rc = grow_dev(h->mem, &h->filt_cap, (size_t)ncalls, GrowSync::stream, st, {grow_buf(&h->d_filt_work, sizeof(float) * (size_t)h->nstreams * ncalls * per)});
         if (rc != PIRIP_OK) return rc;
     }
     rc = demod_batch_seg(dem, d_in, in_stride_bytes, nsamp, nullptr, 0, h->d_filt_work, (size_t)ncalls * per, d_stats, stats_stride, d_nframes, d_consumed,
@@ -438,12 +415,12 @@ int pirip_hip_fsk_ldpc_rx_batch_groups(const pirip_chain_group *groups, int ngro
     if (ngroups == 1)
         return pirip_hip_fsk_ldpc_rx_batch(groups[0].dem, groups[0].ldpc, groups[0].d_in, in_stride_bytes, nsamp, groups[0].d_status, groups[0].d_payload,
                                            groups[0].d_info, groups[0].d_stats, stats_stride, groups[0].d_nframes, groups[0].d_consumed, max_frames, hip_stream);
-    pirip_hip_ldpc *h = groups[0].ldpc;                            // (whose side streams / events carry the groups, and where LCHK records a HIP error)
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    pirip_hip_ldpc *h = groups[0].ldpc;                            // (whose side streams / events carry the groups)
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     if (!side_events(h, pirip_hip_ldpc::kGroupSlot0 + ngroups)) return PIRIP_ERR_HIP;
     for (int g = 0; g < ngroups; g++) if (!side_stream(h, pirip_hip_ldpc::kGroupSlot0 + g)) return PIRIP_ERR_HIP;
     hipStream_t st = (hipStream_t)hip_stream;
-    LCHK(hipEventRecord(h->ev_gfork, st));
+    PIRIP_HIPCHK(hipEventRecord(h->ev_gfork, st));
     int rc = PIRIP_OK;
     hipError_t jerr = hipSuccess;
     for (int g = 0; g < ngroups && rc == PIRIP_OK; g++) {
@@ -461,7 +438,7 @@ int pirip_hip_fsk_ldpc_rx_batch_groups(const pirip_chain_group *groups, int ngro
         if (e != hipSuccess) jerr = e;
     }
     if (rc != PIRIP_OK) return rc;
-    LCHK(jerr);
+    PIRIP_HIPCHK(jerr);
     return PIRIP_OK;
 }
 
@@ -474,22 +451,22 @@ int pirip_hip_ldpc_rx_host(pirip_hip_ldpc *h, const float *rx_filt, int ncalls, 
     if (!h || (!rx_filt && ncalls > 0) || ncalls < 0 || !status || !payload || !info) return PIRIP_ERR_BAD_ARG;
     if (h->nstreams != 1) return PIRIP_ERR_BAD_ARG;
     if (ncalls == 0) return PIRIP_OK;
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     const LdpcDev &c = h->dev;
     const size_t per = (size_t)c.M * c.Nsym, nb = (size_t)(c.k / 8);
     if ((size_t)ncalls > h->h_cap) {
-        const int rc = grow_dev(h, &h->h_cap, (size_t)ncalls, false, nullptr,
+        const int rc = grow_dev(h->mem, &h->h_cap, (size_t)ncalls, GrowSync::none, nullptr,
                                 {grow_buf(&h->d_h_filt, sizeof(float) * per * ncalls), grow_buf(&h->d_h_status, (size_t)ncalls),
                                  grow_buf(&h->d_h_payload, nb * ncalls), grow_buf(&h->d_h_info, sizeof(int32_t) * kInfoPerCall * ncalls)});
         if (rc != PIRIP_OK) return rc;
     }
-    LCHK(hipMemcpy(h->d_h_filt, rx_filt, sizeof(float) * per * ncalls, hipMemcpyHostToDevice));
+    PIRIP_HIPCHK(hipMemcpy(h->d_h_filt, rx_filt, sizeof(float) * per * ncalls, hipMemcpyHostToDevice));
     const int rc = pirip_hip_ldpc_rx_batch(h, h->d_h_filt, 0, nullptr, ncalls, h->d_h_status, h->d_h_payload, h->d_h_info, nullptr);
     if (rc != PIRIP_OK) return rc;
-    LCHK(hipDeviceSynchronize());
-    LCHK(hipMemcpy(status, h->d_h_status, (size_t)ncalls, hipMemcpyDeviceToHost));
-    LCHK(hipMemcpy(payload, h->d_h_payload, nb * ncalls, hipMemcpyDeviceToHost));
-    LCHK(hipMemcpy(info, h->d_h_info, sizeof(int32_t) * kInfoPerCall * ncalls, hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipMemcpy(status, h->d_h_status, (size_t)ncalls, hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(payload, h->d_h_payload, nb * ncalls, hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(info, h->d_h_info, sizeof(int32_t) * kInfoPerCall * ncalls, hipMemcpyDeviceToHost));
     return PIRIP_OK;
 }
 
@@ -497,15 +474,15 @@ int pirip_hip_ldpc_decode_llr(pirip_hip_ldpc *h, const float *d_llr, int ncw, ui
 {
     if (!h || !d_llr || !d_bits || !d_iter_pcc || ncw < 0) return PIRIP_ERR_BAD_ARG;
     if (ncw == 0) return PIRIP_OK;
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t nll = (size_t)ncw * h->dev.n;
     if (nll > h->dd_cap) {
-        const int rc = grow_dev(h, &h->dd_cap, nll, true, st, {grow_buf(&h->d_dd_llr, sizeof(uint16_t) * nll)});
+        const int rc = grow_dev(h->mem, &h->dd_cap, nll, GrowSync::stream, st, {grow_buf(&h->d_dd_llr, sizeof(uint16_t) * nll)});
         if (rc != PIRIP_OK) return rc;
     }
     launch_f32_to_h16(st, d_llr, h->d_dd_llr, nll);   // the decoder's input format
-    LCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     return launch_decode(h, ncw, 1, nullptr, nullptr, h->d_dd_llr, 0, 1, nullptr, 0, nullptr, nullptr, d_bits, d_iter_pcc, st);
 }
 
@@ -513,12 +490,12 @@ int pirip_hip_ldpc_llr(pirip_hip_ldpc *h, const float *d_rx_filt, int ncalls, fl
 {
     if (!h || !d_rx_filt || !d_llr || ncalls < 0) return PIRIP_ERR_BAD_ARG;
     if (ncalls == 0) return PIRIP_OK;
-    if (!bind_dev(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     // one pseudo-stream whose history slot is skipped: write straight to d_llr (offset so that "2*bpf + call*Nbits" lands at call*Nbits)
     const LdpcDev &c = h->dev;
-    LCHK(launch_llr<float>(h, 1, (hipStream_t)hip_stream, d_rx_filt, (size_t)0, (const int32_t *)nullptr, ncalls,
+    PIRIP_HIPCHK(launch_llr<float>(h, 1, (hipStream_t)hip_stream, d_rx_filt, (size_t)0, (const int32_t *)nullptr, ncalls,
                            d_llr - 2 * c.bpf, (size_t)0, (const h16 *)nullptr, (uint32_t *)nullptr, 0));
-    LCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;
 }
 

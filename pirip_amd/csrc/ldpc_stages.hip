@@ -397,7 +397,7 @@ int launch_sync(pirip_hip_ldpc *h, int s0, int n, hipStream_t st, int ncalls, co
     hipLaunchKernelGGL(uwbest_kernel, dim3((ncalls + kUwCalls - 1) / kUwCalls, n), dim3(256), lds, st, c, ncalls, words, nwords, nbits_total, best);
     hipLaunchKernelGGL(fsm_kernel, dim3((n + 63) / 64), dim3(64), 0, st, c, n, ncalls, ncalls_s, words, nwords, best, nbits_total, h->d_fsm + s0,
                        status, info, jobs, njobs, max_jobs);
-    LCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;
 }
 

@@ -16,58 +16,21 @@
 
 using namespace pirip;
 
-#define HIPCHK(expr)                                              \
-    do {                                                          \
-        hipError_t e_ = (expr);                                   \
-        if (e_ != hipSuccess) {                                   \
-            h->last_hip = (int)e_;                                \
-            return PIRIP_ERR_HIP;                                 \
-        }                                                         \
-    } while (0)
-
-
 namespace {
-
-int bytes_per_sample(int fmt)
-{
-    switch (fmt) {
-    case PIRIP_IN_CU8_FSKDEMOD: case PIRIP_IN_CU8_CSDR: return 2;
-    case PIRIP_IN_CS16: return 4;
-    default: return 8;
-    }
-}
-
-template <typename T>
-hipError_t upload(T **dst, const void *src, size_t bytes)
-{
-    hipError_t e = hipMalloc((void **)dst, bytes ? bytes : 16);
-    if (e != hipSuccess) return e;
-    if (bytes) e = hipMemcpy(*dst, src, bytes, hipMemcpyHostToDevice);
-    return e;
-}
-
-void free_all(pirip_hip_demod *h)
-{
-    void *ptrs[] = {h->d_hann, h->d_tw, h->d_perm, h->d_lut, h->d_tph, h->d_teeth, h->d_mask_dtheta,
-                    h->d_osc_drift, h->d_osc_step, h->d_timing_rec, h->d_fast_tab,
-                    h->d_Sf, h->d_theta, h->d_hist, h->d_scal, h->d_phic, h->d_first, h->d_stage_in, h->d_stage_bits,
-                    h->d_stage_filt, h->d_stage_stats, h->d_stage_nframes, h->d_stage_consumed, h->d_eye};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-}
 
 int reset_state(pirip_hip_demod *h, hipStream_t st)
 {
     const FskDims &d = h->plan.d;
     const size_t ns = (size_t)h->nstreams;
-    HIPCHK(hipMemsetAsync(h->d_Sf, 0, sizeof(float) * ns * d.Ndft, st));
-    HIPCHK(hipMemsetAsync(h->d_theta, 0, sizeof(uint32_t) * ns * kMaxTones, st));
-    HIPCHK(hipMemsetAsync(h->d_hist, 0, sizeof(float2) * ns * d.M * d.hist_len, st));
-    HIPCHK(hipMemsetAsync(h->d_phic, 0, sizeof(float2) * ns * kMaxTones, st));
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_Sf, 0, sizeof(float) * ns * d.Ndft, st));
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_theta, 0, sizeof(uint32_t) * ns * kMaxTones, st));
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_hist, 0, sizeof(float2) * ns * d.M * d.hist_len, st));
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_phic, 0, sizeof(float2) * ns * kMaxTones, st));
     std::vector<StreamScalars> sc(ns);
     std::memset(sc.data(), 0, sizeof(StreamScalars) * ns);
     for (auto &s : sc) s.nin = d.N;
-    HIPCHK(hipMemcpyAsync(h->d_scal, sc.data(), sizeof(StreamScalars) * ns, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // sc goes out of scope
+    PIRIP_HIPCHK(hipMemcpyAsync(h->d_scal, sc.data(), sizeof(StreamScalars) * ns, hipMemcpyHostToDevice, st));
+    PIRIP_HIPCHK(hipStreamSynchronize(st));   // sc goes out of scope
     h->nin0 = d.N;
     h->fresh = true;
     return PIRIP_OK;
@@ -83,12 +46,33 @@ void fill_args(const pirip_hip_demod *h, DemodArgs *a)
     a->s = DemodState{h->d_Sf, h->d_theta, h->d_hist, h->d_scal, h->d_phic};
 }
 
-// every entry point runs on the device the handle was created on, whatever the caller's current device is
-bool bind(const pirip_hip_demod *h)
+bool bind(const pirip_hip_demod *h) { return bind_device(h->device); }
+
+// the tables and the per-stream state of a new handle
+int alloc_tables_and_state(pirip_hip_demod *h)
 {
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur == h->device) return true;
-    return hipSetDevice(h->device) == hipSuccess;
+    const FskPlan &pl = h->plan;
+    const FskDims &d = pl.d;
+    const size_t ns = (size_t)h->nstreams;
+    DevMem &m = h->mem;
+    PIRIP_TRY(m.upload(&h->d_hann, pl.hann.data(), sizeof(float) * d.Ndft));
+    PIRIP_TRY(m.upload(&h->d_tw, pl.twiddle.data(), sizeof(float) * 2 * d.Ndft));
+    PIRIP_TRY(m.upload(&h->d_perm, pl.leaf_iperm.data(), sizeof(uint16_t) * d.Ndft));
+    PIRIP_TRY(m.upload(&h->d_lut, pl.u8_lut.data(), sizeof(float) * 256));
+    PIRIP_TRY(m.upload(&h->d_tph, pl.timing_ph.data(), sizeof(float) * 2 * d.P));
+    PIRIP_TRY(m.upload(&h->d_teeth, pl.teeth.data(), sizeof(int16_t) * pl.teeth.size()));
+    PIRIP_TRY(m.upload(&h->d_mask_dtheta, pl.mask_dtheta.data(), sizeof(uint32_t) * pl.mask_dtheta.size()));
+    PIRIP_TRY(m.upload(&h->d_osc_drift, pl.osc_drift.data(), sizeof(float) * pl.osc_drift.size()));
+    PIRIP_TRY(m.upload(&h->d_osc_step, pl.osc_step.data(), sizeof(float) * pl.osc_step.size()));
+    PIRIP_TRY(m.upload(&h->d_timing_rec, pl.timing_rec.data(), sizeof(float) * pl.timing_rec.size()));
+    PIRIP_TRY(m.upload(&h->d_fast_tab, pl.fast_tab.data(), sizeof(float) * pl.fast_tab.size()));
+    PIRIP_TRY(m.alloc(&h->d_Sf, sizeof(float) * ns * d.Ndft));
+    PIRIP_TRY(m.alloc(&h->d_theta, sizeof(uint32_t) * ns * kMaxTones));
+    PIRIP_TRY(m.alloc(&h->d_hist, sizeof(float2) * ns * d.M * d.hist_len));
+    PIRIP_TRY(m.alloc(&h->d_scal, sizeof(StreamScalars) * ns));
+    PIRIP_TRY(m.alloc(&h->d_first, sizeof(int32_t) * ns));
+    PIRIP_TRY(m.alloc(&h->d_phic, sizeof(float2) * ns * kMaxTones));
+    return PIRIP_OK;
 }
 
 }  // namespace
@@ -193,10 +177,8 @@ int pirip_hip_create_recalled(const pirip_fsk_params *p, const pirip_fsk_recalle
     if (rc != PIRIP_OK) { delete h; return rc; }
     if (demod_general_lds_bytes(h->plan.d) > 160 * 1024) { delete h; return PIRIP_ERR_UNSUPPORTED; }
 
-    int ndev = pirip_hip_device_count();
-    if (ndev <= 0) { delete h; return PIRIP_ERR_NO_DEVICE; }
-    if (device >= 0) { if (device >= ndev || hipSetDevice(device) != hipSuccess) { delete h; return PIRIP_ERR_NO_DEVICE; } }
-    if (hipGetDevice(&h->device) != hipSuccess) { delete h; return PIRIP_ERR_NO_DEVICE; }
+    rc = select_device(device, &h->device);
+    if (rc != PIRIP_OK) { delete h; return rc; }
     h->nstreams = nstreams;
     {
         const char *k = getenv("PIRIP_KERNEL");
@@ -222,31 +204,11 @@ int pirip_hip_create_recalled(const pirip_fsk_params *p, const pirip_fsk_recalle
         }
     }
 
-    const FskPlan &pl = h->plan;
-    const FskDims &d = pl.d;
-    const size_t ns = (size_t)nstreams;
-    bool ok = true;
-    ok &= upload(&h->d_hann, pl.hann.data(), sizeof(float) * d.Ndft) == hipSuccess;
-    ok &= upload(&h->d_tw, pl.twiddle.data(), sizeof(float) * 2 * d.Ndft) == hipSuccess;
-    ok &= upload(&h->d_perm, pl.leaf_iperm.data(), sizeof(uint16_t) * d.Ndft) == hipSuccess;
-    ok &= upload(&h->d_lut, pl.u8_lut.data(), sizeof(float) * 256) == hipSuccess;
-    ok &= upload(&h->d_tph, pl.timing_ph.data(), sizeof(float) * 2 * d.P) == hipSuccess;
-    ok &= upload(&h->d_teeth, pl.teeth.data(), sizeof(int16_t) * pl.teeth.size()) == hipSuccess;
-    ok &= upload(&h->d_mask_dtheta, pl.mask_dtheta.data(), sizeof(uint32_t) * pl.mask_dtheta.size()) == hipSuccess;
-    ok &= upload(&h->d_osc_drift, pl.osc_drift.data(), sizeof(float) * pl.osc_drift.size()) == hipSuccess;
-    ok &= upload(&h->d_osc_step, pl.osc_step.data(), sizeof(float) * pl.osc_step.size()) == hipSuccess;
-    ok &= upload(&h->d_timing_rec, pl.timing_rec.data(), sizeof(float) * pl.timing_rec.size()) == hipSuccess;
-    ok &= upload(&h->d_fast_tab, pl.fast_tab.data(), sizeof(float) * pl.fast_tab.size()) == hipSuccess;
-    ok &= hipMalloc((void **)&h->d_Sf, sizeof(float) * ns * d.Ndft) == hipSuccess;
-    ok &= hipMalloc((void **)&h->d_theta, sizeof(uint32_t) * ns * kMaxTones) == hipSuccess;
-    ok &= hipMalloc((void **)&h->d_hist, sizeof(float2) * ns * d.M * d.hist_len) == hipSuccess;
-    ok &= hipMalloc((void **)&h->d_scal, sizeof(StreamScalars) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&h->d_first, sizeof(int32_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&h->d_phic, sizeof(float2) * ns * kMaxTones) == hipSuccess;
-    if (!ok) { free_all(h); delete h; return PIRIP_ERR_NOMEM; }
+    rc = alloc_tables_and_state(h);
+    if (rc != PIRIP_OK) { delete h; return rc; }
     if (const char *e = getenv("PIRIP_EXACT0")) h->exact0 = atoi(e) ? 1 : 0;
     rc = reset_state(h, nullptr);
-    if (rc != PIRIP_OK) { free_all(h); delete h; return rc; }
+    if (rc != PIRIP_OK) { delete h; return rc; }
     *out = h;
     return PIRIP_OK;
 }
@@ -257,7 +219,6 @@ int pirip_hip_destroy(pirip_hip_demod *h)
     (void)bind(h);
     (void)hipDeviceSynchronize();
     pirip::capture_release(h);
-    free_all(h);
     delete h;
     return PIRIP_OK;
 }
@@ -283,11 +244,11 @@ int pirip_hip_clear_estimators(pirip_hip_demod *h, void *hip_stream)
     hipStream_t st = (hipStream_t)hip_stream;
     const FskDims &d = h->plan.d;
     const size_t ns = (size_t)h->nstreams;
-    HIPCHK(hipMemsetAsync(h->d_Sf, 0, sizeof(float) * ns * d.Ndft, st));
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_Sf, 0, sizeof(float) * ns * d.Ndft, st));
     // nin = N in every stream's scalars: a strided copy of one int per stream
     std::vector<int32_t> nin(ns, d.N);
-    HIPCHK(hipMemcpy2DAsync(&h->d_scal->nin, sizeof(StreamScalars), nin.data(), sizeof(int32_t), sizeof(int32_t), ns, hipMemcpyHostToDevice, st));
-    HIPCHK(hipStreamSynchronize(st));   // nin goes out of scope
+    PIRIP_HIPCHK(hipMemcpy2DAsync(&h->d_scal->nin, sizeof(StreamScalars), nin.data(), sizeof(int32_t), sizeof(int32_t), ns, hipMemcpyHostToDevice, st));
+    PIRIP_HIPCHK(hipStreamSynchronize(st));   // nin goes out of scope
     h->nin0 = d.N;
     return PIRIP_OK;
 }
@@ -326,8 +287,7 @@ int exact0_prologue(pirip_hip_demod *h, DemodArgs *a, hipStream_t st)
     p.io.first = nullptr; p.io.first_out = h->d_first;
     p.io.exact0_fmt = h->kernel == PIRIP_KERNEL_WAVE ? PIRIP_KERNEL_WAVE : PIRIP_KERNEL_GENERAL;
     p.io.eye = h->d_eye;
-    const hipError_t e = launch_demod_exact0(p, h->nstreams, st);
-    if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+    PIRIP_HIPCHK(launch_demod_exact0(p, h->nstreams, st));
     a->io.first = h->d_first;
     return PIRIP_OK;
 }
@@ -379,7 +339,7 @@ int demod_batch_seg(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes
     if (h->kernel == 2) {
         e = launch_demod_wave(a, h->nstreams, (hipStream_t)hip_stream);
     } else e = launch_demod_kind(h->kernel, a, h->nstreams, (hipStream_t)hip_stream);
-    if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+    PIRIP_HIPCHK(e);
     return PIRIP_OK;
 }
 
@@ -413,8 +373,7 @@ int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_byte
         nrun = n;
     }
     if (nrun == 0) return PIRIP_OK;
-    const hipError_t e = launch_demod_wave(a, nrun, st);
-    if (e != hipSuccess) { h->last_hip = (int)e; return PIRIP_ERR_HIP; }
+    PIRIP_HIPCHK(launch_demod_wave(a, nrun, st));
     return PIRIP_OK;
 }
 bool demod_soft_capable(const pirip_hip_demod *h, int64_t nsamp)
@@ -441,27 +400,17 @@ int pirip_hip_demod_host(pirip_hip_demod *h, const void *in, int64_t nsamp, uint
     const FskDims &d = h->plan.d;
     const size_t bps = (size_t)bytes_per_sample(d.in_format);
     const size_t in_bytes = (size_t)nsamp * bps;
-    if (in_bytes > h->stage_in_bytes) {
-        if (h->d_stage_in) (void)hipFree(h->d_stage_in);
-        h->d_stage_in = nullptr; h->stage_in_bytes = 0;
-        HIPCHK(hipMalloc(&h->d_stage_in, in_bytes + 64));
-        h->stage_in_bytes = in_bytes;
-    }
-    if (!h->d_stage_in) { HIPCHK(hipMalloc(&h->d_stage_in, 64)); h->stage_in_bytes = 0; }
-    if (max_frames > h->stage_frames) {
-        void *olds[] = {h->d_stage_bits, h->d_stage_filt, h->d_stage_stats};
-        for (void *p : olds) if (p) (void)hipFree(p);
-        h->d_stage_bits = nullptr; h->d_stage_filt = nullptr; h->d_stage_stats = nullptr; h->stage_frames = 0;
-        HIPCHK(hipMalloc((void **)&h->d_stage_bits, (size_t)max_frames * d.Nbits + 16));
-        HIPCHK(hipMalloc((void **)&h->d_stage_filt, sizeof(float) * (size_t)max_frames * d.M * d.Nsym + 16));
-        HIPCHK(hipMalloc((void **)&h->d_stage_stats, sizeof(float) * (size_t)max_frames * PIRIP_STATS_PER_FRAME + 16));
-        h->stage_frames = max_frames;
-    }
-    if (!h->d_stage_nframes) {
-        HIPCHK(hipMalloc((void **)&h->d_stage_nframes, sizeof(int32_t) * (size_t)h->nstreams));
-        HIPCHK(hipMalloc((void **)&h->d_stage_consumed, sizeof(int64_t) * (size_t)h->nstreams));
-    }
-    if (in_bytes) HIPCHK(hipMemcpy(h->d_stage_in, in, in_bytes, hipMemcpyHostToDevice));
+    // (the staging buffers are only ever used by this synchronous call: nothing to wait for before they are replaced)
+    if (in_bytes > h->stage_in_bytes || !h->d_stage_in)
+        PIRIP_TRY(grow_dev(h->mem, &h->stage_in_bytes, in_bytes, GrowSync::none, nullptr, {grow_buf(&h->d_stage_in, in_bytes + 64)}));
+    if (max_frames > h->stage_frames || !h->d_stage_nframes)
+        PIRIP_TRY(grow_dev(h->mem, &h->stage_frames, max_frames, GrowSync::none, nullptr,
+                           {grow_buf(&h->d_stage_bits, (size_t)max_frames * d.Nbits + 16),
+                            grow_buf(&h->d_stage_filt, sizeof(float) * (size_t)max_frames * d.M * d.Nsym + 16),
+                            grow_buf(&h->d_stage_stats, sizeof(float) * (size_t)max_frames * PIRIP_STATS_PER_FRAME + 16),
+                            grow_buf(&h->d_stage_nframes, sizeof(int32_t) * (size_t)h->nstreams),
+                            grow_buf(&h->d_stage_consumed, sizeof(int64_t) * (size_t)h->nstreams)}));
+    if (in_bytes) PIRIP_HIPCHK(hipMemcpy(h->d_stage_in, in, in_bytes, hipMemcpyHostToDevice));
     // all streams of the handle see the same staged buffer (stride 0); callers of this
     // convenience entry normally create the handle with nstreams == 1
     int rc = pirip_hip_demod_batch(h, h->d_stage_in, 0, nsamp, h->d_stage_bits, 0,
@@ -469,16 +418,16 @@ int pirip_hip_demod_host(pirip_hip_demod *h, const void *in, int64_t nsamp, uint
                                    h->d_stage_stats, 0, h->d_stage_nframes, h->d_stage_consumed,
                                    max_frames, nullptr);
     if (rc != PIRIP_OK) return rc;
-    HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipDeviceSynchronize());
     int32_t nf = 0; int64_t cons = 0;
-    HIPCHK(hipMemcpy(&nf, h->d_stage_nframes, sizeof(nf), hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(&cons, h->d_stage_consumed, sizeof(cons), hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(&nf, h->d_stage_nframes, sizeof(nf), hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(&cons, h->d_stage_consumed, sizeof(cons), hipMemcpyDeviceToHost));
     const size_t fb = d.pack_bits ? (size_t)(d.Nbits + 7) / 8 : (size_t)d.Nbits;
-    if (bits && nf) HIPCHK(hipMemcpy(bits, h->d_stage_bits, (size_t)nf * fb, hipMemcpyDeviceToHost));
-    if (rx_filt && nf) HIPCHK(hipMemcpy(rx_filt, h->d_stage_filt, sizeof(float) * (size_t)nf * d.M * d.Nsym, hipMemcpyDeviceToHost));
-    if (stats && nf) HIPCHK(hipMemcpy(stats, h->d_stage_stats, sizeof(float) * (size_t)nf * PIRIP_STATS_PER_FRAME, hipMemcpyDeviceToHost));
+    if (bits && nf) PIRIP_HIPCHK(hipMemcpy(bits, h->d_stage_bits, (size_t)nf * fb, hipMemcpyDeviceToHost));
+    if (rx_filt && nf) PIRIP_HIPCHK(hipMemcpy(rx_filt, h->d_stage_filt, sizeof(float) * (size_t)nf * d.M * d.Nsym, hipMemcpyDeviceToHost));
+    if (stats && nf) PIRIP_HIPCHK(hipMemcpy(stats, h->d_stage_stats, sizeof(float) * (size_t)nf * PIRIP_STATS_PER_FRAME, hipMemcpyDeviceToHost));
     StreamScalars sc;
-    HIPCHK(hipMemcpy(&sc, h->d_scal, sizeof(sc), hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(&sc, h->d_scal, sizeof(sc), hipMemcpyDeviceToHost));
     h->nin0 = sc.nin;
     if (nframes) *nframes = nf;
     if (consumed) *consumed = cons;
@@ -491,8 +440,8 @@ int pirip_hip_get_Sf(pirip_hip_demod *h, int s, float *Sf_host)
 {
     if (!h || !Sf_host || s < 0 || s >= h->nstreams) return PIRIP_ERR_BAD_ARG;
     if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(Sf_host, h->d_Sf + (size_t)s * h->plan.d.Ndft, sizeof(float) * h->plan.d.Ndft, hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipMemcpy(Sf_host, h->d_Sf + (size_t)s * h->plan.d.Ndft, sizeof(float) * h->plan.d.Ndft, hipMemcpyDeviceToHost));
     return PIRIP_OK;
 }
 
@@ -502,16 +451,15 @@ int pirip_hip_enable_eye(pirip_hip_demod *h, int enable)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
     if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
-    HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipDeviceSynchronize());
     if (!enable) {
-        if (h->d_eye) (void)hipFree(h->d_eye);
-        h->d_eye = nullptr;
+        h->mem.release(&h->d_eye);
         return PIRIP_OK;                       // the handle stays on the kernel it has
     }
     if (h->d_eye) return PIRIP_OK;
     const size_t bytes = sizeof(float) * (size_t)h->nstreams * kEyeTraces * kEyePoints;
-    HIPCHK(hipMalloc((void **)&h->d_eye, bytes));
-    HIPCHK(hipMemset(h->d_eye, 0, bytes));
+    PIRIP_TRY(h->mem.alloc(&h->d_eye, bytes));
+    PIRIP_HIPCHK(hipMemset(h->d_eye, 0, bytes));
     if (h->kernel != PIRIP_KERNEL_GENERAL && h->kernel != PIRIP_KERNEL_EXACT) {
         h->kernel = PIRIP_KERNEL_GENERAL;
         return reset_state(h, nullptr);
@@ -524,8 +472,8 @@ int pirip_hip_get_eye(pirip_hip_demod *h, int s, int normalise, float *rx_eye, i
     if (!h || !rx_eye || !neyetr || !neyesamp || s < 0 || s >= h->nstreams) return PIRIP_ERR_BAD_ARG;
     if (!h->d_eye) return PIRIP_ERR_UNSUPPORTED;      // pirip_hip_enable_eye() first
     if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(rx_eye, h->d_eye + (size_t)s * kEyeTraces * kEyePoints, sizeof(float) * kEyeTraces * kEyePoints, hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipMemcpy(rx_eye, h->d_eye + (size_t)s * kEyeTraces * kEyePoints, sizeof(float) * kEyeTraces * kEyePoints, hipMemcpyDeviceToHost));
     const FskDims &d = h->plan.d;
     const int dec = (2 * d.P + kEyePoints - 1) / kEyePoints, npts = (2 * d.P) / dec;
     int traces = kEyeTraces / d.M;
@@ -584,11 +532,11 @@ int pirip_hip_set_burst_mode(pirip_hip_demod *h, int enable)
     h->plan.d.burst_mode = enable ? 1 : 0;
     if (enable) {
         if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
-        HIPCHK(hipDeviceSynchronize());
+        PIRIP_HIPCHK(hipDeviceSynchronize());
         std::vector<StreamScalars> sc((size_t)h->nstreams);
-        HIPCHK(hipMemcpy(sc.data(), h->d_scal, sizeof(StreamScalars) * sc.size(), hipMemcpyDeviceToHost));
+        PIRIP_HIPCHK(hipMemcpy(sc.data(), h->d_scal, sizeof(StreamScalars) * sc.size(), hipMemcpyDeviceToHost));
         for (auto &s : sc) s.nin = h->plan.d.N;
-        HIPCHK(hipMemcpy(h->d_scal, sc.data(), sizeof(StreamScalars) * sc.size(), hipMemcpyHostToDevice));
+        PIRIP_HIPCHK(hipMemcpy(h->d_scal, sc.data(), sizeof(StreamScalars) * sc.size(), hipMemcpyHostToDevice));
         h->nin0 = h->plan.d.N;
     }
     return PIRIP_OK;
@@ -599,9 +547,9 @@ int pirip_hip_get_scalars(pirip_hip_demod *h, int s, float *out8)
 {
     if (!h || !out8 || s < 0 || s >= h->nstreams) return PIRIP_ERR_BAD_ARG;
     if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
-    HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipDeviceSynchronize());
     StreamScalars sc;
-    HIPCHK(hipMemcpy(&sc, h->d_scal + s, sizeof(sc), hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(&sc, h->d_scal + s, sizeof(sc), hipMemcpyDeviceToHost));
     out8[0] = sc.f_est[0]; out8[1] = sc.f_est[1]; out8[2] = sc.f_est[2]; out8[3] = sc.f_est[3];
     out8[4] = sc.norm_rx_timing; out8[5] = sc.SNRest; out8[6] = (float)sc.nin; out8[7] = sc.ppm;
     return PIRIP_OK;
@@ -611,9 +559,9 @@ int pirip_hip_get_stream_state(pirip_hip_demod *h, int s, pirip_stream_state *ou
 {
     if (!h || !out || s < 0 || s >= h->nstreams) return PIRIP_ERR_BAD_ARG;
     if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
-    HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipDeviceSynchronize());
     StreamScalars sc;
-    HIPCHK(hipMemcpy(&sc, h->d_scal + s, sizeof(sc), hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(&sc, h->d_scal + s, sizeof(sc), hipMemcpyDeviceToHost));
     out->nin = sc.nin; out->norm_rx_timing = sc.norm_rx_timing; out->ppm = sc.ppm; out->snr_est = sc.snr_est;
     out->SNRest = sc.SNRest; out->EbNodB = sc.EbNodB; out->v_est = sc.v_est;
     for (int m = 0; m < 4; m++) out->f_est[m] = sc.f_est[m];

@@ -92,19 +92,12 @@ __global__ __launch_bounds__(kWave * kChannelsPerBlock) void rx_advance_kernel(A
     }
 }
 
-int bytes_per_sample(int fmt)
-{
-    switch (fmt) {
-    case PIRIP_IN_CU8_FSKDEMOD: case PIRIP_IN_CU8_CSDR: return 2;
-    case PIRIP_IN_CS16: return 4;
-    default: return 8;
-    }
-}
-
 inline size_t round_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 }  // namespace
 
+// (hidden: a handle's implicit destructor is no dynamic symbol of the library)
+#pragma GCC visibility push(hidden)
 struct pirip_hip_rx {
     pirip_hip_demod *dem = nullptr;
     pirip_hip_ldpc *ldpc = nullptr;
@@ -120,27 +113,23 @@ struct pirip_hip_rx {
     int D = 1;
     int64_t H = 0;                         // decimator history (u8 samples)
     size_t raw_pre = 0, raw_row_bytes = 0; // tuner-rate rows: block at raw_pre bytes
+    DevMem mem;
     uint8_t *d_rows = nullptr, *d_raw = nullptr;
     int64_t *d_consumed = nullptr, *d_total = nullptr;
     int32_t *d_carry = nullptr, *d_flag = nullptr;
     SegDesc *d_seg = nullptr;
     bool first = true;                     // the next call runs without descriptors (every carry is 0)
 };
+#pragma GCC visibility pop
 
 namespace {
-
-void rx_free(pirip_hip_rx *rx)
-{
-    void *ptrs[] = {rx->d_rows, rx->d_raw, rx->d_consumed, rx->d_total, rx->d_carry, rx->d_flag, rx->d_seg};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-}
 
 int rx_clear(pirip_hip_rx *rx, hipStream_t st)
 {
     const size_t ns = (size_t)rx->nstreams;
-    if (hipMemsetAsync(rx->d_carry, 0, sizeof(int32_t) * ns, st) != hipSuccess ||
-        hipMemsetAsync(rx->d_total, 0, sizeof(int64_t) * ns, st) != hipSuccess ||
-        hipMemsetAsync(rx->d_flag, 0, sizeof(int32_t), st) != hipSuccess) return PIRIP_ERR_HIP;
+    PIRIP_HIPCHK(hipMemsetAsync(rx->d_carry, 0, sizeof(int32_t) * ns, st));
+    PIRIP_HIPCHK(hipMemsetAsync(rx->d_total, 0, sizeof(int64_t) * ns, st));
+    PIRIP_HIPCHK(hipMemsetAsync(rx->d_flag, 0, sizeof(int32_t), st));
     rx->first = true;
     rx->t_in = 0;
     return PIRIP_OK;
@@ -185,9 +174,9 @@ int rx_run(pirip_hip_rx *rx, uint8_t *d_bits, size_t bits_stride, float *d_rx_fi
         int rc = rx->dec ? pirip_hip_decim_batch(rx->dec, in, rx->raw_row_bytes, n_in, land, rx->row_bytes, rx->nstreams, st)
                          : pirip_hip_chan_batch(rx->chan, in, rx->raw_row_bytes, n_in, rx->first ? 0 : rx->t_in - rx->H, land, rx->row_bytes, st);
         if (rc != PIRIP_OK) return rc;
-        if (rx->H > 0 && hipMemcpy2DAsync(rx->d_raw + rx->raw_pre - (size_t)rx->H * 2, rx->raw_row_bytes,
-                                          rx->d_raw + rx->raw_pre + (size_t)(rx->block - rx->H) * 2, rx->raw_row_bytes,
-                                          (size_t)rx->H * 2, (size_t)rx->nraw, hipMemcpyDeviceToDevice, st) != hipSuccess) return PIRIP_ERR_HIP;
+        if (rx->H > 0) PIRIP_HIPCHK(hipMemcpy2DAsync(rx->d_raw + rx->raw_pre - (size_t)rx->H * 2, rx->raw_row_bytes,
+                                                     rx->d_raw + rx->raw_pre + (size_t)(rx->block - rx->H) * 2, rx->raw_row_bytes,
+                                                     (size_t)rx->H * 2, (size_t)rx->nraw, hipMemcpyDeviceToDevice, st));
     }
     // 2. demodulator (or the FSK_LDPC chain): the first call on row + C_pre without descriptors -- the exact-first-frame prologue then
     //    applies as in pirip_hip_demod_batch --, every later one from each channel's carried tail
@@ -203,9 +192,30 @@ int rx_run(pirip_hip_rx *rx, uint8_t *d_bits, size_t bits_stride, float *d_rx_fi
     AdvanceArgs a{rx->d_rows, rx->row_bytes, rx->bps, rx->c_pre, mc, rx->nin_max, (int32_t)rx->budget, rx->d_consumed, rx->d_carry, rx->d_total,
                   rx->d_seg, rx->d_flag, rx->nstreams};
     hipLaunchKernelGGL(rx_advance_kernel, dim3((rx->nstreams + kChannelsPerBlock - 1) / kChannelsPerBlock), dim3(kWave * kChannelsPerBlock), 0, st, a);
-    if (hipGetLastError() != hipSuccess) return PIRIP_ERR_HIP;
+    PIRIP_HIPCHK(hipGetLastError());
     rx->first = false;
     rx->t_in += rx->block;
+    return PIRIP_OK;
+}
+
+// the rows and the per-channel bookkeeping of a new receiver, zeroed
+int rx_alloc(pirip_hip_rx *rx)
+{
+    const size_t ns = (size_t)rx->nstreams, raw_bytes = rx->raw_row_bytes * (size_t)rx->nraw;
+    DevMem &m = rx->mem;
+    PIRIP_TRY(m.alloc(&rx->d_rows, rx->row_bytes * ns));
+    if (raw_bytes) PIRIP_TRY(m.alloc(&rx->d_raw, raw_bytes));
+    PIRIP_TRY(m.alloc(&rx->d_consumed, sizeof(int64_t) * ns));
+    PIRIP_TRY(m.alloc(&rx->d_total, sizeof(int64_t) * ns));
+    PIRIP_TRY(m.alloc(&rx->d_carry, sizeof(int32_t) * ns));
+    PIRIP_TRY(m.alloc(&rx->d_flag, sizeof(int32_t)));
+    PIRIP_TRY(m.alloc(&rx->d_seg, sizeof(SegDesc) * ns));
+    // (rows start zeroed: nothing reads bytes the caller or the decimator did not write, but a fresh buffer is not left to chance)
+    PIRIP_HIPCHK(hipMemset(rx->d_rows, 0, rx->row_bytes * ns));
+    if (rx->d_raw) PIRIP_HIPCHK(hipMemset(rx->d_raw, 0, raw_bytes));
+    PIRIP_HIPCHK(hipMemset(rx->d_seg, 0, sizeof(SegDesc) * ns));
+    PIRIP_TRY(rx_clear(rx, nullptr));
+    PIRIP_HIPCHK(hipDeviceSynchronize());
     return PIRIP_OK;
 }
 
@@ -261,26 +271,12 @@ int rx_create_impl(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *
     if (dem->kernel == PIRIP_KERNEL_WAVE && rx->c_pre + rx->m > demod_wave_max_samples(d)) { delete rx; return PIRIP_ERR_UNSUPPORTED; }
     if (rx->budget > (1 << 24)) { delete rx; return PIRIP_ERR_UNSUPPORTED; }
     rx->row_bytes = round_up((size_t)(rx->c_pre + rx->m) * rx->bps, 256);
-    const size_t ns = (size_t)rx->nstreams;
-    bool ok = hipMalloc((void **)&rx->d_rows, rx->row_bytes * ns) == hipSuccess;
     if (dec || chan) {
         rx->raw_pre = round_up((size_t)rx->H * 2, 256);
         rx->raw_row_bytes = round_up(rx->raw_pre + (size_t)block * 2, 256);
-        ok &= hipMalloc((void **)&rx->d_raw, rx->raw_row_bytes * (size_t)nraw) == hipSuccess;
     }
-    ok &= hipMalloc((void **)&rx->d_consumed, sizeof(int64_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&rx->d_total, sizeof(int64_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&rx->d_carry, sizeof(int32_t) * ns) == hipSuccess;
-    ok &= hipMalloc((void **)&rx->d_flag, sizeof(int32_t)) == hipSuccess;
-    ok &= hipMalloc((void **)&rx->d_seg, sizeof(SegDesc) * ns) == hipSuccess;
-    if (!ok) { rx_free(rx); delete rx; return PIRIP_ERR_NOMEM; }
-    // (rows start zeroed: nothing reads bytes the caller or the decimator did not write, but a fresh buffer is not left to chance)
-    ok = hipMemset(rx->d_rows, 0, rx->row_bytes * ns) == hipSuccess;
-    if (rx->d_raw) ok &= hipMemset(rx->d_raw, 0, rx->raw_row_bytes * (size_t)nraw) == hipSuccess;
-    ok &= hipMemset(rx->d_seg, 0, sizeof(SegDesc) * ns) == hipSuccess;
-    ok &= rx_clear(rx, nullptr) == PIRIP_OK;
-    ok &= hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { rx_free(rx); delete rx; return PIRIP_ERR_HIP; }
+    const int rc = rx_alloc(rx);
+    if (rc != PIRIP_OK) { delete rx; return rc; }
     *out = rx;
     return PIRIP_OK;
 }
@@ -305,7 +301,6 @@ int pirip_hip_rx_destroy(pirip_hip_rx *rx)
     if (!rx) return PIRIP_ERR_BAD_ARG;
     (void)demod_bind(rx->dem);
     (void)hipDeviceSynchronize();
-    rx_free(rx);
     delete rx;
     return PIRIP_OK;
 }
@@ -340,8 +335,8 @@ int pirip_hip_rx_push(pirip_hip_rx *rx, const void *d_in, size_t in_stride_bytes
     const size_t width = (size_t)rx->block * (rx->dec || rx->chan ? 2 : rx->bps);
     const int rows = rx->chan ? rx->nraw : rx->nstreams;
     if (in_stride_bytes < width && rows > 1) return PIRIP_ERR_BAD_ARG;
-    if (hipMemcpy2DAsync(dst, dpitch, d_in, in_stride_bytes ? in_stride_bytes : width, width, (size_t)rows, hipMemcpyDeviceToDevice,
-                         (hipStream_t)hip_stream) != hipSuccess) return PIRIP_ERR_HIP;
+    PIRIP_HIPCHK(hipMemcpy2DAsync(dst, dpitch, d_in, in_stride_bytes ? in_stride_bytes : width, width, (size_t)rows, hipMemcpyDeviceToDevice,
+                                  (hipStream_t)hip_stream));
     return rx_run(rx, d_bits, bits_stride, d_rx_filt, filt_stride, d_status, d_payload, d_info, d_stats, stats_stride, d_nframes, (hipStream_t)hip_stream);
 }
 
@@ -351,10 +346,10 @@ int pirip_hip_rx_get_counters(pirip_hip_rx *rx, int64_t *consumed_total, int32_t
     if (!demod_bind(rx->dem)) return PIRIP_ERR_NO_DEVICE;
     const size_t ns = (size_t)rx->nstreams;
     int32_t flag = 0;
-    if (hipDeviceSynchronize() != hipSuccess) return PIRIP_ERR_HIP;
-    if (consumed_total && hipMemcpy(consumed_total, rx->d_total, sizeof(int64_t) * ns, hipMemcpyDeviceToHost) != hipSuccess) return PIRIP_ERR_HIP;
-    if (backlog && hipMemcpy(backlog, rx->d_carry, sizeof(int32_t) * ns, hipMemcpyDeviceToHost) != hipSuccess) return PIRIP_ERR_HIP;
-    if (hipMemcpy(&flag, rx->d_flag, sizeof(flag), hipMemcpyDeviceToHost) != hipSuccess) return PIRIP_ERR_HIP;
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    if (consumed_total) PIRIP_HIPCHK(hipMemcpy(consumed_total, rx->d_total, sizeof(int64_t) * ns, hipMemcpyDeviceToHost));
+    if (backlog) PIRIP_HIPCHK(hipMemcpy(backlog, rx->d_carry, sizeof(int32_t) * ns, hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(&flag, rx->d_flag, sizeof(flag), hipMemcpyDeviceToHost));
     return flag ? PIRIP_ERR_HIP : PIRIP_OK;
 }
 

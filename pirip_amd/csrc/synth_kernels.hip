@@ -21,6 +21,9 @@
 #include <vector>
 
 #include "../../include/pirip_hip.h"
+#include "noise_device.hpp"
+
+using namespace pirip;
 
 namespace {
 
@@ -34,14 +37,6 @@ struct SynthArgs {
     float amp, sigma;
     uint64_t seed;
 };
-
-__device__ __forceinline__ uint64_t splitmix(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
 
 __global__ __launch_bounds__(64) void synth_kernel(SynthArgs a)
 {
@@ -66,18 +61,8 @@ __global__ __launch_bounds__(64) void synth_kernel(SynthArgs a)
             pr = nr; pi = ni;
             if (n >= 0 && n < a.nsamp) {
                 float xr = 2 * pr, xi = 2 * pi;
-                if (a.sigma > 0.f) {
-                    const uint64_t r = splitmix(a.seed ^ splitmix(((uint64_t)s << 40) ^ (uint64_t)n));
-                    const float u1 = ((float)(uint32_t)(r >> 40) + 1.0f) * (1.0f / 16777216.0f);     // (0,1]
-                    const float u2 = (float)(uint32_t)((r >> 8) & 0xffffffu) * (1.0f / 16777216.0f); // [0,1)
-                    const float mag = a.sigma * sqrtf(-2.0f * logf(u1));
-                    float sn, cs;
-                    sincosf(6.2831853071795865f * u2, &sn, &cs);
-                    xr += mag * cs; xi += mag * sn;
-                }
-                float qr = rintf(127.0f + a.amp * xr), qi = rintf(127.0f + a.amp * xi);
-                qr = fminf(fmaxf(qr, 0.f), 255.f); qi = fminf(fmaxf(qi, 0.f), 255.f);
-                *(uchar2 *)(out + 2 * n) = make_uchar2((unsigned char)qr, (unsigned char)qi);
+                if (a.sigma > 0.f) add_awgn(a.seed, s, n, a.sigma, xr, xi);
+                *(uchar2 *)(out + 2 * n) = make_uchar2((unsigned char)quant_u8(xr, a.amp), (unsigned char)quant_u8(xi, a.amp));
             }
         }
         if ((i + 1) % a.norm_syms == 0) {         // comp_normalize() at the end of each fsk_mod_c call
@@ -97,8 +82,7 @@ extern "C" int pirip_hip_synth_cu8(int Fs, int Rs, int M, int nstreams,
 {
     if (!f1_hz || !d_bits || !d_out || nstreams <= 0 || nsym < 0 || nsamp < 0) return PIRIP_ERR_BAD_ARG;
     if (Fs <= 0 || Rs <= 0 || Fs % Rs || (M != 2 && M != 4) || tone_spacing_hz <= 0) return PIRIP_ERR_BAD_CONFIG;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return PIRIP_ERR_NO_DEVICE;
+    if (pirip_hip_device_count() <= 0) return PIRIP_ERR_NO_DEVICE;
     // per-stream tone phasors exactly as fsk_mod computes them: comp_exp_j(2*pi*(f1 + m*spacing)/Fs)
     std::vector<float> dosc((size_t)nstreams * M * 2);
     for (int s = 0; s < nstreams; s++)

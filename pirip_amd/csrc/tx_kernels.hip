@@ -33,6 +33,8 @@
 
 #include "../../include/pirip_hip.h"
 #include "fsk_ldpc.hpp"
+#include "hip_host.hpp"
+#include "noise_device.hpp"
 
 using namespace pirip;
 
@@ -235,14 +237,6 @@ __global__ __launch_bounds__(kScanThreads) void tx_prefix_kernel(ModArgs a)
     if (tid == 0) a.phase[s] = carry;
 }
 
-__device__ __forceinline__ uint64_t splitmix(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 // (a b) mod Fs for 0 <= a, b <= 2^24: the product is exact in double, the quotient right or one off, the remainder exact
 __device__ __forceinline__ uint32_t mulmod(uint32_t x, uint32_t y, int Fs, double inv_fs)
 {
@@ -265,23 +259,11 @@ __device__ __forceinline__ float2 sample(const ModArgs &a, bool on, uint32_t p, 
         sincospif((float)pc * a.two_over_fs, &sn, &cs);
         xr = 2 * cs; xi = 2 * sn;
     }
-    if (a.sigma > 0.f) {                                    // synth_kernels.hip's generator and key
-        const uint64_t r = splitmix(a.seed ^ splitmix(((uint64_t)s << 40) ^ (uint64_t)nabs));
-        const float u1 = ((float)(uint32_t)(r >> 40) + 1.0f) * (1.0f / 16777216.0f);     // (0,1]
-        const float u2 = (float)(uint32_t)((r >> 8) & 0xffffffu) * (1.0f / 16777216.0f); // [0,1)
-        const float mag = a.sigma * sqrtf(-2.0f * logf(u1));
-        float sn, cs;
-        sincosf(6.2831853071795865f * u2, &sn, &cs);
-        xr += mag * cs; xi += mag * sn;
-    }
+    if (a.sigma > 0.f) add_awgn(a.seed, s, nabs, a.sigma, xr, xi);      // synth_kernels.hip's generator and key
     return make_float2(xr, xi);
 }
 
-__device__ __forceinline__ uint32_t quant(float v, float amp)
-{
-    const float q = rintf(127.0f + amp * v);
-    return (uint32_t)fminf(fmaxf(q, 0.f), 255.f);
-}
+__device__ __forceinline__ uint32_t quant(float v, float amp) { return (uint32_t)quant_u8(v, amp); }
 
 // SPU samples per 16-byte unit: 8 (u8 IQ) or 2 (complex float)
 template <int SPU>
@@ -435,10 +417,11 @@ __global__ __launch_bounds__(64) void tx_repeat_kernel(RepeatArgs a)
 
 struct pirip_hip_tx {
     LdpcCode code;
-    int Fs = 0, Rs = 0, M = 0, Ts = 0, bps = 1, nstreams = 0, device = 0, last_hip = 0;
+    int Fs = 0, Rs = 0, M = 0, Ts = 0, bps = 1, nstreams = 0, device = 0;
     int pre_bits = 0;
     int64_t samples_sent = 0;              // per stream since create / reset (every stream sends the same count per call)
     int max_lead = 0, max_gap = 0;
+    DevMem mem;
     int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr, *d_lead = nullptr, *d_gap = nullptr, *d_nsym = nullptr;
     uint32_t *d_fm = nullptr, *d_tm = nullptr, *d_phase = nullptr;
     // work buffers, grown on demand
@@ -451,28 +434,33 @@ struct pirip_hip_tx {
 
 namespace {
 
-#define TCHK(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { h->last_hip = (int)e_; return PIRIP_ERR_HIP; } } while (0)
-
-void tx_free(pirip_hip_tx *h)
-{
-    void *ptrs[] = {h->d_row_ptr, h->d_col_idx, h->d_lead, h->d_gap, h->d_nsym, h->d_fm, h->d_tm, h->d_phase, h->d_off, h->d_prefix, h->d_syms, h->d_rep_state, h->d_rep_held};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
-}
-
-bool tx_bind(const pirip_hip_tx *h)
-{
-    int cur = -1;
-    if (hipGetDevice(&cur) == hipSuccess && cur == h->device) return true;
-    return hipSetDevice(h->device) == hipSuccess;
-}
-
+// a work buffer of `want` elements at least; calls in flight may still use the one it replaces
 template <typename T>
 int tx_grow(pirip_hip_tx *h, T **buf, size_t *cap, size_t want)
 {
     if (want <= *cap) return PIRIP_OK;
-    if (*buf) { TCHK(hipDeviceSynchronize()); (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
-    if (hipMalloc((void **)buf, want * sizeof(T)) != hipSuccess) return PIRIP_ERR_NOMEM;
-    *cap = want;
+    return grow_dev(h->mem, cap, want, *buf ? GrowSync::device : GrowSync::none, nullptr, {grow_buf(buf, want * sizeof(T))});
+}
+
+// the code's CSR and the per-stream settings of a new handle, zeroed
+int tx_alloc(pirip_hip_tx *h)
+{
+    const size_t S = (size_t)h->nstreams;
+    DevMem &m = h->mem;
+    PIRIP_TRY(m.upload(&h->d_row_ptr, h->code.row_ptr.data(), sizeof(int32_t) * h->code.row_ptr.size()));
+    PIRIP_TRY(m.upload(&h->d_col_idx, h->code.col_idx.data(), sizeof(int32_t) * h->code.col_idx.size()));
+    PIRIP_TRY(m.alloc(&h->d_lead, sizeof(int32_t) * S));
+    PIRIP_TRY(m.alloc(&h->d_gap, sizeof(int32_t) * S));
+    PIRIP_TRY(m.alloc(&h->d_nsym, sizeof(int32_t) * S));
+    PIRIP_TRY(m.alloc(&h->d_fm, sizeof(uint32_t) * 4 * S));
+    PIRIP_TRY(m.alloc(&h->d_tm, sizeof(uint32_t) * 4 * S));
+    PIRIP_TRY(m.alloc(&h->d_phase, sizeof(uint32_t) * S));
+    PIRIP_HIPCHK(hipMemset(h->d_lead, 0, sizeof(int32_t) * S));
+    PIRIP_HIPCHK(hipMemset(h->d_gap, 0, sizeof(int32_t) * S));
+    PIRIP_HIPCHK(hipMemset(h->d_fm, 0, sizeof(uint32_t) * 4 * S));
+    PIRIP_HIPCHK(hipMemset(h->d_tm, 0, sizeof(uint32_t) * 4 * S));
+    PIRIP_HIPCHK(hipMemset(h->d_phase, 0, sizeof(uint32_t) * S));
+    PIRIP_HIPCHK(hipDeviceSynchronize());
     return PIRIP_OK;
 }
 
@@ -495,26 +483,9 @@ int pirip_hip_tx_create(const char *code_path, int Fs, int Rs, int M, int nstrea
     h->pre_bits = (int)preamble_bits(M).size();
     // the kernels' tiling: whole symbols per frame and per preamble, 32-bit sample counts in the phase integers
     if (Fs > kMaxFs || h->code.bits_per_frame() % h->bps || h->pre_bits % h->bps) { delete h; return PIRIP_ERR_UNSUPPORTED; }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { delete h; return PIRIP_ERR_NO_DEVICE; }
-    if (device >= 0 && (device >= ndev || hipSetDevice(device) != hipSuccess)) { delete h; return PIRIP_ERR_NO_DEVICE; }
-    if (hipGetDevice(&h->device) != hipSuccess) { delete h; return PIRIP_ERR_NO_DEVICE; }
-    const size_t S = (size_t)nstreams, nr = h->code.row_ptr.size(), ne = h->code.col_idx.size();
-    bool ok = hipMalloc((void **)&h->d_row_ptr, sizeof(int32_t) * nr) == hipSuccess &&
-              hipMalloc((void **)&h->d_col_idx, sizeof(int32_t) * ne) == hipSuccess &&
-              hipMalloc((void **)&h->d_lead, sizeof(int32_t) * S) == hipSuccess &&
-              hipMalloc((void **)&h->d_gap, sizeof(int32_t) * S) == hipSuccess &&
-              hipMalloc((void **)&h->d_nsym, sizeof(int32_t) * S) == hipSuccess &&
-              hipMalloc((void **)&h->d_fm, sizeof(uint32_t) * 4 * S) == hipSuccess &&
-              hipMalloc((void **)&h->d_tm, sizeof(uint32_t) * 4 * S) == hipSuccess &&
-              hipMalloc((void **)&h->d_phase, sizeof(uint32_t) * S) == hipSuccess;
-    if (!ok) { tx_free(h); delete h; return PIRIP_ERR_NOMEM; }
-    ok = hipMemcpy(h->d_row_ptr, h->code.row_ptr.data(), sizeof(int32_t) * nr, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemcpy(h->d_col_idx, h->code.col_idx.data(), sizeof(int32_t) * ne, hipMemcpyHostToDevice) == hipSuccess &&
-         hipMemset(h->d_lead, 0, sizeof(int32_t) * S) == hipSuccess && hipMemset(h->d_gap, 0, sizeof(int32_t) * S) == hipSuccess &&
-         hipMemset(h->d_fm, 0, sizeof(uint32_t) * 4 * S) == hipSuccess && hipMemset(h->d_tm, 0, sizeof(uint32_t) * 4 * S) == hipSuccess &&
-         hipMemset(h->d_phase, 0, sizeof(uint32_t) * S) == hipSuccess && hipDeviceSynchronize() == hipSuccess;
-    if (!ok) { tx_free(h); delete h; return PIRIP_ERR_HIP; }
+    int rc = select_device(device, &h->device);
+    if (rc == PIRIP_OK) rc = tx_alloc(h);
+    if (rc != PIRIP_OK) { delete h; return rc; }
     *out = h;
     return PIRIP_OK;
 }
@@ -522,9 +493,8 @@ int pirip_hip_tx_create(const char *code_path, int Fs, int Rs, int M, int nstrea
 int pirip_hip_tx_destroy(pirip_hip_tx *h)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
-    (void)hipSetDevice(h->device);
+    (void)bind_device(h->device);
     (void)hipDeviceSynchronize();
-    tx_free(h);
     delete h;
     return PIRIP_OK;
 }
@@ -543,7 +513,7 @@ int pirip_hip_tx_get_info(const pirip_hip_tx *h, pirip_tx_info *info)
 int pirip_hip_tx_set_tones(pirip_hip_tx *h, const int32_t *f1_hz, int tone_spacing_hz)
 {
     if (!h || !f1_hz) return PIRIP_ERR_BAD_ARG;
-    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     std::vector<uint32_t> fm((size_t)h->nstreams * 4, 0), tm((size_t)h->nstreams * 4, 0);
     for (int s = 0; s < h->nstreams; s++)
         for (int m = 0; m < h->M; m++) {
@@ -551,16 +521,16 @@ int pirip_hip_tx_set_tones(pirip_hip_tx *h, const int32_t *f1_hz, int tone_spaci
             fm[(size_t)s * 4 + m] = (uint32_t)f;
             tm[(size_t)s * 4 + m] = (uint32_t)((f * h->Ts) % h->Fs);
         }
-    TCHK(hipDeviceSynchronize());                            // calls in flight still read the old tones
-    TCHK(hipMemcpy(h->d_fm, fm.data(), sizeof(uint32_t) * fm.size(), hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(h->d_tm, tm.data(), sizeof(uint32_t) * tm.size(), hipMemcpyHostToDevice));
+    PIRIP_HIPCHK(hipDeviceSynchronize());                    // calls in flight still read the old tones
+    PIRIP_HIPCHK(hipMemcpy(h->d_fm, fm.data(), sizeof(uint32_t) * fm.size(), hipMemcpyHostToDevice));
+    PIRIP_HIPCHK(hipMemcpy(h->d_tm, tm.data(), sizeof(uint32_t) * tm.size(), hipMemcpyHostToDevice));
     return PIRIP_OK;
 }
 
 int pirip_hip_tx_set_gaps(pirip_hip_tx *h, const int32_t *lead_syms, const int32_t *gap_syms)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
-    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     std::vector<int32_t> lead((size_t)h->nstreams, 0), gap((size_t)h->nstreams, 0);
     int ml = 0, mg = 0;
     for (int s = 0; s < h->nstreams; s++) {
@@ -568,9 +538,9 @@ int pirip_hip_tx_set_gaps(pirip_hip_tx *h, const int32_t *lead_syms, const int32
         if (lead_syms) { lead[(size_t)s] = lead_syms[s]; if (lead_syms[s] > ml) ml = lead_syms[s]; }
         if (gap_syms) { gap[(size_t)s] = gap_syms[s]; if (gap_syms[s] > mg) mg = gap_syms[s]; }
     }
-    TCHK(hipDeviceSynchronize());
-    TCHK(hipMemcpy(h->d_lead, lead.data(), sizeof(int32_t) * lead.size(), hipMemcpyHostToDevice));
-    TCHK(hipMemcpy(h->d_gap, gap.data(), sizeof(int32_t) * gap.size(), hipMemcpyHostToDevice));
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipMemcpy(h->d_lead, lead.data(), sizeof(int32_t) * lead.size(), hipMemcpyHostToDevice));
+    PIRIP_HIPCHK(hipMemcpy(h->d_gap, gap.data(), sizeof(int32_t) * gap.size(), hipMemcpyHostToDevice));
     h->max_lead = ml; h->max_gap = mg;
     return PIRIP_OK;
 }
@@ -578,9 +548,9 @@ int pirip_hip_tx_set_gaps(pirip_hip_tx *h, const int32_t *lead_syms, const int32
 int pirip_hip_tx_reset(pirip_hip_tx *h, void *hip_stream)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
-    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
-    TCHK(hipMemsetAsync(h->d_phase, 0, sizeof(uint32_t) * (size_t)h->nstreams, (hipStream_t)hip_stream));
-    if (h->d_rep_state) TCHK(hipMemsetAsync(h->d_rep_state, 0, sizeof(int32_t) * 2 * (size_t)h->nstreams, (hipStream_t)hip_stream));
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
+    PIRIP_HIPCHK(hipMemsetAsync(h->d_phase, 0, sizeof(uint32_t) * (size_t)h->nstreams, (hipStream_t)hip_stream));
+    if (h->d_rep_state) PIRIP_HIPCHK(hipMemsetAsync(h->d_rep_state, 0, sizeof(int32_t) * 2 * (size_t)h->nstreams, (hipStream_t)hip_stream));
     h->samples_sent = 0;
     return PIRIP_OK;
 }
@@ -601,7 +571,7 @@ int pirip_hip_tx_frame(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_str
     if (max_syms < need || sym_stride < (size_t)max_syms || (d_bits && bits_stride < (size_t)max_syms * h->bps)) return PIRIP_ERR_BAD_ARG;
     if (rec_stride < (size_t)max_rec * (size_t)(1 + h->code.data_bytes())) return PIRIP_ERR_BAD_ARG;
     if (max_syms > 0x7fffffff || (max_rec + kFrameWaves - 1) / kFrameWaves > 65535 || h->nstreams > 65535) return PIRIP_ERR_UNSUPPORTED;
-    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     const int rc = tx_grow(h, &h->d_off, &h->off_cap, (size_t)h->nstreams * (size_t)(max_rec > 0 ? max_rec : 1));
     if (rc != PIRIP_OK) return rc;
     FrameArgs a{};
@@ -620,7 +590,7 @@ int pirip_hip_tx_frame(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_str
     if (max_rec > 0)
         hipLaunchKernelGGL(tx_frame_kernel, dim3((unsigned)((max_rec + kFrameWaves - 1) / kFrameWaves), (unsigned)h->nstreams), dim3(kFrameWaves * 64),
                            (size_t)kFrameWaves * a.wave_lds, st, a);
-    TCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;
 }
 
@@ -635,7 +605,7 @@ int pirip_hip_tx_modulate(pirip_hip_tx *h, const uint8_t *d_syms, size_t sym_str
     if (nsamp > 0x7fffffff) return PIRIP_ERR_UNSUPPORTED;
     if (out_stride_bytes < (size_t)nsamp * bsamp && h->nstreams > 1) return PIRIP_ERR_BAD_ARG;
     if (nsym == 0) return PIRIP_OK;
-    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     const int rc = tx_grow(h, &h->d_prefix, &h->prefix_cap, (size_t)h->nstreams * (size_t)nsym);
     if (rc != PIRIP_OK) return rc;
     ModArgs a{};
@@ -652,7 +622,7 @@ int pirip_hip_tx_modulate(pirip_hip_tx *h, const uint8_t *d_syms, size_t sym_str
                     (unsigned)((h->nstreams + 65534) / 65535));
     if (spu == 8) hipLaunchKernelGGL(tx_mod_kernel<8>, grid, dim3(kModThreads), 0, st, a);
     else hipLaunchKernelGGL(tx_mod_kernel<2>, grid, dim3(kModThreads), 0, st, a);
-    TCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     h->samples_sent += nsamp;
     return PIRIP_OK;
 }
@@ -662,7 +632,7 @@ int pirip_hip_tx_records_to_iq(pirip_hip_tx *h, const uint8_t *d_records, size_t
                                int32_t *d_nsym, void *hip_stream)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
-    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     int64_t cap = pirip_hip_tx_max_syms(h, max_rec);
     if (cap < 1) cap = 1;
     int rc = tx_grow(h, &h->d_syms, &h->syms_cap, (size_t)h->nstreams * (size_t)cap);
@@ -688,12 +658,16 @@ int pirip_hip_tx_repeat_records(pirip_hip_tx *h, const uint8_t *d_status, size_t
     if (status_stride < (size_t)ncalls || payload_stride < (size_t)ncalls * kb || rec_stride < (size_t)max_rec * (size_t)(1 + kb)) return PIRIP_ERR_BAD_ARG;
     if (max_rec < pirip_hip_tx_repeat_max_records(h, ncalls)) return PIRIP_ERR_BAD_ARG;
     if (ncalls > 4096) return PIRIP_ERR_UNSUPPORTED;         // the call table lives in LDS
-    if (!tx_bind(h)) return PIRIP_ERR_NO_DEVICE;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     if (!h->d_rep_state) {
+        // first use: both buffers, the state zeroed, and only then the handle's pointers -- a failure leaves neither behind
         const size_t S = (size_t)h->nstreams;
-        if (hipMalloc((void **)&h->d_rep_state, sizeof(int32_t) * 2 * S) != hipSuccess ||
-            hipMalloc((void **)&h->d_rep_held, S * PIRIP_TX_REPEAT_MAX_FRAMES * (size_t)kb) != hipSuccess) return PIRIP_ERR_NOMEM;
-        TCHK(hipMemset(h->d_rep_state, 0, sizeof(int32_t) * 2 * S));
+        int32_t *state = nullptr; uint8_t *held = nullptr;
+        int rc = h->mem.alloc(&state, sizeof(int32_t) * 2 * S);
+        if (rc == PIRIP_OK) rc = h->mem.alloc(&held, S * PIRIP_TX_REPEAT_MAX_FRAMES * (size_t)kb);
+        if (rc == PIRIP_OK && hipMemset(state, 0, sizeof(int32_t) * 2 * S) != hipSuccess) rc = PIRIP_ERR_HIP;
+        if (rc != PIRIP_OK) { h->mem.release(&state); h->mem.release(&held); return rc; }
+        h->d_rep_state = state; h->d_rep_held = held;
     }
     RepeatArgs a{};
     a.status = d_status; a.status_stride = status_stride; a.payload = d_payload; a.payload_stride = payload_stride; a.ncalls_s = d_ncalls; a.ncalls = ncalls;
@@ -701,7 +675,7 @@ int pirip_hip_tx_repeat_records(pirip_hip_tx *h, const uint8_t *d_status, size_t
     a.state = h->d_rep_state; a.held = h->d_rep_held; a.kb = kb; a.max_burst = PIRIP_TX_REPEAT_MAX_FRAMES; a.source = source_byte;
     const size_t lds = sizeof(int32_t) * (3 * (size_t)ncalls + 2) + (size_t)ncalls + 16;
     hipLaunchKernelGGL(tx_repeat_kernel, dim3((unsigned)h->nstreams), dim3(64), lds, (hipStream_t)hip_stream, a);
-    TCHK(hipGetLastError());
+    PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;
 }
 
