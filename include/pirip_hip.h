@@ -451,7 +451,8 @@ typedef struct pirip_chan_info {
  * the one-shot output bit for bit, and a channel's output does not depend on which other channels the handle has. csdr's own
  * shift_addition_cc runs a recursive cos/sin phasor restarted every buffer (its rounding depends on csdr's buffer size): that recursion
  * is deliberately not reproduced. PIRIP_ERR_BAD_ARG for nchan < 1, ninputs < 1, D < 1, a chan_input outside [0, ninputs) or an offset
- * outside -Fs/2 < f_c < Fs/2; PIRIP_ERR_UNSUPPORTED for Fs > 2^24. */
+ * outside -Fs/2 < f_c < Fs/2; PIRIP_ERR_UNSUPPORTED for Fs > 2^24, and for a decimation of which two rows no longer fit the 64 KiB of
+ * LDS a workgroup stages its window in (D > 4095 at up to D taps). */
 int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s16, int ninputs, int nchan, const int32_t *chan_input,
                           const int32_t *chan_offset_hz, int device, pirip_hip_chan **out);
 int pirip_hip_chan_destroy(pirip_hip_chan *ch);

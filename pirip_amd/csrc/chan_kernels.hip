@@ -36,7 +36,7 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxGroup = 8;               // channels per lane (accumulator pairs)
-constexpr int kMaxFs = 1 << 24;            // the rotation's index arithmetic is exact in 32 bits below this (see rotation())
+constexpr int kMaxFs = 1 << 24;            // the rotation's index arithmetic is exact in 32 bits up to this (see rotation())
 constexpr size_t kLdsTarget = 40 * 1024;   // staged window per workgroup: four workgroups per CU
 constexpr size_t kLdsMax = 64 * 1024;
 
@@ -77,13 +77,15 @@ __device__ __forceinline__ int32_t mulmod(int64_t a, int64_t b, int Fs, double i
 }
 
 // e^{-j w_c n} for n = n0 + k D, as p = (B + k S) mod Fs with B = f_c n0 mod Fs and S = f_c D mod Fs: v = B + k S < 256 Fs <= 2^32 (k < 256,
-// Fs <= 2^24), the float quotient is right or one off, the 32-bit remainder exact. The angle goes to sincospi as a fraction of pi in
-// [-1, 1): p is the same integer however a capture is split, so is the rotation.
+// Fs <= 2^24; k and S each fit the 24-bit multiply). The float quotient q <= 256 is right or one off; q Fs is a full 32-bit multiply
+// (Fs = 2^24 itself does not fit the 24-bit one) that stays below 2^32, so the remainder is exact, within one Fs of [0, Fs), and 2 r
+// stays below 2^26. The angle goes to sincospi as a fraction of pi in [-1, 1), from |r| <= 2^23 exact in float: p is the same integer
+// however a capture is split, so is the rotation.
 __device__ __forceinline__ dv2f rotation(uint32_t B, uint32_t S, uint32_t k, const ChanArgs &a)
 {
     const uint32_t v = B + __umul24(k, S);
     const uint32_t q = (uint32_t)((float)v * a.inv_fs);
-    int32_t r = (int32_t)(v - __umul24(q, (uint32_t)a.Fs));
+    int32_t r = (int32_t)(v - q * (uint32_t)a.Fs);
     if (r < 0) r += a.Fs;
     if (r >= a.Fs) r -= a.Fs;
     if (2 * r > a.Fs) r -= a.Fs;

@@ -34,8 +34,45 @@ def channel(u8, h, D, Fs, fc, t0=0):
 
 
 def bound(h):
-    """contract 1: every complex-float component within 1e-5 * sum |h| of the float64 value"""
-    return 1e-5 * float(np.sum(np.abs(np.asarray(h, dtype=np.float64))))
+    """contract 1: every complex-float component within 1e-5 * sum |h| of the float64 value. Past Lp = 84 the same derivation at its worst
+    case: each component is one chain of 2 Lp float fmas, each rounding at most 2^-24 of a partial sum that sum |h| bounds, then a
+    handful of roundings from the rotation -- (2 Lp + 8) 2^-24 sum |h|."""
+    s = float(np.sum(np.abs(np.asarray(h, dtype=np.float64))))
+    Lp = lp_of(h)
+    return 1e-5 * s if Lp <= 84 else (2 * Lp + 8) * 2.0 ** -24 * s
+
+
+def filter_len(transition_bw):
+    """csdr's firdes_filter_len on the float the C entry point receives: 0.05f lies above 0.05, so the default is 79 taps, not 81"""
+    L = int(4.0 / float(np.float32(transition_bw)))
+    return L + 1 - L % 2
+
+
+# The two functions below mirror the constants of pirip_hip_chan_create (pirip_amd/csrc/chan_kernels.hip: kThreads 256, kMaxGroup 8,
+# kLdsTarget 40 KiB, kLdsMax 64 KiB) and must move with them. They compute nothing that a test compares with the device: they exist so
+# that a shape table can assert which of the kernel's paths each of its shapes reaches.
+def tile_geometry(D, Lp):
+    """(P, Tpad, T, lds_bytes) of the host rule, or None where it answers PIRIP_ERR_UNSUPPORTED: row pitch P = D | 1, Tpad the most
+    outputs (256 down to 64 in steps of 64) whose staged window fits 40 KiB, T = Tpad lowered until the window fits 64 KiB"""
+    P = D | 1
+    lds = lambda T: (T + -(-Lp // D)) * P * 8
+    Tpad = 256
+    while Tpad > 64 and lds(Tpad) > 40 * 1024:
+        Tpad -= 64
+    T = Tpad
+    while T > 1 and lds(T) > 64 * 1024:
+        T -= 1
+    return None if lds(T) > 64 * 1024 else (P, Tpad, T, lds(T))
+
+
+def group_sizes(K, Tpad):
+    """the sizes of the balanced groups (at most 8 channels each) that K channels of one capture are split into: at least
+    ceil(256 / Tpad) of them, so that every wave of the workgroup has work"""
+    fill = -(-256 // Tpad)
+    ng = -(-K // 8)
+    if ng < fill:
+        ng = min(K, fill)
+    return [K // ng + (1 if g < K % ng else 0) for g in range(ng)]
 
 
 def to_s16(y):
