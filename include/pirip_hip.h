@@ -20,6 +20,8 @@
  *              the input; also the front end of a section G receiver.
  *   section I  FSK_LDPC transmit (pirip_hip_tx_*)           : rpitx_fsk --code's record protocol ->
  *              channel symbols -> continuous-phase M-FSK IQ for a batch of streams.
+ *   section J  multiplexer (pirip_hip_mux_*)               : K modem-rate channels interpolated,
+ *              shifted, scaled and summed onto W wideband u8 / complex float IQ streams.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -542,6 +544,54 @@ int pirip_hip_tx_repeat_records(pirip_hip_tx *h, const uint8_t *d_status, size_t
                                 int32_t *d_nrec, void *hip_stream);
 /* One HIP stream per handle: the phase, the repeater's state and the work buffers are device state advanced in stream order, the sample
  * count of the noise key is host state advanced when a call is enqueued. Calls on one handle from several streams must be ordered by the caller. */
+
+/* ----------------------------------------------------------------------------------- */
+/* section J : multiplexer (K modem-rate channels onto W wideband IQ streams)           */
+/*   The channelizer's mirror image and the last Tx stage: per channel interpolate by D, */
+/*   move to the centre offset, scale; sum the channels of an output; u8 or complex      */
+/*   float out. For one channel this is the reference bench chain's     */
+/*   `tlininterp - t.iq8 D -d -f` (/root/reference/README.md:142) with PIRIP_MUX_LINEAR. */
+/* ----------------------------------------------------------------------------------- */
+#define PIRIP_MUX_FIR    0   /* h[i] = D * h_B[i], h_B section B's / H's csdr Hamming low-pass for the same D / transition_bw (cutoff 0.5/D) */
+#define PIRIP_MUX_LINEAR 1   /* h[i] = 1 - |i - (D-1)| / D, i = 0 .. 2D-2: linear interpolation, delayed by D - 1 samples; D = 1: h = {1} */
+typedef struct pirip_hip_mux pirip_hip_mux;
+typedef struct pirip_mux_info {
+    int Fs, D, kind, ntaps, ntaps_padded, Q, noutputs, nchan, out_format, device;
+} pirip_mux_info;
+/* noutputs wideband streams at Fs samples/s; nchan channels at Fs / D, channel c = (output chan_output[c], centre offset chan_offset_hz[c]
+ * in integer Hz, real gain chan_gain[c]; chan_gain NULL = all 1). The prototype h has L taps (ntaps), Q = ceil(L / D) per polyphase branch,
+ * padded with zeros to Lp = Q D (ntaps_padded). With z_c[m] the channel's complex float samples, m the absolute input index, n = mD + p and
+ * 0 <= p < D:
+ *     u_c[n] = sum_{q=0}^{Q-1} h[p + qD] z_c[m - q]
+ *     w_i[n] = sum_{c : chan_output[c] = i, ascending c} chan_gain[c] e^{+j 2 pi f_c n / Fs} u_c[n]
+ * PIRIP_MUX_LINEAR gives u[mD + p + D - 1] = (1 - p/D) z[m] + (p/D) z[m+1]. out_format PIRIP_IN_CF32: w itself; PIRIP_IN_CU8_CSDR: per
+ * component clamp(rintf(127.5f v + 127.5f), 0, 255), product and sum rounded separately -- the inverse of the channelizer's b/127.5 - 1.
+ * An output that no channel is assigned to is all zeros (cf32) / all bytes 128 (u8).
+ * Computed as g_c[i] = a_c h[i] e^{+j 2 pi f_c i / Fs} (host, double, rounded to float), one rotation per input sample,
+ * z'_c[m] = z_c[m] e^{+j 2 pi f_c m D / Fs} with the phase from the exact integer ((f_c D mod Fs)(m mod Fs)) mod Fs, and
+ * w_i[mD + p] = sum_c sum_q g_c[p + qD] z'_c[m - q]: each channel's sum its own fma chain in ascending q, the channels added in ascending
+ * index. A sample is a function of the absolute index and of its own output's channels only: consecutive calls that overlap by Q - 1
+ * input samples give the one-shot output bit for bit, m0 and m0 + k Fs give the same bytes, and an output does not depend on what the
+ * other outputs carry. Numerics: DESIGN.md 4.10.
+ * PIRIP_ERR_BAD_ARG for nchan < 1, noutputs < 1, D < 1, Fs < 2, an unknown kind or out_format, a chan_output outside [0, noutputs), an
+ * offset outside -Fs/2 < f_c < Fs/2, a gain that is not finite. PIRIP_ERR_UNSUPPORTED for Fs > 2^24, noutputs > 65535, and for a filter
+ * whose working set for ONE channel does not fit the 64 KiB of LDS a workgroup stages a tile of 2048 outputs in:
+ *     2048 B + 8 (Q Dp + floor((D + 2046) / D) + Q) > 65536,   B = 2 (u8) or 8 (cf32),  Dp = D (D <= 32) or D + 31
+ * -- with PIRIP_MUX_LINEAR, D > 3807 (u8) or D > 3039 (cf32). The number of channels per output is not limited: they are staged in groups
+ * of as many as fit (at most 8). */
+int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_bw, int out_format, int noutputs, int nchan,
+                         const int32_t *chan_output, const int32_t *chan_offset_hz, const float *chan_gain, int device, pirip_hip_mux **out);
+int pirip_hip_mux_destroy(pirip_hip_mux *mux);
+int pirip_hip_mux_get_info(const pirip_hip_mux *mux, pirip_mux_info *info);
+int pirip_hip_mux_taps(const pirip_hip_mux *mux, float *taps, int *ntaps);         /* host copy of the prototype h (ntaps, unpadded) */
+/* output samples per output for n_in input samples per channel: (n_in - Q + 1) D, or 0 when n_in < Q */
+int64_t pirip_hip_mux_nout(const pirip_hip_mux *mux, int64_t n_in);
+/* Channel c: n_in complex float samples at (char*)d_in + c*in_stride_bytes (8-byte aligned), the first with absolute index m0 (may be
+ * negative). Output i: pirip_hip_mux_nout(n_in) samples at (char*)d_out + i*out_stride_bytes, aligned to the output sample (2 or 8 bytes;
+ * 16-byte aligned rows get 16-byte stores, the bytes are the same), the first with absolute index (m0 + Q - 1) D. Rows of several outputs
+ * must not overlap (PIRIP_ERR_BAD_ARG). Stateless; enqueued on hip_stream (NULL = default stream), never synchronises. n_in D <= 2^40. */
+int pirip_hip_mux_batch(pirip_hip_mux *mux, const void *d_in, size_t in_stride_bytes, int64_t n_in, int64_t m0,
+                        void *d_out, size_t out_stride_bytes, void *hip_stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

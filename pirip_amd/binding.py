@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H and I).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I and J).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -38,6 +38,10 @@ class CaptureReport(C.Structure):
 
 class ChanInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("Fs", "D", "ntaps", "ntaps_padded", "ninputs", "nchan", "out_s16", "device")]
+
+
+class MuxInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("Fs", "D", "kind", "ntaps", "ntaps_padded", "Q", "noutputs", "nchan", "out_format", "device")]
 
 
 class TxInfo(C.Structure):
@@ -154,6 +158,13 @@ def lib():
     L.pirip_hip_tx_records_to_iq.argtypes = [vp, vp, sz, vp, i32, i64, i32, vp, sz, C.c_float, C.c_float, C.c_uint64, vp, vp]
     L.pirip_hip_tx_repeat_max_records.argtypes = [vp, i32]
     L.pirip_hip_tx_repeat_records.argtypes = [vp, vp, sz, vp, sz, vp, i32, i32, vp, sz, i32, vp, vp]
+    L.pirip_hip_mux_create.argtypes = [i32, i32, i32, C.c_float, i32, i32, i32, vp, vp, vp, i32, C.POINTER(vp)]
+    L.pirip_hip_mux_destroy.argtypes = [vp]
+    L.pirip_hip_mux_get_info.argtypes = [vp, C.POINTER(MuxInfo)]
+    L.pirip_hip_mux_taps.argtypes = [vp, vp, C.POINTER(i32)]
+    L.pirip_hip_mux_nout.restype = i64
+    L.pirip_hip_mux_nout.argtypes = [vp, i64]
+    L.pirip_hip_mux_batch.argtypes = [vp, vp, sz, i64, i64, vp, sz, vp]
     _lib = L
     return L
 
@@ -497,6 +508,65 @@ class HipTx:
                       amp=32.0, sigma=0.0, seed=1, stream=0):
         _chk(self.L.pirip_hip_tx_records_to_iq(self.h, d_records, rec_stride, d_nrec, int(max_rec), int(nsym), out_format, d_out, out_stride,
                                                amp, sigma, seed, d_nsym, stream), "pirip_hip_tx_records_to_iq")
+
+
+MUX_FIR, MUX_LINEAR = 0, 1
+
+
+class HipMux:
+    """Multiplexer (include/pirip_hip.h section J), the channelizer's mirror image: channel c (complex float at Fs / D) is interpolated
+    by D, moved to offsets[c] Hz, scaled by gains[c] (all 1 when gains is None) and added to wideband stream outputs[c] (all 0 when
+    outputs is None; noutputs: more streams than the largest index, the others empty). kind: MUX_FIR (D times section B's low-pass) or
+    MUX_LINEAR; out_format: IN_CU8_CSDR (u8 IQ) or IN_CF32."""
+
+    def __init__(self, Fs, D, offsets, outputs=None, gains=None, kind=MUX_FIR, transition_bw=0.05, out_format=IN_CU8_CSDR, device=-1,
+                 noutputs=None):
+        import numpy as np
+        self.L = lib()
+        off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
+        outp = np.zeros(off.size, dtype=np.int32) if outputs is None else np.ascontiguousarray(outputs, dtype=np.int32).reshape(-1)
+        g = None if gains is None else np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
+        if outp.size != off.size or (g is not None and g.size != off.size):
+            raise ValueError("outputs, gains and offsets must have the same length")
+        if noutputs is None:
+            noutputs = int(outp.max()) + 1 if outp.size else 1
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_mux_create(int(Fs), int(D), int(kind), transition_bw, int(out_format), int(noutputs), int(off.size),
+                                         outp.ctypes.data if outp.size else None, off.ctypes.data if off.size else None,
+                                         g.ctypes.data if g is not None and g.size else None, device, C.byref(h)), "pirip_hip_mux_create")
+        self.h = h
+        self.info = MuxInfo()
+        _chk(self.L.pirip_hip_mux_get_info(self.h, C.byref(self.info)), "pirip_hip_mux_get_info")
+        self.Fs, self.D, self.kind, self.out_format = int(Fs), int(D), int(kind), int(out_format)
+        self.offsets, self.outputs = off.copy(), outp.copy()
+        self.gains = np.ones(off.size, dtype=np.float32) if g is None else g.copy()
+        self.Q, self.ntaps, self.ntaps_padded = self.info.Q, self.info.ntaps, self.info.ntaps_padded
+        self.nchan, self.noutputs = self.info.nchan, self.info.noutputs
+        self.bytes_per_sample = 8 if out_format == IN_CF32 else 2
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_mux_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def taps(self):
+        """the prototype h (ntaps, unpadded)"""
+        import numpy as np
+        n = C.c_int(0)
+        self.L.pirip_hip_mux_taps(self.h, None, C.byref(n))
+        t = np.zeros(n.value, dtype=np.float32)
+        self.L.pirip_hip_mux_taps(self.h, t.ctypes.data, C.byref(n))
+        return t
+
+    def nout(self, n_in):
+        return int(self.L.pirip_hip_mux_nout(self.h, int(n_in)))
+
+    def batch(self, d_in, in_stride, n_in, d_out, out_stride, m0=0, stream=0):
+        """channel c at d_in + c * in_stride (n_in complex floats, the first at absolute index m0) -> output i at d_out + i * out_stride
+        (nout(n_in) samples, the first at absolute index (m0 + Q - 1) D); raw device pointers, enqueued on `stream`, does not synchronise"""
+        _chk(self.L.pirip_hip_mux_batch(self.h, d_in, in_stride, int(n_in), int(m0), d_out, out_stride, stream), "pirip_hip_mux_batch")
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

@@ -1,0 +1,331 @@
+// pirip_amd/csrc/mux_kernels.hip -- include/pirip_hip.h section J: the multiplexer, the channelizer's mirror image.
+//
+// K channels of modem-rate complex float onto W wideband IQ streams. Channel c = (output chan_output[c], centre offset f_c, gain a_c):
+//     u_c[n] = sum_{q=0}^{Q-1} h[p + qD] z_c[m - q],                n = mD + p, 0 <= p < D      (polyphase interpolation by D)
+//     w_i[n] = sum_{c of output i, ascending} a_c e^{+j w_c n} u_c[n],   w_c = 2 pi f_c / Fs
+// Modulated-filter form, turned round: g_c[i] = a_c h[i] e^{+j w_c i} (host, double, rounded to float) and one rotation per INPUT sample,
+// z'_c[m] = z_c[m] e^{+j w_c m D}, whose phase is the exact integer ((f_c D mod Fs)(m mod Fs)) mod Fs of the absolute input index m. Then
+//     w_i[mD + p] = sum_c sum_q g_c[p + qD] z'_c[m - q]
+// with no transcendental at the wideband rate, no phasor recursion, and a value that is a function of the absolute index alone: any split
+// of a row into calls that overlap by Q - 1 input samples gives the one-shot output bit for bit.
+//
+// Kernel: one workgroup per (tile of kTile = 2048 outputs, output). The channels of the output are taken in groups of at most kMaxGroup
+// (fewer when LDS says so), ascending; per group the workgroup stages the modulated taps and the tile's input span of every channel of the
+// group in LDS, the samples already rotated, and then every thread adds the group to its 8 accumulators: thread t owns the outputs
+// k * 256 + t of the tile, so the lanes of a wave always cover 64 consecutive outputs. (m, p) of a thread's first output is one division
+// per tile; from output to output it moves by (256 div D, 256 mod D) with one carry. Every channel's Q-tap sum is its own chain of fmas
+// in ascending q -- acc = fma((zr, zr), (gr, gi), acc); acc = fma((zi, zi), (-gi, gr), acc) -- added to the output's sum in ascending
+// channel order: the value of an output does not depend on the tile, on the group size or on what other outputs carry.
+// LDS layout: taps [channel][q][Dp] float2, staged samples [channel][Mt] float2. A ds_read_b64 is served in lane groups {0-31}, {32-63}
+// on bank pairs (a / 8) mod 32. The 32 lanes of a group read z' at m = n div D: up to 32 consecutive float2 (distinct bank pairs) or
+// fewer addresses shared by several lanes (broadcast). They read taps at p = n mod D: for D <= 32 at most D consecutive float2, each
+// shared by the lanes of equal p; for D > 32 the row of D taps is followed by its own first 31 (Dp = D + 31), and a lane whose p has
+// wrapped since the group's first lane reads at p + D, so that the group always reads 32 consecutive float2 -- without that, the part
+// before the wrap and the part after it would fall on the same bank pairs whenever D is no multiple of 32.
+// Epilogue: the tile's samples go through LDS once more (quantised for u8) so that every lane stores 16 consecutive bytes and the wave
+// 1024 consecutive bytes; rows that are only aligned to the sample, and a tile's ragged end, are stored sample by sample.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <cstdlib>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/pirip_hip.h"
+#include "fsk_plan.hpp"
+#include "hip_host.hpp"
+
+using namespace pirip;
+
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kPerThread = 8;              // outputs per thread and tile (accumulator pairs)
+constexpr int kTile = kThreads * kPerThread;
+constexpr int kMaxGroup = 8;               // channels staged together
+constexpr int kMaxFs = 1 << 24;            // the rotation's integers are exact in float and in the double product up to this
+constexpr size_t kLdsMax = 64 * 1024;
+
+typedef float dv2f __attribute__((ext_vector_type(2)));
+
+struct MuxArgs {
+    const char *in; size_t in_stride; int64_t n_in, n_out;
+    char *out; size_t out_stride;
+    const dv2f *taps;                      // [nchan][Q][Dp] g_c, each row of D followed by its first Dp - D entries
+    const int32_t *out_start;              // [noutputs + 1]: the channels of output i are out_ch[out_start[i] .. out_start[i + 1])
+    const int32_t *out_ch;                 // [nchan] channel indices, ascending within an output
+    const int32_t *sc;                     // [nchan] (f_c mod Fs) D mod Fs
+    int Fs, D, Dp, Q, Mt, G, aligned16;
+    int step_m, step_p;                    // 256 div D, 256 mod D
+    int32_t m0m;                           // m0 mod Fs
+    float two_over_fs;
+    double inv_fs_d;
+};
+
+// (a b) mod Fs for 0 <= a, b < 2^24: the product is exact in double, the quotient is right or one off, the remainder exact.
+__device__ __forceinline__ int32_t mulmod(int32_t a, int32_t b, int Fs, double inv_fs)
+{
+    const double p = (double)a * (double)b;
+    const double q = floor(p * inv_fs);
+    double r = fma(-q, (double)Fs, p);
+    if (r < 0.0) r += (double)Fs;
+    if (r >= (double)Fs) r -= (double)Fs;
+    return (int32_t)r;
+}
+
+// clamp(rintf(127.5f v + 127.5f), 0, 255): the product and the sum round separately (the build has fp-contract off)
+__device__ __forceinline__ uint32_t quant(float v)
+{
+    const float q = rintf(127.5f * v + 127.5f);
+    return (uint32_t)fminf(fmaxf(q, 0.f), 255.f);
+}
+
+// BS: bytes per output sample, 2 (u8 IQ) or 8 (complex float)
+template <int BS>
+__global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char *s_out = smem;                                                 // [kTile] samples as they are stored
+    dv2f *s_g = (dv2f *)(smem + (size_t)kTile * BS);                    // [G][Q * Dp]
+    const int tapsz = a.Q * a.Dp;
+    dv2f *s_z = s_g + (size_t)a.G * tapsz;                              // [G][Mt]
+    const int tid = threadIdx.x;
+    const int i = blockIdx.y;
+    const int64_t j0 = (int64_t)blockIdx.x * kTile;                     // first output of the tile (of this call)
+    const int cnt = (int)((a.n_out - j0) < kTile ? (a.n_out - j0) : kTile);
+    // output j of the call is absolute n = (m0 + Q - 1) D + j: p = j mod D, and its newest input sample is input Q - 1 + j div D of the call
+    const int64_t a0 = j0 / a.D;
+    const int p0 = (int)(j0 - a0 * a.D);
+    const int mt = (p0 + cnt - 1) / a.D + a.Q;                          // input samples of the tile, from input a0 of the call on
+    const int32_t base = (int32_t)(((int64_t)a.m0m + a0 % a.Fs) % a.Fs);
+    const int m_first = (p0 + tid) / a.D, p_first = (p0 + tid) - m_first * a.D;
+    const int lane32 = tid & 31;
+    dv2f acc[kPerThread];
+#pragma unroll
+    for (int k = 0; k < kPerThread; k++) acc[k] = dv2f{0.f, 0.f};
+
+    const int c0 = a.out_start[i], c1 = a.out_start[i + 1];
+    for (int cb = c0; cb < c1; cb += a.G) {
+        const int ng = c1 - cb < a.G ? c1 - cb : a.G;
+        if (cb > c0) __syncthreads();
+        for (int m = 0; m < ng; m++) {
+            const int ch = a.out_ch[cb + m];
+            const dv2f *g = a.taps + (size_t)ch * tapsz;
+            for (int e = tid; e < tapsz; e += kThreads) s_g[(size_t)m * tapsz + e] = g[e];
+            const float2 *z = (const float2 *)(a.in + (size_t)ch * a.in_stride);
+            const int32_t s = a.sc[ch];
+            for (int r = tid; r < mt; r += kThreads) {
+                float2 v = make_float2(0.f, 0.f);
+                if (a0 + r < a.n_in) v = z[a0 + r];
+                const int32_t idx = (int32_t)(((uint32_t)base + (uint32_t)r) % (uint32_t)a.Fs);
+                int32_t ph = mulmod(s, idx, a.Fs, a.inv_fs_d);
+                if (2 * ph > a.Fs) ph -= a.Fs;                          // the angle as a fraction of pi in (-1, 1]
+                float sn, cs;
+                sincospif((float)ph * a.two_over_fs, &sn, &cs);
+                s_z[(size_t)m * a.Mt + r] = dv2f{__builtin_fmaf(v.x, cs, -(v.y * sn)), __builtin_fmaf(v.x, sn, v.y * cs)};
+            }
+        }
+        __syncthreads();
+        int mm = m_first, pp = p_first;
+#pragma unroll
+        for (int k = 0; k < kPerThread; k++) {
+            if (k * kThreads + tid < cnt) {
+                const int e = (a.Dp != a.D && pp < lane32) ? pp + a.D : pp;
+                for (int m = 0; m < ng; m++) {
+                    const dv2f *g = s_g + (size_t)m * tapsz + e;
+                    const dv2f *z = s_z + (size_t)m * a.Mt + mm + a.Q - 1;
+                    dv2f u = {0.f, 0.f};
+                    for (int q = 0; q < a.Q; q++, g += a.Dp, z--) {
+                        const dv2f gg = *g, zz = *z;
+                        u = __builtin_elementwise_fma(dv2f{zz.x, zz.x}, gg, u);
+                        u = __builtin_elementwise_fma(dv2f{zz.y, zz.y}, dv2f{-gg.y, gg.x}, u);
+                    }
+                    acc[k] += u;
+                }
+            }
+            pp += a.step_p; mm += a.step_m;
+            if (pp >= a.D) { pp -= a.D; mm++; }
+        }
+    }
+
+    // the tile as it is stored, through LDS: thread t holds outputs k * 256 + t, and stores 16 consecutive bytes
+#pragma unroll
+    for (int k = 0; k < kPerThread; k++) {
+        const int n = k * kThreads + tid;
+        if (BS == 2) ((uint16_t *)s_out)[n] = (uint16_t)(quant(acc[k].x) | (quant(acc[k].y) << 8));
+        else ((dv2f *)s_out)[n] = acc[k];
+    }
+    __syncthreads();
+    constexpr int SPU = 16 / BS;                                        // samples per 16-byte unit
+    char *row = a.out + (size_t)i * a.out_stride + (size_t)j0 * BS;
+    for (int u = tid; u * SPU < cnt; u += kThreads) {
+        const int first = u * SPU;
+        if (a.aligned16 && first + SPU <= cnt) {
+            *(uint4 *)(row + (size_t)u * 16) = *(const uint4 *)(s_out + (size_t)u * 16);
+        } else {
+            for (int n = first; n < first + SPU && n < cnt; n++) {
+                if (BS == 2) ((uint16_t *)row)[n] = ((const uint16_t *)s_out)[n];
+                else ((float2 *)row)[n] = ((const float2 *)s_out)[n];
+            }
+        }
+    }
+}
+
+}  // namespace
+
+struct pirip_hip_mux {
+    int Fs = 0, D = 0, kind = 0, L = 0, Q = 0, Dp = 0, Mt = 0, G = 0, out_format = 0, bs = 0, device = 0, noutputs = 0, nchan = 0;
+    size_t lds = 0;
+    std::vector<float> h;                  // prototype taps (L)
+    DevMem mem;
+    dv2f *d_taps = nullptr;
+    int32_t *d_out_start = nullptr, *d_out_ch = nullptr, *d_sc = nullptr;
+};
+
+namespace {
+
+// LDS bytes of a workgroup that stages G channels: the tile as stored, G tap tables, G input spans
+size_t mux_lds(int G, int bs, int Q, int Dp, int Mt) { return (size_t)kTile * bs + (size_t)G * ((size_t)Q * Dp + Mt) * sizeof(dv2f); }
+
+}  // namespace
+
+extern "C" {
+
+int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_bw, int out_format, int noutputs, int nchan,
+                         const int32_t *chan_output, const int32_t *chan_offset_hz, const float *chan_gain, int device, pirip_hip_mux **out)
+{
+    if (!out) return PIRIP_ERR_BAD_ARG;
+    *out = nullptr;
+    if (Fs < 2 || interpolation < 1 || noutputs < 1 || nchan < 1 || !chan_output || !chan_offset_hz) return PIRIP_ERR_BAD_ARG;
+    if (kind != PIRIP_MUX_FIR && kind != PIRIP_MUX_LINEAR) return PIRIP_ERR_BAD_ARG;
+    if (kind == PIRIP_MUX_FIR && !(transition_bw > 0.f)) return PIRIP_ERR_BAD_ARG;
+    if (out_format != PIRIP_IN_CU8_CSDR && out_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
+    for (int c = 0; c < nchan; c++) {
+        if (chan_output[c] < 0 || chan_output[c] >= noutputs) return PIRIP_ERR_BAD_ARG;
+        if (2 * (int64_t)chan_offset_hz[c] <= -(int64_t)Fs || 2 * (int64_t)chan_offset_hz[c] >= (int64_t)Fs) return PIRIP_ERR_BAD_ARG;
+        if (chan_gain && !std::isfinite(chan_gain[c])) return PIRIP_ERR_BAD_ARG;
+    }
+    if (Fs > kMaxFs || noutputs > 65535) return PIRIP_ERR_UNSUPPORTED;
+    const int D = interpolation;
+    const int64_t L64 = kind == PIRIP_MUX_FIR ? (int64_t)csdr_filter_len(transition_bw) : 2 * (int64_t)D - 1;
+    const int64_t Q64 = (L64 + D - 1) / D, Dp64 = D > 32 ? (int64_t)D + 31 : D, Mt64 = ((int64_t)D + kTile - 2) / D + Q64;
+    const int bs = out_format == PIRIP_IN_CF32 ? 8 : 2;
+    // the working set of one channel must fit the LDS of a workgroup (the header's rule)
+    if (L64 < 1 || (Q64 * Dp64 + Mt64) * (int64_t)sizeof(dv2f) + (int64_t)kTile * bs > (int64_t)kLdsMax) return PIRIP_ERR_UNSUPPORTED;
+    int dev = 0;
+    PIRIP_TRY(select_device(device, &dev));
+    pirip_hip_mux *mx = new (std::nothrow) pirip_hip_mux();
+    if (!mx) return PIRIP_ERR_NOMEM;
+    mx->device = dev;
+    mx->Fs = Fs; mx->D = D; mx->kind = kind; mx->out_format = out_format; mx->bs = bs; mx->noutputs = noutputs; mx->nchan = nchan;
+    mx->L = (int)L64; mx->Q = (int)Q64; mx->Dp = (int)Dp64; mx->Mt = (int)Mt64;
+    mx->h.resize((size_t)mx->L);
+    if (kind == PIRIP_MUX_FIR) {
+        // section B's prototype (csdr's Hamming low-pass, cutoff 0.5 / D) times D: unity gain for the interpolated signal
+        csdr_lowpass_hamming(mx->h.data(), mx->L, 0.5 / (float)D);
+        for (float &v : mx->h) v = (float)((double)D * (double)v);
+    } else {
+        for (int i = 0; i < mx->L; i++) mx->h[(size_t)i] = (float)(1.0 - std::fabs((double)(i - (D - 1))) / (double)D);
+    }
+    mx->G = kMaxGroup;
+    while (mx->G > 1 && mux_lds(mx->G, bs, mx->Q, mx->Dp, mx->Mt) > kLdsMax) mx->G--;
+    mx->lds = mux_lds(mx->G, bs, mx->Q, mx->Dp, mx->Mt);
+    // the channels of every output, ascending
+    std::vector<int32_t> out_start(1, 0), out_ch;
+    for (int w = 0; w < noutputs; w++) {
+        for (int c = 0; c < nchan; c++) if (chan_output[c] == w) out_ch.push_back(c);
+        out_start.push_back((int32_t)out_ch.size());
+    }
+    // g_c[i] = a_c h[i] e^{+j 2 pi f_c i / Fs} in double (the phase from the exact integer f_c i mod Fs), rounded to float
+    const size_t tapsz = (size_t)mx->Q * mx->Dp;
+    std::vector<dv2f> taps((size_t)nchan * tapsz, dv2f{0.f, 0.f});
+    std::vector<int32_t> sc((size_t)nchan);
+    for (int c = 0; c < nchan; c++) {
+        const int64_t f = ((int64_t)chan_offset_hz[c] % Fs + Fs) % Fs;
+        sc[(size_t)c] = (int32_t)((f * (D % Fs)) % Fs);
+        const double gain = chan_gain ? (double)chan_gain[c] : 1.0;
+        for (int q = 0; q < mx->Q; q++)
+            for (int e = 0; e < mx->Dp; e++) {
+                const int64_t idx = (int64_t)q * D + e % D;
+                if (idx >= mx->L) continue;
+                const double ph = 2.0 * M_PI * (double)((f * idx) % Fs) / (double)Fs;
+                const double v = gain * (double)mx->h[(size_t)idx];
+                taps[(size_t)c * tapsz + (size_t)q * mx->Dp + e] = dv2f{(float)(v * std::cos(ph)), (float)(v * std::sin(ph))};
+            }
+    }
+    auto tables = [&]() -> int {
+        DevMem &m = mx->mem;
+        PIRIP_TRY(m.upload(&mx->d_taps, taps.data(), sizeof(dv2f) * taps.size()));
+        PIRIP_TRY(m.upload(&mx->d_out_start, out_start.data(), sizeof(int32_t) * out_start.size()));
+        PIRIP_TRY(m.upload(&mx->d_out_ch, out_ch.data(), sizeof(int32_t) * out_ch.size()));
+        PIRIP_TRY(m.upload(&mx->d_sc, sc.data(), sizeof(int32_t) * sc.size()));
+        return PIRIP_OK;
+    };
+    const int rc = tables();
+    if (rc != PIRIP_OK) { delete mx; return rc; }
+    *out = mx;
+    return PIRIP_OK;
+}
+
+int pirip_hip_mux_destroy(pirip_hip_mux *mx)
+{
+    if (!mx) return PIRIP_ERR_BAD_ARG;
+    (void)bind_device(mx->device);
+    (void)hipDeviceSynchronize();
+    delete mx;
+    return PIRIP_OK;
+}
+
+int pirip_hip_mux_get_info(const pirip_hip_mux *mx, pirip_mux_info *info)
+{
+    if (!mx || !info) return PIRIP_ERR_BAD_ARG;
+    *info = pirip_mux_info{mx->Fs, mx->D, mx->kind, mx->L, mx->Q * mx->D, mx->Q, mx->noutputs, mx->nchan, mx->out_format, mx->device};
+    return PIRIP_OK;
+}
+
+int pirip_hip_mux_taps(const pirip_hip_mux *mx, float *taps, int *ntaps)
+{
+    if (!mx || !ntaps) return PIRIP_ERR_BAD_ARG;
+    if (taps) std::memcpy(taps, mx->h.data(), sizeof(float) * (size_t)mx->L);
+    *ntaps = mx->L;
+    return PIRIP_OK;
+}
+
+int64_t pirip_hip_mux_nout(const pirip_hip_mux *mx, int64_t n_in)
+{
+    if (!mx || n_in < mx->Q) return 0;
+    return (n_in - mx->Q + 1) * mx->D;
+}
+
+int pirip_hip_mux_batch(pirip_hip_mux *mx, const void *d_in, size_t in_stride_bytes, int64_t n_in, int64_t m0,
+                        void *d_out, size_t out_stride_bytes, void *hip_stream)
+{
+    if (!mx || !d_in || !d_out || n_in < 0) return PIRIP_ERR_BAD_ARG;
+    if (((uintptr_t)d_in | in_stride_bytes) & 7) return PIRIP_ERR_BAD_ARG;                  // whole complex floats
+    if (((uintptr_t)d_out | out_stride_bytes) & (size_t)(mx->bs - 1)) return PIRIP_ERR_BAD_ARG;
+    if (n_in > ((int64_t)1 << 40) / mx->D) return PIRIP_ERR_UNSUPPORTED;
+    const int64_t n_out = pirip_hip_mux_nout(mx, n_in);
+    if (n_out <= 0) return PIRIP_OK;
+    if (mx->noutputs > 1 && out_stride_bytes < (size_t)n_out * mx->bs) return PIRIP_ERR_BAD_ARG;   // rows would overlap
+    if (!bind_device(mx->device)) return PIRIP_ERR_NO_DEVICE;
+    const int64_t ntiles = (n_out + kTile - 1) / kTile;
+    if (ntiles > 0x7fffffff) return PIRIP_ERR_UNSUPPORTED;
+    MuxArgs a{};
+    a.in = (const char *)d_in; a.in_stride = in_stride_bytes; a.n_in = n_in; a.n_out = n_out;
+    a.out = (char *)d_out; a.out_stride = out_stride_bytes;
+    a.taps = mx->d_taps; a.out_start = mx->d_out_start; a.out_ch = mx->d_out_ch; a.sc = mx->d_sc;
+    a.Fs = mx->Fs; a.D = mx->D; a.Dp = mx->Dp; a.Q = mx->Q; a.Mt = mx->Mt; a.G = mx->G;
+    a.aligned16 = (((uintptr_t)d_out | out_stride_bytes) & 15) == 0;
+    a.step_m = kThreads / mx->D; a.step_p = kThreads % mx->D;
+    a.m0m = (int32_t)(((m0 % mx->Fs) + mx->Fs) % mx->Fs);
+    a.two_over_fs = 2.0f / (float)mx->Fs; a.inv_fs_d = 1.0 / (double)mx->Fs;
+    const dim3 grid((unsigned)ntiles, (unsigned)mx->noutputs);
+    hipStream_t st = (hipStream_t)hip_stream;
+    if (mx->bs == 2) hipLaunchKernelGGL(mux_kernel<2>, grid, dim3(kThreads), mx->lds, st, a);
+    else hipLaunchKernelGGL(mux_kernel<8>, grid, dim3(kThreads), mx->lds, st, a);
+    return hipGetLastError() == hipSuccess ? PIRIP_OK : PIRIP_ERR_HIP;
+}
+
+}  // extern "C"

@@ -1,0 +1,256 @@
+// fsk_ldpc_tx_channels -- the transmit twin of rtl_fsk_channels: K FSK_LDPC transmitters (include/pirip_hip.h section I) and the
+// multiplexer (section J) behind them, on the GPU. Each channel's records become complex float IQ at the modem rate; all channels are
+// then interpolated by wideFs / modemFs, moved to their centre offsets, scaled, summed and written as ONE wideband IQ file -- for one
+// channel, what the reference bench chain does with `... | tlininterp - t.iq8 D -d -f` (/root/reference/README.md:142).
+//
+//   fsk_ldpc_tx_channels --code NAME|FILE -s wideFs -a modemFs -r Rs [-m M] --f1 Hz --shift Hz -c off1,off2,...
+//                        [--gain g | --gains g1,g2,...] [--linear] [--format u8|cf32] [--packed] [--gap BITS] [--lead BITS]
+//                        -i PREFIX -o OUT|-
+//       channel k's records are read from PREFIX.<k>: one burst-control byte + data_bits_per_frame bits (one per byte) or, with
+//       --packed, /8 bytes, as fsk_ldpc_tx reads them; --gap / --lead: carrier off for every `2` record / in front, as there.
+//   fsk_ldpc_tx_channels ... --testframes N [--bursts B] [--seq] [--source BYTE | --source b1,b2,...] -o OUT|-
+//       fsk_ldpc_tx's test frames, the same on every channel but for the source byte (one for all channels, or one per channel).
+// A modem sample has modulus 2 (section I), so --gain g puts a channel at 255 g u8 steps of amplitude; the default is 0.1 / K.
+// The whole input is processed in one piece: every channel's row is as long as the longest (carrier off behind a shorter one), with
+// Q - 1 zeros in front, and the multiplexer runs at m0 = -(Q - 1), so that wideband sample 0 corresponds to modem sample 0.
+// Exit codes: 1 arguments / files, 2 the code file (as fsk_ldpc_tx), 3 no usable HIP device or a device error (nothing is written).
+#include <getopt.h>
+#include <hip/hip_runtime_api.h>
+#include <sys/stat.h>
+#include <unistd.h>
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "../../include/pirip_hip.h"
+#include "fsk_ldpc.hpp"
+
+using namespace pirip;
+
+static int usage(const char *a0)
+{
+    fprintf(stderr, "usage: %s --code NAME|FILE -s wideFs -a modemFs -r Rs [-m 2|4] --f1 Hz --shift Hz -c off1,off2,...\n"
+                    "          [--gain g | --gains g1,g2,...] [--linear] [--format u8|cf32] [--packed] [--gap BITS] [--lead BITS]\n"
+                    "          [--testframes N [--bursts B] [--seq] [--source BYTE|b1,b2,...]] -i PREFIX -o out|-\n", a0);
+    return 1;
+}
+
+static bool file_exists(const std::string &p) { struct stat st; return !p.empty() && stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
+
+// --code NAME: NAME as a file path, then $PIRIP_CODE_DIR/NAME.code, then <exe>/../data/NAME.code (as rtl_fsk_channels resolves it)
+static std::string resolve_code(const std::string &name, const char *argv0)
+{
+    if (file_exists(name)) return name;
+    if (const char *d = getenv("PIRIP_CODE_DIR")) { const std::string p = std::string(d) + "/" + name + ".code"; if (file_exists(p)) return p; }
+    char exe[4096];
+    const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1);
+    std::string base = n > 0 ? std::string(exe, (size_t)n) : std::string(argv0);
+    const size_t s = base.rfind('/');
+    base = s == std::string::npos ? "." : base.substr(0, s);
+    const std::string p = base + "/../data/" + name + ".code";
+    return file_exists(p) ? p : std::string();
+}
+
+template <typename T, typename F>
+static bool parse_list(const char *s, std::vector<T> &out, F conv)
+{
+    const std::string all(s);
+    for (size_t pos = 0; pos <= all.size();) {
+        size_t end = all.find(',', pos);
+        if (end == std::string::npos) end = all.size();
+        const std::string tok = all.substr(pos, end - pos);
+        if (tok.empty()) return false;
+        char *e = nullptr;
+        const T v = conv(tok.c_str(), &e);
+        if (*e) return false;
+        out.push_back(v);
+        pos = end + 1;
+    }
+    return !out.empty();
+}
+
+int main(int argc, char **argv)
+{
+    std::string code, format = "u8", prefix, out_name;
+    long wideFs = 0, modemFs = 0, Rs = 0;
+    int M = 2, packed = 0, testframes = 0, bursts = 1, seq = 0, linear = 0, f1 = 0, shift = 0, have_f1 = 0, gap = 0, lead_bits = 0;
+    std::vector<int32_t> offsets;
+    std::vector<float> gains;
+    std::vector<long> sources;
+    static struct option lopts[] = {{"code", required_argument, 0, 1000}, {"packed", no_argument, 0, 1001},
+                                    {"testframes", required_argument, 0, 1002}, {"bursts", required_argument, 0, 1003},
+                                    {"source", required_argument, 0, 1004}, {"seq", no_argument, 0, 1005},
+                                    {"f1", required_argument, 0, 1006}, {"shift", required_argument, 0, 1007},
+                                    {"format", required_argument, 0, 1008}, {"gain", required_argument, 0, 1009},
+                                    {"gains", required_argument, 0, 1009}, {"linear", no_argument, 0, 1010},
+                                    {"gap", required_argument, 0, 1011}, {"lead", required_argument, 0, 1012}, {0, 0, 0, 0}};
+    auto to_long = [](const char *t, char **e) { return strtol(t, e, 0); };
+    int o, oi;
+    while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:h", lopts, &oi)) != -1) {
+        switch (o) {
+        case 's': wideFs = (long)atof(optarg); break;
+        case 'a': modemFs = (long)atof(optarg); break;
+        case 'r': Rs = (long)atof(optarg); break;
+        case 'm': M = atoi(optarg); break;
+        case 'c':
+            if (!parse_list(optarg, offsets, [](const char *t, char **e) { return (int32_t)strtol(t, e, 10); })) {
+                fprintf(stderr, "fsk_ldpc_tx_channels: -c wants integer offsets in Hz, comma separated\n"); return 1;
+            }
+            break;
+        case 'i': prefix = optarg; break;
+        case 'o': out_name = optarg; break;
+        case 1000: code = optarg; break;
+        case 1001: packed = 1; break;
+        case 1002: testframes = atoi(optarg); break;
+        case 1003: bursts = atoi(optarg); break;
+        case 1004: if (!parse_list(optarg, sources, to_long)) { fprintf(stderr, "fsk_ldpc_tx_channels: --source BYTE or b1,b2,...\n"); return 1; } break;
+        case 1005: seq = 1; break;
+        case 1006: f1 = atoi(optarg); have_f1 = 1; break;
+        case 1007: shift = atoi(optarg); break;
+        case 1008: format = optarg; break;
+        case 1009: if (!parse_list(optarg, gains, [](const char *t, char **e) { return strtof(t, e); })) { fprintf(stderr, "fsk_ldpc_tx_channels: --gain g or --gains g1,g2,...\n"); return 1; } break;
+        case 1010: linear = 1; break;
+        case 1011: gap = atoi(optarg); break;
+        case 1012: lead_bits = atoi(optarg); break;
+        default: return usage(argv[0]);
+        }
+    }
+    const int K = (int)offsets.size();
+    if (code.empty() || wideFs <= 0 || modemFs <= 0 || Rs <= 0 || K == 0 || out_name.empty() || !have_f1 || (M != 2 && M != 4)) return usage(argv[0]);
+    if (testframes <= 0 && prefix.empty()) return usage(argv[0]);
+    if (wideFs % modemFs) { fprintf(stderr, "fsk_ldpc_tx_channels: the wideband rate %ld must be a multiple of the modem rate %ld\n", wideFs, modemFs); return 1; }
+    if (modemFs % Rs || shift <= 0) { fprintf(stderr, "fsk_ldpc_tx_channels: need modemFs %% Rs == 0 and --shift > 0\n"); return 1; }
+    if (format != "u8" && format != "cf32") { fprintf(stderr, "fsk_ldpc_tx_channels: --format u8|cf32\n"); return 1; }
+    const int bps = M == 2 ? 1 : 2;
+    if (bursts < 1 || testframes < 0 || gap < 0 || lead_bits < 0 || gap % bps || lead_bits % bps) {
+        fprintf(stderr, "fsk_ldpc_tx_channels: --gap / --lead are whole symbols, --bursts >= 1, --testframes >= 0\n"); return 1;
+    }
+    if (gains.empty()) gains.assign(1, 0.1f / (float)K);
+    if (gains.size() == 1) gains.assign((size_t)K, gains[0]);
+    if ((int)gains.size() != K) { fprintf(stderr, "fsk_ldpc_tx_channels: one gain, or one per channel\n"); return 1; }
+    if (sources.size() == 1) sources.assign((size_t)K, sources[0]);
+    if (!sources.empty() && (int)sources.size() != K) { fprintf(stderr, "fsk_ldpc_tx_channels: one --source byte, or one per channel\n"); return 1; }
+    const std::string code_path = resolve_code(code, argv[0]);
+    if (code_path.empty()) {
+        fprintf(stderr, "fsk_ldpc_tx_channels: no table for --code %s (format: pirip_amd/csrc/fsk_ldpc.hpp; $PIRIP_CODE_DIR or a file path)\n", code.c_str());
+        return 2;
+    }
+    LdpcCode ldpc;
+    const std::string err = ldpc.load(code_path);
+    if (!err.empty()) { fprintf(stderr, "fsk_ldpc_tx_channels: %s: %s\n", code_path.c_str(), err.c_str()); return 2; }
+    if (!ldpc.accumulator) { fprintf(stderr, "fsk_ldpc_tx_channels: %s has no dual-diagonal parity part: no linear-time encoder\n", ldpc.name.c_str()); return 2; }
+
+    // every channel's record stream, packed; rows of max_rec records
+    const int k = ldpc.k, kb = k / 8, rl = 1 + kb;
+    std::vector<std::vector<uint8_t>> recs((size_t)K);
+    std::vector<uint8_t> data((size_t)k), bytes((size_t)kb);
+    for (int c = 0; c < K; c++) {
+        std::vector<uint8_t> &r = recs[(size_t)c];
+        auto push = [&](uint8_t ctl) { r.push_back(ctl); r.insert(r.end(), bytes.begin(), bytes.end()); };
+        if (testframes > 0) {
+            testframe_payload(data.data(), k);
+            const long source = sources.empty() ? -1 : sources[(size_t)c];
+            for (int b = 0; b < bursts; b++) {
+                for (int f = 0; f < testframes; f++) {
+                    if (source >= 0) for (int i = 0; i < 8; i++) data[(size_t)i] = (source >> (7 - i)) & 1;
+                    if (seq) { const int s = (f + 1) & 0xff; for (int i = 0; i < 8; i++) data[(size_t)(8 + i)] = (s >> (7 - i)) & 1; }
+                    pack_bits_msb(bytes.data(), data.data(), k);
+                    push(f == 0 ? 1 : 0);
+                }
+                std::fill(bytes.begin(), bytes.end(), 0);
+                push(2);
+            }
+        } else {
+            const std::string name = prefix + "." + std::to_string(c);
+            FILE *fin = fopen(name.c_str(), "rb");
+            if (!fin) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open %s\n", name.c_str()); return 1; }
+            for (;;) {
+                uint8_t ctl;
+                if (fread(&ctl, 1, 1, fin) != 1) break;
+                size_t nread;
+                if (packed) nread = fread(bytes.data(), 1, bytes.size(), fin) * 8;
+                else { nread = fread(data.data(), 1, (size_t)k, fin); pack_bits_msb(bytes.data(), data.data(), k); }
+                if ((int)nread != k) break;
+                push(ctl);
+            }
+            fclose(fin);
+        }
+    }
+    int max_rec = 0;
+    for (const auto &r : recs) if ((int)(r.size() / (size_t)rl) > max_rec) max_rec = (int)(r.size() / (size_t)rl);
+    const size_t rec_stride = (size_t)max_rec * (size_t)rl + 1;
+    std::vector<uint8_t> rec_rows((size_t)K * rec_stride, 0);
+    std::vector<int32_t> nrec((size_t)K);
+    for (int c = 0; c < K; c++) {
+        nrec[(size_t)c] = (int32_t)(recs[(size_t)c].size() / (size_t)rl);
+        if (!recs[(size_t)c].empty()) memcpy(&rec_rows[(size_t)c * rec_stride], recs[(size_t)c].data(), recs[(size_t)c].size());
+    }
+
+    const int D = (int)(wideFs / modemFs), Ts = (int)(modemFs / Rs);
+    pirip_hip_tx *tx = nullptr;
+    pirip_hip_mux *mux = nullptr;
+    int rc = pirip_hip_tx_create(code_path.c_str(), (int)modemFs, (int)Rs, M, K, -1, &tx);
+    if (rc != PIRIP_OK) { fprintf(stderr, "fsk_ldpc_tx_channels: pirip_hip_tx_create: %s\n", pirip_hip_strerror(rc)); return rc == PIRIP_ERR_BAD_CONFIG || rc == PIRIP_ERR_UNSUPPORTED ? 2 : 3; }
+    auto fail = [&](const char *what, int status) {
+        fprintf(stderr, "fsk_ldpc_tx_channels: %s: %s\n", what, pirip_hip_strerror(status));
+        if (mux) pirip_hip_mux_destroy(mux);
+        pirip_hip_tx_destroy(tx);
+        return status == PIRIP_ERR_BAD_ARG ? 1 : 3;
+    };
+    const int out_format = format == "u8" ? PIRIP_IN_CU8_CSDR : PIRIP_IN_CF32, bsamp = format == "u8" ? 2 : 8;
+    std::vector<int32_t> outputs((size_t)K, 0), f1s((size_t)K, f1);
+    rc = pirip_hip_mux_create((int)wideFs, D, linear ? PIRIP_MUX_LINEAR : PIRIP_MUX_FIR, 0.05f, out_format, 1, K, outputs.data(), offsets.data(),
+                              gains.data(), -1, &mux);
+    if (rc != PIRIP_OK) return fail("pirip_hip_mux_create", rc);
+    pirip_mux_info mi;
+    pirip_hip_mux_get_info(mux, &mi);
+    if ((rc = pirip_hip_tx_set_tones(tx, f1s.data(), shift)) != PIRIP_OK) return fail("pirip_hip_tx_set_tones", rc);
+    const std::vector<int32_t> leads((size_t)K, lead_bits / bps), gaps((size_t)K, gap / bps);
+    if ((rc = pirip_hip_tx_set_gaps(tx, leads.data(), gaps.data())) != PIRIP_OK) return fail("pirip_hip_tx_set_gaps", rc);
+
+    uint8_t *d_rec = nullptr; int32_t *d_nrec = nullptr, *d_nsym = nullptr; char *d_mod = nullptr; void *d_out = nullptr;
+    if (hipMalloc((void **)&d_rec, rec_rows.size()) != hipSuccess || hipMalloc((void **)&d_nrec, sizeof(int32_t) * (size_t)K) != hipSuccess ||
+        hipMalloc((void **)&d_nsym, sizeof(int32_t) * (size_t)K) != hipSuccess) return fail("hipMalloc", PIRIP_ERR_NOMEM);
+    if (hipMemcpy(d_rec, rec_rows.data(), rec_rows.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(d_nrec, nrec.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy", PIRIP_ERR_HIP);
+    // the symbols each channel's records make: the longest one sets the length of every row
+    int64_t nsym = 0;
+    for (int c = 0; c < K; c++) {
+        int64_t n = lead_bits / bps;
+        const std::vector<uint8_t> &r = recs[(size_t)c];
+        pirip_tx_info ti;
+        pirip_hip_tx_get_info(tx, &ti);
+        for (int i = 0; i < nrec[(size_t)c]; i++) {
+            const uint8_t ctl = r[(size_t)i * (size_t)rl];
+            n += ctl == 1 ? ti.preamble_syms + ti.frame_syms : ctl == 0 ? ti.frame_syms : ctl == 2 ? gap / bps : 0;
+        }
+        if (n > nsym) nsym = n;
+    }
+    const int64_t nmod = nsym * Ts, lead = mi.Q - 1, n_in = nmod + lead;
+    const int64_t n_out = pirip_hip_mux_nout(mux, n_in);
+    const size_t mod_stride = (size_t)n_in * 8, out_bytes = (size_t)n_out * (size_t)bsamp;
+    std::vector<uint8_t> out(out_bytes);
+    if (nsym > 0) {
+        if (hipMalloc((void **)&d_mod, (size_t)K * mod_stride) != hipSuccess || hipMalloc(&d_out, out_bytes) != hipSuccess) return fail("hipMalloc", PIRIP_ERR_NOMEM);
+        if (hipMemset(d_mod, 0, (size_t)K * mod_stride) != hipSuccess) return fail("hipMemset", PIRIP_ERR_HIP);
+        rc = pirip_hip_tx_records_to_iq(tx, d_rec, rec_stride, d_nrec, max_rec, nsym, PIRIP_IN_CF32, d_mod + (size_t)lead * 8, mod_stride, 0.f, 0.f, 0,
+                                        d_nsym, nullptr);
+        if (rc != PIRIP_OK) return fail("pirip_hip_tx_records_to_iq", rc);
+        rc = pirip_hip_mux_batch(mux, d_mod, mod_stride, n_in, -lead, d_out, out_bytes, nullptr);
+        if (rc != PIRIP_OK) return fail("pirip_hip_mux_batch", rc);
+        if (hipMemcpy(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail("hipMemcpy", PIRIP_ERR_HIP);
+    }
+    (void)hipFree(d_rec); (void)hipFree(d_nrec); (void)hipFree(d_nsym); if (d_mod) (void)hipFree(d_mod); if (d_out) (void)hipFree(d_out);
+    pirip_hip_mux_destroy(mux);
+    pirip_hip_tx_destroy(tx);
+    FILE *fout = out_name == "-" ? stdout : fopen(out_name.c_str(), "wb");
+    if (!fout) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open the output\n"); return 1; }
+    if (fwrite(out.data(), 1, out.size(), fout) != out.size()) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return 1; }
+    if (fout != stdout) fclose(fout);
+    fprintf(stderr, "fsk_ldpc_tx_channels: code %s M %d channels %d interpolation %d taps %d: %lld symbols, %lld wideband samples\n", ldpc.name.c_str(), M, K, D,
+            mi.ntaps, (long long)nsym, (long long)n_out);
+    return 0;
+}
