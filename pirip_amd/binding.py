@@ -342,6 +342,16 @@ class HipDemod:
         return out
 
 
+def _taps(fn, h):
+    """the *_taps protocol: ask for the length, allocate, ask again"""
+    import numpy as np
+    n = C.c_int(0)
+    fn(h, None, C.byref(n))
+    t = np.zeros(n.value, dtype=np.float32)
+    fn(h, t.ctypes.data, C.byref(n))
+    return t
+
+
 class HipDecim:
     """csdr convert_u8_f | fir_decimate_cc D | [convert_f_s16] as one device stage."""
 
@@ -360,12 +370,7 @@ class HipDecim:
     __del__ = close
 
     def taps(self):
-        import numpy as np
-        n = C.c_int(0)
-        self.L.pirip_hip_decim_taps(self.h, None, C.byref(n))
-        t = np.zeros(n.value, dtype=np.float32)
-        self.L.pirip_hip_decim_taps(self.h, t.ctypes.data, C.byref(n))
-        return t
+        return _taps(self.L.pirip_hip_decim_taps, self.h)
 
     def nout(self, n_in):
         return int(self.L.pirip_hip_decim_nout(self.h, n_in))
@@ -413,12 +418,7 @@ class HipChan:
 
     def taps(self):
         """the prototype low-pass h (section B's taps for the same D / transition_bw, unpadded)"""
-        import numpy as np
-        n = C.c_int(0)
-        self.L.pirip_hip_chan_taps(self.h, None, C.byref(n))
-        t = np.zeros(n.value, dtype=np.float32)
-        self.L.pirip_hip_chan_taps(self.h, t.ctypes.data, C.byref(n))
-        return t
+        return _taps(self.L.pirip_hip_chan_taps, self.h)
 
     def nout(self, n_in):
         return int(self.L.pirip_hip_chan_nout(self.h, int(n_in)))
@@ -553,12 +553,7 @@ class HipMux:
 
     def taps(self):
         """the prototype h (ntaps, unpadded)"""
-        import numpy as np
-        n = C.c_int(0)
-        self.L.pirip_hip_mux_taps(self.h, None, C.byref(n))
-        t = np.zeros(n.value, dtype=np.float32)
-        self.L.pirip_hip_mux_taps(self.h, t.ctypes.data, C.byref(n))
-        return t
+        return _taps(self.L.pirip_hip_mux_taps, self.h)
 
     def nout(self, n_in):
         return int(self.L.pirip_hip_mux_nout(self.h, int(n_in)))

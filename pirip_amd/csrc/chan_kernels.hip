@@ -3,9 +3,8 @@
 // K channels out of W wideband u8 IQ captures in one pass over the input. Channel c = (capture chan_input[c], centre offset f_c):
 //     y_c[j] = sum_{i=0}^{Lp-1} h[i] x[jD+i] e^{-j w_c (t0 + jD + i)},   w_c = 2 pi f_c / Fs,  x = convert_u8_f(byte) = b / 127.5 - 1
 // which is csdr's shift_addition_cc (-f_c/Fs) | fir_decimate_cc D with section B's taps h (Hamming, cutoff 0.5/D, padded to Lp).
-// Modulated-filter form: g_c[i] = h[i] e^{-j w_c i} (host, double, rounded to float) and one rotation r_c[j] = e^{-j w_c (t0 + jD)} per
-// output, whose phase is the exact integer p = (f_c mod Fs)(t0 + jD) mod Fs. The rotation is then a function of the absolute sample index
-// alone: no phasor recursion, no drift, and any split of a capture into calls gives the one-shot output bit for bit.
+// Modulated-filter form: g_c[i] = h[i] e^{-j w_c i} (rate_host.hpp's modulated_tap) and one rotation r_c[j] = e^{-j w_c (t0 + jD)} per
+// output, from the exact integer phase p = (f_c mod Fs)(t0 + jD) mod Fs (iq_device.hpp: exact phase).
 //
 // Kernel: one workgroup per (output tile, capture). It stages the tile's u8 span once (16-byte loads, converted to float in LDS; tiles
 // overlap by Lp - D samples) and then computes every channel of that capture from LDS, so the capture is read from HBM once whatever K is.
@@ -18,10 +17,7 @@
 // (MI355X: banks (a/4) mod 64, lane groups {0-31}, {32-63}); with P = D an even D would be 2-way conflicted.
 #include <hip/hip_runtime.h>
 
-#include <climits>
-#include <cmath>
 #include <cstdint>
-#include <cstdlib>
 #include <cstring>
 #include <new>
 #include <vector>
@@ -29,6 +25,8 @@
 #include "../../include/pirip_hip.h"
 #include "fsk_plan.hpp"
 #include "hip_host.hpp"
+#include "iq_device.hpp"
+#include "rate_host.hpp"
 
 using namespace pirip;
 
@@ -36,14 +34,11 @@ namespace {
 
 constexpr int kThreads = 256;
 constexpr int kMaxGroup = 8;               // channels per lane (accumulator pairs)
-constexpr int kMaxFs = 1 << 24;            // the rotation's index arithmetic is exact in 32 bits up to this (see rotation())
 constexpr size_t kLdsTarget = 40 * 1024;   // staged window per workgroup: four workgroups per CU
 constexpr size_t kLdsMax = 64 * 1024;
 
-typedef float dv2f __attribute__((ext_vector_type(2)));
-typedef float dv4f __attribute__((ext_vector_type(4)));
 // the taps are read through the constant address space: wave-uniform addresses there become scalar loads into SGPRs
-typedef const __attribute__((address_space(4))) dv4f cdv4f;
+typedef const __attribute__((address_space(4))) v4f cv4f;
 
 struct ChanGroup {
     int32_t n;                             // channels in the group (1..kMaxGroup)
@@ -53,98 +48,80 @@ struct ChanGroup {
 struct ChanArgs {
     const uint8_t *in; size_t in_stride; int64_t n_in, n_out;
     void *out; size_t out_stride;
-    const dv4f *taps;                      // [group][Lp][kMaxGroup] (gr, gi, -gi, gr) of g_c[i], zero for the unused slots
+    const v4f *taps;                       // [group][Lp][kMaxGroup] (gr, gi, -gi, gr) of g_c[i], zero for the unused slots
     const ChanGroup *groups;
     const int32_t *in_groups;              // [ninputs + 1]: groups of capture w are [in_groups[w], in_groups[w + 1])
     const int32_t *fcm, *sc;               // [nchan]: f_c mod Fs, (f_c mod Fs) D mod Fs
     int Fs, D, Lp, P, T, Tpad, out_s16;
     int32_t t0m;                           // t0 mod Fs
     int32_t dm;                            // D mod Fs
-    float c_hi, c_lo;                      // convert_u8_f as two fmas (decim_kernels.hip)
+    float c_hi, c_lo;                      // u8_to_float's constants
     float inv_fs, m2_over_fs;              // 1 / Fs, -2 / Fs
     double inv_fs_d;
 };
 
-// (a b) mod Fs for 0 <= a, b < 2^24: the product is exact in double, the quotient is right or one off, the remainder exact.
-__device__ __forceinline__ int32_t mulmod(int64_t a, int64_t b, int Fs, double inv_fs)
-{
-    const double p = (double)a * (double)b;
-    const double q = floor(p * inv_fs);
-    double r = fma(-q, (double)Fs, p);
-    if (r < 0.0) r += (double)Fs;
-    if (r >= (double)Fs) r -= (double)Fs;
-    return (int32_t)r;
-}
-
 // e^{-j w_c n} for n = n0 + k D, as p = (B + k S) mod Fs with B = f_c n0 mod Fs and S = f_c D mod Fs: v = B + k S < 256 Fs <= 2^32 (k < 256,
 // Fs <= 2^24; k and S each fit the 24-bit multiply). The float quotient q <= 256 is right or one off; q Fs is a full 32-bit multiply
 // (Fs = 2^24 itself does not fit the 24-bit one) that stays below 2^32, so the remainder is exact, within one Fs of [0, Fs), and 2 r
-// stays below 2^26. The angle goes to sincospi as a fraction of pi in [-1, 1), from |r| <= 2^23 exact in float: p is the same integer
-// however a capture is split, so is the rotation.
-__device__ __forceinline__ dv2f rotation(uint32_t B, uint32_t S, uint32_t k, const ChanArgs &a)
+// stays below 2^26. Fs <= kMaxFs is what all of this rests on. p is the same integer however a capture is split, so is the rotation.
+__device__ __forceinline__ v2f rotation(uint32_t B, uint32_t S, uint32_t k, const ChanArgs &a)
 {
     const uint32_t v = B + __umul24(k, S);
     const uint32_t q = (uint32_t)((float)v * a.inv_fs);
     int32_t r = (int32_t)(v - q * (uint32_t)a.Fs);
     if (r < 0) r += a.Fs;
     if (r >= a.Fs) r -= a.Fs;
-    if (2 * r > a.Fs) r -= a.Fs;
     float s, c;
-    sincospif((float)r * a.m2_over_fs, &s, &c);
-    return dv2f{c, s};
+    unit_phasor(r, a.Fs, a.m2_over_fs, c, s);
+    return v2f{c, s};
 }
 
-__device__ __forceinline__ void store(const ChanArgs &a, int ch, int64_t j, dv2f y)
+__device__ __forceinline__ void store(const ChanArgs &a, int ch, int64_t j, v2f y)
 {
     char *row = (char *)a.out + (size_t)ch * a.out_stride;
-    if (a.out_s16) {
-        const float vr = fminf(fmaxf(y.x * (float)SHRT_MAX, -32768.0f), 32767.0f);
-        const float vi = fminf(fmaxf(y.y * (float)SHRT_MAX, -32768.0f), 32767.0f);
-        ((short2 *)row)[j] = make_short2((short)vr, (short)vi);
-    } else {
-        ((float2 *)row)[j] = make_float2(y.x, y.y);
-    }
+    if (a.out_s16) ((short2 *)row)[j] = make_short2(f_to_s16_clamped(y.x), f_to_s16_clamped(y.y));
+    else ((float2 *)row)[j] = make_float2(y.x, y.y);
 }
 
 // One lane, one output (k of the tile), the CG channels of group gi: the tap loop from LDS, then the rotation and the store.
 template <int CG>
-__device__ __forceinline__ void run_group(const ChanArgs &a, const dv2f *s_x, int gi, int k, int nouts, int64_t j0, int32_t n0)
+__device__ __forceinline__ void run_group(const ChanArgs &a, const v2f *s_x, int gi, int k, int nouts, int64_t j0, int32_t n0)
 {
     if (k >= nouts) return;                                             // (a partial tile's idle lanes: nothing to read or write)
     const ChanGroup &g = a.groups[gi];
-    cdv4f *taps = (cdv4f *)(a.taps + (size_t)gi * a.Lp * kMaxGroup);
-    dv2f acc[CG];
+    cv4f *taps = (cv4f *)(a.taps + (size_t)gi * a.Lp * kMaxGroup);
+    v2f acc[CG];
 #pragma unroll
-    for (int m = 0; m < CG; m++) acc[m] = dv2f{0.f, 0.f};
-    const dv2f *xrow = s_x + (size_t)k * a.P;
+    for (int m = 0; m < CG; m++) acc[m] = v2f{0.f, 0.f};
+    const v2f *xrow = s_x + (size_t)k * a.P;
     for (int i = 0; i < a.Lp; xrow += a.P) {
         const int ue = a.D < a.Lp - i ? a.D : a.Lp - i;
 #pragma unroll 2
         for (int u = 0; u < ue; u++, i++) {
-            const dv2f x = xrow[u];
-            cdv4f *t = taps + (size_t)i * kMaxGroup;
+            const v2f x = xrow[u];
+            cv4f *t = taps + (size_t)i * kMaxGroup;
 #pragma unroll
             for (int m = 0; m < CG; m++) {
-                const dv4f h = t[m];
-                acc[m] = __builtin_elementwise_fma(dv2f{x.x, x.x}, dv2f{h.x, h.y}, acc[m]);
-                acc[m] = __builtin_elementwise_fma(dv2f{x.y, x.y}, dv2f{h.z, h.w}, acc[m]);
+                const v4f h = t[m];
+                acc[m] = __builtin_elementwise_fma(v2f{x.x, x.x}, v2f{h.x, h.y}, acc[m]);
+                acc[m] = __builtin_elementwise_fma(v2f{x.y, x.y}, v2f{h.z, h.w}, acc[m]);
             }
         }
     }
 #pragma unroll
     for (int m = 0; m < CG; m++) {
         const int ch = g.ch[m];
-        const uint32_t B = (uint32_t)mulmod(a.fcm[ch], n0, a.Fs, a.inv_fs_d);
-        const dv2f rot = rotation(B, (uint32_t)a.sc[ch], (uint32_t)k, a);
-        const dv2f y = {__builtin_fmaf(acc[m].x, rot.x, -(acc[m].y * rot.y)), __builtin_fmaf(acc[m].x, rot.y, acc[m].y * rot.x)};
-        store(a, ch, j0 + k, y);
+        // (the int operands convert to double exactly; the residue comes back through int32_t, one v_cvt_i32_f64, before it is reread as unsigned)
+        const uint32_t B = (uint32_t)(int32_t)mulmod_fs(a.fcm[ch], n0, a.Fs, a.inv_fs_d);
+        const v2f rot = rotation(B, (uint32_t)a.sc[ch], (uint32_t)k, a);
+        store(a, ch, j0 + k, crot(acc[m], rot.x, rot.y));
     }
 }
 
 // Stage the u8 span of outputs [j0, j0 + nouts) of one capture as float2 in the row layout: bounds-checked 16-byte loads through a buffer
 // descriptor (all in flight together), each chunk converted as its 8 samples. The capture's address and stride are even (create / batch
 // check), so a chunk holds whole samples. Bytes past the capture are never used by a valid output.
-__device__ __forceinline__ void stage(const ChanArgs &a, const uint8_t *src, int64_t j0, int nouts, dv2f *s_x, int tid)
+__device__ __forceinline__ void stage(const ChanArgs &a, const uint8_t *src, int64_t j0, int nouts, v2f *s_x, int tid)
 {
     const int64_t b0 = 2 * j0 * a.D;
     const int nwin = (nouts - 1) * a.D + a.Lp;                         // samples
@@ -153,7 +130,7 @@ __device__ __forceinline__ void stage(const ChanArgs &a, const uint8_t *src, int
     const int64_t gbase = b0 - head;
     const int wlen = (head + 2 * nwin + 15) & ~15;
     const int64_t total = 2 * a.n_in;
-    const dv2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo}, m1 = {-1.0f, -1.0f};
+    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
     auto convert = [&](uint4 w, int o) {
         const uint32_t dw[4] = {w.x, w.y, w.z, w.w};
         int s = (o - head) / 2;                                         // sample of the chunk's first byte pair (head is even)
@@ -162,8 +139,8 @@ __device__ __forceinline__ void stage(const ChanArgs &a, const uint8_t *src, int
         for (int q = 0; q < 8; q++, s++) {
             if (s >= 0 && s < nwin) {
                 const uint32_t pr = dw[q >> 1] >> (16 * (q & 1));
-                const dv2f x = {(float)(pr & 0xffu), (float)((pr >> 8) & 0xffu)};
-                s_x[(size_t)r * a.P + u] = __builtin_elementwise_fma(x, clo, __builtin_elementwise_fma(x, chi, m1));
+                const v2f x = {(float)(pr & 0xffu), (float)((pr >> 8) & 0xffu)};
+                s_x[(size_t)r * a.P + u] = u8_to_float(x, chi, clo);
             }
             if (s >= 0 && ++u == a.D) { u = 0; r++; }
         }
@@ -188,7 +165,7 @@ __device__ __forceinline__ void stage(const ChanArgs &a, const uint8_t *src, int
 __global__ __launch_bounds__(kThreads) void chan_kernel(ChanArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    dv2f *s_x = (dv2f *)smem;
+    v2f *s_x = (v2f *)smem;
     const int tid = threadIdx.x;
     const int w = blockIdx.y;
     const int g0 = a.in_groups[w], ng = a.in_groups[w + 1] - g0;
@@ -197,12 +174,9 @@ __global__ __launch_bounds__(kThreads) void chan_kernel(ChanArgs a)
     const int nouts = (int)((a.n_out - j0) < a.T ? (a.n_out - j0) : a.T);
     stage(a, a.in + (size_t)w * a.in_stride, j0, nouts, s_x, tid);
     __syncthreads();
-    // (t0 + j0 D) mod Fs, from j0 mod Fs: j0 < 2^53, so the double quotient is right or one off and the remainder exact
-    double jq = floor((double)j0 * a.inv_fs_d);
-    double jr = fma(-jq, (double)a.Fs, (double)j0);
-    if (jr < 0.0) jr += (double)a.Fs;
-    if (jr >= (double)a.Fs) jr -= (double)a.Fs;
-    int32_t n0 = a.t0m + mulmod((int64_t)jr, a.dm, a.Fs, a.inv_fs_d);
+    // (t0 + j0 D) mod Fs, from j0 mod Fs (j0 < 2^53)
+    const int64_t jr = (int64_t)mod_fs((double)j0, a.Fs, a.inv_fs_d);
+    int32_t n0 = a.t0m + (int32_t)mulmod_fs(jr, a.dm, a.Fs, a.inv_fs_d);
     if (n0 >= a.Fs) n0 -= a.Fs;
     for (int it = tid; it < ng * a.Tpad; it += kThreads) {
         const int gi = g0 + __builtin_amdgcn_readfirstlane(it / a.Tpad);   // (Tpad is a multiple of 64: one group per wave)
@@ -226,11 +200,11 @@ struct pirip_hip_chan {
     int Fs = 0, D = 0, L = 0, Lp = 0, out_s16 = 0, device = 0, ninputs = 0, nchan = 0;
     int P = 0, T = 0, Tpad = 0;
     size_t lds = 0;
-    float c_hi = 0.f, c_lo = 0.f;
+    U8Split u8{};
     std::vector<float> h;                  // prototype taps (L)
     std::vector<int32_t> input, offset;    // per channel
     DevMem mem;
-    dv4f *d_taps = nullptr;
+    v4f *d_taps = nullptr;
     ChanGroup *d_groups = nullptr;
     int32_t *d_in_groups = nullptr, *d_fcm = nullptr, *d_sc = nullptr;
 };
@@ -238,7 +212,7 @@ struct pirip_hip_chan {
 namespace {
 
 // outputs per tile (T), its padding to whole waves (Tpad) and the staged window's LDS bytes
-size_t chan_lds(int Tpad, int D, int Lp, int P) { return ((size_t)Tpad + (Lp + D - 1) / D) * (size_t)P * sizeof(dv2f); }
+size_t chan_lds(int Tpad, int D, int Lp, int P) { return ((size_t)Tpad + (Lp + D - 1) / D) * (size_t)P * sizeof(v2f); }
 
 }  // namespace
 
@@ -250,10 +224,7 @@ int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s
     if (!out) return PIRIP_ERR_BAD_ARG;
     *out = nullptr;
     if (Fs < 2 || decimation < 1 || !(transition_bw > 0.f) || ninputs < 1 || nchan < 1 || !chan_input || !chan_offset_hz) return PIRIP_ERR_BAD_ARG;
-    for (int c = 0; c < nchan; c++) {
-        if (chan_input[c] < 0 || chan_input[c] >= ninputs) return PIRIP_ERR_BAD_ARG;
-        if (2 * (int64_t)chan_offset_hz[c] <= -(int64_t)Fs || 2 * (int64_t)chan_offset_hz[c] >= (int64_t)Fs) return PIRIP_ERR_BAD_ARG;
-    }
+    if (!channels_ok(Fs, ninputs, nchan, chan_input, chan_offset_hz)) return PIRIP_ERR_BAD_ARG;
     if (Fs > kMaxFs) return PIRIP_ERR_UNSUPPORTED;
     int dev = 0;
     PIRIP_TRY(select_device(device, &dev));
@@ -261,16 +232,10 @@ int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s
     if (!ch) return PIRIP_ERR_NOMEM;
     ch->device = dev;
     ch->Fs = Fs; ch->D = decimation; ch->out_s16 = out_s16 ? 1 : 0; ch->ninputs = ninputs; ch->nchan = nchan;
-    // section B's prototype: csdr's Hamming low-pass, cutoff 0.5 / D, padded with zeros to a multiple of 4
-    ch->L = csdr_filter_len(transition_bw);
-    ch->Lp = ch->L + 3 - ((ch->L + 3) % 4);
-    if (ch->L > 4096) { delete ch; return PIRIP_ERR_UNSUPPORTED; }
-    ch->h.resize(ch->L);
-    csdr_lowpass_hamming(ch->h.data(), ch->L, 0.5 / (float)decimation);
+    ch->u8 = csdr_u8_split();
+    if (prototype_filter(decimation, transition_bw, &ch->L, &ch->Lp, &ch->h) != PIRIP_OK || !ch->u8.exact) { delete ch; return PIRIP_ERR_UNSUPPORTED; }
     ch->input.assign(chan_input, chan_input + nchan);
     ch->offset.assign(chan_offset_hz, chan_offset_hz + nchan);
-    ch->c_hi = (float)(std::nearbyint((1.0 / 127.5) * 4194304.0) / 4194304.0);
-    ch->c_lo = (float)(1.0 / 127.5 - (double)ch->c_hi);
     // tile geometry: as many outputs (a multiple of 64, at most 256) as fit the LDS target; wide decimations fall back to one partial wave
     const int D = ch->D, Lp = ch->Lp;
     ch->P = (D & 1) ? D : D + 1;
@@ -300,26 +265,22 @@ int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s
         }
         in_groups.push_back((int32_t)groups.size());
     }
-    // modulated taps g_c[i] = h[i] e^{-j 2 pi f_c i / Fs} in double (the phase from the exact integer f_c i mod Fs), rounded to float
-    std::vector<dv4f> taps(groups.size() * (size_t)Lp * kMaxGroup, dv4f{0.f, 0.f, 0.f, 0.f});
+    // modulated taps g_c[i] = h[i] e^{-j 2 pi f_c i / Fs}
+    std::vector<v4f> taps(groups.size() * (size_t)Lp * kMaxGroup, v4f{0.f, 0.f, 0.f, 0.f});
     std::vector<int32_t> fcm(nchan), sc(nchan);
-    for (int c = 0; c < nchan; c++) {
-        const int64_t f = ((int64_t)chan_offset_hz[c] % Fs + Fs) % Fs;
-        fcm[c] = (int32_t)f;
-        sc[c] = (int32_t)((f * (D % Fs)) % Fs);
-    }
+    for (int c = 0; c < nchan; c++) { fcm[c] = (int32_t)fs_residue(chan_offset_hz[c], Fs); sc[c] = fs_step(fcm[c], D, Fs); }
     for (size_t g = 0; g < groups.size(); g++)
         for (int m = 0; m < groups[g].n; m++) {
             const int c = groups[g].ch[m];
             for (int i = 0; i < ch->L; i++) {
-                const double ph = -2.0 * M_PI * (double)(((int64_t)fcm[c] * i) % Fs) / (double)Fs;
-                const float gr = (float)((double)ch->h[i] * std::cos(ph)), gi = (float)((double)ch->h[i] * std::sin(ph));
-                taps[((size_t)g * Lp + i) * kMaxGroup + m] = dv4f{gr, gi, -gi, gr};
+                float gr, gi;
+                modulated_tap((double)ch->h[i], fcm[c], i, Fs, -1.0, &gr, &gi);
+                taps[((size_t)g * Lp + i) * kMaxGroup + m] = v4f{gr, gi, -gi, gr};
             }
         }
     auto tables = [&]() -> int {
         DevMem &m = ch->mem;
-        PIRIP_TRY(m.upload(&ch->d_taps, taps.data(), sizeof(dv4f) * taps.size()));
+        PIRIP_TRY(m.upload(&ch->d_taps, taps.data(), sizeof(v4f) * taps.size()));
         PIRIP_TRY(m.upload(&ch->d_groups, groups.data(), sizeof(ChanGroup) * groups.size()));
         PIRIP_TRY(m.upload(&ch->d_in_groups, in_groups.data(), sizeof(int32_t) * in_groups.size()));
         PIRIP_TRY(m.upload(&ch->d_fcm, fcm.data(), sizeof(int32_t) * nchan));
@@ -351,10 +312,7 @@ int pirip_hip_chan_get_info(const pirip_hip_chan *ch, pirip_chan_info *info)
 
 int pirip_hip_chan_taps(const pirip_hip_chan *ch, float *taps, int *ntaps)
 {
-    if (!ch || !ntaps) return PIRIP_ERR_BAD_ARG;
-    if (taps) std::memcpy(taps, ch->h.data(), sizeof(float) * ch->L);
-    *ntaps = ch->L;
-    return PIRIP_OK;
+    return copy_taps(ch ? &ch->h : nullptr, taps, ntaps);
 }
 
 int64_t pirip_hip_chan_nout(const pirip_hip_chan *ch, int64_t n_in)
@@ -380,9 +338,9 @@ int pirip_hip_chan_batch(pirip_hip_chan *ch, const uint8_t *d_in, size_t in_stri
     a.out = d_out; a.out_stride = out_stride_bytes;
     a.taps = ch->d_taps; a.groups = ch->d_groups; a.in_groups = ch->d_in_groups; a.fcm = ch->d_fcm; a.sc = ch->d_sc;
     a.Fs = ch->Fs; a.D = ch->D; a.Lp = ch->Lp; a.P = ch->P; a.T = ch->T; a.Tpad = ch->Tpad; a.out_s16 = ch->out_s16;
-    a.t0m = (int32_t)(((t0 % ch->Fs) + ch->Fs) % ch->Fs);
+    a.t0m = (int32_t)fs_residue(t0, ch->Fs);
     a.dm = ch->D % ch->Fs;
-    a.c_hi = ch->c_hi; a.c_lo = ch->c_lo;
+    a.c_hi = ch->u8.c_hi; a.c_lo = ch->u8.c_lo;
     a.inv_fs = 1.0f / (float)ch->Fs; a.m2_over_fs = -2.0f / (float)ch->Fs; a.inv_fs_d = 1.0 / (double)ch->Fs;
     hipLaunchKernelGGL(chan_kernel, dim3((unsigned)ntiles, (unsigned)ch->ninputs), dim3(kThreads), ch->lds, (hipStream_t)hip_stream, a);
     return hipGetLastError() == hipSuccess ? PIRIP_OK : PIRIP_ERR_HIP;

@@ -45,6 +45,8 @@
 #include "../../include/pirip_hip.h"
 #include "fsk_plan.hpp"
 #include "hip_host.hpp"
+#include "iq_device.hpp"
+#include "rate_host.hpp"
 
 using namespace pirip;
 
@@ -138,24 +140,21 @@ __device__ __forceinline__ void store_out(const DecimArgs &a, int sid, int64_t k
 {
     if (a.out_s16) {
         short2 *o = (short2 *)((char *)a.out + (size_t)sid * a.out_stride) + k;
-        *o = make_short2((short)(acci * (float)SHRT_MAX), (short)(accq * (float)SHRT_MAX));
+        *o = make_short2(f_to_s16_csdr(acci), f_to_s16_csdr(accq));
     } else {
         float2 *o = (float2 *)((char *)a.out + (size_t)sid * a.out_stride) + k;
         *o = make_float2(acci, accq);
     }
 }
 
-// csdr's u8->float, x/127.5 - 1 evaluated in double and rounded to float, as two fused multiply-adds:
-// fma(x, c_lo, fma(x, c_hi, -1)) with c_hi = 1/127.5 rounded to a multiple of 2^-22 (so the inner fma is exact for
-// every byte value) and c_lo the float remainder; bit-identical to the double formula for all 256 byte values,
-// checked at create time. Then one separate multiply and add per component (the scalar csdr loop's arithmetic).
+// One tap on an (I, Q) byte pair: csdr's u8->float (iq_device.hpp's u8_to_float; create checks it against the double formula), then
+// one separate multiply and add per component (the scalar csdr loop's arithmetic).
 template <int MODE>
 __device__ __forceinline__ void tap_mac(const DecimArgs &a, uint32_t w, float h, float &acci, float &accq)
 {
     const float xi = (float)(w & 0xffu), xq = (float)(w >> 8);
     if (MODE == kDecimFmaRaw) { acci = __builtin_fmaf(xi, h, acci); accq = __builtin_fmaf(xq, h, accq); return; }
-    const float yi = __builtin_fmaf(xi, a.c_lo, __builtin_fmaf(xi, a.c_hi, -1.0f));
-    const float yq = __builtin_fmaf(xq, a.c_lo, __builtin_fmaf(xq, a.c_hi, -1.0f));
+    const float yi = u8_to_float(xi, a.c_hi, a.c_lo), yq = u8_to_float(xq, a.c_hi, a.c_lo);
     if (MODE == kDecimFma) { acci = __builtin_fmaf(yi, h, acci); accq = __builtin_fmaf(yq, h, accq); return; }
     acci += yi * h;
     accq += yq * h;
@@ -241,7 +240,6 @@ __global__ __launch_bounds__(kThreads) void decim_kernel(DecimArgs a)
 // Per output 2 OV x 2 + 2 OV + (D - OV) x 6 + 2 OV = 340 VALU instructions at D = 45 against 474, 45 LDS sample reads against 79, two
 // independent sum chains per lane; the same float32 operations on the same operands in the same order: bit-identical outputs (f32 and
 // s16; tested against decim_kernel and the oracle). PIRIP_DECIM_SHARED=0 (read at create) keeps decim_kernel for A/B runs.
-typedef float dv2f __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ float from_lane_down(float v)      // the value of lane - 1 (lane 0: 0)
 {
     return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x138, 0xf, 0xf, true));
@@ -263,11 +261,8 @@ __global__ __launch_bounds__(kThreads, 5) void decim_shared_kernel(DecimArgs a)
     const int64_t ntiles = (a.n_out + a.tile - 1) / a.tile;
     const int64_t t_begin = (int64_t)blockIdx.x * a.tpw;
     const int64_t t_end = (t_begin + a.tpw < ntiles) ? t_begin + a.tpw : ntiles;
-    const dv2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo}, m1 = {-1.0f, -1.0f};
-    auto conv = [&](uint32_t w) {                        // csdr's x / 127.5 - 1 for the (I, Q) byte pair, as decim_kernel's tap_mac computes it
-        const dv2f x = {(float)(w & 0xffu), (float)(w >> 8)};
-        return __builtin_elementwise_fma(x, clo, __builtin_elementwise_fma(x, chi, m1));
-    };
+    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
+    auto conv = [&](uint32_t w) { return u8_to_float(v2f{(float)(w & 0xffu), (float)(w >> 8)}, chi, clo); };   // (the (I, Q) pair of one LDS read, as tap_mac converts it)
     typedef float f32x4_t __attribute__((ext_vector_type(4)));
     for (int64_t tile = t_begin; tile < t_end; tile++) {
         const TileGeom g = tile_geom(a, src, tile);
@@ -282,7 +277,7 @@ __global__ __launch_bounds__(kThreads, 5) void decim_shared_kernel(DecimArgs a)
             asm volatile("" : "+v"(taps));
             auto tap4 = [&](int t0) { return *(const __attribute__((address_space(3))) f32x4_t *)(uintptr_t)(taps + 4u * (uint32_t)t0); };
             // steps 1 + 2: own samples [D, L), and with them the next output's prefix over taps [0, OV)
-            dv2f sv[OV], pre = {0.f, 0.f};
+            v2f sv[OV], pre = {0.f, 0.f};
 #pragma unroll
             for (int u0 = 0; u0 < OV; u0 += 4) {
                 const f32x4_t h4 = tap4(u0);
@@ -291,14 +286,14 @@ __global__ __launch_bounds__(kThreads, 5) void decim_shared_kernel(DecimArgs a)
                 for (int q = 0; q < 4 && u0 + q < OV; q++) {
                     const int u = u0 + q;
                     sv[u] = conv(lds_u16(x + 2 * (D + u)));
-                    pre = pre + sv[u] * dv2f{hh[q], hh[q]};
+                    pre = pre + sv[u] * v2f{hh[q], hh[q]};
                 }
                 // (pins the running sums in place: their only use is the store under the lane mask below, and the compiler otherwise sinks the
                 //  whole accumulation under that branch -- behind every product, which it then has to spill)
                 asm volatile("" : "+v"(pre));
             }
             // step 3: continue from the neighbour's prefix
-            dv2f acc = {from_lane_down(pre.x), from_lane_down(pre.y)};
+            v2f acc = {from_lane_down(pre.x), from_lane_down(pre.y)};
 #pragma unroll
             for (int t0 = OV & ~3; t0 < L; t0 += 4) {
                 const f32x4_t h4 = tap4(t0);
@@ -307,8 +302,8 @@ __global__ __launch_bounds__(kThreads, 5) void decim_shared_kernel(DecimArgs a)
                 for (int q = 0; q < 4; q++) {
                     const int t = t0 + q;
                     if (t < OV || t >= L) continue;
-                    const dv2f y = t < D ? conv(lds_u16(x + 2 * t)) : sv[t - D];
-                    acc = acc + y * dv2f{hh[q], hh[q]};
+                    const v2f y = t < D ? conv(lds_u16(x + 2 * t)) : sv[t - D];
+                    acc = acc + y * v2f{hh[q], hh[q]};
                 }
                 asm volatile("" : "+v"(acc));
             }
@@ -344,11 +339,8 @@ __global__ __launch_bounds__(kThreads, 5) void decim_systolic_kernel(DecimArgs a
     const int64_t ntiles = (a.n_out + a.tile - 1) / a.tile;
     const int64_t t_begin = (int64_t)blockIdx.x * a.tpw;
     const int64_t t_end = (t_begin + a.tpw < ntiles) ? t_begin + a.tpw : ntiles;
-    const dv2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo}, m1 = {-1.0f, -1.0f};
-    auto conv = [&](uint32_t w) {
-        const dv2f x = {(float)(w & 0xffu), (float)(w >> 8)};
-        return __builtin_elementwise_fma(x, clo, __builtin_elementwise_fma(x, chi, m1));
-    };
+    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
+    auto conv = [&](uint32_t w) { return u8_to_float(v2f{(float)(w & 0xffu), (float)(w >> 8)}, chi, clo); };   // (the (I, Q) pair of one LDS read, as tap_mac converts it)
     for (int64_t tile = t_begin; tile < t_end; tile++) {
         const TileGeom g = tile_geom(a, src, tile);
         stage_window(g, total, s_x, tid);
@@ -357,19 +349,19 @@ __global__ __launch_bounds__(kThreads, 5) void decim_systolic_kernel(DecimArgs a
             const uint8_t *x = s_x + g.head + 2 * (B0 + lane) * D;                       // this lane's block of D fresh samples
             uint32_t taps = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) char *)smem;
             asm volatile("" : "+v"(taps));
-            dv2f y[D];
+            v2f y[D];
 #pragma unroll
             for (int u = 0; u < D; u++) y[u] = conv(lds_u16(x + 2 * u));
-            dv2f acc = {0.f, 0.f};
+            v2f acc = {0.f, 0.f};
 #pragma unroll
             for (int st = 0; st < S; st++) {
-                if (st) acc = dv2f{from_lane_down(acc.x), from_lane_down(acc.y)};
+                if (st) acc = v2f{from_lane_down(acc.x), from_lane_down(acc.y)};
 #pragma unroll
                 for (int u = 0; u < D; u++) {
                     const int t = st * D + u;
                     if (t >= L) break;
                     const float h = *(const __attribute__((address_space(3))) float *)(uintptr_t)(taps + 4u * (uint32_t)t);
-                    acc = acc + y[u] * dv2f{h, h};
+                    acc = acc + y[u] * v2f{h, h};
                 }
                 asm volatile("" : "+v"(acc));             // (pins the sum in place: see decim_shared_kernel)
             }
@@ -408,7 +400,7 @@ __global__ __launch_bounds__(kThreads) void cvt_u8_f_kernel(const uint8_t *in, f
 __global__ __launch_bounds__(kThreads) void cvt_f_s16_kernel(const float *in, short *out, int n)
 {
     for (int i = blockIdx.x * kThreads + threadIdx.x; i < n; i += gridDim.x * kThreads)
-        out[i] = (short)(in[i] * (float)SHRT_MAX);
+        out[i] = f_to_s16_csdr(in[i]);
 }
 
 template <typename TI, typename TO, typename F>
@@ -436,7 +428,7 @@ void host_elementwise(const char *name, const TI *in, TO *out, int n, F launch)
 struct pirip_hip_decim {
     int D = 0, L = 0, Lp = 0, out_s16 = 0, tile = 0, device = 0;
     size_t lds = 0;
-    float c_hi = 0.f, c_lo = 0.f;   // exact arithmetic u8->float (see decim_kernel)
+    U8Split u8{};                   // exact arithmetic u8->float (see decim_kernel)
     int arith = 0;
     int mode = 0;                   // kDecimExact unless PIRIP_DECIM_FMA asked for a measurement variant at create
     int shared = 0;                 // 1: decim_shared_kernel<D, L>, 2: decim_systolic_kernel<D, L> exists for this shape (and PIRIP_DECIM_SHARED != 0): tile_sh / lds_sh are its geometry
@@ -447,6 +439,8 @@ struct pirip_hip_decim {
     float *d_taps = nullptr, *d_lut = nullptr;
 };
 #pragma GCC visibility pop
+
+void pirip::decim_handle_shape(const pirip_hip_decim *d, int *Lp, int *D, int *out_s16) { *Lp = d->Lp; *D = d->D; *out_s16 = d->out_s16; }
 
 extern "C" {
 
@@ -459,13 +453,7 @@ int pirip_hip_decim_create(int decimation, float transition_bw, int out_s16, int
     pirip_hip_decim *d = new (std::nothrow) pirip_hip_decim();
     if (!d) return PIRIP_ERR_NOMEM;
     d->D = decimation; d->out_s16 = out_s16 ? 1 : 0; d->device = dev;
-    d->L = csdr_filter_len(transition_bw);
-    // csdr pads the taps with zeros to a multiple of 4 and uses the padded length in the
-    // "enough input left" test; zero taps add +0 and are skipped in the kernel.
-    d->Lp = d->L + 3 - ((d->L + 3) % 4);
-    if (d->L > 4096) { delete d; return PIRIP_ERR_UNSUPPORTED; }
-    d->taps.resize(d->L);
-    csdr_lowpass_hamming(d->taps.data(), d->L, 0.5 / (float)decimation);
+    if (prototype_filter(decimation, transition_bw, &d->L, &d->Lp, &d->taps) != PIRIP_OK) { delete d; return PIRIP_ERR_UNSUPPORTED; }
     // tile: as many outputs per workgroup as fit a 48 KiB u8 window
     int tile = kThreads;
     while (tile > 1 && 2 * ((size_t)(tile - 1) * d->D + d->L) + 32 > 48 * 1024) tile /= 2;
@@ -479,14 +467,8 @@ int pirip_hip_decim_create(int decimation, float transition_bw, int out_s16, int
     if (rc != PIRIP_OK) { delete d; return rc; }
     // arithmetic u8->float must reproduce csdr's double formula for every byte value, else keep the table
     {
-        d->c_hi = (float)(std::nearbyint((1.0 / 127.5) * 4194304.0) / 4194304.0);
-        d->c_lo = (float)(1.0 / 127.5 - (double)d->c_hi);
-        bool exact = true;
-        for (int x = 0; x < 256; x++) {
-            const float y = std::fmaf((float)x, d->c_lo, std::fmaf((float)x, d->c_hi, -1.0f));
-            exact &= (y == lut[x]);
-        }
-        d->arith = exact && !getenv("PIRIP_DECIM_LUT");
+        d->u8 = csdr_u8_split();
+        d->arith = d->u8.exact && !getenv("PIRIP_DECIM_LUT");
         if (const char *e = getenv("PIRIP_DECIM_FMA")) {
             const int m = atoi(e);
             if (d->arith && (m == kDecimFma || m == kDecimFmaRaw)) d->mode = m;
@@ -530,10 +512,7 @@ int pirip_hip_decim_get_arith(const pirip_hip_decim *d) { return d ? d->mode : P
 
 int pirip_hip_decim_taps(const pirip_hip_decim *d, float *taps, int *ntaps)
 {
-    if (!d || !ntaps) return PIRIP_ERR_BAD_ARG;
-    if (taps) std::memcpy(taps, d->taps.data(), sizeof(float) * d->L);
-    *ntaps = d->L;
-    return PIRIP_OK;
+    return copy_taps(d ? &d->taps : nullptr, taps, ntaps);
 }
 
 int64_t pirip_hip_decim_nout(const pirip_hip_decim *d, int64_t n_in)
@@ -552,7 +531,7 @@ int pirip_hip_decim_batch(pirip_hip_decim *d, const uint8_t *d_in, size_t in_str
     // the shape-specialised kernel (every sample converted once per wave) where it exists: exact arithmetic, 16-bit aligned windows
     const bool sh = d->shared && d->mode == kDecimExact && !(((uintptr_t)d_in | (uintptr_t)in_stride_bytes) & 1);
     const int tile = sh ? d->tile_sh : d->tile;
-    DecimArgs a{d_in, in_stride_bytes, n_in, d_out, out_stride_bytes, n_out, d->d_taps, d->d_lut, d->D, d->L, tile, d->out_s16, d->arith, 0, d->mode, d->c_hi, d->c_lo, d->tap_sum};
+    DecimArgs a{d_in, in_stride_bytes, n_in, d_out, out_stride_bytes, n_out, d->d_taps, d->d_lut, d->D, d->L, tile, d->out_s16, d->arith, 0, d->mode, d->u8.c_hi, d->u8.c_lo, d->tap_sum};
     const int64_t ntiles = (n_out + tile - 1) / tile;
     // tiles per workgroup: a long walk (read-ahead, taps staged once) as long as the chip stays many times over-filled
     int tpw = 8;

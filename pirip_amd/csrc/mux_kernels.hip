@@ -3,11 +3,10 @@
 // K channels of modem-rate complex float onto W wideband IQ streams. Channel c = (output chan_output[c], centre offset f_c, gain a_c):
 //     u_c[n] = sum_{q=0}^{Q-1} h[p + qD] z_c[m - q],                n = mD + p, 0 <= p < D      (polyphase interpolation by D)
 //     w_i[n] = sum_{c of output i, ascending} a_c e^{+j w_c n} u_c[n],   w_c = 2 pi f_c / Fs
-// Modulated-filter form, turned round: g_c[i] = a_c h[i] e^{+j w_c i} (host, double, rounded to float) and one rotation per INPUT sample,
-// z'_c[m] = z_c[m] e^{+j w_c m D}, whose phase is the exact integer ((f_c D mod Fs)(m mod Fs)) mod Fs of the absolute input index m. Then
-//     w_i[mD + p] = sum_c sum_q g_c[p + qD] z'_c[m - q]
-// with no transcendental at the wideband rate, no phasor recursion, and a value that is a function of the absolute index alone: any split
-// of a row into calls that overlap by Q - 1 input samples gives the one-shot output bit for bit.
+// Modulated-filter form, turned round: g_c[i] = a_c h[i] e^{+j w_c i} (rate_host.hpp's modulated_tap) and one rotation per INPUT sample,
+// z'_c[m] = z_c[m] e^{+j w_c m D}, from the exact integer phase ((f_c D mod Fs)(m mod Fs)) mod Fs of the absolute input index m
+// (iq_device.hpp). Then w_i[mD + p] = sum_c sum_q g_c[p + qD] z'_c[m - q], with no transcendental at the wideband rate; any split of a
+// row into calls that overlap by Q - 1 input samples gives the one-shot output bit for bit.
 //
 // Kernel: one workgroup per (tile of kTile = 2048 outputs, output). The channels of the output are taken in groups of at most kMaxGroup
 // (fewer when LDS says so), ascending; per group the workgroup stages the modulated taps and the tile's input span of every channel of the
@@ -28,14 +27,14 @@
 
 #include <cmath>
 #include <cstdint>
-#include <cstdlib>
-#include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/pirip_hip.h"
 #include "fsk_plan.hpp"
 #include "hip_host.hpp"
+#include "iq_device.hpp"
+#include "rate_host.hpp"
 
 using namespace pirip;
 
@@ -45,15 +44,12 @@ constexpr int kThreads = 256;
 constexpr int kPerThread = 8;              // outputs per thread and tile (accumulator pairs)
 constexpr int kTile = kThreads * kPerThread;
 constexpr int kMaxGroup = 8;               // channels staged together
-constexpr int kMaxFs = 1 << 24;            // the rotation's integers are exact in float and in the double product up to this
 constexpr size_t kLdsMax = 64 * 1024;
-
-typedef float dv2f __attribute__((ext_vector_type(2)));
 
 struct MuxArgs {
     const char *in; size_t in_stride; int64_t n_in, n_out;
     char *out; size_t out_stride;
-    const dv2f *taps;                      // [nchan][Q][Dp] g_c, each row of D followed by its first Dp - D entries
+    const v2f *taps;                       // [nchan][Q][Dp] g_c, each row of D followed by its first Dp - D entries
     const int32_t *out_start;              // [noutputs + 1]: the channels of output i are out_ch[out_start[i] .. out_start[i + 1])
     const int32_t *out_ch;                 // [nchan] channel indices, ascending within an output
     const int32_t *sc;                     // [nchan] (f_c mod Fs) D mod Fs
@@ -64,33 +60,15 @@ struct MuxArgs {
     double inv_fs_d;
 };
 
-// (a b) mod Fs for 0 <= a, b < 2^24: the product is exact in double, the quotient is right or one off, the remainder exact.
-__device__ __forceinline__ int32_t mulmod(int32_t a, int32_t b, int Fs, double inv_fs)
-{
-    const double p = (double)a * (double)b;
-    const double q = floor(p * inv_fs);
-    double r = fma(-q, (double)Fs, p);
-    if (r < 0.0) r += (double)Fs;
-    if (r >= (double)Fs) r -= (double)Fs;
-    return (int32_t)r;
-}
-
-// clamp(rintf(127.5f v + 127.5f), 0, 255): the product and the sum round separately (the build has fp-contract off)
-__device__ __forceinline__ uint32_t quant(float v)
-{
-    const float q = rintf(127.5f * v + 127.5f);
-    return (uint32_t)fminf(fmaxf(q, 0.f), 255.f);
-}
-
 // BS: bytes per output sample, 2 (u8 IQ) or 8 (complex float)
 template <int BS>
 __global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     char *s_out = smem;                                                 // [kTile] samples as they are stored
-    dv2f *s_g = (dv2f *)(smem + (size_t)kTile * BS);                    // [G][Q * Dp]
+    v2f *s_g = (v2f *)(smem + (size_t)kTile * BS);                      // [G][Q * Dp]
     const int tapsz = a.Q * a.Dp;
-    dv2f *s_z = s_g + (size_t)a.G * tapsz;                              // [G][Mt]
+    v2f *s_z = s_g + (size_t)a.G * tapsz;                               // [G][Mt]
     const int tid = threadIdx.x;
     const int i = blockIdx.y;
     const int64_t j0 = (int64_t)blockIdx.x * kTile;                     // first output of the tile (of this call)
@@ -102,9 +80,9 @@ __global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
     const int32_t base = (int32_t)(((int64_t)a.m0m + a0 % a.Fs) % a.Fs);
     const int m_first = (p0 + tid) / a.D, p_first = (p0 + tid) - m_first * a.D;
     const int lane32 = tid & 31;
-    dv2f acc[kPerThread];
+    v2f acc[kPerThread];
 #pragma unroll
-    for (int k = 0; k < kPerThread; k++) acc[k] = dv2f{0.f, 0.f};
+    for (int k = 0; k < kPerThread; k++) acc[k] = v2f{0.f, 0.f};
 
     const int c0 = a.out_start[i], c1 = a.out_start[i + 1];
     for (int cb = c0; cb < c1; cb += a.G) {
@@ -112,7 +90,7 @@ __global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
         if (cb > c0) __syncthreads();
         for (int m = 0; m < ng; m++) {
             const int ch = a.out_ch[cb + m];
-            const dv2f *g = a.taps + (size_t)ch * tapsz;
+            const v2f *g = a.taps + (size_t)ch * tapsz;
             for (int e = tid; e < tapsz; e += kThreads) s_g[(size_t)m * tapsz + e] = g[e];
             const float2 *z = (const float2 *)(a.in + (size_t)ch * a.in_stride);
             const int32_t s = a.sc[ch];
@@ -120,11 +98,9 @@ __global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
                 float2 v = make_float2(0.f, 0.f);
                 if (a0 + r < a.n_in) v = z[a0 + r];
                 const int32_t idx = (int32_t)(((uint32_t)base + (uint32_t)r) % (uint32_t)a.Fs);
-                int32_t ph = mulmod(s, idx, a.Fs, a.inv_fs_d);
-                if (2 * ph > a.Fs) ph -= a.Fs;                          // the angle as a fraction of pi in (-1, 1]
                 float sn, cs;
-                sincospif((float)ph * a.two_over_fs, &sn, &cs);
-                s_z[(size_t)m * a.Mt + r] = dv2f{__builtin_fmaf(v.x, cs, -(v.y * sn)), __builtin_fmaf(v.x, sn, v.y * cs)};
+                unit_phasor((int32_t)mulmod_fs(s, idx, a.Fs, a.inv_fs_d), a.Fs, a.two_over_fs, cs, sn);
+                s_z[(size_t)m * a.Mt + r] = crot(v2f{v.x, v.y}, cs, sn);
             }
         }
         __syncthreads();
@@ -134,13 +110,13 @@ __global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
             if (k * kThreads + tid < cnt) {
                 const int e = (a.Dp != a.D && pp < lane32) ? pp + a.D : pp;
                 for (int m = 0; m < ng; m++) {
-                    const dv2f *g = s_g + (size_t)m * tapsz + e;
-                    const dv2f *z = s_z + (size_t)m * a.Mt + mm + a.Q - 1;
-                    dv2f u = {0.f, 0.f};
+                    const v2f *g = s_g + (size_t)m * tapsz + e;
+                    const v2f *z = s_z + (size_t)m * a.Mt + mm + a.Q - 1;
+                    v2f u = {0.f, 0.f};
                     for (int q = 0; q < a.Q; q++, g += a.Dp, z--) {
-                        const dv2f gg = *g, zz = *z;
-                        u = __builtin_elementwise_fma(dv2f{zz.x, zz.x}, gg, u);
-                        u = __builtin_elementwise_fma(dv2f{zz.y, zz.y}, dv2f{-gg.y, gg.x}, u);
+                        const v2f gg = *g, zz = *z;
+                        u = __builtin_elementwise_fma(v2f{zz.x, zz.x}, gg, u);
+                        u = __builtin_elementwise_fma(v2f{zz.y, zz.y}, v2f{-gg.y, gg.x}, u);
                     }
                     acc[k] += u;
                 }
@@ -154,8 +130,8 @@ __global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
 #pragma unroll
     for (int k = 0; k < kPerThread; k++) {
         const int n = k * kThreads + tid;
-        if (BS == 2) ((uint16_t *)s_out)[n] = (uint16_t)(quant(acc[k].x) | (quant(acc[k].y) << 8));
-        else ((dv2f *)s_out)[n] = acc[k];
+        if (BS == 2) ((uint16_t *)s_out)[n] = (uint16_t)((uint32_t)quant_u8_csdr(acc[k].x) | ((uint32_t)quant_u8_csdr(acc[k].y) << 8));
+        else ((v2f *)s_out)[n] = acc[k];
     }
     __syncthreads();
     constexpr int SPU = 16 / BS;                                        // samples per 16-byte unit
@@ -180,14 +156,14 @@ struct pirip_hip_mux {
     size_t lds = 0;
     std::vector<float> h;                  // prototype taps (L)
     DevMem mem;
-    dv2f *d_taps = nullptr;
+    v2f *d_taps = nullptr;
     int32_t *d_out_start = nullptr, *d_out_ch = nullptr, *d_sc = nullptr;
 };
 
 namespace {
 
 // LDS bytes of a workgroup that stages G channels: the tile as stored, G tap tables, G input spans
-size_t mux_lds(int G, int bs, int Q, int Dp, int Mt) { return (size_t)kTile * bs + (size_t)G * ((size_t)Q * Dp + Mt) * sizeof(dv2f); }
+size_t mux_lds(int G, int bs, int Q, int Dp, int Mt) { return (size_t)kTile * bs + (size_t)G * ((size_t)Q * Dp + Mt) * sizeof(v2f); }
 
 }  // namespace
 
@@ -202,18 +178,15 @@ int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_b
     if (kind != PIRIP_MUX_FIR && kind != PIRIP_MUX_LINEAR) return PIRIP_ERR_BAD_ARG;
     if (kind == PIRIP_MUX_FIR && !(transition_bw > 0.f)) return PIRIP_ERR_BAD_ARG;
     if (out_format != PIRIP_IN_CU8_CSDR && out_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
-    for (int c = 0; c < nchan; c++) {
-        if (chan_output[c] < 0 || chan_output[c] >= noutputs) return PIRIP_ERR_BAD_ARG;
-        if (2 * (int64_t)chan_offset_hz[c] <= -(int64_t)Fs || 2 * (int64_t)chan_offset_hz[c] >= (int64_t)Fs) return PIRIP_ERR_BAD_ARG;
-        if (chan_gain && !std::isfinite(chan_gain[c])) return PIRIP_ERR_BAD_ARG;
-    }
+    if (!channels_ok(Fs, noutputs, nchan, chan_output, chan_offset_hz)) return PIRIP_ERR_BAD_ARG;
+    for (int c = 0; chan_gain && c < nchan; c++) if (!std::isfinite(chan_gain[c])) return PIRIP_ERR_BAD_ARG;
     if (Fs > kMaxFs || noutputs > 65535) return PIRIP_ERR_UNSUPPORTED;
     const int D = interpolation;
     const int64_t L64 = kind == PIRIP_MUX_FIR ? (int64_t)csdr_filter_len(transition_bw) : 2 * (int64_t)D - 1;
     const int64_t Q64 = (L64 + D - 1) / D, Dp64 = D > 32 ? (int64_t)D + 31 : D, Mt64 = ((int64_t)D + kTile - 2) / D + Q64;
     const int bs = out_format == PIRIP_IN_CF32 ? 8 : 2;
     // the working set of one channel must fit the LDS of a workgroup (the header's rule)
-    if (L64 < 1 || (Q64 * Dp64 + Mt64) * (int64_t)sizeof(dv2f) + (int64_t)kTile * bs > (int64_t)kLdsMax) return PIRIP_ERR_UNSUPPORTED;
+    if (L64 < 1 || (Q64 * Dp64 + Mt64) * (int64_t)sizeof(v2f) + (int64_t)kTile * bs > (int64_t)kLdsMax) return PIRIP_ERR_UNSUPPORTED;
     int dev = 0;
     PIRIP_TRY(select_device(device, &dev));
     pirip_hip_mux *mx = new (std::nothrow) pirip_hip_mux();
@@ -221,12 +194,12 @@ int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_b
     mx->device = dev;
     mx->Fs = Fs; mx->D = D; mx->kind = kind; mx->out_format = out_format; mx->bs = bs; mx->noutputs = noutputs; mx->nchan = nchan;
     mx->L = (int)L64; mx->Q = (int)Q64; mx->Dp = (int)Dp64; mx->Mt = (int)Mt64;
-    mx->h.resize((size_t)mx->L);
     if (kind == PIRIP_MUX_FIR) {
-        // section B's prototype (csdr's Hamming low-pass, cutoff 0.5 / D) times D: unity gain for the interpolated signal
-        csdr_lowpass_hamming(mx->h.data(), mx->L, 0.5 / (float)D);
+        // section B's prototype times D: unity gain for the interpolated signal
+        prototype_taps(D, mx->L, &mx->h);
         for (float &v : mx->h) v = (float)((double)D * (double)v);
     } else {
+        mx->h.resize((size_t)mx->L);
         for (int i = 0; i < mx->L; i++) mx->h[(size_t)i] = (float)(1.0 - std::fabs((double)(i - (D - 1))) / (double)D);
     }
     mx->G = kMaxGroup;
@@ -238,26 +211,26 @@ int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_b
         for (int c = 0; c < nchan; c++) if (chan_output[c] == w) out_ch.push_back(c);
         out_start.push_back((int32_t)out_ch.size());
     }
-    // g_c[i] = a_c h[i] e^{+j 2 pi f_c i / Fs} in double (the phase from the exact integer f_c i mod Fs), rounded to float
+    // g_c[i] = a_c h[i] e^{+j 2 pi f_c i / Fs}
     const size_t tapsz = (size_t)mx->Q * mx->Dp;
-    std::vector<dv2f> taps((size_t)nchan * tapsz, dv2f{0.f, 0.f});
+    std::vector<v2f> taps((size_t)nchan * tapsz, v2f{0.f, 0.f});
     std::vector<int32_t> sc((size_t)nchan);
     for (int c = 0; c < nchan; c++) {
-        const int64_t f = ((int64_t)chan_offset_hz[c] % Fs + Fs) % Fs;
-        sc[(size_t)c] = (int32_t)((f * (D % Fs)) % Fs);
+        const int64_t f = fs_residue(chan_offset_hz[c], Fs);
+        sc[(size_t)c] = fs_step(f, D, Fs);
         const double gain = chan_gain ? (double)chan_gain[c] : 1.0;
         for (int q = 0; q < mx->Q; q++)
             for (int e = 0; e < mx->Dp; e++) {
                 const int64_t idx = (int64_t)q * D + e % D;
                 if (idx >= mx->L) continue;
-                const double ph = 2.0 * M_PI * (double)((f * idx) % Fs) / (double)Fs;
-                const double v = gain * (double)mx->h[(size_t)idx];
-                taps[(size_t)c * tapsz + (size_t)q * mx->Dp + e] = dv2f{(float)(v * std::cos(ph)), (float)(v * std::sin(ph))};
+                float gr, gi;
+                modulated_tap(gain * (double)mx->h[(size_t)idx], f, idx, Fs, +1.0, &gr, &gi);
+                taps[(size_t)c * tapsz + (size_t)q * mx->Dp + e] = v2f{gr, gi};
             }
     }
     auto tables = [&]() -> int {
         DevMem &m = mx->mem;
-        PIRIP_TRY(m.upload(&mx->d_taps, taps.data(), sizeof(dv2f) * taps.size()));
+        PIRIP_TRY(m.upload(&mx->d_taps, taps.data(), sizeof(v2f) * taps.size()));
         PIRIP_TRY(m.upload(&mx->d_out_start, out_start.data(), sizeof(int32_t) * out_start.size()));
         PIRIP_TRY(m.upload(&mx->d_out_ch, out_ch.data(), sizeof(int32_t) * out_ch.size()));
         PIRIP_TRY(m.upload(&mx->d_sc, sc.data(), sizeof(int32_t) * sc.size()));
@@ -287,10 +260,7 @@ int pirip_hip_mux_get_info(const pirip_hip_mux *mx, pirip_mux_info *info)
 
 int pirip_hip_mux_taps(const pirip_hip_mux *mx, float *taps, int *ntaps)
 {
-    if (!mx || !ntaps) return PIRIP_ERR_BAD_ARG;
-    if (taps) std::memcpy(taps, mx->h.data(), sizeof(float) * (size_t)mx->L);
-    *ntaps = mx->L;
-    return PIRIP_OK;
+    return copy_taps(mx ? &mx->h : nullptr, taps, ntaps);
 }
 
 int64_t pirip_hip_mux_nout(const pirip_hip_mux *mx, int64_t n_in)
@@ -319,7 +289,7 @@ int pirip_hip_mux_batch(pirip_hip_mux *mx, const void *d_in, size_t in_stride_by
     a.Fs = mx->Fs; a.D = mx->D; a.Dp = mx->Dp; a.Q = mx->Q; a.Mt = mx->Mt; a.G = mx->G;
     a.aligned16 = (((uintptr_t)d_out | out_stride_bytes) & 15) == 0;
     a.step_m = kThreads / mx->D; a.step_p = kThreads % mx->D;
-    a.m0m = (int32_t)(((m0 % mx->Fs) + mx->Fs) % mx->Fs);
+    a.m0m = (int32_t)fs_residue(m0, mx->Fs);
     a.two_over_fs = 2.0f / (float)mx->Fs; a.inv_fs_d = 1.0 / (double)mx->Fs;
     const dim3 grid((unsigned)ntiles, (unsigned)mx->noutputs);
     hipStream_t st = (hipStream_t)hip_stream;

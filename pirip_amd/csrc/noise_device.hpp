@@ -1,7 +1,7 @@
-// pirip_amd/csrc/noise_device.hpp -- the product's noise source and u8 quantiser on the device, shared by the synthetic transmitter
-// (synth_kernels.hip) and the batch transmitter (tx_kernels.hip): equal keys give equal bytes in both (tests/test_tx_noise.py).
+// pirip_amd/csrc/noise_device.hpp -- the product's noise source on the device, shared by the synthetic transmitter (synth_kernels.hip) and the
+// batch transmitter (tx_kernels.hip): equal keys give equal bytes in both (tests/test_tx_noise.py; their quantiser is iq_device.hpp's quant_u8).
 // AWGN: sigma * N(0,1) per component from a counter-based generator -- SplitMix64 finaliser of (seed, stream, sample) -> two uniforms
-// -> Box-Muller; it is not meant to reproduce any CPU generator. Quantiser: u8 = clamp(rintf(127 + amp * x)), float32 arithmetic.
+// -> Box-Muller; it is not meant to reproduce any CPU generator.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -27,12 +27,6 @@ __device__ __forceinline__ void add_awgn(uint64_t seed, int s, int64_t n, float 
     float sn, cs;
     sincosf(6.2831853071795865f * u2, &sn, &cs);
     xr += mag * cs; xi += mag * sn;
-}
-
-__device__ __forceinline__ float quant_u8(float v, float amp)      // the byte's value, still a float
-{
-    const float q = rintf(127.0f + amp * v);
-    return fminf(fmaxf(q, 0.f), 255.f);
 }
 
 }  // namespace pirip

@@ -21,6 +21,7 @@
 #include "../../include/pirip_hip.h"
 #include "fsk_device.hpp"
 #include "demod_handle.hpp"
+#include "rate_host.hpp"
 
 using namespace pirip;
 
@@ -135,31 +136,6 @@ int rx_clear(pirip_hip_rx *rx, hipStream_t st)
     return PIRIP_OK;
 }
 
-// What section B does not expose: the padded filter length and D (from pirip_hip_decim_nout) and the output format (one output of
-// the decimator on zeros: an s16 output is 4 bytes, a complex float one 8). Synchronous.
-int decim_shape(pirip_hip_decim *dec, int *Lp, int *D, int *out_s16)
-{
-    int ntaps = 0;
-    if (pirip_hip_decim_taps(dec, nullptr, &ntaps) != PIRIP_OK || ntaps <= 0) return PIRIP_ERR_BAD_ARG;
-    int lp = ntaps;
-    while (pirip_hip_decim_nout(dec, lp) < 1) if (++lp > ntaps + 64) return PIRIP_ERR_BAD_ARG;
-    int d = 1;
-    while (pirip_hip_decim_nout(dec, (int64_t)lp + d) < 2) if (++d > (1 << 20)) return PIRIP_ERR_BAD_ARG;
-    uint8_t *buf = nullptr;
-    const size_t in_b = round_up((size_t)lp * 2, 256);
-    if (hipMalloc((void **)&buf, in_b + 256) != hipSuccess) return PIRIP_ERR_NOMEM;
-    uint8_t out[8] = {};
-    int rc = PIRIP_OK;
-    if (hipMemset(buf, 0, in_b) != hipSuccess || hipMemset(buf + in_b, 0xA5, 256) != hipSuccess) rc = PIRIP_ERR_HIP;
-    if (rc == PIRIP_OK) rc = pirip_hip_decim_batch(dec, buf, in_b, lp, buf + in_b, 8, 1, nullptr);
-    if (rc == PIRIP_OK && (hipDeviceSynchronize() != hipSuccess || hipMemcpy(out, buf + in_b, 8, hipMemcpyDeviceToHost) != hipSuccess)) rc = PIRIP_ERR_HIP;
-    (void)hipFree(buf);
-    if (rc != PIRIP_OK) return rc;
-    *Lp = lp; *D = d;
-    *out_s16 = out[4] == 0xA5 && out[5] == 0xA5 && out[6] == 0xA5 && out[7] == 0xA5;   // (zeros in: a float output is -sum(taps), never the fill)
-    return PIRIP_OK;
-}
-
 int rx_run(pirip_hip_rx *rx, uint8_t *d_bits, size_t bits_stride, float *d_rx_filt, size_t filt_stride, uint8_t *d_status, uint8_t *d_payload,
            int32_t *d_info, float *d_stats, size_t stats_stride, int32_t *d_nframes, hipStream_t st)
 {
@@ -234,8 +210,7 @@ int rx_create_impl(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *
     int Lp = 0, D = 1, out_s16 = 0, nraw = dem->nstreams;
     if (dec) {
         if (d.in_format != PIRIP_IN_CF32 && d.in_format != PIRIP_IN_CS16) return PIRIP_ERR_BAD_ARG;
-        const int rc = decim_shape(dec, &Lp, &D, &out_s16);
-        if (rc != PIRIP_OK) return rc;
+        decim_handle_shape(dec, &Lp, &D, &out_s16);
         if (out_s16 != (d.in_format == PIRIP_IN_CS16)) return PIRIP_ERR_BAD_ARG;
         if (block % D != 0) return PIRIP_ERR_BAD_ARG;
     }

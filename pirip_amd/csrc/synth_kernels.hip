@@ -21,6 +21,7 @@
 #include <vector>
 
 #include "../../include/pirip_hip.h"
+#include "iq_device.hpp"
 #include "noise_device.hpp"
 
 using namespace pirip;

@@ -34,13 +34,14 @@
 #include "../../include/pirip_hip.h"
 #include "fsk_ldpc.hpp"
 #include "hip_host.hpp"
+#include "iq_device.hpp"
 #include "noise_device.hpp"
+#include "rate_host.hpp"
 
 using namespace pirip;
 
 namespace {
 
-constexpr int kMaxFs = 1 << 24;            // p, f < 2^24: exact in float and in the 32-bit sums below
 constexpr int kFrameWaves = 4;             // records per workgroup of the framer
 constexpr int kScanThreads = 256;
 constexpr int kModThreads = 256;
@@ -237,26 +238,13 @@ __global__ __launch_bounds__(kScanThreads) void tx_prefix_kernel(ModArgs a)
     if (tid == 0) a.phase[s] = carry;
 }
 
-// (a b) mod Fs for 0 <= a, b <= 2^24: the product is exact in double, the quotient right or one off, the remainder exact
-__device__ __forceinline__ uint32_t mulmod(uint32_t x, uint32_t y, int Fs, double inv_fs)
-{
-    const double p = (double)x * (double)y;
-    const double q = floor(p * inv_fs);
-    double r = fma(-q, (double)Fs, p);
-    if (r < 0.0) r += (double)Fs;
-    if (r >= (double)Fs) r -= (double)Fs;
-    return (uint32_t)r;
-}
-
 // One sample: x = 2 e^{j 2 pi p / Fs} (0 when the carrier is off), plus the noise of (stream, absolute sample)
 __device__ __forceinline__ float2 sample(const ModArgs &a, bool on, uint32_t p, int s, int64_t nabs)
 {
     float xr = 0.f, xi = 0.f;
     if (on) {
-        int32_t pc = (int32_t)p;
-        if (2 * pc > a.Fs) pc -= a.Fs;                       // the angle as a fraction of pi in (-1, 1]
         float sn, cs;
-        sincospif((float)pc * a.two_over_fs, &sn, &cs);
+        unit_phasor((int32_t)p, a.Fs, a.two_over_fs, cs, sn);
         xr = 2 * cs; xi = 2 * sn;
     }
     if (a.sigma > 0.f) add_awgn(a.seed, s, nabs, a.sigma, xr, xi);      // synth_kernels.hip's generator and key
@@ -283,7 +271,7 @@ __global__ __launch_bounds__(kModThreads) void tx_mod_kernel(ModArgs a)
     int r = (int)(first - i * a.Ts);
     int sym = sym_at(a, sy, (int)valid, i);
     uint32_t f = sym < 0 ? 0u : a.fm[(size_t)s * 4 + sym];
-    uint32_t p = pre[i] + mulmod((uint32_t)r, f, a.Fs, a.inv_fs_d);     // the phase after r samples of symbol i
+    uint32_t p = pre[i] + (uint32_t)mulmod_fs((uint32_t)r, f, a.Fs, a.inv_fs_d);     // the phase after r samples of symbol i
     if (p >= Fs) p -= Fs;
     float2 x[SPU];
     const int cnt = (int)(nsamp - first < SPU ? nsamp - first : SPU);
@@ -517,9 +505,9 @@ int pirip_hip_tx_set_tones(pirip_hip_tx *h, const int32_t *f1_hz, int tone_spaci
     std::vector<uint32_t> fm((size_t)h->nstreams * 4, 0), tm((size_t)h->nstreams * 4, 0);
     for (int s = 0; s < h->nstreams; s++)
         for (int m = 0; m < h->M; m++) {
-            const int64_t f = (((int64_t)f1_hz[s] + (int64_t)m * tone_spacing_hz) % h->Fs + h->Fs) % h->Fs;
+            const int64_t f = fs_residue((int64_t)f1_hz[s] + (int64_t)m * tone_spacing_hz, h->Fs);
             fm[(size_t)s * 4 + m] = (uint32_t)f;
-            tm[(size_t)s * 4 + m] = (uint32_t)((f * h->Ts) % h->Fs);
+            tm[(size_t)s * 4 + m] = (uint32_t)fs_step(f, h->Ts, h->Fs);
         }
     PIRIP_HIPCHK(hipDeviceSynchronize());                    // calls in flight still read the old tones
     PIRIP_HIPCHK(hipMemcpy(h->d_fm, fm.data(), sizeof(uint32_t) * fm.size(), hipMemcpyHostToDevice));

@@ -196,22 +196,27 @@ def test_stream_backlog_stays_below_nin_max(oracle, built_lib):
 
 FRONT_ENDS = {
     # u8 IQ at 240 kS/s, /6 -> complex float -> Ts = 40 (rtl_fsk -a 40000 -r 1000)
-    "div6_cf32": (6, False, CFG_TS40, "cf32", dict(CFG_TS40, Fs=240000, P=10), 16, 44),
+    "div6_cf32": (6, False, CFG_TS40, "cf32", dict(CFG_TS40, Fs=240000, P=10), 16, 44, 0.05, None),
     # config 3: u8 IQ at 1.8 MS/s, /45 -> s16 -> Ts = 40 (the README.md:109 pipe)
-    "div45_s16": (45, True, sigutil.CFG3, "s16", dict(sigutil.CFG3, Fs=1800000), 6, 41),
+    "div45_s16": (45, True, sigutil.CFG3, "s16", dict(sigutil.CFG3, Fs=1800000), 6, 41, 0.05, None),
 }
+# The receiver sizes its rows from the decimator's padded filter length Lp, D and output format: the shapes where a wrong one would
+# show. D = 1 (every input sample is an output), and both paddings -- csdr's filter length L is always odd, so Lp == L does not occur:
+# transition_bw 0.05 gives L = 79, Lp = L + 1, and 0.0975 gives L = 41, Lp = L + 3 -- for both output formats; a block of 4096 samples,
+# three pushes.
+FRONT_ENDS.update({f"div1_{fmt}_L{L}": (1, s16, sigutil.CFG1, fmt, sigutil.CFG1, 4, 10, tbw, (4096, 3))
+                   for fmt, s16 in (("cf32", False), ("s16", True)) for tbw, L in ((0.05, 79), (0.0975, 41))})
 
 
 @pytest.mark.parametrize("front", list(FRONT_ENDS))
 def test_stream_front_end_equals_decimator_then_demod(oracle, built_lib, front):
     import torch
     import pirip_amd
-    D, out_s16, c, fmt, tx, nch, frames = FRONT_ENDS[front]
-    dec = pirip_amd.HipDecim(D, out_s16=out_s16)
+    D, out_s16, c, fmt, tx, nch, frames, tbw, fixed = FRONT_ENDS[front]
+    dec = pirip_amd.HipDecim(D, transition_bw=tbw, out_s16=out_s16)
     dem_ref = _demod(c, nch, fmt)
     N = dem_ref.N
-    block = D * (N + 301)
-    K = -(-frames * N // (block // D))
+    block, K = fixed or (D * (N + 301), -(-frames * N // (N + 301)))
     n_raw = K * block
     host = _channels(oracle, c, nch, n_raw, "u8", seed=D, tx_cfg=tx, nbase=2)
     dev = torch.from_numpy(host).cuda()
