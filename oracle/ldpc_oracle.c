@@ -260,8 +260,9 @@ void oracle_ldpc_llr(const LDPC_ORACLE *o, const float *r, float *llr)
         }
         l0 = l0 > lmax ? lmax : (l0 < -lmax ? -lmax : l0);
         l1 = l1 > lmax ? lmax : (l1 < -lmax ? -lmax : l1);
-        llr[bps * i] = oracle_f16_round(l0);
-        if (bps == 2) llr[2 * i + 1] = oracle_f16_round(l1);
+        /* a NaN soft bit (the clamps pass it; inf or NaN magnitudes make one) is an erasure: +0 */
+        llr[bps * i] = l0 == l0 ? oracle_f16_round(l0) : 0.0f;
+        if (bps == 2) llr[2 * i + 1] = l1 == l1 ? oracle_f16_round(l1) : 0.0f;
     }
 }
 
@@ -270,7 +271,8 @@ int oracle_ldpc_decode(const LDPC_ORACLE *o, const float *llr_in, uint8_t *hard,
 {
     float *Q = (float *)malloc(sizeof(float) * (size_t)o->n), *r = (float *)calloc((size_t)o->E, sizeof(float));
     float *llr = (float *)malloc(sizeof(float) * (size_t)o->n);
-    for (int v = 0; v < o->n; v++) llr[v] = oracle_f16_round(llr_in[v]);     /* the decoder's input format is binary16 */
+    /* the decoder's input format is binary16; a NaN is an erasure, +0 (the product's entry does the same: no decoder sees a NaN) */
+    for (int v = 0; v < o->n; v++) llr[v] = llr_in[v] == llr_in[v] ? oracle_f16_round(llr_in[v]) : 0.0f;
     for (int v = 0; v < o->n; v++) Q[v] = llr[v];
     int iter = 0, ok = 0;
     for (int it = 1; it <= o->max_iter; it++) {

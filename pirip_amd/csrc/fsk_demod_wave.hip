@@ -1352,7 +1352,8 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                 l0 = l0 > lmax ? lmax : (l0 < -lmax ? -lmax : l0);
                 l1 = l1 > lmax ? lmax : (l1 < -lmax ? -lmax : l1);
                 // soft bits are handed over as IEEE binary16 (round to nearest even); the hard decisions are the signs of THOSE values
-                const _Float16 h0v = (_Float16)l0, h1v = (_Float16)l1;
+                // (a NaN -- the clamps pass it; frame sums that overflow make one -- is an erasure, +0, as in the LLR stage: no decoder sees a NaN)
+                const _Float16 h0v = (_Float16)(l0 == l0 ? l0 : 0.0f), h1v = (_Float16)(l1 == l1 ? l1 : 0.0f);
                 l0 = (float)h0v; l1 = (float)h1v;
                 uint16_t *llr_o = a.io.soft.llr + (size_t)sid * a.io.soft.llr_stride + a.io.soft.bit0 + (size_t)frame * NBITS;
                 if (act) {

@@ -154,8 +154,11 @@ __global__ __launch_bounds__(kLlrThreads) void llr_tile_kernel(LdpcDev c, const 
         l0 = l0 > lmax ? lmax : (l0 < -lmax ? -lmax : l0);
         l1 = l1 > lmax ? lmax : (l1 < -lmax ? -lmax : l1);
         const bool live = call0 + cl < valid;                                    // no demodulator output for this call: neutral soft bits
-        s_t[cl * 2 * c.Nsym + bps * i] = live ? round16(l0) : 0.0f;          // what is handed over is the binary16 value: signs below follow it
-        if (bps == 2) s_t[cl * 2 * c.Nsym + 2 * i + 1] = live ? round16(l1) : 0.0f;
+        // (the clamps above let a NaN through -- both comparisons are false -- and NaN does arise: an infinite magnitude makes the noise
+        //  term inf - inf, a NaN magnitude every sum of its call. A NaN soft bit is an ERASURE, +0: the decoders never see one -- the
+        //  generic decoder reads "q < 0", the other two q's sign bit, and they would part on a NaN whose sign bit is set)
+        s_t[cl * 2 * c.Nsym + bps * i] = live && l0 == l0 ? round16(l0) : 0.0f;          // what is handed over is the binary16 value: signs below follow it
+        if (bps == 2) s_t[cl * 2 * c.Nsym + 2 * i + 1] = live && l1 == l1 ? round16(l1) : 0.0f;
     };
     if constexpr (REG) {
 #pragma unroll
@@ -337,11 +340,11 @@ __global__ void hist_prepare_kernel(int bpf, const h16 *llr_hist, h16 *llr_all, 
     }
 }
 
-// stand-alone decode entry: caller's float LLRs into the decoder's input format
+// stand-alone decode entry: caller's float LLRs into the decoder's input format; a NaN is an erasure (+0), as in the LLR stage
 __global__ void f32_to_h16_kernel(const float *src, h16 *dst, size_t n)
 {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) dst[i] = f2h(src[i]);
+    if (i < n) { const float x = src[i]; dst[i] = f2h(x == x ? x : 0.0f); }
 }
 
 __global__ void save_hist_kernel(const h16 *llr_all, size_t llr_stride, int ncalls, const int32_t *ncalls_s, int Nbits, int bpf, h16 *llr_hist)

@@ -396,27 +396,7 @@ def test_unique_word_search_under_awkward_call_sizes(oracle, built_lib, M, Nsym)
     assert ((ws & RX_BITS) != 0).sum() >= 2
 
 
-def _write_random_code(path, n, k, wcol, seed, max_iter=15):
-    """A small repeat-accumulate code in the code-file format (not a good code: a different SHAPE for the decoder's
-    run-time paths -- row degrees above and below the register fast path, a frame length that is not a multiple of 32)."""
-    rng = np.random.default_rng(seed)
-    m = n - k
-    rows = [[] for _ in range(m)]
-    for c in range(k):
-        order = sorted(range(m), key=lambda r: (len(rows[r]), rng.random()))      # least-loaded rows first: balanced degrees
-        for r in order[:wcol]:
-            rows[r].append(c)
-    for p in range(m):
-        if p:
-            rows[p].append(k + p - 1)
-        rows[p].append(k + p)
-    with open(path, "w") as f:
-        f.write("# test code\nname TEST_%d_%d\nn %d\nk %d\nmax_iter %d\n" % (k, n, n, k, max_iter))
-        f.write("uw " + " ".join(str((0x1ACFFC1D >> (31 - i)) & 1) for i in range(32)) + "\n")
-        f.write("uw_thresh1 4\nuw_thresh2 6\nbad_uw_thresh 1\nrows %d\n" % m)
-        for r in rows:
-            f.write(" ".join(str(c) for c in sorted(r)) + "\n")
-    return max(len(r) for r in rows)
+from ldpcshapes import _write_random_code      # the repeat-accumulate code writer, shared with test_ldpc_decoders.py
 
 
 @pytest.mark.gpu
