@@ -450,6 +450,8 @@ def test_other_code_shapes_take_the_generic_paths(oracle, built_lib, tmp_path, m
     (40000, 1000, 2, 10, "cf32", 0, True),         # the services' modem (script/ping:47, script/frame_repeater:36)
     (100000, 10000, 2, 10, "cf32tiny", 0, True),   # the same shape at 1e-17 of the amplitude: |f|^2 below 2^-96, the hand-over's sqrtf / IEEE-quotient path
     (240000, 10000, 2, 12, "u8d", 0, False),       # no wave instance: magnitudes through the work buffer, same records
+    (240000, 1000, 2, 15, "csdr", 0, False),       # rtl_fsk -r 1000 --code: the block instance, not soft-capable -- the unfused route as well
+    (240000, 1000, 4, 15, "u8d", 2000, False),     # ... 4-FSK with the mask estimator, `-d` format
     (240000, 10000, 4, 8, "u8d", 0, True, "rician"),     # the same two shapes with the code file's llr_map key set to the exact
     (240000, 10000, 2, 6, "csdr", 0, True, "rician"),    # Rician mapping (every other row: the default, codec2's as recalled)
 ], ids=lambda s: "Fs%d-M%d-P%d-%s-mask%d%s" % (s[0], s[2], s[3], s[4], s[5], "-" + s[7] if len(s) > 7 else ""))
