@@ -594,6 +594,55 @@ int pirip_hip_mux_batch(pirip_hip_mux *mux, const void *d_in, size_t in_stride_b
                         void *d_out, size_t out_stride_bytes, void *hip_stream);
 
 /* ----------------------------------------------------------------------------------- */
+/* section K : streaming transmitter (queued records to wideband IQ, block after block) */
+/*   Section G's mirror image. Composes a transmitter (section I: code, framer, tones,   */
+/*   gap) and a multiplexer (section J: taps, offsets, gains, outputs, format): every     */
+/*   channel has a queue of channel symbols on the device, and one call turns the next    */
+/*   block of every queue into wideband samples. No modem-rate IQ is written: the         */
+/*   multiplexer's staging computes each modem sample from its symbol and the exact       */
+/*   integer phase.                                                      */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_txs pirip_hip_txs;
+typedef struct pirip_txs_info {
+    int64_t block, queue_syms;
+    int S, H, nchan, noutputs, out_format, device;
+} pirip_txs_info;
+/* tx and mux are borrowed and must outlive the handle. PIRIP_ERR_BAD_ARG unless tx's nstreams == mux's nchan, tx's Fs * mux's D == mux's
+ * Fs and both are on the same device. block: wideband samples per output per call, a positive multiple of D * Ts (else PIRIP_ERR_BAD_ARG):
+ * every call sends S = block / (D * Ts) whole symbols per channel. queue_syms: each channel's queue capacity in symbols, used as given,
+ * at least S (else PIRIP_ERR_BAD_ARG). H = ceil((Q - 1) / Ts) symbols of history are kept per channel (0 when Q = 1).
+ * PIRIP_ERR_UNSUPPORTED when (H + S) Ts + Q + 2304 does not fit 31 bits. The handle keeps its own per-channel phase and symbol history: it never
+ * touches tx's carried phase or sample count, and calls on tx in between change nothing here. Tones and gaps are read from tx when a call
+ * runs. Create synchronises the device. */
+int pirip_hip_txs_create(pirip_hip_tx *tx, pirip_hip_mux *mux, int64_t block, int64_t queue_syms, pirip_hip_txs **out);
+int pirip_hip_txs_destroy(pirip_hip_txs *txs);
+int pirip_hip_txs_get_info(const pirip_hip_txs *txs, pirip_txs_info *info);
+/* Channel s: d_nrec[s] (NULL = max_rec; clamped to [0, max_rec]) records at d_records + s * rec_stride, exactly what pirip_hip_tx_frame
+ * reads (burst control 1 / 0 / 2 / other, CRC, UW, parity, and tx's gap for a `2`). tx's lead is NOT applied: a streaming transmitter's
+ * silence is its empty queue. Per channel all or nothing: if the symbols of this call's records fit the queue's free space they are
+ * appended in order and d_taken[s] is the record count; otherwise nothing is appended, d_taken[s] = 0 and the channel's refused count goes
+ * up. d_taken may be NULL. Enqueued on hip_stream (NULL = default stream); does not synchronise, except that a call with a larger
+ * max_rec than any before it grows the handle's work rows, as in section I. */
+int pirip_hip_txs_send(pirip_hip_txs *txs, const uint8_t *d_records, size_t rec_stride, const int32_t *d_nrec, int max_rec, int32_t *d_taken,
+                       void *hip_stream);
+/* Every channel dequeues up to S symbols; the rest of the block is carrier off (the phase does not move, as in section I). Output i gets
+ * block samples of mux's out_format at (char*)d_out + i * out_stride_bytes, aligned as pirip_hip_mux_batch asks (to the sample; 16-byte
+ * aligned rows get 16-byte stores; rows of several outputs must not overlap). d_sent[s] (may be NULL): symbols dequeued. Enqueued on
+ * hip_stream; never synchronises.
+ * Contract: let each channel's symbol timeline be what the calls dequeued, call after call, with carrier off where nothing was queued. The
+ * concatenation of all outputs since create / reset equals, byte for byte, pirip_hip_tx_modulate(..., PIRIP_IN_CF32, sigma = 0) on a fresh
+ * handle over that timeline followed by pirip_hip_mux_batch on those rows with Q - 1 zero samples in front and m0 = -(Q - 1): wideband
+ * sample 0 is modem sample 0. This holds for every block, every interleaving of send and process, and after reset. */
+int pirip_hip_txs_process(pirip_hip_txs *txs, void *d_out, size_t out_stride_bytes, int32_t *d_sent, void *hip_stream);
+/* Host copies (synchronises the device), per channel [nchan], each may be NULL: symbols queued now, symbols sent since create / reset,
+ * underrun symbols (carrier off because the queue was empty), refused sends. */
+int pirip_hip_txs_get_counters(pirip_hip_txs *txs, int64_t *queued, int64_t *sent, int64_t *underrun, int64_t *refused);
+/* Empties the queues and clears phases, history, counters and the sample index: the next call is the first after create. */
+int pirip_hip_txs_reset(pirip_hip_txs *txs, void *hip_stream);
+/* One HIP stream per handle: queues, phases and history are device state advanced in stream order, the sample index is host state advanced
+ * when a call is enqueued. */
+
+/* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */
 /*             names and signatures as codec2 src/fsk.h [UPSTREAM-RECALLED]              */
 /* ----------------------------------------------------------------------------------- */

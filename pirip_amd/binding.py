@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I and J).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J and K).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -47,6 +47,11 @@ class MuxInfo(C.Structure):
 class TxInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("Fs", "Rs", "M", "Ts", "n", "k", "bits_per_frame", "data_bytes", "preamble_syms", "frame_syms",
                                        "nstreams", "device")]
+
+
+class TxsInfo(C.Structure):
+    _fields_ = [("block", C.c_int64), ("queue_syms", C.c_int64)] + \
+               [(n, C.c_int) for n in ("S", "H", "nchan", "noutputs", "out_format", "device")]
 
 
 class LdpcInfo(C.Structure):
@@ -165,6 +170,13 @@ def lib():
     L.pirip_hip_mux_nout.restype = i64
     L.pirip_hip_mux_nout.argtypes = [vp, i64]
     L.pirip_hip_mux_batch.argtypes = [vp, vp, sz, i64, i64, vp, sz, vp]
+    L.pirip_hip_txs_create.argtypes = [vp, vp, i64, i64, C.POINTER(vp)]
+    L.pirip_hip_txs_destroy.argtypes = [vp]
+    L.pirip_hip_txs_get_info.argtypes = [vp, C.POINTER(TxsInfo)]
+    L.pirip_hip_txs_send.argtypes = [vp, vp, sz, vp, i32, vp, vp]
+    L.pirip_hip_txs_process.argtypes = [vp, vp, sz, vp, vp]
+    L.pirip_hip_txs_get_counters.argtypes = [vp, vp, vp, vp, vp]
+    L.pirip_hip_txs_reset.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -562,6 +574,50 @@ class HipMux:
         """channel c at d_in + c * in_stride (n_in complex floats, the first at absolute index m0) -> output i at d_out + i * out_stride
         (nout(n_in) samples, the first at absolute index (m0 + Q - 1) D); raw device pointers, enqueued on `stream`, does not synchronise"""
         _chk(self.L.pirip_hip_mux_batch(self.h, d_in, in_stride, int(n_in), int(m0), d_out, out_stride, stream), "pirip_hip_mux_batch")
+
+
+class HipTxStream:
+    """Streaming transmitter (include/pirip_hip.h section K): every channel of HipTx `tx` has a symbol queue on the device, and each
+    process() turns the next S = block / (D Ts) symbols of every queue into `block` wideband samples per output of HipMux `mux`, with no
+    modem-rate IQ in between. queue_syms: each queue's capacity in symbols (>= S). Both handles must outlive the stream."""
+
+    def __init__(self, tx, mux, block, queue_syms):
+        self.L = lib()
+        self.tx, self.mux = tx, mux
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_txs_create(tx.h, mux.h, int(block), int(queue_syms), C.byref(h)), "pirip_hip_txs_create")
+        self.h = h
+        self.info = TxsInfo()
+        _chk(self.L.pirip_hip_txs_get_info(self.h, C.byref(self.info)), "pirip_hip_txs_get_info")
+        self.block, self.queue_syms, self.S, self.H = self.info.block, self.info.queue_syms, self.info.S, self.info.H
+        self.nchan, self.noutputs, self.bytes_per_sample = self.info.nchan, self.info.noutputs, mux.bytes_per_sample
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_txs_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def send(self, d_records, rec_stride, max_rec, d_nrec=0, d_taken=0, stream=0):
+        """offer every channel its records (HipTx.frame's format); per channel all or nothing, d_taken[s] = records taken. Raw device
+        pointers, enqueued on `stream`."""
+        _chk(self.L.pirip_hip_txs_send(self.h, d_records, rec_stride, d_nrec, int(max_rec), d_taken, stream), "pirip_hip_txs_send")
+
+    def process(self, d_out, out_stride, d_sent=0, stream=0):
+        """one block: output i gets `block` samples at d_out + i * out_stride; d_sent[s] = symbols dequeued. Does not synchronise."""
+        _chk(self.L.pirip_hip_txs_process(self.h, d_out, out_stride, d_sent, stream), "pirip_hip_txs_process")
+
+    def counters(self):
+        """dict of int64[nchan]: queued, sent, underrun, refused -- synchronises."""
+        import numpy as np
+        out = {k: np.zeros(self.nchan, dtype=np.int64) for k in ("queued", "sent", "underrun", "refused")}
+        _chk(self.L.pirip_hip_txs_get_counters(self.h, *(out[k].ctypes.data for k in ("queued", "sent", "underrun", "refused"))),
+             "pirip_hip_txs_get_counters")
+        return out
+
+    def reset(self, stream=0):
+        _chk(self.L.pirip_hip_txs_reset(self.h, stream), "pirip_hip_txs_reset")
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

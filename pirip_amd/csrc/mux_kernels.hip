@@ -8,7 +8,7 @@
 // (iq_device.hpp). Then w_i[mD + p] = sum_c sum_q g_c[p + qD] z'_c[m - q], with no transcendental at the wideband rate; any split of a
 // row into calls that overlap by Q - 1 input samples gives the one-shot output bit for bit.
 //
-// Kernel: one workgroup per (tile of kTile = 2048 outputs, output). The channels of the output are taken in groups of at most kMaxGroup
+// Kernel: one workgroup per (tile of kMuxTile = 2048 outputs, output). The channels of the output are taken in groups of at most kMuxMaxGroup
 // (fewer when LDS says so), ascending; per group the workgroup stages the modulated taps and the tile's input span of every channel of the
 // group in LDS, the samples already rotated, and then every thread adds the group to its 8 accumulators: thread t owns the outputs
 // k * 256 + t of the tile, so the lanes of a wave always cover 64 consecutive outputs. (m, p) of a thread's first output is one division
@@ -34,136 +34,32 @@
 #include "fsk_plan.hpp"
 #include "hip_host.hpp"
 #include "iq_device.hpp"
+#include "mux_handle.hpp"
 #include "rate_host.hpp"
 
 using namespace pirip;
 
 namespace {
 
-constexpr int kThreads = 256;
-constexpr int kPerThread = 8;              // outputs per thread and tile (accumulator pairs)
-constexpr int kTile = kThreads * kPerThread;
-constexpr int kMaxGroup = 8;               // channels staged together
-constexpr size_t kLdsMax = 64 * 1024;
-
-struct MuxArgs {
-    const char *in; size_t in_stride; int64_t n_in, n_out;
-    char *out; size_t out_stride;
-    const v2f *taps;                       // [nchan][Q][Dp] g_c, each row of D followed by its first Dp - D entries
-    const int32_t *out_start;              // [noutputs + 1]: the channels of output i are out_ch[out_start[i] .. out_start[i + 1])
-    const int32_t *out_ch;                 // [nchan] channel indices, ascending within an output
-    const int32_t *sc;                     // [nchan] (f_c mod Fs) D mod Fs
-    int Fs, D, Dp, Q, Mt, G, aligned16;
-    int step_m, step_p;                    // 256 div D, 256 mod D
-    int32_t m0m;                           // m0 mod Fs
-    float two_over_fs;
-    double inv_fs_d;
+// the multiplexer proper: a channel's samples are read from its modem-rate row
+struct LoadStage {
+    const char *in; size_t in_stride; int64_t n_in;
+    struct Cursor {};
+    __device__ __forceinline__ Cursor begin(int64_t, int) const { return Cursor{}; }
+    __device__ __forceinline__ void next(Cursor &) const {}
+    __device__ __forceinline__ float2 sample(int ch, const Cursor &, int64_t at) const
+    {
+        float2 v = make_float2(0.f, 0.f);
+        if (at < n_in) v = ((const float2 *)(in + (size_t)ch * in_stride))[at];
+        return v;
+    }
 };
 
-// BS: bytes per output sample, 2 (u8 IQ) or 8 (complex float)
 template <int BS>
-__global__ __launch_bounds__(kThreads) void mux_kernel(MuxArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    char *s_out = smem;                                                 // [kTile] samples as they are stored
-    v2f *s_g = (v2f *)(smem + (size_t)kTile * BS);                      // [G][Q * Dp]
-    const int tapsz = a.Q * a.Dp;
-    v2f *s_z = s_g + (size_t)a.G * tapsz;                               // [G][Mt]
-    const int tid = threadIdx.x;
-    const int i = blockIdx.y;
-    const int64_t j0 = (int64_t)blockIdx.x * kTile;                     // first output of the tile (of this call)
-    const int cnt = (int)((a.n_out - j0) < kTile ? (a.n_out - j0) : kTile);
-    // output j of the call is absolute n = (m0 + Q - 1) D + j: p = j mod D, and its newest input sample is input Q - 1 + j div D of the call
-    const int64_t a0 = j0 / a.D;
-    const int p0 = (int)(j0 - a0 * a.D);
-    const int mt = (p0 + cnt - 1) / a.D + a.Q;                          // input samples of the tile, from input a0 of the call on
-    const int32_t base = (int32_t)(((int64_t)a.m0m + a0 % a.Fs) % a.Fs);
-    const int m_first = (p0 + tid) / a.D, p_first = (p0 + tid) - m_first * a.D;
-    const int lane32 = tid & 31;
-    v2f acc[kPerThread];
-#pragma unroll
-    for (int k = 0; k < kPerThread; k++) acc[k] = v2f{0.f, 0.f};
-
-    const int c0 = a.out_start[i], c1 = a.out_start[i + 1];
-    for (int cb = c0; cb < c1; cb += a.G) {
-        const int ng = c1 - cb < a.G ? c1 - cb : a.G;
-        if (cb > c0) __syncthreads();
-        for (int m = 0; m < ng; m++) {
-            const int ch = a.out_ch[cb + m];
-            const v2f *g = a.taps + (size_t)ch * tapsz;
-            for (int e = tid; e < tapsz; e += kThreads) s_g[(size_t)m * tapsz + e] = g[e];
-            const float2 *z = (const float2 *)(a.in + (size_t)ch * a.in_stride);
-            const int32_t s = a.sc[ch];
-            for (int r = tid; r < mt; r += kThreads) {
-                float2 v = make_float2(0.f, 0.f);
-                if (a0 + r < a.n_in) v = z[a0 + r];
-                const int32_t idx = (int32_t)(((uint32_t)base + (uint32_t)r) % (uint32_t)a.Fs);
-                float sn, cs;
-                unit_phasor((int32_t)mulmod_fs(s, idx, a.Fs, a.inv_fs_d), a.Fs, a.two_over_fs, cs, sn);
-                s_z[(size_t)m * a.Mt + r] = crot(v2f{v.x, v.y}, cs, sn);
-            }
-        }
-        __syncthreads();
-        int mm = m_first, pp = p_first;
-#pragma unroll
-        for (int k = 0; k < kPerThread; k++) {
-            if (k * kThreads + tid < cnt) {
-                const int e = (a.Dp != a.D && pp < lane32) ? pp + a.D : pp;
-                for (int m = 0; m < ng; m++) {
-                    const v2f *g = s_g + (size_t)m * tapsz + e;
-                    const v2f *z = s_z + (size_t)m * a.Mt + mm + a.Q - 1;
-                    v2f u = {0.f, 0.f};
-                    for (int q = 0; q < a.Q; q++, g += a.Dp, z--) {
-                        const v2f gg = *g, zz = *z;
-                        u = __builtin_elementwise_fma(v2f{zz.x, zz.x}, gg, u);
-                        u = __builtin_elementwise_fma(v2f{zz.y, zz.y}, v2f{-gg.y, gg.x}, u);
-                    }
-                    acc[k] += u;
-                }
-            }
-            pp += a.step_p; mm += a.step_m;
-            if (pp >= a.D) { pp -= a.D; mm++; }
-        }
-    }
-
-    // the tile as it is stored, through LDS: thread t holds outputs k * 256 + t, and stores 16 consecutive bytes
-#pragma unroll
-    for (int k = 0; k < kPerThread; k++) {
-        const int n = k * kThreads + tid;
-        if (BS == 2) ((uint16_t *)s_out)[n] = (uint16_t)((uint32_t)quant_u8_csdr(acc[k].x) | ((uint32_t)quant_u8_csdr(acc[k].y) << 8));
-        else ((v2f *)s_out)[n] = acc[k];
-    }
-    __syncthreads();
-    constexpr int SPU = 16 / BS;                                        // samples per 16-byte unit
-    char *row = a.out + (size_t)i * a.out_stride + (size_t)j0 * BS;
-    for (int u = tid; u * SPU < cnt; u += kThreads) {
-        const int first = u * SPU;
-        if (a.aligned16 && first + SPU <= cnt) {
-            *(uint4 *)(row + (size_t)u * 16) = *(const uint4 *)(s_out + (size_t)u * 16);
-        } else {
-            for (int n = first; n < first + SPU && n < cnt; n++) {
-                if (BS == 2) ((uint16_t *)row)[n] = ((const uint16_t *)s_out)[n];
-                else ((float2 *)row)[n] = ((const float2 *)s_out)[n];
-            }
-        }
-    }
-}
-
-}  // namespace
-
-struct pirip_hip_mux {
-    int Fs = 0, D = 0, kind = 0, L = 0, Q = 0, Dp = 0, Mt = 0, G = 0, out_format = 0, bs = 0, device = 0, noutputs = 0, nchan = 0;
-    size_t lds = 0;
-    std::vector<float> h;                  // prototype taps (L)
-    DevMem mem;
-    v2f *d_taps = nullptr;
-    int32_t *d_out_start = nullptr, *d_out_ch = nullptr, *d_sc = nullptr;
-};
-
-namespace {
+__global__ __launch_bounds__(kMuxThreads) void mux_kernel(MuxArgs a, LoadStage st) { mux_tile<BS>(a, st); }
 
 // LDS bytes of a workgroup that stages G channels: the tile as stored, G tap tables, G input spans
-size_t mux_lds(int G, int bs, int Q, int Dp, int Mt) { return (size_t)kTile * bs + (size_t)G * ((size_t)Q * Dp + Mt) * sizeof(v2f); }
+size_t mux_lds(int G, int bs, int Q, int Dp, int Mt) { return (size_t)kMuxTile * bs + (size_t)G * ((size_t)Q * Dp + Mt) * sizeof(v2f); }
 
 }  // namespace
 
@@ -183,10 +79,10 @@ int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_b
     if (Fs > kMaxFs || noutputs > 65535) return PIRIP_ERR_UNSUPPORTED;
     const int D = interpolation;
     const int64_t L64 = kind == PIRIP_MUX_FIR ? (int64_t)csdr_filter_len(transition_bw) : 2 * (int64_t)D - 1;
-    const int64_t Q64 = (L64 + D - 1) / D, Dp64 = D > 32 ? (int64_t)D + 31 : D, Mt64 = ((int64_t)D + kTile - 2) / D + Q64;
+    const int64_t Q64 = (L64 + D - 1) / D, Dp64 = D > 32 ? (int64_t)D + 31 : D, Mt64 = ((int64_t)D + kMuxTile - 2) / D + Q64;
     const int bs = out_format == PIRIP_IN_CF32 ? 8 : 2;
     // the working set of one channel must fit the LDS of a workgroup (the header's rule)
-    if (L64 < 1 || (Q64 * Dp64 + Mt64) * (int64_t)sizeof(v2f) + (int64_t)kTile * bs > (int64_t)kLdsMax) return PIRIP_ERR_UNSUPPORTED;
+    if (L64 < 1 || (Q64 * Dp64 + Mt64) * (int64_t)sizeof(v2f) + (int64_t)kMuxTile * bs > (int64_t)kMuxLdsMax) return PIRIP_ERR_UNSUPPORTED;
     int dev = 0;
     PIRIP_TRY(select_device(device, &dev));
     pirip_hip_mux *mx = new (std::nothrow) pirip_hip_mux();
@@ -202,8 +98,8 @@ int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_b
         mx->h.resize((size_t)mx->L);
         for (int i = 0; i < mx->L; i++) mx->h[(size_t)i] = (float)(1.0 - std::fabs((double)(i - (D - 1))) / (double)D);
     }
-    mx->G = kMaxGroup;
-    while (mx->G > 1 && mux_lds(mx->G, bs, mx->Q, mx->Dp, mx->Mt) > kLdsMax) mx->G--;
+    mx->G = kMuxMaxGroup;
+    while (mx->G > 1 && mux_lds(mx->G, bs, mx->Q, mx->Dp, mx->Mt) > kMuxLdsMax) mx->G--;
     mx->lds = mux_lds(mx->G, bs, mx->Q, mx->Dp, mx->Mt);
     // the channels of every output, ascending
     std::vector<int32_t> out_start(1, 0), out_ch;
@@ -280,21 +176,15 @@ int pirip_hip_mux_batch(pirip_hip_mux *mx, const void *d_in, size_t in_stride_by
     if (n_out <= 0) return PIRIP_OK;
     if (mx->noutputs > 1 && out_stride_bytes < (size_t)n_out * mx->bs) return PIRIP_ERR_BAD_ARG;   // rows would overlap
     if (!bind_device(mx->device)) return PIRIP_ERR_NO_DEVICE;
-    const int64_t ntiles = (n_out + kTile - 1) / kTile;
+    const int64_t ntiles = (n_out + kMuxTile - 1) / kMuxTile;
     if (ntiles > 0x7fffffff) return PIRIP_ERR_UNSUPPORTED;
     MuxArgs a{};
-    a.in = (const char *)d_in; a.in_stride = in_stride_bytes; a.n_in = n_in; a.n_out = n_out;
-    a.out = (char *)d_out; a.out_stride = out_stride_bytes;
-    a.taps = mx->d_taps; a.out_start = mx->d_out_start; a.out_ch = mx->d_out_ch; a.sc = mx->d_sc;
-    a.Fs = mx->Fs; a.D = mx->D; a.Dp = mx->Dp; a.Q = mx->Q; a.Mt = mx->Mt; a.G = mx->G;
-    a.aligned16 = (((uintptr_t)d_out | out_stride_bytes) & 15) == 0;
-    a.step_m = kThreads / mx->D; a.step_p = kThreads % mx->D;
-    a.m0m = (int32_t)fs_residue(m0, mx->Fs);
-    a.two_over_fs = 2.0f / (float)mx->Fs; a.inv_fs_d = 1.0 / (double)mx->Fs;
+    mux_fill_args(mx, n_out, m0, d_out, out_stride_bytes, &a);
+    const LoadStage ld{(const char *)d_in, in_stride_bytes, n_in};
     const dim3 grid((unsigned)ntiles, (unsigned)mx->noutputs);
     hipStream_t st = (hipStream_t)hip_stream;
-    if (mx->bs == 2) hipLaunchKernelGGL(mux_kernel<2>, grid, dim3(kThreads), mx->lds, st, a);
-    else hipLaunchKernelGGL(mux_kernel<8>, grid, dim3(kThreads), mx->lds, st, a);
+    if (mx->bs == 2) hipLaunchKernelGGL(mux_kernel<2>, grid, dim3(kMuxThreads), mx->lds, st, a, ld);
+    else hipLaunchKernelGGL(mux_kernel<8>, grid, dim3(kMuxThreads), mx->lds, st, a, ld);
     return hipGetLastError() == hipSuccess ? PIRIP_OK : PIRIP_ERR_HIP;
 }
 

@@ -37,13 +37,13 @@
 #include "iq_device.hpp"
 #include "noise_device.hpp"
 #include "rate_host.hpp"
+#include "tx_handle.hpp"
 
 using namespace pirip;
 
 namespace {
 
 constexpr int kFrameWaves = 4;             // records per workgroup of the framer
-constexpr int kScanThreads = 256;
 constexpr int kModThreads = 256;
 constexpr uint8_t kOff = 0xFF;             // carrier off
 
@@ -209,33 +209,13 @@ __device__ __forceinline__ int sym_at(const ModArgs &a, const uint8_t *sy, int v
 __global__ __launch_bounds__(kScanThreads) void tx_prefix_kernel(ModArgs a)
 {
     __shared__ uint32_t s_tot[kScanThreads / 64];
-    const int s = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int s = blockIdx.x;
     const uint8_t *sy = a.syms + (size_t)s * a.sym_stride;
     int64_t valid = a.nsym ? a.nsym[s] : a.total;
     if (valid > a.total) valid = a.total;
-    const uint32_t Fs = (uint32_t)a.Fs;
-    uint32_t tm[4];
-    for (int m = 0; m < 4; m++) tm[m] = a.tm[(size_t)s * 4 + m];
-    uint32_t carry = a.phase[s];
-    uint32_t *pre = a.prefix + (size_t)s * (size_t)a.total;
-    for (int64_t base = 0; base < a.total; base += kScanThreads) {
-        const int64_t i = base + tid;
-        const int sym = i < a.total ? sym_at(a, sy, (int)valid, i) : -1;
-        const uint32_t v = sym < 0 ? 0u : tm[sym];
-        uint32_t incl = v;                                   // < 64 * 2^24
-        for (int d = 1; d < 64; d <<= 1) {
-            const uint32_t up = __shfl_up(incl, d, 64);
-            if (lane >= d) incl += up;
-        }
-        if (lane == 63) s_tot[wave] = incl % Fs;
-        __syncthreads();
-        uint32_t before = carry, all = carry;                // carry + the waves in front: < 5 * 2^24
-        for (int w = 0; w < kScanThreads / 64; w++) { if (w < wave) before += s_tot[w]; all += s_tot[w]; }
-        if (i < a.total) pre[i] = (before + (incl - v)) % Fs;
-        carry = all % Fs;
-        __syncthreads();
-    }
-    if (tid == 0) a.phase[s] = carry;
+    const uint32_t carry = tx_scan_row([&](int64_t i) { return sym_at(a, sy, (int)valid, i); }, a.total, a.tm + (size_t)s * 4, (uint32_t)a.Fs,
+                                       a.phase[s], a.prefix + (size_t)s * (size_t)a.total, s_tot);
+    if (threadIdx.x == 0) a.phase[s] = carry;
 }
 
 // One sample: x = 2 e^{j 2 pi p / Fs} (0 when the carrier is off), plus the noise of (stream, absolute sample)
@@ -403,23 +383,6 @@ __global__ __launch_bounds__(64) void tx_repeat_kernel(RepeatArgs a)
 
 }  // namespace
 
-struct pirip_hip_tx {
-    LdpcCode code;
-    int Fs = 0, Rs = 0, M = 0, Ts = 0, bps = 1, nstreams = 0, device = 0;
-    int pre_bits = 0;
-    int64_t samples_sent = 0;              // per stream since create / reset (every stream sends the same count per call)
-    int max_lead = 0, max_gap = 0;
-    DevMem mem;
-    int32_t *d_row_ptr = nullptr, *d_col_idx = nullptr, *d_lead = nullptr, *d_gap = nullptr, *d_nsym = nullptr;
-    uint32_t *d_fm = nullptr, *d_tm = nullptr, *d_phase = nullptr;
-    // work buffers, grown on demand
-    int32_t *d_off = nullptr; size_t off_cap = 0;
-    uint32_t *d_prefix = nullptr; size_t prefix_cap = 0;
-    uint8_t *d_syms = nullptr; size_t syms_cap = 0;
-    // record conversion (the repeater): per stream {receiving, frames held} and the held frames, made on first use
-    int32_t *d_rep_state = nullptr; uint8_t *d_rep_held = nullptr;
-};
-
 namespace {
 
 // a work buffer of `want` elements at least; calls in flight may still use the one it replaces
@@ -453,6 +416,46 @@ int tx_alloc(pirip_hip_tx *h)
 }
 
 }  // namespace
+
+// symbols a row of max_rec records can need behind max_lead symbols of lead
+int64_t pirip::tx_row_syms(const pirip_hip_tx *h, int max_rec, int max_lead)
+{
+    const int64_t per_frame = (h->pre_bits + h->code.bits_per_frame()) / h->bps;
+    return (int64_t)max_lead + (int64_t)max_rec * (per_frame > h->max_gap ? per_frame : (int64_t)h->max_gap);
+}
+
+// what stage 1 asks of its rows, before anything touches the device
+int pirip::tx_frame_check(const pirip_hip_tx *h, size_t rec_stride, int max_rec, size_t sym_stride, int64_t max_syms, bool bits, size_t bits_stride)
+{
+    if (sym_stride < (size_t)max_syms || (bits && bits_stride < (size_t)max_syms * h->bps)) return PIRIP_ERR_BAD_ARG;
+    if (rec_stride < (size_t)max_rec * (size_t)(1 + h->code.data_bytes())) return PIRIP_ERR_BAD_ARG;
+    if (max_syms > 0x7fffffff || (max_rec + kFrameWaves - 1) / kFrameWaves > 65535 || h->nstreams > 65535) return PIRIP_ERR_UNSUPPORTED;
+    return PIRIP_OK;
+}
+
+// Stage 1 on rows, leads and a record-offset table ([nstreams][max_rec]) of the caller's, checked by tx_frame_check; the handle's device is current
+int pirip::tx_frame_rows(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_stride, const int32_t *d_nrec, int max_rec,
+                         uint8_t *d_syms, size_t sym_stride, int64_t max_syms, int32_t *d_nsym, uint8_t *d_bits, size_t bits_stride,
+                         const int32_t *d_lead, int32_t *d_off, hipStream_t st)
+{
+    FrameArgs a{};
+    a.rec = d_records; a.rec_stride = rec_stride; a.nrec = d_nrec; a.max_rec = max_rec; a.off = d_off;
+    a.syms = d_syms; a.sym_stride = sym_stride; a.max_syms = max_syms; a.nsym = d_nsym;
+    a.bits = d_bits; a.bits_stride = bits_stride;
+    a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.lead = d_lead; a.gap = h->d_gap;
+    a.uw = 0;
+    for (int i = 0; i < kUwBits; i++) a.uw |= (uint32_t)(h->code.uw[i] & 1) << (31 - i);
+    a.k = h->code.k; a.m = h->code.m; a.kb = h->code.data_bytes(); a.bpf = h->code.bits_per_frame(); a.bps = h->bps;
+    a.pre_bits = h->pre_bits; a.nstreams = h->nstreams;
+    a.frame_lds = (a.bpf + 15) & ~15;
+    a.wave_lds = a.frame_lds + ((a.kb + 15) & ~15);
+    hipLaunchKernelGGL(tx_layout_kernel, dim3((unsigned)h->nstreams), dim3(64), 0, st, a);
+    if (max_rec > 0)
+        hipLaunchKernelGGL(tx_frame_kernel, dim3((unsigned)((max_rec + kFrameWaves - 1) / kFrameWaves), (unsigned)h->nstreams), dim3(kFrameWaves * 64),
+                           (size_t)kFrameWaves * a.wave_lds, st, a);
+    PIRIP_HIPCHK(hipGetLastError());
+    return PIRIP_OK;
+}
 
 extern "C" {
 
@@ -546,8 +549,7 @@ int pirip_hip_tx_reset(pirip_hip_tx *h, void *hip_stream)
 int64_t pirip_hip_tx_max_syms(const pirip_hip_tx *h, int max_rec)
 {
     if (!h || max_rec < 0) return 0;
-    const int64_t per_frame = (h->pre_bits + h->code.bits_per_frame()) / h->bps;
-    return (int64_t)h->max_lead + (int64_t)max_rec * (per_frame > h->max_gap ? per_frame : (int64_t)h->max_gap);
+    return tx_row_syms(h, max_rec, h->max_lead);
 }
 
 int pirip_hip_tx_frame(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_stride, const int32_t *d_nrec, int max_rec,
@@ -555,31 +557,13 @@ int pirip_hip_tx_frame(pirip_hip_tx *h, const uint8_t *d_records, size_t rec_str
                        void *hip_stream)
 {
     if (!h || !d_records || !d_syms || max_rec < 0 || max_syms < 0) return PIRIP_ERR_BAD_ARG;
-    const int64_t need = pirip_hip_tx_max_syms(h, max_rec);
-    if (max_syms < need || sym_stride < (size_t)max_syms || (d_bits && bits_stride < (size_t)max_syms * h->bps)) return PIRIP_ERR_BAD_ARG;
-    if (rec_stride < (size_t)max_rec * (size_t)(1 + h->code.data_bytes())) return PIRIP_ERR_BAD_ARG;
-    if (max_syms > 0x7fffffff || (max_rec + kFrameWaves - 1) / kFrameWaves > 65535 || h->nstreams > 65535) return PIRIP_ERR_UNSUPPORTED;
+    if (max_syms < pirip_hip_tx_max_syms(h, max_rec)) return PIRIP_ERR_BAD_ARG;
+    PIRIP_TRY(tx_frame_check(h, rec_stride, max_rec, sym_stride, max_syms, d_bits != nullptr, bits_stride));
     if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     const int rc = tx_grow(h, &h->d_off, &h->off_cap, (size_t)h->nstreams * (size_t)(max_rec > 0 ? max_rec : 1));
     if (rc != PIRIP_OK) return rc;
-    FrameArgs a{};
-    a.rec = d_records; a.rec_stride = rec_stride; a.nrec = d_nrec; a.max_rec = max_rec; a.off = h->d_off;
-    a.syms = d_syms; a.sym_stride = sym_stride; a.max_syms = max_syms; a.nsym = d_nsym ? d_nsym : h->d_nsym;
-    a.bits = d_bits; a.bits_stride = bits_stride;
-    a.row_ptr = h->d_row_ptr; a.col_idx = h->d_col_idx; a.lead = h->d_lead; a.gap = h->d_gap;
-    a.uw = 0;
-    for (int i = 0; i < kUwBits; i++) a.uw |= (uint32_t)(h->code.uw[i] & 1) << (31 - i);
-    a.k = h->code.k; a.m = h->code.m; a.kb = h->code.data_bytes(); a.bpf = h->code.bits_per_frame(); a.bps = h->bps;
-    a.pre_bits = h->pre_bits; a.nstreams = h->nstreams;
-    a.frame_lds = (a.bpf + 15) & ~15;
-    a.wave_lds = a.frame_lds + ((a.kb + 15) & ~15);
-    hipStream_t st = (hipStream_t)hip_stream;
-    hipLaunchKernelGGL(tx_layout_kernel, dim3((unsigned)h->nstreams), dim3(64), 0, st, a);
-    if (max_rec > 0)
-        hipLaunchKernelGGL(tx_frame_kernel, dim3((unsigned)((max_rec + kFrameWaves - 1) / kFrameWaves), (unsigned)h->nstreams), dim3(kFrameWaves * 64),
-                           (size_t)kFrameWaves * a.wave_lds, st, a);
-    PIRIP_HIPCHK(hipGetLastError());
-    return PIRIP_OK;
+    return tx_frame_rows(h, d_records, rec_stride, d_nrec, max_rec, d_syms, sym_stride, max_syms, d_nsym ? d_nsym : h->d_nsym, d_bits, bits_stride,
+                         h->d_lead, h->d_off, (hipStream_t)hip_stream);
 }
 
 int pirip_hip_tx_modulate(pirip_hip_tx *h, const uint8_t *d_syms, size_t sym_stride, const int32_t *d_nsym, int64_t nsym,

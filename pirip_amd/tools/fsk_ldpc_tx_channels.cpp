@@ -5,7 +5,7 @@
 //
 //   fsk_ldpc_tx_channels --code NAME|FILE -s wideFs -a modemFs -r Rs [-m M] --f1 Hz --shift Hz -c off1,off2,...
 //                        [--gain g | --gains g1,g2,...] [--linear] [--format u8|cf32] [--packed] [--gap BITS] [--lead BITS]
-//                        -i PREFIX -o OUT|-
+//                        [--block N [--queue SYMS]] -i PREFIX -o OUT|-
 //       channel k's records are read from PREFIX.<k>: one burst-control byte + data_bits_per_frame bits (one per byte) or, with
 //       --packed, /8 bytes, as fsk_ldpc_tx reads them; --gap / --lead: carrier off for every `2` record / in front, as there.
 //   fsk_ldpc_tx_channels ... --testframes N [--bursts B] [--seq] [--source BYTE | --source b1,b2,...] -o OUT|-
@@ -13,6 +13,14 @@
 // A modem sample has modulus 2 (section I), so --gain g puts a channel at 255 g u8 steps of amplitude; the default is 0.1 / K.
 // The whole input is processed in one piece: every channel's row is as long as the longest (carrier off behind a shorter one), with
 // Q - 1 zeros in front, and the multiplexer runs at m0 = -(Q - 1), so that wideband sample 0 corresponds to modem sample 0.
+// --block N (wideband samples, a multiple of D * Ts): the streaming transmitter instead (section K). Before every block each channel is
+// offered its next burst -- the records up to and including a `2` -- again and again until one is refused or its input is exhausted, and
+// every block is written as it is produced: memory no longer grows with the input. --queue: each channel's queue in symbols, by default
+// the largest burst plus one block's symbols, with which no queue runs dry before its input ends: the first n_out samples are then the
+// one-piece mode's, byte for byte, and the rest, up to a whole block, is the filter's tail and silence. A smaller --queue (it must hold
+// the largest burst) is served too: a burst then waits until the queue has room, the channel sends carrier off where it ran dry, and
+// the output is longer than the one-piece mode's by that much. The tool ends when every input is exhausted and every queue is empty; it
+// follows the fill levels on the host from what each send took. --lead does not go with --block.
 // Exit codes: 1 arguments / files, 2 the code file (as fsk_ldpc_tx), 3 no usable HIP device or a device error (nothing is written).
 #include <getopt.h>
 #include <hip/hip_runtime_api.h>
@@ -34,7 +42,7 @@ static int usage(const char *a0)
 {
     fprintf(stderr, "usage: %s --code NAME|FILE -s wideFs -a modemFs -r Rs [-m 2|4] --f1 Hz --shift Hz -c off1,off2,...\n"
                     "          [--gain g | --gains g1,g2,...] [--linear] [--format u8|cf32] [--packed] [--gap BITS] [--lead BITS]\n"
-                    "          [--testframes N [--bursts B] [--seq] [--source BYTE|b1,b2,...]] -i PREFIX -o out|-\n", a0);
+                    "          [--testframes N [--bursts B] [--seq] [--source BYTE|b1,b2,...]] [--block N [--queue SYMS]] -i PREFIX -o out|-\n", a0);
     return 1;
 }
 
@@ -77,6 +85,7 @@ int main(int argc, char **argv)
     std::string code, format = "u8", prefix, out_name;
     long wideFs = 0, modemFs = 0, Rs = 0;
     int M = 2, packed = 0, testframes = 0, bursts = 1, seq = 0, linear = 0, f1 = 0, shift = 0, have_f1 = 0, gap = 0, lead_bits = 0;
+    long long block = 0, queue = 0;
     std::vector<int32_t> offsets;
     std::vector<float> gains;
     std::vector<long> sources;
@@ -86,7 +95,8 @@ int main(int argc, char **argv)
                                     {"f1", required_argument, 0, 1006}, {"shift", required_argument, 0, 1007},
                                     {"format", required_argument, 0, 1008}, {"gain", required_argument, 0, 1009},
                                     {"gains", required_argument, 0, 1009}, {"linear", no_argument, 0, 1010},
-                                    {"gap", required_argument, 0, 1011}, {"lead", required_argument, 0, 1012}, {0, 0, 0, 0}};
+                                    {"gap", required_argument, 0, 1011}, {"lead", required_argument, 0, 1012},
+                                    {"block", required_argument, 0, 1013}, {"queue", required_argument, 0, 1014}, {0, 0, 0, 0}};
     auto to_long = [](const char *t, char **e) { return strtol(t, e, 0); };
     int o, oi;
     while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:h", lopts, &oi)) != -1) {
@@ -115,6 +125,8 @@ int main(int argc, char **argv)
         case 1010: linear = 1; break;
         case 1011: gap = atoi(optarg); break;
         case 1012: lead_bits = atoi(optarg); break;
+        case 1013: block = atoll(optarg); if (block <= 0) { fprintf(stderr, "fsk_ldpc_tx_channels: --block wants a positive number of wideband samples\n"); return 1; } break;
+        case 1014: queue = atoll(optarg); if (queue <= 0) { fprintf(stderr, "fsk_ldpc_tx_channels: --queue wants a positive number of symbols\n"); return 1; } break;
         default: return usage(argv[0]);
         }
     }
@@ -128,6 +140,8 @@ int main(int argc, char **argv)
     if (bursts < 1 || testframes < 0 || gap < 0 || lead_bits < 0 || gap % bps || lead_bits % bps) {
         fprintf(stderr, "fsk_ldpc_tx_channels: --gap / --lead are whole symbols, --bursts >= 1, --testframes >= 0\n"); return 1;
     }
+    if (block > 0 && lead_bits > 0) { fprintf(stderr, "fsk_ldpc_tx_channels: --lead does not go with --block: a streaming transmitter's silence is its empty queue\n"); return 1; }
+    if (queue > 0 && block <= 0) { fprintf(stderr, "fsk_ldpc_tx_channels: --queue needs --block\n"); return 1; }
     if (gains.empty()) gains.assign(1, 0.1f / (float)K);
     if (gains.size() == 1) gains.assign((size_t)K, gains[0]);
     if ((int)gains.size() != K) { fprintf(stderr, "fsk_ldpc_tx_channels: one gain, or one per channel\n"); return 1; }
@@ -210,6 +224,102 @@ int main(int argc, char **argv)
     if ((rc = pirip_hip_tx_set_tones(tx, f1s.data(), shift)) != PIRIP_OK) return fail("pirip_hip_tx_set_tones", rc);
     const std::vector<int32_t> leads((size_t)K, lead_bits / bps), gaps((size_t)K, gap / bps);
     if ((rc = pirip_hip_tx_set_gaps(tx, leads.data(), gaps.data())) != PIRIP_OK) return fail("pirip_hip_tx_set_gaps", rc);
+
+    if (block > 0) {
+        // the streaming transmitter: each channel's bursts (record ranges and the symbols they make), offered burst by burst
+        pirip_tx_info ti;
+        pirip_hip_tx_get_info(tx, &ti);
+        struct Burst { int r0, r1; int64_t syms; };
+        std::vector<std::vector<Burst>> bursts((size_t)K);
+        int64_t max_burst = 0, max_total = 0;
+        int max_brec = 1;
+        for (int c = 0; c < K; c++) {
+            Burst b{0, 0, 0};
+            int64_t total = 0;
+            for (int i = 0; i < nrec[(size_t)c]; i++) {
+                const uint8_t ctl = recs[(size_t)c][(size_t)i * (size_t)rl];
+                b.syms += ctl == 1 ? ti.preamble_syms + ti.frame_syms : ctl == 0 ? ti.frame_syms : ctl == 2 ? gap / bps : 0;
+                b.r1 = i + 1;
+                if (ctl == 2 || i + 1 == nrec[(size_t)c]) {
+                    bursts[(size_t)c].push_back(b);
+                    total += b.syms;
+                    if (b.syms > max_burst) max_burst = b.syms;
+                    if (b.r1 - b.r0 > max_brec) max_brec = b.r1 - b.r0;
+                    b = Burst{i + 1, i + 1, 0};
+                }
+            }
+            if (total > max_total) max_total = total;
+        }
+        const int64_t per_sym = (int64_t)D * Ts, S = block / per_sym;
+        if (block % per_sym) { fprintf(stderr, "fsk_ldpc_tx_channels: --block must be a multiple of D * Ts = %lld wideband samples\n", (long long)per_sym); pirip_hip_mux_destroy(mux); pirip_hip_tx_destroy(tx); return 1; }
+        if (queue <= 0) queue = max_burst + S;
+        if (queue < max_burst) { fprintf(stderr, "fsk_ldpc_tx_channels: --queue %lld cannot hold the largest burst, %lld symbols\n", queue, (long long)max_burst); pirip_hip_mux_destroy(mux); pirip_hip_tx_destroy(tx); return 1; }
+        pirip_hip_txs *txs = nullptr;
+        if ((rc = pirip_hip_txs_create(tx, mux, block, queue, &txs)) != PIRIP_OK) return fail("pirip_hip_txs_create", rc);
+        FILE *fout = out_name == "-" ? stdout : fopen(out_name.c_str(), "wb");
+        uint8_t *d_stage = nullptr; int32_t *d_offered = nullptr, *d_taken = nullptr; void *d_blk = nullptr;
+        // every way out of block mode: the device buffers, the three handles, the output
+        auto done = [&](int status) {
+            (void)hipFree(d_stage); (void)hipFree(d_offered); (void)hipFree(d_taken); (void)hipFree(d_blk);
+            pirip_hip_txs_destroy(txs);
+            pirip_hip_mux_destroy(mux);
+            pirip_hip_tx_destroy(tx);
+            if (fout && fout != stdout) fclose(fout);
+            return status;
+        };
+        auto sfail = [&](const char *what, int status) {
+            fprintf(stderr, "fsk_ldpc_tx_channels: %s: %s\n", what, pirip_hip_strerror(status));
+            return done(status == PIRIP_ERR_BAD_ARG ? 1 : 3);
+        };
+        if (!fout) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open the output\n"); return done(1); }
+        const size_t stage_stride = (size_t)max_brec * (size_t)rl, blk_bytes = (size_t)block * (size_t)bsamp;
+        std::vector<uint8_t> stage((size_t)K * stage_stride, 0), blk(blk_bytes);
+        std::vector<int32_t> offered((size_t)K), taken((size_t)K);
+        std::vector<size_t> next((size_t)K, 0);
+        // each queue's fill level, followed on the host: a burst that was taken adds its symbols, a block takes up to S away
+        std::vector<int64_t> fill((size_t)K, 0);
+        if (hipMalloc((void **)&d_stage, stage.size()) != hipSuccess || hipMalloc((void **)&d_offered, sizeof(int32_t) * (size_t)K) != hipSuccess ||
+            hipMalloc((void **)&d_taken, sizeof(int32_t) * (size_t)K) != hipSuccess || hipMalloc(&d_blk, blk_bytes) != hipSuccess) return sfail("hipMalloc", PIRIP_ERR_NOMEM);
+        int64_t calls = 0;
+        for (;;) {
+            std::vector<char> refused((size_t)K, 0);
+            for (;;) {
+                bool any = false;
+                for (int c = 0; c < K; c++) {
+                    offered[(size_t)c] = 0;
+                    if (refused[(size_t)c] || next[(size_t)c] >= bursts[(size_t)c].size()) continue;
+                    const Burst &b = bursts[(size_t)c][next[(size_t)c]];
+                    memcpy(&stage[(size_t)c * stage_stride], &recs[(size_t)c][(size_t)b.r0 * (size_t)rl], (size_t)(b.r1 - b.r0) * (size_t)rl);
+                    offered[(size_t)c] = b.r1 - b.r0;
+                    any = true;
+                }
+                if (!any) break;
+                if (hipMemcpy(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice) != hipSuccess ||
+                    hipMemcpy(d_offered, offered.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) return sfail("hipMemcpy", PIRIP_ERR_HIP);
+                if ((rc = pirip_hip_txs_send(txs, d_stage, stage_stride, d_offered, max_brec, d_taken, nullptr)) != PIRIP_OK) return sfail("pirip_hip_txs_send", rc);
+                if (hipMemcpy(taken.data(), d_taken, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost) != hipSuccess) return sfail("hipMemcpy", PIRIP_ERR_HIP);
+                for (int c = 0; c < K; c++) {
+                    if (!offered[(size_t)c]) continue;
+                    if (taken[(size_t)c] == offered[(size_t)c]) { fill[(size_t)c] += bursts[(size_t)c][next[(size_t)c]].syms; next[(size_t)c]++; }
+                    else refused[(size_t)c] = 1;
+                }
+            }
+            // the end: every channel's input is exhausted and every queue is empty
+            bool more = false;
+            for (int c = 0; c < K; c++) if (next[(size_t)c] < bursts[(size_t)c].size() || fill[(size_t)c] > 0) more = true;
+            if (!more) break;
+            if ((rc = pirip_hip_txs_process(txs, d_blk, blk_bytes, nullptr, nullptr)) != PIRIP_OK) return sfail("pirip_hip_txs_process", rc);
+            if (hipMemcpy(blk.data(), d_blk, blk_bytes, hipMemcpyDeviceToHost) != hipSuccess) return sfail("hipMemcpy", PIRIP_ERR_HIP);
+            if (fwrite(blk.data(), 1, blk.size(), fout) != blk.size()) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return done(1); }
+            for (int c = 0; c < K; c++) fill[(size_t)c] -= fill[(size_t)c] < S ? fill[(size_t)c] : S;
+            calls++;
+        }
+        if (fflush(fout) != 0) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return done(1); }
+        done(0);
+        fprintf(stderr, "fsk_ldpc_tx_channels: code %s M %d channels %d interpolation %d taps %d: %lld symbols in %lld blocks of %lld wideband samples, queues of %lld symbols\n",
+                ldpc.name.c_str(), M, K, D, mi.ntaps, (long long)max_total, (long long)calls, block, queue);
+        return 0;
+    }
 
     uint8_t *d_rec = nullptr; int32_t *d_nrec = nullptr, *d_nsym = nullptr; char *d_mod = nullptr; void *d_out = nullptr;
     if (hipMalloc((void **)&d_rec, rec_rows.size()) != hipSuccess || hipMalloc((void **)&d_nrec, sizeof(int32_t) * (size_t)K) != hipSuccess ||
