@@ -22,6 +22,9 @@
  *              channel symbols -> continuous-phase M-FSK IQ for a batch of streams.
  *   section J  multiplexer (pirip_hip_mux_*)               : K modem-rate channels interpolated,
  *              shifted, scaled and summed onto W wideband u8 / complex float IQ streams.
+ *   section K  streaming transmitter (pirip_hip_txs_*)      : section G's mirror image, queued records to wideband IQ block after block.
+ *   section L  test-frame counter (pirip_hip_tbits_*)       : fsk_put_test_bits / rtl_fsk --testframes for a batch of streams,
+ *              counted on the device behind the demodulator or the receiver.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -641,6 +644,63 @@ int pirip_hip_txs_get_counters(pirip_hip_txs *txs, int64_t *queued, int64_t *sen
 int pirip_hip_txs_reset(pirip_hip_txs *txs, void *hip_stream);
 /* One HIP stream per handle: queues, phases and history are device state advanced in stream order, the sample index is host state advanced
  * when a call is enqueued. */
+
+/* ----------------------------------------------------------------------------------- */
+/* section L : test-frame counter (bit errors per stream, counted on the device)        */
+/*   What every receive pipeline of the reference ends in: `| fsk_put_test_bits -`        */
+/*   (/root/reference/README.md:105,109,114,152,172, test/loopback_rtl_fsk.sh,            */
+/*   test/loopback_rtl_sdr.sh) for uncoded bits, and the ecdd column of                   */
+/*   `rtl_fsk --code NAME --testframes` for FSK_LDPC records -- for a batch of streams,   */
+/*   chained behind the demodulator or the receiver on the same HIP stream, so that no    */
+/*   bit has to reach the host to learn a link's error rate. All results */
+/*   are integers and equal the CPU counter's exactly.                                    */
+/* ----------------------------------------------------------------------------------- */
+#define PIRIP_TBITS_MAX_FRAMESIZE 4096
+typedef struct pirip_hip_tbits pirip_hip_tbits;
+/* nstreams counters for one test frame. Replaces nstreams x fsk_put_test_bits [-f framesize] [-t valid_thresh]. frame_bits == NULL: the
+ * tool's own frame (glibc srand(158324), rand() & 1 per bit, computed on the host here and uploaded); else framesize host bytes, each 0
+ * or 1. A window is valid iff (float)errs < thr with thr = valid_thresh * framesize evaluated once in float -- the tool's own expression,
+ * not an integer limit (0.09f * 300 is 27.000002f: 27 errors are valid; 0.07f * 100 is exactly 7.0f: 7 are not). PIRIP_ERR_BAD_ARG for framesize < 1, nstreams < 1, a frame byte
+ * above 1 or out == NULL; PIRIP_ERR_UNSUPPORTED for framesize > PIRIP_TBITS_MAX_FRAMESIZE; PIRIP_ERR_NO_DEVICE without a device. */
+int pirip_hip_tbits_create(int framesize, float valid_thresh, const uint8_t *frame_bits, int nstreams, int device, pirip_hip_tbits **out);
+int pirip_hip_tbits_destroy(pirip_hip_tbits *h);
+/* Stream s hands over nf_s = clamp(d_nframes[s], 0, max_frames) rows (d_nframes == NULL: max_frames) at d_bits + s * bits_stride (bytes),
+ * each row row_bits bits: packed = 0 one byte per bit (the low bit counts), rows row_bits bytes apart; packed = 1 ceil(row_bits / 8) bytes
+ * per row, MSB first, pad bits ignored -- the layouts pirip_hip_demod_batch, pirip_hip_demod_capture and pirip_hip_rx_process write, with
+ * their d_nframes. Replaces piping those bits into fsk_put_test_bits: with b the stream's bits in order since create / reset and b[i] = 0
+ * for i < 0 (the tool's zero-filled window), every position j whose window b[j - F + 1 .. j] is valid adds 1 to packets, F to bits and
+ * its Hamming distance to the frame to errors; overlapping valid windows all count, as in the tool. The handle carries each stream's last
+ * F - 1 bits from call to call, so a window may straddle any number of calls, and calls of 0 rows or of fewer than F - 1 bits are fine.
+ * Enqueued on hip_stream (NULL = default stream); never synchronises. PIRIP_ERR_BAD_ARG unless row_bits >= 1, max_frames >= 0 and
+ * max_frames * row_bits < 2^31; PIRIP_ERR_UNSUPPORTED when nstreams * ceil(max_frames * row_bits / 2048) does not fit 31 bits.
+ * One HIP stream per handle: which of the two history rows a call reads is host state advanced when the call is enqueued. */
+int pirip_hip_tbits_push(pirip_hip_tbits *h, const uint8_t *d_bits, size_t bits_stride, int row_bits, int packed, const int32_t *d_nframes,
+                         int64_t max_frames, void *hip_stream);
+/* Host copies (synchronises the device), per stream [nstreams], each may be NULL: fsk_put_test_bits' packetcnt, bitcnt and biterr, and
+ * the bits handed over since create / reset. */
+int pirip_hip_tbits_get_counters(pirip_hip_tbits *h, int64_t *packets, int64_t *bits, int64_t *errors, int64_t *pushed);
+/* The same on the device, for callers that stay there: int64 [nstreams][4] = {packets, bits, errors, pushed}, valid in stream order. */
+int pirip_hip_tbits_counters_device(pirip_hip_tbits *h, int64_t **d_counters);
+/* Counters (both blocks) and history back to the created state, in stream order. */
+int pirip_hip_tbits_reset(pirip_hip_tbits *h, void *hip_stream);
+
+/* The payload of --testframes for a code of k data bits, packed MSB first into k / 8 bytes: rtl_fsk.cpp's tf_bytes, what
+ * fsk_ldpc_framer --testframes sends. Host function, needs no device. PIRIP_ERR_BAD_ARG for k < 8 or k % 8. */
+int pirip_hip_tbits_testframe_payload(int k, uint8_t *bytes_out);
+/* What push_records compares with: data_bytes host bytes (NULL: the test payload of k = 8 * data_bytes). Synchronises the device. */
+int pirip_hip_tbits_set_payload(pirip_hip_tbits *h, int data_bytes, const uint8_t *payload);
+/* Replaces the ecdd column of `rtl_fsk --code NAME --testframes -v`, tallied: stream s reads nc_s = clamp(d_ncalls[s], 0, ncalls)
+ * (d_ncalls == NULL: ncalls) records as pirip_hip_fsk_ldpc_rx_batch / pirip_hip_rx_process wrote them -- status bytes at d_status +
+ * s * status_stride, payloads of data_bytes bytes at d_payload + s * payload_stride, info rows of PIRIP_LDPC_INFO_PER_CALL int32 at
+ * d_info + s * info_stride (strides in elements). A record counts when info[6] >= 0 (a frame was decoded); its errors are the popcount of
+ * payload ^ test payload over bytes 2 .. data_bytes - 3 (bytes 0, 1 carry source / sequence, the last two the CRC). Needs set_payload
+ * first (else PIRIP_ERR_BAD_ARG). Enqueued on hip_stream; never synchronises. */
+int pirip_hip_tbits_push_records(pirip_hip_tbits *h, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                                 const int32_t *d_info, size_t info_stride, const int32_t *d_ncalls, int ncalls, void *hip_stream);
+/* Host copies (synchronises the device), per stream [nstreams], each may be NULL: decoded frames, payload bits compared, payload bit
+ * errors, frames with at least one error, records with PIRIP_RX_BITS. */
+int pirip_hip_tbits_get_record_counters(pirip_hip_tbits *h, int64_t *frames, int64_t *bits, int64_t *errors, int64_t *frames_in_error,
+                                        int64_t *crc_ok);
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J and K).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J, K and L).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -177,6 +177,16 @@ def lib():
     L.pirip_hip_txs_process.argtypes = [vp, vp, sz, vp, vp]
     L.pirip_hip_txs_get_counters.argtypes = [vp, vp, vp, vp, vp]
     L.pirip_hip_txs_reset.argtypes = [vp, vp]
+    L.pirip_hip_tbits_create.argtypes = [i32, C.c_float, vp, i32, i32, C.POINTER(vp)]
+    L.pirip_hip_tbits_destroy.argtypes = [vp]
+    L.pirip_hip_tbits_push.argtypes = [vp, vp, sz, i32, i32, vp, i64, vp]
+    L.pirip_hip_tbits_get_counters.argtypes = [vp, vp, vp, vp, vp]
+    L.pirip_hip_tbits_counters_device.argtypes = [vp, C.POINTER(vp)]
+    L.pirip_hip_tbits_reset.argtypes = [vp, vp]
+    L.pirip_hip_tbits_testframe_payload.argtypes = [i32, vp]
+    L.pirip_hip_tbits_set_payload.argtypes = [vp, i32, vp]
+    L.pirip_hip_tbits_push_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, i32, vp]
+    L.pirip_hip_tbits_get_record_counters.argtypes = [vp, vp, vp, vp, vp, vp]
     _lib = L
     return L
 
@@ -618,6 +628,127 @@ class HipTxStream:
 
     def reset(self, stream=0):
         _chk(self.L.pirip_hip_txs_reset(self.h, stream), "pirip_hip_txs_reset")
+
+
+def testframe_payload(k):
+    """The --testframes payload of a code with k data bits, packed MSB first: uint8[k / 8] (pirip_hip_tbits_testframe_payload; no device)."""
+    import numpy as np
+    out = np.zeros(max(int(k) // 8, 1), dtype=np.uint8)
+    _chk(lib().pirip_hip_tbits_testframe_payload(int(k), out.ctypes.data), "pirip_hip_tbits_testframe_payload")
+    return out
+
+
+def _dev(x):
+    """a device pointer: None / 0, an int, or anything with data_ptr() (a torch tensor)"""
+    if x is None:
+        return 0
+    return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+
+def _hip_stream(stream):
+    """stream=None: torch's current stream when torch is loaded, else the default stream"""
+    if stream is not None:
+        return int(stream)
+    import sys
+    torch = sys.modules.get("torch")
+    return int(torch.cuda.current_stream().cuda_stream) if torch is not None and torch.cuda.is_available() else 0
+
+
+class HipTestBits:
+    """Test-frame counter (include/pirip_hip.h section L): fsk_put_test_bits [-f framesize] [-t valid_thresh] for nstreams streams, counted
+    on the device. frame: None for the tool's own frame, else framesize values 0 / 1. push() takes the demodulator's bit rows,
+    push_records() the FSK_LDPC receiver's records (rtl_fsk --testframes' ecdd, tallied)."""
+
+    def __init__(self, framesize=100, valid_thresh=0.1, frame=None, nstreams=1, device=-1):
+        import numpy as np
+        self.L = lib()
+        fb = None
+        if frame is not None:
+            fb = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
+            if fb.size != framesize:
+                raise ValueError("frame must hold framesize bits")
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_tbits_create(int(framesize), float(valid_thresh), None if fb is None else fb.ctypes.data, int(nstreams), device,
+                                           C.byref(h)), "pirip_hip_tbits_create")
+        self.h = h
+        self.framesize, self.valid_thresh, self.nstreams, self.data_bytes = int(framesize), float(valid_thresh), int(nstreams), 0
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_tbits_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def push(self, bits, nframes=None, row_bits=None, packed=False, stream=None, max_frames=None, bits_stride=None):
+        """bits: a uint8 tensor [nstreams, max_frames, row bytes] (the last two dimensions contiguous) or a raw device pointer with
+        max_frames and bits_stride (bytes per stream) given; nframes: int32 tensor / pointer [nstreams] or None (every row counts);
+        row_bits: bits per row (default: the row's bytes, unpacked). Enqueued on `stream` (None: torch's current stream); no synchronisation."""
+        if hasattr(bits, "data_ptr") and hasattr(bits, "shape"):
+            if bits.dim() != 3 or bits.shape[0] != self.nstreams or bits.element_size() != 1:
+                raise ValueError("bits: uint8 [nstreams, max_frames, row bytes]")
+            rb = int(bits.shape[2])
+            if row_bits is None:
+                if packed:
+                    raise ValueError("packed rows need row_bits")
+                row_bits = rb
+            need = (int(row_bits) + 7) // 8 if packed else int(row_bits)
+            if rb != need or (bits.shape[1] > 1 and bits.stride(1) != rb) or bits.stride(2) != 1:
+                raise ValueError("bits: rows of exactly row_bits bits, one after the other")
+            max_frames = int(bits.shape[1]) if max_frames is None else int(max_frames)
+            bits_stride = int(bits.stride(0)) if bits_stride is None else int(bits_stride)
+        elif max_frames is None or bits_stride is None or row_bits is None:
+            raise ValueError("a raw pointer needs row_bits, max_frames and bits_stride")
+        _chk(self.L.pirip_hip_tbits_push(self.h, _dev(bits), int(bits_stride), int(row_bits), 1 if packed else 0, _dev(nframes),
+                                         int(max_frames), _hip_stream(stream)), "pirip_hip_tbits_push")
+
+    def set_payload(self, data_bytes, payload=None):
+        """what push_records compares with: data_bytes bytes, None = testframe_payload(8 * data_bytes)"""
+        import numpy as np
+        p = None if payload is None else np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
+        if p is not None and p.size != data_bytes:
+            raise ValueError("payload must hold data_bytes bytes")
+        _chk(self.L.pirip_hip_tbits_set_payload(self.h, int(data_bytes), None if p is None else p.ctypes.data), "pirip_hip_tbits_set_payload")
+        self.data_bytes = int(data_bytes)
+
+    def push_records(self, status, payload, info, ncalls=None, max_calls=None, status_stride=None, payload_stride=None, info_stride=None,
+                     stream=None):
+        """the records HipLdpc.chain_batch / HipRx.process wrote: status uint8 [nstreams, max_calls], payload uint8 [nstreams, max_calls,
+        data_bytes], info int32 [nstreams, max_calls, LDPC_INFO_PER_CALL] as tensors (per-stream rows contiguous), or raw pointers with
+        max_calls and the three strides (elements per stream); ncalls: int32 [nstreams] or None."""
+        if hasattr(status, "shape"):
+            max_calls = int(status.shape[1]) if max_calls is None else int(max_calls)
+            status_stride = int(status.stride(0)) if status_stride is None else int(status_stride)
+            payload_stride = int(payload.stride(0)) if payload_stride is None else int(payload_stride)
+            info_stride = int(info.stride(0)) if info_stride is None else int(info_stride)
+        elif None in (max_calls, status_stride, payload_stride, info_stride):
+            raise ValueError("raw pointers need max_calls and the three strides")
+        _chk(self.L.pirip_hip_tbits_push_records(self.h, _dev(status), status_stride, _dev(payload), payload_stride, _dev(info), info_stride,
+                                                 _dev(ncalls), int(max_calls), _hip_stream(stream)), "pirip_hip_tbits_push_records")
+
+    def _read(self, fn, names, what):
+        import numpy as np
+        out = {k: np.zeros(self.nstreams, dtype=np.int64) for k in names}
+        _chk(fn(self.h, *(out[k].ctypes.data for k in names)), what)
+        return out
+
+    def counters(self):
+        """dict of int64[nstreams]: packets, bits, errors (fsk_put_test_bits' packetcnt, bitcnt, biterr), pushed -- synchronises."""
+        return self._read(self.L.pirip_hip_tbits_get_counters, ("packets", "bits", "errors", "pushed"), "pirip_hip_tbits_get_counters")
+
+    def counters_device(self):
+        """device pointer of the int64 [nstreams][4] counters {packets, bits, errors, pushed}"""
+        p = C.c_void_p()
+        _chk(self.L.pirip_hip_tbits_counters_device(self.h, C.byref(p)), "pirip_hip_tbits_counters_device")
+        return int(p.value)
+
+    def record_counters(self):
+        """dict of int64[nstreams]: frames (decoded), bits (payload bits compared), errors, frames_in_error, crc_ok -- synchronises."""
+        return self._read(self.L.pirip_hip_tbits_get_record_counters, ("frames", "bits", "errors", "frames_in_error", "crc_ok"),
+                          "pirip_hip_tbits_get_record_counters")
+
+    def reset(self, stream=None):
+        _chk(self.L.pirip_hip_tbits_reset(self.h, _hip_stream(stream)), "pirip_hip_tbits_reset")
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

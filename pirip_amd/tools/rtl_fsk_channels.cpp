@@ -3,6 +3,7 @@
 //
 //   rtl_fsk_channels -s rtlFs -a modemFs -r Rs [-m M] [--mask S] [--fsk_lower Hz] [--fsk_upper Hz] [--code NAME|FILE]
 //                    -c OFF1,OFF2,... [-i FILE|-] -o PREFIX [-q]
+//                    [--put-test-bits [-p packetsPass] [-b berPass] [-t validBER] [-f frameBits]] [--testframes]
 //
 // Channel k is centred at OFFk Hz from the capture's centre (integer, -rtlFs/2 < OFFk < rtlFs/2) and is what
 // `csdr shift_addition_cc (-OFFk/rtlFs) | fir_decimate_cc (rtlFs/modemFs)` would hand `rtl_fsk -a modemFs`: the same modem settings as
@@ -11,6 +12,11 @@
 // processed. Output, one file per channel, PREFIX.<k>:
 //   uncoded        one byte per bit, as rtl_fsk writes to stdout
 //   --code NAME    the packed payload bytes of every frame whose CRC16 matches, as rtl_fsk --code
+// --put-test-bits (uncoded) is `| fsk_put_test_bits [-p] [-b] [-t] [-f] -` behind every channel, --testframes (with --code) the tally of
+// rtl_fsk --testframes' ecdd column: counted on the device behind every block (include/pirip_hip.h section L), the files stay as they
+// are. At the end one line per channel on stderr, the channel number in front of fsk_put_test_bits' final line (--testframes: decoded
+// frames for packets, payload bits compared, payload bit errors); exit 0 only if every channel meets that tool's PASS rule
+// (packets >= packetsPass && bits > 0 && BER <= berPass), else 1.
 #include <getopt.h>
 #include <sys/stat.h>
 #include <unistd.h>
@@ -30,6 +36,7 @@ static void usage()
     fprintf(stderr,
             "rtl_fsk_channels (pirip_hip): -s rtlFs -a modemFs -r Rs [-m M] [--mask spacing] [--fsk_lower Hz] [--fsk_upper Hz]\n"
             "        [--code NAME|FILE] -c off1,off2,... [-i <u8 IQ file|->] -o PREFIX [-q]\n"
+            "        [--put-test-bits [-p packetsPass] [-b berPass] [-t validBER] [-f frameBits]] [--testframes (with --code)]\n"
             "        writes PREFIX.<k> per channel: bits one per byte, or with --code the payload bytes of every CRC-ok frame\n");
 }
 
@@ -76,13 +83,16 @@ int main(int argc, char **argv)
     }
     long rtlFs = 0, modemFs = 0, Rs = 0;
     int M = 2, mask = 0, quiet = 0, fsk_lower = 0, fsk_upper = 0, user_lower = 0, user_upper = 0;
+    int put_bits = 0, testframes = 0, framesize = 100, packet_pass = 0;
+    float valid_thresh = 0.1f, ber_pass = 0.0f;
     std::string in_name = "-", prefix, code;
     std::vector<int32_t> offsets;
     static struct option lopts[] = {{"code", required_argument, 0, 1000}, {"mask", required_argument, 0, 1001},
                                     {"fsk_lower", required_argument, 0, 1002}, {"fsk_upper", required_argument, 0, 1003},
+                                    {"put-test-bits", no_argument, 0, 1004}, {"testframes", no_argument, 0, 1005},
                                     {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
     int o, oi;
-    while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:qh", lopts, &oi)) != -1) {
+    while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:qhp:b:t:f:", lopts, &oi)) != -1) {
         switch (o) {
         case 's': rtlFs = (long)atof(optarg); break;
         case 'a': modemFs = (long)atof(optarg); break;
@@ -96,12 +106,20 @@ int main(int argc, char **argv)
         case 1001: mask = atoi(optarg); break;
         case 1002: fsk_lower = atoi(optarg); user_lower = 1; break;
         case 1003: fsk_upper = atoi(optarg); user_upper = 1; break;
+        case 1004: put_bits = 1; break;
+        case 1005: testframes = 1; break;
+        case 'p': packet_pass = atoi(optarg); break;
+        case 'b': ber_pass = (float)atof(optarg); break;
+        case 't': valid_thresh = (float)atof(optarg); break;
+        case 'f': framesize = atoi(optarg); break;
         default: usage(); return 1;
         }
     }
     if (rtlFs <= 0 || modemFs <= 0 || Rs <= 0 || offsets.empty() || prefix.empty() || (M != 2 && M != 4)) { usage(); return 1; }
     if (rtlFs % modemFs) { fprintf(stderr, "rtl_fsk_channels: rtl rate %ld must be a multiple of the modem rate %ld\n", rtlFs, modemFs); return 1; }
     if (modemFs % Rs) { fprintf(stderr, "rtl_fsk_channels: modem rate must be a multiple of the symbol rate\n"); return 1; }
+    if (put_bits && !code.empty()) { fprintf(stderr, "rtl_fsk_channels: --put-test-bits counts uncoded bits; with --code use --testframes\n"); return 1; }
+    if (testframes && code.empty()) { fprintf(stderr, "rtl_fsk_channels: --testframes needs --code\n"); return 1; }
     const int D = (int)(rtlFs / modemFs), Fs = (int)modemFs, K = (int)offsets.size();
     const int Ts = Fs / (int)Rs;
     int P = Ts;
@@ -136,6 +154,12 @@ int main(int argc, char **argv)
         PIRIPOK(pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, K, -1, &ldpc), "--code");
         pirip_hip_ldpc_get_info(ldpc, &li);
     }
+    pirip_hip_tbits *tb = nullptr;
+    if (put_bits) PIRIPOK(pirip_hip_tbits_create(framesize, valid_thresh, nullptr, K, -1, &tb), "--put-test-bits");
+    if (testframes) {
+        PIRIPOK(pirip_hip_tbits_create(framesize, valid_thresh, nullptr, K, -1, &tb), "--testframes");
+        PIRIPOK(pirip_hip_tbits_set_payload(tb, li.data_bytes, nullptr), "--testframes");
+    }
     const int64_t block = (int64_t)(rtlFs / 4) / D * D;
     PIRIPOK(pirip_hip_rx_create_chan(dem, ldpc, chan, block, &rx), "receiver");
     pirip_fsk_info info;
@@ -169,6 +193,11 @@ int main(int argc, char **argv)
         HIPOK(hipMemcpy(d_block, raw.data(), raw.size(), hipMemcpyHostToDevice));
         if (ldpc) PIRIPOK(pirip_hip_rx_process(rx, nullptr, 0, nullptr, 0, d_status, d_payload, d_info, nullptr, 0, d_nfr, nullptr), "receiver");
         else PIRIPOK(pirip_hip_rx_process(rx, d_bits, (size_t)R * info.Nbits, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, d_nfr, nullptr), "receiver");
+        // the counters run on the device behind the block, on the same HIP stream: nothing below waits for them
+        if (put_bits) PIRIPOK(pirip_hip_tbits_push(tb, d_bits, (size_t)R * info.Nbits, info.Nbits, 0, d_nfr, R, nullptr), "--put-test-bits");
+        if (testframes)
+            PIRIPOK(pirip_hip_tbits_push_records(tb, d_status, (size_t)R, d_payload, (size_t)R * li.data_bytes, d_info,
+                                                 (size_t)R * PIRIP_LDPC_INFO_PER_CALL, d_nfr, (int)R, nullptr), "--testframes");
         HIPOK(hipMemcpy(nfr.data(), d_nfr, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost));
         if (ldpc) {
             HIPOK(hipMemcpy(status.data(), d_status, rows, hipMemcpyDeviceToHost));
@@ -186,6 +215,20 @@ int main(int argc, char **argv)
     }
     if (!quiet) fprintf(stderr, "rtl_fsk_channels: %ld blocks of %lld samples\n", blocks, (long long)block);
     for (FILE *f : fout) fclose(f);
+    int verdict = 0;
+    if (tb) {
+        std::vector<int64_t> pk((size_t)K), nb((size_t)K), ne((size_t)K);
+        if (put_bits) PIRIPOK(pirip_hip_tbits_get_counters(tb, pk.data(), nb.data(), ne.data(), nullptr), "--put-test-bits");
+        else PIRIPOK(pirip_hip_tbits_get_record_counters(tb, pk.data(), nb.data(), ne.data(), nullptr, nullptr), "--testframes");
+        for (int k = 0; k < K; k++) {
+            const long bitcnt = (long)nb[(size_t)k], biterr = (long)ne[(size_t)k];
+            const float ber = bitcnt ? (float)biterr / (float)bitcnt : 0.5f;                // PutBits::ber()
+            fprintf(stderr, "%d: [%04d] BER %5.3f, bits tested %6ld, bit errors %6ld\n", k, (int)pk[(size_t)k], ber, bitcnt, biterr);
+            if (!(pk[(size_t)k] >= packet_pass && bitcnt > 0 && ber <= ber_pass)) verdict = 1;
+        }
+        fprintf(stderr, verdict ? "FAIL\n" : "PASS\n");
+        pirip_hip_tbits_destroy(tb);
+    }
     if (fin != stdin) fclose(fin);
     pirip_hip_rx_destroy(rx);
     if (ldpc) pirip_hip_ldpc_destroy(ldpc);
@@ -193,5 +236,5 @@ int main(int argc, char **argv)
     pirip_hip_chan_destroy(chan);
     void *ptrs[] = {d_bits, d_status, d_payload, d_info, d_nfr};
     for (void *p : ptrs) if (p) (void)hipFree(p);
-    return 0;
+    return verdict;
 }
