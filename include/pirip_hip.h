@@ -703,6 +703,75 @@ int pirip_hip_tbits_get_record_counters(pirip_hip_tbits *h, int64_t *frames, int
                                         int64_t *crc_ok);
 
 /* ----------------------------------------------------------------------------------- */
+/* section M : streaming repeater (wideband IQ in, repeated bursts out, block by block)  */
+/*   The reference's product as one call per block:                                       */
+/*   `rtl_fsk --code NAME --filter A -q -b | frame_repeater 256 A | rpitx_fsk - --code    */
+/*   NAME --packed` (/root/reference/script/frame_repeater:36-38) for a batch of channels.  */
+/*   Composes a streaming receiver (section G, optional), a transmitter (section I) and    */
+/*   its streaming transmitter (section K): received records go through rtl_fsk's          */
+/*   --filter and frame_repeater.c's state machine, finished bursts wait in a ring per      */
+/*   transmit channel and are handed to section K's queue whole, when they are due and      */
+/*   fit. No call synchronises or allocates; every call enqueues the same  */
+/*   launches.                                                                              */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_rpt pirip_hip_rpt;
+typedef struct pirip_rpt_info {
+    int nrx, nchan, source_byte, filter_byte, holdoff_calls, max_burst_frames, pending_records, has_rx, rx_rows, device;
+} pirip_rpt_info;
+/* All handles are borrowed, must be on one device and must outlive the repeater. rx: NULL (records come from the caller:
+ * pirip_hip_rpt_push_records) or a streaming receiver created with an ldpc, of nrx channels and tx's data_bytes, whose
+ * pirip_hip_rx_max_frames is at most 4096 (PIRIP_ERR_UNSUPPORTED above). txs must have been created on tx. route[c] (host array, nrx
+ * entries): the transmit channel of receive channel c, negative = do not repeat; the non-negative entries distinct and below tx's
+ * nstreams. source_byte 0 .. 255: byte 0 of every repeated frame (frame_repeater's source address). filter_byte: -1, or 0 .. 255 =
+ * rtl_fsk's --filter: a received frame whose byte 0 is filter_byte loses PIRIP_RX_BITS before the state machine sees it. holdoff_calls
+ * >= 0: a burst that ends in call n is offered from call n + holdoff_calls on (frame_repeater.c:91's wait, in blocks).
+ * max_burst_frames 1 .. PIRIP_TX_REPEAT_MAX_FRAMES: frames held per burst, further ones are dropped as in section I.
+ * pending_records >= max_burst_frames + 1: records of each transmit channel's pending ring. txs's queue_syms must hold one burst of
+ * max_burst_frames frames: preamble_syms + max_burst_frames * frame_syms + tx's largest gap. Anything else: PIRIP_ERR_BAD_ARG.
+ * Every work row is sized here with tx's gaps as they are, the framer's rows of pending_records records per channel in txs included: set
+ * the gaps first. The handle keeps its own state-machine state per receive channel and never touches tx's repeat state, phase or sample
+ * count. Create synchronises the device. */
+int pirip_hip_rpt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, int nrx, const int32_t *route, int source_byte, int filter_byte,
+                         int holdoff_calls, int max_burst_frames, int pending_records, pirip_hip_rpt **out);
+int pirip_hip_rpt_destroy(pirip_hip_rpt *rpt);
+int pirip_hip_rpt_get_info(const pirip_hip_rpt *rpt, pirip_rpt_info *info);
+/* Call n (n = 0, 1, ... since create / reset), in stream order:
+ * 1. intake, per receive channel c over its d_ncalls[c] (NULL = ncalls; clamped to [0, ncalls]) records -- status bytes at d_status +
+ *    c * status_stride, payloads of data_bytes bytes at d_payload + c * payload_stride, as pirip_hip_fsk_ldpc_rx_batch writes them; they
+ *    are only read --: the filter, then the state machine of pirip_hip_tx_repeat_records. A burst that ends here is the records 1, 0, ...,
+ *    0, 2; with t = route[c] >= 0 it is appended to transmit channel t's pending ring with ready = n + holdoff_calls, or dropped whole when
+ *    the ring's free space does not hold it; with route[c] < 0 it is discarded.
+ * 2. offer, per transmit channel t, from the ring's head and in order: whole bursts while ready <= n and the burst's symbols (preamble +
+ *    frames * frame_syms + tx's gap of channel t now) fit what is left of txs's free space (queue_syms - queued); the first burst that does
+ *    not qualify stops the channel. The taken records go through pirip_hip_txs_send's path, which by construction never refuses.
+ * 3. pirip_hip_txs_process into d_out (its rules for d_out / out_stride_bytes).
+ * Works with and without rx (with rx it changes nothing of the receiver). ncalls <= 4096 (PIRIP_ERR_UNSUPPORTED above). Enqueued on
+ * hip_stream (NULL = default stream); never synchronises. */
+int pirip_hip_rpt_push_records(pirip_hip_rpt *rpt, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                               const int32_t *d_ncalls, int ncalls, void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* Need rx (PIRIP_ERR_BAD_ARG without): pirip_hip_rx_process on the block at pirip_hip_rx_input (push: after copying it from d_in as
+ * pirip_hip_rx_push does) into the handle's own record rows, then the three steps above over them. */
+int pirip_hip_rpt_process(pirip_hip_rpt *rpt, void *d_out, size_t out_stride_bytes, void *hip_stream);
+int pirip_hip_rpt_push(pirip_hip_rpt *rpt, const void *d_in, size_t in_stride_bytes, void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* The records the last call read, as received (the filter changes no byte of them): after process / push the handle's rows -- rx_rows
+ * rows per channel, strides in elements, d_nframes [nrx] --, after push_records the caller's own (d_info NULL, its stride 0). Valid in
+ * stream order: pirip_hip_tbits_push_records or a logger can be chained on the same stream. Each pointer may be NULL.
+ * PIRIP_ERR_BAD_ARG before the first call. */
+int pirip_hip_rpt_records(pirip_hip_rpt *rpt, const uint8_t **d_status, size_t *status_stride, const uint8_t **d_payload, size_t *payload_stride,
+                          const int32_t **d_info, size_t *info_stride, const int32_t **d_nframes);
+/* The records offered to the streaming transmitter in the last call: channel t's d_nrec[t] records at d_records + t * rec_stride. */
+int pirip_hip_rpt_offered(pirip_hip_rpt *rpt, const uint8_t **d_records, size_t *rec_stride, const int32_t **d_nrec);
+/* Host copies (synchronises the device), each may be NULL. Per receive channel [nrx]: bursts that ended, the frames they held, frames
+ * the filter removed, bursts discarded for want of a route. Per transmit channel [nchan]: bursts offered, records waiting in the ring,
+ * bursts dropped on a full ring. */
+int pirip_hip_rpt_get_counters(pirip_hip_rpt *rpt, int64_t *bursts_in, int64_t *frames_in, int64_t *filtered, int64_t *unrouted,
+                               int64_t *bursts_out, int64_t *pending, int64_t *dropped);
+/* Forgets open bursts and the pending rings, clears the counters and resets txs, and rx where present: the next call is n = 0. */
+int pirip_hip_rpt_reset(pirip_hip_rpt *rpt, void *hip_stream);
+/* One HIP stream per handle: rings, ready tags and the state machines are device state advanced in stream order, the call index is host
+ * state advanced when a call is enqueued. */
+
+/* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */
 /*             names and signatures as codec2 src/fsk.h [UPSTREAM-RECALLED]              */
 /* ----------------------------------------------------------------------------------- */

@@ -54,6 +54,11 @@ class TxsInfo(C.Structure):
                [(n, C.c_int) for n in ("S", "H", "nchan", "noutputs", "out_format", "device")]
 
 
+class RptInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nrx", "nchan", "source_byte", "filter_byte", "holdoff_calls", "max_burst_frames", "pending_records",
+                                       "has_rx", "rx_rows", "device")]
+
+
 class LdpcInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "k", "bits_per_frame", "data_bytes", "nbits_per_call", "max_iter", "nstreams")] + \
                [("name", C.c_char * 64)]
@@ -187,6 +192,16 @@ def lib():
     L.pirip_hip_tbits_set_payload.argtypes = [vp, i32, vp]
     L.pirip_hip_tbits_push_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, i32, vp]
     L.pirip_hip_tbits_get_record_counters.argtypes = [vp, vp, vp, vp, vp, vp]
+    L.pirip_hip_rpt_create.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(vp)]
+    L.pirip_hip_rpt_destroy.argtypes = [vp]
+    L.pirip_hip_rpt_get_info.argtypes = [vp, C.POINTER(RptInfo)]
+    L.pirip_hip_rpt_push_records.argtypes = [vp, vp, sz, vp, sz, vp, i32, vp, sz, vp]
+    L.pirip_hip_rpt_process.argtypes = [vp, vp, sz, vp]
+    L.pirip_hip_rpt_push.argtypes = [vp, vp, sz, vp, sz, vp]
+    L.pirip_hip_rpt_records.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
+    L.pirip_hip_rpt_offered.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
+    L.pirip_hip_rpt_get_counters.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
+    L.pirip_hip_rpt_reset.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -749,6 +764,85 @@ class HipTestBits:
 
     def reset(self, stream=None):
         _chk(self.L.pirip_hip_tbits_reset(self.h, _hip_stream(stream)), "pirip_hip_tbits_reset")
+
+
+class HipRepeater:
+    """Streaming repeater (include/pirip_hip.h section M): one call per block from received FSK_LDPC records -- or, with a HipRx `rx`
+    created with an ldpc, from wideband IQ -- to the repeated wideband IQ of HipTxStream `txs` (created on HipTx `tx`). route[c]: the
+    transmit channel of receive channel c, negative = not repeated; source: byte 0 of every repeated frame; filter: None, or the byte 0
+    of frames that are not repeated (the repeater's own); holdoff: calls a finished burst waits; max_burst: frames held per burst;
+    pending: records of each transmit channel's pending ring (default: two bursts). The handles must outlive the repeater; pointer
+    arguments take torch tensors or raw device pointers, streams default to torch's current stream."""
+
+    def __init__(self, tx, txs, route, source, filter=None, holdoff=0, max_burst=100, pending=None, rx=None):
+        import numpy as np
+        self.L = lib()
+        self.rx, self.tx, self.txs = rx, tx, txs
+        rt = np.ascontiguousarray(route, dtype=np.int32).reshape(-1)
+        if pending is None:
+            pending = 2 * (int(max_burst) + 1)
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_rpt_create(rx.h if rx is not None else None, tx.h, txs.h, int(rt.size), rt.ctypes.data, int(source),
+                                         -1 if filter is None else int(filter), int(holdoff), int(max_burst), int(pending), C.byref(h)),
+             "pirip_hip_rpt_create")
+        self.h = h
+        self.info = RptInfo()
+        _chk(self.L.pirip_hip_rpt_get_info(self.h, C.byref(self.info)), "pirip_hip_rpt_get_info")
+        self.nrx, self.nchan, self.pending, self.rx_rows = self.info.nrx, self.info.nchan, self.info.pending_records, self.info.rx_rows
+        self.data_bytes = tx.data_bytes
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_rpt_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def push_records(self, status, payload, out, out_stride, ncalls=None, max_calls=None, status_stride=None, payload_stride=None, stream=None):
+        """status uint8 [nrx, max_calls], payload uint8 [nrx, max_calls, data_bytes] (tensors, per-channel rows contiguous; or raw
+        pointers with max_calls and the strides), ncalls int32 [nrx] or None -> one block per output at out + i * out_stride."""
+        if hasattr(status, "shape"):
+            max_calls = int(status.shape[1]) if max_calls is None else int(max_calls)
+            status_stride = int(status.stride(0)) if status_stride is None else int(status_stride)
+            payload_stride = int(payload.stride(0)) if payload_stride is None else int(payload_stride)
+        elif None in (max_calls, status_stride, payload_stride):
+            raise ValueError("raw pointers need max_calls and the two strides")
+        _chk(self.L.pirip_hip_rpt_push_records(self.h, _dev(status), status_stride, _dev(payload), payload_stride, _dev(ncalls), int(max_calls),
+                                               _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_rpt_push_records")
+
+    def process(self, out, out_stride, stream=None):
+        """the block at rx.input() -> one block per output (needs rx)"""
+        _chk(self.L.pirip_hip_rpt_process(self.h, _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_rpt_process")
+
+    def push(self, d_in, in_stride, out, out_stride, stream=None):
+        """process() after copying the block from d_in (rows in_stride bytes apart) into rx's input"""
+        _chk(self.L.pirip_hip_rpt_push(self.h, _dev(d_in), int(in_stride), _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_rpt_push")
+
+    def records(self):
+        """dict of the last call's received records: device pointers status, payload, info, nframes and the strides in elements"""
+        p = [C.c_void_p() for _ in range(4)]
+        st = [C.c_size_t(0) for _ in range(3)]
+        _chk(self.L.pirip_hip_rpt_records(self.h, C.byref(p[0]), C.byref(st[0]), C.byref(p[1]), C.byref(st[1]), C.byref(p[2]), C.byref(st[2]),
+                                          C.byref(p[3])), "pirip_hip_rpt_records")
+        return dict(status=int(p[0].value or 0), status_stride=int(st[0].value), payload=int(p[1].value or 0), payload_stride=int(st[1].value),
+                    info=int(p[2].value or 0), info_stride=int(st[2].value), nframes=int(p[3].value or 0))
+
+    def offered(self):
+        """(device pointer of the records offered in the last call, bytes per channel row, device pointer of the int32 [nchan] counts)"""
+        p, n, st = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        _chk(self.L.pirip_hip_rpt_offered(self.h, C.byref(p), C.byref(st), C.byref(n)), "pirip_hip_rpt_offered")
+        return int(p.value), int(st.value), int(n.value)
+
+    def counters(self):
+        """dict of int64 arrays -- [nrx]: bursts_in, frames_in, filtered, unrouted; [nchan]: bursts_out, pending, dropped. Synchronises."""
+        import numpy as np
+        names = ("bursts_in", "frames_in", "filtered", "unrouted", "bursts_out", "pending", "dropped")
+        out = {k: np.zeros(self.nrx if i < 4 else self.nchan, dtype=np.int64) for i, k in enumerate(names)}
+        _chk(self.L.pirip_hip_rpt_get_counters(self.h, *(out[k].ctypes.data for k in names)), "pirip_hip_rpt_get_counters")
+        return out
+
+    def reset(self, stream=None):
+        _chk(self.L.pirip_hip_rpt_reset(self.h, _hip_stream(stream)), "pirip_hip_rpt_reset")
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

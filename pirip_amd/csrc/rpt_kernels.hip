@@ -1,0 +1,425 @@
+// pirip_amd/csrc/rpt_kernels.hip -- include/pirip_hip.h section M: the streaming repeater.
+// One call per block: received FSK_LDPC records -> rtl_fsk's --filter -> frame_repeater.c's state machine -> finished bursts in a pending
+// ring per transmit channel -> whole bursts into section K's symbol queue when they are due and fit -> one block of wideband IQ.
+//
+//   intake:  records --rpt_intake_kernel (one wave per receive channel)--> pending ring of route[c]
+//   offer:   pending ring --rpt_offer_kernel (one wave per transmit channel)--> record rows --section K's send path--> symbol queue
+//   process: pirip_hip_txs_process
+//
+// Pending ring of a transmit channel: `pending` records of 1 + kb bytes, head and tail 64-bit record counts on the device. A burst is the
+// records 1, 0, ..., 0, 2; at the slot of its first record lie its length in records and its ready tag (the call from which it may be
+// offered). route's non-negative entries are distinct, so a ring has one writer; the offer of call n runs behind the intake of call n and
+// in front of the intake of call n + 1 (stream order), so head and tail are never written while they are read.
+// The call index n is host state advanced when a call is enqueued, as the sample index of section K.
+#include <hip/hip_runtime.h>
+
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/pirip_hip.h"
+#include "hip_host.hpp"
+#include "ldpc_handle.hpp"
+#include "rpt_handle.hpp"
+#include "tx_handle.hpp"
+#include "txs_handle.hpp"
+
+using namespace pirip;
+
+namespace {
+
+constexpr int kMaxCalls = 4096;            // the call table lives in LDS (as pirip_hip_tx_repeat_records')
+
+struct IntakeArgs {
+    const uint8_t *status; size_t status_stride; const uint8_t *payload; size_t payload_stride; const int32_t *ncalls_s; int ncalls;
+    int32_t *state;                        // [nrx][2] receiving, frames held
+    uint8_t *held;                         // [nrx][max_burst][kb]
+    const int32_t *route;                  // [nrx]
+    RptRxCount *cnt;                       // [nrx]
+    RptRing *rs;                           // [ntx]
+    uint8_t *ring; int64_t *ready; int32_t *blen;
+    int pending, kb, max_burst, source, filter;
+    int64_t ready_at;                      // n + holdoff
+};
+
+// Lane 0 walks the status bytes (staged in LDS with the filter applied) through tx_handle.hpp's state machine and then places every burst
+// that ended: its first record's offset behind the ring's tail, or nowhere (no route, or no room for all of it). The wave then copies the
+// payloads, lane-parallel: into the ring across its wrap, or into the handle for the burst that is still open.
+__global__ __launch_bounds__(64) void rpt_intake_kernel(IntakeArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
+    int32_t *s_act = (int32_t *)smem;                        // [ncalls] -1, or (burst << 16) | slot of the call's frame
+    int32_t *s_base = s_act + a.ncalls;                      // [ncalls + 1] a burst's first record behind the tail; -1 still open, -2 not kept
+    int32_t *s_n = s_base + a.ncalls + 1;                    // [ncalls + 1] frames of the burst
+    uint8_t *s_st = (uint8_t *)(s_n + a.ncalls + 1);         // [ncalls]
+    __shared__ int32_t s_hdr[4];                             // bursts, records out, receiving, frames held at the end
+    __shared__ int32_t s_start;                              // the ring slot of the tail
+    const int c = blockIdx.x, lane = threadIdx.x;
+    int nc = a.ncalls_s ? a.ncalls_s[c] : a.ncalls;
+    nc = nc < 0 ? 0 : (nc > a.ncalls ? a.ncalls : nc);
+    const uint8_t *st = a.status + (size_t)c * a.status_stride;
+    const uint8_t *pl = a.payload + (size_t)c * a.payload_stride;
+    uint8_t *held = a.held + (size_t)c * a.max_burst * a.kb;
+    const int rl = 1 + a.kb;
+    const int held0 = a.state[2 * c + 1];
+    const int t = a.route[c];
+    int nfilt = 0;
+    for (int i = lane; i < nc; i += 64) {                    // rtl_fsk --filter: a frame of the repeater's own is no frame
+        uint8_t v = st[i];
+        if ((v & PIRIP_RX_BITS) && a.filter >= 0 && pl[(size_t)i * a.kb] == (uint8_t)a.filter) { v = (uint8_t)(v & ~PIRIP_RX_BITS); nfilt++; }
+        s_st[i] = v;
+    }
+    for (int d = 32; d > 0; d >>= 1) nfilt += __shfl_down(nfilt, d, 64);
+    __syncthreads();
+    if (lane == 0) {
+        tx_repeat_walk([&](int i) { return (int)s_st[i]; }, nc, a.state[2 * c], held0, a.max_burst, s_act, s_base, s_n, s_hdr);
+        const int nb = s_hdr[0];
+        int64_t frames = 0, unrouted = 0, dropped = 0;
+        int off = 0, start = 0;
+        if (t >= 0) {
+            const uint64_t head = a.rs[t].head, tail = a.rs[t].tail;
+            int64_t room = (int64_t)a.pending - (int64_t)(tail - head);
+            start = (int)(tail % (uint64_t)a.pending);
+            for (int b = 0; b < nb; b++) {
+                const int len = s_n[b] + 1;
+                frames += s_n[b];
+                if (len <= room) {
+                    int slot = start + off;
+                    if (slot >= a.pending) slot -= a.pending;
+                    a.ready[(size_t)t * a.pending + slot] = a.ready_at;
+                    a.blen[(size_t)t * a.pending + slot] = len;
+                    s_base[b] = off; off += len; room -= len;
+                } else {
+                    s_base[b] = -2; dropped++;
+                }
+            }
+            a.rs[t].tail = tail + (uint64_t)off;
+            a.rs[t].dropped += dropped;
+        } else {
+            for (int b = 0; b < nb; b++) { frames += s_n[b]; s_base[b] = -2; unrouted++; }
+        }
+        s_start = start;
+        a.cnt[c].bursts += nb; a.cnt[c].frames += frames; a.cnt[c].filtered += nfilt; a.cnt[c].unrouted += unrouted;
+    }
+    __syncthreads();
+    const int nb = s_hdr[0], start = s_start;
+    uint8_t *ring = a.ring + (size_t)(t >= 0 ? t : 0) * a.pending * rl;
+    auto slot_of = [&](int j) { int s = start + j; return s >= a.pending ? s - a.pending : s; };
+    // frames that were held from earlier calls belong to burst 0: out they go if it ended here and is kept (else they stay or are forgotten)
+    if (held0 > 0 && nb > 0 && s_base[0] >= 0)
+        for (int i = lane; i < held0 * a.kb; i += 64) {
+            const int j = i / a.kb, o = i - j * a.kb;
+            uint8_t *rec = ring + (size_t)slot_of(s_base[0] + j) * rl;
+            rec[1 + o] = o == 0 ? (uint8_t)a.source : held[i];
+            if (o == 0) rec[0] = j == 0 ? 1 : 0;
+        }
+    __syncthreads();
+    for (int i = lane; i < nc * a.kb; i += 64) {
+        const int q = i / a.kb, o = i - q * a.kb;
+        const int act = s_act[q];
+        if (act < 0) continue;
+        const int b = act >> 16, slot = act & 0xffff;
+        const uint8_t v = pl[(size_t)q * a.kb + o];
+        if (s_base[b] >= 0) {
+            uint8_t *rec = ring + (size_t)slot_of(s_base[b] + slot) * rl;
+            rec[1 + o] = o == 0 ? (uint8_t)a.source : v;     // the repeater's own source address
+            if (o == 0) rec[0] = slot == 0 ? 1 : 0;
+        } else if (s_base[b] == -1) {
+            held[(size_t)slot * a.kb + o] = v;
+        }
+    }
+    for (int i = lane; i < nb * rl; i += 64) {               // end of burst: control byte 2, zero data
+        const int b = i / rl, o = i - b * rl;
+        if (s_base[b] >= 0) ring[(size_t)slot_of(s_base[b] + s_n[b]) * rl + o] = o == 0 ? 2 : 0;
+    }
+    if (lane == 0) { a.state[2 * c] = s_hdr[2]; a.state[2 * c + 1] = s_hdr[3]; }
+}
+
+struct OfferArgs {
+    RptRing *rs;                           // [ntx]
+    const uint8_t *ring; const int64_t *ready; const int32_t *blen;
+    const TxsChanState *queue; int64_t queue_syms;           // section K's queues: free space = queue_syms - (tail - head)
+    const int32_t *gap;                    // [ntx] tx's gaps (device)
+    uint8_t *rec; int32_t *nrec;           // [ntx][pending][1 + kb] and [ntx]: what section K's send path reads
+    int pending, rl, psyms, fsyms;
+    int64_t now;                           // n
+};
+
+// Every lane walks the ring's bursts from the head (the same loads and the same decisions in all of them: no divergence), then the wave
+// copies the taken records out of the ring, across its wrap, into the channel's row.
+__global__ __launch_bounds__(64) void rpt_offer_kernel(OfferArgs a)
+{
+    const int t = blockIdx.x, lane = threadIdx.x;
+    const uint64_t head = a.rs[t].head, tail = a.rs[t].tail;
+    int64_t room = a.queue_syms - (int64_t)(a.queue[t].tail - a.queue[t].head);
+    const int gap = a.gap[t] > 0 ? a.gap[t] : 0;              // tx_layout_kernel's rule
+    const int start = (int)(head % (uint64_t)a.pending);
+    int take = 0, bursts = 0;
+    while (head + (uint64_t)take < tail) {
+        int slot = start + take;
+        if (slot >= a.pending) slot -= a.pending;
+        const int len = a.blen[(size_t)t * a.pending + slot];
+        if (len < 2 || take + len > a.pending || a.ready[(size_t)t * a.pending + slot] > a.now) break;
+        const int64_t cost = (int64_t)a.psyms + (int64_t)(len - 1) * a.fsyms + gap;
+        if (cost > room) break;                              // head of the line: the bursts behind it wait
+        room -= cost; take += len; bursts++;
+    }
+    const uint8_t *ring = a.ring + (size_t)t * a.pending * a.rl;
+    uint8_t *out = a.rec + (size_t)t * a.pending * a.rl;
+    const int first = (a.pending - start) * a.rl;            // bytes up to the end of the ring
+    for (int i = lane; i < take * a.rl; i += 64) out[i] = i < first ? ring[(size_t)start * a.rl + i] : ring[i - first];
+    if (lane == 0) {
+        a.rs[t].head = head + (uint64_t)take;
+        a.rs[t].bursts_out += bursts;
+        a.nrec[t] = take;
+    }
+}
+
+int rpt_clear(pirip_hip_rpt *r, hipStream_t st)
+{
+    PIRIP_HIPCHK(hipMemsetAsync(r->d_state, 0, sizeof(int32_t) * 2 * (size_t)r->nrx, st));
+    PIRIP_HIPCHK(hipMemsetAsync(r->d_cnt, 0, sizeof(RptRxCount) * (size_t)r->nrx, st));
+    PIRIP_HIPCHK(hipMemsetAsync(r->d_ring_state, 0, sizeof(RptRing) * (size_t)r->ntx, st));
+    PIRIP_HIPCHK(hipMemsetAsync(r->d_noffered, 0, sizeof(int32_t) * (size_t)r->ntx, st));
+    r->calls = 0;
+    return PIRIP_OK;
+}
+
+int rpt_alloc(pirip_hip_rpt *r, const int32_t *route)
+{
+    const size_t nrx = (size_t)r->nrx, ntx = (size_t)r->ntx, P = (size_t)r->pending, rl = 1 + (size_t)r->kb;
+    DevMem &m = r->mem;
+    PIRIP_TRY(m.upload(&r->d_route, route, sizeof(int32_t) * nrx));
+    PIRIP_TRY(m.alloc(&r->d_state, sizeof(int32_t) * 2 * nrx));
+    PIRIP_TRY(m.alloc(&r->d_held, nrx * (size_t)r->max_burst * (size_t)r->kb));
+    PIRIP_TRY(m.alloc(&r->d_cnt, sizeof(RptRxCount) * nrx));
+    PIRIP_TRY(m.alloc(&r->d_ring_state, sizeof(RptRing) * ntx));
+    PIRIP_TRY(m.alloc(&r->d_ring, ntx * P * rl));
+    PIRIP_TRY(m.alloc(&r->d_ready, sizeof(int64_t) * ntx * P));
+    PIRIP_TRY(m.alloc(&r->d_blen, sizeof(int32_t) * ntx * P));
+    PIRIP_TRY(m.alloc(&r->d_offered, ntx * P * rl));
+    PIRIP_TRY(m.alloc(&r->d_noffered, sizeof(int32_t) * ntx));
+    PIRIP_HIPCHK(hipMemset(r->d_held, 0, nrx * (size_t)r->max_burst * (size_t)r->kb));
+    PIRIP_HIPCHK(hipMemset(r->d_ring, 0, ntx * P * rl));
+    PIRIP_HIPCHK(hipMemset(r->d_ready, 0, sizeof(int64_t) * ntx * P));
+    PIRIP_HIPCHK(hipMemset(r->d_blen, 0, sizeof(int32_t) * ntx * P));
+    PIRIP_HIPCHK(hipMemset(r->d_offered, 0, ntx * P * rl));
+    if (r->rx) {
+        const size_t R = (size_t)r->rx_rows;
+        PIRIP_TRY(m.alloc(&r->d_status, nrx * R));
+        PIRIP_TRY(m.alloc(&r->d_payload, nrx * R * (size_t)r->kb));
+        PIRIP_TRY(m.alloc(&r->d_info, sizeof(int32_t) * nrx * R * PIRIP_LDPC_INFO_PER_CALL));
+        PIRIP_TRY(m.alloc(&r->d_nframes, sizeof(int32_t) * nrx));
+        PIRIP_HIPCHK(hipMemset(r->d_status, 0, nrx * R));
+        PIRIP_HIPCHK(hipMemset(r->d_payload, 0, nrx * R * (size_t)r->kb));
+        PIRIP_HIPCHK(hipMemset(r->d_info, 0, sizeof(int32_t) * nrx * R * PIRIP_LDPC_INFO_PER_CALL));
+        PIRIP_HIPCHK(hipMemset(r->d_nframes, 0, sizeof(int32_t) * nrx));
+    }
+    PIRIP_TRY(txs_reserve(r->txs, r->pending));
+    PIRIP_TRY(rpt_clear(r, nullptr));
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    return PIRIP_OK;
+}
+
+// steps 1 - 3 over record rows that are on the device; the handle's device is current
+int rpt_run(pirip_hip_rpt *r, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride, const int32_t *d_ncalls,
+            int ncalls, void *d_out, size_t out_stride_bytes, hipStream_t st)
+{
+    const pirip_hip_tx *tx = r->tx;
+    IntakeArgs ia{};
+    ia.status = d_status; ia.status_stride = status_stride; ia.payload = d_payload; ia.payload_stride = payload_stride;
+    ia.ncalls_s = d_ncalls; ia.ncalls = ncalls;
+    ia.state = r->d_state; ia.held = r->d_held; ia.route = r->d_route; ia.cnt = r->d_cnt; ia.rs = r->d_ring_state;
+    ia.ring = r->d_ring; ia.ready = r->d_ready; ia.blen = r->d_blen;
+    ia.pending = r->pending; ia.kb = r->kb; ia.max_burst = r->max_burst; ia.source = r->source; ia.filter = r->filter;
+    ia.ready_at = r->calls + r->holdoff;
+    const size_t lds = sizeof(int32_t) * (3 * (size_t)ncalls + 2) + (size_t)ncalls + 16;
+    hipLaunchKernelGGL(rpt_intake_kernel, dim3((unsigned)r->nrx), dim3(64), lds, st, ia);
+    OfferArgs oa{};
+    oa.rs = r->d_ring_state; oa.ring = r->d_ring; oa.ready = r->d_ready; oa.blen = r->d_blen;
+    oa.queue = r->txs->d_state; oa.queue_syms = r->txs->queue_syms; oa.gap = tx->d_gap;
+    oa.rec = r->d_offered; oa.nrec = r->d_noffered;
+    oa.pending = r->pending; oa.rl = 1 + r->kb; oa.psyms = tx->pre_bits / tx->bps; oa.fsyms = tx->code.bits_per_frame() / tx->bps;
+    oa.now = r->calls;
+    hipLaunchKernelGGL(rpt_offer_kernel, dim3((unsigned)r->ntx), dim3(64), 0, st, oa);
+    PIRIP_HIPCHK(hipGetLastError());
+    PIRIP_TRY(pirip_hip_txs_send(r->txs, r->d_offered, (size_t)r->pending * (size_t)(1 + r->kb), r->d_noffered, r->pending, nullptr, st));
+    PIRIP_TRY(pirip_hip_txs_process(r->txs, d_out, out_stride_bytes, nullptr, st));
+    r->calls++;
+    return PIRIP_OK;
+}
+
+// txs_process's own checks, made before anything is enqueued: a call either runs whole or not at all
+int rpt_check_out(const pirip_hip_rpt *r, const void *d_out, size_t out_stride_bytes)
+{
+    pirip_txs_info ti{};
+    if (!d_out || pirip_hip_txs_get_info(r->txs, &ti) != PIRIP_OK) return PIRIP_ERR_BAD_ARG;
+    const size_t bs = ti.out_format == PIRIP_IN_CF32 ? 8 : 2;
+    if (((uintptr_t)d_out | out_stride_bytes) & (bs - 1)) return PIRIP_ERR_BAD_ARG;
+    if (ti.noutputs > 1 && out_stride_bytes < (size_t)ti.block * bs) return PIRIP_ERR_BAD_ARG;
+    return PIRIP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pirip_hip_rpt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, int nrx, const int32_t *route, int source_byte, int filter_byte,
+                         int holdoff_calls, int max_burst_frames, int pending_records, pirip_hip_rpt **out)
+{
+    if (!out) return PIRIP_ERR_BAD_ARG;
+    *out = nullptr;
+    if (!tx || !txs || !route || nrx < 1 || txs->tx != tx || txs->device != tx->device) return PIRIP_ERR_BAD_ARG;
+    if (source_byte < 0 || source_byte > 255 || filter_byte < -1 || filter_byte > 255 || holdoff_calls < 0) return PIRIP_ERR_BAD_ARG;
+    if (max_burst_frames < 1 || max_burst_frames > PIRIP_TX_REPEAT_MAX_FRAMES || pending_records < max_burst_frames + 1) return PIRIP_ERR_BAD_ARG;
+    const int ntx = tx->nstreams, kb = tx->code.data_bytes();
+    for (int c = 0; c < nrx; c++) {
+        if (route[c] >= ntx) return PIRIP_ERR_BAD_ARG;
+        for (int q = 0; q < c; q++) if (route[c] >= 0 && route[q] == route[c]) return PIRIP_ERR_BAD_ARG;
+    }
+    const int64_t psyms = tx->pre_bits / tx->bps, fsyms = tx->code.bits_per_frame() / tx->bps;
+    if (psyms + (int64_t)max_burst_frames * fsyms + tx->max_gap > txs->queue_syms) return PIRIP_ERR_BAD_ARG;
+    int rx_rows = 0;
+    if (rx) {
+        int ns = 0, dev = 0;
+        const pirip_hip_ldpc *ldpc = nullptr;
+        rx_handle_shape(rx, &ns, &ldpc, &dev);
+        if (!ldpc || ns != nrx || dev != tx->device || ldpc->code.data_bytes() != kb) return PIRIP_ERR_BAD_ARG;
+        const int64_t rows = pirip_hip_rx_max_frames(rx);
+        if (rows < 1) return PIRIP_ERR_BAD_ARG;
+        if (rows > kMaxCalls) return PIRIP_ERR_UNSUPPORTED;
+        rx_rows = (int)rows;
+    }
+    // what section K's send path asks of rows of pending_records records
+    int64_t cap = tx_row_syms(tx, pending_records, 0);
+    if (cap < 1) cap = 1;
+    PIRIP_TRY(tx_frame_check(tx, (size_t)pending_records * (size_t)(1 + kb), pending_records, (size_t)cap, cap, false, 0));
+    if (!bind_device(tx->device)) return PIRIP_ERR_NO_DEVICE;
+    pirip_hip_rpt *r = new (std::nothrow) pirip_hip_rpt();
+    if (!r) return PIRIP_ERR_NOMEM;
+    r->rx = rx; r->tx = tx; r->txs = txs; r->nrx = nrx; r->ntx = ntx; r->device = tx->device; r->kb = kb;
+    r->source = source_byte; r->filter = filter_byte; r->holdoff = holdoff_calls; r->max_burst = max_burst_frames; r->pending = pending_records;
+    r->rx_rows = rx_rows;
+    const int rc = rpt_alloc(r, route);
+    if (rc != PIRIP_OK) { delete r; return rc; }
+    *out = r;
+    return PIRIP_OK;
+}
+
+int pirip_hip_rpt_destroy(pirip_hip_rpt *r)
+{
+    if (!r) return PIRIP_ERR_BAD_ARG;
+    (void)bind_device(r->device);
+    (void)hipDeviceSynchronize();
+    delete r;
+    return PIRIP_OK;
+}
+
+int pirip_hip_rpt_get_info(const pirip_hip_rpt *r, pirip_rpt_info *info)
+{
+    if (!r || !info) return PIRIP_ERR_BAD_ARG;
+    *info = pirip_rpt_info{r->nrx, r->ntx, r->source, r->filter, r->holdoff, r->max_burst, r->pending, r->rx ? 1 : 0, r->rx_rows, r->device};
+    return PIRIP_OK;
+}
+
+int pirip_hip_rpt_push_records(pirip_hip_rpt *r, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                               const int32_t *d_ncalls, int ncalls, void *d_out, size_t out_stride_bytes, void *hip_stream)
+{
+    if (!r || !d_status || !d_payload || ncalls < 0) return PIRIP_ERR_BAD_ARG;
+    if (r->nrx > 1 && (status_stride < (size_t)ncalls || payload_stride < (size_t)ncalls * (size_t)r->kb)) return PIRIP_ERR_BAD_ARG;
+    if (ncalls > kMaxCalls) return PIRIP_ERR_UNSUPPORTED;
+    PIRIP_TRY(rpt_check_out(r, d_out, out_stride_bytes));
+    if (!bind_device(r->device)) return PIRIP_ERR_NO_DEVICE;
+    PIRIP_TRY(rpt_run(r, d_status, status_stride, d_payload, payload_stride, d_ncalls, ncalls, d_out, out_stride_bytes, (hipStream_t)hip_stream));
+    r->last_status = d_status; r->last_status_stride = status_stride; r->last_payload = d_payload; r->last_payload_stride = payload_stride;
+    r->last_info = nullptr; r->last_info_stride = 0; r->last_nframes = d_ncalls;
+    return PIRIP_OK;
+}
+
+static int rpt_receive(pirip_hip_rpt *r, const void *d_in, size_t in_stride_bytes, void *d_out, size_t out_stride_bytes, void *hip_stream)
+{
+    if (!r || !r->rx) return PIRIP_ERR_BAD_ARG;
+    PIRIP_TRY(rpt_check_out(r, d_out, out_stride_bytes));
+    if (!bind_device(r->device)) return PIRIP_ERR_NO_DEVICE;
+    const size_t R = (size_t)r->rx_rows;
+    if (d_in)
+        PIRIP_TRY(pirip_hip_rx_push(r->rx, d_in, in_stride_bytes, nullptr, 0, nullptr, 0, r->d_status, r->d_payload, r->d_info, nullptr, 0, r->d_nframes,
+                                    hip_stream));
+    else
+        PIRIP_TRY(pirip_hip_rx_process(r->rx, nullptr, 0, nullptr, 0, r->d_status, r->d_payload, r->d_info, nullptr, 0, r->d_nframes, hip_stream));
+    r->last_status = r->d_status; r->last_status_stride = R; r->last_payload = r->d_payload; r->last_payload_stride = R * (size_t)r->kb;
+    r->last_info = r->d_info; r->last_info_stride = R * PIRIP_LDPC_INFO_PER_CALL; r->last_nframes = r->d_nframes;
+    return rpt_run(r, r->d_status, R, r->d_payload, R * (size_t)r->kb, r->d_nframes, r->rx_rows, d_out, out_stride_bytes, (hipStream_t)hip_stream);
+}
+
+int pirip_hip_rpt_process(pirip_hip_rpt *r, void *d_out, size_t out_stride_bytes, void *hip_stream)
+{
+    return rpt_receive(r, nullptr, 0, d_out, out_stride_bytes, hip_stream);
+}
+
+int pirip_hip_rpt_push(pirip_hip_rpt *r, const void *d_in, size_t in_stride_bytes, void *d_out, size_t out_stride_bytes, void *hip_stream)
+{
+    if (!d_in) return PIRIP_ERR_BAD_ARG;
+    return rpt_receive(r, d_in, in_stride_bytes, d_out, out_stride_bytes, hip_stream);
+}
+
+int pirip_hip_rpt_records(pirip_hip_rpt *r, const uint8_t **d_status, size_t *status_stride, const uint8_t **d_payload, size_t *payload_stride,
+                          const int32_t **d_info, size_t *info_stride, const int32_t **d_nframes)
+{
+    if (!r || !r->last_status) return PIRIP_ERR_BAD_ARG;
+    if (d_status) *d_status = r->last_status;
+    if (status_stride) *status_stride = r->last_status_stride;
+    if (d_payload) *d_payload = r->last_payload;
+    if (payload_stride) *payload_stride = r->last_payload_stride;
+    if (d_info) *d_info = r->last_info;
+    if (info_stride) *info_stride = r->last_info_stride;
+    if (d_nframes) *d_nframes = r->last_nframes;
+    return PIRIP_OK;
+}
+
+int pirip_hip_rpt_offered(pirip_hip_rpt *r, const uint8_t **d_records, size_t *rec_stride, const int32_t **d_nrec)
+{
+    if (!r) return PIRIP_ERR_BAD_ARG;
+    if (d_records) *d_records = r->d_offered;
+    if (rec_stride) *rec_stride = (size_t)r->pending * (size_t)(1 + r->kb);
+    if (d_nrec) *d_nrec = r->d_noffered;
+    return PIRIP_OK;
+}
+
+int pirip_hip_rpt_get_counters(pirip_hip_rpt *r, int64_t *bursts_in, int64_t *frames_in, int64_t *filtered, int64_t *unrouted,
+                               int64_t *bursts_out, int64_t *pending, int64_t *dropped)
+{
+    if (!r) return PIRIP_ERR_BAD_ARG;
+    if (!bind_device(r->device)) return PIRIP_ERR_NO_DEVICE;
+    std::vector<RptRxCount> rc((size_t)r->nrx);
+    std::vector<RptRing> rs((size_t)r->ntx);
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipMemcpy(rc.data(), r->d_cnt, sizeof(RptRxCount) * rc.size(), hipMemcpyDeviceToHost));
+    PIRIP_HIPCHK(hipMemcpy(rs.data(), r->d_ring_state, sizeof(RptRing) * rs.size(), hipMemcpyDeviceToHost));
+    for (size_t c = 0; c < rc.size(); c++) {
+        if (bursts_in) bursts_in[c] = rc[c].bursts;
+        if (frames_in) frames_in[c] = rc[c].frames;
+        if (filtered) filtered[c] = rc[c].filtered;
+        if (unrouted) unrouted[c] = rc[c].unrouted;
+    }
+    for (size_t t = 0; t < rs.size(); t++) {
+        if (bursts_out) bursts_out[t] = rs[t].bursts_out;
+        if (pending) pending[t] = (int64_t)(rs[t].tail - rs[t].head);
+        if (dropped) dropped[t] = rs[t].dropped;
+    }
+    return PIRIP_OK;
+}
+
+int pirip_hip_rpt_reset(pirip_hip_rpt *r, void *hip_stream)
+{
+    if (!r) return PIRIP_ERR_BAD_ARG;
+    if (!bind_device(r->device)) return PIRIP_ERR_NO_DEVICE;
+    PIRIP_TRY(rpt_clear(r, (hipStream_t)hip_stream));
+    PIRIP_TRY(pirip_hip_txs_reset(r->txs, hip_stream));
+    if (r->rx) PIRIP_TRY(pirip_hip_rx_reset(r->rx, hip_stream));
+    r->last_status = nullptr;
+    return PIRIP_OK;
+}
+
+}  // extern "C"

@@ -22,6 +22,7 @@
 #include "fsk_device.hpp"
 #include "demod_handle.hpp"
 #include "rate_host.hpp"
+#include "rpt_handle.hpp"
 
 using namespace pirip;
 
@@ -257,6 +258,12 @@ int rx_create_impl(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *
 }
 
 }  // namespace
+
+// what the streaming repeater (rpt_kernels.hip) asks of a receiver it borrows
+void pirip::rx_handle_shape(const pirip_hip_rx *rx, int *nstreams, const pirip_hip_ldpc **ldpc, int *device)
+{
+    *nstreams = rx->nstreams; *ldpc = rx->ldpc; *device = rx->dem->device;
+}
 
 extern "C" {
 

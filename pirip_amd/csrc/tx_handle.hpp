@@ -1,5 +1,6 @@
 // pirip_amd/csrc/tx_handle.hpp -- the transmitter's handle behind include/pirip_hip.h's opaque pirip_hip_tx, and what the streaming
-// transmitter (txs_kernels.hip, section K) needs of section I (library-private: tx_kernels.hip owns the life cycle and the entry points).
+// transmitter (txs_kernels.hip, section K) and the streaming repeater (rpt_kernels.hip, section M) need of section I (library-private:
+// tx_kernels.hip owns the life cycle and the entry points).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -68,6 +69,33 @@ __device__ __forceinline__ uint32_t tx_scan_row(SymAt sym, int64_t total, const 
         __syncthreads();
     }
     return carry;
+}
+
+// The repeater's state machine (tx/frame_repeater.c:68-107) over nc status bytes, run by ONE lane: tx_repeat_kernel's walk, shared with
+// the streaming repeater's intake (rpt_kernels.hip). status(c): the call's rx_status. receiving / n: the stream's state carried in (a burst
+// is open; the frames it holds). A burst starts at a status of exactly SYNC | BITS, takes every later record with BITS while it holds
+// fewer than max_burst frames (further frames are dropped where the original asserts) and ends at the first record without SYNC.
+// Writes act[c] = -1, or (burst << 16) | slot of the call's frame; for every burst b that ended here base[b] = its first output record
+// (bursts laid out one after the other, each followed by its end record) and nfr[b] = its frames; base[bursts] = -1 and nfr[bursts] = the
+// frames of the burst still open. hdr = {bursts ended, records out, receiving, frames held at the end}.
+template <typename StatusAt>
+__device__ __forceinline__ void tx_repeat_walk(StatusAt status, int nc, int receiving, int n, int max_burst, int32_t *act_out, int32_t *base,
+                                               int32_t *nfr, int32_t *hdr)
+{
+    int b = 0, nout = 0;
+    for (int c = 0; c < nc; c++) {
+        const int v = status(c);
+        int act = -1;
+        if (!receiving) {
+            if (v == (PIRIP_RX_SYNC | PIRIP_RX_BITS)) { receiving = 1; n = 1; act = (b << 16) | 0; }
+        } else {
+            if ((v & PIRIP_RX_BITS) && n < max_burst) { act = (b << 16) | n; n++; }
+            if (!(v & PIRIP_RX_SYNC)) { base[b] = nout; nfr[b] = n; nout += n + 1; b++; receiving = 0; n = 0; }
+        }
+        act_out[c] = act;
+    }
+    base[b] = -1; nfr[b] = n;
+    hdr[0] = b; hdr[1] = nout; hdr[2] = receiving; hdr[3] = receiving ? n : 0;
 }
 
 }  // namespace pirip

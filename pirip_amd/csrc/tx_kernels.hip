@@ -326,22 +326,7 @@ __global__ __launch_bounds__(64) void tx_repeat_kernel(RepeatArgs a)
     const int held0 = a.state[2 * s + 1];
     for (int c = lane; c < nc; c += 64) s_st[c] = st[c];
     __syncthreads();
-    if (lane == 0) {
-        int receiving = a.state[2 * s], n = held0, b = 0, nout = 0;
-        for (int c = 0; c < nc; c++) {
-            const int v = s_st[c];
-            int act = -1;
-            if (!receiving) {
-                if (v == (PIRIP_RX_SYNC | PIRIP_RX_BITS)) { receiving = 1; n = 1; act = (b << 16) | 0; }
-            } else {
-                if ((v & PIRIP_RX_BITS) && n < a.max_burst) { act = (b << 16) | n; n++; }
-                if (!(v & PIRIP_RX_SYNC)) { s_base[b] = nout; s_n[b] = n; nout += n + 1; b++; receiving = 0; n = 0; }
-            }
-            s_act[c] = act;
-        }
-        s_base[b] = -1; s_n[b] = n;
-        s_hdr[0] = b; s_hdr[1] = nout; s_hdr[2] = receiving; s_hdr[3] = receiving ? n : 0;
-    }
+    if (lane == 0) tx_repeat_walk([&](int c) { return (int)s_st[c]; }, nc, a.state[2 * s], held0, a.max_burst, s_act, s_base, s_n, s_hdr);
     __syncthreads();
     const int nb = s_hdr[0];
     // frames that were held from earlier calls belong to burst 0: out they go if it ended here (else they stay where they are)

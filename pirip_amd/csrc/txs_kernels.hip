@@ -31,6 +31,7 @@
 #include "iq_device.hpp"
 #include "mux_handle.hpp"
 #include "tx_handle.hpp"
+#include "txs_handle.hpp"
 
 using namespace pirip;
 
@@ -39,11 +40,7 @@ namespace {
 constexpr int kAppendThreads = 256;
 constexpr uint8_t kOff = PIRIP_TX_CARRIER_OFF;
 
-struct ChanState {
-    uint64_t head, tail;                   // symbols dequeued / queued since create / reset; the ring holds [head, tail)
-    int64_t sent, underrun, refused;
-    uint32_t phase, pad;                   // the modulator's phase integer after the last dequeued symbol
-};
+using ChanState = TxsChanState;
 
 struct AppendArgs {
     const uint8_t *frm; size_t frm_stride; const int32_t *nsym;      // the framer's rows of this call
@@ -165,28 +162,6 @@ __global__ __launch_bounds__(kMuxThreads) void txs_mux_kernel(MuxArgs a, SymStag
 
 }  // namespace
 
-// (hidden: a handle's implicit destructor is no dynamic symbol of the library)
-#pragma GCC visibility push(hidden)
-struct pirip_hip_txs {
-    pirip_hip_tx *tx = nullptr;
-    pirip_hip_mux *mux = nullptr;
-    int nchan = 0, device = 0, S = 0, H = 0;
-    int64_t block = 0, queue_syms = 0;
-    int64_t calls = 0;                     // process calls since create / reset: call k starts at modem sample k S Ts
-    size_t row = 0;                        // H + S
-    DevMem mem;
-    uint8_t *d_ring = nullptr;             // [nchan][queue_syms]
-    ChanState *d_state = nullptr;          // [nchan]
-    uint8_t *d_sy = nullptr;               // [2][nchan][row]
-    uint32_t *d_pre = nullptr;             // [2][nchan][row]
-    int32_t *d_no_lead = nullptr;          // [nchan] zeros: a streaming transmitter's silence is its empty queue
-    // the framer's rows of a send, grown on demand
-    uint8_t *d_frm = nullptr; size_t frm_cap = 0;            // [nchan][frm_cap]
-    int32_t *d_off = nullptr; size_t off_cap = 0;            // [nchan][off_cap]
-    int32_t *d_nsym = nullptr;             // [nchan]
-};
-#pragma GCC visibility pop
-
 namespace {
 
 int txs_clear(pirip_hip_txs *t, hipStream_t st)
@@ -217,6 +192,21 @@ int txs_alloc(pirip_hip_txs *t)
 }
 
 }  // namespace
+
+// the framer's rows of a send of max_rec records per channel (rows of a call larger than any before it: calls in flight may still use
+// the ones they replace); the handle's device is current
+int pirip::txs_reserve(pirip_hip_txs *t, int max_rec)
+{
+    int64_t cap = tx_row_syms(t->tx, max_rec, 0);
+    if (cap < 1) cap = 1;
+    if ((size_t)cap > t->frm_cap)
+        PIRIP_TRY(grow_dev(t->mem, &t->frm_cap, (size_t)cap, t->d_frm ? GrowSync::device : GrowSync::none, nullptr,
+                           {grow_buf(&t->d_frm, (size_t)t->nchan * (size_t)cap)}));
+    if ((size_t)max_rec > t->off_cap)
+        PIRIP_TRY(grow_dev(t->mem, &t->off_cap, (size_t)max_rec, t->d_off ? GrowSync::device : GrowSync::none, nullptr,
+                           {grow_buf(&t->d_off, sizeof(int32_t) * (size_t)t->nchan * (size_t)max_rec)}));
+    return PIRIP_OK;
+}
 
 extern "C" {
 
@@ -269,13 +259,7 @@ int pirip_hip_txs_send(pirip_hip_txs *t, const uint8_t *d_records, size_t rec_st
     if (cap < 1) cap = 1;
     PIRIP_TRY(tx_frame_check(tx, rec_stride, max_rec, (size_t)cap, cap, false, 0));
     if (!bind_device(t->device)) return PIRIP_ERR_NO_DEVICE;
-    // (rows of a call larger than any before it: calls in flight may still use the ones they replace)
-    if ((size_t)cap > t->frm_cap)
-        PIRIP_TRY(grow_dev(t->mem, &t->frm_cap, (size_t)cap, t->d_frm ? GrowSync::device : GrowSync::none, nullptr,
-                           {grow_buf(&t->d_frm, (size_t)t->nchan * (size_t)cap)}));
-    if ((size_t)max_rec > t->off_cap)
-        PIRIP_TRY(grow_dev(t->mem, &t->off_cap, (size_t)max_rec, t->d_off ? GrowSync::device : GrowSync::none, nullptr,
-                           {grow_buf(&t->d_off, sizeof(int32_t) * (size_t)t->nchan * (size_t)max_rec)}));
+    PIRIP_TRY(txs_reserve(t, max_rec));
     hipStream_t st = (hipStream_t)hip_stream;
     PIRIP_TRY(tx_frame_rows(tx, d_records, rec_stride, d_nrec, max_rec, t->d_frm, t->frm_cap, cap, t->d_nsym, nullptr, 0, t->d_no_lead, t->d_off, st));
     const AppendArgs a{t->d_frm, t->frm_cap, t->d_nsym, d_nrec, max_rec, t->d_ring, t->queue_syms, t->d_state, d_taken};
