@@ -18,8 +18,6 @@
 //   rx <c>: bursts B frames F filtered X unrouted U        tx <t>: bursts B pending P dropped D
 // Exit codes: 1 arguments / files, 2 the code file or a handle that cannot be made, 3 a device error.
 #include <getopt.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <cstdio>
 #include <cstdlib>
@@ -27,9 +25,7 @@
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime_api.h>
-
-#include "../../include/pirip_hip.h"
+#include "tool_common.hpp"
 
 static int usage()
 {
@@ -40,48 +36,11 @@ static int usage()
     return 1;
 }
 
-static bool file_exists(const std::string &p) { struct stat st; return !p.empty() && stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-
-// --code NAME: NAME as a file path, then $PIRIP_CODE_DIR/NAME.code, then <exe>/../data/NAME.code (as rtl_fsk_channels resolves it)
-static std::string resolve_code(const std::string &name, const char *argv0)
-{
-    if (file_exists(name)) return name;
-    if (const char *d = getenv("PIRIP_CODE_DIR")) { const std::string p = std::string(d) + "/" + name + ".code"; if (file_exists(p)) return p; }
-    char exe[4096];
-    const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1);
-    std::string base = n > 0 ? std::string(exe, (size_t)n) : std::string(argv0);
-    const size_t s = base.rfind('/');
-    base = s == std::string::npos ? "." : base.substr(0, s);
-    const std::string p = base + "/../data/" + name + ".code";
-    return file_exists(p) ? p : std::string();
-}
-
-template <typename T, typename F>
-static bool parse_list(const char *s, std::vector<T> &out, F conv)
-{
-    const std::string all(s);
-    for (size_t pos = 0; pos <= all.size();) {
-        size_t end = all.find(',', pos);
-        if (end == std::string::npos) end = all.size();
-        const std::string tok = all.substr(pos, end - pos);
-        if (tok.empty()) return false;
-        char *e = nullptr;
-        const T v = conv(tok.c_str(), &e);
-        if (*e) return false;
-        out.push_back(v);
-        pos = end + 1;
-    }
-    return !out.empty();
-}
-
-#define HIPOK(expr) do { if ((expr) != hipSuccess) { fprintf(stderr, "frame_repeater_channels: HIP error at %s:%d\n", __FILE__, __LINE__); return 3; } } while (0)
-#define PIRIPOK(expr, what) do { const int rc_ = (expr); if (rc_ != PIRIP_OK) { fprintf(stderr, "frame_repeater_channels: %s: %s\n", what, pirip_hip_strerror(rc_)); return rc_ == PIRIP_ERR_HIP ? 3 : 2; } } while (0)
+static const ToolErrors kTool{"frame_repeater_channels", [](int status) { return status == PIRIP_ERR_HIP ? 3 : 2; }};
 
 int main(int argc, char **argv)
 {
-    if (!pirip_hip_abi_check(PIRIP_HIP_ABI_VERSION, PIRIP_STATS_PER_FRAME, sizeof(pirip_stream_state))) {
-        fprintf(stderr, "%s: built against a different pirip_hip.h than %s\n", argv[0], pirip_hip_version()); return 2;
-    }
+    if (!abi_ok(argv[0])) return 2;
     long wideFs = 0, modemFs = 0, Rs = 0;
     int M = 2, mask = 0, quiet = 0, fsk_lower = 0, fsk_upper = 0, user_lower = 0, user_upper = 0;
     int f1 = 0, have_f1 = 0, shift = 0, linear = 0, gap = 0, source = -1, filter = -1, holdoff = 0, max_burst = PIRIP_TX_REPEAT_MAX_FRAMES, pending = 0;
@@ -97,7 +56,6 @@ int main(int argc, char **argv)
                                     {"source", required_argument, 0, 1020}, {"filter", required_argument, 0, 1021}, {"route", required_argument, 0, 1022},
                                     {"holdoff", required_argument, 0, 1023}, {"max-burst", required_argument, 0, 1024},
                                     {"pending", required_argument, 0, 1025}, {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
-    auto to_i32 = [](const char *t, char **e) { return (int32_t)strtol(t, e, 10); };
     int o, oi;
     while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:qh", lopts, &oi)) != -1) {
         switch (o) {
@@ -105,7 +63,7 @@ int main(int argc, char **argv)
         case 'a': modemFs = (long)atof(optarg); break;
         case 'r': Rs = (long)atof(optarg); break;
         case 'm': M = atoi(optarg); break;
-        case 'c': if (!parse_list(optarg, offsets, to_i32)) { fprintf(stderr, "frame_repeater_channels: -c wants integer offsets in Hz, comma separated\n"); return 1; } break;
+        case 'c': if (!parse_list(optarg, offsets, conv_i32)) { fprintf(stderr, "frame_repeater_channels: -c wants integer offsets in Hz, comma separated\n"); return 1; } break;
         case 'i': in_name = optarg; break;
         case 'o': out_name = optarg; break;
         case 'q': quiet = 1; break;
@@ -115,14 +73,14 @@ int main(int argc, char **argv)
         case 1003: fsk_upper = atoi(optarg); user_upper = 1; break;
         case 1006: f1 = atoi(optarg); have_f1 = 1; break;
         case 1007: shift = atoi(optarg); break;
-        case 1009: if (!parse_list(optarg, gains, [](const char *t, char **e) { return strtof(t, e); })) { fprintf(stderr, "frame_repeater_channels: --gain g or --gains g1,g2,...\n"); return 1; } break;
+        case 1009: if (!parse_list(optarg, gains, conv_float)) { fprintf(stderr, "frame_repeater_channels: --gain g or --gains g1,g2,...\n"); return 1; } break;
         case 1010: linear = 1; break;
         case 1011: gap = atoi(optarg); break;
         case 1013: block = atoll(optarg); break;
         case 1014: queue = atoll(optarg); break;
         case 1020: source = (int)strtol(optarg, nullptr, 0); break;
         case 1021: filter = (int)strtol(optarg, nullptr, 0); break;
-        case 1022: if (!parse_list(optarg, route, to_i32)) { fprintf(stderr, "frame_repeater_channels: --route wants one transmit channel per receive channel, -1 = none\n"); return 1; } break;
+        case 1022: if (!parse_list(optarg, route, conv_i32)) { fprintf(stderr, "frame_repeater_channels: --route wants one transmit channel per receive channel, -1 = none\n"); return 1; } break;
         case 1023: holdoff = atoi(optarg); break;
         case 1024: max_burst = atoi(optarg); break;
         case 1025: pending = atoi(optarg); break;
@@ -145,40 +103,36 @@ int main(int argc, char **argv)
     if ((int)gains.size() != K) { fprintf(stderr, "frame_repeater_channels: one gain, or one per channel\n"); return 1; }
     const int D = (int)(wideFs / modemFs), Fs = (int)modemFs, Ts = Fs / (int)Rs;
     if (block % ((long long)D * Ts)) { fprintf(stderr, "frame_repeater_channels: --block must be a multiple of D * Ts = %lld wideband samples\n", (long long)D * Ts); return 1; }
-    int P = Ts;
-    while (P > 10 && (P % 2) == 0) P /= 2;                       // rtl_fsk's oversample rule
-    if (P < 4) P = Ts;
-    if (!user_lower) fsk_lower = (int)Rs / 2;
-    if (!user_upper) fsk_upper = Fs / 2;
     const std::string code_path = resolve_code(code, argv[0]);
     if (code_path.empty()) {
         fprintf(stderr, "frame_repeater_channels: no table for --code %s (format: pirip_amd/csrc/fsk_ldpc.hpp; $PIRIP_CODE_DIR or a file path)\n", code.c_str());
         return 2;
     }
-    FILE *fin = in_name == "-" ? stdin : fopen(in_name.c_str(), "rb");
+    File fin(in_name == "-" ? stdin : fopen(in_name.c_str(), "rb"));
     if (!fin) { fprintf(stderr, "frame_repeater_channels: can't open %s\n", in_name.c_str()); return 1; }
-    FILE *fout = out_name == "-" ? stdout : fopen(out_name.c_str(), "wb");
+    File fout(out_name == "-" ? stdout : fopen(out_name.c_str(), "wb"));
     if (!fout) { fprintf(stderr, "frame_repeater_channels: can't open %s\n", out_name.c_str()); return 1; }
 
     // receive side: K channels of one capture -> FSK_LDPC records (rtl_fsk_channels' handles)
     std::vector<int32_t> zeros((size_t)K, 0), f1s((size_t)K, f1), gaps((size_t)K, gap / bps);
-    pirip_hip_chan *chan = nullptr;
-    pirip_hip_demod *dem = nullptr;
-    pirip_hip_ldpc *ldpc = nullptr;
-    pirip_hip_rx *rx = nullptr;
-    PIRIPOK(pirip_hip_chan_create((int)wideFs, D, 0.05f, 0, 1, K, zeros.data(), offsets.data(), -1, &chan), "channelizer");
-    pirip_fsk_params prm{Fs, (int)Rs, M, P, PIRIP_FSK_DEFAULT_NSYM, fsk_lower, fsk_upper, mask ? 1 : 0, mask ? mask : 100, PIRIP_IN_CF32};
-    PIRIPOK(pirip_hip_create(&prm, K, -1, &dem), "demodulator");
-    PIRIPOK(pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, K, -1, &ldpc), "--code");
-    PIRIPOK(pirip_hip_rx_create_chan(dem, ldpc, chan, block, &rx), "receiver (--block)");
+    ChanHandle chan;
+    DemodHandle dem;
+    LdpcHandle ldpc;
+    RxHandle rx;
+    TxHandle tx;
+    MuxHandle mux;
+    TxsHandle txs;
+    RptHandle rpt;
+    PIRIPOK(pirip_hip_chan_create((int)wideFs, D, 0.05f, 0, 1, K, zeros.data(), offsets.data(), -1, chan.out()), "channelizer");
+    // rtl_fsk's modem settings, under its default rules
+    const pirip_fsk_params prm = rtl_fsk_params(Fs, (int)Rs, M, mask, user_lower ? &fsk_lower : nullptr, user_upper ? &fsk_upper : nullptr, PIRIP_IN_CF32);
+    PIRIPOK(pirip_hip_create(&prm, K, -1, dem.out()), "demodulator");
+    PIRIPOK(pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, K, -1, ldpc.out()), "--code");
+    PIRIPOK(pirip_hip_rx_create_chan(dem, ldpc, chan, block, rx.out()), "receiver (--block)");
     // transmit side: fsk_ldpc_tx_channels --block's handles on the same offsets
-    pirip_hip_tx *tx = nullptr;
-    pirip_hip_mux *mux = nullptr;
-    pirip_hip_txs *txs = nullptr;
-    pirip_hip_rpt *rpt = nullptr;
-    PIRIPOK(pirip_hip_tx_create(code_path.c_str(), Fs, (int)Rs, M, K, -1, &tx), "transmitter");
+    PIRIPOK(pirip_hip_tx_create(code_path.c_str(), Fs, (int)Rs, M, K, -1, tx.out()), "transmitter");
     PIRIPOK(pirip_hip_mux_create((int)wideFs, D, linear ? PIRIP_MUX_LINEAR : PIRIP_MUX_FIR, 0.05f, PIRIP_IN_CU8_CSDR, 1, K, zeros.data(), offsets.data(),
-                                 gains.data(), -1, &mux), "multiplexer");
+                                 gains.data(), -1, mux.out()), "multiplexer");
     PIRIPOK(pirip_hip_tx_set_tones(tx, f1s.data(), shift), "--f1 / --shift");
     PIRIPOK(pirip_hip_tx_set_gaps(tx, nullptr, gaps.data()), "--gap");
     pirip_tx_info ti;
@@ -186,17 +140,18 @@ int main(int argc, char **argv)
     const long long burst = (long long)ti.preamble_syms + (long long)max_burst * ti.frame_syms + gap / bps, S = block / ((long long)D * Ts);
     if (queue <= 0) queue = burst + S;
     if (queue < burst) { fprintf(stderr, "frame_repeater_channels: --queue %lld cannot hold the largest burst, %lld symbols\n", queue, burst); return 1; }
-    PIRIPOK(pirip_hip_txs_create(tx, mux, block, queue, &txs), "streaming transmitter");
-    PIRIPOK(pirip_hip_rpt_create(rx, tx, txs, K, route.data(), source, filter, holdoff, max_burst, pending, &rpt), "repeater (--route / --pending)");
+    PIRIPOK(pirip_hip_txs_create(tx, mux, block, queue, txs.out()), "streaming transmitter");
+    PIRIPOK(pirip_hip_rpt_create(rx, tx, txs, K, route.data(), source, filter, holdoff, max_burst, pending, rpt.out()), "repeater (--route / --pending)");
     if (!quiet)
         fprintf(stderr, "frame_repeater_channels: wide rate %ld Fs %d Rs %ld M %d P %d D %d channels %d block %lld (%lld symbols) queue %lld source %d filter %d "
-                        "holdoff %d max-burst %d pending %d\n", wideFs, Fs, Rs, M, P, D, K, block, S, queue, source, filter, holdoff, max_burst, pending);
+                        "holdoff %d max-burst %d pending %d\n", wideFs, Fs, Rs, M, prm.P, D, K, block, S, queue, source, filter, holdoff, max_burst, pending);
 
-    void *d_in = nullptr, *d_out = nullptr;
+    void *d_in = nullptr;
+    DevBuf<void> d_out;
     size_t in_stride = 0;
     PIRIPOK(pirip_hip_rx_input(rx, &d_in, &in_stride), "receiver input");
     const size_t blk_bytes = (size_t)block * 2;
-    HIPOK(hipMalloc(&d_out, blk_bytes));
+    HIPOK(hipMalloc(d_out.out(), blk_bytes));
     std::vector<uint8_t> raw(blk_bytes), out(blk_bytes);
     long blocks = 0;
     for (;;) {
@@ -217,16 +172,5 @@ int main(int argc, char **argv)
                 (long long)cr[(size_t)(2 * K + c)], (long long)cr[(size_t)(3 * K + c)]);
     for (int t = 0; t < K; t++)
         fprintf(stderr, "tx %d: bursts %lld pending %lld dropped %lld\n", t, (long long)ct[(size_t)t], (long long)ct[(size_t)(K + t)], (long long)ct[(size_t)(2 * K + t)]);
-    if (fin != stdin) fclose(fin);
-    if (fout != stdout) fclose(fout);
-    pirip_hip_rpt_destroy(rpt);
-    pirip_hip_txs_destroy(txs);
-    pirip_hip_mux_destroy(mux);
-    pirip_hip_tx_destroy(tx);
-    pirip_hip_rx_destroy(rx);
-    pirip_hip_ldpc_destroy(ldpc);
-    pirip_hip_destroy(dem);
-    pirip_hip_chan_destroy(chan);
-    (void)hipFree(d_out);
     return 0;
 }

@@ -26,14 +26,11 @@
 #include <cstdlib>
 #include <cstring>
 #include <vector>
-#include "../../include/pirip_hip.h"
+#include "tool_common.hpp"
 
 int main(int argc, char **argv)
 {
-    {   // a binary compiled against another header generation must not run against this library (stats rows, stream state sizes)
-        const int abi_ok = pirip_hip_abi_check(PIRIP_HIP_ABI_VERSION, PIRIP_STATS_PER_FRAME, sizeof(pirip_stream_state));
-        if (!abi_ok) { fprintf(stderr, "%s: built against a different pirip_hip.h than %s\n", argv[0], pirip_hip_version()); return 2; }
-    }
+    if (!abi_ok(argv[0])) return 2;
     int complex_in = 0, u8_in = 0, soft = 0, P = PIRIP_FSK_DEFAULT_P, mask = 0, nsym = PIRIP_FSK_DEFAULT_NSYM;
     int user_lower = 0, user_upper = 0, fsk_lower = 0, fsk_upper = 0, testmode = 0;
     static struct option lopts[] = {
@@ -110,10 +107,9 @@ int main(int argc, char **argv)
     if (testmode) chunk_frames = 1;                                    // statistics are read back after every frame
     if (chunk_frames < 1) chunk_frames = 1;
     const size_t chunk = (size_t)chunk_frames * info.N;
-    // frames a buffer of (carry + chunk) samples can hold when every frame is the short one (nin = N - Ts/4):
+    // frames a buffer of (carry + chunk) samples can hold when every frame is the shortest one:
     // every call demodulates ALL whole frames present, so the carry stays below nin_max and buf never overflows
-    const size_t nin_min = (size_t)(info.N - info.Ts / 4);
-    const int64_t max_frames = (int64_t)((chunk + (size_t)info.nin_max) / nin_min) + 2;
+    const int64_t max_frames = (int64_t)((chunk + (size_t)info.nin_max) / (size_t)shortest_frame(info)) + 2;
 
     std::vector<uint8_t> buf((chunk + info.nin_max) * bps_dev);       // [carry | new]
     std::vector<uint8_t> rd(chunk * bps_file);

@@ -22,7 +22,7 @@
 #include <string>
 #include <vector>
 
-#include "fsk_ldpc.hpp"
+#include "tx_records.hpp"
 
 using namespace pirip;
 
@@ -65,12 +65,10 @@ int main(int argc, char **argv)
     const std::vector<uint8_t> pre = preamble_bits(M);
 
     if (testframes > 0) {
-        testframe_payload(data.data(), k);
         for (int b = 0; b < bursts; b++) {
             fwrite(pre.data(), 1, pre.size(), fout);
             for (int f = 0; f < testframes; f++) {
-                if (source >= 0) for (int i = 0; i < 8; i++) data[i] = (source >> (7 - i)) & 1;
-                if (seq) { const int s = (f + 1) & 0xff; for (int i = 0; i < 8; i++) data[8 + i] = (s >> (7 - i)) & 1; }
+                testframe_bits(data.data(), k, source, seq, f);
                 insert_crc(data.data(), k);
                 frame_bits(code, data.data(), frame.data());
                 fwrite(frame.data(), 1, frame.size(), fout);

@@ -14,7 +14,6 @@
 // --testframes and file cases; a live repeater drives the handle block after block through the library instead).
 // Exit codes: 1 arguments / files, 2 the code file (as fsk_ldpc_framer), 3 no usable HIP device or a device error (nothing is written).
 #include <getopt.h>
-#include <hip/hip_runtime_api.h>
 
 #include <cstdio>
 #include <cstdlib>
@@ -22,8 +21,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pirip_hip.h"
-#include "fsk_ldpc.hpp"
+#include "tool_common.hpp"
+#include "tx_records.hpp"
 
 using namespace pirip;
 
@@ -33,6 +32,9 @@ static int usage(const char *a0)
                     "          [--format u8|cf32] [--amp A] Fs Rs f1 shift in|- out|-\n", a0);
     return 1;
 }
+
+// every failure behind pirip_hip_tx_create is the device's
+static const ToolErrors kTool{"fsk_ldpc_tx", [](int) { return 3; }};
 
 int main(int argc, char **argv)
 {
@@ -71,71 +73,45 @@ int main(int argc, char **argv)
     const std::string err = code.load(code_path);
     if (!err.empty()) { fprintf(stderr, "fsk_ldpc_tx: %s: %s\n", code_path.c_str(), err.c_str()); return 2; }
     if (!code.accumulator) { fprintf(stderr, "fsk_ldpc_tx: %s has no dual-diagonal parity part: no linear-time encoder\n", code.name.c_str()); return 2; }
-    FILE *fin = strcmp(argv[optind + 4], "-") ? fopen(argv[optind + 4], "rb") : stdin;
+    File fin(strcmp(argv[optind + 4], "-") ? fopen(argv[optind + 4], "rb") : stdin);
     if (!fin) { fprintf(stderr, "fsk_ldpc_tx: couldn't open the input\n"); return 1; }
 
     // the record stream, packed
-    const int k = code.k, kb = k / 8, rl = 1 + kb;
-    std::vector<uint8_t> recs, data((size_t)k), bytes((size_t)kb);
-    auto push = [&](uint8_t ctl) { recs.push_back(ctl); recs.insert(recs.end(), bytes.begin(), bytes.end()); };
-    if (testframes > 0) {
-        testframe_payload(data.data(), k);
-        for (int b = 0; b < bursts; b++) {
-            for (int f = 0; f < testframes; f++) {
-                if (source >= 0) for (int i = 0; i < 8; i++) data[i] = (source >> (7 - i)) & 1;
-                if (seq) { const int s = (f + 1) & 0xff; for (int i = 0; i < 8; i++) data[8 + i] = (s >> (7 - i)) & 1; }
-                pack_bits_msb(bytes.data(), data.data(), k);
-                push(f == 0 ? 1 : 0);
-            }
-            std::fill(bytes.begin(), bytes.end(), 0);
-            push(2);
-        }
-    } else {
-        for (;;) {
-            uint8_t ctl;
-            if (fread(&ctl, 1, 1, fin) != 1) break;
-            size_t nread;
-            if (packed) nread = fread(bytes.data(), 1, bytes.size(), fin) * 8;
-            else { nread = fread(data.data(), 1, (size_t)k, fin); pack_bits_msb(bytes.data(), data.data(), k); }
-            if ((int)nread != k) break;
-            push(ctl);
-        }
-    }
+    const int k = code.k, rl = 1 + k / 8;
+    std::vector<uint8_t> recs;
+    if (testframes > 0) testframe_records(k, testframes, bursts, source, seq, recs);
+    else read_records(fin, k, packed, recs);
     const int nrec = (int)(recs.size() / (size_t)rl);
     fprintf(stderr, "fsk_ldpc_tx: code %s data_bits_per_frame %d bits_per_frame %d M %d records %d\n", code.name.c_str(), k, code.bits_per_frame(), M, nrec);
 
-    pirip_hip_tx *tx = nullptr;
-    int rc = pirip_hip_tx_create(code_path.c_str(), Fs, Rs, M, 1, -1, &tx);
-    if (rc != PIRIP_OK) { fprintf(stderr, "fsk_ldpc_tx: pirip_hip_tx_create: %s\n", pirip_hip_strerror(rc)); return rc == PIRIP_ERR_BAD_CONFIG || rc == PIRIP_ERR_UNSUPPORTED ? 2 : 3; }
+    TxHandle tx;
+    const int rc = pirip_hip_tx_create(code_path.c_str(), Fs, Rs, M, 1, -1, tx.out());
+    if (rc != PIRIP_OK) return status_fail(ToolErrors{kTool.name, tx_create_exit_code}, "pirip_hip_tx_create", rc);
     const int32_t f1a = f1, leada = lead / bps, gapa = gap / bps;
-    auto fail = [&](const char *what, int status) { fprintf(stderr, "fsk_ldpc_tx: %s: %s\n", what, pirip_hip_strerror(status)); pirip_hip_tx_destroy(tx); return 3; };
-    if ((rc = pirip_hip_tx_set_tones(tx, &f1a, shift)) != PIRIP_OK) return fail("pirip_hip_tx_set_tones", rc);
-    if ((rc = pirip_hip_tx_set_gaps(tx, &leada, &gapa)) != PIRIP_OK) return fail("pirip_hip_tx_set_gaps", rc);
+    PIRIPOK(pirip_hip_tx_set_tones(tx, &f1a, shift), "pirip_hip_tx_set_tones");
+    PIRIPOK(pirip_hip_tx_set_gaps(tx, &leada, &gapa), "pirip_hip_tx_set_gaps");
     const int64_t cap = pirip_hip_tx_max_syms(tx, nrec) > 0 ? pirip_hip_tx_max_syms(tx, nrec) : 1;
     const int bsamp = format == "u8" ? 2 : 8, Ts = Fs / Rs;
-    uint8_t *d_rec = nullptr, *d_syms = nullptr; int32_t *d_nsym = nullptr; void *d_out = nullptr;
-    if (hipMalloc((void **)&d_rec, recs.size() + 1) != hipSuccess || hipMalloc((void **)&d_syms, (size_t)cap) != hipSuccess ||
-        hipMalloc((void **)&d_nsym, sizeof(int32_t)) != hipSuccess) return fail("hipMalloc", PIRIP_ERR_NOMEM);
-    if (!recs.empty() && hipMemcpy(d_rec, recs.data(), recs.size(), hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy", PIRIP_ERR_HIP);
-    if ((rc = pirip_hip_tx_frame(tx, d_rec, recs.size() + 1, nullptr, nrec, d_syms, (size_t)cap, cap, d_nsym, nullptr, 0, nullptr)) != PIRIP_OK)
-        return fail("pirip_hip_tx_frame", rc);
+    DevBuf<uint8_t> d_rec, d_syms;
+    DevBuf<int32_t> d_nsym;
+    DevBuf<void> d_out;
+    if (hipMalloc((void **)d_rec.out(), recs.size() + 1) != hipSuccess || hipMalloc((void **)d_syms.out(), (size_t)cap) != hipSuccess ||
+        hipMalloc((void **)d_nsym.out(), sizeof(int32_t)) != hipSuccess) return status_fail(kTool, "hipMalloc", PIRIP_ERR_NOMEM);
+    if (!recs.empty() && hipMemcpy(d_rec, recs.data(), recs.size(), hipMemcpyHostToDevice) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
+    PIRIPOK(pirip_hip_tx_frame(tx, d_rec, recs.size() + 1, nullptr, nrec, d_syms, (size_t)cap, cap, d_nsym, nullptr, 0, nullptr), "pirip_hip_tx_frame");
     int32_t nsym = 0;
-    if (hipMemcpy(&nsym, d_nsym, sizeof(nsym), hipMemcpyDeviceToHost) != hipSuccess) return fail("hipMemcpy", PIRIP_ERR_HIP);
+    if (hipMemcpy(&nsym, d_nsym, sizeof(nsym), hipMemcpyDeviceToHost) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
     const size_t out_bytes = (size_t)nsym * (size_t)Ts * (size_t)bsamp;
     std::vector<uint8_t> out(out_bytes);
     if (nsym > 0) {
-        if (hipMalloc(&d_out, out_bytes) != hipSuccess) return fail("hipMalloc", PIRIP_ERR_NOMEM);
-        rc = pirip_hip_tx_modulate(tx, d_syms, (size_t)cap, d_nsym, nsym, format == "u8" ? PIRIP_IN_CU8_FSKDEMOD : PIRIP_IN_CF32, d_out, out_bytes,
-                                   amp, 0.0f, 0, nullptr);
-        if (rc != PIRIP_OK) return fail("pirip_hip_tx_modulate", rc);
-        if (hipMemcpy(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail("hipMemcpy", PIRIP_ERR_HIP);
+        if (hipMalloc(d_out.out(), out_bytes) != hipSuccess) return status_fail(kTool, "hipMalloc", PIRIP_ERR_NOMEM);
+        PIRIPOK(pirip_hip_tx_modulate(tx, d_syms, (size_t)cap, d_nsym, nsym, format == "u8" ? PIRIP_IN_CU8_FSKDEMOD : PIRIP_IN_CF32, d_out, out_bytes,
+                                      amp, 0.0f, 0, nullptr), "pirip_hip_tx_modulate");
+        if (hipMemcpy(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
     }
-    (void)hipFree(d_rec); (void)hipFree(d_syms); (void)hipFree(d_nsym); if (d_out) (void)hipFree(d_out);
-    pirip_hip_tx_destroy(tx);
-    FILE *fout = strcmp(argv[optind + 5], "-") ? fopen(argv[optind + 5], "wb") : stdout;
+    File fout(strcmp(argv[optind + 5], "-") ? fopen(argv[optind + 5], "wb") : stdout);
     if (!fout) { fprintf(stderr, "fsk_ldpc_tx: couldn't open the output\n"); return 1; }
     if (fwrite(out.data(), 1, out.size(), fout) != out.size()) { fprintf(stderr, "fsk_ldpc_tx: short write\n"); return 1; }
-    if (fout != stdout) fclose(fout);
     fprintf(stderr, "fsk_ldpc_tx: %d symbols, %zu samples\n", nsym, (size_t)nsym * Ts);
     return 0;
 }

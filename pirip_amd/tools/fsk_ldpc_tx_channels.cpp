@@ -23,9 +23,6 @@
 // follows the fill levels on the host from what each send took. --lead does not go with --block.
 // Exit codes: 1 arguments / files, 2 the code file (as fsk_ldpc_tx), 3 no usable HIP device or a device error (nothing is written).
 #include <getopt.h>
-#include <hip/hip_runtime_api.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <cstdio>
 #include <cstdlib>
@@ -33,8 +30,8 @@
 #include <string>
 #include <vector>
 
-#include "../../include/pirip_hip.h"
-#include "fsk_ldpc.hpp"
+#include "tool_common.hpp"
+#include "tx_records.hpp"
 
 using namespace pirip;
 
@@ -46,39 +43,8 @@ static int usage(const char *a0)
     return 1;
 }
 
-static bool file_exists(const std::string &p) { struct stat st; return !p.empty() && stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-
-// --code NAME: NAME as a file path, then $PIRIP_CODE_DIR/NAME.code, then <exe>/../data/NAME.code (as rtl_fsk_channels resolves it)
-static std::string resolve_code(const std::string &name, const char *argv0)
-{
-    if (file_exists(name)) return name;
-    if (const char *d = getenv("PIRIP_CODE_DIR")) { const std::string p = std::string(d) + "/" + name + ".code"; if (file_exists(p)) return p; }
-    char exe[4096];
-    const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1);
-    std::string base = n > 0 ? std::string(exe, (size_t)n) : std::string(argv0);
-    const size_t s = base.rfind('/');
-    base = s == std::string::npos ? "." : base.substr(0, s);
-    const std::string p = base + "/../data/" + name + ".code";
-    return file_exists(p) ? p : std::string();
-}
-
-template <typename T, typename F>
-static bool parse_list(const char *s, std::vector<T> &out, F conv)
-{
-    const std::string all(s);
-    for (size_t pos = 0; pos <= all.size();) {
-        size_t end = all.find(',', pos);
-        if (end == std::string::npos) end = all.size();
-        const std::string tok = all.substr(pos, end - pos);
-        if (tok.empty()) return false;
-        char *e = nullptr;
-        const T v = conv(tok.c_str(), &e);
-        if (*e) return false;
-        out.push_back(v);
-        pos = end + 1;
-    }
-    return !out.empty();
-}
+// behind pirip_hip_tx_create: a refused argument is the user's (1), anything else the device's (3)
+static const ToolErrors kTool{"fsk_ldpc_tx_channels", [](int status) { return status == PIRIP_ERR_BAD_ARG ? 1 : 3; }};
 
 int main(int argc, char **argv)
 {
@@ -97,7 +63,6 @@ int main(int argc, char **argv)
                                     {"gains", required_argument, 0, 1009}, {"linear", no_argument, 0, 1010},
                                     {"gap", required_argument, 0, 1011}, {"lead", required_argument, 0, 1012},
                                     {"block", required_argument, 0, 1013}, {"queue", required_argument, 0, 1014}, {0, 0, 0, 0}};
-    auto to_long = [](const char *t, char **e) { return strtol(t, e, 0); };
     int o, oi;
     while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:h", lopts, &oi)) != -1) {
         switch (o) {
@@ -106,7 +71,7 @@ int main(int argc, char **argv)
         case 'r': Rs = (long)atof(optarg); break;
         case 'm': M = atoi(optarg); break;
         case 'c':
-            if (!parse_list(optarg, offsets, [](const char *t, char **e) { return (int32_t)strtol(t, e, 10); })) {
+            if (!parse_list(optarg, offsets, conv_i32)) {
                 fprintf(stderr, "fsk_ldpc_tx_channels: -c wants integer offsets in Hz, comma separated\n"); return 1;
             }
             break;
@@ -116,12 +81,12 @@ int main(int argc, char **argv)
         case 1001: packed = 1; break;
         case 1002: testframes = atoi(optarg); break;
         case 1003: bursts = atoi(optarg); break;
-        case 1004: if (!parse_list(optarg, sources, to_long)) { fprintf(stderr, "fsk_ldpc_tx_channels: --source BYTE or b1,b2,...\n"); return 1; } break;
+        case 1004: if (!parse_list(optarg, sources, conv_long0)) { fprintf(stderr, "fsk_ldpc_tx_channels: --source BYTE or b1,b2,...\n"); return 1; } break;
         case 1005: seq = 1; break;
         case 1006: f1 = atoi(optarg); have_f1 = 1; break;
         case 1007: shift = atoi(optarg); break;
         case 1008: format = optarg; break;
-        case 1009: if (!parse_list(optarg, gains, [](const char *t, char **e) { return strtof(t, e); })) { fprintf(stderr, "fsk_ldpc_tx_channels: --gain g or --gains g1,g2,...\n"); return 1; } break;
+        case 1009: if (!parse_list(optarg, gains, conv_float)) { fprintf(stderr, "fsk_ldpc_tx_channels: --gain g or --gains g1,g2,...\n"); return 1; } break;
         case 1010: linear = 1; break;
         case 1011: gap = atoi(optarg); break;
         case 1012: lead_bits = atoi(optarg); break;
@@ -158,40 +123,14 @@ int main(int argc, char **argv)
     if (!ldpc.accumulator) { fprintf(stderr, "fsk_ldpc_tx_channels: %s has no dual-diagonal parity part: no linear-time encoder\n", ldpc.name.c_str()); return 2; }
 
     // every channel's record stream, packed; rows of max_rec records
-    const int k = ldpc.k, kb = k / 8, rl = 1 + kb;
+    const int k = ldpc.k, rl = 1 + k / 8;
     std::vector<std::vector<uint8_t>> recs((size_t)K);
-    std::vector<uint8_t> data((size_t)k), bytes((size_t)kb);
     for (int c = 0; c < K; c++) {
-        std::vector<uint8_t> &r = recs[(size_t)c];
-        auto push = [&](uint8_t ctl) { r.push_back(ctl); r.insert(r.end(), bytes.begin(), bytes.end()); };
-        if (testframes > 0) {
-            testframe_payload(data.data(), k);
-            const long source = sources.empty() ? -1 : sources[(size_t)c];
-            for (int b = 0; b < bursts; b++) {
-                for (int f = 0; f < testframes; f++) {
-                    if (source >= 0) for (int i = 0; i < 8; i++) data[(size_t)i] = (source >> (7 - i)) & 1;
-                    if (seq) { const int s = (f + 1) & 0xff; for (int i = 0; i < 8; i++) data[(size_t)(8 + i)] = (s >> (7 - i)) & 1; }
-                    pack_bits_msb(bytes.data(), data.data(), k);
-                    push(f == 0 ? 1 : 0);
-                }
-                std::fill(bytes.begin(), bytes.end(), 0);
-                push(2);
-            }
-        } else {
-            const std::string name = prefix + "." + std::to_string(c);
-            FILE *fin = fopen(name.c_str(), "rb");
-            if (!fin) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open %s\n", name.c_str()); return 1; }
-            for (;;) {
-                uint8_t ctl;
-                if (fread(&ctl, 1, 1, fin) != 1) break;
-                size_t nread;
-                if (packed) nread = fread(bytes.data(), 1, bytes.size(), fin) * 8;
-                else { nread = fread(data.data(), 1, (size_t)k, fin); pack_bits_msb(bytes.data(), data.data(), k); }
-                if ((int)nread != k) break;
-                push(ctl);
-            }
-            fclose(fin);
-        }
+        if (testframes > 0) { testframe_records(k, testframes, bursts, sources.empty() ? -1 : sources[(size_t)c], seq, recs[(size_t)c]); continue; }
+        const std::string name = prefix + "." + std::to_string(c);
+        File fin(fopen(name.c_str(), "rb"));
+        if (!fin) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open %s\n", name.c_str()); return 1; }
+        read_records(fin, k, packed, recs[(size_t)c]);
     }
     int max_rec = 0;
     for (const auto &r : recs) if ((int)(r.size() / (size_t)rl) > max_rec) max_rec = (int)(r.size() / (size_t)rl);
@@ -204,82 +143,59 @@ int main(int argc, char **argv)
     }
 
     const int D = (int)(wideFs / modemFs), Ts = (int)(modemFs / Rs);
-    pirip_hip_tx *tx = nullptr;
-    pirip_hip_mux *mux = nullptr;
-    int rc = pirip_hip_tx_create(code_path.c_str(), (int)modemFs, (int)Rs, M, K, -1, &tx);
-    if (rc != PIRIP_OK) { fprintf(stderr, "fsk_ldpc_tx_channels: pirip_hip_tx_create: %s\n", pirip_hip_strerror(rc)); return rc == PIRIP_ERR_BAD_CONFIG || rc == PIRIP_ERR_UNSUPPORTED ? 2 : 3; }
-    auto fail = [&](const char *what, int status) {
-        fprintf(stderr, "fsk_ldpc_tx_channels: %s: %s\n", what, pirip_hip_strerror(status));
-        if (mux) pirip_hip_mux_destroy(mux);
-        pirip_hip_tx_destroy(tx);
-        return status == PIRIP_ERR_BAD_ARG ? 1 : 3;
-    };
+    TxHandle tx;
+    MuxHandle mux;
+    const int rc = pirip_hip_tx_create(code_path.c_str(), (int)modemFs, (int)Rs, M, K, -1, tx.out());
+    if (rc != PIRIP_OK) return status_fail(ToolErrors{kTool.name, tx_create_exit_code}, "pirip_hip_tx_create", rc);
     const int out_format = format == "u8" ? PIRIP_IN_CU8_CSDR : PIRIP_IN_CF32, bsamp = format == "u8" ? 2 : 8;
     std::vector<int32_t> outputs((size_t)K, 0), f1s((size_t)K, f1);
-    rc = pirip_hip_mux_create((int)wideFs, D, linear ? PIRIP_MUX_LINEAR : PIRIP_MUX_FIR, 0.05f, out_format, 1, K, outputs.data(), offsets.data(),
-                              gains.data(), -1, &mux);
-    if (rc != PIRIP_OK) return fail("pirip_hip_mux_create", rc);
+    PIRIPOK(pirip_hip_mux_create((int)wideFs, D, linear ? PIRIP_MUX_LINEAR : PIRIP_MUX_FIR, 0.05f, out_format, 1, K, outputs.data(), offsets.data(),
+                                 gains.data(), -1, mux.out()), "pirip_hip_mux_create");
     pirip_mux_info mi;
     pirip_hip_mux_get_info(mux, &mi);
-    if ((rc = pirip_hip_tx_set_tones(tx, f1s.data(), shift)) != PIRIP_OK) return fail("pirip_hip_tx_set_tones", rc);
+    PIRIPOK(pirip_hip_tx_set_tones(tx, f1s.data(), shift), "pirip_hip_tx_set_tones");
     const std::vector<int32_t> leads((size_t)K, lead_bits / bps), gaps((size_t)K, gap / bps);
-    if ((rc = pirip_hip_tx_set_gaps(tx, leads.data(), gaps.data())) != PIRIP_OK) return fail("pirip_hip_tx_set_gaps", rc);
+    PIRIPOK(pirip_hip_tx_set_gaps(tx, leads.data(), gaps.data()), "pirip_hip_tx_set_gaps");
+
+    // each channel's bursts (record ranges and the symbols they make); the channel with the most symbols sets the length of the output
+    pirip_tx_info ti;
+    pirip_hip_tx_get_info(tx, &ti);
+    std::vector<std::vector<Burst>> chan_bursts((size_t)K);
+    int64_t max_burst = 0, max_total = 0;
+    int max_brec = 1;
+    for (int c = 0; c < K; c++) {
+        chan_bursts[(size_t)c] = split_bursts(recs[(size_t)c].data(), nrec[(size_t)c], (size_t)rl, ti.preamble_syms, ti.frame_syms, gap / bps);
+        int64_t total = 0;
+        for (const Burst &b : chan_bursts[(size_t)c]) {
+            total += b.syms;
+            if (b.syms > max_burst) max_burst = b.syms;
+            if (b.r1 - b.r0 > max_brec) max_brec = b.r1 - b.r0;
+        }
+        if (total > max_total) max_total = total;
+    }
 
     if (block > 0) {
-        // the streaming transmitter: each channel's bursts (record ranges and the symbols they make), offered burst by burst
-        pirip_tx_info ti;
-        pirip_hip_tx_get_info(tx, &ti);
-        struct Burst { int r0, r1; int64_t syms; };
-        std::vector<std::vector<Burst>> bursts((size_t)K);
-        int64_t max_burst = 0, max_total = 0;
-        int max_brec = 1;
-        for (int c = 0; c < K; c++) {
-            Burst b{0, 0, 0};
-            int64_t total = 0;
-            for (int i = 0; i < nrec[(size_t)c]; i++) {
-                const uint8_t ctl = recs[(size_t)c][(size_t)i * (size_t)rl];
-                b.syms += ctl == 1 ? ti.preamble_syms + ti.frame_syms : ctl == 0 ? ti.frame_syms : ctl == 2 ? gap / bps : 0;
-                b.r1 = i + 1;
-                if (ctl == 2 || i + 1 == nrec[(size_t)c]) {
-                    bursts[(size_t)c].push_back(b);
-                    total += b.syms;
-                    if (b.syms > max_burst) max_burst = b.syms;
-                    if (b.r1 - b.r0 > max_brec) max_brec = b.r1 - b.r0;
-                    b = Burst{i + 1, i + 1, 0};
-                }
-            }
-            if (total > max_total) max_total = total;
-        }
+        // the streaming transmitter: every channel's bursts are offered burst by burst
         const int64_t per_sym = (int64_t)D * Ts, S = block / per_sym;
-        if (block % per_sym) { fprintf(stderr, "fsk_ldpc_tx_channels: --block must be a multiple of D * Ts = %lld wideband samples\n", (long long)per_sym); pirip_hip_mux_destroy(mux); pirip_hip_tx_destroy(tx); return 1; }
+        if (block % per_sym) { fprintf(stderr, "fsk_ldpc_tx_channels: --block must be a multiple of D * Ts = %lld wideband samples\n", (long long)per_sym); return 1; }
         if (queue <= 0) queue = max_burst + S;
-        if (queue < max_burst) { fprintf(stderr, "fsk_ldpc_tx_channels: --queue %lld cannot hold the largest burst, %lld symbols\n", queue, (long long)max_burst); pirip_hip_mux_destroy(mux); pirip_hip_tx_destroy(tx); return 1; }
-        pirip_hip_txs *txs = nullptr;
-        if ((rc = pirip_hip_txs_create(tx, mux, block, queue, &txs)) != PIRIP_OK) return fail("pirip_hip_txs_create", rc);
-        FILE *fout = out_name == "-" ? stdout : fopen(out_name.c_str(), "wb");
-        uint8_t *d_stage = nullptr; int32_t *d_offered = nullptr, *d_taken = nullptr; void *d_blk = nullptr;
-        // every way out of block mode: the device buffers, the three handles, the output
-        auto done = [&](int status) {
-            (void)hipFree(d_stage); (void)hipFree(d_offered); (void)hipFree(d_taken); (void)hipFree(d_blk);
-            pirip_hip_txs_destroy(txs);
-            pirip_hip_mux_destroy(mux);
-            pirip_hip_tx_destroy(tx);
-            if (fout && fout != stdout) fclose(fout);
-            return status;
-        };
-        auto sfail = [&](const char *what, int status) {
-            fprintf(stderr, "fsk_ldpc_tx_channels: %s: %s\n", what, pirip_hip_strerror(status));
-            return done(status == PIRIP_ERR_BAD_ARG ? 1 : 3);
-        };
-        if (!fout) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open the output\n"); return done(1); }
+        if (queue < max_burst) { fprintf(stderr, "fsk_ldpc_tx_channels: --queue %lld cannot hold the largest burst, %lld symbols\n", queue, (long long)max_burst); return 1; }
+        TxsHandle txs;
+        PIRIPOK(pirip_hip_txs_create(tx, mux, block, queue, txs.out()), "pirip_hip_txs_create");
+        File fout(out_name == "-" ? stdout : fopen(out_name.c_str(), "wb"));
+        if (!fout) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open the output\n"); return 1; }
         const size_t stage_stride = (size_t)max_brec * (size_t)rl, blk_bytes = (size_t)block * (size_t)bsamp;
         std::vector<uint8_t> stage((size_t)K * stage_stride, 0), blk(blk_bytes);
         std::vector<int32_t> offered((size_t)K), taken((size_t)K);
         std::vector<size_t> next((size_t)K, 0);
         // each queue's fill level, followed on the host: a burst that was taken adds its symbols, a block takes up to S away
         std::vector<int64_t> fill((size_t)K, 0);
-        if (hipMalloc((void **)&d_stage, stage.size()) != hipSuccess || hipMalloc((void **)&d_offered, sizeof(int32_t) * (size_t)K) != hipSuccess ||
-            hipMalloc((void **)&d_taken, sizeof(int32_t) * (size_t)K) != hipSuccess || hipMalloc(&d_blk, blk_bytes) != hipSuccess) return sfail("hipMalloc", PIRIP_ERR_NOMEM);
+        DevBuf<uint8_t> d_stage;
+        DevBuf<int32_t> d_offered, d_taken;
+        DevBuf<void> d_blk;
+        if (hipMalloc((void **)d_stage.out(), stage.size()) != hipSuccess || hipMalloc((void **)d_offered.out(), sizeof(int32_t) * (size_t)K) != hipSuccess ||
+            hipMalloc((void **)d_taken.out(), sizeof(int32_t) * (size_t)K) != hipSuccess || hipMalloc(d_blk.out(), blk_bytes) != hipSuccess)
+            return status_fail(kTool, "hipMalloc", PIRIP_ERR_NOMEM);
         int64_t calls = 0;
         for (;;) {
             std::vector<char> refused((size_t)K, 0);
@@ -287,79 +203,63 @@ int main(int argc, char **argv)
                 bool any = false;
                 for (int c = 0; c < K; c++) {
                     offered[(size_t)c] = 0;
-                    if (refused[(size_t)c] || next[(size_t)c] >= bursts[(size_t)c].size()) continue;
-                    const Burst &b = bursts[(size_t)c][next[(size_t)c]];
+                    if (refused[(size_t)c] || next[(size_t)c] >= chan_bursts[(size_t)c].size()) continue;
+                    const Burst &b = chan_bursts[(size_t)c][next[(size_t)c]];
                     memcpy(&stage[(size_t)c * stage_stride], &recs[(size_t)c][(size_t)b.r0 * (size_t)rl], (size_t)(b.r1 - b.r0) * (size_t)rl);
                     offered[(size_t)c] = b.r1 - b.r0;
                     any = true;
                 }
                 if (!any) break;
                 if (hipMemcpy(d_stage, stage.data(), stage.size(), hipMemcpyHostToDevice) != hipSuccess ||
-                    hipMemcpy(d_offered, offered.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) return sfail("hipMemcpy", PIRIP_ERR_HIP);
-                if ((rc = pirip_hip_txs_send(txs, d_stage, stage_stride, d_offered, max_brec, d_taken, nullptr)) != PIRIP_OK) return sfail("pirip_hip_txs_send", rc);
-                if (hipMemcpy(taken.data(), d_taken, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost) != hipSuccess) return sfail("hipMemcpy", PIRIP_ERR_HIP);
+                    hipMemcpy(d_offered, offered.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
+                PIRIPOK(pirip_hip_txs_send(txs, d_stage, stage_stride, d_offered, max_brec, d_taken, nullptr), "pirip_hip_txs_send");
+                if (hipMemcpy(taken.data(), d_taken, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
                 for (int c = 0; c < K; c++) {
                     if (!offered[(size_t)c]) continue;
-                    if (taken[(size_t)c] == offered[(size_t)c]) { fill[(size_t)c] += bursts[(size_t)c][next[(size_t)c]].syms; next[(size_t)c]++; }
+                    if (taken[(size_t)c] == offered[(size_t)c]) { fill[(size_t)c] += chan_bursts[(size_t)c][next[(size_t)c]].syms; next[(size_t)c]++; }
                     else refused[(size_t)c] = 1;
                 }
             }
             // the end: every channel's input is exhausted and every queue is empty
             bool more = false;
-            for (int c = 0; c < K; c++) if (next[(size_t)c] < bursts[(size_t)c].size() || fill[(size_t)c] > 0) more = true;
+            for (int c = 0; c < K; c++) if (next[(size_t)c] < chan_bursts[(size_t)c].size() || fill[(size_t)c] > 0) more = true;
             if (!more) break;
-            if ((rc = pirip_hip_txs_process(txs, d_blk, blk_bytes, nullptr, nullptr)) != PIRIP_OK) return sfail("pirip_hip_txs_process", rc);
-            if (hipMemcpy(blk.data(), d_blk, blk_bytes, hipMemcpyDeviceToHost) != hipSuccess) return sfail("hipMemcpy", PIRIP_ERR_HIP);
-            if (fwrite(blk.data(), 1, blk.size(), fout) != blk.size()) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return done(1); }
+            PIRIPOK(pirip_hip_txs_process(txs, d_blk, blk_bytes, nullptr, nullptr), "pirip_hip_txs_process");
+            if (hipMemcpy(blk.data(), d_blk, blk_bytes, hipMemcpyDeviceToHost) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
+            if (fwrite(blk.data(), 1, blk.size(), fout) != blk.size()) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return 1; }
             for (int c = 0; c < K; c++) fill[(size_t)c] -= fill[(size_t)c] < S ? fill[(size_t)c] : S;
             calls++;
         }
-        if (fflush(fout) != 0) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return done(1); }
-        done(0);
+        if (fflush(fout) != 0) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return 1; }
         fprintf(stderr, "fsk_ldpc_tx_channels: code %s M %d channels %d interpolation %d taps %d: %lld symbols in %lld blocks of %lld wideband samples, queues of %lld symbols\n",
                 ldpc.name.c_str(), M, K, D, mi.ntaps, (long long)max_total, (long long)calls, block, queue);
         return 0;
     }
 
-    uint8_t *d_rec = nullptr; int32_t *d_nrec = nullptr, *d_nsym = nullptr; char *d_mod = nullptr; void *d_out = nullptr;
-    if (hipMalloc((void **)&d_rec, rec_rows.size()) != hipSuccess || hipMalloc((void **)&d_nrec, sizeof(int32_t) * (size_t)K) != hipSuccess ||
-        hipMalloc((void **)&d_nsym, sizeof(int32_t) * (size_t)K) != hipSuccess) return fail("hipMalloc", PIRIP_ERR_NOMEM);
+    DevBuf<uint8_t> d_rec;
+    DevBuf<int32_t> d_nrec, d_nsym;
+    DevBuf<char> d_mod;
+    DevBuf<void> d_out;
+    if (hipMalloc((void **)d_rec.out(), rec_rows.size()) != hipSuccess || hipMalloc((void **)d_nrec.out(), sizeof(int32_t) * (size_t)K) != hipSuccess ||
+        hipMalloc((void **)d_nsym.out(), sizeof(int32_t) * (size_t)K) != hipSuccess) return status_fail(kTool, "hipMalloc", PIRIP_ERR_NOMEM);
     if (hipMemcpy(d_rec, rec_rows.data(), rec_rows.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(d_nrec, nrec.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) return fail("hipMemcpy", PIRIP_ERR_HIP);
-    // the symbols each channel's records make: the longest one sets the length of every row
-    int64_t nsym = 0;
-    for (int c = 0; c < K; c++) {
-        int64_t n = lead_bits / bps;
-        const std::vector<uint8_t> &r = recs[(size_t)c];
-        pirip_tx_info ti;
-        pirip_hip_tx_get_info(tx, &ti);
-        for (int i = 0; i < nrec[(size_t)c]; i++) {
-            const uint8_t ctl = r[(size_t)i * (size_t)rl];
-            n += ctl == 1 ? ti.preamble_syms + ti.frame_syms : ctl == 0 ? ti.frame_syms : ctl == 2 ? gap / bps : 0;
-        }
-        if (n > nsym) nsym = n;
-    }
+        hipMemcpy(d_nrec, nrec.data(), sizeof(int32_t) * (size_t)K, hipMemcpyHostToDevice) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
+    const int64_t nsym = lead_bits / bps + max_total;             // every row is as long as the longest
     const int64_t nmod = nsym * Ts, lead = mi.Q - 1, n_in = nmod + lead;
     const int64_t n_out = pirip_hip_mux_nout(mux, n_in);
     const size_t mod_stride = (size_t)n_in * 8, out_bytes = (size_t)n_out * (size_t)bsamp;
     std::vector<uint8_t> out(out_bytes);
     if (nsym > 0) {
-        if (hipMalloc((void **)&d_mod, (size_t)K * mod_stride) != hipSuccess || hipMalloc(&d_out, out_bytes) != hipSuccess) return fail("hipMalloc", PIRIP_ERR_NOMEM);
-        if (hipMemset(d_mod, 0, (size_t)K * mod_stride) != hipSuccess) return fail("hipMemset", PIRIP_ERR_HIP);
-        rc = pirip_hip_tx_records_to_iq(tx, d_rec, rec_stride, d_nrec, max_rec, nsym, PIRIP_IN_CF32, d_mod + (size_t)lead * 8, mod_stride, 0.f, 0.f, 0,
-                                        d_nsym, nullptr);
-        if (rc != PIRIP_OK) return fail("pirip_hip_tx_records_to_iq", rc);
-        rc = pirip_hip_mux_batch(mux, d_mod, mod_stride, n_in, -lead, d_out, out_bytes, nullptr);
-        if (rc != PIRIP_OK) return fail("pirip_hip_mux_batch", rc);
-        if (hipMemcpy(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return fail("hipMemcpy", PIRIP_ERR_HIP);
+        if (hipMalloc((void **)d_mod.out(), (size_t)K * mod_stride) != hipSuccess || hipMalloc(d_out.out(), out_bytes) != hipSuccess) return status_fail(kTool, "hipMalloc", PIRIP_ERR_NOMEM);
+        if (hipMemset(d_mod, 0, (size_t)K * mod_stride) != hipSuccess) return status_fail(kTool, "hipMemset", PIRIP_ERR_HIP);
+        PIRIPOK(pirip_hip_tx_records_to_iq(tx, d_rec, rec_stride, d_nrec, max_rec, nsym, PIRIP_IN_CF32, d_mod + (size_t)lead * 8, mod_stride, 0.f, 0.f, 0,
+                                           d_nsym, nullptr), "pirip_hip_tx_records_to_iq");
+        PIRIPOK(pirip_hip_mux_batch(mux, d_mod, mod_stride, n_in, -lead, d_out, out_bytes, nullptr), "pirip_hip_mux_batch");
+        if (hipMemcpy(out.data(), d_out, out_bytes, hipMemcpyDeviceToHost) != hipSuccess) return status_fail(kTool, "hipMemcpy", PIRIP_ERR_HIP);
     }
-    (void)hipFree(d_rec); (void)hipFree(d_nrec); (void)hipFree(d_nsym); if (d_mod) (void)hipFree(d_mod); if (d_out) (void)hipFree(d_out);
-    pirip_hip_mux_destroy(mux);
-    pirip_hip_tx_destroy(tx);
-    FILE *fout = out_name == "-" ? stdout : fopen(out_name.c_str(), "wb");
+    File fout(out_name == "-" ? stdout : fopen(out_name.c_str(), "wb"));
     if (!fout) { fprintf(stderr, "fsk_ldpc_tx_channels: couldn't open the output\n"); return 1; }
     if (fwrite(out.data(), 1, out.size(), fout) != out.size()) { fprintf(stderr, "fsk_ldpc_tx_channels: short write\n"); return 1; }
-    if (fout != stdout) fclose(fout);
     fprintf(stderr, "fsk_ldpc_tx_channels: code %s M %d channels %d interpolation %d taps %d: %lld symbols, %lld wideband samples\n", ldpc.name.c_str(), M, K, D,
             mi.ntaps, (long long)nsym, (long long)n_out);
     return 0;

@@ -16,9 +16,7 @@
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime_api.h>
-
-#include "../../include/pirip_hip.h"
+#include "tool_common.hpp"
 #include "../../include/pirip_hip_rccl.h"
 #include "fsk_plan.hpp"
 
@@ -26,10 +24,7 @@
 
 int main(int argc, char **argv)
 {
-    {   // a binary compiled against another header generation must not run against this library (stats rows, stream state sizes)
-        const int abi_ok = pirip_hip_abi_check(PIRIP_HIP_ABI_VERSION, PIRIP_STATS_PER_FRAME, sizeof(pirip_stream_state));
-        if (!abi_ok) { fprintf(stderr, "%s: built against a different pirip_hip.h than %s\n", argv[0], pirip_hip_version()); return 2; }
-    }
+    if (!abi_ok(argv[0])) return 2;
     const int rank = getenv("RANK") ? atoi(getenv("RANK")) : 0, world = getenv("WORLD_SIZE") ? atoi(getenv("WORLD_SIZE")) : 1;
     const int local = getenv("LOCAL_RANK") ? atoi(getenv("LOCAL_RANK")) : rank;
     int B = 6144, steps = 5, warmup = 2; long nsamp = 1200000;
@@ -57,7 +52,9 @@ int main(int argc, char **argv)
     std::vector<int32_t> f1((size_t)B), skip((size_t)B);
     for (int s = 0; s < B; s++) { const long g = (long)rank * B + s; f1[(size_t)s] = 10000 + (int)((g % 5) - 2) * 937; skip[(size_t)s] = (int)((g / 5) % Ts); }
     uint8_t *d_tx = nullptr, *d_iq = nullptr, *d_msg[2] = {nullptr, nullptr}, *d_all = nullptr;
-    const long maxf = nsamp / (Ts * Nsym - Ts / 4) + 2;
+    pirip_fsk_info info;
+    CK(pirip_hip_get_info(h, &info));
+    const long maxf = nsamp / shortest_frame(info) + 2;
     const size_t frame_bytes = 7;
     size_t cnt_off = 0, msg = 0;                     // packed bits | pad to 4 bytes | int32 frame counts (pirip_hip_gather_layout)
     CK(pirip_hip_gather_layout(B, maxf, (int)frame_bytes, &cnt_off, &msg));

@@ -41,7 +41,6 @@
 #include <getopt.h>
 #include <netdb.h>
 #include <sys/socket.h>
-#include <sys/stat.h>
 #include <unistd.h>
 
 #include <cmath>
@@ -52,40 +51,8 @@
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime_api.h>
-
-#include "../../include/pirip_hip.h"
-#include "fsk_ldpc.hpp"
-
-// The two rules of upstream's rtl_fsk.c this tool holds from recall, as data (the tool-level part of the pin-day drill; the
-// demodulator's own recalled constants are pirip_fsk_recalled / PIRIP_RECALLED): flipped without a rebuild through
-//   PIRIP_RTL_FSK_RULES="p_rule=0|1|2,p_max=10,default_rate=240000,wide_rate=1800000,min_rate=900001"
-struct RtlFskRules {
-    int p_rule = 0;                 // timing oversample: 0: halve Ts while it is > p_max and even (recalled); 1: P = Ts; 2: P = 8 (fsk_demod's default)
-    int p_max = 10;
-    long default_rate = 240000;     // RTL rate when -s is absent and the modem rate is absent or divides it
-    long wide_rate = 1800000;       // ... else this one when the modem rate divides it
-    long min_rate = 900001;         // ... else the smallest multiple of the modem rate from here up
-    bool from_env()
-    {
-        const char *e = getenv("PIRIP_RTL_FSK_RULES");
-        if (!e) return true;
-        std::string all(e);
-        for (size_t pos = 0; pos < all.size();) {
-            size_t end = all.find(',', pos);
-            if (end == std::string::npos) end = all.size();
-            const std::string tok = all.substr(pos, end - pos);
-            pos = end + 1;
-            const size_t eq = tok.find('=');
-            if (eq == std::string::npos) return false;
-            const std::string k = tok.substr(0, eq);
-            const long v = atol(tok.c_str() + eq + 1);
-            if (k == "p_rule") p_rule = (int)v; else if (k == "p_max") p_max = (int)v; else if (k == "default_rate") default_rate = v;
-            else if (k == "wide_rate") wide_rate = v; else if (k == "min_rate") min_rate = v; else return false;
-        }
-        return p_rule >= 0 && p_rule <= 2 && p_max >= 4 && default_rate > 0 && wide_rate > 0 && min_rate > 0;
-    }
-};
+#include "tool_common.hpp"
+#include "tx_records.hpp"
 
 static void usage()
 {
@@ -95,29 +62,11 @@ static void usage()
             "        IQ source: -i, or the file named by $PIRIP_IQ_FILE; tuner options -g -f -w -e -p are accepted and ignored\n");
 }
 
-static bool file_exists(const std::string &p) { struct stat st; return !p.empty() && stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-
-static std::string resolve_code(const std::string &name, const char *argv0)
-{
-    if (file_exists(name)) return name;
-    if (const char *d = getenv("PIRIP_CODE_DIR")) { const std::string p = std::string(d) + "/" + name + ".code"; if (file_exists(p)) return p; }
-    char exe[4096];
-    const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1);
-    std::string base = n > 0 ? std::string(exe, (size_t)n) : std::string(argv0);
-    const size_t s = base.rfind('/');
-    base = s == std::string::npos ? "." : base.substr(0, s);
-    const std::string p = base + "/../data/" + name + ".code";
-    return file_exists(p) ? p : std::string();
-}
-
-#define HIPOK(expr) do { if ((expr) != hipSuccess) { fprintf(stderr, "rtl_fsk: HIP error at %s:%d\n", __FILE__, __LINE__); return 2; } } while (0)
+static const ToolErrors kTool{"rtl_fsk", [](int) { return 2; }};
 
 int main(int argc, char **argv)
 {
-    {   // a binary compiled against another header generation must not run against this library (stats rows, stream state sizes)
-        const int abi_ok = pirip_hip_abi_check(PIRIP_HIP_ABI_VERSION, PIRIP_STATS_PER_FRAME, sizeof(pirip_stream_state));
-        if (!abi_ok) { fprintf(stderr, "%s: built against a different pirip_hip.h than %s\n", argv[0], pirip_hip_version()); return 2; }
-    }
+    if (!abi_ok(argv[0])) return 2;
     long rtlFs = 0, modemFs = 0, Rs = 10000, nsamples = 0;
     int M = 2, mask = 0, verbose = 0, quiet = 0, fsk_lower = 0, fsk_upper = 0, user_lower = 0, user_upper = 0, log_frames = 0;
     int status_bytes = 0, testframes = 0, filter = -1;
@@ -168,8 +117,8 @@ int main(int argc, char **argv)
         fprintf(stderr, "rtl_fsk: -b / --testframes / --filter need --code\n");
         return 1;
     }
-    FILE *fin = in_name == "-" ? stdin : fopen(in_name.c_str(), "rb");
-    FILE *fout = strcmp(argv[optind], "-") ? fopen(argv[optind], "wb") : stdout;
+    File fin(in_name == "-" ? stdin : fopen(in_name.c_str(), "rb"));
+    File fout(strcmp(argv[optind], "-") ? fopen(argv[optind], "wb") : stdout);
     if (!fin || !fout) { fprintf(stderr, "rtl_fsk: couldn't open files\n"); return 1; }
     if (modemFs < 0 || rtlFs < 0 || Rs <= 0) { usage(); return 1; }
     RtlFskRules rules;
@@ -184,43 +133,30 @@ int main(int argc, char **argv)
     const int D = (int)(rtlFs / modemFs);
     const int Fs = (int)modemFs;
     if (Fs % Rs) { fprintf(stderr, "rtl_fsk: modem rate must be a multiple of the symbol rate\n"); return 1; }
-    int Ts = Fs / (int)Rs, P = Ts;
-    if (rules.p_rule == 0) while (P > rules.p_max && (P % 2) == 0) P /= 2;        // oversample reduction rule [UPSTREAM-RECALLED, unverified: RtlFskRules]
-    else if (rules.p_rule == 2 && Ts % 8 == 0) P = 8;
-    if (P < 4) P = Ts;
-    if (!user_lower) fsk_lower = (int)Rs / 2;     // keep the estimator off the dongle's DC spur (README.md:116)
-    if (!user_upper) fsk_upper = Fs / 2;
 
     // the in-process decimator hands complex float to the modem (no s16 hop inside rtl_fsk)
-    pirip_fsk_params prm{Fs, (int)Rs, M, P, PIRIP_FSK_DEFAULT_NSYM, fsk_lower, fsk_upper, mask ? 1 : 0,
-                         mask ? mask : 100, D > 1 ? PIRIP_IN_CF32 : PIRIP_IN_CU8_CSDR};
-    pirip_hip_demod *h = nullptr;
-    int rc = pirip_hip_create(&prm, 1, -1, &h);
+    const pirip_fsk_params prm = rtl_fsk_params(Fs, (int)Rs, M, mask, user_lower ? &fsk_lower : nullptr, user_upper ? &fsk_upper : nullptr,
+                                                D > 1 ? PIRIP_IN_CF32 : PIRIP_IN_CU8_CSDR, rules);
+    DemodHandle h;
+    DecimHandle dec;
+    LdpcHandle ldpc;
+    int rc = pirip_hip_create(&prm, 1, -1, h.out());
     if (rc != PIRIP_OK) { fprintf(stderr, "rtl_fsk: %s (AMD GPU only; there is no CPU fallback)\n", pirip_hip_strerror(rc)); return 2; }
-    pirip_hip_decim *dec = nullptr;
-    if (D > 1 && (rc = pirip_hip_decim_create(D, 0.05f, 0, -1, &dec)) != PIRIP_OK) {
-        fprintf(stderr, "rtl_fsk: decimator: %s\n", pirip_hip_strerror(rc)); return 2;
-    }
+    if (D > 1) PIRIPOK(pirip_hip_decim_create(D, 0.05f, 0, -1, dec.out()), "decimator");
     pirip_fsk_info info;
     pirip_hip_get_info(h, &info);
-    pirip_hip_ldpc *ldpc = nullptr;
     pirip_ldpc_info li{};
     pirip::LdpcCode tfcode;                          // --testframes: the known payload, for the ecdd column
     std::vector<uint8_t> tf_bytes;
     if (!code_path.empty()) {
-        rc = pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, 1, -1, &ldpc);
+        rc = pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, 1, -1, ldpc.out());
         if (rc != PIRIP_OK) { fprintf(stderr, "rtl_fsk: --code %s: %s\n", code_path.c_str(), pirip_hip_strerror(rc)); return 2; }
         pirip_hip_ldpc_get_info(ldpc, &li);
-        if (testframes && tfcode.load(code_path).empty()) {
-            std::vector<uint8_t> bits((size_t)li.k);
-            pirip::testframe_payload(bits.data(), li.k);
-            tf_bytes.resize((size_t)li.data_bytes);
-            pirip::pack_bits_msb(tf_bytes.data(), bits.data(), li.k);
-        }
+        if (testframes && tfcode.load(code_path).empty()) tf_bytes = pirip::testframe_bytes(li.k, -1, 0, 0);
     }
     if (!quiet || getenv("PIRIP_RTL_FSK_BANNER"))          // (the environment switch lets a test read the banner of a -q command line)
-        fprintf(stderr, "rtl_fsk: rtl rate %ld Fs %d Rs %ld M %d P %d decimation %d estimator %d..%d Hz kernel %s%s%s\n", rtlFs, Fs, Rs, M, P, D,
-                fsk_lower, fsk_upper, pirip_hip_get_kernel(h) == PIRIP_KERNEL_WAVE ? "wave" : pirip_hip_get_kernel(h) == PIRIP_KERNEL_BLOCK ? "block" : "general", ldpc ? " code " : "", ldpc ? li.name : "");
+        fprintf(stderr, "rtl_fsk: rtl rate %ld Fs %d Rs %ld M %d P %d decimation %d estimator %d..%d Hz kernel %s%s%s\n", rtlFs, Fs, Rs, M, prm.P, D,
+                prm.est_min, prm.est_max, pirip_hip_get_kernel(h) == PIRIP_KERNEL_WAVE ? "wave" : pirip_hip_get_kernel(h) == PIRIP_KERNEL_BLOCK ? "block" : "general", ldpc ? " code " : "", ldpc ? li.name : "");
 
     int sock = -1; sockaddr_in dst{};
     if (!dash_host.empty()) {
@@ -239,23 +175,24 @@ int main(int argc, char **argv)
     const size_t raw_cap = blk + (size_t)(D > 1 ? taps_pad + D : info.nin_max) + 16;
     const size_t mod_cap = D > 1 ? blk / D + (size_t)info.nin_max + 16 : raw_cap;
     const size_t bps_mod = (size_t)info.bytes_per_sample;       // 8 (complex float) behind the decimator, 2 (u8) direct
-    const size_t nin_min = (size_t)(info.N - info.Ts / 4);
-    const int64_t max_frames = (int64_t)(mod_cap / nin_min) + 2;
+    const int64_t max_frames = (int64_t)(mod_cap / (size_t)shortest_frame(info)) + 2;
     std::vector<uint8_t> raw(2 * raw_cap);
     size_t raw_have = 0, mod_have = 0;
-    void *d_raw = nullptr, *d_mod[2] = {nullptr, nullptr};
-    uint8_t *d_bits = nullptr; float *d_stats = nullptr; int32_t *d_nfr = nullptr; int64_t *d_cons = nullptr;
-    uint8_t *d_status = nullptr, *d_payload = nullptr; int32_t *d_linfo = nullptr;
-    HIPOK(hipMalloc(&d_raw, 2 * raw_cap));
-    if (D > 1) { HIPOK(hipMalloc(&d_mod[0], bps_mod * mod_cap)); HIPOK(hipMalloc(&d_mod[1], bps_mod * mod_cap)); }
-    HIPOK(hipMalloc((void **)&d_bits, (size_t)max_frames * info.Nbits));
-    HIPOK(hipMalloc((void **)&d_stats, sizeof(float) * (size_t)max_frames * PIRIP_STATS_PER_FRAME));
-    HIPOK(hipMalloc((void **)&d_nfr, sizeof(int32_t)));
-    HIPOK(hipMalloc((void **)&d_cons, sizeof(int64_t)));
+    DevBuf<uint8_t> d_raw, d_bits, d_status, d_payload;
+    DevBuf<char> d_mod[2];
+    DevBuf<float> d_stats;
+    DevBuf<int32_t> d_nfr, d_linfo;
+    DevBuf<int64_t> d_cons;
+    HIPOK(hipMalloc((void **)d_raw.out(), 2 * raw_cap));
+    if (D > 1) { HIPOK(hipMalloc((void **)d_mod[0].out(), bps_mod * mod_cap)); HIPOK(hipMalloc((void **)d_mod[1].out(), bps_mod * mod_cap)); }
+    HIPOK(hipMalloc((void **)d_bits.out(), (size_t)max_frames * info.Nbits));
+    HIPOK(hipMalloc((void **)d_stats.out(), sizeof(float) * (size_t)max_frames * PIRIP_STATS_PER_FRAME));
+    HIPOK(hipMalloc((void **)d_nfr.out(), sizeof(int32_t)));
+    HIPOK(hipMalloc((void **)d_cons.out(), sizeof(int64_t)));
     if (ldpc) {
-        HIPOK(hipMalloc((void **)&d_status, (size_t)max_frames));
-        HIPOK(hipMalloc((void **)&d_payload, (size_t)max_frames * li.data_bytes));
-        HIPOK(hipMalloc((void **)&d_linfo, sizeof(int32_t) * (size_t)max_frames * PIRIP_LDPC_INFO_PER_CALL));
+        HIPOK(hipMalloc((void **)d_status.out(), (size_t)max_frames));
+        HIPOK(hipMalloc((void **)d_payload.out(), (size_t)max_frames * li.data_bytes));
+        HIPOK(hipMalloc((void **)d_linfo.out(), sizeof(int32_t) * (size_t)max_frames * PIRIP_LDPC_INFO_PER_CALL));
     }
     std::vector<uint8_t> bits((size_t)max_frames * info.Nbits), status((size_t)max_frames), payload((size_t)max_frames * (ldpc ? li.data_bytes : 1));
     std::vector<int32_t> linfo((size_t)max_frames * PIRIP_LDPC_INFO_PER_CALL);
@@ -273,21 +210,21 @@ int main(int argc, char **argv)
         const size_t got = want ? fread(raw.data() + 2 * raw_have, 2, want, fin) : 0;
         total_in += (long)got; raw_have += got;
         HIPOK(hipMemcpy(d_raw, raw.data(), 2 * raw_have, hipMemcpyHostToDevice));
-        const void *d_in = d_raw;
+        const void *d_in = d_raw.p;
         int64_t n_in = (int64_t)raw_have;
         if (D > 1) {
             // decimate on the device straight behind the carried modem samples: no host hop between decimator and demodulator
             const int64_t nout = pirip_hip_decim_nout(dec, (int64_t)raw_have);
             if (nout > 0) {
                 if (mod_have + (size_t)nout > mod_cap) { fprintf(stderr, "rtl_fsk: internal buffer sizing error\n"); return 2; }
-                rc = pirip_hip_decim_batch(dec, (const uint8_t *)d_raw, 0, (int64_t)raw_have, (char *)d_mod[cur] + bps_mod * mod_have, 0, 1, nullptr);
-                if (rc != PIRIP_OK) { fprintf(stderr, "rtl_fsk: decimator: %s\n", pirip_hip_strerror(rc)); return 2; }
+                rc = pirip_hip_decim_batch(dec, d_raw, 0, (int64_t)raw_have, d_mod[cur] + bps_mod * mod_have, 0, 1, nullptr);
+                if (rc != PIRIP_OK) return status_fail(kTool, "decimator", rc);
                 mod_have += (size_t)nout;
                 const size_t used = (size_t)nout * D;             // overlap carry: consumed = D * outputs
                 memmove(raw.data(), raw.data() + 2 * used, 2 * (raw_have - used));
                 raw_have -= used;
             }
-            d_in = d_mod[cur];
+            d_in = d_mod[cur].p;
             n_in = (int64_t)mod_have;
         }
         // --code: demodulator and FSK_LDPC receiver in one call (bit LLRs handed over on the device); else bits out
@@ -309,7 +246,7 @@ int main(int argc, char **argv)
         // carry the unconsumed modem-rate tail in front of the next block
         if (D > 1) {
             const size_t left = mod_have - (size_t)cons;
-            if (left) HIPOK(hipMemcpy(d_mod[cur ^ 1], (char *)d_mod[cur] + bps_mod * (size_t)cons, bps_mod * left, hipMemcpyDeviceToDevice));
+            if (left) HIPOK(hipMemcpy(d_mod[cur ^ 1], d_mod[cur] + bps_mod * (size_t)cons, bps_mod * left, hipMemcpyDeviceToDevice));
             mod_have = left; cur ^= 1;
         } else {
             memmove(raw.data(), raw.data() + 2 * cons, 2 * (raw_have - (size_t)cons));
@@ -365,7 +302,7 @@ int main(int argc, char **argv)
             for (size_t i = 0; i < timing_acc.size(); i++) js += (i ? ", " : "") + std::to_string(timing_acc[i]);
             js += "], \"SfdB\": [";
             for (int i = 0; i < info.Ndft; i++) js += (i ? ", " : "") + std::to_string(20.0 * log10(Sf[i] + 1e-12));
-            js += "], \"fsk_lower_Hz\": " + std::to_string(fsk_lower) + ", \"fsk_upper_Hz\": " + std::to_string(fsk_upper) + ", \"f_est_Hz\": [";
+            js += "], \"fsk_lower_Hz\": " + std::to_string(prm.est_min) + ", \"fsk_upper_Hz\": " + std::to_string(prm.est_max) + ", \"f_est_Hz\": [";
             for (int m = 0; m < M; m++) js += (m ? ", " : "") + std::to_string(s[m]);
             js += "], \"Fs_Hz\": " + std::to_string(Fs) + "}\n";
             sendto(sock, js.data(), js.size(), 0, (sockaddr *)&dst, sizeof(dst));
@@ -373,11 +310,5 @@ int main(int argc, char **argv)
         }
         if (got < want || (nsamples && total_in >= nsamples) || want == 0) break;
     }
-    if (fout != stdout) fclose(fout);
-    pirip_hip_destroy(h);
-    if (dec) pirip_hip_decim_destroy(dec);
-    if (ldpc) pirip_hip_ldpc_destroy(ldpc);
-    void *ptrs[] = {d_raw, d_mod[0], d_mod[1], d_bits, d_stats, d_nfr, d_cons, d_status, d_payload, d_linfo};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     return 0;
 }

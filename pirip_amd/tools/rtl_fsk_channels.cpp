@@ -18,8 +18,6 @@
 // frames for packets, payload bits compared, payload bit errors); exit 0 only if every channel meets that tool's PASS rule
 // (packets >= packetsPass && bits > 0 && BER <= berPass), else 1.
 #include <getopt.h>
-#include <sys/stat.h>
-#include <unistd.h>
 
 #include <cstdio>
 #include <cstdlib>
@@ -27,9 +25,7 @@
 #include <string>
 #include <vector>
 
-#include <hip/hip_runtime_api.h>
-
-#include "../../include/pirip_hip.h"
+#include "tool_common.hpp"
 
 static void usage()
 {
@@ -40,47 +36,11 @@ static void usage()
             "        writes PREFIX.<k> per channel: bits one per byte, or with --code the payload bytes of every CRC-ok frame\n");
 }
 
-static bool file_exists(const std::string &p) { struct stat st; return !p.empty() && stat(p.c_str(), &st) == 0 && S_ISREG(st.st_mode); }
-
-// --code NAME: NAME as a file path, then $PIRIP_CODE_DIR/NAME.code, then <exe>/../data/NAME.code (as rtl_fsk resolves it)
-static std::string resolve_code(const std::string &name, const char *argv0)
-{
-    if (file_exists(name)) return name;
-    if (const char *d = getenv("PIRIP_CODE_DIR")) { const std::string p = std::string(d) + "/" + name + ".code"; if (file_exists(p)) return p; }
-    char exe[4096];
-    const ssize_t n = readlink("/proc/self/exe", exe, sizeof(exe) - 1);
-    std::string base = n > 0 ? std::string(exe, (size_t)n) : std::string(argv0);
-    const size_t s = base.rfind('/');
-    base = s == std::string::npos ? "." : base.substr(0, s);
-    const std::string p = base + "/../data/" + name + ".code";
-    return file_exists(p) ? p : std::string();
-}
-
-static bool parse_offsets(const char *s, std::vector<int32_t> &out)
-{
-    std::string all(s);
-    for (size_t pos = 0; pos <= all.size();) {
-        size_t end = all.find(',', pos);
-        if (end == std::string::npos) end = all.size();
-        const std::string tok = all.substr(pos, end - pos);
-        if (tok.empty()) return false;
-        char *e = nullptr;
-        const long v = strtol(tok.c_str(), &e, 10);
-        if (*e) return false;
-        out.push_back((int32_t)v);
-        pos = end + 1;
-    }
-    return !out.empty();
-}
-
-#define HIPOK(expr) do { if ((expr) != hipSuccess) { fprintf(stderr, "rtl_fsk_channels: HIP error at %s:%d\n", __FILE__, __LINE__); return 2; } } while (0)
-#define PIRIPOK(expr, what) do { const int rc_ = (expr); if (rc_ != PIRIP_OK) { fprintf(stderr, "rtl_fsk_channels: %s: %s\n", what, pirip_hip_strerror(rc_)); return 2; } } while (0)
+static const ToolErrors kTool{"rtl_fsk_channels", [](int) { return 2; }};
 
 int main(int argc, char **argv)
 {
-    if (!pirip_hip_abi_check(PIRIP_HIP_ABI_VERSION, PIRIP_STATS_PER_FRAME, sizeof(pirip_stream_state))) {
-        fprintf(stderr, "%s: built against a different pirip_hip.h than %s\n", argv[0], pirip_hip_version()); return 2;
-    }
+    if (!abi_ok(argv[0])) return 2;
     long rtlFs = 0, modemFs = 0, Rs = 0;
     int M = 2, mask = 0, quiet = 0, fsk_lower = 0, fsk_upper = 0, user_lower = 0, user_upper = 0;
     int put_bits = 0, testframes = 0, framesize = 100, packet_pass = 0;
@@ -98,7 +58,7 @@ int main(int argc, char **argv)
         case 'a': modemFs = (long)atof(optarg); break;
         case 'r': Rs = (long)atof(optarg); break;
         case 'm': M = atoi(optarg); break;
-        case 'c': if (!parse_offsets(optarg, offsets)) { fprintf(stderr, "rtl_fsk_channels: -c wants integer offsets in Hz, comma separated\n"); return 1; } break;
+        case 'c': if (!parse_list(optarg, offsets, conv_i32)) { fprintf(stderr, "rtl_fsk_channels: -c wants integer offsets in Hz, comma separated\n"); return 1; } break;
         case 'i': in_name = optarg; break;
         case 'o': prefix = optarg; break;
         case 'q': quiet = 1; break;
@@ -121,68 +81,63 @@ int main(int argc, char **argv)
     if (put_bits && !code.empty()) { fprintf(stderr, "rtl_fsk_channels: --put-test-bits counts uncoded bits; with --code use --testframes\n"); return 1; }
     if (testframes && code.empty()) { fprintf(stderr, "rtl_fsk_channels: --testframes needs --code\n"); return 1; }
     const int D = (int)(rtlFs / modemFs), Fs = (int)modemFs, K = (int)offsets.size();
-    const int Ts = Fs / (int)Rs;
-    int P = Ts;
-    while (P > 10 && (P % 2) == 0) P /= 2;                       // rtl_fsk's oversample rule
-    if (P < 4) P = Ts;
-    if (!user_lower) fsk_lower = (int)Rs / 2;
-    if (!user_upper) fsk_upper = Fs / 2;
     std::string code_path;
     if (!code.empty() && (code_path = resolve_code(code, argv[0])).empty()) {
         fprintf(stderr, "rtl_fsk_channels: no table for --code %s (format: pirip_amd/csrc/fsk_ldpc.hpp; $PIRIP_CODE_DIR or a file path)\n", code.c_str());
         return 2;
     }
-    FILE *fin = in_name == "-" ? stdin : fopen(in_name.c_str(), "rb");
+    File fin(in_name == "-" ? stdin : fopen(in_name.c_str(), "rb"));
     if (!fin) { fprintf(stderr, "rtl_fsk_channels: can't open %s\n", in_name.c_str()); return 1; }
-    std::vector<FILE *> fout((size_t)K);
+    std::vector<File> fout((size_t)K);
     for (int k = 0; k < K; k++) {
         const std::string name = prefix + "." + std::to_string(k);
-        if (!(fout[(size_t)k] = fopen(name.c_str(), "wb"))) { fprintf(stderr, "rtl_fsk_channels: can't open %s\n", name.c_str()); return 1; }
+        if (!(fout[(size_t)k].p = fopen(name.c_str(), "wb"))) { fprintf(stderr, "rtl_fsk_channels: can't open %s\n", name.c_str()); return 1; }
     }
 
     // handles: K channels of one capture -> K complex-float modem streams -> bits, or FSK_LDPC records
     std::vector<int32_t> inputs((size_t)K, 0);
-    pirip_hip_chan *chan = nullptr;
-    pirip_hip_demod *dem = nullptr;
-    pirip_hip_ldpc *ldpc = nullptr;
-    pirip_hip_rx *rx = nullptr;
-    PIRIPOK(pirip_hip_chan_create((int)rtlFs, D, 0.05f, 0, 1, K, inputs.data(), offsets.data(), -1, &chan), "channelizer");
-    pirip_fsk_params prm{Fs, (int)Rs, M, P, PIRIP_FSK_DEFAULT_NSYM, fsk_lower, fsk_upper, mask ? 1 : 0, mask ? mask : 100, PIRIP_IN_CF32};
-    PIRIPOK(pirip_hip_create(&prm, K, -1, &dem), "demodulator");
+    ChanHandle chan;
+    DemodHandle dem;
+    LdpcHandle ldpc;
+    RxHandle rx;
+    TbitsHandle tb;
+    PIRIPOK(pirip_hip_chan_create((int)rtlFs, D, 0.05f, 0, 1, K, inputs.data(), offsets.data(), -1, chan.out()), "channelizer");
+    // rtl_fsk's modem settings, under its default rules
+    const pirip_fsk_params prm = rtl_fsk_params(Fs, (int)Rs, M, mask, user_lower ? &fsk_lower : nullptr, user_upper ? &fsk_upper : nullptr, PIRIP_IN_CF32);
+    PIRIPOK(pirip_hip_create(&prm, K, -1, dem.out()), "demodulator");
     pirip_ldpc_info li{};
     if (!code_path.empty()) {
-        PIRIPOK(pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, K, -1, &ldpc), "--code");
+        PIRIPOK(pirip_hip_ldpc_create(code_path.c_str(), M, PIRIP_FSK_DEFAULT_NSYM, K, -1, ldpc.out()), "--code");
         pirip_hip_ldpc_get_info(ldpc, &li);
     }
-    pirip_hip_tbits *tb = nullptr;
-    if (put_bits) PIRIPOK(pirip_hip_tbits_create(framesize, valid_thresh, nullptr, K, -1, &tb), "--put-test-bits");
+    if (put_bits) PIRIPOK(pirip_hip_tbits_create(framesize, valid_thresh, nullptr, K, -1, tb.out()), "--put-test-bits");
     if (testframes) {
-        PIRIPOK(pirip_hip_tbits_create(framesize, valid_thresh, nullptr, K, -1, &tb), "--testframes");
+        PIRIPOK(pirip_hip_tbits_create(framesize, valid_thresh, nullptr, K, -1, tb.out()), "--testframes");
         PIRIPOK(pirip_hip_tbits_set_payload(tb, li.data_bytes, nullptr), "--testframes");
     }
     const int64_t block = (int64_t)(rtlFs / 4) / D * D;
-    PIRIPOK(pirip_hip_rx_create_chan(dem, ldpc, chan, block, &rx), "receiver");
+    PIRIPOK(pirip_hip_rx_create_chan(dem, ldpc, chan, block, rx.out()), "receiver");
     pirip_fsk_info info;
     pirip_hip_get_info(dem, &info);
     if (!quiet)
         fprintf(stderr, "rtl_fsk_channels: rtl rate %ld Fs %d Rs %ld M %d P %d decimation %d channels %d estimator %d..%d Hz%s%s\n", rtlFs, Fs, Rs,
-                M, P, D, K, fsk_lower, fsk_upper, ldpc ? " code " : "", ldpc ? li.name : "");
+                M, prm.P, D, K, prm.est_min, prm.est_max, ldpc ? " code " : "", ldpc ? li.name : "");
 
     const int64_t R = pirip_hip_rx_max_frames(rx);
     void *d_block = nullptr;
     size_t in_stride = 0;
     PIRIPOK(pirip_hip_rx_input(rx, &d_block, &in_stride), "receiver input");
-    uint8_t *d_bits = nullptr, *d_status = nullptr, *d_payload = nullptr;
-    int32_t *d_info = nullptr, *d_nfr = nullptr;
+    DevBuf<uint8_t> d_bits, d_status, d_payload;
+    DevBuf<int32_t> d_info, d_nfr;
     const size_t rows = (size_t)K * (size_t)R;
     if (ldpc) {
-        HIPOK(hipMalloc((void **)&d_status, rows));
-        HIPOK(hipMalloc((void **)&d_payload, rows * (size_t)li.data_bytes));
-        HIPOK(hipMalloc((void **)&d_info, sizeof(int32_t) * rows * PIRIP_LDPC_INFO_PER_CALL));
+        HIPOK(hipMalloc((void **)d_status.out(), rows));
+        HIPOK(hipMalloc((void **)d_payload.out(), rows * (size_t)li.data_bytes));
+        HIPOK(hipMalloc((void **)d_info.out(), sizeof(int32_t) * rows * PIRIP_LDPC_INFO_PER_CALL));
     } else {
-        HIPOK(hipMalloc((void **)&d_bits, rows * (size_t)info.Nbits));
+        HIPOK(hipMalloc((void **)d_bits.out(), rows * (size_t)info.Nbits));
     }
-    HIPOK(hipMalloc((void **)&d_nfr, sizeof(int32_t) * (size_t)K));
+    HIPOK(hipMalloc((void **)d_nfr.out(), sizeof(int32_t) * (size_t)K));
     std::vector<uint8_t> raw((size_t)block * 2), bits(ldpc ? 0 : rows * (size_t)info.Nbits), status(ldpc ? rows : 0),
         payload(ldpc ? rows * (size_t)li.data_bytes : 0);
     std::vector<int32_t> nfr((size_t)K);
@@ -214,7 +169,6 @@ int main(int argc, char **argv)
         blocks++;
     }
     if (!quiet) fprintf(stderr, "rtl_fsk_channels: %ld blocks of %lld samples\n", blocks, (long long)block);
-    for (FILE *f : fout) fclose(f);
     int verdict = 0;
     if (tb) {
         std::vector<int64_t> pk((size_t)K), nb((size_t)K), ne((size_t)K);
@@ -227,14 +181,6 @@ int main(int argc, char **argv)
             if (!(pk[(size_t)k] >= packet_pass && bitcnt > 0 && ber <= ber_pass)) verdict = 1;
         }
         fprintf(stderr, verdict ? "FAIL\n" : "PASS\n");
-        pirip_hip_tbits_destroy(tb);
     }
-    if (fin != stdin) fclose(fin);
-    pirip_hip_rx_destroy(rx);
-    if (ldpc) pirip_hip_ldpc_destroy(ldpc);
-    pirip_hip_destroy(dem);
-    pirip_hip_chan_destroy(chan);
-    void *ptrs[] = {d_bits, d_status, d_payload, d_info, d_nfr};
-    for (void *p : ptrs) if (p) (void)hipFree(p);
     return verdict;
 }
