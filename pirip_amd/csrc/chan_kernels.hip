@@ -294,14 +294,7 @@ int pirip_hip_chan_create(int Fs, int decimation, float transition_bw, int out_s
     return PIRIP_OK;
 }
 
-int pirip_hip_chan_destroy(pirip_hip_chan *ch)
-{
-    if (!ch) return PIRIP_ERR_BAD_ARG;
-    (void)bind_device(ch->device);
-    (void)hipDeviceSynchronize();
-    delete ch;
-    return PIRIP_OK;
-}
+int pirip_hip_chan_destroy(pirip_hip_chan *ch) { return destroy_handle(ch, ch ? ch->device : 0); }
 
 int pirip_hip_chan_get_info(const pirip_hip_chan *ch, pirip_chan_info *info)
 {

@@ -492,14 +492,7 @@ int pirip_hip_decim_create(int decimation, float transition_bw, int out_s16, int
     return PIRIP_OK;
 }
 
-int pirip_hip_decim_destroy(pirip_hip_decim *d)
-{
-    if (!d) return PIRIP_ERR_BAD_ARG;
-    (void)bind_device(d->device);
-    (void)hipDeviceSynchronize();
-    delete d;
-    return PIRIP_OK;
-}
+int pirip_hip_decim_destroy(pirip_hip_decim *d) { return destroy_handle(d, d ? d->device : 0); }
 
 int pirip_hip_decim_set_arith(pirip_hip_decim *d, int mode)
 {

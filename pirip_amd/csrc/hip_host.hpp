@@ -8,6 +8,7 @@
 #include <hip/hip_runtime.h>
 
 #include <cstddef>
+#include <cstdint>
 #include <initializer_list>
 #include <vector>
 
@@ -51,7 +52,7 @@ static inline int bytes_per_sample(int fmt)
 // Owner of a handle's device allocations, held by value in the handle. The handle keeps its typed pointers (they go into kernel
 // arguments as they are); DevMem remembers every allocation made through it, so that nothing has to list them again to free them.
 // The destructor frees what is left: `delete h` is the whole error path of a create function, and a destroy function is bind,
-// synchronise, delete.
+// synchronise, delete (destroy_handle).
 class DevMem {
 public:
     DevMem() = default;
@@ -66,6 +67,14 @@ public:
         if (hipMalloc(&q, bytes) != hipSuccess) return PIRIP_ERR_NOMEM;
         if (q) owned_.push_back(Owned{q});
         *p = (T *)q;
+        return PIRIP_OK;
+    }
+    // allocate and set every byte to `byte` (synchronous)
+    template <typename T>
+    int alloc_filled(T **p, int byte, size_t bytes)
+    {
+        PIRIP_TRY(alloc(p, bytes));
+        if (bytes) PIRIP_HIPCHK(hipMemset(*p, byte, bytes));
         return PIRIP_OK;
     }
     // allocate and copy from the host (synchronous); an empty table still gets an allocation (16 bytes): its pointer goes to kernels
@@ -111,6 +120,37 @@ int grow_dev(DevMem &mem, C *cap, C want, GrowSync sync, hipStream_t st, std::in
     *cap = 0;
     for (const GrowBuf &b : bufs) if (b.bytes) PIRIP_TRY(mem.alloc(b.p, b.bytes));
     *cap = want;
+    return PIRIP_OK;
+}
+
+// every destroy function: wait for the handle's work on its device, then free what it owns
+template <class H>
+static inline int destroy_handle(H *h, int device)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    (void)bind_device(device);
+    (void)hipDeviceSynchronize();
+    delete h;
+    return PIRIP_OK;
+}
+
+// every counter getter: out.size() elements from the device, behind all the work enqueued on it
+template <typename T>
+static inline int read_back(int device, const T *d_src, std::vector<T> &out)
+{
+    if (!bind_device(device)) return PIRIP_ERR_NO_DEVICE;
+    PIRIP_HIPCHK(hipDeviceSynchronize());
+    PIRIP_HIPCHK(hipMemcpy(out.data(), d_src, sizeof(T) * out.size(), hipMemcpyDeviceToHost));
+    return PIRIP_OK;
+}
+
+// Rows of IQ output, nsamp samples of bytes_per_sample each: pointer and stride are whole samples, and with more than one row the stride
+// holds a row (rows would overlap). An entry point whose parent checked other things between the two asks twice: nrows = 1 asks the
+// first only.
+static inline int iq_rows_check(const void *d_out, size_t stride_bytes, int bytes_per_sample, int nrows, int64_t nsamp)
+{
+    if (((uintptr_t)d_out | stride_bytes) & (size_t)(bytes_per_sample - 1)) return PIRIP_ERR_BAD_ARG;
+    if (nrows > 1 && stride_bytes < (size_t)nsamp * (size_t)bytes_per_sample) return PIRIP_ERR_BAD_ARG;
     return PIRIP_OK;
 }
 

@@ -138,14 +138,7 @@ int pirip_hip_mux_create(int Fs, int interpolation, int kind, float transition_b
     return PIRIP_OK;
 }
 
-int pirip_hip_mux_destroy(pirip_hip_mux *mx)
-{
-    if (!mx) return PIRIP_ERR_BAD_ARG;
-    (void)bind_device(mx->device);
-    (void)hipDeviceSynchronize();
-    delete mx;
-    return PIRIP_OK;
-}
+int pirip_hip_mux_destroy(pirip_hip_mux *mx) { return destroy_handle(mx, mx ? mx->device : 0); }
 
 int pirip_hip_mux_get_info(const pirip_hip_mux *mx, pirip_mux_info *info)
 {
@@ -170,11 +163,11 @@ int pirip_hip_mux_batch(pirip_hip_mux *mx, const void *d_in, size_t in_stride_by
 {
     if (!mx || !d_in || !d_out || n_in < 0) return PIRIP_ERR_BAD_ARG;
     if (((uintptr_t)d_in | in_stride_bytes) & 7) return PIRIP_ERR_BAD_ARG;                  // whole complex floats
-    if (((uintptr_t)d_out | out_stride_bytes) & (size_t)(mx->bs - 1)) return PIRIP_ERR_BAD_ARG;
+    PIRIP_TRY(iq_rows_check(d_out, out_stride_bytes, mx->bs, 1, 0));
     if (n_in > ((int64_t)1 << 40) / mx->D) return PIRIP_ERR_UNSUPPORTED;
     const int64_t n_out = pirip_hip_mux_nout(mx, n_in);
     if (n_out <= 0) return PIRIP_OK;
-    if (mx->noutputs > 1 && out_stride_bytes < (size_t)n_out * mx->bs) return PIRIP_ERR_BAD_ARG;   // rows would overlap
+    PIRIP_TRY(iq_rows_check(d_out, out_stride_bytes, mx->bs, mx->noutputs, n_out));
     if (!bind_device(mx->device)) return PIRIP_ERR_NO_DEVICE;
     const int64_t ntiles = (n_out + kMuxTile - 1) / kMuxTile;
     if (ntiles > 0x7fffffff) return PIRIP_ERR_UNSUPPORTED;

@@ -21,6 +21,8 @@
 #include "../../include/pirip_hip.h"
 #include "hip_host.hpp"
 #include "ldpc_handle.hpp"
+#include "mux_handle.hpp"
+#include "repeat_device.hpp"
 #include "rpt_handle.hpp"
 #include "tx_handle.hpp"
 #include "txs_handle.hpp"
@@ -29,52 +31,31 @@ using namespace pirip;
 
 namespace {
 
-constexpr int kMaxCalls = 4096;            // the call table lives in LDS (as pirip_hip_tx_repeat_records')
-
 struct IntakeArgs {
-    const uint8_t *status; size_t status_stride; const uint8_t *payload; size_t payload_stride; const int32_t *ncalls_s; int ncalls;
-    int32_t *state;                        // [nrx][2] receiving, frames held
-    uint8_t *held;                         // [nrx][max_burst][kb]
+    RepeatIn in;
     const int32_t *route;                  // [nrx]
     RptRxCount *cnt;                       // [nrx]
     RptRing *rs;                           // [ntx]
     uint8_t *ring; int64_t *ready; int32_t *blen;
-    int pending, kb, max_burst, source, filter;
+    int pending, filter;
     int64_t ready_at;                      // n + holdoff
 };
 
-// Lane 0 walks the status bytes (staged in LDS with the filter applied) through tx_handle.hpp's state machine and then places every burst
-// that ended: its first record's offset behind the ring's tail, or nowhere (no route, or no room for all of it). The wave then copies the
-// payloads, lane-parallel: into the ring across its wrap, or into the handle for the burst that is still open.
+// One wave per receive channel: repeat_device.hpp's body with the filter applied to the status bytes it stages. Behind the walk lane 0
+// places every burst that ended: its first record's offset behind the ring's tail, or nowhere (-2: no route, or no room for all of it).
+// The wave's copies then go into the ring of route[c], across its wrap.
 __global__ __launch_bounds__(64) void rpt_intake_kernel(IntakeArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int32_t *s_act = (int32_t *)smem;                        // [ncalls] -1, or (burst << 16) | slot of the call's frame
-    int32_t *s_base = s_act + a.ncalls;                      // [ncalls + 1] a burst's first record behind the tail; -1 still open, -2 not kept
-    int32_t *s_n = s_base + a.ncalls + 1;                    // [ncalls + 1] frames of the burst
-    uint8_t *s_st = (uint8_t *)(s_n + a.ncalls + 1);         // [ncalls]
-    __shared__ int32_t s_hdr[4];                             // bursts, records out, receiving, frames held at the end
     __shared__ int32_t s_start;                              // the ring slot of the tail
-    const int c = blockIdx.x, lane = threadIdx.x;
-    int nc = a.ncalls_s ? a.ncalls_s[c] : a.ncalls;
-    nc = nc < 0 ? 0 : (nc > a.ncalls ? a.ncalls : nc);
-    const uint8_t *st = a.status + (size_t)c * a.status_stride;
-    const uint8_t *pl = a.payload + (size_t)c * a.payload_stride;
-    uint8_t *held = a.held + (size_t)c * a.max_burst * a.kb;
-    const int rl = 1 + a.kb;
-    const int held0 = a.state[2 * c + 1];
-    const int t = a.route[c];
+    const int c = blockIdx.x, t = a.route[c];
+    const int rl = 1 + a.in.kb;
+    uint8_t *ring = a.ring + (size_t)(t >= 0 ? t : 0) * a.pending * rl;
     int nfilt = 0;
-    for (int i = lane; i < nc; i += 64) {                    // rtl_fsk --filter: a frame of the repeater's own is no frame
-        uint8_t v = st[i];
-        if ((v & PIRIP_RX_BITS) && a.filter >= 0 && pl[(size_t)i * a.kb] == (uint8_t)a.filter) { v = (uint8_t)(v & ~PIRIP_RX_BITS); nfilt++; }
-        s_st[i] = v;
-    }
-    for (int d = 32; d > 0; d >>= 1) nfilt += __shfl_down(nfilt, d, 64);
-    __syncthreads();
-    if (lane == 0) {
-        tx_repeat_walk([&](int i) { return (int)s_st[i]; }, nc, a.state[2 * c], held0, a.max_burst, s_act, s_base, s_n, s_hdr);
-        const int nb = s_hdr[0];
+    auto status = [&](uint8_t v, const uint8_t *frame) {     // rtl_fsk --filter: a frame of the repeater's own is no frame
+        if ((v & PIRIP_RX_BITS) && a.filter >= 0 && frame[0] == (uint8_t)a.filter) { v = (uint8_t)(v & ~PIRIP_RX_BITS); nfilt++; }
+        return v;
+    };
+    auto place = [&](int nb, int32_t *base, const int32_t *nfr) {
         int64_t frames = 0, unrouted = 0, dropped = 0;
         int off = 0, start = 0;
         if (t >= 0) {
@@ -82,58 +63,28 @@ __global__ __launch_bounds__(64) void rpt_intake_kernel(IntakeArgs a)
             int64_t room = (int64_t)a.pending - (int64_t)(tail - head);
             start = (int)(tail % (uint64_t)a.pending);
             for (int b = 0; b < nb; b++) {
-                const int len = s_n[b] + 1;
-                frames += s_n[b];
+                const int len = nfr[b] + 1;
+                frames += nfr[b];
                 if (len <= room) {
-                    int slot = start + off;
-                    if (slot >= a.pending) slot -= a.pending;
+                    const int slot = ring_slot(start, off, a.pending);
                     a.ready[(size_t)t * a.pending + slot] = a.ready_at;
                     a.blen[(size_t)t * a.pending + slot] = len;
-                    s_base[b] = off; off += len; room -= len;
+                    base[b] = off; off += len; room -= len;
                 } else {
-                    s_base[b] = -2; dropped++;
+                    base[b] = -2; dropped++;
                 }
             }
             a.rs[t].tail = tail + (uint64_t)off;
             a.rs[t].dropped += dropped;
         } else {
-            for (int b = 0; b < nb; b++) { frames += s_n[b]; s_base[b] = -2; unrouted++; }
+            for (int b = 0; b < nb; b++) { frames += nfr[b]; base[b] = -2; unrouted++; }
         }
         s_start = start;
-        a.cnt[c].bursts += nb; a.cnt[c].frames += frames; a.cnt[c].filtered += nfilt; a.cnt[c].unrouted += unrouted;
-    }
-    __syncthreads();
-    const int nb = s_hdr[0], start = s_start;
-    uint8_t *ring = a.ring + (size_t)(t >= 0 ? t : 0) * a.pending * rl;
-    auto slot_of = [&](int j) { int s = start + j; return s >= a.pending ? s - a.pending : s; };
-    // frames that were held from earlier calls belong to burst 0: out they go if it ended here and is kept (else they stay or are forgotten)
-    if (held0 > 0 && nb > 0 && s_base[0] >= 0)
-        for (int i = lane; i < held0 * a.kb; i += 64) {
-            const int j = i / a.kb, o = i - j * a.kb;
-            uint8_t *rec = ring + (size_t)slot_of(s_base[0] + j) * rl;
-            rec[1 + o] = o == 0 ? (uint8_t)a.source : held[i];
-            if (o == 0) rec[0] = j == 0 ? 1 : 0;
-        }
-    __syncthreads();
-    for (int i = lane; i < nc * a.kb; i += 64) {
-        const int q = i / a.kb, o = i - q * a.kb;
-        const int act = s_act[q];
-        if (act < 0) continue;
-        const int b = act >> 16, slot = act & 0xffff;
-        const uint8_t v = pl[(size_t)q * a.kb + o];
-        if (s_base[b] >= 0) {
-            uint8_t *rec = ring + (size_t)slot_of(s_base[b] + slot) * rl;
-            rec[1 + o] = o == 0 ? (uint8_t)a.source : v;     // the repeater's own source address
-            if (o == 0) rec[0] = slot == 0 ? 1 : 0;
-        } else if (s_base[b] == -1) {
-            held[(size_t)slot * a.kb + o] = v;
-        }
-    }
-    for (int i = lane; i < nb * rl; i += 64) {               // end of burst: control byte 2, zero data
-        const int b = i / rl, o = i - b * rl;
-        if (s_base[b] >= 0) ring[(size_t)slot_of(s_base[b] + s_n[b]) * rl + o] = o == 0 ? 2 : 0;
-    }
-    if (lane == 0) { a.state[2 * c] = s_hdr[2]; a.state[2 * c + 1] = s_hdr[3]; }
+        a.cnt[c].bursts += nb; a.cnt[c].frames += frames; a.cnt[c].unrouted += unrouted;
+    };
+    repeat_stream(a.in, c, status, place, [&](int base, int j) { return base >= 0 ? ring + (size_t)ring_slot(s_start, base + j, a.pending) * rl : nullptr; });
+    nfilt = wave_sum(nfilt);
+    if (threadIdx.x == 0) a.cnt[c].filtered += nfilt;
 }
 
 struct OfferArgs {
@@ -154,14 +105,14 @@ __global__ __launch_bounds__(64) void rpt_offer_kernel(OfferArgs a)
     const uint64_t head = a.rs[t].head, tail = a.rs[t].tail;
     int64_t room = a.queue_syms - (int64_t)(a.queue[t].tail - a.queue[t].head);
     const int gap = a.gap[t] > 0 ? a.gap[t] : 0;              // tx_layout_kernel's rule
+    const int64_t first_syms = tx_record_syms(1, a.psyms, a.fsyms, gap), next_syms = tx_record_syms(0, a.psyms, a.fsyms, gap);
     const int start = (int)(head % (uint64_t)a.pending);
     int take = 0, bursts = 0;
     while (head + (uint64_t)take < tail) {
-        int slot = start + take;
-        if (slot >= a.pending) slot -= a.pending;
+        const int slot = ring_slot(start, take, a.pending);
         const int len = a.blen[(size_t)t * a.pending + slot];
         if (len < 2 || take + len > a.pending || a.ready[(size_t)t * a.pending + slot] > a.now) break;
-        const int64_t cost = (int64_t)a.psyms + (int64_t)(len - 1) * a.fsyms + gap;
+        const int64_t cost = first_syms + (len - 2) * next_syms + tx_record_syms(2, a.psyms, a.fsyms, gap);     // records 1, 0, ..., 0, 2
         if (cost > room) break;                              // head of the line: the bursts behind it wait
         room -= cost; take += len; bursts++;
     }
@@ -192,29 +143,20 @@ int rpt_alloc(pirip_hip_rpt *r, const int32_t *route)
     DevMem &m = r->mem;
     PIRIP_TRY(m.upload(&r->d_route, route, sizeof(int32_t) * nrx));
     PIRIP_TRY(m.alloc(&r->d_state, sizeof(int32_t) * 2 * nrx));
-    PIRIP_TRY(m.alloc(&r->d_held, nrx * (size_t)r->max_burst * (size_t)r->kb));
+    PIRIP_TRY(m.alloc_filled(&r->d_held, 0, nrx * (size_t)r->max_burst * (size_t)r->kb));
     PIRIP_TRY(m.alloc(&r->d_cnt, sizeof(RptRxCount) * nrx));
     PIRIP_TRY(m.alloc(&r->d_ring_state, sizeof(RptRing) * ntx));
-    PIRIP_TRY(m.alloc(&r->d_ring, ntx * P * rl));
-    PIRIP_TRY(m.alloc(&r->d_ready, sizeof(int64_t) * ntx * P));
-    PIRIP_TRY(m.alloc(&r->d_blen, sizeof(int32_t) * ntx * P));
-    PIRIP_TRY(m.alloc(&r->d_offered, ntx * P * rl));
+    PIRIP_TRY(m.alloc_filled(&r->d_ring, 0, ntx * P * rl));
+    PIRIP_TRY(m.alloc_filled(&r->d_ready, 0, sizeof(int64_t) * ntx * P));
+    PIRIP_TRY(m.alloc_filled(&r->d_blen, 0, sizeof(int32_t) * ntx * P));
+    PIRIP_TRY(m.alloc_filled(&r->d_offered, 0, ntx * P * rl));
     PIRIP_TRY(m.alloc(&r->d_noffered, sizeof(int32_t) * ntx));
-    PIRIP_HIPCHK(hipMemset(r->d_held, 0, nrx * (size_t)r->max_burst * (size_t)r->kb));
-    PIRIP_HIPCHK(hipMemset(r->d_ring, 0, ntx * P * rl));
-    PIRIP_HIPCHK(hipMemset(r->d_ready, 0, sizeof(int64_t) * ntx * P));
-    PIRIP_HIPCHK(hipMemset(r->d_blen, 0, sizeof(int32_t) * ntx * P));
-    PIRIP_HIPCHK(hipMemset(r->d_offered, 0, ntx * P * rl));
     if (r->rx) {
         const size_t R = (size_t)r->rx_rows;
-        PIRIP_TRY(m.alloc(&r->d_status, nrx * R));
-        PIRIP_TRY(m.alloc(&r->d_payload, nrx * R * (size_t)r->kb));
-        PIRIP_TRY(m.alloc(&r->d_info, sizeof(int32_t) * nrx * R * PIRIP_LDPC_INFO_PER_CALL));
-        PIRIP_TRY(m.alloc(&r->d_nframes, sizeof(int32_t) * nrx));
-        PIRIP_HIPCHK(hipMemset(r->d_status, 0, nrx * R));
-        PIRIP_HIPCHK(hipMemset(r->d_payload, 0, nrx * R * (size_t)r->kb));
-        PIRIP_HIPCHK(hipMemset(r->d_info, 0, sizeof(int32_t) * nrx * R * PIRIP_LDPC_INFO_PER_CALL));
-        PIRIP_HIPCHK(hipMemset(r->d_nframes, 0, sizeof(int32_t) * nrx));
+        PIRIP_TRY(m.alloc_filled(&r->d_status, 0, nrx * R));
+        PIRIP_TRY(m.alloc_filled(&r->d_payload, 0, nrx * R * (size_t)r->kb));
+        PIRIP_TRY(m.alloc_filled(&r->d_info, 0, sizeof(int32_t) * nrx * R * PIRIP_LDPC_INFO_PER_CALL));
+        PIRIP_TRY(m.alloc_filled(&r->d_nframes, 0, sizeof(int32_t) * nrx));
     }
     PIRIP_TRY(txs_reserve(r->txs, r->pending));
     PIRIP_TRY(rpt_clear(r, nullptr));
@@ -228,19 +170,17 @@ int rpt_run(pirip_hip_rpt *r, const uint8_t *d_status, size_t status_stride, con
 {
     const pirip_hip_tx *tx = r->tx;
     IntakeArgs ia{};
-    ia.status = d_status; ia.status_stride = status_stride; ia.payload = d_payload; ia.payload_stride = payload_stride;
-    ia.ncalls_s = d_ncalls; ia.ncalls = ncalls;
-    ia.state = r->d_state; ia.held = r->d_held; ia.route = r->d_route; ia.cnt = r->d_cnt; ia.rs = r->d_ring_state;
+    ia.in = RepeatIn{d_status, status_stride, d_payload, payload_stride, d_ncalls, ncalls, r->d_state, r->d_held, r->kb, r->max_burst, r->source};
+    ia.route = r->d_route; ia.cnt = r->d_cnt; ia.rs = r->d_ring_state;
     ia.ring = r->d_ring; ia.ready = r->d_ready; ia.blen = r->d_blen;
-    ia.pending = r->pending; ia.kb = r->kb; ia.max_burst = r->max_burst; ia.source = r->source; ia.filter = r->filter;
+    ia.pending = r->pending; ia.filter = r->filter;
     ia.ready_at = r->calls + r->holdoff;
-    const size_t lds = sizeof(int32_t) * (3 * (size_t)ncalls + 2) + (size_t)ncalls + 16;
-    hipLaunchKernelGGL(rpt_intake_kernel, dim3((unsigned)r->nrx), dim3(64), lds, st, ia);
+    hipLaunchKernelGGL(rpt_intake_kernel, dim3((unsigned)r->nrx), dim3(64), repeat_lds_bytes(ncalls), st, ia);
     OfferArgs oa{};
     oa.rs = r->d_ring_state; oa.ring = r->d_ring; oa.ready = r->d_ready; oa.blen = r->d_blen;
     oa.queue = r->txs->d_state; oa.queue_syms = r->txs->queue_syms; oa.gap = tx->d_gap;
     oa.rec = r->d_offered; oa.nrec = r->d_noffered;
-    oa.pending = r->pending; oa.rl = 1 + r->kb; oa.psyms = tx->pre_bits / tx->bps; oa.fsyms = tx->code.bits_per_frame() / tx->bps;
+    oa.pending = r->pending; oa.rl = 1 + r->kb; oa.psyms = tx_pre_syms(tx); oa.fsyms = tx_frame_syms(tx);
     oa.now = r->calls;
     hipLaunchKernelGGL(rpt_offer_kernel, dim3((unsigned)r->ntx), dim3(64), 0, st, oa);
     PIRIP_HIPCHK(hipGetLastError());
@@ -253,12 +193,8 @@ int rpt_run(pirip_hip_rpt *r, const uint8_t *d_status, size_t status_stride, con
 // txs_process's own checks, made before anything is enqueued: a call either runs whole or not at all
 int rpt_check_out(const pirip_hip_rpt *r, const void *d_out, size_t out_stride_bytes)
 {
-    pirip_txs_info ti{};
-    if (!d_out || pirip_hip_txs_get_info(r->txs, &ti) != PIRIP_OK) return PIRIP_ERR_BAD_ARG;
-    const size_t bs = ti.out_format == PIRIP_IN_CF32 ? 8 : 2;
-    if (((uintptr_t)d_out | out_stride_bytes) & (bs - 1)) return PIRIP_ERR_BAD_ARG;
-    if (ti.noutputs > 1 && out_stride_bytes < (size_t)ti.block * bs) return PIRIP_ERR_BAD_ARG;
-    return PIRIP_OK;
+    if (!d_out) return PIRIP_ERR_BAD_ARG;
+    return iq_rows_check(d_out, out_stride_bytes, r->txs->mux->bs, r->txs->mux->noutputs, r->txs->block);
 }
 
 }  // namespace
@@ -278,7 +214,7 @@ int pirip_hip_rpt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs,
         if (route[c] >= ntx) return PIRIP_ERR_BAD_ARG;
         for (int q = 0; q < c; q++) if (route[c] >= 0 && route[q] == route[c]) return PIRIP_ERR_BAD_ARG;
     }
-    const int64_t psyms = tx->pre_bits / tx->bps, fsyms = tx->code.bits_per_frame() / tx->bps;
+    const int64_t psyms = tx_pre_syms(tx), fsyms = tx_frame_syms(tx);
     if (psyms + (int64_t)max_burst_frames * fsyms + tx->max_gap > txs->queue_syms) return PIRIP_ERR_BAD_ARG;
     int rx_rows = 0;
     if (rx) {
@@ -288,7 +224,7 @@ int pirip_hip_rpt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs,
         if (!ldpc || ns != nrx || dev != tx->device || ldpc->code.data_bytes() != kb) return PIRIP_ERR_BAD_ARG;
         const int64_t rows = pirip_hip_rx_max_frames(rx);
         if (rows < 1) return PIRIP_ERR_BAD_ARG;
-        if (rows > kMaxCalls) return PIRIP_ERR_UNSUPPORTED;
+        if (rows > kRepeatMaxCalls) return PIRIP_ERR_UNSUPPORTED;
         rx_rows = (int)rows;
     }
     // what section K's send path asks of rows of pending_records records
@@ -307,14 +243,7 @@ int pirip_hip_rpt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs,
     return PIRIP_OK;
 }
 
-int pirip_hip_rpt_destroy(pirip_hip_rpt *r)
-{
-    if (!r) return PIRIP_ERR_BAD_ARG;
-    (void)bind_device(r->device);
-    (void)hipDeviceSynchronize();
-    delete r;
-    return PIRIP_OK;
-}
+int pirip_hip_rpt_destroy(pirip_hip_rpt *r) { return destroy_handle(r, r ? r->device : 0); }
 
 int pirip_hip_rpt_get_info(const pirip_hip_rpt *r, pirip_rpt_info *info)
 {
@@ -328,7 +257,7 @@ int pirip_hip_rpt_push_records(pirip_hip_rpt *r, const uint8_t *d_status, size_t
 {
     if (!r || !d_status || !d_payload || ncalls < 0) return PIRIP_ERR_BAD_ARG;
     if (r->nrx > 1 && (status_stride < (size_t)ncalls || payload_stride < (size_t)ncalls * (size_t)r->kb)) return PIRIP_ERR_BAD_ARG;
-    if (ncalls > kMaxCalls) return PIRIP_ERR_UNSUPPORTED;
+    if (ncalls > kRepeatMaxCalls) return PIRIP_ERR_UNSUPPORTED;
     PIRIP_TRY(rpt_check_out(r, d_out, out_stride_bytes));
     if (!bind_device(r->device)) return PIRIP_ERR_NO_DEVICE;
     PIRIP_TRY(rpt_run(r, d_status, status_stride, d_payload, payload_stride, d_ncalls, ncalls, d_out, out_stride_bytes, (hipStream_t)hip_stream));
@@ -391,12 +320,10 @@ int pirip_hip_rpt_get_counters(pirip_hip_rpt *r, int64_t *bursts_in, int64_t *fr
                                int64_t *bursts_out, int64_t *pending, int64_t *dropped)
 {
     if (!r) return PIRIP_ERR_BAD_ARG;
-    if (!bind_device(r->device)) return PIRIP_ERR_NO_DEVICE;
     std::vector<RptRxCount> rc((size_t)r->nrx);
     std::vector<RptRing> rs((size_t)r->ntx);
-    PIRIP_HIPCHK(hipDeviceSynchronize());
-    PIRIP_HIPCHK(hipMemcpy(rc.data(), r->d_cnt, sizeof(RptRxCount) * rc.size(), hipMemcpyDeviceToHost));
-    PIRIP_HIPCHK(hipMemcpy(rs.data(), r->d_ring_state, sizeof(RptRing) * rs.size(), hipMemcpyDeviceToHost));
+    PIRIP_TRY(read_back(r->device, r->d_cnt, rc));
+    PIRIP_TRY(read_back(r->device, r->d_ring_state, rs));
     for (size_t c = 0; c < rc.size(); c++) {
         if (bursts_in) bursts_in[c] = rc[c].bursts;
         if (frames_in) frames_in[c] = rc[c].frames;

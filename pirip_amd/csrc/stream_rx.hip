@@ -180,17 +180,14 @@ int rx_alloc(pirip_hip_rx *rx)
 {
     const size_t ns = (size_t)rx->nstreams, raw_bytes = rx->raw_row_bytes * (size_t)rx->nraw;
     DevMem &m = rx->mem;
-    PIRIP_TRY(m.alloc(&rx->d_rows, rx->row_bytes * ns));
-    if (raw_bytes) PIRIP_TRY(m.alloc(&rx->d_raw, raw_bytes));
+    // (rows start zeroed: nothing reads bytes the caller or the decimator did not write, but a fresh buffer is not left to chance)
+    PIRIP_TRY(m.alloc_filled(&rx->d_rows, 0, rx->row_bytes * ns));
+    if (raw_bytes) PIRIP_TRY(m.alloc_filled(&rx->d_raw, 0, raw_bytes));
     PIRIP_TRY(m.alloc(&rx->d_consumed, sizeof(int64_t) * ns));
     PIRIP_TRY(m.alloc(&rx->d_total, sizeof(int64_t) * ns));
     PIRIP_TRY(m.alloc(&rx->d_carry, sizeof(int32_t) * ns));
     PIRIP_TRY(m.alloc(&rx->d_flag, sizeof(int32_t)));
-    PIRIP_TRY(m.alloc(&rx->d_seg, sizeof(SegDesc) * ns));
-    // (rows start zeroed: nothing reads bytes the caller or the decimator did not write, but a fresh buffer is not left to chance)
-    PIRIP_HIPCHK(hipMemset(rx->d_rows, 0, rx->row_bytes * ns));
-    if (rx->d_raw) PIRIP_HIPCHK(hipMemset(rx->d_raw, 0, raw_bytes));
-    PIRIP_HIPCHK(hipMemset(rx->d_seg, 0, sizeof(SegDesc) * ns));
+    PIRIP_TRY(m.alloc_filled(&rx->d_seg, 0, sizeof(SegDesc) * ns));
     PIRIP_TRY(rx_clear(rx, nullptr));
     PIRIP_HIPCHK(hipDeviceSynchronize());
     return PIRIP_OK;
@@ -278,14 +275,7 @@ int pirip_hip_rx_create_chan(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_h
     return rx_create_impl(dem, ldpc, nullptr, chan, block, out);
 }
 
-int pirip_hip_rx_destroy(pirip_hip_rx *rx)
-{
-    if (!rx) return PIRIP_ERR_BAD_ARG;
-    (void)demod_bind(rx->dem);
-    (void)hipDeviceSynchronize();
-    delete rx;
-    return PIRIP_OK;
-}
+int pirip_hip_rx_destroy(pirip_hip_rx *rx) { return destroy_handle(rx, rx ? rx->dem->device : 0); }
 
 int64_t pirip_hip_rx_max_frames(const pirip_hip_rx *rx) { return rx ? rx->budget : PIRIP_ERR_BAD_ARG; }
 

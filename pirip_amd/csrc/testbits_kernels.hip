@@ -25,6 +25,7 @@
 #include "fsk_ldpc.hpp"
 #include "fsk_plan.hpp"
 #include "hip_host.hpp"
+#include "rows_device.hpp"
 
 using namespace pirip;
 
@@ -49,20 +50,12 @@ struct PushArgs {
     uint32_t ntiles;
 };
 
-__device__ __forceinline__ int wave_sum(int v)
-{
-    for (int o = kLanes / 2; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
 __global__ __launch_bounds__(kLanes) void tbits_count_kernel(PushArgs a)
 {
     __shared__ uint32_t sw[kLdsWords];
     const uint32_t s = blockIdx.x / a.ntiles, tile = blockIdx.x - s * a.ntiles;
     const int lane = threadIdx.x;
-    uint32_t nf = a.max_frames;
-    if (a.nframes) { const int32_t v = a.nframes[s]; nf = v < 0 ? 0u : ((uint32_t)v > a.max_frames ? a.max_frames : (uint32_t)v); }
-    const uint32_t L = nf * a.row_bits;                        // < 2^31
+    const uint32_t L = (uint32_t)row_count(a.nframes, s, (int)a.max_frames) * a.row_bits;      // < 2^31
     const uint32_t my_tiles = L ? (L + kTile - 1) / kTile : 1;  // (a stream without rows still moves its history to the other row)
     if (tile >= my_tiles) return;
     const uint32_t T0 = tile * kTile;
@@ -149,8 +142,7 @@ __global__ __launch_bounds__(kLanes) void tbits_records_kernel(RecArgs a)
 {
     const size_t s = blockIdx.x;
     const int lane = threadIdx.x;
-    int nc = a.max_calls;
-    if (a.ncalls) { const int32_t v = a.ncalls[s]; nc = v < 0 ? 0 : (v > a.max_calls ? a.max_calls : v); }
+    const int nc = row_count(a.ncalls, s, a.max_calls);
     int frames = 0, errors = 0, bad = 0, crc = 0;
     for (int r = lane; r < nc; r += kLanes) {
         crc += (a.status[s * a.status_stride + (size_t)r] & PIRIP_RX_BITS) != 0;
@@ -222,10 +214,8 @@ int tbits_alloc(pirip_hip_tbits *t, const std::vector<uint32_t> &frame)
 // per-stream columns of a [nstreams][ncol] counter block into the host arrays that were asked for
 int tbits_read(pirip_hip_tbits *t, const u64 *d_cnt, int ncol, int64_t *const *cols)
 {
-    if (!bind_device(t->device)) return PIRIP_ERR_NO_DEVICE;
     std::vector<u64> c((size_t)t->nstreams * (size_t)ncol);
-    PIRIP_HIPCHK(hipDeviceSynchronize());
-    PIRIP_HIPCHK(hipMemcpy(c.data(), d_cnt, sizeof(u64) * c.size(), hipMemcpyDeviceToHost));
+    PIRIP_TRY(read_back(t->device, d_cnt, c));
     for (int k = 0; k < ncol; k++)
         if (cols[k]) for (int s = 0; s < t->nstreams; s++) cols[k][s] = (int64_t)c[(size_t)s * (size_t)ncol + (size_t)k];
     return PIRIP_OK;
@@ -265,14 +255,7 @@ int pirip_hip_tbits_create(int framesize, float valid_thresh, const uint8_t *fra
     return PIRIP_OK;
 }
 
-int pirip_hip_tbits_destroy(pirip_hip_tbits *t)
-{
-    if (!t) return PIRIP_ERR_BAD_ARG;
-    (void)bind_device(t->device);
-    (void)hipDeviceSynchronize();
-    delete t;
-    return PIRIP_OK;
-}
+int pirip_hip_tbits_destroy(pirip_hip_tbits *t) { return destroy_handle(t, t ? t->device : 0); }
 
 int pirip_hip_tbits_push(pirip_hip_tbits *t, const uint8_t *d_bits, size_t bits_stride, int row_bits, int packed, const int32_t *d_nframes,
                          int64_t max_frames, void *hip_stream)

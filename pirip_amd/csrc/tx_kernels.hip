@@ -37,6 +37,7 @@
 #include "iq_device.hpp"
 #include "noise_device.hpp"
 #include "rate_host.hpp"
+#include "repeat_device.hpp"
 #include "tx_handle.hpp"
 
 using namespace pirip;
@@ -58,12 +59,6 @@ struct FrameArgs {
     int k, m, kb, bpf, bps, pre_bits, nstreams, wave_lds, frame_lds;
 };
 
-__device__ __forceinline__ int rec_count(const FrameArgs &a, int s)
-{
-    int n = a.nrec ? a.nrec[s] : a.max_rec;
-    return n < 0 ? 0 : (n > a.max_rec ? a.max_rec : n);
-}
-
 // carrier off over symbols [from, from + n) of stream s, clipped to the row
 __device__ __forceinline__ void write_off(const FrameArgs &a, int s, int64_t from, int64_t n, int lane)
 {
@@ -79,7 +74,7 @@ __device__ __forceinline__ void write_off(const FrameArgs &a, int s, int64_t fro
 __global__ __launch_bounds__(64) void tx_layout_kernel(FrameArgs a)
 {
     const int s = blockIdx.x, lane = threadIdx.x;
-    const int nrec = rec_count(a, s);
+    const int nrec = row_count(a.nrec, s, a.max_rec);
     const int lead = a.lead[s] > 0 ? a.lead[s] : 0, gap = a.gap[s] > 0 ? a.gap[s] : 0;
     const int fsyms = a.bpf / a.bps, psyms = a.pre_bits / a.bps;
     write_off(a, s, 0, lead, lane);
@@ -88,10 +83,7 @@ __global__ __launch_bounds__(64) void tx_layout_kernel(FrameArgs a)
     for (int base = 0; base < nrec; base += 64) {
         const int r = base + lane;
         int len = 0;
-        if (r < nrec) {
-            const uint8_t ctl = rec[(size_t)r * (size_t)(1 + a.kb)];
-            len = ctl == 1 ? psyms + fsyms : ctl == 0 ? fsyms : ctl == 2 ? gap : 0;
-        }
+        if (r < nrec) len = tx_record_syms(rec[(size_t)r * (size_t)(1 + a.kb)], psyms, fsyms, gap);
         int64_t incl = len;
         for (int d = 1; d < 64; d <<= 1) {
             const int64_t up = __shfl_up(incl, d, 64);
@@ -133,7 +125,7 @@ __global__ __launch_bounds__(kFrameWaves * 64) void tx_frame_kernel(FrameArgs a)
     const int s = blockIdx.y, r = blockIdx.x * kFrameWaves + wave;
     uint8_t *s_frame = smem + (size_t)wave * a.wave_lds;    // [bpf] UW | data | parity, one bit per byte
     uint8_t *s_bytes = s_frame + a.frame_lds;               // [kb] the record's packed data
-    const bool live = r < rec_count(a, s);
+    const bool live = r < row_count(a.nrec, s, a.max_rec);
     const uint8_t *rec = a.rec + (size_t)s * a.rec_stride + (size_t)(live ? r : 0) * (size_t)(1 + a.kb);
     const uint8_t ctl = live ? rec[0] : 3;
     const bool frame = ctl == 0 || ctl == 1;
@@ -298,72 +290,19 @@ __global__ __launch_bounds__(kModThreads) void tx_mod_kernel(ModArgs a)
 // ---------------------------------------------------------------- receiver records -> Tx records (tx/frame_repeater.c:68-107)
 
 struct RepeatArgs {
-    const uint8_t *status; size_t status_stride; const uint8_t *payload; size_t payload_stride; const int32_t *ncalls_s; int ncalls;
+    RepeatIn in;
     uint8_t *rec; size_t rec_stride; int max_rec; int32_t *nrec;
-    int32_t *state;                        // [nstreams][2] receiving, frames buffered
-    uint8_t *held;                         // [nstreams][max_burst][kb] the frames of a burst that is still being received
-    int kb, max_burst, source;
 };
 
-// One wave per stream. Lane 0 walks the status bytes (staged in LDS) through the state machine and notes, per call, where its frame goes;
-// the wave then copies the payloads. A burst is written out only when SYNC drops: until then its frames wait in the handle.
+// One wave per stream: repeat_device.hpp's body, with the bursts where the walk laid them out in the stream's row of records.
 __global__ __launch_bounds__(64) void tx_repeat_kernel(RepeatArgs a)
 {
-    extern __shared__ __attribute__((aligned(16))) uint8_t smem[];
-    int32_t *s_act = (int32_t *)smem;                        // [ncalls] -1, or (burst << 16) | slot of the call's frame
-    int32_t *s_base = s_act + a.ncalls;                      // [ncalls + 1] first output record of a burst, -1: still open at the end
-    int32_t *s_n = s_base + a.ncalls + 1;                    // [ncalls + 1] frames of the burst
-    uint8_t *s_st = (uint8_t *)(s_n + a.ncalls + 1);         // [ncalls]
-    __shared__ int32_t s_hdr[4];                             // bursts, records out, receiving, frames held at the end
-    const int s = blockIdx.x, lane = threadIdx.x;
-    int nc = a.ncalls_s ? a.ncalls_s[s] : a.ncalls;
-    nc = nc < 0 ? 0 : (nc > a.ncalls ? a.ncalls : nc);
-    const uint8_t *st = a.status + (size_t)s * a.status_stride;
-    const uint8_t *pl = a.payload + (size_t)s * a.payload_stride;
-    uint8_t *held = a.held + (size_t)s * a.max_burst * a.kb;
+    const int s = blockIdx.x;
     uint8_t *out = a.rec + (size_t)s * a.rec_stride;
-    const int rl = 1 + a.kb;
-    const int held0 = a.state[2 * s + 1];
-    for (int c = lane; c < nc; c += 64) s_st[c] = st[c];
-    __syncthreads();
-    if (lane == 0) tx_repeat_walk([&](int c) { return (int)s_st[c]; }, nc, a.state[2 * s], held0, a.max_burst, s_act, s_base, s_n, s_hdr);
-    __syncthreads();
-    const int nb = s_hdr[0];
-    // frames that were held from earlier calls belong to burst 0: out they go if it ended here (else they stay where they are)
-    if (held0 > 0 && nb > 0)
-        for (int i = lane; i < held0 * a.kb; i += 64) {
-            const int j = i / a.kb, o = i - j * a.kb;
-            if (j < a.max_rec) {
-                out[(size_t)j * rl + 1 + o] = o == 0 ? (uint8_t)a.source : held[i];
-                if (o == 0) out[(size_t)j * rl] = j == 0 ? 1 : 0;
-            }
-        }
-    __syncthreads();
-    for (int i = lane; i < nc * a.kb; i += 64) {
-        const int c = i / a.kb, o = i - c * a.kb;
-        const int act = s_act[c];
-        if (act < 0) continue;
-        const int b = act >> 16, slot = act & 0xffff;
-        const uint8_t v = pl[(size_t)c * a.kb + o];
-        if (s_base[b] >= 0) {
-            const int j = s_base[b] + slot;
-            if (j < a.max_rec) {
-                out[(size_t)j * rl + 1 + o] = o == 0 ? (uint8_t)a.source : v;      // the repeater's own source address
-                if (o == 0) out[(size_t)j * rl] = slot == 0 ? 1 : 0;
-            }
-        } else {
-            held[(size_t)slot * a.kb + o] = v;
-        }
-    }
-    for (int i = lane; i < nb * rl; i += 64) {                                    // end of burst: control byte 2, zero data
-        const int b = i / rl, o = i - b * rl;
-        const int j = s_base[b] + s_n[b];
-        if (j < a.max_rec) out[(size_t)j * rl + o] = o == 0 ? 2 : 0;
-    }
-    if (lane == 0) {
-        a.state[2 * s] = s_hdr[2]; a.state[2 * s + 1] = s_hdr[3];
-        if (a.nrec) a.nrec[s] = s_hdr[1];
-    }
+    const int rl = 1 + a.in.kb;
+    const int nout = repeat_stream(a.in, s, [](uint8_t v, const uint8_t *) { return v; }, [](int, int32_t *, const int32_t *) {},
+                                   [&](int base, int j) { return base + j < a.max_rec ? out + (size_t)(base + j) * rl : nullptr; });
+    if (threadIdx.x == 0 && a.nrec) a.nrec[s] = nout;
 }
 
 }  // namespace
@@ -385,17 +324,12 @@ int tx_alloc(pirip_hip_tx *h)
     DevMem &m = h->mem;
     PIRIP_TRY(m.upload(&h->d_row_ptr, h->code.row_ptr.data(), sizeof(int32_t) * h->code.row_ptr.size()));
     PIRIP_TRY(m.upload(&h->d_col_idx, h->code.col_idx.data(), sizeof(int32_t) * h->code.col_idx.size()));
-    PIRIP_TRY(m.alloc(&h->d_lead, sizeof(int32_t) * S));
-    PIRIP_TRY(m.alloc(&h->d_gap, sizeof(int32_t) * S));
+    PIRIP_TRY(m.alloc_filled(&h->d_lead, 0, sizeof(int32_t) * S));
+    PIRIP_TRY(m.alloc_filled(&h->d_gap, 0, sizeof(int32_t) * S));
     PIRIP_TRY(m.alloc(&h->d_nsym, sizeof(int32_t) * S));
-    PIRIP_TRY(m.alloc(&h->d_fm, sizeof(uint32_t) * 4 * S));
-    PIRIP_TRY(m.alloc(&h->d_tm, sizeof(uint32_t) * 4 * S));
-    PIRIP_TRY(m.alloc(&h->d_phase, sizeof(uint32_t) * S));
-    PIRIP_HIPCHK(hipMemset(h->d_lead, 0, sizeof(int32_t) * S));
-    PIRIP_HIPCHK(hipMemset(h->d_gap, 0, sizeof(int32_t) * S));
-    PIRIP_HIPCHK(hipMemset(h->d_fm, 0, sizeof(uint32_t) * 4 * S));
-    PIRIP_HIPCHK(hipMemset(h->d_tm, 0, sizeof(uint32_t) * 4 * S));
-    PIRIP_HIPCHK(hipMemset(h->d_phase, 0, sizeof(uint32_t) * S));
+    PIRIP_TRY(m.alloc_filled(&h->d_fm, 0, sizeof(uint32_t) * 4 * S));
+    PIRIP_TRY(m.alloc_filled(&h->d_tm, 0, sizeof(uint32_t) * 4 * S));
+    PIRIP_TRY(m.alloc_filled(&h->d_phase, 0, sizeof(uint32_t) * S));
     PIRIP_HIPCHK(hipDeviceSynchronize());
     return PIRIP_OK;
 }
@@ -405,7 +339,7 @@ int tx_alloc(pirip_hip_tx *h)
 // symbols a row of max_rec records can need behind max_lead symbols of lead
 int64_t pirip::tx_row_syms(const pirip_hip_tx *h, int max_rec, int max_lead)
 {
-    const int64_t per_frame = (h->pre_bits + h->code.bits_per_frame()) / h->bps;
+    const int64_t per_frame = tx_pre_syms(h) + tx_frame_syms(h);
     return (int64_t)max_lead + (int64_t)max_rec * (per_frame > h->max_gap ? per_frame : (int64_t)h->max_gap);
 }
 
@@ -466,14 +400,7 @@ int pirip_hip_tx_create(const char *code_path, int Fs, int Rs, int M, int nstrea
     return PIRIP_OK;
 }
 
-int pirip_hip_tx_destroy(pirip_hip_tx *h)
-{
-    if (!h) return PIRIP_ERR_BAD_ARG;
-    (void)bind_device(h->device);
-    (void)hipDeviceSynchronize();
-    delete h;
-    return PIRIP_OK;
-}
+int pirip_hip_tx_destroy(pirip_hip_tx *h) { return destroy_handle(h, h ? h->device : 0); }
 
 int pirip_hip_tx_get_info(const pirip_hip_tx *h, pirip_tx_info *info)
 {
@@ -481,7 +408,7 @@ int pirip_hip_tx_get_info(const pirip_hip_tx *h, pirip_tx_info *info)
     std::memset(info, 0, sizeof(*info));
     info->Fs = h->Fs; info->Rs = h->Rs; info->M = h->M; info->Ts = h->Ts;
     info->n = h->code.n; info->k = h->code.k; info->bits_per_frame = h->code.bits_per_frame(); info->data_bytes = h->code.data_bytes();
-    info->preamble_syms = h->pre_bits / h->bps; info->frame_syms = h->code.bits_per_frame() / h->bps;
+    info->preamble_syms = tx_pre_syms(h); info->frame_syms = tx_frame_syms(h);
     info->nstreams = h->nstreams; info->device = h->device;
     return PIRIP_OK;
 }
@@ -557,10 +484,10 @@ int pirip_hip_tx_modulate(pirip_hip_tx *h, const uint8_t *d_syms, size_t sym_str
     if (!h || !d_syms || !d_out || nsym < 0) return PIRIP_ERR_BAD_ARG;
     if (out_format != PIRIP_IN_CU8_FSKDEMOD && out_format != PIRIP_IN_CF32) return PIRIP_ERR_UNSUPPORTED;
     const int bsamp = out_format == PIRIP_IN_CF32 ? 8 : 2, spu = 16 / bsamp;
-    if (((uintptr_t)d_out | out_stride_bytes) & (size_t)(bsamp - 1)) return PIRIP_ERR_BAD_ARG;
+    PIRIP_TRY(iq_rows_check(d_out, out_stride_bytes, bsamp, 1, 0));
     const int64_t nsamp = nsym * h->Ts;
     if (nsamp > 0x7fffffff) return PIRIP_ERR_UNSUPPORTED;
-    if (out_stride_bytes < (size_t)nsamp * bsamp && h->nstreams > 1) return PIRIP_ERR_BAD_ARG;
+    PIRIP_TRY(iq_rows_check(d_out, out_stride_bytes, bsamp, h->nstreams, nsamp));
     if (nsym == 0) return PIRIP_OK;
     if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     const int rc = tx_grow(h, &h->d_prefix, &h->prefix_cap, (size_t)h->nstreams * (size_t)nsym);
@@ -614,24 +541,21 @@ int pirip_hip_tx_repeat_records(pirip_hip_tx *h, const uint8_t *d_status, size_t
     const int kb = h->code.data_bytes();
     if (status_stride < (size_t)ncalls || payload_stride < (size_t)ncalls * kb || rec_stride < (size_t)max_rec * (size_t)(1 + kb)) return PIRIP_ERR_BAD_ARG;
     if (max_rec < pirip_hip_tx_repeat_max_records(h, ncalls)) return PIRIP_ERR_BAD_ARG;
-    if (ncalls > 4096) return PIRIP_ERR_UNSUPPORTED;         // the call table lives in LDS
+    if (ncalls > kRepeatMaxCalls) return PIRIP_ERR_UNSUPPORTED;
     if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
     if (!h->d_rep_state) {
         // first use: both buffers, the state zeroed, and only then the handle's pointers -- a failure leaves neither behind
         const size_t S = (size_t)h->nstreams;
         int32_t *state = nullptr; uint8_t *held = nullptr;
-        int rc = h->mem.alloc(&state, sizeof(int32_t) * 2 * S);
+        int rc = h->mem.alloc_filled(&state, 0, sizeof(int32_t) * 2 * S);
         if (rc == PIRIP_OK) rc = h->mem.alloc(&held, S * PIRIP_TX_REPEAT_MAX_FRAMES * (size_t)kb);
-        if (rc == PIRIP_OK && hipMemset(state, 0, sizeof(int32_t) * 2 * S) != hipSuccess) rc = PIRIP_ERR_HIP;
         if (rc != PIRIP_OK) { h->mem.release(&state); h->mem.release(&held); return rc; }
         h->d_rep_state = state; h->d_rep_held = held;
     }
     RepeatArgs a{};
-    a.status = d_status; a.status_stride = status_stride; a.payload = d_payload; a.payload_stride = payload_stride; a.ncalls_s = d_ncalls; a.ncalls = ncalls;
+    a.in = RepeatIn{d_status, status_stride, d_payload, payload_stride, d_ncalls, ncalls, h->d_rep_state, h->d_rep_held, kb, PIRIP_TX_REPEAT_MAX_FRAMES, source_byte};
     a.rec = d_records; a.rec_stride = rec_stride; a.max_rec = max_rec; a.nrec = d_nrec;
-    a.state = h->d_rep_state; a.held = h->d_rep_held; a.kb = kb; a.max_burst = PIRIP_TX_REPEAT_MAX_FRAMES; a.source = source_byte;
-    const size_t lds = sizeof(int32_t) * (3 * (size_t)ncalls + 2) + (size_t)ncalls + 16;
-    hipLaunchKernelGGL(tx_repeat_kernel, dim3((unsigned)h->nstreams), dim3(64), lds, (hipStream_t)hip_stream, a);
+    hipLaunchKernelGGL(tx_repeat_kernel, dim3((unsigned)h->nstreams), dim3(64), repeat_lds_bytes(ncalls), (hipStream_t)hip_stream, a);
     PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;
 }

@@ -30,6 +30,7 @@
 #include "hip_host.hpp"
 #include "iq_device.hpp"
 #include "mux_handle.hpp"
+#include "repeat_device.hpp"
 #include "tx_handle.hpp"
 #include "txs_handle.hpp"
 
@@ -60,21 +61,13 @@ __global__ __launch_bounds__(kAppendThreads) void txs_append_kernel(AppendArgs a
         const uint8_t *src = a.frm + (size_t)c * a.frm_stride;
         uint8_t *ring = a.ring + (size_t)c * (size_t)a.cap;
         const int64_t start = (int64_t)(tail % (uint64_t)a.cap);
-        for (int64_t j = tid; j < n; j += kAppendThreads) {
-            int64_t at = start + j;
-            if (at >= a.cap) at -= a.cap;
-            ring[at] = src[j];
-        }
+        for (int64_t j = tid; j < n; j += kAppendThreads) ring[ring_slot(start, j, a.cap)] = src[j];
     }
     __syncthreads();                                         // every thread has read the counters
     if (tid == 0) {
         if (fits) a.st[c].tail = tail + (uint64_t)n;
         else a.st[c].refused++;
-        if (a.taken) {
-            int nr = a.nrec ? a.nrec[c] : a.max_rec;
-            nr = nr < 0 ? 0 : (nr > a.max_rec ? a.max_rec : nr);
-            a.taken[c] = fits ? nr : 0;
-        }
+        if (a.taken) a.taken[c] = fits ? row_count(a.nrec, c, a.max_rec) : 0;
     }
 }
 
@@ -104,11 +97,7 @@ __global__ __launch_bounds__(kScanThreads) void txs_take_kernel(TakeArgs a)
     }
     const uint8_t *ring = a.ring + (size_t)c * (size_t)a.cap;
     const int64_t start = (int64_t)(head % (uint64_t)a.cap);
-    for (int j = tid; j < a.S; j += kScanThreads) {
-        int64_t at = start + j;
-        if (at >= a.cap) at -= a.cap;
-        sy[a.H + j] = j < n ? ring[at] : kOff;
-    }
+    for (int j = tid; j < a.S; j += kScanThreads) sy[a.H + j] = j < n ? ring[ring_slot(start, (int64_t)j, a.cap)] : kOff;
     __syncthreads();
     const uint8_t *cur = sy + a.H;
     const uint32_t carry = tx_scan_row([&](int64_t i) { const int v = cur[i]; return v < a.M ? v : -1; }, a.S, a.tm + (size_t)c * 4, (uint32_t)a.Fs,
@@ -178,14 +167,12 @@ int txs_alloc(pirip_hip_txs *t)
 {
     const size_t K = (size_t)t->nchan, rows = 2 * K * t->row;
     DevMem &m = t->mem;
-    PIRIP_TRY(m.alloc(&t->d_ring, K * (size_t)t->queue_syms));
+    PIRIP_TRY(m.alloc_filled(&t->d_ring, kOff, K * (size_t)t->queue_syms));
     PIRIP_TRY(m.alloc(&t->d_state, sizeof(ChanState) * K));
     PIRIP_TRY(m.alloc(&t->d_sy, rows));
     PIRIP_TRY(m.alloc(&t->d_pre, sizeof(uint32_t) * rows));
-    PIRIP_TRY(m.alloc(&t->d_no_lead, sizeof(int32_t) * K));
+    PIRIP_TRY(m.alloc_filled(&t->d_no_lead, 0, sizeof(int32_t) * K));
     PIRIP_TRY(m.alloc(&t->d_nsym, sizeof(int32_t) * K));
-    PIRIP_HIPCHK(hipMemset(t->d_ring, kOff, K * (size_t)t->queue_syms));
-    PIRIP_HIPCHK(hipMemset(t->d_no_lead, 0, sizeof(int32_t) * K));
     PIRIP_TRY(txs_clear(t, nullptr));
     PIRIP_HIPCHK(hipDeviceSynchronize());
     return PIRIP_OK;
@@ -234,14 +221,7 @@ int pirip_hip_txs_create(pirip_hip_tx *tx, pirip_hip_mux *mux, int64_t block, in
     return PIRIP_OK;
 }
 
-int pirip_hip_txs_destroy(pirip_hip_txs *t)
-{
-    if (!t) return PIRIP_ERR_BAD_ARG;
-    (void)bind_device(t->device);
-    (void)hipDeviceSynchronize();
-    delete t;
-    return PIRIP_OK;
-}
+int pirip_hip_txs_destroy(pirip_hip_txs *t) { return destroy_handle(t, t ? t->device : 0); }
 
 int pirip_hip_txs_get_info(const pirip_hip_txs *t, pirip_txs_info *info)
 {
@@ -273,8 +253,7 @@ int pirip_hip_txs_process(pirip_hip_txs *t, void *d_out, size_t out_stride_bytes
     if (!t || !d_out) return PIRIP_ERR_BAD_ARG;
     const pirip_hip_tx *tx = t->tx;
     const pirip_hip_mux *mx = t->mux;
-    if (((uintptr_t)d_out | out_stride_bytes) & (size_t)(mx->bs - 1)) return PIRIP_ERR_BAD_ARG;
-    if (mx->noutputs > 1 && out_stride_bytes < (size_t)t->block * mx->bs) return PIRIP_ERR_BAD_ARG;      // rows would overlap
+    PIRIP_TRY(iq_rows_check(d_out, out_stride_bytes, mx->bs, mx->noutputs, t->block));
     if (!bind_device(t->device)) return PIRIP_ERR_NO_DEVICE;
     hipStream_t st = (hipStream_t)hip_stream;
     const size_t half = (size_t)t->nchan * t->row, cur = (size_t)(t->calls & 1) * half, prev = half - cur;
@@ -301,10 +280,8 @@ int pirip_hip_txs_process(pirip_hip_txs *t, void *d_out, size_t out_stride_bytes
 int pirip_hip_txs_get_counters(pirip_hip_txs *t, int64_t *queued, int64_t *sent, int64_t *underrun, int64_t *refused)
 {
     if (!t) return PIRIP_ERR_BAD_ARG;
-    if (!bind_device(t->device)) return PIRIP_ERR_NO_DEVICE;
     std::vector<ChanState> cs((size_t)t->nchan);
-    PIRIP_HIPCHK(hipDeviceSynchronize());
-    PIRIP_HIPCHK(hipMemcpy(cs.data(), t->d_state, sizeof(ChanState) * cs.size(), hipMemcpyDeviceToHost));
+    PIRIP_TRY(read_back(t->device, t->d_state, cs));
     for (size_t c = 0; c < cs.size(); c++) {
         if (queued) queued[c] = (int64_t)(cs[c].tail - cs[c].head);
         if (sent) sent[c] = cs[c].sent;

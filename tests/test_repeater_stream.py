@@ -262,6 +262,71 @@ def test_4096_records_in_one_call(built_lib):
     assert torch.equal(iq, run.host_driven(offered))
 
 
+def test_the_intake_writes_the_records_of_the_record_conversion(built_lib, tmp_path):
+    """The two users of the one repeater body, held to each other on frame_repeater's own cases with 13-byte frames (bursts open across
+    calls, bursts of more than 100 frames, BITS without SYNC): every case is a receive channel routed to the transmit channel of its index,
+    cut into the same random pieces for HipTx.repeat_records and for HipRepeater.push_records. A pending ring holds every record of the
+    largest case and a queue every symbol of a channel, so a burst is offered in the call in which it ends and nothing is dropped."""
+    import torch
+    import pirip_amd
+    import txref
+    from test_tx_repeater import _call, _code_for, _cuts
+    kb, src, pieces, drain = 13, 0x31, 5, 2
+    cases = [c for c in txref.repeater_cases() if c["kb"] == kb]
+    B, total = len(cases), sum(c["out"].shape[0] for c in cases)
+    assert B > 80 and total > 2000
+    tx = pirip_amd.HipTx(_code_for(kb, tmp_path), MFS, RS, 2, nstreams=B, f1=1000, shift=RS, gap=rptref.GAP_SYMS)
+    assert tx.data_bytes == kb
+    rng = np.random.default_rng(1300)
+    cuts = [_cuts(rng, c["status"].size, pieces) for c in cases]
+    parts = [([c["status"][cuts[s][p][0]:cuts[s][p][1]] for s, c in enumerate(cases)],
+              [c["payload"][cuts[s][p][0]:cuts[s][p][1]] for s, c in enumerate(cases)]) for p in range(pieces)]
+    parts += [([c["status"][:0] for c in cases], [c["payload"][:0] for c in cases])] * drain
+    # path one: the record conversion, call by call
+    got = [_call(tx, kb, src, st, pl) for st, pl in parts[:pieces]]
+    one = [np.concatenate([g[s] for g in got]) for s in range(B)]
+    for s, c in enumerate(cases):
+        want = c["out"].copy()
+        want[want[:, 0] != 2, 1] = src                               # the fixture's records with this test's source byte
+        assert np.array_equal(one[s], want), c["name"]
+    # path two: the streaming repeater's intake, and what it offers call by call
+    ctl = [r[:, 0] for r in one]
+    syms = [int((x == 1).sum() * tx.preamble_syms + (x <= 1).sum() * tx.frame_syms + (x == 2).sum() * rptref.GAP_SYMS) for x in ctl]
+    P = max(max(r.shape[0] for r in one), 101)
+    mux = pirip_amd.HipMux(MFS, 1, [int(-19000 + 38000 * (c + 0.5) / B) for c in range(B)], gains=[0.5 / B] * B, kind=pirip_amd.MUX_LINEAR)
+    block = 2 * tx.Ts
+    txs = pirip_amd.HipTxStream(tx, mux, block, max(max(syms), rptref.burst_cost(100, tx.preamble_syms, tx.frame_syms, rptref.GAP_SYMS)))
+    rpt = pirip_amd.HipRepeater(tx, txs, list(range(B)), src, filter=None, holdoff=0, max_burst=100, pending=P)
+    rt = _hip()
+    rl = 1 + kb
+    p_rec, stride, p_n = rpt.offered()
+    assert stride == P * rl
+    out = torch.zeros(block * 2, dtype=torch.uint8, device="cuda")
+    off = torch.full((len(parts), B, P, rl), 0xEE, dtype=torch.uint8, device="cuda")
+    cnt = torch.full((len(parts), B), -7, dtype=torch.int32, device="cuda")
+    staged = []
+    for n, (st, pl) in enumerate(parts):
+        w = max(max(x.size for x in st), 1)
+        hst, hpl = np.full((B, w), 6, np.uint8), np.full((B, w, kb), 0x5A, np.uint8)
+        for s in range(B):
+            hst[s, :st[s].size], hpl[s, :st[s].size] = st[s], pl[s]
+        staged.append([torch.from_numpy(x).cuda() for x in (hst, hpl, np.array([x.size for x in st], np.int32))])
+        rpt.push_records(staged[n][0], staged[n][1], out, block * 2, ncalls=staged[n][2])
+        _d2d(rt, off[n].data_ptr(), p_rec, B * stride)
+        _d2d(rt, cnt[n].data_ptr(), p_n, B * 4)
+    torch.cuda.synchronize()
+    off, cnt = off.cpu().numpy(), cnt.cpu().numpy()
+    compared = 0
+    for t in range(B):
+        two = np.concatenate([off[n, t, :cnt[n, t]] for n in range(len(parts))])
+        assert two.shape == one[t].shape and np.array_equal(two, one[t]), cases[t]["name"]
+        compared += two.shape[0]
+    assert compared == total
+    c = rpt.counters()
+    assert not c["dropped"].any() and not c["unrouted"].any() and not c["pending"].any() and not c["filtered"].any()
+    assert c["frames_in"].sum() == sum(int((x <= 1).sum()) for x in ctl) and not txs.counters()["refused"].any()
+
+
 # ---------------------------------------------------------------- the closed loop (tests/muxshapes.py's LOOP)
 
 ROUTE = [1, 0, 3, 2]
