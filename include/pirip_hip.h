@@ -772,6 +772,104 @@ int pirip_hip_rpt_reset(pirip_hip_rpt *rpt, void *hip_stream);
  * state advanced when a call is enqueued. */
 
 /* ----------------------------------------------------------------------------------- */
+/* section N : ping terminal (test bursts out, a per-frame link log in, block by block)  */
+/*   The other end of section M's link: the reference's script/ping, which sends a burst   */
+/*   of test frames every few seconds (`rpitx_fsk --testframes 3 --source 0x1 --seq`) and   */
+/*   logs what comes back with `rtl_fsk --code NAME -L --filter 0x1`                        */
+/*   (the reference's script/ping:47 and README.md:57-89), for a batch of                  */
+/*   channels. Composes a streaming receiver (section G, optional) and a transmitter with    */
+/*   its streaming transmitter (sections I and K, optional): received records go through     */
+/*   rtl_fsk's --filter into a log ring per receive channel, and bursts of test frames go     */
+/*   into section K's queue on a schedule counted in calls. No call          */
+/*   synchronises or allocates; every call enqueues the same launches.                        */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_ping pirip_hip_ping;
+typedef struct pirip_ping_config {
+    int nrx;                    /* receive channels (== rx's channels when rx is given) */
+    int source_byte;            /* 0..255: byte 0 of every frame sent */
+    int filter_byte;            /* -1, or 0..255 = rtl_fsk --filter: such a frame loses PIRIP_RX_BITS before it is logged */
+    int frames_per_burst;       /* 1..PIRIP_TX_REPEAT_MAX_FRAMES */
+    int seq;                    /* 1: byte 1 of frame f of a burst = (f + 1) & 0xff (rpitx_fsk --seq) */
+    int period_calls;           /* >= 1 */
+    const int32_t *first_call;  /* [tx channels] host, NULL = zeros; each >= 0 */
+    int64_t max_bursts;         /* per channel; 0 = no limit (script/ping start N) */
+    int log_entries;            /* >= 1: entries of each receive channel's log ring */
+    int nin0;                   /* samples the first demodulator call consumes (info.N); taken from rx when rx is given */
+} pirip_ping_config;
+typedef struct pirip_ping_entry {           /* 40 bytes */
+    int64_t t_samples;                      /* the channel's modem-rate sample clock after the call that delivered the frame */
+    int32_t call, row;                      /* n, f */
+    float S, N, SNRest;                     /* stats row [8], [9], [5], bit for bit */
+    int32_t ecdd;                           /* popcount(payload ^ test payload) over bytes 2 .. data_bytes - 3 (section L's rule) */
+    int32_t eraw;                           /* info[8] */
+    uint8_t source, seq, status, iters;     /* payload[0], payload[1], status as received, min(info[4], 255) */
+} pirip_ping_entry;
+typedef struct pirip_ping_info {
+    int nrx, nchan, source_byte, filter_byte, frames_per_burst, seq, period_calls, log_entries, nin0, has_rx, rx_rows, data_bytes, device;
+    int64_t max_bursts;
+} pirip_ping_info;
+/* All handles are borrowed, must be on one device and must outlive the terminal. rx: NULL (records come from the caller:
+ * pirip_hip_ping_push_records) or a streaming receiver created with an ldpc, of cfg->nrx channels, whose pirip_hip_rx_max_frames is at most
+ * 4096 (PIRIP_ERR_UNSUPPORTED above); with tx also of tx's data_bytes. tx and txs: both NULL -- the handle is a logger only, nchan = 0 and
+ * every call's d_out must be NULL -- or a transmitter and the streaming transmitter created on it; one without the other is
+ * PIRIP_ERR_BAD_ARG, and so are rx, tx and txs all NULL (nothing would tell the frame's size). Also PIRIP_ERR_BAD_ARG: cfg or out NULL,
+ * nrx < 1 or not rx's channels, source_byte outside 0 .. 255, filter_byte outside -1 .. 255, frames_per_burst outside 1 ..
+ * PIRIP_TX_REPEAT_MAX_FRAMES, period_calls < 1, a negative first_call entry, max_bursts < 0, log_entries < 1, nin0 < 0 without rx, handles
+ * on different devices, a frame of fewer than 4 data bytes, and a txs whose queue_syms does not hold one burst: preamble_syms +
+ * frames_per_burst * frame_syms + tx's largest gap. The burst's frames_per_burst + 1 records -- those of fsk_ldpc_framer --testframes
+ * frames_per_burst --bursts 1 --source source_byte [--seq] -- are made here, once, on the host. Every work row is sized here with tx's gaps
+ * as they are, the framer's rows in txs included: set the gaps first. Create synchronises the device. */
+int pirip_hip_ping_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, const pirip_ping_config *cfg, pirip_hip_ping **out);
+int pirip_hip_ping_destroy(pirip_hip_ping *ping);
+int pirip_hip_ping_get_info(const pirip_hip_ping *ping, pirip_ping_info *info);
+/* Call n (n = 0, 1, ... since create / reset), in stream order:
+ * 1. log, per receive channel c over its nf = d_ncalls[c] (NULL = ncalls; clamped to [0, ncalls]) rows -- status bytes at d_status +
+ *    c * status_stride, payloads of data_bytes bytes at d_payload + c * payload_stride, info rows of PIRIP_LDPC_INFO_PER_CALL int32 at
+ *    d_info + c * info_stride, stats rows of PIRIP_STATS_PER_FRAME floats at d_stats + c * stats_stride (strides in elements), as
+ *    pirip_hip_fsk_ldpc_rx_batch / pirip_hip_rx_process write them; they are only read. The channel carries a sample clock {samples = 0,
+ *    next_nin = nin0}; for rows f = 0 .. nf - 1 in order: samples += next_nin; next_nin = (int)stats[f][6] (rtl_fsk -L's clock). A row with
+ *    PIRIP_RX_BITS whose payload byte 0 is filter_byte loses BITS (filtered); a row that still has BITS gets one pirip_ping_entry with
+ *    t_samples = samples, appended in row order to the channel's ring at written % log_entries: the ring overwrites its oldest entry.
+ * 2. schedule, per transmit channel t: a burst is due iff n >= first_call[t], (n - first_call[t]) % period_calls == 0 and fewer than
+ *    max_bursts bursts were sent (max_bursts 0: no limit). It costs preamble_syms + frames_per_burst * frame_syms + tx's gap of channel t
+ *    now. If that fits txs's free space (queue_syms - queued) the burst's records are offered and go through pirip_hip_txs_send's path,
+ *    which by construction never refuses; otherwise nothing is offered, skipped goes up and the burst is not tried again before its next
+ *    due call.
+ * 3. pirip_hip_txs_process into d_out (its rules for d_out / out_stride_bytes).
+ * A logger-only handle runs step 1 alone and wants d_out == NULL (else PIRIP_ERR_BAD_ARG); a handle with tx wants d_out. d_status,
+ * d_payload, d_info and d_stats are all required (PIRIP_ERR_BAD_ARG), as are strides that hold ncalls rows when nrx > 1. ncalls <= 4096
+ * (PIRIP_ERR_UNSUPPORTED above), ncalls < 0 is PIRIP_ERR_BAD_ARG. Works with and without rx (with rx it changes nothing of the receiver).
+ * Enqueued on hip_stream (NULL = default stream); never synchronises. */
+int pirip_hip_ping_push_records(pirip_hip_ping *ping, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                                const int32_t *d_info, size_t info_stride, const float *d_stats, size_t stats_stride, const int32_t *d_ncalls,
+                                int ncalls, void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* Need rx (PIRIP_ERR_BAD_ARG without): pirip_hip_rx_process on the block at pirip_hip_rx_input (push: after copying it from d_in as
+ * pirip_hip_rx_push does; d_in == NULL is PIRIP_ERR_BAD_ARG) into the handle's own status, payload, info, stats and nframes rows, then the
+ * steps above over them. */
+int pirip_hip_ping_process(pirip_hip_ping *ping, void *d_out, size_t out_stride_bytes, void *hip_stream);
+int pirip_hip_ping_push(pirip_hip_ping *ping, const void *d_in, size_t in_stride_bytes, void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* The rows the last call read, as received: after process / push the handle's own -- rx_rows rows per channel, strides in elements,
+ * d_nframes [nrx] --, after push_records the caller's. Valid in stream order; each pointer may be NULL. PIRIP_ERR_BAD_ARG before the
+ * first call. */
+int pirip_hip_ping_records(pirip_hip_ping *ping, const uint8_t **d_status, size_t *status_stride, const uint8_t **d_payload, size_t *payload_stride,
+                           const int32_t **d_info, size_t *info_stride, const float **d_stats, size_t *stats_stride, const int32_t **d_nframes);
+/* The records offered to the streaming transmitter in the last call: channel t's d_nrec[t] (0 or frames_per_burst + 1) records at
+ * d_records + t * rec_stride. PIRIP_ERR_BAD_ARG on a logger-only handle. */
+int pirip_hip_ping_offered(pirip_hip_ping *ping, const uint8_t **d_records, size_t *rec_stride, const int32_t **d_nrec);
+/* Host copies (synchronises the device), each may be NULL. Per receive channel [nrx]: frames logged, frames the filter removed, rows with a
+ * decoded frame (info[6] >= 0), decoded rows without PIRIP_RX_BITS as received, the sum of the logged entries' ecdd, entries the ring
+ * overwrote. Per transmit channel [nchan]: bursts sent, frames sent, due bursts skipped for want of queue space. */
+int pirip_hip_ping_get_counters(pirip_hip_ping *ping, int64_t *frames, int64_t *filtered, int64_t *decoded, int64_t *crc_fail, int64_t *bit_errors,
+                                int64_t *lost, int64_t *bursts_sent, int64_t *frames_sent, int64_t *skipped);
+/* Host copy (synchronises the device) of the newest min(frames logged, log_entries, max) entries of receive channel chan, oldest first;
+ * *written (may be NULL): how many. PIRIP_ERR_BAD_ARG for chan outside [0, nrx), max < 0 or entries == NULL with max > 0. */
+int pirip_hip_ping_get_log(pirip_hip_ping *ping, int chan, pirip_ping_entry *entries, int max, int *written);
+/* Clears the sample clocks, the rings and the counters and resets txs, and rx where present: the next call is n = 0. */
+int pirip_hip_ping_reset(pirip_hip_ping *ping, void *hip_stream);
+/* One HIP stream per handle: clocks, rings and counters are device state advanced in stream order, the call index is host state advanced
+ * when a call is enqueued. */
+
+/* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */
 /*             names and signatures as codec2 src/fsk.h [UPSTREAM-RECALLED]              */
 /* ----------------------------------------------------------------------------------- */

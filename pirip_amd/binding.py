@@ -59,6 +59,26 @@ class RptInfo(C.Structure):
                                        "has_rx", "rx_rows", "device")]
 
 
+class PingConfig(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nrx", "source_byte", "filter_byte", "frames_per_burst", "seq", "period_calls")] + \
+               [("first_call", C.POINTER(C.c_int32)), ("max_bursts", C.c_int64), ("log_entries", C.c_int), ("nin0", C.c_int)]
+
+
+class PingEntry(C.Structure):
+    _fields_ = [("t_samples", C.c_int64), ("call", C.c_int32), ("row", C.c_int32), ("S", C.c_float), ("N", C.c_float), ("SNRest", C.c_float),
+                ("ecdd", C.c_int32), ("eraw", C.c_int32), ("source", C.c_uint8), ("seq", C.c_uint8), ("status", C.c_uint8), ("iters", C.c_uint8)]
+
+
+# pirip_ping_entry as a numpy structured dtype (40 bytes, the C layout): what HipPing.log returns
+PING_ENTRY_DTYPE = [("t_samples", "<i8"), ("call", "<i4"), ("row", "<i4"), ("S", "<f4"), ("N", "<f4"), ("SNRest", "<f4"), ("ecdd", "<i4"),
+                    ("eraw", "<i4"), ("source", "u1"), ("seq", "u1"), ("status", "u1"), ("iters", "u1")]
+
+
+class PingInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nrx", "nchan", "source_byte", "filter_byte", "frames_per_burst", "seq", "period_calls", "log_entries",
+                                       "nin0", "has_rx", "rx_rows", "data_bytes", "device")] + [("max_bursts", C.c_int64)]
+
+
 class LdpcInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "k", "bits_per_frame", "data_bytes", "nbits_per_call", "max_iter", "nstreams")] + \
                [("name", C.c_char * 64)]
@@ -202,6 +222,17 @@ def lib():
     L.pirip_hip_rpt_offered.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
     L.pirip_hip_rpt_get_counters.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
     L.pirip_hip_rpt_reset.argtypes = [vp, vp]
+    L.pirip_hip_ping_create.argtypes = [vp, vp, vp, C.POINTER(PingConfig), C.POINTER(vp)]
+    L.pirip_hip_ping_destroy.argtypes = [vp]
+    L.pirip_hip_ping_get_info.argtypes = [vp, C.POINTER(PingInfo)]
+    L.pirip_hip_ping_push_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, i32, vp, sz, vp]
+    L.pirip_hip_ping_process.argtypes = [vp, vp, sz, vp]
+    L.pirip_hip_ping_push.argtypes = [vp, vp, sz, vp, sz, vp]
+    L.pirip_hip_ping_records.argtypes = [vp] + [C.POINTER(vp), C.POINTER(sz)] * 4 + [C.POINTER(vp)]
+    L.pirip_hip_ping_offered.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
+    L.pirip_hip_ping_get_counters.argtypes = [vp] + [vp] * 9
+    L.pirip_hip_ping_get_log.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
+    L.pirip_hip_ping_reset.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -843,6 +874,112 @@ class HipRepeater:
 
     def reset(self, stream=None):
         _chk(self.L.pirip_hip_rpt_reset(self.h, _hip_stream(stream)), "pirip_hip_rpt_reset")
+
+
+class HipPing:
+    """Ping terminal (include/pirip_hip.h section N): per call the received FSK_LDPC records -- the caller's, or with a HipRx `rx` created
+    with an ldpc those of the wideband block -- go through the filter into a log ring per receive channel, and on a schedule counted in
+    calls a burst of `frames` test frames (source in byte 0, with seq the frame's number in byte 1) goes out through HipTxStream `txs`
+    (created on HipTx `tx`). Without tx / txs the handle is a logger only and every call's out is None. first_call: the first due call
+    per transmit channel (None: 0); period: calls between bursts; max_bursts: per channel, 0 = no limit; log_entries: entries of each
+    ring; nin0: what the first demodulator call consumes (taken from rx where given). The handles must outlive the terminal; pointer
+    arguments take torch tensors or raw device pointers, streams default to torch's current stream."""
+
+    RX_COUNTERS = ("frames", "filtered", "decoded", "crc_fail", "bit_errors", "lost")
+    TX_COUNTERS = ("bursts_sent", "frames_sent", "skipped")
+
+    def __init__(self, rx=None, tx=None, txs=None, nrx=None, source=1, filter=None, frames=3, seq=False, period=1, first_call=None, max_bursts=0,
+                 log_entries=256, nin0=0):
+        import numpy as np
+        self.L = lib()
+        self.rx, self.tx, self.txs = rx, tx, txs
+        if nrx is None:
+            nrx = rx.nstreams if rx is not None else 0
+        fc = None if first_call is None else np.ascontiguousarray(first_call, dtype=np.int32).reshape(-1)
+        if fc is not None and tx is not None and fc.size != tx.nstreams:
+            raise ValueError("first_call: one entry per transmit channel")
+        cfg = PingConfig(int(nrx), int(source), -1 if filter is None else int(filter), int(frames), 1 if seq else 0, int(period),
+                         None if fc is None else fc.ctypes.data_as(C.POINTER(C.c_int32)), int(max_bursts), int(log_entries), int(nin0))
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_ping_create(rx.h if rx is not None else None, tx.h if tx is not None else None,
+                                          txs.h if txs is not None else None, C.byref(cfg), C.byref(h)), "pirip_hip_ping_create")
+        self.h = h
+        self.info = PingInfo()
+        _chk(self.L.pirip_hip_ping_get_info(self.h, C.byref(self.info)), "pirip_hip_ping_get_info")
+        i = self.info
+        self.nrx, self.nchan, self.rx_rows, self.data_bytes, self.log_entries, self.nin0 = i.nrx, i.nchan, i.rx_rows, i.data_bytes, i.log_entries, i.nin0
+        self.frames = i.frames_per_burst
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_ping_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def push_records(self, status, payload, info, stats, out=None, out_stride=0, ncalls=None, max_calls=None, status_stride=None,
+                     payload_stride=None, info_stride=None, stats_stride=None, stream=None):
+        """status uint8 [nrx, max_calls], payload uint8 [nrx, max_calls, data_bytes], info int32 [nrx, max_calls, 10], stats float32 [nrx,
+        max_calls, 10] (tensors, per-channel rows contiguous; or raw pointers with max_calls and the strides in elements), ncalls int32
+        [nrx] or None -> the log, and with tx one block per output at out + i * out_stride."""
+        if hasattr(status, "shape"):
+            max_calls = int(status.shape[1]) if max_calls is None else int(max_calls)
+            status_stride = int(status.stride(0)) if status_stride is None else int(status_stride)
+            payload_stride = int(payload.stride(0)) if payload_stride is None else int(payload_stride)
+            info_stride = int(info.stride(0)) if info_stride is None else int(info_stride)
+            stats_stride = int(stats.stride(0)) if stats_stride is None else int(stats_stride)
+        elif None in (max_calls, status_stride, payload_stride, info_stride, stats_stride):
+            raise ValueError("raw pointers need max_calls and the four strides")
+        _chk(self.L.pirip_hip_ping_push_records(self.h, _dev(status), status_stride, _dev(payload), payload_stride, _dev(info), info_stride,
+                                                _dev(stats), stats_stride, _dev(ncalls), int(max_calls), _dev(out), int(out_stride),
+                                                _hip_stream(stream)), "pirip_hip_ping_push_records")
+
+    def process(self, out=None, out_stride=0, stream=None):
+        """the block at rx.input() -> the log, and with tx one block per output (needs rx)"""
+        _chk(self.L.pirip_hip_ping_process(self.h, _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_ping_process")
+
+    def push(self, d_in, in_stride, out=None, out_stride=0, stream=None):
+        """process() after copying the block from d_in (rows in_stride bytes apart) into rx's input"""
+        _chk(self.L.pirip_hip_ping_push(self.h, _dev(d_in), int(in_stride), _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_ping_push")
+
+    def records(self):
+        """dict of the last call's rows: device pointers status, payload, info, stats, nframes and the strides in elements"""
+        p = [C.c_void_p() for _ in range(5)]
+        st = [C.c_size_t(0) for _ in range(4)]
+        _chk(self.L.pirip_hip_ping_records(self.h, C.byref(p[0]), C.byref(st[0]), C.byref(p[1]), C.byref(st[1]), C.byref(p[2]), C.byref(st[2]),
+                                           C.byref(p[3]), C.byref(st[3]), C.byref(p[4])), "pirip_hip_ping_records")
+        return dict(status=int(p[0].value or 0), status_stride=int(st[0].value), payload=int(p[1].value or 0), payload_stride=int(st[1].value),
+                    info=int(p[2].value or 0), info_stride=int(st[2].value), stats=int(p[3].value or 0), stats_stride=int(st[3].value),
+                    nframes=int(p[4].value or 0))
+
+    def offered(self):
+        """(device pointer of the records offered in the last call, bytes per channel row, device pointer of the int32 [nchan] counts)"""
+        p, n, st = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        _chk(self.L.pirip_hip_ping_offered(self.h, C.byref(p), C.byref(st), C.byref(n)), "pirip_hip_ping_offered")
+        return int(p.value), int(st.value), int(n.value)
+
+    def counters(self):
+        """dict of int64 arrays -- [nrx]: frames, filtered, decoded, crc_fail, bit_errors, lost; [nchan]: bursts_sent, frames_sent, skipped.
+        Synchronises."""
+        import numpy as np
+        out = {k: np.zeros(self.nrx, dtype=np.int64) for k in self.RX_COUNTERS}
+        out.update({k: np.zeros(self.nchan, dtype=np.int64) for k in self.TX_COUNTERS})
+        _chk(self.L.pirip_hip_ping_get_counters(self.h, *(out[k].ctypes.data for k in self.RX_COUNTERS + self.TX_COUNTERS)),
+             "pirip_hip_ping_get_counters")
+        return out
+
+    def log(self, chan, max_entries=None):
+        """the newest entries of receive channel chan, oldest first: numpy structured array of PING_ENTRY_DTYPE. Synchronises."""
+        import numpy as np
+        n = self.log_entries if max_entries is None else int(max_entries)
+        out = np.zeros(max(n, 1), dtype=np.dtype(PING_ENTRY_DTYPE))
+        assert out.dtype.itemsize == C.sizeof(PingEntry) == 40
+        got = C.c_int(0)
+        _chk(self.L.pirip_hip_ping_get_log(self.h, int(chan), out.ctypes.data, n, C.byref(got)), "pirip_hip_ping_get_log")
+        return out[:got.value].copy()
+
+    def reset(self, stream=None):
+        _chk(self.L.pirip_hip_ping_reset(self.h, _hip_stream(stream)), "pirip_hip_ping_reset")
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

@@ -30,4 +30,22 @@ __device__ __forceinline__ int wave_sum(int v)
     return v;
 }
 
+// the inclusive prefix sum over the wave's 64 lanes: lane i gets v[0] + ... + v[i] (six shuffle-and-add steps)
+template <typename T>
+__device__ __forceinline__ T wave_scan(T v)
+{
+    const int lane = threadIdx.x & 63;
+    for (int d = 1; d < 64; d <<= 1) {
+        const T up = __shfl_up(v, d, 64);
+        if (lane >= d) v += up;
+    }
+    return v;
+}
+
+// lanes below this one whose bit is set in a 64-lane ballot: the lane's place in a compaction
+__device__ __forceinline__ int wave_rank(unsigned long long mask)
+{
+    return (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(mask >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)mask, 0u));
+}
+
 }  // namespace pirip

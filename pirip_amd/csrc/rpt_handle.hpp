@@ -22,6 +22,8 @@ struct RptRxCount {
 
 // (stream_rx.hip) channels, the FSK_LDPC receiver (NULL: none) and the device of a streaming receiver
 void rx_handle_shape(const pirip_hip_rx *rx, int *nstreams, const pirip_hip_ldpc **ldpc, int *device);
+// (stream_rx.hip) modem-rate samples the first demodulator call of a streaming receiver consumes: its demodulator's N
+int rx_handle_nin0(const pirip_hip_rx *rx);
 
 }  // namespace pirip
 

@@ -262,6 +262,9 @@ void pirip::rx_handle_shape(const pirip_hip_rx *rx, int *nstreams, const pirip_h
     *nstreams = rx->nstreams; *ldpc = rx->ldpc; *device = rx->dem->device;
 }
 
+// ... and the ping terminal (ping_kernels.hip): what the first demodulator call consumes
+int pirip::rx_handle_nin0(const pirip_hip_rx *rx) { return rx->dem->plan.d.N; }
+
 extern "C" {
 
 int pirip_hip_rx_create(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *dec, int64_t block, pirip_hip_rx **out)

@@ -3,7 +3,7 @@
 //
 //   rtl_fsk_channels -s rtlFs -a modemFs -r Rs [-m M] [--mask S] [--fsk_lower Hz] [--fsk_upper Hz] [--code NAME|FILE]
 //                    -c OFF1,OFF2,... [-i FILE|-] -o PREFIX [-q]
-//                    [--put-test-bits [-p packetsPass] [-b berPass] [-t validBER] [-f frameBits]] [--testframes]
+//                    [--put-test-bits [-p packetsPass] [-b berPass] [-t validBER] [-f frameBits]] [--testframes] [-L]
 //
 // Channel k is centred at OFFk Hz from the capture's centre (integer, -rtlFs/2 < OFFk < rtlFs/2) and is what
 // `csdr shift_addition_cc (-OFFk/rtlFs) | fir_decimate_cc (rtlFs/modemFs)` would hand `rtl_fsk -a modemFs`: the same modem settings as
@@ -17,6 +17,10 @@
 // are. At the end one line per channel on stderr, the channel number in front of fsk_put_test_bits' final line (--testframes: decoded
 // frames for packets, payload bits compared, payload bit errors); exit 0 only if every channel meets that tool's PASS rule
 // (packets >= packetsPass && bits > 0 && BER <= berPass), else 1.
+// -L (with --code) is rtl_fsk -L for every channel: after every block one line on stderr per frame whose CRC16 matches,
+//   <k>: Rx frame src: 0x%02x seq: %3d S: %e N: %e SNR: %5.2f dB t_rx: %.4f s
+// -- rtl_fsk's columns without the wall clock --, from a logger-only ping terminal (section N) chained behind the receiver on the device.
+// (The usage text on stderr is pinned by tests/test_tools_cli_cpu.py and does not list -L.)
 #include <getopt.h>
 
 #include <cstdio>
@@ -43,7 +47,7 @@ int main(int argc, char **argv)
     if (!abi_ok(argv[0])) return 2;
     long rtlFs = 0, modemFs = 0, Rs = 0;
     int M = 2, mask = 0, quiet = 0, fsk_lower = 0, fsk_upper = 0, user_lower = 0, user_upper = 0;
-    int put_bits = 0, testframes = 0, framesize = 100, packet_pass = 0;
+    int put_bits = 0, testframes = 0, framesize = 100, packet_pass = 0, log_frames = 0;
     float valid_thresh = 0.1f, ber_pass = 0.0f;
     std::string in_name = "-", prefix, code;
     std::vector<int32_t> offsets;
@@ -52,7 +56,7 @@ int main(int argc, char **argv)
                                     {"put-test-bits", no_argument, 0, 1004}, {"testframes", no_argument, 0, 1005},
                                     {"help", no_argument, 0, 'h'}, {0, 0, 0, 0}};
     int o, oi;
-    while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:qhp:b:t:f:", lopts, &oi)) != -1) {
+    while ((o = getopt_long(argc, argv, "s:a:r:m:c:i:o:qhp:b:t:f:L", lopts, &oi)) != -1) {
         switch (o) {
         case 's': rtlFs = (long)atof(optarg); break;
         case 'a': modemFs = (long)atof(optarg); break;
@@ -62,6 +66,7 @@ int main(int argc, char **argv)
         case 'i': in_name = optarg; break;
         case 'o': prefix = optarg; break;
         case 'q': quiet = 1; break;
+        case 'L': log_frames = 1; break;
         case 1000: code = optarg; break;
         case 1001: mask = atoi(optarg); break;
         case 1002: fsk_lower = atoi(optarg); user_lower = 1; break;
@@ -80,6 +85,7 @@ int main(int argc, char **argv)
     if (modemFs % Rs) { fprintf(stderr, "rtl_fsk_channels: modem rate must be a multiple of the symbol rate\n"); return 1; }
     if (put_bits && !code.empty()) { fprintf(stderr, "rtl_fsk_channels: --put-test-bits counts uncoded bits; with --code use --testframes\n"); return 1; }
     if (testframes && code.empty()) { fprintf(stderr, "rtl_fsk_channels: --testframes needs --code\n"); return 1; }
+    if (log_frames && code.empty()) { fprintf(stderr, "rtl_fsk_channels: -L needs --code\n"); return 1; }
     const int D = (int)(rtlFs / modemFs), Fs = (int)modemFs, K = (int)offsets.size();
     std::string code_path;
     if (!code.empty() && (code_path = resolve_code(code, argv[0])).empty()) {
@@ -101,6 +107,7 @@ int main(int argc, char **argv)
     LdpcHandle ldpc;
     RxHandle rx;
     TbitsHandle tb;
+    PingHandle logger;
     PIRIPOK(pirip_hip_chan_create((int)rtlFs, D, 0.05f, 0, 1, K, inputs.data(), offsets.data(), -1, chan.out()), "channelizer");
     // rtl_fsk's modem settings, under its default rules
     const pirip_fsk_params prm = rtl_fsk_params(Fs, (int)Rs, M, mask, user_lower ? &fsk_lower : nullptr, user_upper ? &fsk_upper : nullptr, PIRIP_IN_CF32);
@@ -117,6 +124,11 @@ int main(int argc, char **argv)
     }
     const int64_t block = (int64_t)(rtlFs / 4) / D * D;
     PIRIPOK(pirip_hip_rx_create_chan(dem, ldpc, chan, block, rx.out()), "receiver");
+    if (log_frames) {
+        pirip_ping_config cfg{};
+        cfg.nrx = K; cfg.filter_byte = -1; cfg.frames_per_burst = 1; cfg.period_calls = 1; cfg.log_entries = (int)pirip_hip_rx_max_frames(rx);
+        PIRIPOK(pirip_hip_ping_create(rx, nullptr, nullptr, &cfg, logger.out()), "-L");
+    }
     pirip_fsk_info info;
     pirip_hip_get_info(dem, &info);
     if (!quiet)
@@ -129,11 +141,13 @@ int main(int argc, char **argv)
     PIRIPOK(pirip_hip_rx_input(rx, &d_block, &in_stride), "receiver input");
     DevBuf<uint8_t> d_bits, d_status, d_payload;
     DevBuf<int32_t> d_info, d_nfr;
+    DevBuf<float> d_stats;
     const size_t rows = (size_t)K * (size_t)R;
     if (ldpc) {
         HIPOK(hipMalloc((void **)d_status.out(), rows));
         HIPOK(hipMalloc((void **)d_payload.out(), rows * (size_t)li.data_bytes));
         HIPOK(hipMalloc((void **)d_info.out(), sizeof(int32_t) * rows * PIRIP_LDPC_INFO_PER_CALL));
+        if (log_frames) HIPOK(hipMalloc((void **)d_stats.out(), sizeof(float) * rows * PIRIP_STATS_PER_FRAME));
     } else {
         HIPOK(hipMalloc((void **)d_bits.out(), rows * (size_t)info.Nbits));
     }
@@ -141,18 +155,25 @@ int main(int argc, char **argv)
     std::vector<uint8_t> raw((size_t)block * 2), bits(ldpc ? 0 : rows * (size_t)info.Nbits), status(ldpc ? rows : 0),
         payload(ldpc ? rows * (size_t)li.data_bytes : 0);
     std::vector<int32_t> nfr((size_t)K);
+    std::vector<int64_t> logged((size_t)K, 0);
+    std::vector<pirip_ping_entry> entries;
     long blocks = 0;
     for (;;) {
         const size_t got = fread(raw.data(), 2, (size_t)block, fin);
         if (got < (size_t)block) break;
         HIPOK(hipMemcpy(d_block, raw.data(), raw.size(), hipMemcpyHostToDevice));
-        if (ldpc) PIRIPOK(pirip_hip_rx_process(rx, nullptr, 0, nullptr, 0, d_status, d_payload, d_info, nullptr, 0, d_nfr, nullptr), "receiver");
+        if (ldpc) PIRIPOK(pirip_hip_rx_process(rx, nullptr, 0, nullptr, 0, d_status, d_payload, d_info, d_stats, log_frames ? (size_t)R * PIRIP_STATS_PER_FRAME : 0, d_nfr, nullptr), "receiver");
         else PIRIPOK(pirip_hip_rx_process(rx, d_bits, (size_t)R * info.Nbits, nullptr, 0, nullptr, nullptr, nullptr, nullptr, 0, d_nfr, nullptr), "receiver");
         // the counters run on the device behind the block, on the same HIP stream: nothing below waits for them
         if (put_bits) PIRIPOK(pirip_hip_tbits_push(tb, d_bits, (size_t)R * info.Nbits, info.Nbits, 0, d_nfr, R, nullptr), "--put-test-bits");
         if (testframes)
             PIRIPOK(pirip_hip_tbits_push_records(tb, d_status, (size_t)R, d_payload, (size_t)R * li.data_bytes, d_info,
                                                  (size_t)R * PIRIP_LDPC_INFO_PER_CALL, d_nfr, (int)R, nullptr), "--testframes");
+        if (log_frames) {
+            PIRIPOK(pirip_hip_ping_push_records(logger, d_status, (size_t)R, d_payload, (size_t)R * li.data_bytes, d_info, (size_t)R * PIRIP_LDPC_INFO_PER_CALL,
+                                                d_stats, (size_t)R * PIRIP_STATS_PER_FRAME, d_nfr, (int)R, nullptr, 0, nullptr), "-L");
+            PIRIPOK(print_new_ping_entries(logger, Fs, logged, entries), "-L");
+        }
         HIPOK(hipMemcpy(nfr.data(), d_nfr, sizeof(int32_t) * (size_t)K, hipMemcpyDeviceToHost));
         if (ldpc) {
             HIPOK(hipMemcpy(status.data(), d_status, rows, hipMemcpyDeviceToHost));

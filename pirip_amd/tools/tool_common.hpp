@@ -6,6 +6,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include <cmath>
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -163,6 +164,36 @@ using TxHandle = Owned<pirip_hip_tx, pirip_hip_tx_destroy>;
 using MuxHandle = Owned<pirip_hip_mux, pirip_hip_mux_destroy>;
 using TxsHandle = Owned<pirip_hip_txs, pirip_hip_txs_destroy>;
 using RptHandle = Owned<pirip_hip_rpt, pirip_hip_rpt_destroy>;
+using PingHandle = Owned<pirip_hip_ping, pirip_hip_ping_destroy>;
+
+// ---- the ping terminal's log (ping_channels, rtl_fsk_channels -L) ------------------------------------------------------------------------
+// rtl_fsk -L's line without the wall clock, the channel in front; the dB value is computed here as in rtl_fsk.cpp
+static inline void print_ping_entry(FILE *f, int chan, const pirip_ping_entry &e, int Fs)
+{
+    const double S = e.S, N = e.N;
+    fprintf(f, "%d: Rx frame src: 0x%02x seq: %3d S: %e N: %e SNR: %5.2f dB t_rx: %.4f s\n", chan, e.source, e.seq, S, N,
+            10.0 * log10(S / (N + 1e-30) + 1e-30), (double)e.t_samples / (double)Fs);
+}
+// The entries logged since the last look, per receive channel, on stderr: seen [nrx] = the frames printed so far (zeros at first), buf a
+// work array. A channel that logged more than its ring holds since then says so and prints what the ring kept. Synchronises the device.
+static inline int print_new_ping_entries(pirip_hip_ping *ping, int Fs, std::vector<int64_t> &seen, std::vector<pirip_ping_entry> &buf)
+{
+    pirip_ping_info pi;
+    int rc = pirip_hip_ping_get_info(ping, &pi);
+    if (rc != PIRIP_OK) return rc;
+    std::vector<int64_t> frames((size_t)pi.nrx);
+    if ((rc = pirip_hip_ping_get_counters(ping, frames.data(), nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr)) != PIRIP_OK) return rc;
+    buf.resize((size_t)pi.log_entries);
+    for (int c = 0; c < pi.nrx; c++) {
+        int64_t fresh = frames[(size_t)c] - seen[(size_t)c];
+        if (fresh > pi.log_entries) { fprintf(stderr, "%d: %lld log entries lost\n", c, (long long)(fresh - pi.log_entries)); fresh = pi.log_entries; }
+        int got = 0;
+        if (fresh > 0 && (rc = pirip_hip_ping_get_log(ping, c, buf.data(), (int)fresh, &got)) != PIRIP_OK) return rc;
+        for (int i = 0; i < got; i++) print_ping_entry(stderr, c, buf[(size_t)i], Fs);
+        seen[(size_t)c] = frames[(size_t)c];
+    }
+    return PIRIP_OK;
+}
 
 // an input or output file; the process's own stdin / stdout stay open
 static inline int close_file(FILE *f) { return f == stdin || f == stdout ? 0 : fclose(f); }
