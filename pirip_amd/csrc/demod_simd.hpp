@@ -57,12 +57,24 @@ __device__ __forceinline__ float wave_sum(float v)
 // arg-max with codec2's tie rule (first maximum wins): larger value, then smaller index. v >= 0 and never NaN (a lane's
 // candidate is only ever replaced by "w > best" with best starting at 0), so the wave maximum is six v_max_f32 with a DPP
 // source and the winning index is the minimum index among the lanes that hold the maximum (six v_min_i32).
+// SINGLE (the wave kernel's call sites): short of an exact tie the maximum sits in ONE lane -- the ballot of the lanes that hold it has one
+// bit set (a scalar count) and that lane's index is one v_readlane; only a tie runs the second reduction. The same winner either way.
+template <bool SINGLE = false>
 __device__ __forceinline__ void wave_argmax(float &v, int &idx)
 {
     float red = v;
     int smax, smin;
     asm(PIRIP_DPP_REDUCE("v_max_f32_dpp") : "+v"(red), "=s"(smax));
-    int cand = (__builtin_bit_cast(int, v) == smax) ? idx : 0x7fffffff;      // v >= 0: equal values <=> equal bit patterns
+    const bool holds = __builtin_bit_cast(int, v) == smax;                   // v >= 0: equal values <=> equal bit patterns
+    if constexpr (SINGLE) {
+        const unsigned long long who = __ballot(holds);
+        if (__builtin_popcountll(who) == 1) {
+            v = __builtin_bit_cast(float, smax);
+            idx = __builtin_amdgcn_readlane(idx, __builtin_ctzll(who));
+            return;
+        }
+    }
+    int cand = holds ? idx : 0x7fffffff;
     asm(PIRIP_DPP_REDUCE("v_min_i32_dpp") : "+v"(cand), "=s"(smin));
     v = __builtin_bit_cast(float, smax);
     idx = smin;

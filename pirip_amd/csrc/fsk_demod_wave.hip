@@ -126,6 +126,24 @@ __device__ __forceinline__ v2f smooth2(v2f sf, v2f mag, v2f k)
     return sf;
 }
 
+// bit B of flags as a mask: all ones / zero, one instruction (written as shifts hipcc turns it and the AND that follows into
+// v_and + v_cmp + v_cndmask)
+template <int B>
+__device__ __forceinline__ uint32_t flag_mask_at(uint32_t flags)
+{
+    uint32_t r;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(r) : "v"(flags), "n"(B));
+    return r;
+}
+__device__ __forceinline__ uint32_t flag_mask(uint32_t flags, int b)      // (b is a constant after unrolling)
+{
+    switch (b) {
+    case 0: return flag_mask_at<0>(flags); case 1: return flag_mask_at<1>(flags); case 2: return flag_mask_at<2>(flags);
+    case 3: return flag_mask_at<3>(flags); case 4: return flag_mask_at<4>(flags); case 5: return flag_mask_at<5>(flags);
+    case 6: return flag_mask_at<6>(flags); default: return flag_mask_at<7>(flags);
+    }
+}
+
 // ---- input formats ------------------------------------------------------------------------------------------------
 // Exact conversions (each checked against the defining expression for every input value in tests/test_boundary_cpu.py; the 8-bit maps
 // on (I, Q) pairs, cvt_u8_pair: demod_simd.hpp):
@@ -280,6 +298,27 @@ struct WaveCfg {
     static_assert(M * P <= 48, "window prefix sums are kept in registers");
 };
 
+// Instances that keep the frame loop they had before the frame cache, the per-call range flags and the single-lane arg-max (the kernel's
+// "what a locked receiver's frames have in common" block): where the register report (tools/kernel_resources.sh) shows more SGPRs spilled
+// with them than without, or the interleaved A/B a lower rate (profiles/fc_instance_rates_4fsk_mask_ab.txt: the 4-FSK comb-estimator
+// instances on float input, 1 - 4 % slower). DESIGN.md 4.1 has the table.
+constexpr bool wave_plain_instance(int M, int TS, int P, int NDFT, int FMT, int WPS, bool FFT_FMA, bool MASK, int BAND)
+{
+    if (MASK && M == 4) return true;                                                  // every 4-FSK comb instance (the float ones: slower; the rest: spills)
+    if (MASK && M == 2 && TS == 24 && FMT == PIRIP_IN_CU8_CSDR) return true;          // + 1 spilled SGPR either way
+    if (!MASK && M == 4 && FMT == PIRIP_IN_CF32 && (TS == 18 || TS == 10)) return true;   // + 1 / + 3
+    return false;
+}
+
+// ... and instances that take the rest but keep the two-reduction arg-max: the single-lane form's ballot and branch cost them one to
+// three more spilled SGPRs (same report).
+constexpr bool wave_two_pass_argmax_instance(int M, int TS, int FMT, bool MASK, int BAND)
+{
+    if (MASK && M == 2 && TS == 24) return true;
+    if (!MASK && M == 4 && (FMT == PIRIP_IN_CF32 || FMT == PIRIP_IN_CS16 || BAND == 4)) return true;
+    return false;
+}
+
 // Per-wave LDS footprint, also used by the launcher to report occupancy
 template <class C, int M> constexpr int wave_lds_bytes() { return C::RAW_B + C::XP_B; }
 
@@ -306,6 +345,8 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     // latency at the point of use costs more than a lane write and a lane read). So: by value, except Ts = 10 (`rtl_fsk -a 100000 -r 10000`,
     // README.md:196: + 1.9 % / + 4.1 %).
     constexpr bool INPLACE = TS == 10;
+    constexpr bool PLAIN = wave_plain_instance(M, TS, P, NDFT, FMT, WPS, FFT_FMA, MASK, BAND);
+    constexpr bool ARGMAX_SINGLE = !PLAIN && !wave_two_pass_argmax_instance(M, TS, FMT, MASK, BAND);
     static_assert(offsetof(DemodArgs, d) == 0, "the argument block is the first kernel argument");
     auto ap = [&]() {
         if constexpr (INPLACE) return (const __attribute__((address_space(4))) DemodArgs *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -370,7 +411,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     // when there is no last frame (state as pirip_hip_reset / fsk_create leave it: integrator memory all zero).
     // Last frame's tone estimates (phase step, oscillator-table row) and length: the old positions are mixed with THOSE.
     uint32_t *st32 = (uint32_t *)(a.s.hist + (size_t)sid * M * HIST);
-    int ninp = __builtin_amdgcn_readfirstlane((int)st32[C::TRAILER_DW + 2 * M]);
+    const int ninp0 = __builtin_amdgcn_readfirstlane((int)st32[C::TRAILER_DW + 2 * M]);
     uint32_t dthp[M];
     int tixp[M];
 #pragma unroll
@@ -378,7 +419,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
         dthp[m] = (uint32_t)__builtin_amdgcn_readfirstlane((int)st32[C::TRAILER_DW + m]);
         tixp[m] = __builtin_amdgcn_readfirstlane((int)st32[C::TRAILER_DW + M + m]);
     }
-    for (int i = lane0; i < GUARD_B / 4; i += kWave) ((uint32_t *)raw)[i] = ninp ? st32[i] : InFmt<FMT>::NEUTRAL;
+    for (int i = lane0; i < GUARD_B / 4; i += kWave) ((uint32_t *)raw)[i] = ninp0 ? st32[i] : InFmt<FMT>::NEUTRAL;
 
     // ---- per-lane estimator state: owned Sf bins -------------------------------------------------------------------
     // Lane-derived indices and addresses are cheap to compute and expensive to keep: hipcc hoists them out of the frame
@@ -439,8 +480,44 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     // the stream's first frame after fsk_create / reset was demodulated by the exact prologue of this call (fsk_demod_general.hip:
     // fsk_demod_exact0_kernel; P == Ts instances only): start behind it -- its state block, scalars and Sf are what was loaded above
     if (a.io.first) { pos = __builtin_amdgcn_readfirstlane(a.io.first[sid]); frame = pos ? 1 : 0; }
-    const int64_t frame_first = frame;
+    const int64_t frame_first = frame;                  // (read by PLAIN instances only: the others note in ninp_fc that a frame ran)
     int last_freqi0 = 0, last_freqi1 = 0, last_freqi2 = 0, last_freqi3 = 0;   // tone bins of the last frame (uniform)
+
+    // ---- what a locked receiver's frames have in common is kept across the frame loop -------------------------------------
+    // Peak search: which owned bins lie in the search range (call constants and the lane): one flag bit per bin, tested once per call.
+    uint32_t in_range = 0;
+    if constexpr (!MASK && !PLAIN) {
+#pragma unroll
+        for (int b = 0; b < NB; b++) {
+            const int sfi = (BAND && lane0 >= 16) ? -1 : own_sfi(lane0, b);
+            if (sfi >= d.est_st && sfi < d.est_en) in_range |= 1u << b;
+        }
+    }
+    // Correlator: each lane's start phasor per tone. It is a function of the frame's and last frame's tone rows and lengths (all
+    // wave-uniform), and a locked receiver sees the same rows and nin == N for thousands of frames: while this frame's rows equal last
+    // frame's and both frames are N samples long, the frame reuses what the last such frame computed (operand for operand what the
+    // set-up below would compute again) and skips the set-up with its per-lane table load. The cache's state costs no scalar register of
+    // its own: it rides in the top bits of the word that carries last frame's length, ninp_fc = ninp | kFcStale | kFcNever (ninp < 2^16).
+    // kFcStale clear: ph_c was computed by such a frame and every frame since was one. kFcNever: never hit (FskDims::frame_cache == 0, a
+    // test hook: every frame takes the miss branch -- the one branch is all the two ways differ by). Nothing of it outlives the call: a
+    // call's first frame misses.
+    // Registers decide how much is kept: 2 M for ph_c everywhere but at four waves per SIMD (128 VGPRs: no cache there), and 2 M more
+    // for the tones' per-sample steps (wave-uniform table rows) where that still fits the instance's occupancy -- 2-FSK, or two waves
+    // per SIMD; elsewhere a hit reads the rows again. PLAIN instances (wave_plain_instance) keep the frame loop they had.
+    constexpr bool FCACHE = WPS <= 3 && !PLAIN;
+    constexpr bool KEEP_STEP = FCACHE && (M == 2 || WPS == 2);
+    constexpr uint32_t kFcStale = 0x40000000u, kFcNever = 0x80000000u, kFcRan = 0x20000000u;   // (kFcRan: the call has run a frame -- the same word again)
+    static_assert(N + Q < 0x10000, "last frame's length leaves the flag bits free");
+    v2f ph_c[FCACHE ? M : 1], step_c[KEEP_STEP ? M : 1];
+    if constexpr (FCACHE) {
+#pragma unroll
+        for (int m = 0; m < M; m++) ph_c[m] = v2f{0.f, 0.f};
+    }
+    if constexpr (KEEP_STEP) {
+#pragma unroll
+        for (int m = 0; m < M; m++) step_c[m] = v2f{0.f, 0.f};
+    }
+    uint32_t ninp_fc = (uint32_t)ninp0 | (d.frame_cache ? kFcStale : kFcNever);
 
     // LDS-DMA of the frame superset [p0, p0 + N + Q) to raw + GUARD_B (lane-linear: 16 or 4 bytes per lane per instruction)
     typedef __attribute__((address_space(3))) void *lds_ptr;
@@ -959,19 +1036,21 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                 for (int k = 0; k < d.n_teeth; k++) corr += sfl[b + a.t.teeth[k]];    // tooth sums in ascending order
                 if (corr > best) { best = corr; ib = b; }
             }
-            wave_argmax(best, ib);
+            wave_argmax<ARGMAX_SINGLE>(best, ib);
             bb = ib;
             wave_lds_sync();
         } else {
             PIRIP_PHASE_LANE(lane);
             float w[NB];
             int sfi[NB];
+            static_assert(NB <= 8, "one flag bit per owned bin");
 #pragma unroll
             for (int b = 0; b < NB; b++) {
                 sfi[b] = (BAND && lane >= 16) ? -1 : own_sfi(lane, b);                                 // (BAND: group 0's copy competes)
-                // the search range is tested ONCE per frame, not once per tone: a bin outside it competes with 0, which the strict
-                // comparison against best >= 0 never selects -- the same winners as testing the range in every tone's loop
-                w[b] = (sfi[b] >= d.est_st && sfi[b] < d.est_en) ? Sf[b] : 0.0f;
+                // the search range is tested ONCE per call (in_range), not once per tone or frame: a bin outside it competes with +0, which
+                // the strict comparison against best >= 0 never selects -- the same winners as testing the range in every tone's loop
+                if constexpr (PLAIN) w[b] = (sfi[b] >= d.est_st && sfi[b] < d.est_en) ? Sf[b] : 0.0f;
+                else w[b] = __builtin_bit_cast(float, fbits(Sf[b]) & flag_mask(in_range, b));
             }
 #pragma unroll
             for (int m = 0; m < M; m++) {
@@ -979,7 +1058,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
 #pragma unroll
                 for (int b = 0; b < NB; b++)
                     if (w[b] > best) { best = w[b]; ib = sfi[b]; }
-                wave_argmax(best, ib);
+                wave_argmax<ARGMAX_SINGLE>(best, ib);
                 int f_min = ib - d.f_zero; f_min = f_min < 0 ? 0 : f_min;
                 int f_max = ib + d.f_zero; f_max = f_max > NDFT ? NDFT : f_max;
 #pragma unroll
@@ -1036,24 +1115,55 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             // continues. Both oscillators are at the phase reference (0) between the last old and the first new sample: an old position
             // n0 + k <= 0 steps before it is mixed with phasor((n0 + k) dtheta_old), at the gain the old recursion had reached there
             // (nin_prev + n0 + k steps after its renormalisation), which is what last frame's kernel stored in the f_dc ring of round 3.
-#pragma unroll
-            for (int m = 0; m < M; m++) {
-                const float2 stn = a.t.osc_step[tix[m]], stp = a.t.osc_step[tixp[m]];          // uniform loads
-                const float dn = a.t.osc_drift[tix[m]].x, dp = a.t.osc_drift[tixp[m]].x;
-                const uint32_t th = (uint32_t)n0 * (oldl ? dthp[m] : dthv[m]);
-                const float g = 1.0f + (oldl ? dp * (float)(ninp + n0) : dn * (float)n0);
-                const float2 pcs = phasor(th);
-                ph[m] = v2f{pcs.x * g, pcs.y * g};
-                dph[m] = oldl ? v2f{stp.x, stp.y} : v2f{stn.x, stn.y};
-                const float2 p1 = phasor(dthv[m]);
-                const float g1 = 1.0f + dn;
-                sw_ph[m] = v2f{p1.x * g1, p1.y * g1};
-                sw_dph[m] = v2f{stn.x, stn.y};
-                acc[m] = v2f{0.f, 0.f};
-            }
+            // the set-up's inputs: tix / tixp (dthv / dthp are functions of them), nin, ninp. moved == 0: they are what a locked receiver's
+            // are (as differences OR-ed together, not as booleans: hipcc evaluates these on the scalar unit; none reaches the sign bit)
+            const int ninp = (int)(ninp_fc & 0xffffu);
             // without a last frame the old positions hold neutral samples (converted to exactly 0.0); csdr's u8 mapping has no such
             // byte value: that format zeroes the converted sample of an old position instead
             const int zero_blk = ninp ? 0 : nold_blk;
+            uint32_t moved = (uint32_t)(nin ^ N) | (uint32_t)(ninp ^ N);
+#pragma unroll
+            for (int m = 0; m < M; m++) moved |= (uint32_t)(tix[m] ^ tixp[m]);
+            static_assert(Q > 0 && Q < TS, "a block changes oscillators at sample Ts/4 or Ts - Ts/4 only: never where nold_blk is a multiple of Ts");
+            if (FCACHE && (moved | (ninp_fc & (kFcStale | kFcNever))) == 0) {
+                // hit: the rows are last frame's (old and new positions step alike). nin == N: nold = 2 Ts, nold_blk is a multiple of Ts in
+                // every lane and no block changes oscillators (the assertion above) -- sw_ph / sw_dph are never selected in this frame,
+                // they only have to hold something: the step
+#pragma unroll
+                for (int m = 0; m < M; m++) {
+                    if constexpr (KEEP_STEP) dph[m] = step_c[m];
+                    else { const float2 stn = a.t.osc_step[tix[m]]; dph[m] = v2f{stn.x, stn.y}; }      // uniform load
+                    if constexpr (FCACHE) ph[m] = ph_c[m];
+                    sw_ph[m] = dph[m];
+                    sw_dph[m] = dph[m];
+                }
+            } else {
+#pragma unroll
+                for (int m = 0; m < M; m++) {
+                    const float2 stn = a.t.osc_step[tix[m]], stp = a.t.osc_step[tixp[m]];          // uniform loads
+                    const float dn = a.t.osc_drift[tix[m]].x, dp = a.t.osc_drift[tixp[m]].x;
+                    const uint32_t th = (uint32_t)n0 * (oldl ? dthp[m] : dthv[m]);
+                    const float g = 1.0f + (oldl ? dp * (float)(ninp + n0) : dn * (float)n0);
+                    const float2 pcs = phasor(th);
+                    ph[m] = v2f{pcs.x * g, pcs.y * g};
+                    dph[m] = oldl ? v2f{stp.x, stp.y} : v2f{stn.x, stn.y};
+                    const float2 p1 = phasor(dthv[m]);
+                    const float g1 = 1.0f + dn;
+                    sw_ph[m] = v2f{p1.x * g1, p1.y * g1};
+                    sw_dph[m] = v2f{stn.x, stn.y};
+                    if constexpr (FCACHE) ph_c[m] = ph[m];
+                    if constexpr (KEEP_STEP) step_c[m] = sw_dph[m];
+                }
+            }
+            if constexpr (KEEP_STEP) {
+#pragma unroll
+                for (int m = 0; m < M; m++) sw_dph[m] = step_c[m];         // (one register pair for both: neither is written in the recursion)
+            }
+            // last frame's length for the next frame, with the cache's state: stale unless this frame's inputs were a locked receiver's
+            // (moved < 2^16: the sum carries into kFcStale exactly when moved != 0)
+            ninp_fc = (uint32_t)nin | (PLAIN ? 0u : kFcRan) | (ninp_fc & kFcNever) | (FCACHE ? ((moved + (kFcStale - 1u)) & kFcStale) : 0u);
+#pragma unroll
+            for (int m = 0; m < M; m++) acc[m] = v2f{0.f, 0.f};
 #pragma unroll
             for (int c = 0; c < TS / C::CHS; c++) {
                 uint32_t rw[C::CH_DW];
@@ -1151,7 +1261,6 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
         wave_lds_sync();
         PIRIP_T_MARK(3);                                   // correlator
         dma_frame(pos + nin);
-        ninp = nin;
 #pragma unroll
         for (int m = 0; m < M; m++) { dthp[m] = dthv[m]; tixp[m] = tix[m]; }
 
@@ -1190,18 +1299,11 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
 
         PIRIP_T_MARK(4);                                   // DMA issue, hist copy, window sums, timing reduction
         PIRIP_ARGS_REREAD();                               // (the output phase reads its pointers and strides afresh: nothing of them is live across the estimator and correlator)
-        const int frame_bytes = d.pack_bits ? (d.Nbits + 7) / 8 : d.Nbits;
+        const int frame_bytes = d.pack_bits ? (NBITS + 7) / 8 : NBITS;     // (Nbits is the instance's: two constants, nothing to keep across the loop)
         const size_t orow = (size_t)(frame + out0);
         uint8_t *bits_o = a.io.bits ? a.io.bits + (size_t)sid * a.io.bits_stride + orow * frame_bytes : nullptr;
         float *filt_o = a.io.filt ? a.io.filt + (size_t)sid * a.io.filt_stride + orow * M * NSYM : nullptr;
         float *stats_o = a.io.stats ? a.io.stats + (size_t)sid * a.io.stats_stride + orow * PIRIP_STATS_PER_FRAME : nullptr;
-        float f_est[kMaxTones] = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < M; m++) {
-            if constexpr (MASK) f_est[m] = (float)((bb - NDFT / 2) * d.Fs / NDFT) + (float)(m * d.tone_spacing);
-            else f_est[m] = (float)freqi[m] * d.bin_hz;
-        }
-
         const bool bad = isnan(tcr) || isnan(tci);
         int nin_next = nin;
         if (!bad) {
@@ -1415,6 +1517,13 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
         if constexpr (MASK) last_freqi0 = bb;
         else { last_freqi0 = freqi[0]; last_freqi1 = freqi[M > 1 ? 1 : 0]; last_freqi2 = freqi[M > 2 ? 2 : 0]; last_freqi3 = freqi[M > 3 ? 3 : 0]; }
         if (stats_o && lane == 0) {
+            // (the tone estimates in Hz are a stats column only: the stream's state gets them from last_freqi* at the end of the call)
+            float f_est[kMaxTones] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int m = 0; m < M; m++) {
+                if constexpr (MASK) f_est[m] = (float)((bb - NDFT / 2) * d.Fs / NDFT) + (float)(m * d.tone_spacing);
+                else f_est[m] = (float)freqi[m] * d.bin_hz;
+            }
             stats_o[0] = f_est[0]; stats_o[1] = f_est[1]; stats_o[2] = f_est[2]; stats_o[3] = f_est[3];
             stats_o[4] = sc_norm_rx_timing; stats_o[5] = sc_SNRest; stats_o[6] = (float)nin_next; stats_o[7] = sc_ppm;
         }
@@ -1440,11 +1549,11 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     if (lane == 0) {
 #pragma unroll
         for (int m = 0; m < M; m++) { st32[C::TRAILER_DW + m] = dthp[m]; st32[C::TRAILER_DW + M + m] = (uint32_t)tixp[m]; }
-        st32[C::TRAILER_DW + 2 * M] = (uint32_t)ninp;
+        st32[C::TRAILER_DW + 2 * M] = ninp_fc & 0xffffu;
         StreamScalars sc = a.s.scal[sid];
         sc.nin = nin; sc.norm_rx_timing = sc_norm_rx_timing; sc.ppm = sc_ppm; sc.SNRest = sc_SNRest;
         sc.snr_est = s_misc[wv][0]; sc.EbNodB = s_misc[wv][1]; sc.v_est = s_misc[wv][2];
-        if (frame > frame_first) {
+        if (PLAIN ? frame > frame_first : (ninp_fc & kFcRan) != 0) {                            // this call demodulated a frame: its tone estimates are the stream's
             const int fq[4] = {last_freqi0, last_freqi1, last_freqi2, last_freqi3};
             for (int m = 0; m < kMaxTones; m++) {
                 if (MASK) sc.f_est[m] = m < M ? (float)((fq[0] - NDFT / 2) * d.Fs / NDFT) + (float)(m * d.tone_spacing) : 0.f;

@@ -78,6 +78,7 @@ int FskPlan::init(int Fs, int Rs, int M, int P, int Nsym, int est_min, int est_m
     }
     d.burst_mode = 0;
     d.block_stagger = 0;
+    d.frame_cache = 1;
     d.fft_fma = 0;
     d.est_band = 0;
     d.pack_bits = 0;

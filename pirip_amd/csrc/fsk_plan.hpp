@@ -52,6 +52,8 @@ struct FskDims {
     int sf_power;
     int recalled_fast_ok;
     int block_stagger;                       // block kernel: start-up stagger of co-resident workgroups, in s_sleep(127) units per wave slot (0: none)
+    int frame_cache;                         // wave kernel: 1 = the correlator's start state is kept across frames while its inputs repeat; 0 (PIRIP_FRAME_CACHE=0,
+                                             // tests): every frame rebuilds it -- the same outputs, word for word
 };
 
 struct FskPlan {

@@ -8,6 +8,8 @@
 # burn the call's whole limit.
 # PARTS (default: headline band configs_stats configs_pmc):
 #   headline       bench.py (BASELINE configs[1]): kernel-trace stats at the default shape; counter sets at 6144 streams
+#                  (headline_stats / headline_pmc: one half only; PMC_SET=SQ1|SQ2|SQ3: only that counter set -- e.g. the instruction
+#                  counts of two builds, the second through PIRIP_HIP_LIB)
 #   band           the same through the OPT-IN band-only estimator (PIRIP_EST_BAND=1): stats + FETCH / WRITE / instruction counts
 #   configs_stats  tools/bench_configs.py (config 4 demod and whole chain, config 3, the rtl_fsk shapes): kernel-trace stats
 #   configs_pmc    ... its counter sets, per kernel
@@ -28,18 +30,21 @@ SQ2="SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_LDS SQ_ACTIVE_INST_VALU SQ_LDS_BANK_CONFL
 SQ3="SQ_WAIT_INST_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_ACTIVE_INST_SCA SQ_ACTIVE_INST_MISC"
 SQ4="SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM SQ_INSTS_BRANCH SQ_INSTS_SENDMSG SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT"
 SETS=("FETCH_SIZE" "WRITE_SIZE" "$SQ1" "$SQ2" "$SQ3")
+case "$PMC_SET" in SQ1) SETS=("$SQ1");; SQ2) SETS=("$SQ2");; SQ3) SETS=("$SQ3");; esac
 khash() { python3 -c "import sys,ctypes; sys.path.insert(0,'$R'); import pirip_amd; L=pirip_amd.lib(); L.pirip_hip_kernel_source_hash.restype=ctypes.c_char_p; print(L.pirip_hip_kernel_source_hash().decode())"; }
 # stats CMD... : one kernel-trace --stats run of CMD into /tmp/pr (+ /tmp/pr.log)
 stats() { rm -rf /tmp/pr; timeout $1 rocprofv3 --kernel-trace --stats -d /tmp/pr -- "${@:2}" > /tmp/pr.log 2>&1; }
 # pmc TIMEOUT "SET" CMD... : one counter run of CMD into /tmp/pm
 pmc() { rm -rf /tmp/pm; timeout $1 rocprofv3 --kernel-trace --pmc $2 -d /tmp/pm -- "${@:3}" > /tmp/pm.log 2>&1; }
 
-if has headline; then
+if has headline || has headline_stats; then
   O=$R/gpurun_out/${tag}_headline_stats.txt
   echo "# rocprofv3 --kernel-trace --stats -- python bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra --check-streams 16" > $O
   stats $ST python $R/bench.py --steps 5 --warmup 2 --full --no-cpu-baseline --no-extra --check-streams 16
   python $R/tools/rocprof_summary.py /tmp/pr | head -6 >> $O
   echo "# bench line under the profiler:" >> $O; grep '^{' /tmp/pr.log | cut -c1-1600 >> $O
+fi
+if has headline || has headline_pmc; then
   O=$R/gpurun_out/${tag}_headline_pmc.txt
   echo "# PMC passes, each its own run of: rocprofv3 --kernel-trace --pmc <set> -- python bench.py --streams 6144 --steps 2 --warmup 1 --full --no-cpu-baseline --no-extra --check-streams 4" > $O
   echo "# kernel_source_hash $(khash)" >> $O
