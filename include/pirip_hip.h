@@ -25,6 +25,8 @@
  *   section K  streaming transmitter (pirip_hip_txs_*)      : section G's mirror image, queued records to wideband IQ block after block.
  *   section L  test-frame counter (pirip_hip_tbits_*)       : fsk_put_test_bits / rtl_fsk --testframes for a batch of streams,
  *              counted on the device behind the demodulator or the receiver.
+ *   section O  channel (pirip_hip_air_*)                    : T transmitted wideband IQ streams onto R received ones: paths with
+ *              gain, delay and carrier offset, AWGN per receiver, block after block.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -867,6 +869,58 @@ int pirip_hip_ping_get_log(pirip_hip_ping *ping, int chan, pirip_ping_entry *ent
 /* Clears the sample clocks, the rings and the counters and resets txs, and rx where present: the next call is n = 0. */
 int pirip_hip_ping_reset(pirip_hip_ping *ping, void *hip_stream);
 /* One HIP stream per handle: clocks, rings and counters are device state advanced in stream order, the call index is host state advanced
+ * when a call is enqueued. */
+
+/* ----------------------------------------------------------------------------------- */
+/* section O : channel (T transmitted wideband IQ streams onto R received ones)          */
+/*   What lies between the terminals of sections M and N: the reference's "60 dB           */
+/*   attenuator" or the air (its test/loopback_rtl_fsk.sh and README "MDS tests"). Every    */
+/*   received stream is a sum of paths -- a transmitter, a real gain, a delay in samples,    */
+/*   a carrier offset in Hz -- plus its own AWGN, written as u8 or complex float, block       */
+/*   after block with the history carried on the device.                     */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_air pirip_hip_air;
+typedef struct pirip_air_path { int32_t rx, tx, delay, offset_hz; float gain; } pirip_air_path;
+typedef struct pirip_air_info { int Fs, ntx, nrx, npaths, in_format, out_format, max_delay, device; } pirip_air_info;
+/* ntx transmitted and nrx received streams at Fs samples/s; path p = (received stream rx_p, transmitted stream t_p = tx, real gain a_p,
+ * delay d_p in samples, carrier offset f_p in integer Hz). With n the absolute sample index and x_t[k] = 0 for k below the index of the
+ * last reset (0 after create) -- for u8 input exactly zero, not the value of byte 128:
+ *     y_r[n] = sum_{p : rx_p = r, ascending p} a_p e^{+j 2 pi f_p n / Fs} x_{t_p}[n - d_p]  +  sigma_r w_r[n]
+ * w_r[n]: the product's one noise source (sections B2 and I), unit variance per component, keyed by (seed, r, n).
+ * Arithmetic, per component in float: in_format PIRIP_IN_CU8_CSDR is read as b / 127.5 - 1 (section H's conversion), PIRIP_IN_CF32 as it is.
+ * A path with f_p != 0 is rotated by the unit phasor of the exact integer phase ((f_p mod Fs)(n mod Fs)) mod Fs (section J's mixer: one
+ * product and one fma per component); a path with f_p == 0 is not rotated. The sum starts at 0 and takes the paths in ascending index as
+ * acc = fma(a_p, v, acc). With sigma_r > 0 the noise of key (seed, r, n) is added. out_format PIRIP_IN_CF32 stores acc, PIRIP_IN_CU8_CSDR
+ * clamp(rintf(127.5f v + 127.5f), 0, 255) per component, section J's byte: the clamp is the ADC's clipping. A received stream with no path
+ * and sigma 0 is all zeros (cf32) / all bytes 128 (u8).
+ * A sample is a function of the absolute index, of its own stream's paths and of the input alone: any cutting of the same input into calls
+ * gives the one-shot output bit for bit (n = 1 and calls shorter than the longest delay included), with sigma 0 a start at n0 and one at
+ * n0 + k Fs give the same bytes, and a received stream does not depend on the other streams' paths. Numerics: DESIGN.md 4.15.
+ * sigma: [nrx] host, NULL = all 0. The number of paths per received stream is not limited.
+ * PIRIP_ERR_BAD_ARG for out or (with npaths > 0) paths NULL, ntx < 1, nrx < 1, npaths < 0, Fs < 2, a format other than the two above, an rx
+ * outside [0, nrx), a tx outside [0, ntx), a delay < 0, an offset outside -Fs/2 < f < Fs/2, a gain or a sigma that is not finite, a
+ * sigma < 0. PIRIP_ERR_UNSUPPORTED for Fs > 2^24, a delay > 2^20, ntx or nrx > 65535. Create sizes everything and synchronises. */
+int pirip_hip_air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path *paths, const float *sigma,
+                         uint64_t seed, int device, pirip_hip_air **out);
+int pirip_hip_air_destroy(pirip_hip_air *air);
+int pirip_hip_air_get_info(const pirip_hip_air *air, pirip_air_info *info);      /* max_delay: the longest delay of any path */
+/* New sigma [nrx] (host; read before the call returns) for the calls enqueued behind this one: a level sweep needs no new handle and no
+ * synchronisation. PIRIP_ERR_BAD_ARG for NULL, a value that is not finite or < 0. */
+int pirip_hip_air_set_sigma(pirip_hip_air *air, const float *sigma, void *hip_stream);
+/* Transmitted stream t: n samples of in_format at (char*)d_in + t*in_stride_bytes, the first with the absolute index that follows the last
+ * call's (n0 of the last reset; 0 after create). Received stream r: n samples of out_format at (char*)d_out + r*out_stride_bytes. Rows are
+ * aligned to their sample (2 or 8 bytes; 16-byte aligned u8 output rows get 16-byte stores, the bytes are the same) and the rows of one
+ * side must not overlap; d_out must not overlap d_in. PIRIP_ERR_BAD_ARG for those, NULL pointers and n < 1; PIRIP_ERR_UNSUPPORTED when the
+ * absolute index would reach 2^53. State: per transmitted stream a ring of its last samples in in_format, at least its longest delay long,
+ * addressed by the absolute index; the call reads x[n - d] from its own rows where that index lies in the call and from the ring otherwise,
+ * and a carry step behind it, in stream order, writes the call's last samples into the ring. Enqueued on hip_stream (NULL = default
+ * stream); never synchronises, never allocates; every call makes the same launches. */
+int pirip_hip_air_push(pirip_hip_air *air, const void *d_in, size_t in_stride_bytes, int64_t n, void *d_out, size_t out_stride_bytes,
+                       void *hip_stream);
+/* Forget the history: the next sample has absolute index n0 >= 0 (PIRIP_ERR_BAD_ARG below 0, PIRIP_ERR_UNSUPPORTED from 2^53), and every
+ * earlier one is zero. sigma stays. */
+int pirip_hip_air_reset(pirip_hip_air *air, int64_t n0, void *hip_stream);
+/* One HIP stream per handle: the rings and sigma are device state advanced in stream order, the absolute index is host state advanced
  * when a call is enqueued. */
 
 /* ----------------------------------------------------------------------------------- */

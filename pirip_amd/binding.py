@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J, K and L).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J, K, L, M, N and O).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -77,6 +77,15 @@ PING_ENTRY_DTYPE = [("t_samples", "<i8"), ("call", "<i4"), ("row", "<i4"), ("S",
 class PingInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("nrx", "nchan", "source_byte", "filter_byte", "frames_per_burst", "seq", "period_calls", "log_entries",
                                        "nin0", "has_rx", "rx_rows", "data_bytes", "device")] + [("max_bursts", C.c_int64)]
+
+
+class AirPath(C.Structure):
+    """pirip_air_path: received stream, transmitted stream, delay in samples, carrier offset in Hz, real gain"""
+    _fields_ = [("rx", C.c_int32), ("tx", C.c_int32), ("delay", C.c_int32), ("offset_hz", C.c_int32), ("gain", C.c_float)]
+
+
+class AirInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("Fs", "ntx", "nrx", "npaths", "in_format", "out_format", "max_delay", "device")]
 
 
 class LdpcInfo(C.Structure):
@@ -233,6 +242,12 @@ def lib():
     L.pirip_hip_ping_get_counters.argtypes = [vp] + [vp] * 9
     L.pirip_hip_ping_get_log.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
     L.pirip_hip_ping_reset.argtypes = [vp, vp]
+    L.pirip_hip_air_create.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, C.c_uint64, i32, C.POINTER(vp)]
+    L.pirip_hip_air_destroy.argtypes = [vp]
+    L.pirip_hip_air_get_info.argtypes = [vp, C.POINTER(AirInfo)]
+    L.pirip_hip_air_set_sigma.argtypes = [vp, vp, vp]
+    L.pirip_hip_air_push.argtypes = [vp, vp, sz, i64, vp, sz, vp]
+    L.pirip_hip_air_reset.argtypes = [vp, i64, vp]
     _lib = L
     return L
 
@@ -980,6 +995,75 @@ class HipPing:
 
     def reset(self, stream=None):
         _chk(self.L.pirip_hip_ping_reset(self.h, _hip_stream(stream)), "pirip_hip_ping_reset")
+
+
+class HipAir:
+    """Channel (include/pirip_hip.h section O): ntx transmitted wideband IQ streams onto nrx received ones. paths: AirPath entries, or
+    tuples / dicts of (rx, tx, gain, delay, offset_hz) -- received stream rx hears transmitted stream tx scaled by the real gain, `delay`
+    samples late and `offset_hz` Hz up; sigma: the noise per component of every received stream (a number, nrx numbers, or None for none),
+    keyed by (seed, stream, absolute sample) as HipTx.modulate's; in_format / out_format: IN_CU8_CSDR or IN_CF32. The history of every
+    transmitted stream stays on the device: any cutting of a stream into push() calls gives the same output. Pointer arguments take torch
+    tensors or raw device pointers, streams default to torch's current stream."""
+
+    def __init__(self, Fs, paths, ntx, nrx, sigma=None, seed=1, in_format=IN_CU8_CSDR, out_format=IN_CU8_CSDR, device=-1):
+        self.L = lib()
+        rows = []
+        for p in paths:
+            if isinstance(p, AirPath):
+                rows.append((p.rx, p.tx, p.gain, p.delay, p.offset_hz))
+            elif isinstance(p, dict):
+                rows.append((p["rx"], p["tx"], p.get("gain", 1.0), p.get("delay", 0), p.get("offset_hz", 0)))
+            else:
+                rows.append(tuple(p))
+        arr = (AirPath * max(len(rows), 1))()
+        for i, (rx, tx, gain, delay, off) in enumerate(rows):
+            arr[i] = AirPath(int(rx), int(tx), int(delay), int(off), float(gain))
+        self.paths = rows
+        sg = self._sigma(sigma, int(nrx))
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_air_create(int(Fs), int(in_format), int(out_format), int(ntx), int(nrx), len(rows), C.addressof(arr) if rows else None,
+                                         None if sg is None else sg.ctypes.data, int(seed), device, C.byref(h)), "pirip_hip_air_create")
+        self.h = h
+        self.info = AirInfo()
+        _chk(self.L.pirip_hip_air_get_info(self.h, C.byref(self.info)), "pirip_hip_air_get_info")
+        self.Fs, self.ntx, self.nrx, self.seed, self.max_delay = int(Fs), self.info.ntx, self.info.nrx, int(seed), self.info.max_delay
+        self.in_format, self.out_format = int(in_format), int(out_format)
+        self.in_bytes_per_sample = 8 if in_format == IN_CF32 else 2
+        self.out_bytes_per_sample = 8 if out_format == IN_CF32 else 2
+
+    @staticmethod
+    def _sigma(sigma, nrx):
+        import numpy as np
+        if sigma is None:
+            return None
+        sg = np.ascontiguousarray(sigma, dtype=np.float32).reshape(-1)
+        if sg.size == 1:
+            sg = np.full(nrx, sg[0], dtype=np.float32)
+        if sg.size != nrx:
+            raise ValueError("sigma: one value, or one per received stream")
+        return sg
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_air_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def push(self, d_in, in_stride, n, d_out, out_stride, stream=None):
+        """transmitted stream t: n samples at d_in + t * in_stride -> received stream r: n samples at d_out + r * out_stride (strides in
+        bytes); the samples follow the last call's. Does not synchronise."""
+        _chk(self.L.pirip_hip_air_push(self.h, _dev(d_in), int(in_stride), int(n), _dev(d_out), int(out_stride), _hip_stream(stream)),
+             "pirip_hip_air_push")
+
+    def set_sigma(self, sigma, stream=None):
+        """new sigma (a number or nrx numbers) for the calls behind this one; does not synchronise"""
+        sg = self._sigma(0.0 if sigma is None else sigma, self.nrx)
+        _chk(self.L.pirip_hip_air_set_sigma(self.h, sg.ctypes.data, _hip_stream(stream)), "pirip_hip_air_set_sigma")
+
+    def reset(self, n0=0, stream=None):
+        """forget the history: the next sample has absolute index n0, every earlier one is zero"""
+        _chk(self.L.pirip_hip_air_reset(self.h, int(n0), _hip_stream(stream)), "pirip_hip_air_reset")
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

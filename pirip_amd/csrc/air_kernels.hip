@@ -1,0 +1,319 @@
+// pirip_amd/csrc/air_kernels.hip -- include/pirip_hip.h section O: the channel.
+//
+// T transmitted wideband IQ streams onto R received ones, block after block. Path p = (receiver rx_p, transmitter t_p, gain a_p, delay d_p,
+// offset f_p); with n the absolute sample index and x_t[k] = 0 below the last reset:
+//     y_r[n] = sum_{p of receiver r, ascending} a_p e^{+j 2 pi f_p n / Fs} x_{t_p}[n - d_p]  +  sigma_r w_r[n]
+// Every piece is the one definition of iq_device.hpp and noise_device.hpp: u8_to_float, the exact integer phase (mulmod_fs once per lane
+// and path, then its exact integer increment f_p with one wrap per sample -- no recursion in floating point), unit_phasor, crot, one fma
+// per component and path into a sum that starts at 0, add_awgn keyed by (seed, r, n), quant_u8_csdr.
+//
+// Mix kernel: one workgroup per (tile of kAirTile = 2048 outputs, receiver); thread t owns the 8 consecutive outputs 8 t .. 8 t + 7 of the
+// tile, so a u8 row is stored 16 bytes per lane and 1024 consecutive bytes per wave, and a complex float row as four 16-byte stores per
+// lane; rows that are only aligned to the sample, and a tile's ragged end, are stored sample by sample -- the same values.
+// The paths of the receiver are taken one after the other, ascending. The tile's span of the path's transmitter -- cnt consecutive samples
+// from call index j0 - d_p on -- is unaligned by construction, so it goes through LDS as the 16-byte units that hold it, loaded aligned:
+// the part below the call's first sample from the transmitter's ring (units taken modulo the ring, which is a power of two of samples and so
+// wraps on a unit), the rest from the call's row. The two parts keep their own byte shift in LDS; a lane reads its samples at
+// shift + 16 u + BS k, two or eight bytes at a time, from the part its sample lies in: the choice between ring and row is an address, not a
+// branch, and the staging loops are the only place where the two sources differ (each loop is uniform but for its last trip).
+// An aligned unit that holds one byte of a row lies in that byte's page: the bytes it over-reads are never used.
+// Samples below the last reset are zero by their index (for u8: the float zero, not byte 128), whatever the ring holds.
+// Carry kernel, behind the mix kernel in stream order: the call's last min(n, ring) samples of every transmitter go to their ring slots
+// (absolute index modulo the ring), sample by sample.
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+#include <new>
+#include <vector>
+
+#include "../../include/pirip_hip.h"
+#include "air_handle.hpp"
+#include "hip_host.hpp"
+#include "iq_device.hpp"
+#include "noise_device.hpp"
+#include "rate_host.hpp"
+
+using namespace pirip;
+
+namespace {
+
+template <int BSI>
+__device__ __forceinline__ v2f air_sample(const char *p, v2f chi, v2f clo)
+{
+    if (BSI == 2) {
+        const uint32_t w = *(const uint16_t *)p;
+        return u8_to_float(v2f{(float)(w & 0xffu), (float)(w >> 8)}, chi, clo);
+    }
+    return *(const v2f *)p;
+}
+
+// LDS: kAirTile * BSI + 64 bytes (the span's units: two parts, each with a unit of slack at either end)
+template <int BSI, int BSO>
+__global__ __launch_bounds__(kAirThreads) void air_mix_kernel(AirArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int64_t j0 = (int64_t)blockIdx.x * kAirTile;                 // first output of the tile (of this call)
+    const int cnt = (int)((a.n - j0) < kAirTile ? (a.n - j0) : kAirTile);
+    const int jl = tid * kAirPerThread;                                 // the thread's first output of the tile
+    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
+    // (n mod Fs) of the thread's first output
+    const uint32_t base = (uint32_t)(((int64_t)a.n0m + j0 % a.Fs) % a.Fs);
+    const uint32_t idx0 = (base + (uint32_t)jl) % (uint32_t)a.Fs;
+    v2f acc[kAirPerThread];
+#pragma unroll
+    for (int k = 0; k < kAirPerThread; k++) acc[k] = v2f{0.f, 0.f};
+
+    const int p0 = a.rx_start[r], p1 = a.rx_start[r + 1];
+    for (int pi = p0; pi < p1; pi++) {
+        const AirPath pth = a.paths[pi];
+        const AirRing rg = a.rings[pth.tx];
+        const int64_t s0 = j0 - pth.delay;                              // the span's first sample, as an index of this call
+        const int cnt_r = s0 >= 0 ? 0 : (-s0 < cnt ? (int)-s0 : cnt);   // samples from the ring
+        const int cnt_w = cnt - cnt_r;                                  // samples from the call's row
+        // tile index of the first sample at or above the last reset
+        const int64_t vf = a.first - (a.N0 + s0);
+        const int vfirst = vf <= 0 ? 0 : (vf < kAirTile ? (int)vf : kAirTile);
+        if (pi > p0) __syncthreads();
+        int shift_r = 0, units_r = 0;
+        if (cnt_r > 0) {
+            const uint32_t b0 = (uint32_t)((uint64_t)(a.N0 + s0) & rg.mask) * BSI;        // (a ring holds at most 2^20 samples of 8 bytes)
+            const uint32_t umask = ((rg.mask + 1u) * BSI >> 4) - 1u;
+            const uint4 *src = (const uint4 *)(a.ring + (size_t)rg.off * BSI);
+            shift_r = (int)(b0 & 15u);
+            units_r = (shift_r + cnt_r * BSI + 15) >> 4;
+            for (int u = tid; u < units_r; u += kAirThreads) ((uint4 *)smem)[u] = src[((b0 >> 4) + (uint32_t)u) & umask];
+        }
+        int shift_w = 0;
+        if (cnt_w > 0) {
+            const char *p = a.in + (size_t)pth.tx * a.in_stride + (size_t)(s0 + cnt_r) * BSI;
+            shift_w = (int)((uintptr_t)p & 15);
+            const uint4 *src = (const uint4 *)(p - shift_w);
+            const int units_w = (shift_w + cnt_w * BSI + 15) >> 4;
+            for (int u = tid; u < units_w; u += kAirThreads) ((uint4 *)smem)[units_r + u] = src[u];
+        }
+        __syncthreads();
+        const int off_r = shift_r, off_w = units_r * 16 + shift_w - cnt_r * BSI;
+        const v2f g = {pth.gain, pth.gain};
+        if (pth.fres != 0) {
+            uint32_t ph = (uint32_t)(int32_t)mulmod_fs((double)pth.fres, (double)idx0, a.Fs, a.inv_fs_d);
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) {
+                const int j = jl + k;
+                v2f v = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
+                if (j < vfirst) v = v2f{0.f, 0.f};
+                float cs, sn;
+                unit_phasor((int32_t)ph, a.Fs, a.two_over_fs, cs, sn);
+                acc[k] = __builtin_elementwise_fma(g, crot(v, cs, sn), acc[k]);
+                ph += (uint32_t)pth.fres;
+                if (ph >= (uint32_t)a.Fs) ph -= (uint32_t)a.Fs;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) {
+                const int j = jl + k;
+                v2f v = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
+                if (j < vfirst) v = v2f{0.f, 0.f};
+                acc[k] = __builtin_elementwise_fma(g, v, acc[k]);
+            }
+        }
+    }
+
+    const float sigma = a.sigma[r];
+    if (sigma > 0.f) {
+        const int64_t n_abs = a.N0 + j0 + jl;
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) {
+            float xr = acc[k].x, xi = acc[k].y;
+            add_awgn(a.seed, r, n_abs + k, sigma, xr, xi);
+            acc[k] = v2f{xr, xi};
+        }
+    }
+
+    if (jl >= cnt) return;
+    char *row = a.out + (size_t)r * a.out_stride + (size_t)(j0 + jl) * BSO;
+    const bool whole = a.aligned16 && jl + kAirPerThread <= cnt;
+    if (BSO == 2) {
+        uint32_t w[kAirPerThread];
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) w[k] = (uint32_t)quant_u8_csdr(acc[k].x) | ((uint32_t)quant_u8_csdr(acc[k].y) << 8);
+        if (whole) {
+            *(uint4 *)row = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((uint16_t *)row)[k] = (uint16_t)w[k];
+        }
+    } else {
+        if (whole) {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k += 2) ((float4 *)row)[k >> 1] = make_float4(acc[k].x, acc[k].y, acc[k + 1].x, acc[k + 1].y);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((float2 *)row)[k] = make_float2(acc[k].x, acc[k].y);
+        }
+    }
+}
+
+// the call's last min(n, ring) samples of transmitter blockIdx.y -> ring[absolute index & mask]
+template <typename S>
+__global__ __launch_bounds__(kAirThreads) void air_carry_kernel(AirArgs a)
+{
+    const int t = blockIdx.y;
+    const AirRing rg = a.rings[t];
+    const int64_t R = (int64_t)rg.mask + 1;
+    const int64_t count = a.n < R ? a.n : R;
+    const S *row = (const S *)(a.in + (size_t)t * a.in_stride);
+    S *ring = (S *)a.ring + rg.off;
+    for (int64_t i = (int64_t)blockIdx.x * kAirThreads + threadIdx.x; i < count; i += (int64_t)gridDim.x * kAirThreads) {
+        const int64_t s = a.n - count + i;
+        ring[(uint64_t)(a.N0 + s) & rg.mask] = row[s];
+    }
+}
+
+bool sigma_ok(const float *sigma, int nrx)
+{
+    for (int r = 0; sigma && r < nrx; r++) if (!std::isfinite(sigma[r]) || sigma[r] < 0.f) return false;
+    return true;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pirip_hip_air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path *paths, const float *sigma,
+                         uint64_t seed, int device, pirip_hip_air **out)
+{
+    if (!out) return PIRIP_ERR_BAD_ARG;
+    *out = nullptr;
+    if (Fs < 2 || ntx < 1 || nrx < 1 || npaths < 0 || (npaths > 0 && !paths)) return PIRIP_ERR_BAD_ARG;
+    if (in_format != PIRIP_IN_CU8_CSDR && in_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
+    if (out_format != PIRIP_IN_CU8_CSDR && out_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
+    int max_delay = 0;
+    for (int p = 0; p < npaths; p++) {
+        const pirip_air_path &q = paths[p];
+        const int64_t f2 = 2 * (int64_t)q.offset_hz;
+        if (q.rx < 0 || q.rx >= nrx || q.tx < 0 || q.tx >= ntx || q.delay < 0 || f2 <= -(int64_t)Fs || f2 >= (int64_t)Fs) return PIRIP_ERR_BAD_ARG;
+        if (!std::isfinite(q.gain)) return PIRIP_ERR_BAD_ARG;
+        if (q.delay > max_delay) max_delay = q.delay;
+    }
+    if (!sigma_ok(sigma, nrx)) return PIRIP_ERR_BAD_ARG;
+    if (Fs > kMaxFs || max_delay > kAirMaxDelay || ntx > 65535 || nrx > 65535) return PIRIP_ERR_UNSUPPORTED;
+    const U8Split u8 = csdr_u8_split();
+    if (!u8.exact) return PIRIP_ERR_UNSUPPORTED;
+    int dev = 0;
+    PIRIP_TRY(select_device(device, &dev));
+    pirip_hip_air *h = new (std::nothrow) pirip_hip_air();
+    if (!h) return PIRIP_ERR_NOMEM;
+    h->device = dev;
+    h->Fs = Fs; h->ntx = ntx; h->nrx = nrx; h->npaths = npaths; h->in_format = in_format; h->out_format = out_format;
+    h->bsi = bytes_per_sample(in_format); h->bso = bytes_per_sample(out_format);
+    h->max_delay = max_delay; h->seed = seed; h->u8 = u8;
+    // the paths of every receiver, ascending; every transmitter's ring: the smallest power of two that holds its longest delay
+    std::vector<int32_t> rx_start(1, 0);
+    std::vector<AirPath> sorted;
+    std::vector<int32_t> longest((size_t)ntx, 0);
+    for (int r = 0; r < nrx; r++) {
+        for (int p = 0; p < npaths; p++) {
+            if (paths[p].rx != r) continue;
+            sorted.push_back(AirPath{paths[p].tx, paths[p].delay, (int32_t)fs_residue(paths[p].offset_hz, Fs), paths[p].gain});
+            if (paths[p].delay > longest[(size_t)paths[p].tx]) longest[(size_t)paths[p].tx] = paths[p].delay;
+        }
+        rx_start.push_back((int32_t)sorted.size());
+    }
+    std::vector<AirRing> rings((size_t)ntx);
+    uint64_t total = 0;
+    for (int t = 0; t < ntx; t++) {
+        uint32_t R = kAirMinRing;
+        while (R < (uint32_t)longest[(size_t)t]) R <<= 1;
+        rings[(size_t)t] = AirRing{total, R - 1u, 0u};
+        if ((int)R > h->max_ring) h->max_ring = (int)R;
+        total += R;
+    }
+    std::vector<float> sg((size_t)nrx, 0.f);
+    for (int r = 0; sigma && r < nrx; r++) sg[(size_t)r] = sigma[r];
+    auto tables = [&]() -> int {
+        DevMem &m = h->mem;
+        PIRIP_TRY(m.alloc_filled(&h->d_ring, 0, (size_t)total * (size_t)h->bsi));
+        PIRIP_TRY(m.upload(&h->d_rings, rings.data(), sizeof(AirRing) * rings.size()));
+        PIRIP_TRY(m.upload(&h->d_rx_start, rx_start.data(), sizeof(int32_t) * rx_start.size()));
+        PIRIP_TRY(m.upload(&h->d_paths, sorted.data(), sizeof(AirPath) * sorted.size()));
+        PIRIP_TRY(m.upload(&h->d_sigma, sg.data(), sizeof(float) * sg.size()));
+        return PIRIP_OK;
+    };
+    const int rc = tables();
+    if (rc != PIRIP_OK) { delete h; return rc; }
+    *out = h;
+    return PIRIP_OK;
+}
+
+int pirip_hip_air_destroy(pirip_hip_air *air) { return destroy_handle(air, air ? air->device : 0); }
+
+int pirip_hip_air_get_info(const pirip_hip_air *air, pirip_air_info *info)
+{
+    if (!air || !info) return PIRIP_ERR_BAD_ARG;
+    *info = pirip_air_info{air->Fs, air->ntx, air->nrx, air->npaths, air->in_format, air->out_format, air->max_delay, air->device};
+    return PIRIP_OK;
+}
+
+int pirip_hip_air_set_sigma(pirip_hip_air *air, const float *sigma, void *hip_stream)
+{
+    if (!air || !sigma || !sigma_ok(sigma, air->nrx)) return PIRIP_ERR_BAD_ARG;
+    if (!bind_device(air->device)) return PIRIP_ERR_NO_DEVICE;
+    PIRIP_HIPCHK(hipMemcpyAsync(air->d_sigma, sigma, sizeof(float) * (size_t)air->nrx, hipMemcpyHostToDevice, (hipStream_t)hip_stream));
+    return PIRIP_OK;
+}
+
+int pirip_hip_air_push(pirip_hip_air *air, const void *d_in, size_t in_stride_bytes, int64_t n, void *d_out, size_t out_stride_bytes,
+                       void *hip_stream)
+{
+    if (!air || !d_in || !d_out || n < 1) return PIRIP_ERR_BAD_ARG;
+    PIRIP_TRY(iq_rows_check(d_in, in_stride_bytes, air->bsi, air->ntx, n));
+    PIRIP_TRY(iq_rows_check(d_out, out_stride_bytes, air->bso, air->nrx, n));
+    if (n >= kAirMaxIndex || air->pos + n >= kAirMaxIndex) return PIRIP_ERR_UNSUPPORTED;
+    const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(air->ntx - 1) * in_stride_bytes + (size_t)n * (size_t)air->bsi;
+    const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(air->nrx - 1) * out_stride_bytes + (size_t)n * (size_t)air->bso;
+    if (i0 < o1 && o0 < i1) return PIRIP_ERR_BAD_ARG;
+    const int64_t ntiles = (n + kAirTile - 1) / kAirTile;
+    if (ntiles > 0x7fffffff) return PIRIP_ERR_UNSUPPORTED;
+    if (!bind_device(air->device)) return PIRIP_ERR_NO_DEVICE;
+    AirArgs a{};
+    a.in = (const char *)d_in; a.in_stride = in_stride_bytes;
+    a.out = (char *)d_out; a.out_stride = out_stride_bytes;
+    a.ring = air->d_ring; a.rings = air->d_rings; a.rx_start = air->d_rx_start; a.paths = air->d_paths; a.sigma = air->d_sigma;
+    a.seed = air->seed; a.n = n; a.N0 = air->pos; a.first = air->first;
+    a.n0m = (int32_t)fs_residue(air->pos, air->Fs);
+    a.Fs = air->Fs; a.ntx = air->ntx;
+    a.aligned16 = (((uintptr_t)d_out | out_stride_bytes) & 15) == 0;
+    a.two_over_fs = 2.0f / (float)air->Fs; a.c_hi = air->u8.c_hi; a.c_lo = air->u8.c_lo;
+    a.inv_fs_d = 1.0 / (double)air->Fs;
+    hipStream_t st = (hipStream_t)hip_stream;
+    const dim3 grid((unsigned)ntiles, (unsigned)air->nrx);
+    const size_t lds = (size_t)kAirTile * (size_t)air->bsi + 64;
+    if (air->bsi == 2 && air->bso == 2) hipLaunchKernelGGL((air_mix_kernel<2, 2>), grid, dim3(kAirThreads), lds, st, a);
+    else if (air->bsi == 2) hipLaunchKernelGGL((air_mix_kernel<2, 8>), grid, dim3(kAirThreads), lds, st, a);
+    else if (air->bso == 2) hipLaunchKernelGGL((air_mix_kernel<8, 2>), grid, dim3(kAirThreads), lds, st, a);
+    else hipLaunchKernelGGL((air_mix_kernel<8, 8>), grid, dim3(kAirThreads), lds, st, a);
+    // the carry: as many workgroups per transmitter as the longest ring and the call ask for (at most 64, which stride)
+    const int64_t most = n < (int64_t)air->max_ring ? n : (int64_t)air->max_ring;
+    int64_t cblocks = (most + kAirThreads - 1) / kAirThreads;
+    if (cblocks > 64) cblocks = 64;
+    const dim3 cgrid((unsigned)cblocks, (unsigned)air->ntx);
+    if (air->bsi == 2) hipLaunchKernelGGL(air_carry_kernel<uint16_t>, cgrid, dim3(kAirThreads), 0, st, a);
+    else hipLaunchKernelGGL(air_carry_kernel<float2>, cgrid, dim3(kAirThreads), 0, st, a);
+    if (hipGetLastError() != hipSuccess) return PIRIP_ERR_HIP;
+    air->pos += n;
+    return PIRIP_OK;
+}
+
+int pirip_hip_air_reset(pirip_hip_air *air, int64_t n0, void *hip_stream)
+{
+    (void)hip_stream;                                                   // nothing to enqueue: the rings are masked by the index of the reset
+    if (!air || n0 < 0) return PIRIP_ERR_BAD_ARG;
+    if (n0 >= kAirMaxIndex) return PIRIP_ERR_UNSUPPORTED;
+    air->pos = air->first = n0;
+    return PIRIP_OK;
+}
+
+}  // extern "C"

@@ -1,5 +1,6 @@
-// pirip_amd/csrc/noise_device.hpp -- the product's noise source on the device, shared by the synthetic transmitter (synth_kernels.hip) and the
-// batch transmitter (tx_kernels.hip): equal keys give equal bytes in both (tests/test_tx_noise.py; their quantiser is iq_device.hpp's quant_u8).
+// pirip_amd/csrc/noise_device.hpp -- the product's noise source on the device, shared by the synthetic transmitter (synth_kernels.hip), the
+// batch transmitter (tx_kernels.hip) and the channel (air_kernels.hip): equal keys give equal samples in all three (tests/test_tx_noise.py,
+// tests/test_air.py; the transmitters' quantiser is iq_device.hpp's quant_u8, the channel's quant_u8_csdr).
 // AWGN: sigma * N(0,1) per component from a counter-based generator -- SplitMix64 finaliser of (seed, stream, sample) -> two uniforms
 // -> Box-Muller; it is not meant to reproduce any CPU generator.
 #pragma once
