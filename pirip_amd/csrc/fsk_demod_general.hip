@@ -686,6 +686,11 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
                 }
             }
             float sig = 0.f, nse = 0.f, mean_e = 0.f, std_e = 0.f;
+            // EXACT == 2: the symbols' power terms for the serial sums below, two rows of Nsym floats in the dead fdc -- BEHIND the Nbits
+            // bytes of bits_l: fdc shares the FFT work array with them where it fits ((Nsym + 2) Ts <= Ndft: short frames), and a row
+            // starting at fdc[0] overwrote the staged bits of this very loop before the pack loop read them
+            // ((Nbits + 3) / 4 + 2 Nsym floats <= 2 Nmem: Nbits <= 2 Nsym, Ts >= 4)
+            float *pw = (float *)L.fdc + (d.Nbits + 3) / 4;
             for (int i = tid; i < Nsym; i += NT) {
                 const int st = (i + 1) * P;
                 float tmax[kMaxTones] = {0.f, 0.f, 0.f, 0.f};
@@ -716,7 +721,7 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
                 nse += (sum - mx) / (float)(M - 1);
                 std_e += mx;
                 mean_e += sqrtf(mx);
-                if (EXACTALL) { ((float *)L.fdc)[i] = mx; ((float *)L.fdc)[Nsym + i] = (sum - mx) / (float)(M - 1); }   // (the timing terms there are dead)
+                if (EXACTALL) { pw[i] = mx; pw[Nsym + i] = (sum - mx) / (float)(M - 1); }   // (the timing terms there are dead)
             }
             if (bits_o && d.pack_bits) {
                 __syncthreads();
@@ -734,8 +739,8 @@ __device__ __forceinline__ void fsk_demod_general_body(const DemodArgs &a)
                 if (tid == 0) {
                     float rs = 0.0f, rn = 1e-12f, me = 0.0f, se = 0.0f;
                     for (int i = 0; i < Nsym; i++) {
-                        const float mxv = ((float *)L.fdc)[i];
-                        rs += mxv; rn += ((float *)L.fdc)[Nsym + i];
+                        const float mxv = pw[i];
+                        rs += mxv; rn += pw[Nsym + i];
                         se += mxv; me += sqrtf(mxv);
                     }
                     red[0] = rs; red[1] = rn; red[2] = me; red[3] = se;

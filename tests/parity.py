@@ -8,11 +8,11 @@ SNR_TOL = 2e-3            # relative, SNRest (ratio of two reductions)
 TIMING_TOL = 5e-5         # absolute, norm_rx_timing in symbols: the oracle's recursive timing phasor drifts ~1e-5 over 1224 steps
 
 
-def _pair(ob, c, fmt_o, fmt_h, nstreams=1, mask=0):
+def _pair(ob, c, fmt_o, fmt_h, nstreams=1, mask=0, Nsym=50):
     import pirip_amd
-    o = ob.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"],
+    o = ob.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], Nsym=Nsym, est_min=c["est_min"], est_max=c["est_max"],
                      tone_spacing=mask if mask else 100, mask=bool(mask))
-    h = pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"],
+    h = pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], Nsym=Nsym, est_min=c["est_min"], est_max=c["est_max"],
                            mask=mask, in_format=fmt_h, nstreams=nstreams)
     return o, h
 

@@ -29,6 +29,27 @@ def test_four_hundred_random_draws_have_nothing_unexplained(oracle, built_lib):
     assert counts.get("exact", 0) > 300 and {"wave", "block", "general"} <= kernels
 
 
+def test_sixty_random_frame_lengths_have_nothing_unexplained(oracle, built_lib):
+    """draw_nsym: the configurations of draw() at frame lengths of 9 .. 130 symbols per call (short and long ones weighted), all on the
+    general kernel -- tests/test_frame_lengths.py holds the chosen rows, this the ones nobody chose."""
+    import fuzz_parity
+    import pirip_amd
+    import sigutil
+    import test_gpu_parity as cmp
+    counts, kernels, fails = {}, set(), []
+    for seed in range(2600000, 2600060):
+        cfg = fuzz_parity.draw_nsym(seed)
+        res, msg, kern = fuzz_parity.run_one(cfg, oracle, pirip_amd, sigutil, cmp)
+        counts[res] = counts.get(res, 0) + 1
+        if kern:
+            kernels.add(kern)
+        if res == "FAIL":
+            fails.append((seed, cfg, msg))
+    print(counts)
+    assert not fails, fails[:3]
+    assert counts.get("exact", 0) >= 40 and counts.get("skipped", 0) <= 6 and kernels == {"general"}
+
+
 def test_two_thousand_random_decimator_draws_are_bit_exact(oracle, built_lib):
     """csdr front end: random decimation, tap count, stream count, length, byte alignment and stride; f32 and s16 outputs bit for bit."""
     import fuzz_parity

@@ -56,12 +56,25 @@ def draw(seed):
                     nframes=int(rng.integers(30, 120)), pieces=int(rng.integers(1, 5)), seed=seed)
 
 
+def draw_nsym(seed):
+    """a draw() configuration plus a frame length (Nsym, the symbols per demodulator call) from 9 .. 130, weighted to the short frames
+    (9 .. 24: one wave per stream, few or no estimator FFTs per frame) and the long ones (100 .. 130: the wide workgroup, direct input at
+    large Ts); the recording is kept to about 150 k samples. Any value but the compiled 50 runs on the general kernel."""
+    cfg = draw(seed)
+    rng = np.random.default_rng(seed + 3)
+    u = rng.random()
+    cfg["Nsym"] = int(rng.integers(9, 25)) if u < 0.4 else int(rng.integers(100, 131)) if u < 0.8 else int(rng.integers(9, 131))
+    cfg["nframes"] = min(cfg["nframes"], max(8, 150000 // ((cfg["Fs"] // cfg["Rs"]) * cfg["Nsym"])))
+    return cfg
+
+
 def run_one(cfg, ob, A, sigutil, cmp):
     rng = np.random.default_rng(cfg["seed"] + 1)
     Fs, Rs, M, P = cfg["Fs"], cfg["Rs"], cfg["M"], cfg["P"]
     Ts = Fs // Rs
+    Nsym = cfg.get("Nsym", 50)                               # (draw_nsym: the receiver's frame length; the transmitter keeps its own)
     c = dict(Fs=Fs, Rs=Rs, M=M, P=P, f1=cfg["f1"], shift=cfg["shift"], est_min=Rs // 2, est_max=min(Fs // 2 - Rs, cfg["f1"] + M * cfg["shift"] + 2 * Rs))
-    bits = rng.integers(0, 2, cfg["nframes"] * 50 * (1 if M == 2 else 2)).astype(np.uint8)
+    bits = rng.integers(0, 2, cfg["nframes"] * Nsym * (1 if M == 2 else 2)).astype(np.uint8)
     x = sigutil.mod_complex(ob, c, bits)[int(rng.integers(0, Ts)):]
     if cfg["ebno"] is not None:
         x = sigutil.add_awgn(x, cfg["ebno"], c, rng)
@@ -81,9 +94,9 @@ def run_one(cfg, ob, A, sigutil, cmp):
     else:
         buf = np.ascontiguousarray(x, dtype=np.float32); fo, fh = ob.IN_CF32, A.IN_CF32
     mask = cfg["mask"]
-    o = ob.OracleFsk(Fs, Rs, M, P=P, est_min=c["est_min"], est_max=c["est_max"], tone_spacing=mask if mask else 100, mask=bool(mask))
+    o = ob.OracleFsk(Fs, Rs, M, P=P, Nsym=Nsym, est_min=c["est_min"], est_max=c["est_max"], tone_spacing=mask if mask else 100, mask=bool(mask))
     try:
-        h = A.HipDemod(Fs, Rs, M, P=P, est_min=c["est_min"], est_max=c["est_max"], mask=mask, in_format=fh, nstreams=1)
+        h = A.HipDemod(Fs, Rs, M, P=P, Nsym=Nsym, est_min=c["est_min"], est_max=c["est_max"], mask=mask, in_format=fh, nstreams=1)
     except A.PiripError as e:
         return "skipped", str(e), None
     kern = h.kernel()
@@ -98,7 +111,7 @@ def run_one(cfg, ob, A, sigutil, cmp):
           "bits": np.concatenate([p["bits"] for p in parts]), "rx_filt": np.concatenate([p["rx_filt"] for p in parts]),
           "stats": np.concatenate([p["stats"] for p in parts])}
     h.close()
-    tol = cmp.RX_FILT_TOL * max(1.0, Ts * 50 / 2400.0)
+    tol = cmp.RX_FILT_TOL * max(1.0, Ts * Nsym / 2400.0)
     note = None
     n = min(rh["nframes"], ro["nframes"])
     nin_o, nin_h = ro["stats"][:n, 6], rh["stats"][:n, 6]
@@ -485,6 +498,7 @@ def main():
     ap.add_argument("--ldpc", action="store_true", help="fuzz the FSK_LDPC receiver (records bit-exact against the mirror oracle) instead of the demodulator")
     ap.add_argument("--decimator", action="store_true", help="fuzz the csdr front end (u8 -> decimated f32 / s16, bit-exact) instead of the demodulator")
     ap.add_argument("--tx", action="store_true", help="fuzz the batch transmitter (section I): framer against the tool and H, modulator and noise against their float64 statements")
+    ap.add_argument("--nsym", action="store_true", help="draw the frame length too (draw_nsym: 9 .. 130 symbols per call, all on the general kernel)")
     ap.add_argument("--minutes", type=float, default=10.0)
     ap.add_argument("--seed0", type=int, default=1)
     ap.add_argument("--max-draws", type=int, default=1 << 30)
@@ -498,7 +512,7 @@ def main():
     seed = a.seed0
     print(f"# tools/fuzz_parity.py --minutes {a.minutes} --seed0 {a.seed0}: one line per draw that is not an exact pass")
     while time.time() - t0 < a.minutes * 60 and seed - a.seed0 < a.max_draws:
-        cfg = draw(seed)
+        cfg = draw_nsym(seed) if a.nsym else draw(seed)
         try:
             if a.decimator:
                 res, msg = decim_one(seed, ob, A); kern = "decim"
