@@ -282,7 +282,11 @@ int pirip_hip_decim_taps(const pirip_hip_decim *d, float *taps, int *ntaps);   /
  * float32 result bit for bit. OPT-IN measurement variants (also PIRIP_DECIM_FMA=1 / 2 at create): 1 = the same conversion, the
  * accumulation fused (acc = fma(y, h, acc)); 2 = the affine u8 map pulled out of the sum (acc = fma(byte, h, acc), y = acc/127.5 - sum h).
  * Upstream csdr is built -O3 -ffast-math [UPSTREAM-RECALLED]: which float32 result the shipped binary produces is a property of that
- * build's vectoriser, so neither variant is "wrong" a priori -- they are simply not what oracle/csdr_oracle.c states. */
+ * build's vectoriser, so neither variant is "wrong" a priori -- they are simply not what oracle/csdr_oracle.c's scalar loop states.
+ * What each computes is pinned bit for bit (oracle_fir_decimate_cc_arith, tests/test_switches.py): sums in ascending tap order from
+ * zero; 2 ends with y = fmaf(acc, c, -tap_sum), c = the float sum of the two constants of the exact u8 conversion (1/127.5 rounded),
+ * tap_sum = the float of the taps' double sum. A stream whose first byte sits at an odd address takes the table loop whatever the
+ * mode: its outputs are those of mode 0. With PIRIP_DECIM_LUT set at create every stream does, and modes 1 and 2 are PIRIP_ERR_UNSUPPORTED. */
 #define PIRIP_DECIM_EXACT   0
 #define PIRIP_DECIM_FMA     1
 #define PIRIP_DECIM_FMA_RAW 2
@@ -348,6 +352,11 @@ int pirip_hip_ldpc_reset(pirip_hip_ldpc *h, void *hip_stream);
  * as IEEE binary16 -- written by the LLR stage or by the demodulator's fused hand-over alike. A checking aid: the fused path keeps no
  * other copy of them. */
 int pirip_hip_ldpc_get_llr_history(pirip_hip_ldpc *h, int s, uint16_t *host_llr);
+/* A checking aid: the storage layout the fast and persistent decoders run on (searched at create, PIRIP_LAYOUT_TRIES moves; 0 keeps the
+ * identity layout) as its bank conflicts -- extra LDS cycles per decoder iteration of the identity layout and of the layout in use. The
+ * layout moves where values are stored, never the order of a sum: decoded words do not depend on it. PIRIP_ERR_UNSUPPORTED: the code
+ * has no such layout (the generic decoder serves it). */
+int pirip_hip_ldpc_get_layout_conflicts(const pirip_hip_ldpc *h, int *identity, int *in_use);
 /* Stream s consumes `ncalls` demodulator frames of soft decisions d_rx_filt + s*filt_stride (floats; each frame is
  * M*Nsym magnitudes in fsk_demod_sd() layout [m][sym] = pirip_hip_demod_batch's d_rx_filt); d_ncalls[s] (or NULL = all)
  * says how many of them are valid (d_nframes of the demodulator): the receiver advances by exactly that many calls -- the

@@ -52,6 +52,10 @@ def _load():
     lib.oracle_firdes_lowpass_f_hamming.argtypes = [C.c_void_p, C.c_int, C.c_float]
     lib.oracle_fir_decimate_cc.restype = C.c_int
     lib.oracle_fir_decimate_cc.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.oracle_fir_decimate_cc_arith.restype = C.c_int
+    lib.oracle_fir_decimate_cc_arith.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    lib.kiss_fft_oracle_set_fused_mul.argtypes = [C.c_int]
+    lib.kiss_fft_oracle_get_fused_mul.restype = C.c_int
     lib.oracle_csdr_fir_decimate_stream.restype = C.c_long
     lib.oracle_csdr_fir_decimate_stream.argtypes = [C.c_void_p, C.c_long, C.c_void_p, C.c_long,
                                                     C.c_int, C.c_float, C.c_int]
@@ -188,6 +192,42 @@ def quantise_cu8(x_c, amp=32.0):
     the reference has no synthetic u8 generator: SURVEY.md 8d cfg 1)."""
     q = np.rint(127.0 + amp * x_c.astype(np.float64))
     return np.clip(q, 0, 255).astype(np.uint8)
+
+
+def set_fft_fused(on):
+    """Process-wide: the estimator FFT's twiddle multiply as the product's opt-in 'fused FFT multiply' computes it (kiss_fft_oracle.c).
+    Whoever turns it on turns it off again."""
+    lib().kiss_fft_oracle_set_fused_mul(1 if on else 0)
+
+
+def decim_taps(D, transition_bw=0.05):
+    """(taps padded with zeros to a multiple of 4, the way `csdr fir_decimate_cc D tbw` holds them; number of designed taps)"""
+    L = lib()
+    ntaps = int(L.oracle_firdes_filter_len(transition_bw))
+    tp = np.zeros(ntaps + 3 - (ntaps + 3) % 4, dtype=np.float32)
+    L.oracle_firdes_lowpass_f_hamming(_p(tp), ntaps, 0.5 / D)
+    return tp, ntaps
+
+
+def decim_u8(u8, D, transition_bw=0.05, mode=0, out_s16=False):
+    """convert_u8_f | fir_decimate_cc D tbw [| convert_f_s16] of u8 IQ [n, 2] in tap-loop arithmetic `mode` (0: the scalar csdr
+    loop, 1 / 2: the product's opt-in fma arithmetics; oracle_fir_decimate_cc_arith). Returns [n_out, 2] float32 or int16."""
+    u8 = np.ascontiguousarray(u8, dtype=np.uint8)
+    n_in = u8.shape[0]
+    tp, _ = decim_taps(D, transition_bw)
+    y = np.zeros((max(0, (n_in - len(tp)) // D + 1), 2), dtype=np.float32)
+    if mode == 0:        # the three csdr stages as every other test chains them (the restatement's mode 0 is held equal to it on the CPU)
+        f = np.zeros(u8.shape, dtype=np.float32)
+        lib().oracle_convert_u8_f(_p(u8), _p(f), u8.size)
+        n_out = lib().oracle_fir_decimate_cc(_p(f), _p(y), n_in, D, _p(tp), len(tp))
+    else:
+        n_out = lib().oracle_fir_decimate_cc_arith(mode, _p(u8), _p(y), n_in, D, _p(tp), len(tp))
+    assert n_out == y.shape[0], (n_out, y.shape)
+    if not out_s16:
+        return y
+    s16 = np.zeros(y.shape, dtype=np.int16)
+    lib().oracle_convert_f_s16(_p(y), _p(s16), y.size)
+    return s16
 
 
 # ---- FSK_LDPC (oracle/ldpc_oracle.c) --------------------------------------------------------------------------------

@@ -70,6 +70,41 @@ int oracle_fir_decimate_cc(const float *input, float *output, int input_size, in
     return oi;
 }
 
+/* convert_u8_f | fir_decimate_cc on u8 IQ in one of the product's three documented tap-loop arithmetics (include/pirip_hip.h section B,
+ * pirip_hip_decim_set_arith) -- restated from those formulas, not from csdr. fmaf is libm's: independent of -ffp-contract.
+ *   0  y = convert_u8_f(byte); acc += y * h              (the scalar csdr loop: oracle_fir_decimate_cc on the converted samples)
+ *   1  y = convert_u8_f(byte); acc = fmaf(y, h, acc)
+ *   2  acc = fmaf((float)byte, h, acc); y = fmaf(acc, c, -tap_sum), c = (float)(c_hi + c_lo) with c_hi = 1/127.5 rounded to a multiple
+ *      of 2^-22 and c_lo = (float)(1/127.5 - c_hi); tap_sum = (float)(the double sum of the taps)
+ * every sum in ascending tap order from zero, I and Q separately. */
+int oracle_fir_decimate_cc_arith(int mode, const unsigned char *input, float *output, int input_size, int decimation,
+                                 const float *taps, int taps_length)
+{
+    const float c_hi = (float)(nearbyint((1.0 / 127.5) * 4194304.0) / 4194304.0);
+    const float c_lo = (float)(1.0 / 127.5 - (double)c_hi);
+    const float c = c_hi + c_lo;
+    double hs = 0.0;
+    for (int ti = 0; ti < taps_length; ti++) hs += (double)taps[ti];
+    const float tap_sum = (float)hs;
+    if (mode < 0 || mode > 2) return -1;
+    int oi = 0;
+    for (int i = 0; i < input_size; i += decimation) {
+        if (i + taps_length > input_size) break;
+        float acc[2] = {0, 0};
+        for (int ti = 0; ti < taps_length; ti++)
+            for (int q = 0; q < 2; q++) {
+                const unsigned char b = input[2 * (i + ti) + q];
+                const float y = ((float)b) / (UCHAR_MAX / 2.0) - 1.0;
+                if (mode == 0) acc[q] += y * taps[ti];
+                else if (mode == 1) acc[q] = fmaf(y, taps[ti], acc[q]);
+                else acc[q] = fmaf((float)b, taps[ti], acc[q]);
+            }
+        for (int q = 0; q < 2; q++) output[2 * oi + q] = mode == 2 ? fmaf(acc[q], c, -tap_sum) : acc[q];
+        oi++;
+    }
+    return oi;
+}
+
 /* [UPSTREAM-RECALLED csdr.c: "fir_decimate_cc" command loop] */
 long oracle_csdr_fir_decimate_stream(const float *in_c, long nsamp, float *out_c, long max_out,
                                      int decimation, float transition_bw, int bufsize)

@@ -16,6 +16,10 @@ void oracle_firdes_lowpass_f_hamming(float *output, int length, float cutoff_rat
 /* complex in/out as interleaved float pairs; returns number of outputs written */
 int  oracle_fir_decimate_cc(const float *input, float *output, int input_size, int decimation,
                             const float *taps, int taps_length);
+/* u8 IQ in, convert_u8_f | fir_decimate_cc in tap-loop arithmetic `mode` (0 exact, 1 fma, 2 fma on the raw bytes: csdr_oracle.c);
+ * returns the number of outputs written, -1 for an unknown mode */
+int  oracle_fir_decimate_cc_arith(int mode, const unsigned char *input, float *output, int input_size, int decimation,
+                                  const float *taps, int taps_length);
 /* Streaming driver restating the buffer loop of `csdr fir_decimate_cc D [tbw]` over a whole
  * buffer: block size the_bufsize (csdr "bigbufs" default 16384), taps padded with zeros to a
  * multiple of 4, overlap carried, trailing partial block dropped. Returns outputs written. */

@@ -27,8 +27,17 @@ struct kiss_fft_oracle_state {
     kiss_fft_oracle_cpx *twiddles;
 };
 
-#define C_MUL(m, a, b) do { (m).r = (a).r * (b).r - (a).i * (b).i; \
-                            (m).i = (a).r * (b).i + (a).i * (b).r; } while (0)
+/* Process-wide: 0 (default) = the multiply as C computes it without contraction, every product and sum rounded once.
+ * 1 = the product's opt-in "fused FFT multiply" (PIRIP_FFT_FMA=1; demod_simd.hpp rot_step): the a.r products rounded, the a.i products
+ * fused into the sum. fmaf from libm, so the result does not depend on -ffp-contract. */
+static int g_fused_mul = 0;
+void kiss_fft_oracle_set_fused_mul(int on) { g_fused_mul = on ? 1 : 0; }
+int kiss_fft_oracle_get_fused_mul(void) { return g_fused_mul; }
+
+#define C_MUL(m, a, b) do { if (g_fused_mul) { const float pr_ = (a).r * (b).r, pi_ = (a).r * (b).i; \
+                                               (m).r = fmaf((a).i, -(b).i, pr_); (m).i = fmaf((a).i, (b).r, pi_); } \
+                            else { (m).r = (a).r * (b).r - (a).i * (b).i; \
+                                   (m).i = (a).r * (b).i + (a).i * (b).r; } } while (0)
 #define C_ADD(res, a, b) do { (res).r = (a).r + (b).r; (res).i = (a).i + (b).i; } while (0)
 #define C_SUB(res, a, b) do { (res).r = (a).r - (b).r; (res).i = (a).i - (b).i; } while (0)
 #define C_ADDTO(res, a) do { (res).r += (a).r; (res).i += (a).i; } while (0)

@@ -1119,6 +1119,13 @@ class HipLdpc:
         _chk(self.L.pirip_hip_ldpc_get_llr_history(self.h, s, out.ctypes.data), "pirip_hip_ldpc_get_llr_history")
         return out
 
+    def layout_conflicts(self):
+        """(identity layout's, layout in use's) bank conflicts per decoder iteration (pirip_hip_ldpc_get_layout_conflicts)."""
+        ident, used = C.c_int(0), C.c_int(0)
+        self.L.pirip_hip_ldpc_get_layout_conflicts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+        _chk(self.L.pirip_hip_ldpc_get_layout_conflicts(self.h, C.byref(ident), C.byref(used)), "pirip_hip_ldpc_get_layout_conflicts")
+        return ident.value, used.value
+
     def rx_batch(self, d_rx_filt, filt_stride, d_ncalls, ncalls, d_status, d_payload, d_info, stream=0):
         _chk(self.L.pirip_hip_ldpc_rx_batch(self.h, d_rx_filt, filt_stride, d_ncalls, ncalls, d_status, d_payload, d_info, stream),
              "pirip_hip_ldpc_rx_batch")

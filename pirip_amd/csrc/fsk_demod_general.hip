@@ -838,10 +838,13 @@ hipError_t launch_demod_general(const DemodArgs &a, int nstreams, hipStream_t st
     // with four -- barriers and the serial pieces stop scaling) unless the frame is too small to feed them
     // long frames (measured at Ts = 240 / Ndft = 4096, profiles/r03_instance_rates.txt): one stream per CU fits, so its workgroup is wide
     int nt = 2 * kWave;
-    if (const char *e = getenv("PIRIP_GENERAL_THREADS")) { const int v = atoi(e); if (v >= 64 && v <= 512 && v % 64 == 0) nt = v; }
-    else if (a.d.N + a.d.nin_step < 512) nt = kWave;
+    if (a.d.N + a.d.nin_step < 512) nt = kWave;
     else if (lds > 80 * 1024) nt = 8 * kWave;
     else if (direct_input(a.d)) nt = 4 * kWave;          // long frames, two streams per CU: 45 G at 256 threads against 27 G at 128, 36 G at 512 (one stream per CU)
+    // PIRIP_GENERAL_THREADS (A/B runs): any whole number of waves up to 512 threads -- the body strides its loops by blockDim.x and adds its
+    // per-wave partials in a plain loop, so each is a supported launch (another rounding of the workgroup sums); any other value is
+    // ignored and the rule above stands
+    if (const char *e = getenv("PIRIP_GENERAL_THREADS")) { const int v = atoi(e); if (v >= 64 && v <= 512 && v % 64 == 0) nt = v; }
     if (nt > 4 * kWave) {
         if (lds > 48 * 1024) {
             hipError_t e = hipFuncSetAttribute((const void *)fsk_demod_general_wide_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -227,6 +227,14 @@ int pirip_hip_ldpc_get_info(const pirip_hip_ldpc *h, pirip_ldpc_info *info)
     return PIRIP_OK;
 }
 
+int pirip_hip_ldpc_get_layout_conflicts(const pirip_hip_ldpc *h, int *identity, int *in_use)
+{
+    if (!h || !identity || !in_use) return PIRIP_ERR_BAD_ARG;
+    if (!h->layout.ok) return PIRIP_ERR_UNSUPPORTED;
+    *identity = h->layout.gather_conflicts_identity; *in_use = h->layout.gather_conflicts;
+    return PIRIP_OK;
+}
+
 int pirip_hip_ldpc_get_llr_history(pirip_hip_ldpc *h, int s, uint16_t *host_llr)
 {
     if (!h || !host_llr || s < 0 || s >= h->nstreams) return PIRIP_ERR_BAD_ARG;
