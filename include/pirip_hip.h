@@ -26,7 +26,7 @@
  *   section L  test-frame counter (pirip_hip_tbits_*)       : fsk_put_test_bits / rtl_fsk --testframes for a batch of streams,
  *              counted on the device behind the demodulator or the receiver.
  *   section O  channel (pirip_hip_air_*)                    : T transmitted wideband IQ streams onto R received ones: paths with
- *              gain, delay and carrier offset, AWGN per receiver, block after block.
+ *              gain, delay, carrier offset and sample-clock offset, AWGN per receiver, block after block.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -931,6 +931,40 @@ int pirip_hip_air_push(pirip_hip_air *air, const void *d_in, size_t in_stride_by
 int pirip_hip_air_reset(pirip_hip_air *air, int64_t n0, void *hip_stream);
 /* One HIP stream per handle: the rings and sigma are device state advanced in stream order, the absolute index is host state advanced
  * when a call is enqueued. */
+
+/* ---- section O, drift: a path whose two ends run on sample clocks that disagree. Only symbols are added: the entry
+ * points above, their handles' launches and PIRIP_HIP_ABI_VERSION stand as they are. */
+typedef struct pirip_air_path_ex { int32_t rx, tx, delay, offset_hz; float gain; int32_t clock_ppb; } pirip_air_path_ex;
+/* pirip_hip_air_create with a clock offset q = clock_ppb per path, in parts per billion (q > 0: the transmitter's clock runs fast as the
+ * receiver sees it), and max_slip, the largest whole-sample slip |S| any path may reach. A path with q = 0 is a path of
+ * pirip_hip_air_create, bit for bit, and a handle without a drifting path makes that function's launches. With Q = 10^9, n_r the index of
+ * the last reset and m = age0 + (n - n_r) the clock age (age0 = 0 after create and pirip_hip_air_reset):
+ *     S(m) = floor(m q / Q) (toward -inf),  rho(m) = m q - Q S(m) in [0, Q),  i = n - d_p + S(m),  phi = floor(1024 rho / Q)
+ *     v_p[n] = sum_{k = 0 .. 15} T[phi][k] x_{t_p}[i - 7 + k]      per component from 0 in ascending k as acc = fma(T, x, acc)
+ * and v_p takes the place of x_{t_p}[n - d_p] in y_r[n]: rotated by the same exact integer phase of n where f_p != 0, then
+ * acc_r = fma(a_p, v, acc_r). x_t[j] = 0 for j < n_r by index, as above. T: pirip_hip_air_interp_table. Integers throughout: S, rho and phi
+ * are exact, so every sample stays a function of the absolute index, the clock age of the reset, its receiver's paths and the input, and
+ * any cutting into calls gives the one-shot output bit for bit.
+ * The slip budget: both ends get n samples per call, so a drifting path eats its delay (q > 0) or the ring (q < 0). For every path with
+ * q != 0: PIRIP_ERR_BAD_ARG unless max_slip >= 1 and d_p >= 8 + (q > 0 ? max_slip : 0) (the taps never reach past sample n);
+ * PIRIP_ERR_UNSUPPORTED for d_p + 7 + (q < 0 ? max_slip : 0) > 2^20 or |q| > 10^6. max_slip < 0 is PIRIP_ERR_BAD_ARG. A transmitter's ring
+ * is the smallest power of two, at least 64, that holds its paths' longest lag, slip and the 7 leading taps included.
+ * pirip_hip_air_push returns PIRIP_ERR_UNSUPPORTED, enqueues nothing and changes no state when the call's last sample would take a path's
+ * |S| past max_slip (q > 0: m q < (max_slip + 1) Q; q < 0: m |q| <= max_slip Q). pirip_air_info.max_delay stays the longest delay field. */
+int pirip_hip_air_create_ex(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths,
+                            const float *sigma, uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out);
+/* The interpolator's table, the very floats the kernel uses: taps [1024][16] (host), T[phi][k] = sinc(k - 7 - mu) w((k - 7 - mu) / 8) with
+ * mu = phi / 1024 and w the Kaiser window of beta 6, w(u) = I0(beta sqrt(1 - u^2)) / I0(beta), every phase divided by its own sum (DC gain
+ * 1), computed in double and rounded once to float; phase 0 is the exact unit impulse at k = 7. *nphases = 1024, *ntaps = 16 (either may be
+ * NULL). Host only: no device is looked for. PIRIP_ERR_BAD_ARG for taps NULL. */
+int pirip_hip_air_interp_table(float *taps, int *nphases, int *ntaps);
+/* Host state, no synchronisation: max_slip, and how many more samples pirip_hip_air_push will take (the slip budget of a handle with a
+ * drifting path, and the absolute index below 2^53). Either pointer may be NULL. */
+int pirip_hip_air_get_drift(const pirip_hip_air *air, int32_t *max_slip, int64_t *samples_left);
+/* pirip_hip_air_reset with a clock age: the next sample has absolute index n0 and clock age age0, so a long run resumes where a budget
+ * ended (with the delays moved by S) or starts anywhere inside it. PIRIP_ERR_BAD_ARG for n0 or age0 < 0; PIRIP_ERR_UNSUPPORTED for either
+ * from 2^53, or an age0 that already breaks the budget. */
+int pirip_hip_air_reset_drift(pirip_hip_air *air, int64_t n0, int64_t age0, void *hip_stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

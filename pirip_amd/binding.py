@@ -84,6 +84,11 @@ class AirPath(C.Structure):
     _fields_ = [("rx", C.c_int32), ("tx", C.c_int32), ("delay", C.c_int32), ("offset_hz", C.c_int32), ("gain", C.c_float)]
 
 
+class AirPathEx(C.Structure):
+    """pirip_air_path_ex: AirPath and the path's clock offset in parts per billion"""
+    _fields_ = AirPath._fields_ + [("clock_ppb", C.c_int32)]
+
+
 class AirInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("Fs", "ntx", "nrx", "npaths", "in_format", "out_format", "max_delay", "device")]
 
@@ -248,6 +253,10 @@ def lib():
     L.pirip_hip_air_set_sigma.argtypes = [vp, vp, vp]
     L.pirip_hip_air_push.argtypes = [vp, vp, sz, i64, vp, sz, vp]
     L.pirip_hip_air_reset.argtypes = [vp, i64, vp]
+    L.pirip_hip_air_create_ex.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, C.c_uint64, C.c_int32, i32, C.POINTER(vp)]
+    L.pirip_hip_air_interp_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
+    L.pirip_hip_air_get_drift.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
+    L.pirip_hip_air_reset_drift.argtypes = [vp, i64, i64, vp]
     _lib = L
     return L
 
@@ -1003,26 +1012,41 @@ class HipAir:
     samples late and `offset_hz` Hz up; sigma: the noise per component of every received stream (a number, nrx numbers, or None for none),
     keyed by (seed, stream, absolute sample) as HipTx.modulate's; in_format / out_format: IN_CU8_CSDR or IN_CF32. The history of every
     transmitted stream stays on the device: any cutting of a stream into push() calls gives the same output. Pointer arguments take torch
-    tensors or raw device pointers, streams default to torch's current stream."""
+    tensors or raw device pointers, streams default to torch's current stream.
+    Two clocks that disagree: a sixth element or key `clock_ppb` (AirPathEx) is the clock offset of the path's transmitter
+    in parts per billion, fast when positive; such a path is read through the interpolator and may slip max_slip whole samples, of its
+    delay (fast: delay >= 8 + max_slip) or of the ring (slow). drift() says how many samples push() still takes, reset(n0, age=...)
+    resumes at a clock age. Without a clock offset and with max_slip 0 the handle is pirip_hip_air_create's."""
 
-    def __init__(self, Fs, paths, ntx, nrx, sigma=None, seed=1, in_format=IN_CU8_CSDR, out_format=IN_CU8_CSDR, device=-1):
+    def __init__(self, Fs, paths, ntx, nrx, sigma=None, seed=1, in_format=IN_CU8_CSDR, out_format=IN_CU8_CSDR, device=-1, max_slip=0):
         self.L = lib()
         rows = []
         for p in paths:
-            if isinstance(p, AirPath):
+            if isinstance(p, AirPathEx):
+                rows.append((p.rx, p.tx, p.gain, p.delay, p.offset_hz, p.clock_ppb))
+            elif isinstance(p, AirPath):
                 rows.append((p.rx, p.tx, p.gain, p.delay, p.offset_hz))
             elif isinstance(p, dict):
-                rows.append((p["rx"], p["tx"], p.get("gain", 1.0), p.get("delay", 0), p.get("offset_hz", 0)))
+                rows.append((p["rx"], p["tx"], p.get("gain", 1.0), p.get("delay", 0), p.get("offset_hz", 0)) +
+                            ((p["clock_ppb"],) if "clock_ppb" in p else ()))
             else:
                 rows.append(tuple(p))
-        arr = (AirPath * max(len(rows), 1))()
-        for i, (rx, tx, gain, delay, off) in enumerate(rows):
-            arr[i] = AirPath(int(rx), int(tx), int(delay), int(off), float(gain))
         self.paths = rows
         sg = self._sigma(sigma, int(nrx))
         h = C.c_void_p()
-        _chk(self.L.pirip_hip_air_create(int(Fs), int(in_format), int(out_format), int(ntx), int(nrx), len(rows), C.addressof(arr) if rows else None,
-                                         None if sg is None else sg.ctypes.data, int(seed), device, C.byref(h)), "pirip_hip_air_create")
+        common = (int(Fs), int(in_format), int(out_format), int(ntx), int(nrx), len(rows))
+        if int(max_slip) == 0 and not any(len(p) > 5 and int(p[5]) for p in rows):
+            arr = (AirPath * max(len(rows), 1))()
+            for i, (rx, tx, gain, delay, off) in enumerate(p[:5] for p in rows):
+                arr[i] = AirPath(int(rx), int(tx), int(delay), int(off), float(gain))
+            _chk(self.L.pirip_hip_air_create(*common, C.addressof(arr) if rows else None, None if sg is None else sg.ctypes.data, int(seed),
+                                             device, C.byref(h)), "pirip_hip_air_create")
+        else:
+            arr = (AirPathEx * max(len(rows), 1))()
+            for i, p in enumerate(rows):
+                arr[i] = AirPathEx(int(p[0]), int(p[1]), int(p[3]), int(p[4]), float(p[2]), int(p[5]) if len(p) > 5 else 0)
+            _chk(self.L.pirip_hip_air_create_ex(*common, C.addressof(arr) if rows else None, None if sg is None else sg.ctypes.data, int(seed),
+                                                int(max_slip), device, C.byref(h)), "pirip_hip_air_create_ex")
         self.h = h
         self.info = AirInfo()
         _chk(self.L.pirip_hip_air_get_info(self.h, C.byref(self.info)), "pirip_hip_air_get_info")
@@ -1061,9 +1085,18 @@ class HipAir:
         sg = self._sigma(0.0 if sigma is None else sigma, self.nrx)
         _chk(self.L.pirip_hip_air_set_sigma(self.h, sg.ctypes.data, _hip_stream(stream)), "pirip_hip_air_set_sigma")
 
-    def reset(self, n0=0, stream=None):
-        """forget the history: the next sample has absolute index n0, every earlier one is zero"""
-        _chk(self.L.pirip_hip_air_reset(self.h, int(n0), _hip_stream(stream)), "pirip_hip_air_reset")
+    def reset(self, n0=0, stream=None, age=0):
+        """forget the history: the next sample has absolute index n0 and clock age `age`, every earlier one is zero"""
+        if age:
+            _chk(self.L.pirip_hip_air_reset_drift(self.h, int(n0), int(age), _hip_stream(stream)), "pirip_hip_air_reset_drift")
+        else:
+            _chk(self.L.pirip_hip_air_reset(self.h, int(n0), _hip_stream(stream)), "pirip_hip_air_reset")
+
+    def drift(self):
+        """(max_slip, how many more samples push() will take): host state, no synchronisation"""
+        ms, left = C.c_int32(0), C.c_int64(0)
+        _chk(self.L.pirip_hip_air_get_drift(self.h, C.byref(ms), C.byref(left)), "pirip_hip_air_get_drift")
+        return ms.value, left.value
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

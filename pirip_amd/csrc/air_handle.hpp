@@ -17,6 +17,13 @@ constexpr int kAirTile = kAirThreads * kAirPerThread;
 constexpr int kAirMaxDelay = 1 << 20;
 constexpr int kAirMinRing = 64;             // samples; a ring is a power of two of them, so that it wraps on a 16-byte unit in both formats
 constexpr int64_t kAirMaxIndex = (int64_t)1 << 53;
+// drifting paths: a polyphase windowed-sinc interpolator of kAirTaps taps at kAirPhases fractional positions
+constexpr int kAirPhases = 1024;
+constexpr int kAirTaps = 16;
+constexpr int kAirLead = kAirTaps / 2 - 1;  // taps in front of the read position: 7
+constexpr int32_t kAirMaxPpb = 1000000;
+// samples of a drifting path's span beyond the tile's: the taps, and S moves by at most 3 across a tile at kAirMaxPpb, plus one
+constexpr int kAirSpanExtra = kAirTaps - 1 + 4 + 1;
 
 // a path as the mix kernel reads it: sorted by receiver, ascending path index within one
 struct AirPath { int32_t tx, delay, fres; float gain; };          // fres = f_p mod Fs in [0, Fs); 0: not rotated
@@ -41,6 +48,13 @@ struct AirArgs {
     double inv_fs_d;
 };
 
+// what a handle with a drifting path passes beside AirArgs (air_mix_drift_kernel only)
+struct AirDrift {
+    const int32_t *ppb;                     // [npaths], in the order of paths: clock offset in parts per billion, 0: a static path
+    const float *taps;                      // [kAirPhases][kAirTaps], the host's table
+    int64_t age;                            // clock age of the call's first sample: age0 + (N0 - first)
+};
+
 }  // namespace pirip
 
 // (hidden: a handle's implicit destructor is no dynamic symbol of the library)
@@ -49,6 +63,10 @@ struct pirip_hip_air {
     int Fs = 0, ntx = 0, nrx = 0, npaths = 0, in_format = 0, out_format = 0, bsi = 0, bso = 0, max_delay = 0, max_ring = 0, device = 0;
     uint64_t seed = 0;
     int64_t pos = 0, first = 0;             // host state: absolute index of the next sample, and of the last reset
+    // drift (4.15a), host state: the clock age of sample `first`, the slip budget and the last clock age that stays inside it
+    int64_t age0 = 0, last_age = 0;
+    int32_t max_slip = 0;
+    bool drift = false;                     // some path has a clock offset: the drift instantiation, its table and its LDS
     pirip::U8Split u8{};
     pirip::DevMem mem;
     char *d_ring = nullptr;
@@ -56,5 +74,7 @@ struct pirip_hip_air {
     int32_t *d_rx_start = nullptr;
     pirip::AirPath *d_paths = nullptr;
     float *d_sigma = nullptr;
+    int32_t *d_ppb = nullptr;
+    float *d_taps = nullptr;
 };
 #pragma GCC visibility pop

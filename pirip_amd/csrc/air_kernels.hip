@@ -20,6 +20,9 @@
 // Samples below the last reset are zero by their index (for u8: the float zero, not byte 128), whatever the ring holds.
 // Carry kernel, behind the mix kernel in stream order: the call's last min(n, ring) samples of every transmitter go to their ring slots
 // (absolute index modulo the ring), sample by sample.
+// Drift: a path with a clock offset reads its transmitter at a fractional position through a 16-tap polyphase
+// interpolator. Handles that have such a path launch air_mix_drift_kernel, on a longer span and with the table; every other handle launches
+// air_mix_kernel, which is kept as it was. The slip budget is host state, checked when a call is enqueued.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -46,6 +49,170 @@ __device__ __forceinline__ v2f air_sample(const char *p, v2f chi, v2f clo)
         return u8_to_float(v2f{(float)(w & 0xffu), (float)(w >> 8)}, chi, clo);
     }
     return *(const v2f *)p;
+}
+
+// cnt_r + cnt_w consecutive samples of transmitter tx from call index s0 on, into LDS as the 16-byte units that hold them: the cnt_r below
+// the call's first sample from the ring, the rest from the call's row. Sample u of the span is then at (u < cnt_r ? off_r : off_w) + u * BSI.
+template <int BSI>
+__device__ __forceinline__ void air_stage(const AirArgs &a, int tx, const AirRing &rg, int64_t s0, int cnt_r, int cnt_w, int tid, char *smem,
+                                          int &off_r, int &off_w)
+{
+    int shift_r = 0, units_r = 0;
+    if (cnt_r > 0) {
+        const uint32_t b0 = (uint32_t)((uint64_t)(a.N0 + s0) & rg.mask) * BSI;            // (a ring holds at most 2^20 samples of 8 bytes)
+        const uint32_t umask = ((rg.mask + 1u) * BSI >> 4) - 1u;
+        const uint4 *src = (const uint4 *)(a.ring + (size_t)rg.off * BSI);
+        shift_r = (int)(b0 & 15u);
+        units_r = (shift_r + cnt_r * BSI + 15) >> 4;
+        for (int u = tid; u < units_r; u += kAirThreads) ((uint4 *)smem)[u] = src[((b0 >> 4) + (uint32_t)u) & umask];
+    }
+    int shift_w = 0;
+    if (cnt_w > 0) {
+        const char *p = a.in + (size_t)tx * a.in_stride + (size_t)(s0 + cnt_r) * BSI;
+        shift_w = (int)((uintptr_t)p & 15);
+        const uint4 *src = (const uint4 *)(p - shift_w);
+        const int units_w = (shift_w + cnt_w * BSI + 15) >> 4;
+        for (int u = tid; u < units_w; u += kAirThreads) ((uint4 *)smem)[units_r + u] = src[u];
+    }
+    __syncthreads();
+    off_r = shift_r;
+    off_w = units_r * 16 + shift_w - cnt_r * BSI;
+}
+
+// The mix kernel of a handle with a drifting path: air_mix_kernel below (kept as it is, so that a handle without drift runs the very
+// code it ran before) with one more branch, uniform per workgroup and path. A path with a clock offset q != 0 reads its transmitter at
+// n - d_p + S + rho / Q through the interpolator. Its span is [i_first - 7, i_last + 8] with i = n - d_p + S: at most
+// kAirTile + kAirSpanExtra samples, staged as a static path's is. A lane takes (S, rho) of its first output from the tile's by exact
+// integers, steps them per output, and reads tap k of an output at span position j + (S - S_first) + k, from the part that position lies
+// in; the table row of phase floor(1024 rho / Q) comes through the caches. A path with q == 0 takes the static kernel's steps.
+// LDS: (kAirTile + kAirSpanExtra) * BSI + 64 bytes
+template <int BSI, int BSO>
+__global__ __launch_bounds__(kAirThreads) void air_mix_drift_kernel(AirArgs a, AirDrift d)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int64_t j0 = (int64_t)blockIdx.x * kAirTile;                 // first output of the tile (of this call)
+    const int cnt = (int)((a.n - j0) < kAirTile ? (a.n - j0) : kAirTile);
+    const int jl = tid * kAirPerThread;                                 // the thread's first output of the tile
+    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
+    // (n mod Fs) of the thread's first output
+    const uint32_t base = (uint32_t)(((int64_t)a.n0m + j0 % a.Fs) % a.Fs);
+    const uint32_t idx0 = (base + (uint32_t)jl) % (uint32_t)a.Fs;
+    v2f acc[kAirPerThread];
+#pragma unroll
+    for (int k = 0; k < kAirPerThread; k++) acc[k] = v2f{0.f, 0.f};
+
+    const int p0 = a.rx_start[r], p1 = a.rx_start[r + 1];
+    for (int pi = p0; pi < p1; pi++) {
+        const AirPath pth = a.paths[pi];
+        const AirRing rg = a.rings[pth.tx];
+        const int32_t q = d.ppb[pi];
+        v2f v[kAirPerThread];                                           // what the path reads for the lane's outputs
+        if (q != 0) {
+            constexpr int kSpan = kAirTile + kAirSpanExtra;
+            int64_t S0;
+            int32_t rho0;
+            clock_slip(d.age + j0, q, S0, rho0);                        // the tile's first output
+            int32_t dS = 0, rho1 = rho0;
+            clock_advance(cnt - 1, q, dS, rho1);                        // ... and how far S moves up to its last
+            const int64_t s0 = j0 - pth.delay + S0 - kAirLead;          // the span's first sample, as an index of this call
+            const int scnt = cnt + dS + kAirTaps - 1;
+            const int64_t vf = a.first - (a.N0 + s0);
+            const int vfirst = vf <= 0 ? 0 : (vf < kSpan ? (int)vf : kSpan);
+            const int cnt_r = s0 >= 0 ? 0 : (-s0 < scnt ? (int)-s0 : scnt);
+            if (pi > p0) __syncthreads();
+            int off_r, off_w;
+            air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, scnt - cnt_r, tid, smem, off_r, off_w);
+            int32_t S = 0, rho = rho0;                                  // S from here on: relative to the tile's first
+            clock_advance(jl, q, S, rho);
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) {
+                const int u0 = jl + k + S;                              // span position of the output's first tap
+                const float4 *row = (const float4 *)(d.taps + clock_phase_1024(rho) * kAirTaps);
+                v2f s = {0.f, 0.f};
+#pragma unroll
+                for (int c = 0; c < kAirTaps / 4; c++) {
+                    const float4 t4 = row[c];
+                    const float t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; e++) {
+                        const int u = u0 + 4 * c + e;
+                        v2f x = air_sample<BSI>(smem + (u < cnt_r ? off_r : off_w) + u * BSI, chi, clo);
+                        if (u < vfirst) x = v2f{0.f, 0.f};
+                        s = __builtin_elementwise_fma(v2f{t[e], t[e]}, x, s);
+                    }
+                }
+                v[k] = s;
+                clock_step(q, S, rho);
+            }
+        } else {
+            const int64_t s0 = j0 - pth.delay;                          // the span's first sample, as an index of this call
+            const int cnt_r = s0 >= 0 ? 0 : (-s0 < cnt ? (int)-s0 : cnt);       // samples from the ring
+            // tile index of the first sample at or above the last reset
+            const int64_t vf = a.first - (a.N0 + s0);
+            const int vfirst = vf <= 0 ? 0 : (vf < kAirTile ? (int)vf : kAirTile);
+            if (pi > p0) __syncthreads();
+            int off_r, off_w;
+            air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, cnt - cnt_r, tid, smem, off_r, off_w);
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) {
+                const int j = jl + k;
+                v[k] = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
+                if (j < vfirst) v[k] = v2f{0.f, 0.f};
+            }
+        }
+        // the mix, a static path's and a drifting one's alike
+        const v2f g = {pth.gain, pth.gain};
+        if (pth.fres != 0) {
+            uint32_t ph = (uint32_t)(int32_t)mulmod_fs((double)pth.fres, (double)idx0, a.Fs, a.inv_fs_d);
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) {
+                float cs, sn;
+                unit_phasor((int32_t)ph, a.Fs, a.two_over_fs, cs, sn);
+                acc[k] = __builtin_elementwise_fma(g, crot(v[k], cs, sn), acc[k]);
+                ph += (uint32_t)pth.fres;
+                if (ph >= (uint32_t)a.Fs) ph -= (uint32_t)a.Fs;
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) acc[k] = __builtin_elementwise_fma(g, v[k], acc[k]);
+        }
+    }
+
+    const float sigma = a.sigma[r];
+    if (sigma > 0.f) {
+        const int64_t n_abs = a.N0 + j0 + jl;
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) {
+            float xr = acc[k].x, xi = acc[k].y;
+            add_awgn(a.seed, r, n_abs + k, sigma, xr, xi);
+            acc[k] = v2f{xr, xi};
+        }
+    }
+
+    if (jl >= cnt) return;
+    char *row = a.out + (size_t)r * a.out_stride + (size_t)(j0 + jl) * BSO;
+    const bool whole = a.aligned16 && jl + kAirPerThread <= cnt;
+    if (BSO == 2) {
+        uint32_t w[kAirPerThread];
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) w[k] = (uint32_t)quant_u8_csdr(acc[k].x) | ((uint32_t)quant_u8_csdr(acc[k].y) << 8);
+        if (whole) {
+            *(uint4 *)row = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((uint16_t *)row)[k] = (uint16_t)w[k];
+        }
+    } else {
+        if (whole) {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k += 2) ((float4 *)row)[k >> 1] = make_float4(acc[k].x, acc[k].y, acc[k + 1].x, acc[k + 1].y);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((float2 *)row)[k] = make_float2(acc[k].x, acc[k].y);
+        }
+    }
 }
 
 // LDS: kAirTile * BSI + 64 bytes (the span's units: two parts, each with a unit of slack at either end)
@@ -178,28 +345,82 @@ bool sigma_ok(const float *sigma, int nrx)
     return true;
 }
 
-}  // namespace
+// ---- the interpolator's table (4.15a): T[phi][k] = sinc(k - 7 - mu) w((k - 7 - mu) / 8), mu = phi / 1024, w a Kaiser window of beta 6; every
+// phase divided by its own sum; in double, rounded once to float
 
-extern "C" {
+double bessel_i0(double x)
+{
+    double sum = 1.0, term = 1.0;
+    for (int k = 1; k < 64; k++) {
+        term *= (x / (2.0 * k)) * (x / (2.0 * k));
+        sum += term;
+        if (term < 1e-20 * sum) break;
+    }
+    return sum;
+}
 
-int pirip_hip_air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path *paths, const float *sigma,
-                         uint64_t seed, int device, pirip_hip_air **out)
+struct InterpTable {
+    float t[kAirPhases][kAirTaps];
+    InterpTable()
+    {
+        const double pi = 3.14159265358979323846, beta = 6.0, i0b = bessel_i0(beta);
+        for (int phi = 0; phi < kAirPhases; phi++) {
+            double row[kAirTaps], sum = 0.0;
+            for (int k = 0; k < kAirTaps; k++) {
+                const double x = (double)(k - kAirLead) - (double)phi / kAirPhases, u = x / (kAirTaps / 2);
+                // (sinc of a whole number but 0 is 0, not what sin makes of a multiple of pi: phase 0 is the exact unit impulse)
+                const double sinc = x == 0.0 ? 1.0 : (x == std::floor(x) ? 0.0 : std::sin(pi * x) / (pi * x));
+                const double w = std::fabs(u) > 1.0 ? 0.0 : bessel_i0(beta * std::sqrt(1.0 - u * u)) / i0b;
+                row[k] = sinc * w;
+                sum += row[k];
+            }
+            for (int k = 0; k < kAirTaps; k++) t[phi][k] = (float)(row[k] / sum);
+        }
+    }
+};
+
+const InterpTable &interp_table()
+{
+    static const InterpTable table;
+    return table;
+}
+
+// the last clock age the slip budget lets a sample have: q > 0: m q < (max_slip + 1) Q; q < 0: m |q| <= max_slip Q (no product above 2^51)
+int64_t last_age_of(int32_t max_slip, int32_t q_fast, int32_t q_slow)
+{
+    int64_t last = INT64_MAX;
+    if (q_fast > 0) last = (((int64_t)max_slip + 1) * kClockQ - 1) / q_fast;
+    if (q_slow > 0 && (int64_t)max_slip * kClockQ / q_slow < last) last = (int64_t)max_slip * kClockQ / q_slow;
+    return last;
+}
+
+int air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths, const float *sigma,
+               uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out)
 {
     if (!out) return PIRIP_ERR_BAD_ARG;
     *out = nullptr;
-    if (Fs < 2 || ntx < 1 || nrx < 1 || npaths < 0 || (npaths > 0 && !paths)) return PIRIP_ERR_BAD_ARG;
+    if (Fs < 2 || ntx < 1 || nrx < 1 || npaths < 0 || (npaths > 0 && !paths) || max_slip < 0) return PIRIP_ERR_BAD_ARG;
     if (in_format != PIRIP_IN_CU8_CSDR && in_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
     if (out_format != PIRIP_IN_CU8_CSDR && out_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
     int max_delay = 0;
+    int32_t q_fast = 0, q_slow = 0;                                     // the largest clock offset of either sign, as magnitudes
+    bool unsupported = false;
     for (int p = 0; p < npaths; p++) {
-        const pirip_air_path &q = paths[p];
+        const pirip_air_path_ex &q = paths[p];
         const int64_t f2 = 2 * (int64_t)q.offset_hz;
         if (q.rx < 0 || q.rx >= nrx || q.tx < 0 || q.tx >= ntx || q.delay < 0 || f2 <= -(int64_t)Fs || f2 >= (int64_t)Fs) return PIRIP_ERR_BAD_ARG;
         if (!std::isfinite(q.gain)) return PIRIP_ERR_BAD_ARG;
         if (q.delay > max_delay) max_delay = q.delay;
+        if (q.clock_ppb == 0) continue;
+        // the taps never reach past sample n, and the lag with slip and leading taps stays inside the longest ring
+        if (max_slip < 1 || (int64_t)q.delay < (int64_t)kAirLead + 1 + (q.clock_ppb > 0 ? max_slip : 0)) return PIRIP_ERR_BAD_ARG;
+        if ((int64_t)q.delay + kAirLead + (q.clock_ppb < 0 ? max_slip : 0) > kAirMaxDelay) unsupported = true;
+        if (q.clock_ppb > kAirMaxPpb || q.clock_ppb < -kAirMaxPpb) { unsupported = true; continue; }
+        if (q.clock_ppb > q_fast) q_fast = q.clock_ppb;
+        if (-q.clock_ppb > q_slow) q_slow = -q.clock_ppb;
     }
     if (!sigma_ok(sigma, nrx)) return PIRIP_ERR_BAD_ARG;
-    if (Fs > kMaxFs || max_delay > kAirMaxDelay || ntx > 65535 || nrx > 65535) return PIRIP_ERR_UNSUPPORTED;
+    if (unsupported || Fs > kMaxFs || max_delay > kAirMaxDelay || ntx > 65535 || nrx > 65535) return PIRIP_ERR_UNSUPPORTED;
     const U8Split u8 = csdr_u8_split();
     if (!u8.exact) return PIRIP_ERR_UNSUPPORTED;
     int dev = 0;
@@ -210,15 +431,21 @@ int pirip_hip_air_create(int Fs, int in_format, int out_format, int ntx, int nrx
     h->Fs = Fs; h->ntx = ntx; h->nrx = nrx; h->npaths = npaths; h->in_format = in_format; h->out_format = out_format;
     h->bsi = bytes_per_sample(in_format); h->bso = bytes_per_sample(out_format);
     h->max_delay = max_delay; h->seed = seed; h->u8 = u8;
-    // the paths of every receiver, ascending; every transmitter's ring: the smallest power of two that holds its longest delay
+    h->max_slip = max_slip; h->drift = q_fast != 0 || q_slow != 0; h->last_age = last_age_of(max_slip, q_fast, q_slow);
+    // the paths of every receiver, ascending; every transmitter's ring: the smallest power of two that holds its longest lag -- a static
+    // path's delay, a drifting one's with its slip and the leading taps
     std::vector<int32_t> rx_start(1, 0);
     std::vector<AirPath> sorted;
+    std::vector<int32_t> ppb;
     std::vector<int32_t> longest((size_t)ntx, 0);
     for (int r = 0; r < nrx; r++) {
         for (int p = 0; p < npaths; p++) {
             if (paths[p].rx != r) continue;
             sorted.push_back(AirPath{paths[p].tx, paths[p].delay, (int32_t)fs_residue(paths[p].offset_hz, Fs), paths[p].gain});
-            if (paths[p].delay > longest[(size_t)paths[p].tx]) longest[(size_t)paths[p].tx] = paths[p].delay;
+            ppb.push_back(paths[p].clock_ppb);
+            const int32_t q = paths[p].clock_ppb;
+            const int32_t lag = paths[p].delay + (q != 0 ? kAirLead : 0) + (q < 0 ? max_slip : 0);
+            if (lag > longest[(size_t)paths[p].tx]) longest[(size_t)paths[p].tx] = lag;
         }
         rx_start.push_back((int32_t)sorted.size());
     }
@@ -240,11 +467,74 @@ int pirip_hip_air_create(int Fs, int in_format, int out_format, int ntx, int nrx
         PIRIP_TRY(m.upload(&h->d_rx_start, rx_start.data(), sizeof(int32_t) * rx_start.size()));
         PIRIP_TRY(m.upload(&h->d_paths, sorted.data(), sizeof(AirPath) * sorted.size()));
         PIRIP_TRY(m.upload(&h->d_sigma, sg.data(), sizeof(float) * sg.size()));
+        if (h->drift) {
+            PIRIP_TRY(m.upload(&h->d_ppb, ppb.data(), sizeof(int32_t) * ppb.size()));
+            PIRIP_TRY(m.upload(&h->d_taps, &interp_table().t[0][0], sizeof(InterpTable)));
+        }
         return PIRIP_OK;
     };
     const int rc = tables();
     if (rc != PIRIP_OK) { delete h; return rc; }
     *out = h;
+    return PIRIP_OK;
+}
+
+// what push will still take: the absolute index stays below 2^53, and a drifting handle's clock age inside its budget
+int64_t samples_left(const pirip_hip_air *air)
+{
+    int64_t left = kAirMaxIndex - 1 - air->pos;
+    if (air->drift) {
+        const int64_t age = air->age0 + (air->pos - air->first);
+        const int64_t by_slip = air->last_age < age ? 0 : air->last_age - age + 1;
+        if (by_slip < left) left = by_slip;
+    }
+    return left < 0 ? 0 : left;
+}
+
+}  // namespace
+
+extern "C" {
+
+int pirip_hip_air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path *paths, const float *sigma,
+                         uint64_t seed, int device, pirip_hip_air **out)
+{
+    std::vector<pirip_air_path_ex> ex;
+    for (int p = 0; paths && p < npaths; p++) ex.push_back(pirip_air_path_ex{paths[p].rx, paths[p].tx, paths[p].delay, paths[p].offset_hz, paths[p].gain, 0});
+    return air_create(Fs, in_format, out_format, ntx, nrx, npaths, paths ? ex.data() : nullptr, sigma, seed, 0, device, out);
+}
+
+int pirip_hip_air_create_ex(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths, const float *sigma,
+                            uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out)
+{
+    return air_create(Fs, in_format, out_format, ntx, nrx, npaths, paths, sigma, seed, max_slip, device, out);
+}
+
+int pirip_hip_air_interp_table(float *taps, int *nphases, int *ntaps)
+{
+    if (!taps) return PIRIP_ERR_BAD_ARG;
+    const InterpTable &t = interp_table();
+    for (int phi = 0; phi < kAirPhases; phi++)
+        for (int k = 0; k < kAirTaps; k++) taps[phi * kAirTaps + k] = t.t[phi][k];
+    if (nphases) *nphases = kAirPhases;
+    if (ntaps) *ntaps = kAirTaps;
+    return PIRIP_OK;
+}
+
+int pirip_hip_air_get_drift(const pirip_hip_air *air, int32_t *max_slip, int64_t *left)
+{
+    if (!air) return PIRIP_ERR_BAD_ARG;
+    if (max_slip) *max_slip = air->max_slip;
+    if (left) *left = samples_left(air);
+    return PIRIP_OK;
+}
+
+int pirip_hip_air_reset_drift(pirip_hip_air *air, int64_t n0, int64_t age0, void *hip_stream)
+{
+    (void)hip_stream;                                                   // nothing to enqueue, as in pirip_hip_air_reset
+    if (!air || n0 < 0 || age0 < 0) return PIRIP_ERR_BAD_ARG;
+    if (n0 >= kAirMaxIndex || age0 >= kAirMaxIndex || (air->drift && age0 > air->last_age)) return PIRIP_ERR_UNSUPPORTED;
+    air->pos = air->first = n0;
+    air->age0 = age0;
     return PIRIP_OK;
 }
 
@@ -272,6 +562,7 @@ int pirip_hip_air_push(pirip_hip_air *air, const void *d_in, size_t in_stride_by
     PIRIP_TRY(iq_rows_check(d_in, in_stride_bytes, air->bsi, air->ntx, n));
     PIRIP_TRY(iq_rows_check(d_out, out_stride_bytes, air->bso, air->nrx, n));
     if (n >= kAirMaxIndex || air->pos + n >= kAirMaxIndex) return PIRIP_ERR_UNSUPPORTED;
+    if (air->drift && n > samples_left(air)) return PIRIP_ERR_UNSUPPORTED;  // the call's last sample would take a path past max_slip
     const uintptr_t i0 = (uintptr_t)d_in, i1 = i0 + (size_t)(air->ntx - 1) * in_stride_bytes + (size_t)n * (size_t)air->bsi;
     const uintptr_t o0 = (uintptr_t)d_out, o1 = o0 + (size_t)(air->nrx - 1) * out_stride_bytes + (size_t)n * (size_t)air->bso;
     if (i0 < o1 && o0 < i1) return PIRIP_ERR_BAD_ARG;
@@ -290,11 +581,20 @@ int pirip_hip_air_push(pirip_hip_air *air, const void *d_in, size_t in_stride_by
     a.inv_fs_d = 1.0 / (double)air->Fs;
     hipStream_t st = (hipStream_t)hip_stream;
     const dim3 grid((unsigned)ntiles, (unsigned)air->nrx);
-    const size_t lds = (size_t)kAirTile * (size_t)air->bsi + 64;
-    if (air->bsi == 2 && air->bso == 2) hipLaunchKernelGGL((air_mix_kernel<2, 2>), grid, dim3(kAirThreads), lds, st, a);
-    else if (air->bsi == 2) hipLaunchKernelGGL((air_mix_kernel<2, 8>), grid, dim3(kAirThreads), lds, st, a);
-    else if (air->bso == 2) hipLaunchKernelGGL((air_mix_kernel<8, 2>), grid, dim3(kAirThreads), lds, st, a);
-    else hipLaunchKernelGGL((air_mix_kernel<8, 8>), grid, dim3(kAirThreads), lds, st, a);
+    // a handle with a drifting path: the drift instantiation on a longer span; every other one: the static kernel on the tile's
+    const size_t lds = (size_t)(kAirTile + (air->drift ? kAirSpanExtra : 0)) * (size_t)air->bsi + 64;
+    const AirDrift d{air->d_ppb, air->d_taps, air->age0 + (air->pos - air->first)};
+    const int kind = (air->drift ? 4 : 0) + (air->bsi == 2 ? 0 : 2) + (air->bso == 2 ? 0 : 1);
+    switch (kind) {
+    case 0: hipLaunchKernelGGL((air_mix_kernel<2, 2>), grid, dim3(kAirThreads), lds, st, a); break;
+    case 1: hipLaunchKernelGGL((air_mix_kernel<2, 8>), grid, dim3(kAirThreads), lds, st, a); break;
+    case 2: hipLaunchKernelGGL((air_mix_kernel<8, 2>), grid, dim3(kAirThreads), lds, st, a); break;
+    case 3: hipLaunchKernelGGL((air_mix_kernel<8, 8>), grid, dim3(kAirThreads), lds, st, a); break;
+    case 4: hipLaunchKernelGGL((air_mix_drift_kernel<2, 2>), grid, dim3(kAirThreads), lds, st, a, d); break;
+    case 5: hipLaunchKernelGGL((air_mix_drift_kernel<2, 8>), grid, dim3(kAirThreads), lds, st, a, d); break;
+    case 6: hipLaunchKernelGGL((air_mix_drift_kernel<8, 2>), grid, dim3(kAirThreads), lds, st, a, d); break;
+    default: hipLaunchKernelGGL((air_mix_drift_kernel<8, 8>), grid, dim3(kAirThreads), lds, st, a, d); break;
+    }
     // the carry: as many workgroups per transmitter as the longest ring and the call ask for (at most 64, which stride)
     const int64_t most = n < (int64_t)air->max_ring ? n : (int64_t)air->max_ring;
     int64_t cblocks = (most + kAirThreads - 1) / kAirThreads;
@@ -313,6 +613,7 @@ int pirip_hip_air_reset(pirip_hip_air *air, int64_t n0, void *hip_stream)
     if (!air || n0 < 0) return PIRIP_ERR_BAD_ARG;
     if (n0 >= kAirMaxIndex) return PIRIP_ERR_UNSUPPORTED;
     air->pos = air->first = n0;
+    air->age0 = 0;
     return PIRIP_OK;
 }
 

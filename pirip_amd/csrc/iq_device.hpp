@@ -39,6 +39,41 @@ __device__ __forceinline__ void unit_phasor(int32_t p, int Fs, float k_over_fs, 
 // v (c + j s): one fma per component on an unfused product
 __device__ __forceinline__ v2f crot(v2f v, float c, float s) { return v2f{__builtin_fmaf(v.x, c, -(v.y * s)), __builtin_fmaf(v.x, s, v.y * c)}; }
 
+// ---- exact clock slip (the channel's drifting paths) -----------------------------------------------------------------------------------
+// A stream read by a clock q parts per billion off is read, at clock age m, at m q / Q samples from where a static one is: S = floor(m q / Q)
+// whole samples and rho = m q - Q S in [0, Q) billionths. Integers throughout: from one sample to the next rho moves by its exact
+// increment q with one wrap (S +- 1), as the mixers' phase does -- no recursion in floating point. |m q| < 2^53 (mod_fs's way to a quotient).
+constexpr int32_t kClockQ = 1000000000;
+__device__ __forceinline__ void clock_slip(int64_t m, int32_t q, int64_t &S, int32_t &rho)
+{
+    const int64_t p = m * (int64_t)q;
+    int64_t s = (int64_t)floor((double)p * 1e-9);                      // p is exact in a double: the quotient is right or one off
+    int64_t r = p - s * kClockQ;                                        // ... and the remainder says which
+    if (r < 0) { r += kClockQ; s -= 1; }
+    if (r >= kClockQ) { r -= kClockQ; s += 1; }
+    S = s; rho = (int32_t)r;
+}
+// one sample on, |q| <= kClockQ: rho + q stays inside an int32
+__device__ __forceinline__ void clock_step(int32_t q, int32_t &S, int32_t &rho)
+{
+    rho += q;
+    if (rho >= kClockQ) { rho -= kClockQ; S += 1; }
+    if (rho < 0) { rho += kClockQ; S -= 1; }
+}
+// `steps` samples on in one go, for 0 <= steps |q| < 3 Q: at most three wraps
+__device__ __forceinline__ void clock_advance(int32_t steps, int32_t q, int32_t &S, int32_t &rho)
+{
+    int64_t t = (int64_t)rho + (int64_t)steps * (int64_t)q;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+        if (t >= kClockQ) { t -= kClockQ; S += 1; }
+        if (t < 0) { t += kClockQ; S -= 1; }
+    }
+    rho = (int32_t)t;
+}
+// floor(phases rho / Q) for phases = 1024 = 2^10: Q / 2^10 = 1953125 / 2, so it is 2 rho / 1953125 in 32 bits (2 rho < 2^31)
+__device__ __forceinline__ uint32_t clock_phase_1024(int32_t rho) { return (2u * (uint32_t)rho) / 1953125u; }
+
 // ---- sample formats in -----------------------------------------------------------------------------------------------------------
 // csdr's convert_u8_f, x / 127.5 - 1 in double rounded to float, as two fmas: c_hi is 1 / 127.5 rounded to a multiple of 2^-22 (the inner fma
 // is then exact for every byte value), c_lo the float remainder; bit-identical to the double formula for all 256 bytes (rate_host.hpp's

@@ -1,13 +1,16 @@
 #!/usr/bin/env python3
 """Rate of the channel (include/pirip_hip.h section O): T transmitted wideband u8 IQ streams onto R received ones on the device.
 
-    python tools/air_rate.py [--receivers 64] [--paths 2] [--n 1048576] [--calls 1000] [--reps 5] [--sigma 0.1]
+    python tools/air_rate.py [--receivers 64] [--paths 2] [--n 1048576] [--calls 1000] [--reps 5] [--sigma 0.1] [--clock-ppb 0]
 
 R receivers x K paths each (two transmitters; every path rotated, delays up to 4097 samples), u8 in and out, n samples per call.
 Printed per variant -- with noise, and with sigma 0 (no Box-Muller) --: wideband samples/s of pirip_hip_air_push over --calls consecutive
 calls, and the HBM traffic it implies at (2 K + 2) bytes per output sample (every path's input read once, every output written once;
 --hbm-gbs, default 8000). Times are medians of --reps runs after one warm-up run, each a
-fraction of a second of back-to-back calls bracketed by device synchronisation."""
+fraction of a second of back-to-back calls bracketed by device synchronisation.
+--clock-ppb Q (default 0: the run above and nothing else) adds, behind that run and in the same session, the same paths with a clock
+offset of Q parts per billion each: every delay grows by 8 + max_slip, max_slip being what one run of --calls calls
+slips, and every run starts from a reset, which enqueues nothing."""
 import argparse
 import os
 import sys
@@ -43,6 +46,7 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sigma", type=float, default=0.1)
     ap.add_argument("--hbm-gbs", type=float, default=8000.0)
+    ap.add_argument("--clock-ppb", type=int, default=0)
     a = ap.parse_args()
     R, K, n, Fs, T = a.receivers, a.paths, a.n, 2400000, 2
     print(f"device: {torch.cuda.get_device_name(0)}; {R} receivers x {K} paths, {T} transmitters, u8 -> u8, {n} samples per call, {a.calls} calls per run")
@@ -51,19 +55,24 @@ def main():
     d_in = torch.randint(0, 256, (T, n * 2), dtype=torch.uint8, device="cuda")
     d_out = torch.zeros((R, n * 2), dtype=torch.uint8, device="cuda")
     bps = 2.0 * K + 2.0
-    for sigma in (a.sigma, 0.0):
-        air = pirip_amd.HipAir(Fs, paths, T, R, sigma=sigma, seed=1)
+    variants = [("", paths, 0)]
+    if a.clock_ppb:
+        slip = abs(a.clock_ppb) * n * a.calls // 10 ** 9 + 1
+        variants.append((f"clock {a.clock_ppb} ppb, max_slip {slip}, ", [(r, t, g, d + 8 + slip, f, a.clock_ppb) for r, t, g, d, f in paths], slip))
+    for tag, pth, slip, sigma in [(t, p, s, sg) for t, p, s in variants for sg in (a.sigma, 0.0)]:
+        air = pirip_amd.HipAir(Fs, pth, T, R, sigma=sigma, seed=1, max_slip=slip)
 
         def run():
+            if slip:
+                air.reset(0)                                      # the budget starts again; nothing is enqueued
             for _ in range(a.calls):
                 air.push(d_in, n * 2, n, d_out, n * 2)
 
         t, lo, hi = med(run, a.reps)
         sps = R * n * a.calls / t
-        print(f"sigma {sigma}: {t / a.calls * 1e3:8.3f} ms per call (runs {lo / a.calls * 1e3:.3f} .. {hi / a.calls * 1e3:.3f}), {sps / 1e9:7.2f} G wideband samples/s, "
+        print(f"{tag}sigma {sigma}: {t / a.calls * 1e3:8.3f} ms per call (runs {lo / a.calls * 1e3:.3f} .. {hi / a.calls * 1e3:.3f}), {sps / 1e9:7.2f} G wideband samples/s, "
               f"{bps:.0f} B per output sample -> {bps * sps / 1e9:7.1f} GB/s = {100 * bps * sps / 1e9 / a.hbm_gbs:5.2f} % of {a.hbm_gbs:.0f} GB/s")
         air.close()
-
 
 if __name__ == "__main__":
     main()
