@@ -40,6 +40,7 @@
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 
 #include "../../include/pirip_hip.h"
 #include "demod_simd.hpp"
@@ -319,6 +320,19 @@ constexpr bool wave_two_pass_argmax_instance(int M, int TS, int FMT, bool MASK, 
     return false;
 }
 
+// Instances whose locked-receiver frames skip two more pieces of work that select nothing on such a frame ("locked paths"):
+//   hit:    a frame-cache hit branches round the correlator's oscillator-switch selects
+//   slots:  the peak search runs over the bin slots the call's search range reaches (two of four for a range inside FFT bins 0 .. 31)
+// Opt-in: where the register report (tools/kernel_resources.sh, profiles/lp_resources_{parent,result}.txt) shows no VGPR spill, the same
+// occupancy and no more spilled SGPRs with both than without, AND an interleaved A/B was taken (profiles/lp_ab_headline.txt). That is the
+// `fsk_demod -p 24` instance. With both everywhere they apply the 4-FSK instances spill 20 more SGPRs (24 -> 44) and the 4-FSK Ts = 20
+// one 9 VGPRs; the csdr / fused-multiply twins of the headline and the 2-FSK P = 8 / 6 and float instances pass the register test
+// (3 to 18 spilled SGPRs against 5 to 17) but have no A/B yet: every instance not named here compiles the code it had.
+constexpr bool wave_locked_paths_instance(int M, int TS, int P, int NDFT, int FMT, bool FFT_FMA, bool MASK, int BAND)
+{
+    return M == 2 && TS == 24 && P == 24 && NDFT == 256 && FMT == PIRIP_IN_CU8_FSKDEMOD && !FFT_FMA && !MASK && BAND == 0;
+}
+
 // Per-wave LDS footprint, also used by the launcher to report occupancy
 template <class C, int M> constexpr int wave_lds_bytes() { return C::RAW_B + C::XP_B; }
 
@@ -506,6 +520,8 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     // per SIMD; elsewhere a hit reads the rows again. PLAIN instances (wave_plain_instance) keep the frame loop they had.
     constexpr bool FCACHE = WPS <= 3 && !PLAIN;
     constexpr bool KEEP_STEP = FCACHE && (M == 2 || WPS == 2);
+    // a hit frame branches round the oscillator-switch selects in the correlator's unrolled recursion (see there)
+    constexpr bool HIT_BRANCH = FCACHE && wave_locked_paths_instance(M, TS, P, NDFT, FMT, FFT_FMA, MASK, BAND);
     constexpr uint32_t kFcStale = 0x40000000u, kFcNever = 0x80000000u, kFcRan = 0x20000000u;   // (kFcRan: the call has run a frame -- the same word again)
     static_assert(N + Q < 0x10000, "last frame's length leaves the flag bits free");
     v2f ph_c[FCACHE ? M : 1], step_c[KEEP_STEP ? M : 1];
@@ -518,6 +534,16 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
         for (int m = 0; m < M; m++) step_c[m] = v2f{0.f, 0.f};
     }
     uint32_t ninp_fc = (uint32_t)ninp0 | (d.frame_cache ? kFcStale : kFcNever);
+    // Peak search, slots: a lane's NB = 4 owned bins are FFT bins e16 + 16 b (+ 64 per lane group), so a search range inside FFT bins
+    // 0 .. 31 -- the reference's 500 .. 25000 Hz is bins 1 .. 26 -- has in-range bins in slots 0 and 1 only: slots 2 and 3 compete with + 0
+    // in every lane of every frame. Which slots are live is a property of the call: when none above NLIVE - 1 is, the frames search NLIVE
+    // slots (one more flag of the same word; with the test hook FskDims::frame_cache == 0 every frame searches all NB).
+    constexpr bool LIVE_SLOTS = !PLAIN && NB == 4 && wave_locked_paths_instance(M, TS, P, NDFT, FMT, FFT_FMA, MASK, BAND);
+    constexpr int NLIVE = 2;
+    constexpr uint32_t kFcLowSlots = 0x10000000u;
+    if constexpr (LIVE_SLOTS) {
+        if (d.frame_cache && !__any((in_range >> NLIVE) != 0u)) ninp_fc |= kFcLowSlots;
+    }
 
     // LDS-DMA of the frame superset [p0, p0 + N + Q) to raw + GUARD_B (lane-linear: 16 or 4 bytes per lane per instruction)
     typedef __attribute__((address_space(3))) void *lds_ptr;
@@ -1041,29 +1067,62 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             wave_lds_sync();
         } else {
             PIRIP_PHASE_LANE(lane);
-            float w[NB];
-            int sfi[NB];
-            static_assert(NB <= 8, "one flag bit per owned bin");
+            if constexpr (LIVE_SLOTS) {
+                // the search below over the first NBL of a lane's NB bin slots: NBL = NLIVE where the call's search range leaves the other
+                // slots at +0 in every lane (kFcLowSlots) -- a slot at +0 never beats best >= 0, so the winners are the same -- else NB
+                // (argument fields are read outside the lambda: read through its closure, hipcc holds many more of them in scalar
+                //  registers across the frame loop, and spills them)
+                const int f_zero = d.f_zero;
+                auto pick = [&](auto nbl_c) __attribute__((always_inline)) {
+                    constexpr int NBL = decltype(nbl_c)::value;
+                    float w[NBL];
+                    int sfi[NBL];
 #pragma unroll
-            for (int b = 0; b < NB; b++) {
-                sfi[b] = (BAND && lane >= 16) ? -1 : own_sfi(lane, b);                                 // (BAND: group 0's copy competes)
-                // the search range is tested ONCE per call (in_range), not once per tone or frame: a bin outside it competes with +0, which
-                // the strict comparison against best >= 0 never selects -- the same winners as testing the range in every tone's loop
-                if constexpr (PLAIN) w[b] = (sfi[b] >= d.est_st && sfi[b] < d.est_en) ? Sf[b] : 0.0f;
-                else w[b] = __builtin_bit_cast(float, fbits(Sf[b]) & flag_mask(in_range, b));
-            }
+                    for (int b = 0; b < NBL; b++) {
+                        sfi[b] = (BAND && lane >= 16) ? -1 : own_sfi(lane, b);                             // (BAND: group 0's copy competes)
+                        w[b] = __builtin_bit_cast(float, fbits(Sf[b]) & flag_mask(in_range, b));           // (as below: a bin outside the range competes with +0)
+                    }
 #pragma unroll
-            for (int m = 0; m < M; m++) {
-                float best = 0.0f; int ib = 0;
+                    for (int m = 0; m < M; m++) {
+                        float best = 0.0f; int ib = 0;
 #pragma unroll
-                for (int b = 0; b < NB; b++)
-                    if (w[b] > best) { best = w[b]; ib = sfi[b]; }
-                wave_argmax<ARGMAX_SINGLE>(best, ib);
-                int f_min = ib - d.f_zero; f_min = f_min < 0 ? 0 : f_min;
-                int f_max = ib + d.f_zero; f_max = f_max > NDFT ? NDFT : f_max;
+                        for (int b = 0; b < NBL; b++)
+                            if (w[b] > best) { best = w[b]; ib = sfi[b]; }
+                        wave_argmax<ARGMAX_SINGLE>(best, ib);
+                        int f_min = ib - f_zero; f_min = f_min < 0 ? 0 : f_min;
+                        int f_max = ib + f_zero; f_max = f_max > NDFT ? NDFT : f_max;
 #pragma unroll
-                for (int b = 0; b < NB; b++) if (sfi[b] >= f_min && sfi[b] < f_max) w[b] = 0.0f;
-                freqi[m] = ib - NDFT / 2;
+                        for (int b = 0; b < NBL; b++) if (sfi[b] >= f_min && sfi[b] < f_max) w[b] = 0.0f;
+                        freqi[m] = ib - NDFT / 2;
+                    }
+                };
+                if (ninp_fc & kFcLowSlots) pick(std::integral_constant<int, NLIVE>{});
+                else pick(std::integral_constant<int, NB>{});
+            } else {
+                float w[NB];
+                int sfi[NB];
+                static_assert(NB <= 8, "one flag bit per owned bin");
+#pragma unroll
+                for (int b = 0; b < NB; b++) {
+                    sfi[b] = (BAND && lane >= 16) ? -1 : own_sfi(lane, b);                                 // (BAND: group 0's copy competes)
+                    // the search range is tested ONCE per call (in_range), not once per tone or frame: a bin outside it competes with +0, which
+                    // the strict comparison against best >= 0 never selects -- the same winners as testing the range in every tone's loop
+                    if constexpr (PLAIN) w[b] = (sfi[b] >= d.est_st && sfi[b] < d.est_en) ? Sf[b] : 0.0f;
+                    else w[b] = __builtin_bit_cast(float, fbits(Sf[b]) & flag_mask(in_range, b));
+                }
+#pragma unroll
+                for (int m = 0; m < M; m++) {
+                    float best = 0.0f; int ib = 0;
+#pragma unroll
+                    for (int b = 0; b < NB; b++)
+                        if (w[b] > best) { best = w[b]; ib = sfi[b]; }
+                    wave_argmax<ARGMAX_SINGLE>(best, ib);
+                    int f_min = ib - d.f_zero; f_min = f_min < 0 ? 0 : f_min;
+                    int f_max = ib + d.f_zero; f_max = f_max > NDFT ? NDFT : f_max;
+#pragma unroll
+                    for (int b = 0; b < NB; b++) if (sfi[b] >= f_min && sfi[b] < f_max) w[b] = 0.0f;
+                    freqi[m] = ib - NDFT / 2;
+                }
             }
 #pragma unroll
             for (int x = 1; x < M; x++)
@@ -1125,17 +1184,17 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
 #pragma unroll
             for (int m = 0; m < M; m++) moved |= (uint32_t)(tix[m] ^ tixp[m]);
             static_assert(Q > 0 && Q < TS, "a block changes oscillators at sample Ts/4 or Ts - Ts/4 only: never where nold_blk is a multiple of Ts");
-            if (FCACHE && (moved | (ninp_fc & (kFcStale | kFcNever))) == 0) {
+            const bool hit = FCACHE && (moved | (ninp_fc & (kFcStale | kFcNever))) == 0;
+            if (hit) {
                 // hit: the rows are last frame's (old and new positions step alike). nin == N: nold = 2 Ts, nold_blk is a multiple of Ts in
-                // every lane and no block changes oscillators (the assertion above) -- sw_ph / sw_dph are never selected in this frame,
-                // they only have to hold something: the step
+                // every lane and no block changes oscillators (the assertion above) -- sw_ph / sw_dph are never selected in this frame.
+                // HIT_BRANCH: the frame branches round the selects and leaves both unset; else they only have to hold something: the step
 #pragma unroll
                 for (int m = 0; m < M; m++) {
                     if constexpr (KEEP_STEP) dph[m] = step_c[m];
                     else { const float2 stn = a.t.osc_step[tix[m]]; dph[m] = v2f{stn.x, stn.y}; }      // uniform load
                     if constexpr (FCACHE) ph[m] = ph_c[m];
-                    sw_ph[m] = dph[m];
-                    sw_dph[m] = dph[m];
+                    if constexpr (!HIT_BRANCH) { sw_ph[m] = dph[m]; sw_dph[m] = dph[m]; }
                 }
             } else {
 #pragma unroll
@@ -1161,7 +1220,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             }
             // last frame's length for the next frame, with the cache's state: stale unless this frame's inputs were a locked receiver's
             // (moved < 2^16: the sum carries into kFcStale exactly when moved != 0)
-            ninp_fc = (uint32_t)nin | (PLAIN ? 0u : kFcRan) | (ninp_fc & kFcNever) | (FCACHE ? ((moved + (kFcStale - 1u)) & kFcStale) : 0u);
+            ninp_fc = (uint32_t)nin | (PLAIN ? 0u : kFcRan) | (ninp_fc & (kFcNever | kFcLowSlots)) | (FCACHE ? ((moved + (kFcStale - 1u)) & kFcStale) : 0u);
 #pragma unroll
             for (int m = 0; m < M; m++) acc[m] = v2f{0.f, 0.f};
 #pragma unroll
@@ -1205,7 +1264,8 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                     if (!InFmt<FMT>::NEUTRAL_OK && k < zero_blk) x = v2f{0.f, 0.f};   // old position of a stream's very first frame
                     // the one block that holds the last old and the first new sample (nold = 2 Ts -/+ Ts/4: block 1 at k = Ts - Ts/4,
                     // block 2 at k = Ts/4) changes oscillators there
-                    if (k == Q || k == TS - Q) {
+                    // (HIT_BRANCH: not on a frame-cache hit -- a wave-uniform branch round the 4 M selects; a miss runs them as ever)
+                    if ((k == Q || k == TS - Q) && !(HIT_BRANCH && hit)) {
                         const bool sw = nold_blk == k;
 #pragma unroll
                         for (int m = 0; m < M; m++) {
