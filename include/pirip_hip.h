@@ -26,7 +26,7 @@
  *   section L  test-frame counter (pirip_hip_tbits_*)       : fsk_put_test_bits / rtl_fsk --testframes for a batch of streams,
  *              counted on the device behind the demodulator or the receiver.
  *   section O  channel (pirip_hip_air_*)                    : T transmitted wideband IQ streams onto R received ones: paths with
- *              gain, delay, carrier offset and sample-clock offset, AWGN per receiver, block after block.
+ *              gain, delay, carrier offset, sample-clock offset and Rayleigh / Rician fading, AWGN per receiver, block after block.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -965,6 +965,44 @@ int pirip_hip_air_get_drift(const pirip_hip_air *air, int32_t *max_slip, int64_t
  * ended (with the delays moved by S) or starts anywhere inside it. PIRIP_ERR_BAD_ARG for n0 or age0 < 0; PIRIP_ERR_UNSUPPORTED for either
  * from 2^53, or an age0 that already breaks the budget. */
 int pirip_hip_air_reset_drift(pirip_hip_air *air, int64_t n0, int64_t age0, void *hip_stream);
+
+/* ---- section O, fading: a path whose gain moves, Rayleigh or Rician with a Doppler spread. Only symbols are added: the
+ * entry points above, the launches of a handle without a fading path and PIRIP_HIP_ABI_VERSION stand as they are. */
+typedef struct pirip_air_fade { int32_t path; int32_t doppler_millihz; float rice_k; uint32_t key; } pirip_air_fade;
+/* pirip_hip_air_create_ex with nfades fades, each attached to one path (an index into paths): (path, doppler_millihz >= 0, rice_k >= 0,
+ * key). A fade is a sum of J = 16 scatterers and a line-of-sight term. The host makes, per fade, 16 signed increments w_j, 16 start phases
+ * theta_j and two floats (pirip_hip_air_fade_table returns them), with f_d = doppler_millihz / 1000 in double and K = rice_k:
+ *     alpha_j = 2 pi (j + u_j) / 16,  u_j in [0, 1): the top 53 bits of r1_j = splitmix(seed ^ splitmix((key << 32) ^ j)), the product's
+ *                                     SplitMix64 finaliser (section B2's noise source), times 2^-53
+ *     nu_j = f_d cos(alpha_j),  w_j = (int32) llrint(nu_j / Fs * 2^32),  theta_j = the top 32 bits of splitmix(r1_j)
+ *     s = float(sqrt(1 / (16 (K + 1)))),  los = float(sqrt(K / (K + 1)))            in double, rounded once
+ * The phase of scatterer j at the absolute index n is the 32-bit integer psi_j(n) = theta_j + w_j * (uint32) n, plain unsigned wrap-around
+ * arithmetic. The gain lives on an absolute grid of G = 16 samples; at grid point k, the absolute index 16 k:
+ *     t_j = float((int32) psi_j(16 k) >> 8) * 2^-23            exact, in [-1, 1)
+ *     (cos_j, sin_j) = sincospif(t_j);  C = sum_j cos_j,  D = sum_j sin_j          ascending j from 0, plain float adds
+ *     c_k = ( fma(s, C, los),  s * D )
+ * and between grid points it is the line through them: with k = n >> 4 and mu = float(n & 15) / 16
+ *     g[n] = ( fma(mu, c_{k+1}.re - c_k.re, c_k.re),  fma(mu, c_{k+1}.im - c_k.im, c_k.im) )
+ * v_p[n] -- a static path's x_t[n - d_p] or a drifting path's interpolated value -- becomes crot(v_p[n], g.re, g.im), the complex product
+ * v g by section J's arithmetic, BEFORE the carrier rotation; the path's mix follows unchanged: the rotation by the exact integer phase
+ * where f_p != 0, then acc_r = fma(a_p, v, acc_r). g is taken at the receiver's index n, whatever the path's delay and slip. A path
+ * without a fade is the path of pirip_hip_air_create_ex, bit for bit; with nfades == 0 the call is pirip_hip_air_create_ex, bit for bit
+ * and launch for launch.
+ * Consequences: a sample stays a function of the absolute index, of the reset's clock age, of its receiver's paths and fades, and of the
+ * input; any cutting into calls gives the one-shot output bit for bit. For a receiver with a fading path the guarantee "starts n0 and
+ * n0 + k Fs give the same bytes" is replaced by "starts n0 and n0 + 2^32 give the same bytes", which holds with sigma 0, no drifting path
+ * and every carrier offset 0 (the exact mixer phase is not 2^32-periodic in general). |g| <= Gamma = los + 16 s, which is 4 at K = 0.
+ * Time-averaged over a long span |g|^2 tends to 1: the mean power gain is 1.
+ * PIRIP_ERR_BAD_ARG for nfades < 0, fades NULL with nfades > 0, a path index outside [0, npaths), two fades on one path,
+ * doppler_millihz < 0, a rice_k that is negative or not finite. PIRIP_ERR_UNSUPPORTED for doppler_millihz > floor(1000 Fs / 1024): at that
+ * limit a phase moves at most 2 pi 16 / 1024 per grid step, and the line departs from the continuous process by at most
+ * (2 pi / 64)^2 / 8 = 1.2e-3 of the scatter amplitude. Every argument check comes before a device is looked for.
+ * push, reset, reset_drift, set_sigma, get_info and get_drift work unchanged on such a handle. */
+int pirip_hip_air_create_fade(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths, int nfades,
+                              const pirip_air_fade *fades, const float *sigma, uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out);
+/* A fade's table, the very integers and floats the kernel reads (fade->path is not looked at). Host only: no device is looked for.
+ * PIRIP_ERR_BAD_ARG for a NULL pointer, Fs < 2 and the fade's values refused above; PIRIP_ERR_UNSUPPORTED as above. */
+int pirip_hip_air_fade_table(int Fs, uint64_t seed, const pirip_air_fade *fade, int32_t w[16], uint32_t theta[16], float *scale, float *los);
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

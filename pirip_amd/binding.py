@@ -89,6 +89,11 @@ class AirPathEx(C.Structure):
     _fields_ = AirPath._fields_ + [("clock_ppb", C.c_int32)]
 
 
+class AirFade(C.Structure):
+    """pirip_air_fade: index of the path the fade is attached to, Doppler spread in millihertz, Rician K (0: Rayleigh), key of its draws"""
+    _fields_ = [("path", C.c_int32), ("doppler_millihz", C.c_int32), ("rice_k", C.c_float), ("key", C.c_uint32)]
+
+
 class AirInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("Fs", "ntx", "nrx", "npaths", "in_format", "out_format", "max_delay", "device")]
 
@@ -257,6 +262,8 @@ def lib():
     L.pirip_hip_air_interp_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
     L.pirip_hip_air_get_drift.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
     L.pirip_hip_air_reset_drift.argtypes = [vp, i64, i64, vp]
+    L.pirip_hip_air_create_fade.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, C.c_uint64, C.c_int32, i32, C.POINTER(vp)]
+    L.pirip_hip_air_fade_table.argtypes = [i32, C.c_uint64, C.POINTER(AirFade), vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
     _lib = L
     return L
 
@@ -1016,9 +1023,12 @@ class HipAir:
     Two clocks that disagree: a sixth element or key `clock_ppb` (AirPathEx) is the clock offset of the path's transmitter
     in parts per billion, fast when positive; such a path is read through the interpolator and may slip max_slip whole samples, of its
     delay (fast: delay >= 8 + max_slip) or of the ring (slow). drift() says how many samples push() still takes, reset(n0, age=...)
-    resumes at a clock age. Without a clock offset and with max_slip 0 the handle is pirip_hip_air_create's."""
+    resumes at a clock age. Without a clock offset and with max_slip 0 the handle is pirip_hip_air_create's.
+    Fading: fades is a list of AirFade, of tuples (path, doppler_hz, rice_k, key) or of dicts with those keys (rice_k and
+    key default to 0) -- the path of that index gets a Rayleigh (rice_k 0) or Rician gain of that Doppler spread, a float in Hz that is
+    rounded to whole millihertz. Without fades the handle is the one it was."""
 
-    def __init__(self, Fs, paths, ntx, nrx, sigma=None, seed=1, in_format=IN_CU8_CSDR, out_format=IN_CU8_CSDR, device=-1, max_slip=0):
+    def __init__(self, Fs, paths, ntx, nrx, sigma=None, seed=1, in_format=IN_CU8_CSDR, out_format=IN_CU8_CSDR, device=-1, max_slip=0, fades=None):
         self.L = lib()
         rows = []
         for p in paths:
@@ -1035,7 +1045,16 @@ class HipAir:
         sg = self._sigma(sigma, int(nrx))
         h = C.c_void_p()
         common = (int(Fs), int(in_format), int(out_format), int(ntx), int(nrx), len(rows))
-        if int(max_slip) == 0 and not any(len(p) > 5 and int(p[5]) for p in rows):
+        self.fades = [air_fade(f) for f in fades or ()]
+        if self.fades:
+            arr = (AirPathEx * max(len(rows), 1))()
+            for i, p in enumerate(rows):
+                arr[i] = AirPathEx(int(p[0]), int(p[1]), int(p[3]), int(p[4]), float(p[2]), int(p[5]) if len(p) > 5 else 0)
+            farr = (AirFade * len(self.fades))(*self.fades)
+            _chk(self.L.pirip_hip_air_create_fade(*common, C.addressof(arr) if rows else None, len(self.fades), C.addressof(farr),
+                                                  None if sg is None else sg.ctypes.data, int(seed), int(max_slip), device, C.byref(h)),
+                 "pirip_hip_air_create_fade")
+        elif int(max_slip) == 0 and not any(len(p) > 5 and int(p[5]) for p in rows):
             arr = (AirPath * max(len(rows), 1))()
             for i, (rx, tx, gain, delay, off) in enumerate(p[:5] for p in rows):
                 arr[i] = AirPath(int(rx), int(tx), int(delay), int(off), float(gain))
@@ -1097,6 +1116,27 @@ class HipAir:
         ms, left = C.c_int32(0), C.c_int64(0)
         _chk(self.L.pirip_hip_air_get_drift(self.h, C.byref(ms), C.byref(left)), "pirip_hip_air_get_drift")
         return ms.value, left.value
+
+
+def air_fade(f):
+    """an AirFade of an AirFade, a tuple (path, doppler_hz, rice_k, key) or a dict: Hz as a float, rounded to whole millihertz"""
+    if isinstance(f, AirFade):
+        return f
+    if isinstance(f, dict):
+        f = (f["path"], f["doppler_hz"], f.get("rice_k", 0.0), f.get("key", 0))
+    path, hz, k, key = (tuple(f) + (0.0, 0))[:4]
+    return AirFade(int(path), int(round(float(hz) * 1000.0)), float(k), int(key))
+
+
+def air_fade_table(Fs, seed, fade):
+    """pirip_hip_air_fade_table (host only): (w int32 [16], theta uint32 [16], scale, los), the integers and floats the kernel reads"""
+    import numpy as np
+    f = air_fade(fade)
+    w, theta = np.zeros(16, dtype=np.int32), np.zeros(16, dtype=np.uint32)
+    scale, los = C.c_float(0), C.c_float(0)
+    _chk(lib().pirip_hip_air_fade_table(int(Fs), int(seed), C.byref(f), w.ctypes.data, theta.ctypes.data, C.byref(scale), C.byref(los)),
+         "pirip_hip_air_fade_table")
+    return w, theta, float(scale.value), float(los.value)
 
 
 def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, out_stride, nsamp,

@@ -1,4 +1,4 @@
-// pirip_amd/csrc/air_handle.hpp -- the channel's handle behind include/pirip_hip.h's opaque pirip_hip_air and the arguments of its two
+// pirip_amd/csrc/air_handle.hpp -- the channel's handle behind include/pirip_hip.h's opaque pirip_hip_air and the arguments of its
 // kernels (air_kernels.hip owns the life cycle and the entry points of section O; the kernels' description is at the top of that file).
 // Library-private.
 #pragma once
@@ -24,6 +24,12 @@ constexpr int kAirLead = kAirTaps / 2 - 1;  // taps in front of the read positio
 constexpr int32_t kAirMaxPpb = 1000000;
 // samples of a drifting path's span beyond the tile's: the taps, and S moves by at most 3 across a tile at kAirMaxPpb, plus one
 constexpr int kAirSpanExtra = kAirTaps - 1 + 4 + 1;
+// fading paths: kAirScatter scatterers per fade, the gain on an absolute grid of kAirFadeGrid samples and the line between
+constexpr int kAirScatter = 16;
+constexpr int kAirFadeGrid = 16;
+constexpr int kAirFadeGridLog2 = 4;
+// grid points a tile can need: its first sample up to kAirFadeGrid - 1 into a cell, and the point behind the last cell: 130
+constexpr int kAirFadePoints = (kAirTile + kAirFadeGrid - 1 + kAirFadeGrid - 1) / kAirFadeGrid + 1;
 
 // a path as the mix kernel reads it: sorted by receiver, ascending path index within one
 struct AirPath { int32_t tx, delay, fres; float gain; };          // fres = f_p mod Fs in [0, Fs); 0: not rotated
@@ -55,6 +61,17 @@ struct AirDrift {
     int64_t age;                            // clock age of the call's first sample: age0 + (N0 - first)
 };
 
+// a fade as the kernel reads it (pirip_hip_air_fade_table makes it): scatterer j has the phase theta[j] + w[j] * (uint32) n
+struct AirFadeTable { int32_t w[kAirScatter]; uint32_t theta[kAirScatter]; float scale, los; };
+static_assert(sizeof(AirFadeTable) == 136, "the fade table is w, theta, scale and los");
+
+// what a handle with a fading path passes beside AirArgs and AirDrift (air_mix_fade_kernel only)
+struct AirFade {
+    const int32_t *index;                   // [npaths], in the order of paths: the path's row of `table`, -1: no fade
+    const AirFadeTable *table;
+    int grid_off;                           // byte offset of the tile's kAirFadePoints grid points in LDS, behind the staging area
+};
+
 }  // namespace pirip
 
 // (hidden: a handle's implicit destructor is no dynamic symbol of the library)
@@ -76,5 +93,9 @@ struct pirip_hip_air {
     float *d_sigma = nullptr;
     int32_t *d_ppb = nullptr;
     float *d_taps = nullptr;
+    // fading (4.15b): some path has a fade: the fade instantiation, its tables and its LDS
+    bool fade = false;
+    int32_t *d_fade_index = nullptr;
+    pirip::AirFadeTable *d_fade_table = nullptr;
 };
 #pragma GCC visibility pop

@@ -23,6 +23,9 @@
 // Drift: a path with a clock offset reads its transmitter at a fractional position through a 16-tap polyphase
 // interpolator. Handles that have such a path launch air_mix_drift_kernel, on a longer span and with the table; every other handle launches
 // air_mix_kernel, which is kept as it was. The slip budget is host state, checked when a call is enqueued.
+// Fading: a path with a fade has its samples multiplied by a gain that moves, the sum of sixteen scatterers whose 32-bit
+// phases are a function of the absolute index, made on a grid of 16 samples and a line between. Handles that have such a path launch
+// air_mix_fade_kernel, with the grid points of the tile in LDS behind the staging area; every other handle launches what it launched before.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -77,6 +80,135 @@ __device__ __forceinline__ void air_stage(const AirArgs &a, int tx, const AirRin
     __syncthreads();
     off_r = shift_r;
     off_w = units_r * 16 + shift_w - cnt_r * BSI;
+}
+
+// ---- air_mix_drift_kernel's pieces as functions, for air_mix_fade_kernel: that kernel is kept as it is, since calling them from it moved
+// its instructions. `sync`: the barrier between the reads of the path before and this path's staging (uniform per workgroup)
+
+// a static path: x_t[n - d_p] for the lane's outputs, staged as air_mix_kernel stages it
+template <int BSI>
+__device__ __forceinline__ void air_read_static(const AirArgs &a, const AirPath &pth, const AirRing &rg, int64_t j0, int cnt, int jl, int tid, bool sync,
+                                                v2f chi, v2f clo, char *smem, v2f (&v)[kAirPerThread])
+{
+    const int64_t s0 = j0 - pth.delay;                                  // the span's first sample, as an index of this call
+    const int cnt_r = s0 >= 0 ? 0 : (-s0 < cnt ? (int)-s0 : cnt);       // samples from the ring
+    // tile index of the first sample at or above the last reset
+    const int64_t vf = a.first - (a.N0 + s0);
+    const int vfirst = vf <= 0 ? 0 : (vf < kAirTile ? (int)vf : kAirTile);
+    if (sync) __syncthreads();
+    int off_r, off_w;
+    air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, cnt - cnt_r, tid, smem, off_r, off_w);
+#pragma unroll
+    for (int k = 0; k < kAirPerThread; k++) {
+        const int j = jl + k;
+        v[k] = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
+        if (j < vfirst) v[k] = v2f{0.f, 0.f};
+    }
+}
+
+// a path with a clock offset q != 0 reads its transmitter at n - d_p + S + rho / Q through the interpolator. Its span is
+// [i_first - 7, i_last + 8] with i = n - d_p + S: at most kAirTile + kAirSpanExtra samples, staged as a static path's is. A lane takes
+// (S, rho) of its first output from the tile's by exact integers, steps them per output, and reads tap k of an output at span position
+// j + (S - S_first) + k, from the part that position lies in; the table row of phase floor(1024 rho / Q) comes through the caches.
+template <int BSI>
+__device__ __forceinline__ void air_read_drift(const AirArgs &a, const AirDrift &d, const AirPath &pth, const AirRing &rg, int32_t q, int64_t j0, int cnt,
+                                               int jl, int tid, bool sync, v2f chi, v2f clo, char *smem, v2f (&v)[kAirPerThread])
+{
+    constexpr int kSpan = kAirTile + kAirSpanExtra;
+    int64_t S0;
+    int32_t rho0;
+    clock_slip(d.age + j0, q, S0, rho0);                                // the tile's first output
+    int32_t dS = 0, rho1 = rho0;
+    clock_advance(cnt - 1, q, dS, rho1);                                // ... and how far S moves up to its last
+    const int64_t s0 = j0 - pth.delay + S0 - kAirLead;                  // the span's first sample, as an index of this call
+    const int scnt = cnt + dS + kAirTaps - 1;
+    const int64_t vf = a.first - (a.N0 + s0);
+    const int vfirst = vf <= 0 ? 0 : (vf < kSpan ? (int)vf : kSpan);
+    const int cnt_r = s0 >= 0 ? 0 : (-s0 < scnt ? (int)-s0 : scnt);
+    if (sync) __syncthreads();
+    int off_r, off_w;
+    air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, scnt - cnt_r, tid, smem, off_r, off_w);
+    int32_t S = 0, rho = rho0;                                          // S from here on: relative to the tile's first
+    clock_advance(jl, q, S, rho);
+#pragma unroll
+    for (int k = 0; k < kAirPerThread; k++) {
+        const int u0 = jl + k + S;                                      // span position of the output's first tap
+        const float4 *row = (const float4 *)(d.taps + clock_phase_1024(rho) * kAirTaps);
+        v2f s = {0.f, 0.f};
+#pragma unroll
+        for (int c = 0; c < kAirTaps / 4; c++) {
+            const float4 t4 = row[c];
+            const float t[4] = {t4.x, t4.y, t4.z, t4.w};
+#pragma unroll
+            for (int e = 0; e < 4; e++) {
+                const int u = u0 + 4 * c + e;
+                v2f x = air_sample<BSI>(smem + (u < cnt_r ? off_r : off_w) + u * BSI, chi, clo);
+                if (u < vfirst) x = v2f{0.f, 0.f};
+                s = __builtin_elementwise_fma(v2f{t[e], t[e]}, x, s);
+            }
+        }
+        v[k] = s;
+        clock_step(q, S, rho);
+    }
+}
+
+// the mix, a static path's and a drifting one's alike: the rotation by the exact integer phase where f_p != 0, then acc = fma(a_p, v, acc)
+__device__ __forceinline__ void air_mix_path(const AirArgs &a, const AirPath &pth, uint32_t idx0, const v2f (&v)[kAirPerThread], v2f (&acc)[kAirPerThread])
+{
+    const v2f g = {pth.gain, pth.gain};
+    if (pth.fres != 0) {
+        uint32_t ph = (uint32_t)(int32_t)mulmod_fs((double)pth.fres, (double)idx0, a.Fs, a.inv_fs_d);
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) {
+            float cs, sn;
+            unit_phasor((int32_t)ph, a.Fs, a.two_over_fs, cs, sn);
+            acc[k] = __builtin_elementwise_fma(g, crot(v[k], cs, sn), acc[k]);
+            ph += (uint32_t)pth.fres;
+            if (ph >= (uint32_t)a.Fs) ph -= (uint32_t)a.Fs;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) acc[k] = __builtin_elementwise_fma(g, v[k], acc[k]);
+    }
+}
+
+// the receiver's noise on the lane's sums, and the store: air_mix_kernel's, statement for statement
+template <int BSO>
+__device__ __forceinline__ void air_finish(const AirArgs &a, int r, int64_t j0, int jl, int cnt, v2f (&acc)[kAirPerThread])
+{
+    const float sigma = a.sigma[r];
+    if (sigma > 0.f) {
+        const int64_t n_abs = a.N0 + j0 + jl;
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) {
+            float xr = acc[k].x, xi = acc[k].y;
+            add_awgn(a.seed, r, n_abs + k, sigma, xr, xi);
+            acc[k] = v2f{xr, xi};
+        }
+    }
+
+    if (jl >= cnt) return;
+    char *row = a.out + (size_t)r * a.out_stride + (size_t)(j0 + jl) * BSO;
+    const bool whole = a.aligned16 && jl + kAirPerThread <= cnt;
+    if (BSO == 2) {
+        uint32_t w[kAirPerThread];
+#pragma unroll
+        for (int k = 0; k < kAirPerThread; k++) w[k] = (uint32_t)quant_u8_csdr(acc[k].x) | ((uint32_t)quant_u8_csdr(acc[k].y) << 8);
+        if (whole) {
+            *(uint4 *)row = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((uint16_t *)row)[k] = (uint16_t)w[k];
+        }
+    } else {
+        if (whole) {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k += 2) ((float4 *)row)[k >> 1] = make_float4(acc[k].x, acc[k].y, acc[k + 1].x, acc[k + 1].y);
+        } else {
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((float2 *)row)[k] = make_float2(acc[k].x, acc[k].y);
+        }
+    }
 }
 
 // The mix kernel of a handle with a drifting path: air_mix_kernel below (kept as it is, so that a handle without drift runs the very
@@ -213,6 +345,84 @@ __global__ __launch_bounds__(kAirThreads) void air_mix_drift_kernel(AirArgs a, A
             for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((float2 *)row)[k] = make_float2(acc[k].x, acc[k].y);
         }
     }
+}
+
+// ---- fading -----------------------------------------------------------------------------------------------------------
+// Grid point k of a fade, at absolute index 16 k: scatterer j has the 32-bit phase theta_j + w_j * (uint32)(16 k), plain wrap-around
+// arithmetic on the absolute index; its top 24 bits are exact in a float, t in [-1, 1), and sincospif takes t half turns.
+__device__ __forceinline__ v2f fade_grid_point(const AirFadeTable &f, uint32_t n16)
+{
+    float C = 0.f, D = 0.f;
+#pragma unroll 4
+    for (int j = 0; j < kAirScatter; j++) {
+        const uint32_t psi = f.theta[j] + (uint32_t)f.w[j] * n16;
+        const float t = (float)((int32_t)psi >> 8) * 0x1p-23f;
+        float sn, cs;
+        sincospif(t, &sn, &cs);
+        C += cs; D += sn;
+    }
+    return v2f{__builtin_fmaf(f.scale, C, f.los), f.scale * D};
+}
+
+// The mix kernel of a handle with a fading path: air_mix_drift_kernel with one more branch, uniform per workgroup and path. A fading
+// path's samples -- a static path's or the interpolator's -- are multiplied by the gain g[n] of the receiver's index n before the mix:
+// thread i makes grid point (first of the tile) + i and writes it to LDS behind the staging area, between the barrier that separates the
+// paths and the one that ends the staging; a lane's 8 consecutive outputs lie in at most two cells, so it reads three grid points and forms
+// the line per output.
+// LDS: the staging area ((kAirTile [+ kAirSpanExtra with a drifting path]) * BSI + 64) + kAirFadePoints * 8 bytes
+template <int BSI, int BSO>
+__global__ __launch_bounds__(kAirThreads) void air_mix_fade_kernel(AirArgs a, AirDrift d, AirFade f)
+{
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int tid = threadIdx.x;
+    const int r = blockIdx.y;
+    const int64_t j0 = (int64_t)blockIdx.x * kAirTile;                 // first output of the tile (of this call)
+    const int cnt = (int)((a.n - j0) < kAirTile ? (a.n - j0) : kAirTile);
+    const int jl = tid * kAirPerThread;                                 // the thread's first output of the tile
+    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
+    // (n mod Fs) of the thread's first output
+    const uint32_t base = (uint32_t)(((int64_t)a.n0m + j0 % a.Fs) % a.Fs);
+    const uint32_t idx0 = (base + (uint32_t)jl) % (uint32_t)a.Fs;
+    v2f *grid = (v2f *)(smem + f.grid_off);
+    v2f acc[kAirPerThread];
+#pragma unroll
+    for (int k = 0; k < kAirPerThread; k++) acc[k] = v2f{0.f, 0.f};
+
+    const int p0 = a.rx_start[r], p1 = a.rx_start[r + 1];
+    for (int pi = p0; pi < p1; pi++) {
+        const AirPath pth = a.paths[pi];
+        const AirRing rg = a.rings[pth.tx];
+        const int32_t q = d.ppb[pi];
+        const int32_t fi = f.index[pi];
+        v2f v[kAirPerThread];                                           // what the path reads for the lane's outputs
+        if (pi > p0) __syncthreads();
+        if (fi >= 0) {
+            // the tile's first grid point, as (uint32) of its absolute index, and how many the tile needs: at most kAirFadePoints
+            const uint32_t nt = (uint32_t)(uint64_t)(a.N0 + j0), into = nt & (uint32_t)(kAirFadeGrid - 1);
+            const int points = (int)((into + (uint32_t)cnt - 1u) >> kAirFadeGridLog2) + 2;
+            if (tid < points) grid[tid] = fade_grid_point(f.table[fi], nt - into + (uint32_t)tid * (uint32_t)kAirFadeGrid);
+        }
+        if (q != 0) air_read_drift<BSI>(a, d, pth, rg, q, j0, cnt, jl, tid, false, chi, clo, smem, v);
+        else air_read_static<BSI>(a, pth, rg, j0, cnt, jl, tid, false, chi, clo, smem, v);
+        if (fi >= 0) {
+            // the lane's first output, in samples behind the tile's first grid point
+            const uint32_t l0 = ((uint32_t)(uint64_t)(a.N0 + j0) & (uint32_t)(kAirFadeGrid - 1)) + (uint32_t)jl;
+            const int c0 = (int)(l0 >> kAirFadeGridLog2);
+            const int c2 = c0 + 2 < kAirFadePoints ? c0 + 2 : kAirFadePoints - 1;       // (needed only where the lane crosses into cell c0 + 1)
+            const v2f ga = grid[c0], gb = grid[c0 + 1], gc = grid[c2];
+#pragma unroll
+            for (int k = 0; k < kAirPerThread; k++) {
+                const uint32_t l = l0 + (uint32_t)k;
+                const bool next = (int)(l >> kAirFadeGridLog2) != c0;
+                const v2f lo = next ? gb : ga, hi = next ? gc : gb;
+                const float mu = (float)(l & (uint32_t)(kAirFadeGrid - 1)) * (1.0f / kAirFadeGrid);
+                const v2f g = __builtin_elementwise_fma(v2f{mu, mu}, hi - lo, lo);
+                v[k] = crot(v[k], g.x, g.y);
+            }
+        }
+        air_mix_path(a, pth, idx0, v, acc);
+    }
+    air_finish<BSO>(a, r, j0, jl, cnt, acc);
 }
 
 // LDS: kAirTile * BSI + 64 bytes (the span's units: two parts, each with a unit of slack at either end)
@@ -394,12 +604,53 @@ int64_t last_age_of(int32_t max_slip, int32_t q_fast, int32_t q_slow)
     return last;
 }
 
-int air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths, const float *sigma,
-               uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out)
+// ---- a fade's table (4.15b): the integers and floats the kernel reads, made on the host in double and rounded once
+
+// noise_device.hpp's SplitMix64 finaliser, on the host
+uint64_t splitmix_host(uint64_t z)
+{
+    z += 0x9E3779B97F4A7C15ull;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
+    return z ^ (z >> 31);
+}
+
+int32_t max_doppler_millihz(int Fs) { return (int32_t)(1000 * (int64_t)Fs / 1024); }
+
+bool fade_ok(const pirip_air_fade &f) { return f.doppler_millihz >= 0 && std::isfinite(f.rice_k) && f.rice_k >= 0.f; }
+
+// scatterer j: the first draw of key (seed, key, j) is u_j (its top 53 bits), the draw of that draw gives theta_j (its top 32 bits)
+AirFadeTable fade_table(int Fs, uint64_t seed, const pirip_air_fade &f)
+{
+    const double pi = 3.14159265358979323846, fd = (double)f.doppler_millihz / 1000.0, K = (double)f.rice_k;
+    AirFadeTable t{};
+    for (int j = 0; j < kAirScatter; j++) {
+        const uint64_t r1 = splitmix_host(seed ^ splitmix_host(((uint64_t)f.key << 32) ^ (uint64_t)j));
+        const uint64_t r2 = splitmix_host(r1);
+        const double u = (double)(r1 >> 11) * 0x1p-53;
+        const double alpha = 2.0 * pi * ((double)j + u) / kAirScatter;
+        const double nu = fd * std::cos(alpha);
+        t.w[j] = (int32_t)std::llrint(nu / (double)Fs * 4294967296.0);
+        t.theta[j] = (uint32_t)(r2 >> 32);
+    }
+    t.scale = (float)std::sqrt(1.0 / (kAirScatter * (K + 1.0)));
+    t.los = (float)std::sqrt(K / (K + 1.0));
+    return t;
+}
+
+int air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths, int nfades,
+               const pirip_air_fade *fades, const float *sigma, uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out)
 {
     if (!out) return PIRIP_ERR_BAD_ARG;
     *out = nullptr;
     if (Fs < 2 || ntx < 1 || nrx < 1 || npaths < 0 || (npaths > 0 && !paths) || max_slip < 0) return PIRIP_ERR_BAD_ARG;
+    if (nfades < 0 || (nfades > 0 && !fades)) return PIRIP_ERR_BAD_ARG;
+    bool fast_fade = false;
+    for (int i = 0; i < nfades; i++) {
+        if (fades[i].path < 0 || fades[i].path >= npaths || !fade_ok(fades[i])) return PIRIP_ERR_BAD_ARG;
+        for (int k = 0; k < i; k++) if (fades[k].path == fades[i].path) return PIRIP_ERR_BAD_ARG;
+        if (Fs <= kMaxFs && fades[i].doppler_millihz > max_doppler_millihz(Fs)) fast_fade = true;
+    }
     if (in_format != PIRIP_IN_CU8_CSDR && in_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
     if (out_format != PIRIP_IN_CU8_CSDR && out_format != PIRIP_IN_CF32) return PIRIP_ERR_BAD_ARG;
     int max_delay = 0;
@@ -420,7 +671,7 @@ int air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npat
         if (-q.clock_ppb > q_slow) q_slow = -q.clock_ppb;
     }
     if (!sigma_ok(sigma, nrx)) return PIRIP_ERR_BAD_ARG;
-    if (unsupported || Fs > kMaxFs || max_delay > kAirMaxDelay || ntx > 65535 || nrx > 65535) return PIRIP_ERR_UNSUPPORTED;
+    if (unsupported || fast_fade || Fs > kMaxFs || max_delay > kAirMaxDelay || ntx > 65535 || nrx > 65535) return PIRIP_ERR_UNSUPPORTED;
     const U8Split u8 = csdr_u8_split();
     if (!u8.exact) return PIRIP_ERR_UNSUPPORTED;
     int dev = 0;
@@ -432,17 +683,26 @@ int air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npat
     h->bsi = bytes_per_sample(in_format); h->bso = bytes_per_sample(out_format);
     h->max_delay = max_delay; h->seed = seed; h->u8 = u8;
     h->max_slip = max_slip; h->drift = q_fast != 0 || q_slow != 0; h->last_age = last_age_of(max_slip, q_fast, q_slow);
+    h->fade = nfades > 0;
     // the paths of every receiver, ascending; every transmitter's ring: the smallest power of two that holds its longest lag -- a static
     // path's delay, a drifting one's with its slip and the leading taps
     std::vector<int32_t> rx_start(1, 0);
     std::vector<AirPath> sorted;
     std::vector<int32_t> ppb;
+    std::vector<int32_t> fade_index;                                    // per sorted path: its row of fade_tables, -1: none
+    std::vector<AirFadeTable> fade_tables;
     std::vector<int32_t> longest((size_t)ntx, 0);
     for (int r = 0; r < nrx; r++) {
         for (int p = 0; p < npaths; p++) {
             if (paths[p].rx != r) continue;
             sorted.push_back(AirPath{paths[p].tx, paths[p].delay, (int32_t)fs_residue(paths[p].offset_hz, Fs), paths[p].gain});
             ppb.push_back(paths[p].clock_ppb);
+            fade_index.push_back(-1);
+            for (int i = 0; i < nfades; i++) {
+                if (fades[i].path != p) continue;
+                fade_index.back() = (int32_t)fade_tables.size();
+                fade_tables.push_back(fade_table(Fs, seed, fades[i]));
+            }
             const int32_t q = paths[p].clock_ppb;
             const int32_t lag = paths[p].delay + (q != 0 ? kAirLead : 0) + (q < 0 ? max_slip : 0);
             if (lag > longest[(size_t)paths[p].tx]) longest[(size_t)paths[p].tx] = lag;
@@ -467,9 +727,11 @@ int air_create(int Fs, int in_format, int out_format, int ntx, int nrx, int npat
         PIRIP_TRY(m.upload(&h->d_rx_start, rx_start.data(), sizeof(int32_t) * rx_start.size()));
         PIRIP_TRY(m.upload(&h->d_paths, sorted.data(), sizeof(AirPath) * sorted.size()));
         PIRIP_TRY(m.upload(&h->d_sigma, sg.data(), sizeof(float) * sg.size()));
-        if (h->drift) {
-            PIRIP_TRY(m.upload(&h->d_ppb, ppb.data(), sizeof(int32_t) * ppb.size()));
-            PIRIP_TRY(m.upload(&h->d_taps, &interp_table().t[0][0], sizeof(InterpTable)));
+        if (h->drift || h->fade) PIRIP_TRY(m.upload(&h->d_ppb, ppb.data(), sizeof(int32_t) * ppb.size()));
+        if (h->drift) PIRIP_TRY(m.upload(&h->d_taps, &interp_table().t[0][0], sizeof(InterpTable)));
+        if (h->fade) {
+            PIRIP_TRY(m.upload(&h->d_fade_index, fade_index.data(), sizeof(int32_t) * fade_index.size()));
+            PIRIP_TRY(m.upload(&h->d_fade_table, fade_tables.data(), sizeof(AirFadeTable) * fade_tables.size()));
         }
         return PIRIP_OK;
     };
@@ -500,13 +762,29 @@ int pirip_hip_air_create(int Fs, int in_format, int out_format, int ntx, int nrx
 {
     std::vector<pirip_air_path_ex> ex;
     for (int p = 0; paths && p < npaths; p++) ex.push_back(pirip_air_path_ex{paths[p].rx, paths[p].tx, paths[p].delay, paths[p].offset_hz, paths[p].gain, 0});
-    return air_create(Fs, in_format, out_format, ntx, nrx, npaths, paths ? ex.data() : nullptr, sigma, seed, 0, device, out);
+    return air_create(Fs, in_format, out_format, ntx, nrx, npaths, paths ? ex.data() : nullptr, 0, nullptr, sigma, seed, 0, device, out);
 }
 
 int pirip_hip_air_create_ex(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths, const float *sigma,
                             uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out)
 {
-    return air_create(Fs, in_format, out_format, ntx, nrx, npaths, paths, sigma, seed, max_slip, device, out);
+    return air_create(Fs, in_format, out_format, ntx, nrx, npaths, paths, 0, nullptr, sigma, seed, max_slip, device, out);
+}
+
+int pirip_hip_air_create_fade(int Fs, int in_format, int out_format, int ntx, int nrx, int npaths, const pirip_air_path_ex *paths, int nfades,
+                              const pirip_air_fade *fades, const float *sigma, uint64_t seed, int32_t max_slip, int device, pirip_hip_air **out)
+{
+    return air_create(Fs, in_format, out_format, ntx, nrx, npaths, paths, nfades, fades, sigma, seed, max_slip, device, out);
+}
+
+int pirip_hip_air_fade_table(int Fs, uint64_t seed, const pirip_air_fade *fade, int32_t w[16], uint32_t theta[16], float *scale, float *los)
+{
+    if (Fs < 2 || !fade || !w || !theta || !scale || !los || !fade_ok(*fade)) return PIRIP_ERR_BAD_ARG;
+    if (fade->doppler_millihz > max_doppler_millihz(Fs)) return PIRIP_ERR_UNSUPPORTED;
+    const AirFadeTable t = fade_table(Fs, seed, *fade);
+    for (int j = 0; j < kAirScatter; j++) { w[j] = t.w[j]; theta[j] = t.theta[j]; }
+    *scale = t.scale; *los = t.los;
+    return PIRIP_OK;
 }
 
 int pirip_hip_air_interp_table(float *taps, int *nphases, int *ntaps)
@@ -584,8 +862,15 @@ int pirip_hip_air_push(pirip_hip_air *air, const void *d_in, size_t in_stride_by
     // a handle with a drifting path: the drift instantiation on a longer span; every other one: the static kernel on the tile's
     const size_t lds = (size_t)(kAirTile + (air->drift ? kAirSpanExtra : 0)) * (size_t)air->bsi + 64;
     const AirDrift d{air->d_ppb, air->d_taps, air->age0 + (air->pos - air->first)};
-    const int kind = (air->drift ? 4 : 0) + (air->bsi == 2 ? 0 : 2) + (air->bso == 2 ? 0 : 1);
+    // a handle with a fading path: the fade instantiation, the tile's grid points behind the staging area
+    const AirFade f{air->d_fade_index, air->d_fade_table, (int)lds};
+    const size_t lds_fade = lds + (size_t)kAirFadePoints * sizeof(float2);
+    const int kind = (air->fade ? 8 : air->drift ? 4 : 0) + (air->bsi == 2 ? 0 : 2) + (air->bso == 2 ? 0 : 1);
     switch (kind) {
+    case 8: hipLaunchKernelGGL((air_mix_fade_kernel<2, 2>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
+    case 9: hipLaunchKernelGGL((air_mix_fade_kernel<2, 8>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
+    case 10: hipLaunchKernelGGL((air_mix_fade_kernel<8, 2>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
+    case 11: hipLaunchKernelGGL((air_mix_fade_kernel<8, 8>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
     case 0: hipLaunchKernelGGL((air_mix_kernel<2, 2>), grid, dim3(kAirThreads), lds, st, a); break;
     case 1: hipLaunchKernelGGL((air_mix_kernel<2, 8>), grid, dim3(kAirThreads), lds, st, a); break;
     case 2: hipLaunchKernelGGL((air_mix_kernel<8, 2>), grid, dim3(kAirThreads), lds, st, a); break;

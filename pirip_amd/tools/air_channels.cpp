@@ -2,12 +2,14 @@
 // or the air (its test/loopback_rtl_fsk.sh and README "MDS tests"), as one call per block of the channel (include/pirip_hip.h section O).
 //
 //   air_channels --fs Fs [--in-format u8|cf32] [--out-format u8|cf32] [--path rx,tx,gain,delay,offset[,ppb]]... [--max-slip N]
-//                [--sigma s0,s1,...] [--seed N] [--block N] [--start n0] [-q] IN_0 ... IN_{T-1} -- OUT_0 ... OUT_{R-1}
+//                [--fade path,doppler_millihz,rice_k[,key]]... [--sigma s0,s1,...] [--seed N] [--block N] [--start n0] [-q] IN_0 ... IN_{T-1} -- OUT_0 ... OUT_{R-1}
 //
 // T input files, one per transmitter, and behind "--" R output files, one per receiver. --path (repeated, in path order): received stream,
 // transmitted stream, real gain, delay in samples, carrier offset in integer Hz and, optionally, the clock offset of the path's transmitter
 // in parts per billion, which wants --max-slip N: the whole samples such a path may slip before the tool stops (section O, drift; without
-// either the tool makes what it made before them). --sigma: one value for every receiver, or one per receiver
+// either the tool makes what it made before them). --fade (repeated): the path of that index, counted in --path order from 0, gets a
+// Rayleigh (rice_k 0) or Rician gain with a Doppler spread in millihertz, drawn with the key (default 0) (section O, fading; without it
+// the tool makes what it makes without). --sigma: one value for every receiver, or one per receiver
 // (default 0). --start: the absolute index of the first sample (default 0; earlier samples are zero). --block: samples per call (default
 // 65536); the files are read block by block to the end of the shortest input, the last block as long as what is left, and every block is
 // written as it is made.
@@ -27,7 +29,7 @@ static int usage()
 {
     fprintf(stderr,
             "air_channels (pirip_hip): --fs Fs [--in-format u8|cf32] [--out-format u8|cf32] [--path rx,tx,gain,delay,offset[,ppb]]...\n"
-            "        [--max-slip N] [--sigma s0,s1,...] [--seed N] [--block N] [--start n0] [-q] IN_0 ... IN_{T-1} -- OUT_0 ... OUT_{R-1}\n");
+            "        [--max-slip N] [--fade path,doppler_millihz,rice_k[,key]]... [--sigma s0,s1,...] [--seed N] [--block N] [--start n0] [-q] IN_0 ... IN_{T-1} -- OUT_0 ... OUT_{R-1}\n");
     return 1;
 }
 
@@ -50,11 +52,12 @@ int main(int argc, char **argv)
     bool drift = false;
     unsigned long long seed = 1;
     std::vector<pirip_air_path_ex> paths;
+    std::vector<pirip_air_fade> fades;
     std::vector<float> sigma;
     static struct option lopts[] = {{"fs", required_argument, 0, 1000}, {"in-format", required_argument, 0, 1001},
                                     {"out-format", required_argument, 0, 1002}, {"path", required_argument, 0, 1003},
                                     {"sigma", required_argument, 0, 1004}, {"seed", required_argument, 0, 1005}, {"block", required_argument, 0, 1006},
-                                    {"start", required_argument, 0, 1007}, {"max-slip", required_argument, 0, 1008}, {"help", no_argument, 0, 'h'},
+                                    {"start", required_argument, 0, 1007}, {"max-slip", required_argument, 0, 1008}, {"fade", required_argument, 0, 1009}, {"help", no_argument, 0, 'h'},
                                     {0, 0, 0, 0}};
     int o, oi;
     // ("+": the first file name ends the options, so that "--" stays where it separates inputs from outputs)
@@ -80,6 +83,16 @@ int main(int argc, char **argv)
         case 1006: block = atoll(optarg); break;
         case 1007: start = atoll(optarg); break;
         case 1008: max_slip = atoll(optarg); break;
+        case 1009: {
+            std::vector<double> v;
+            if (!parse_list(optarg, v, strtod) || (v.size() != 3 && v.size() != 4) || v[0] != (double)(int32_t)v[0] || v[1] != (double)(int32_t)v[1] ||
+                (v.size() == 4 && v[3] != (double)(uint32_t)v[3])) {
+                fprintf(stderr, "air_channels: --fade wants path,doppler_millihz,rice_k[,key]: integers but for rice_k\n");
+                return 1;
+            }
+            fades.push_back(pirip_air_fade{(int32_t)v[0], (int32_t)v[1], (float)v[2], v.size() == 4 ? (uint32_t)v[3] : 0u});
+            break;
+        }
         default: return usage();
         }
     }
@@ -106,7 +119,11 @@ int main(int argc, char **argv)
     }
 
     AirHandle air;
-    if (drift || max_slip) {
+    if (!fades.empty()) {
+        PIRIPOK(pirip_hip_air_create_fade((int)Fs, in_format, out_format, T, R, (int)paths.size(), paths.data(), (int)fades.size(), fades.data(),
+                                          sigma.empty() ? nullptr : sigma.data(), (uint64_t)seed, (int32_t)max_slip, -1, air.out()),
+                "channel (--path / --fade / --max-slip / --sigma / --fs)");
+    } else if (drift || max_slip) {
         PIRIPOK(pirip_hip_air_create_ex((int)Fs, in_format, out_format, T, R, (int)paths.size(), paths.data(), sigma.empty() ? nullptr : sigma.data(),
                                         (uint64_t)seed, (int32_t)max_slip, -1, air.out()), "channel (--path / --max-slip / --sigma / --fs)");
     } else {

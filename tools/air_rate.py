@@ -2,6 +2,7 @@
 """Rate of the channel (include/pirip_hip.h section O): T transmitted wideband u8 IQ streams onto R received ones on the device.
 
     python tools/air_rate.py [--receivers 64] [--paths 2] [--n 1048576] [--calls 1000] [--reps 5] [--sigma 0.1] [--clock-ppb 0]
+                             [--fade-millihz 0] [--rice-k 0]
 
 R receivers x K paths each (two transmitters; every path rotated, delays up to 4097 samples), u8 in and out, n samples per call.
 Printed per variant -- with noise, and with sigma 0 (no Box-Muller) --: wideband samples/s of pirip_hip_air_push over --calls consecutive
@@ -10,7 +11,9 @@ calls, and the HBM traffic it implies at (2 K + 2) bytes per output sample (ever
 fraction of a second of back-to-back calls bracketed by device synchronisation.
 --clock-ppb Q (default 0: the run above and nothing else) adds, behind that run and in the same session, the same paths with a clock
 offset of Q parts per billion each: every delay grows by 8 + max_slip, max_slip being what one run of --calls calls
-slips, and every run starts from a reset, which enqueues nothing."""
+slips, and every run starts from a reset, which enqueues nothing.
+--fade-millihz N [--rice-k K] (default 0: nothing more) adds, in the same session, the static paths with a fade of N millihertz and Rician
+K on every one of them, keyed by the path's index."""
 import argparse
 import os
 import sys
@@ -47,6 +50,8 @@ def main():
     ap.add_argument("--sigma", type=float, default=0.1)
     ap.add_argument("--hbm-gbs", type=float, default=8000.0)
     ap.add_argument("--clock-ppb", type=int, default=0)
+    ap.add_argument("--fade-millihz", type=int, default=0)
+    ap.add_argument("--rice-k", type=float, default=0.0)
     a = ap.parse_args()
     R, K, n, Fs, T = a.receivers, a.paths, a.n, 2400000, 2
     print(f"device: {torch.cuda.get_device_name(0)}; {R} receivers x {K} paths, {T} transmitters, u8 -> u8, {n} samples per call, {a.calls} calls per run")
@@ -55,12 +60,15 @@ def main():
     d_in = torch.randint(0, 256, (T, n * 2), dtype=torch.uint8, device="cuda")
     d_out = torch.zeros((R, n * 2), dtype=torch.uint8, device="cuda")
     bps = 2.0 * K + 2.0
-    variants = [("", paths, 0)]
+    variants = [("", paths, 0, None)]
     if a.clock_ppb:
         slip = abs(a.clock_ppb) * n * a.calls // 10 ** 9 + 1
-        variants.append((f"clock {a.clock_ppb} ppb, max_slip {slip}, ", [(r, t, g, d + 8 + slip, f, a.clock_ppb) for r, t, g, d, f in paths], slip))
-    for tag, pth, slip, sigma in [(t, p, s, sg) for t, p, s in variants for sg in (a.sigma, 0.0)]:
-        air = pirip_amd.HipAir(Fs, pth, T, R, sigma=sigma, seed=1, max_slip=slip)
+        variants.append((f"clock {a.clock_ppb} ppb, max_slip {slip}, ", [(r, t, g, d + 8 + slip, f, a.clock_ppb) for r, t, g, d, f in paths], slip, None))
+    if a.fade_millihz:
+        fades = [pirip_amd.AirFade(i, a.fade_millihz, a.rice_k, i) for i in range(len(paths))]
+        variants.append((f"fade {a.fade_millihz} mHz, K {a.rice_k:g}, ", paths, 0, fades))
+    for tag, pth, slip, fades, sigma in [(t, p, s, fd, sg) for t, p, s, fd in variants for sg in (a.sigma, 0.0)]:
+        air = pirip_amd.HipAir(Fs, pth, T, R, sigma=sigma, seed=1, max_slip=slip, fades=fades)
 
         def run():
             if slip:
