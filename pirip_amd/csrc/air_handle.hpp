@@ -54,7 +54,7 @@ struct AirArgs {
     double inv_fs_d;
 };
 
-// what a handle with a drifting path passes beside AirArgs (air_mix_drift_kernel only)
+// what the mix body reads with its DRIFT switch on (air_mix_drift_kernel and air_mix_fade_kernel pass it beside AirArgs)
 struct AirDrift {
     const int32_t *ppb;                     // [npaths], in the order of paths: clock offset in parts per billion, 0: a static path
     const float *taps;                      // [kAirPhases][kAirTaps], the host's table
@@ -65,7 +65,7 @@ struct AirDrift {
 struct AirFadeTable { int32_t w[kAirScatter]; uint32_t theta[kAirScatter]; float scale, los; };
 static_assert(sizeof(AirFadeTable) == 136, "the fade table is w, theta, scale and los");
 
-// what a handle with a fading path passes beside AirArgs and AirDrift (air_mix_fade_kernel only)
+// what the mix body reads with its FADE switch on (air_mix_fade_kernel passes it beside AirArgs and AirDrift)
 struct AirFade {
     const int32_t *index;                   // [npaths], in the order of paths: the path's row of `table`, -1: no fade
     const AirFadeTable *table;
@@ -83,7 +83,7 @@ struct pirip_hip_air {
     // drift (4.15a), host state: the clock age of sample `first`, the slip budget and the last clock age that stays inside it
     int64_t age0 = 0, last_age = 0;
     int32_t max_slip = 0;
-    bool drift = false;                     // some path has a clock offset: the drift instantiation, its table and its LDS
+    bool drift = false;                     // some path has a clock offset: the body's DRIFT switch, the table and the longer span in LDS
     pirip::U8Split u8{};
     pirip::DevMem mem;
     char *d_ring = nullptr;
@@ -93,7 +93,7 @@ struct pirip_hip_air {
     float *d_sigma = nullptr;
     int32_t *d_ppb = nullptr;
     float *d_taps = nullptr;
-    // fading (4.15b): some path has a fade: the fade instantiation, its tables and its LDS
+    // fading (4.15b): some path has a fade: the body's FADE switch (with DRIFT), the fades' tables and the grid points in LDS
     bool fade = false;
     int32_t *d_fade_index = nullptr;
     pirip::AirFadeTable *d_fade_table = nullptr;

@@ -21,11 +21,15 @@
 // Carry kernel, behind the mix kernel in stream order: the call's last min(n, ring) samples of every transmitter go to their ring slots
 // (absolute index modulo the ring), sample by sample.
 // Drift: a path with a clock offset reads its transmitter at a fractional position through a 16-tap polyphase
-// interpolator. Handles that have such a path launch air_mix_drift_kernel, on a longer span and with the table; every other handle launches
-// air_mix_kernel, which is kept as it was. The slip budget is host state, checked when a call is enqueued.
+// interpolator, on a longer span and with the table. The slip budget is host state, checked when a call is enqueued.
 // Fading: a path with a fade has its samples multiplied by a gain that moves, the sum of sixteen scatterers whose 32-bit
-// phases are a function of the absolute index, made on a grid of 16 samples and a line between. Handles that have such a path launch
-// air_mix_fade_kernel, with the grid points of the tile in LDS behind the staging area; every other handle launches what it launched before.
+// phases are a function of the absolute index, made on a grid of 16 samples and a line between, the grid points of the tile in LDS behind
+// the staging area.
+// The mix kernel is one body, air_mix_body<bytes in, bytes out, DRIFT, FADE>, whose two compile-time switches say whether a path may have a
+// clock offset and whether it may have a fade; per path it stages and reads (a static span or the interpolator's), applies the fade, mixes,
+// and behind the paths adds the noise and stores. Three thin kernels name its instantiations: air_mix_kernel (neither switch; AirArgs)
+// for handles without such paths, air_mix_drift_kernel (DRIFT; + AirDrift) for handles with a drifting path, air_mix_fade_kernel (both;
+// + AirFade) for handles with a fading one. A path without offset and fade gives the same words in all three.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -54,12 +58,25 @@ __device__ __forceinline__ v2f air_sample(const char *p, v2f chi, v2f clo)
     return *(const v2f *)p;
 }
 
-// cnt_r + cnt_w consecutive samples of transmitter tx from call index s0 on, into LDS as the 16-byte units that hold them: the cnt_r below
-// the call's first sample from the ring, the rest from the call's row. Sample u of the span is then at (u < cnt_r ? off_r : off_w) + u * BSI.
+// ---- the pieces of air_mix_body below, which owns the barrier between the reads of the path before and a path's staging
+
+// A span of a transmitter staged in LDS: sample u of it is at (u < cnt_r ? off_r : off_w) + u * BSI, and the samples below vfirst lie
+// below the last reset
+struct AirSpan { int cnt_r, off_r, off_w, vfirst; };
+
+// scnt consecutive samples of transmitter tx from call index s0 on, into LDS as the 16-byte units that hold them: the cnt_r below the
+// call's first sample from the ring, the rest from the call's row. `limit` is what vfirst is clamped to on its way to an int: any value
+// that no span position of a stored output reaches. Which one a caller passes is tuning, since it moves the compiler's register
+// allocation: the tile's count for the kernel of static paths (72 VGPRs and 7 waves per SIMD with u8 input; 74 and 6 with the constant),
+// the constants for the other two, which then compile to what they were before the kernels shared a body.
 template <int BSI>
-__device__ __forceinline__ void air_stage(const AirArgs &a, int tx, const AirRing &rg, int64_t s0, int cnt_r, int cnt_w, int tid, char *smem,
-                                          int &off_r, int &off_w)
+__device__ __forceinline__ AirSpan air_stage(const AirArgs &a, int tx, const AirRing &rg, int64_t s0, int scnt, int limit, int tid, char *smem)
 {
+    const int cnt_r = s0 >= 0 ? 0 : (-s0 < scnt ? (int)-s0 : scnt);     // samples from the ring
+    const int cnt_w = scnt - cnt_r;                                     // samples from the call's row
+    // span index of the first sample at or above the last reset
+    const int64_t vf = a.first - (a.N0 + s0);
+    const int vfirst = vf <= 0 ? 0 : (vf < limit ? (int)vf : limit);
     int shift_r = 0, units_r = 0;
     if (cnt_r > 0) {
         const uint32_t b0 = (uint32_t)((uint64_t)(a.N0 + s0) & rg.mask) * BSI;            // (a ring holds at most 2^20 samples of 8 bytes)
@@ -78,32 +95,15 @@ __device__ __forceinline__ void air_stage(const AirArgs &a, int tx, const AirRin
         for (int u = tid; u < units_w; u += kAirThreads) ((uint4 *)smem)[units_r + u] = src[u];
     }
     __syncthreads();
-    off_r = shift_r;
-    off_w = units_r * 16 + shift_w - cnt_r * BSI;
+    return AirSpan{cnt_r, shift_r, units_r * 16 + shift_w - cnt_r * BSI, vfirst};
 }
 
-// ---- air_mix_drift_kernel's pieces as functions, for air_mix_fade_kernel: that kernel is kept as it is, since calling them from it moved
-// its instructions. `sync`: the barrier between the reads of the path before and this path's staging (uniform per workgroup)
-
-// a static path: x_t[n - d_p] for the lane's outputs, staged as air_mix_kernel stages it
 template <int BSI>
-__device__ __forceinline__ void air_read_static(const AirArgs &a, const AirPath &pth, const AirRing &rg, int64_t j0, int cnt, int jl, int tid, bool sync,
-                                                v2f chi, v2f clo, char *smem, v2f (&v)[kAirPerThread])
+__device__ __forceinline__ v2f air_span_sample(const char *smem, const AirSpan &sp, int u, v2f chi, v2f clo)
 {
-    const int64_t s0 = j0 - pth.delay;                                  // the span's first sample, as an index of this call
-    const int cnt_r = s0 >= 0 ? 0 : (-s0 < cnt ? (int)-s0 : cnt);       // samples from the ring
-    // tile index of the first sample at or above the last reset
-    const int64_t vf = a.first - (a.N0 + s0);
-    const int vfirst = vf <= 0 ? 0 : (vf < kAirTile ? (int)vf : kAirTile);
-    if (sync) __syncthreads();
-    int off_r, off_w;
-    air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, cnt - cnt_r, tid, smem, off_r, off_w);
-#pragma unroll
-    for (int k = 0; k < kAirPerThread; k++) {
-        const int j = jl + k;
-        v[k] = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
-        if (j < vfirst) v[k] = v2f{0.f, 0.f};
-    }
+    v2f x = air_sample<BSI>(smem + (u < sp.cnt_r ? sp.off_r : sp.off_w) + u * BSI, chi, clo);
+    if (u < sp.vfirst) x = v2f{0.f, 0.f};
+    return x;
 }
 
 // a path with a clock offset q != 0 reads its transmitter at n - d_p + S + rho / Q through the interpolator. Its span is
@@ -112,22 +112,15 @@ __device__ __forceinline__ void air_read_static(const AirArgs &a, const AirPath 
 // j + (S - S_first) + k, from the part that position lies in; the table row of phase floor(1024 rho / Q) comes through the caches.
 template <int BSI>
 __device__ __forceinline__ void air_read_drift(const AirArgs &a, const AirDrift &d, const AirPath &pth, const AirRing &rg, int32_t q, int64_t j0, int cnt,
-                                               int jl, int tid, bool sync, v2f chi, v2f clo, char *smem, v2f (&v)[kAirPerThread])
+                                               int jl, int tid, v2f chi, v2f clo, char *smem, v2f (&v)[kAirPerThread])
 {
-    constexpr int kSpan = kAirTile + kAirSpanExtra;
     int64_t S0;
     int32_t rho0;
     clock_slip(d.age + j0, q, S0, rho0);                                // the tile's first output
     int32_t dS = 0, rho1 = rho0;
     clock_advance(cnt - 1, q, dS, rho1);                                // ... and how far S moves up to its last
-    const int64_t s0 = j0 - pth.delay + S0 - kAirLead;                  // the span's first sample, as an index of this call
-    const int scnt = cnt + dS + kAirTaps - 1;
-    const int64_t vf = a.first - (a.N0 + s0);
-    const int vfirst = vf <= 0 ? 0 : (vf < kSpan ? (int)vf : kSpan);
-    const int cnt_r = s0 >= 0 ? 0 : (-s0 < scnt ? (int)-s0 : scnt);
-    if (sync) __syncthreads();
-    int off_r, off_w;
-    air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, scnt - cnt_r, tid, smem, off_r, off_w);
+    // the span's first sample, as an index of this call, and its length
+    const AirSpan sp = air_stage<BSI>(a, pth.tx, rg, j0 - pth.delay + S0 - kAirLead, cnt + dS + kAirTaps - 1, kAirTile + kAirSpanExtra, tid, smem);
     int32_t S = 0, rho = rho0;                                          // S from here on: relative to the tile's first
     clock_advance(jl, q, S, rho);
 #pragma unroll
@@ -140,20 +133,17 @@ __device__ __forceinline__ void air_read_drift(const AirArgs &a, const AirDrift 
             const float4 t4 = row[c];
             const float t[4] = {t4.x, t4.y, t4.z, t4.w};
 #pragma unroll
-            for (int e = 0; e < 4; e++) {
-                const int u = u0 + 4 * c + e;
-                v2f x = air_sample<BSI>(smem + (u < cnt_r ? off_r : off_w) + u * BSI, chi, clo);
-                if (u < vfirst) x = v2f{0.f, 0.f};
-                s = __builtin_elementwise_fma(v2f{t[e], t[e]}, x, s);
-            }
+            for (int e = 0; e < 4; e++) s = __builtin_elementwise_fma(v2f{t[e], t[e]}, air_span_sample<BSI>(smem, sp, u0 + 4 * c + e, chi, clo), s);
         }
         v[k] = s;
         clock_step(q, S, rho);
     }
 }
 
-// the mix, a static path's and a drifting one's alike: the rotation by the exact integer phase where f_p != 0, then acc = fma(a_p, v, acc)
-__device__ __forceinline__ void air_mix_path(const AirArgs &a, const AirPath &pth, uint32_t idx0, const v2f (&v)[kAirPerThread], v2f (&acc)[kAirPerThread])
+// the mix of a path whose sample for the lane's output k is v(k): the rotation by the exact integer phase where f_p != 0, then
+// acc = fma(a_p, v, acc)
+template <typename V>
+__device__ __forceinline__ void air_mix_path(const AirArgs &a, const AirPath &pth, uint32_t idx0, V v, v2f (&acc)[kAirPerThread])
 {
     const v2f g = {pth.gain, pth.gain};
     if (pth.fres != 0) {
@@ -162,17 +152,17 @@ __device__ __forceinline__ void air_mix_path(const AirArgs &a, const AirPath &pt
         for (int k = 0; k < kAirPerThread; k++) {
             float cs, sn;
             unit_phasor((int32_t)ph, a.Fs, a.two_over_fs, cs, sn);
-            acc[k] = __builtin_elementwise_fma(g, crot(v[k], cs, sn), acc[k]);
+            acc[k] = __builtin_elementwise_fma(g, crot(v(k), cs, sn), acc[k]);
             ph += (uint32_t)pth.fres;
             if (ph >= (uint32_t)a.Fs) ph -= (uint32_t)a.Fs;
         }
     } else {
 #pragma unroll
-        for (int k = 0; k < kAirPerThread; k++) acc[k] = __builtin_elementwise_fma(g, v[k], acc[k]);
+        for (int k = 0; k < kAirPerThread; k++) acc[k] = __builtin_elementwise_fma(g, v(k), acc[k]);
     }
 }
 
-// the receiver's noise on the lane's sums, and the store: air_mix_kernel's, statement for statement
+// the receiver's noise on the lane's sums, and the store
 template <int BSO>
 __device__ __forceinline__ void air_finish(const AirArgs &a, int r, int64_t j0, int jl, int cnt, v2f (&acc)[kAirPerThread])
 {
@@ -211,143 +201,9 @@ __device__ __forceinline__ void air_finish(const AirArgs &a, int r, int64_t j0, 
     }
 }
 
-// The mix kernel of a handle with a drifting path: air_mix_kernel below (kept as it is, so that a handle without drift runs the very
-// code it ran before) with one more branch, uniform per workgroup and path. A path with a clock offset q != 0 reads its transmitter at
-// n - d_p + S + rho / Q through the interpolator. Its span is [i_first - 7, i_last + 8] with i = n - d_p + S: at most
-// kAirTile + kAirSpanExtra samples, staged as a static path's is. A lane takes (S, rho) of its first output from the tile's by exact
-// integers, steps them per output, and reads tap k of an output at span position j + (S - S_first) + k, from the part that position lies
-// in; the table row of phase floor(1024 rho / Q) comes through the caches. A path with q == 0 takes the static kernel's steps.
-// LDS: (kAirTile + kAirSpanExtra) * BSI + 64 bytes
-template <int BSI, int BSO>
-__global__ __launch_bounds__(kAirThreads) void air_mix_drift_kernel(AirArgs a, AirDrift d)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int r = blockIdx.y;
-    const int64_t j0 = (int64_t)blockIdx.x * kAirTile;                 // first output of the tile (of this call)
-    const int cnt = (int)((a.n - j0) < kAirTile ? (a.n - j0) : kAirTile);
-    const int jl = tid * kAirPerThread;                                 // the thread's first output of the tile
-    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
-    // (n mod Fs) of the thread's first output
-    const uint32_t base = (uint32_t)(((int64_t)a.n0m + j0 % a.Fs) % a.Fs);
-    const uint32_t idx0 = (base + (uint32_t)jl) % (uint32_t)a.Fs;
-    v2f acc[kAirPerThread];
-#pragma unroll
-    for (int k = 0; k < kAirPerThread; k++) acc[k] = v2f{0.f, 0.f};
+// ---- fading: a fading path's samples -- a static path's or the interpolator's -- are multiplied by the gain g[n] of the
+// receiver's index n before the mix
 
-    const int p0 = a.rx_start[r], p1 = a.rx_start[r + 1];
-    for (int pi = p0; pi < p1; pi++) {
-        const AirPath pth = a.paths[pi];
-        const AirRing rg = a.rings[pth.tx];
-        const int32_t q = d.ppb[pi];
-        v2f v[kAirPerThread];                                           // what the path reads for the lane's outputs
-        if (q != 0) {
-            constexpr int kSpan = kAirTile + kAirSpanExtra;
-            int64_t S0;
-            int32_t rho0;
-            clock_slip(d.age + j0, q, S0, rho0);                        // the tile's first output
-            int32_t dS = 0, rho1 = rho0;
-            clock_advance(cnt - 1, q, dS, rho1);                        // ... and how far S moves up to its last
-            const int64_t s0 = j0 - pth.delay + S0 - kAirLead;          // the span's first sample, as an index of this call
-            const int scnt = cnt + dS + kAirTaps - 1;
-            const int64_t vf = a.first - (a.N0 + s0);
-            const int vfirst = vf <= 0 ? 0 : (vf < kSpan ? (int)vf : kSpan);
-            const int cnt_r = s0 >= 0 ? 0 : (-s0 < scnt ? (int)-s0 : scnt);
-            if (pi > p0) __syncthreads();
-            int off_r, off_w;
-            air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, scnt - cnt_r, tid, smem, off_r, off_w);
-            int32_t S = 0, rho = rho0;                                  // S from here on: relative to the tile's first
-            clock_advance(jl, q, S, rho);
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) {
-                const int u0 = jl + k + S;                              // span position of the output's first tap
-                const float4 *row = (const float4 *)(d.taps + clock_phase_1024(rho) * kAirTaps);
-                v2f s = {0.f, 0.f};
-#pragma unroll
-                for (int c = 0; c < kAirTaps / 4; c++) {
-                    const float4 t4 = row[c];
-                    const float t[4] = {t4.x, t4.y, t4.z, t4.w};
-#pragma unroll
-                    for (int e = 0; e < 4; e++) {
-                        const int u = u0 + 4 * c + e;
-                        v2f x = air_sample<BSI>(smem + (u < cnt_r ? off_r : off_w) + u * BSI, chi, clo);
-                        if (u < vfirst) x = v2f{0.f, 0.f};
-                        s = __builtin_elementwise_fma(v2f{t[e], t[e]}, x, s);
-                    }
-                }
-                v[k] = s;
-                clock_step(q, S, rho);
-            }
-        } else {
-            const int64_t s0 = j0 - pth.delay;                          // the span's first sample, as an index of this call
-            const int cnt_r = s0 >= 0 ? 0 : (-s0 < cnt ? (int)-s0 : cnt);       // samples from the ring
-            // tile index of the first sample at or above the last reset
-            const int64_t vf = a.first - (a.N0 + s0);
-            const int vfirst = vf <= 0 ? 0 : (vf < kAirTile ? (int)vf : kAirTile);
-            if (pi > p0) __syncthreads();
-            int off_r, off_w;
-            air_stage<BSI>(a, pth.tx, rg, s0, cnt_r, cnt - cnt_r, tid, smem, off_r, off_w);
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) {
-                const int j = jl + k;
-                v[k] = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
-                if (j < vfirst) v[k] = v2f{0.f, 0.f};
-            }
-        }
-        // the mix, a static path's and a drifting one's alike
-        const v2f g = {pth.gain, pth.gain};
-        if (pth.fres != 0) {
-            uint32_t ph = (uint32_t)(int32_t)mulmod_fs((double)pth.fres, (double)idx0, a.Fs, a.inv_fs_d);
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) {
-                float cs, sn;
-                unit_phasor((int32_t)ph, a.Fs, a.two_over_fs, cs, sn);
-                acc[k] = __builtin_elementwise_fma(g, crot(v[k], cs, sn), acc[k]);
-                ph += (uint32_t)pth.fres;
-                if (ph >= (uint32_t)a.Fs) ph -= (uint32_t)a.Fs;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) acc[k] = __builtin_elementwise_fma(g, v[k], acc[k]);
-        }
-    }
-
-    const float sigma = a.sigma[r];
-    if (sigma > 0.f) {
-        const int64_t n_abs = a.N0 + j0 + jl;
-#pragma unroll
-        for (int k = 0; k < kAirPerThread; k++) {
-            float xr = acc[k].x, xi = acc[k].y;
-            add_awgn(a.seed, r, n_abs + k, sigma, xr, xi);
-            acc[k] = v2f{xr, xi};
-        }
-    }
-
-    if (jl >= cnt) return;
-    char *row = a.out + (size_t)r * a.out_stride + (size_t)(j0 + jl) * BSO;
-    const bool whole = a.aligned16 && jl + kAirPerThread <= cnt;
-    if (BSO == 2) {
-        uint32_t w[kAirPerThread];
-#pragma unroll
-        for (int k = 0; k < kAirPerThread; k++) w[k] = (uint32_t)quant_u8_csdr(acc[k].x) | ((uint32_t)quant_u8_csdr(acc[k].y) << 8);
-        if (whole) {
-            *(uint4 *)row = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
-        } else {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((uint16_t *)row)[k] = (uint16_t)w[k];
-        }
-    } else {
-        if (whole) {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k += 2) ((float4 *)row)[k >> 1] = make_float4(acc[k].x, acc[k].y, acc[k + 1].x, acc[k + 1].y);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((float2 *)row)[k] = make_float2(acc[k].x, acc[k].y);
-        }
-    }
-}
-
-// ---- fading -----------------------------------------------------------------------------------------------------------
 // Grid point k of a fade, at absolute index 16 k: scatterer j has the 32-bit phase theta_j + w_j * (uint32)(16 k), plain wrap-around
 // arithmetic on the absolute index; its top 24 bits are exact in a float, t in [-1, 1), and sincospif takes t half turns.
 __device__ __forceinline__ v2f fade_grid_point(const AirFadeTable &f, uint32_t n16)
@@ -364,14 +220,43 @@ __device__ __forceinline__ v2f fade_grid_point(const AirFadeTable &f, uint32_t n
     return v2f{__builtin_fmaf(f.scale, C, f.los), f.scale * D};
 }
 
-// The mix kernel of a handle with a fading path: air_mix_drift_kernel with one more branch, uniform per workgroup and path. A fading
-// path's samples -- a static path's or the interpolator's -- are multiplied by the gain g[n] of the receiver's index n before the mix:
-// thread i makes grid point (first of the tile) + i and writes it to LDS behind the staging area, between the barrier that separates the
-// paths and the one that ends the staging; a lane's 8 consecutive outputs lie in at most two cells, so it reads three grid points and forms
-// the line per output.
-// LDS: the staging area ((kAirTile [+ kAirSpanExtra with a drifting path]) * BSI + 64) + kAirFadePoints * 8 bytes
-template <int BSI, int BSO>
-__global__ __launch_bounds__(kAirThreads) void air_mix_fade_kernel(AirArgs a, AirDrift d, AirFade f)
+// the grid points of a tile of cnt outputs whose first has the absolute index n_tile (taken as uint32), into LDS: thread i makes grid
+// point (first of the tile) + i; the tile needs at most kAirFadePoints
+__device__ __forceinline__ void fade_grid_stage(const AirFadeTable &f, int64_t n_tile, int cnt, int tid, v2f *grid)
+{
+    const uint32_t nt = (uint32_t)(uint64_t)n_tile, into = nt & (uint32_t)(kAirFadeGrid - 1);
+    const int points = (int)((into + (uint32_t)cnt - 1u) >> kAirFadeGridLog2) + 2;
+    if (tid < points) grid[tid] = fade_grid_point(f, nt - into + (uint32_t)tid * (uint32_t)kAirFadeGrid);
+}
+
+// v[k] *= g[n] for the lane's outputs from tile index jl on: they lie in at most two cells, so the lane reads three grid points and forms
+// the line per output
+__device__ __forceinline__ void fade_apply(const v2f *grid, int64_t n_tile, int jl, v2f (&v)[kAirPerThread])
+{
+    // the lane's first output, in samples behind the tile's first grid point
+    const uint32_t l0 = ((uint32_t)(uint64_t)n_tile & (uint32_t)(kAirFadeGrid - 1)) + (uint32_t)jl;
+    const int c0 = (int)(l0 >> kAirFadeGridLog2);
+    const int c2 = c0 + 2 < kAirFadePoints ? c0 + 2 : kAirFadePoints - 1;               // (needed only where the lane crosses into cell c0 + 1)
+    const v2f ga = grid[c0], gb = grid[c0 + 1], gc = grid[c2];
+#pragma unroll
+    for (int k = 0; k < kAirPerThread; k++) {
+        const uint32_t l = l0 + (uint32_t)k;
+        const bool next = (int)(l >> kAirFadeGridLog2) != c0;
+        const v2f lo = next ? gb : ga, hi = next ? gc : gb;
+        const float mu = (float)(l & (uint32_t)(kAirFadeGrid - 1)) * (1.0f / kAirFadeGrid);
+        const v2f g = __builtin_elementwise_fma(v2f{mu, mu}, hi - lo, lo);
+        v[k] = crot(v[k], g.x, g.y);
+    }
+}
+
+// The one body of the three mix kernels. DRIFT: a path may have a clock offset (d is read); FADE: a path may have a fade (f is read).
+// Both branches are uniform per workgroup and path, and a path with neither takes a static path's steps in every instantiation. A fade's
+// grid points go to LDS behind the staging area, between the barrier that separates the paths and the one that ends the staging, so a
+// fade adds no barrier.
+// LDS: the staging area, (kAirTile [+ kAirSpanExtra with DRIFT]) * BSI + 64 bytes (the span's units: two parts, each with a unit of slack at
+// either end) [+ kAirFadePoints * 8 bytes with FADE]
+template <int BSI, int BSO, bool DRIFT, bool FADE>
+__device__ __forceinline__ void air_mix_body(const AirArgs &a, const AirDrift &d, const AirFade &f)
 {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x;
@@ -383,7 +268,6 @@ __global__ __launch_bounds__(kAirThreads) void air_mix_fade_kernel(AirArgs a, Ai
     // (n mod Fs) of the thread's first output
     const uint32_t base = (uint32_t)(((int64_t)a.n0m + j0 % a.Fs) % a.Fs);
     const uint32_t idx0 = (base + (uint32_t)jl) % (uint32_t)a.Fs;
-    v2f *grid = (v2f *)(smem + f.grid_off);
     v2f acc[kAirPerThread];
 #pragma unroll
     for (int k = 0; k < kAirPerThread; k++) acc[k] = v2f{0.f, 0.f};
@@ -392,146 +276,39 @@ __global__ __launch_bounds__(kAirThreads) void air_mix_fade_kernel(AirArgs a, Ai
     for (int pi = p0; pi < p1; pi++) {
         const AirPath pth = a.paths[pi];
         const AirRing rg = a.rings[pth.tx];
-        const int32_t q = d.ppb[pi];
-        const int32_t fi = f.index[pi];
-        v2f v[kAirPerThread];                                           // what the path reads for the lane's outputs
-        if (pi > p0) __syncthreads();
-        if (fi >= 0) {
-            // the tile's first grid point, as (uint32) of its absolute index, and how many the tile needs: at most kAirFadePoints
-            const uint32_t nt = (uint32_t)(uint64_t)(a.N0 + j0), into = nt & (uint32_t)(kAirFadeGrid - 1);
-            const int points = (int)((into + (uint32_t)cnt - 1u) >> kAirFadeGridLog2) + 2;
-            if (tid < points) grid[tid] = fade_grid_point(f.table[fi], nt - into + (uint32_t)tid * (uint32_t)kAirFadeGrid);
-        }
-        if (q != 0) air_read_drift<BSI>(a, d, pth, rg, q, j0, cnt, jl, tid, false, chi, clo, smem, v);
-        else air_read_static<BSI>(a, pth, rg, j0, cnt, jl, tid, false, chi, clo, smem, v);
-        if (fi >= 0) {
-            // the lane's first output, in samples behind the tile's first grid point
-            const uint32_t l0 = ((uint32_t)(uint64_t)(a.N0 + j0) & (uint32_t)(kAirFadeGrid - 1)) + (uint32_t)jl;
-            const int c0 = (int)(l0 >> kAirFadeGridLog2);
-            const int c2 = c0 + 2 < kAirFadePoints ? c0 + 2 : kAirFadePoints - 1;       // (needed only where the lane crosses into cell c0 + 1)
-            const v2f ga = grid[c0], gb = grid[c0 + 1], gc = grid[c2];
+        int32_t q = 0, fi = -1;                                         // (loaded in front of the barrier, with the path)
+        if constexpr (DRIFT) q = d.ppb[pi];
+        if constexpr (FADE) fi = f.index[pi];
+        if (pi > p0) __syncthreads();                                   // the reads of the path before | this path's grid points and staging
+        if constexpr (!DRIFT && !FADE) {
+            // nothing lies between a sample's read and its mix, so each is read where it is mixed: the lane's 8 samples are not held in
+            // registers over the rotation (u8 input: 72 VGPRs and 7 waves per SIMD, against 79 and 6)
+            const AirSpan sp = air_stage<BSI>(a, pth.tx, rg, j0 - pth.delay, cnt, cnt, tid, smem);
+            air_mix_path(a, pth, idx0, [&](int k) { return air_span_sample<BSI>(smem, sp, jl + k, chi, clo); }, acc);
+        } else {
+            v2f *grid = (v2f *)(smem + f.grid_off);
+            v2f v[kAirPerThread];                                       // what the path reads for the lane's outputs
+            if (fi >= 0) fade_grid_stage(f.table[fi], a.N0 + j0, cnt, tid, grid);
+            if (q != 0) air_read_drift<BSI>(a, d, pth, rg, q, j0, cnt, jl, tid, chi, clo, smem, v);
+            else {
+                const AirSpan sp = air_stage<BSI>(a, pth.tx, rg, j0 - pth.delay, cnt, kAirTile, tid, smem);        // a static path: x_t[n - d_p]
 #pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) {
-                const uint32_t l = l0 + (uint32_t)k;
-                const bool next = (int)(l >> kAirFadeGridLog2) != c0;
-                const v2f lo = next ? gb : ga, hi = next ? gc : gb;
-                const float mu = (float)(l & (uint32_t)(kAirFadeGrid - 1)) * (1.0f / kAirFadeGrid);
-                const v2f g = __builtin_elementwise_fma(v2f{mu, mu}, hi - lo, lo);
-                v[k] = crot(v[k], g.x, g.y);
+                for (int k = 0; k < kAirPerThread; k++) v[k] = air_span_sample<BSI>(smem, sp, jl + k, chi, clo);
             }
+            if (fi >= 0) fade_apply(grid, a.N0 + j0, jl, v);
+            air_mix_path(a, pth, idx0, [&](int k) { return v[k]; }, acc);
         }
-        air_mix_path(a, pth, idx0, v, acc);
     }
     air_finish<BSO>(a, r, j0, jl, cnt, acc);
 }
 
-// LDS: kAirTile * BSI + 64 bytes (the span's units: two parts, each with a unit of slack at either end)
+// the three kernels a handle can launch, by what its paths have: nothing more, a clock offset somewhere, a fade somewhere
 template <int BSI, int BSO>
-__global__ __launch_bounds__(kAirThreads) void air_mix_kernel(AirArgs a)
-{
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x;
-    const int r = blockIdx.y;
-    const int64_t j0 = (int64_t)blockIdx.x * kAirTile;                 // first output of the tile (of this call)
-    const int cnt = (int)((a.n - j0) < kAirTile ? (a.n - j0) : kAirTile);
-    const int jl = tid * kAirPerThread;                                 // the thread's first output of the tile
-    const v2f chi = {a.c_hi, a.c_hi}, clo = {a.c_lo, a.c_lo};
-    // (n mod Fs) of the thread's first output
-    const uint32_t base = (uint32_t)(((int64_t)a.n0m + j0 % a.Fs) % a.Fs);
-    const uint32_t idx0 = (base + (uint32_t)jl) % (uint32_t)a.Fs;
-    v2f acc[kAirPerThread];
-#pragma unroll
-    for (int k = 0; k < kAirPerThread; k++) acc[k] = v2f{0.f, 0.f};
-
-    const int p0 = a.rx_start[r], p1 = a.rx_start[r + 1];
-    for (int pi = p0; pi < p1; pi++) {
-        const AirPath pth = a.paths[pi];
-        const AirRing rg = a.rings[pth.tx];
-        const int64_t s0 = j0 - pth.delay;                              // the span's first sample, as an index of this call
-        const int cnt_r = s0 >= 0 ? 0 : (-s0 < cnt ? (int)-s0 : cnt);   // samples from the ring
-        const int cnt_w = cnt - cnt_r;                                  // samples from the call's row
-        // tile index of the first sample at or above the last reset
-        const int64_t vf = a.first - (a.N0 + s0);
-        const int vfirst = vf <= 0 ? 0 : (vf < kAirTile ? (int)vf : kAirTile);
-        if (pi > p0) __syncthreads();
-        int shift_r = 0, units_r = 0;
-        if (cnt_r > 0) {
-            const uint32_t b0 = (uint32_t)((uint64_t)(a.N0 + s0) & rg.mask) * BSI;        // (a ring holds at most 2^20 samples of 8 bytes)
-            const uint32_t umask = ((rg.mask + 1u) * BSI >> 4) - 1u;
-            const uint4 *src = (const uint4 *)(a.ring + (size_t)rg.off * BSI);
-            shift_r = (int)(b0 & 15u);
-            units_r = (shift_r + cnt_r * BSI + 15) >> 4;
-            for (int u = tid; u < units_r; u += kAirThreads) ((uint4 *)smem)[u] = src[((b0 >> 4) + (uint32_t)u) & umask];
-        }
-        int shift_w = 0;
-        if (cnt_w > 0) {
-            const char *p = a.in + (size_t)pth.tx * a.in_stride + (size_t)(s0 + cnt_r) * BSI;
-            shift_w = (int)((uintptr_t)p & 15);
-            const uint4 *src = (const uint4 *)(p - shift_w);
-            const int units_w = (shift_w + cnt_w * BSI + 15) >> 4;
-            for (int u = tid; u < units_w; u += kAirThreads) ((uint4 *)smem)[units_r + u] = src[u];
-        }
-        __syncthreads();
-        const int off_r = shift_r, off_w = units_r * 16 + shift_w - cnt_r * BSI;
-        const v2f g = {pth.gain, pth.gain};
-        if (pth.fres != 0) {
-            uint32_t ph = (uint32_t)(int32_t)mulmod_fs((double)pth.fres, (double)idx0, a.Fs, a.inv_fs_d);
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) {
-                const int j = jl + k;
-                v2f v = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
-                if (j < vfirst) v = v2f{0.f, 0.f};
-                float cs, sn;
-                unit_phasor((int32_t)ph, a.Fs, a.two_over_fs, cs, sn);
-                acc[k] = __builtin_elementwise_fma(g, crot(v, cs, sn), acc[k]);
-                ph += (uint32_t)pth.fres;
-                if (ph >= (uint32_t)a.Fs) ph -= (uint32_t)a.Fs;
-            }
-        } else {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) {
-                const int j = jl + k;
-                v2f v = air_sample<BSI>(smem + (j < cnt_r ? off_r : off_w) + j * BSI, chi, clo);
-                if (j < vfirst) v = v2f{0.f, 0.f};
-                acc[k] = __builtin_elementwise_fma(g, v, acc[k]);
-            }
-        }
-    }
-
-    const float sigma = a.sigma[r];
-    if (sigma > 0.f) {
-        const int64_t n_abs = a.N0 + j0 + jl;
-#pragma unroll
-        for (int k = 0; k < kAirPerThread; k++) {
-            float xr = acc[k].x, xi = acc[k].y;
-            add_awgn(a.seed, r, n_abs + k, sigma, xr, xi);
-            acc[k] = v2f{xr, xi};
-        }
-    }
-
-    if (jl >= cnt) return;
-    char *row = a.out + (size_t)r * a.out_stride + (size_t)(j0 + jl) * BSO;
-    const bool whole = a.aligned16 && jl + kAirPerThread <= cnt;
-    if (BSO == 2) {
-        uint32_t w[kAirPerThread];
-#pragma unroll
-        for (int k = 0; k < kAirPerThread; k++) w[k] = (uint32_t)quant_u8_csdr(acc[k].x) | ((uint32_t)quant_u8_csdr(acc[k].y) << 8);
-        if (whole) {
-            *(uint4 *)row = make_uint4(w[0] | (w[1] << 16), w[2] | (w[3] << 16), w[4] | (w[5] << 16), w[6] | (w[7] << 16));
-        } else {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((uint16_t *)row)[k] = (uint16_t)w[k];
-        }
-    } else {
-        if (whole) {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k += 2) ((float4 *)row)[k >> 1] = make_float4(acc[k].x, acc[k].y, acc[k + 1].x, acc[k + 1].y);
-        } else {
-#pragma unroll
-            for (int k = 0; k < kAirPerThread; k++) if (jl + k < cnt) ((float2 *)row)[k] = make_float2(acc[k].x, acc[k].y);
-        }
-    }
-}
+__global__ __launch_bounds__(kAirThreads) void air_mix_kernel(AirArgs a) { air_mix_body<BSI, BSO, false, false>(a, AirDrift{}, AirFade{}); }
+template <int BSI, int BSO>
+__global__ __launch_bounds__(kAirThreads) void air_mix_drift_kernel(AirArgs a, AirDrift d) { air_mix_body<BSI, BSO, true, false>(a, d, AirFade{}); }
+template <int BSI, int BSO>
+__global__ __launch_bounds__(kAirThreads) void air_mix_fade_kernel(AirArgs a, AirDrift d, AirFade f) { air_mix_body<BSI, BSO, true, true>(a, d, f); }
 
 // the call's last min(n, ring) samples of transmitter blockIdx.y -> ring[absolute index & mask]
 template <typename S>
@@ -606,15 +383,6 @@ int64_t last_age_of(int32_t max_slip, int32_t q_fast, int32_t q_slow)
 
 // ---- a fade's table (4.15b): the integers and floats the kernel reads, made on the host in double and rounded once
 
-// noise_device.hpp's SplitMix64 finaliser, on the host
-uint64_t splitmix_host(uint64_t z)
-{
-    z += 0x9E3779B97F4A7C15ull;
-    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
-    z = (z ^ (z >> 27)) * 0x94D049BB133111EBull;
-    return z ^ (z >> 31);
-}
-
 int32_t max_doppler_millihz(int Fs) { return (int32_t)(1000 * (int64_t)Fs / 1024); }
 
 bool fade_ok(const pirip_air_fade &f) { return f.doppler_millihz >= 0 && std::isfinite(f.rice_k) && f.rice_k >= 0.f; }
@@ -625,8 +393,8 @@ AirFadeTable fade_table(int Fs, uint64_t seed, const pirip_air_fade &f)
     const double pi = 3.14159265358979323846, fd = (double)f.doppler_millihz / 1000.0, K = (double)f.rice_k;
     AirFadeTable t{};
     for (int j = 0; j < kAirScatter; j++) {
-        const uint64_t r1 = splitmix_host(seed ^ splitmix_host(((uint64_t)f.key << 32) ^ (uint64_t)j));
-        const uint64_t r2 = splitmix_host(r1);
+        const uint64_t r1 = splitmix(seed ^ splitmix(((uint64_t)f.key << 32) ^ (uint64_t)j));
+        const uint64_t r2 = splitmix(r1);
         const double u = (double)(r1 >> 11) * 0x1p-53;
         const double alpha = 2.0 * pi * ((double)j + u) / kAirScatter;
         const double nu = fd * std::cos(alpha);
@@ -753,6 +521,16 @@ int64_t samples_left(const pirip_hip_air *air)
     return left < 0 ? 0 : left;
 }
 
+// the mix kernel of a handle's kind for one format pair; `lds` is the staging area's, a fade kernel has its grid points behind it
+template <int BSI, int BSO>
+void air_mix_launch(bool fade, bool drift, dim3 grid, size_t lds, hipStream_t st, const AirArgs &a, const AirDrift &d, const AirFade &f)
+{
+    const dim3 block(kAirThreads);
+    if (fade) hipLaunchKernelGGL((air_mix_fade_kernel<BSI, BSO>), grid, block, lds + (size_t)kAirFadePoints * sizeof(float2), st, a, d, f);
+    else if (drift) hipLaunchKernelGGL((air_mix_drift_kernel<BSI, BSO>), grid, block, lds, st, a, d);
+    else hipLaunchKernelGGL((air_mix_kernel<BSI, BSO>), grid, block, lds, st, a);
+}
+
 }  // namespace
 
 extern "C" {
@@ -859,27 +637,14 @@ int pirip_hip_air_push(pirip_hip_air *air, const void *d_in, size_t in_stride_by
     a.inv_fs_d = 1.0 / (double)air->Fs;
     hipStream_t st = (hipStream_t)hip_stream;
     const dim3 grid((unsigned)ntiles, (unsigned)air->nrx);
-    // a handle with a drifting path: the drift instantiation on a longer span; every other one: the static kernel on the tile's
+    // the staging area: a handle with a drifting path stages a longer span than the tile's
     const size_t lds = (size_t)(kAirTile + (air->drift ? kAirSpanExtra : 0)) * (size_t)air->bsi + 64;
     const AirDrift d{air->d_ppb, air->d_taps, air->age0 + (air->pos - air->first)};
-    // a handle with a fading path: the fade instantiation, the tile's grid points behind the staging area
+    // a handle with a fading path: the tile's grid points behind the staging area
     const AirFade f{air->d_fade_index, air->d_fade_table, (int)lds};
-    const size_t lds_fade = lds + (size_t)kAirFadePoints * sizeof(float2);
-    const int kind = (air->fade ? 8 : air->drift ? 4 : 0) + (air->bsi == 2 ? 0 : 2) + (air->bso == 2 ? 0 : 1);
-    switch (kind) {
-    case 8: hipLaunchKernelGGL((air_mix_fade_kernel<2, 2>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
-    case 9: hipLaunchKernelGGL((air_mix_fade_kernel<2, 8>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
-    case 10: hipLaunchKernelGGL((air_mix_fade_kernel<8, 2>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
-    case 11: hipLaunchKernelGGL((air_mix_fade_kernel<8, 8>), grid, dim3(kAirThreads), lds_fade, st, a, d, f); break;
-    case 0: hipLaunchKernelGGL((air_mix_kernel<2, 2>), grid, dim3(kAirThreads), lds, st, a); break;
-    case 1: hipLaunchKernelGGL((air_mix_kernel<2, 8>), grid, dim3(kAirThreads), lds, st, a); break;
-    case 2: hipLaunchKernelGGL((air_mix_kernel<8, 2>), grid, dim3(kAirThreads), lds, st, a); break;
-    case 3: hipLaunchKernelGGL((air_mix_kernel<8, 8>), grid, dim3(kAirThreads), lds, st, a); break;
-    case 4: hipLaunchKernelGGL((air_mix_drift_kernel<2, 2>), grid, dim3(kAirThreads), lds, st, a, d); break;
-    case 5: hipLaunchKernelGGL((air_mix_drift_kernel<2, 8>), grid, dim3(kAirThreads), lds, st, a, d); break;
-    case 6: hipLaunchKernelGGL((air_mix_drift_kernel<8, 2>), grid, dim3(kAirThreads), lds, st, a, d); break;
-    default: hipLaunchKernelGGL((air_mix_drift_kernel<8, 8>), grid, dim3(kAirThreads), lds, st, a, d); break;
-    }
+    const auto launch = air->bsi == 2 ? (air->bso == 2 ? air_mix_launch<2, 2> : air_mix_launch<2, 8>)
+                                      : (air->bso == 2 ? air_mix_launch<8, 2> : air_mix_launch<8, 8>);
+    launch(air->fade, air->drift, grid, lds, st, a, d, f);
     // the carry: as many workgroups per transmitter as the longest ring and the call ask for (at most 64, which stride)
     const int64_t most = n < (int64_t)air->max_ring ? n : (int64_t)air->max_ring;
     int64_t cblocks = (most + kAirThreads - 1) / kAirThreads;

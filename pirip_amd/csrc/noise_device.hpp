@@ -10,7 +10,8 @@
 
 namespace pirip {
 
-__device__ __forceinline__ uint64_t splitmix(uint64_t z)
+// (on the host too: the channel makes a fade's table from it, air_kernels.hip)
+__host__ __device__ __forceinline__ uint64_t splitmix(uint64_t z)
 {
     z += 0x9E3779B97F4A7C15ull;
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ull;
