@@ -235,6 +235,21 @@ int pirip_hip_set_bit_packing(pirip_hip_demod *h, int packed);
  * pirip_hip_set_freq_est_limits() refuses a range that leaves the band, and switching it off again resets the streams. */
 int pirip_hip_set_estimator_band_only(pirip_hip_demod *h, int enable);
 
+/* Launch tail of the wave-per-stream demodulator. A launch of more workgroups than the device holds at once ends with its queue run
+ * dry: the workgroups dispatched last have their whole stream ahead of them while the waves they share a SIMD with are nearly done, and
+ * the hardware issues the oldest wave first. With enable = 1 (the default) the workgroups of the launch's last residency -- the highest
+ * block indices, as many as the device holds at once -- start at wave priority 1; a launch of one residency or less raises nothing.
+ * Every output word is the same either way: only the order in which the hardware issues the waves' instructions changes. Applies to
+ * every later launch of the handle (batch, chunked, capture and segment calls); 0 switches it off (measurement A/B). */
+int pirip_hip_set_launch_tail_first(pirip_hip_demod *h, int enable);
+/* Workgroups of the handle's wave instance that its device holds at once (streams per CU / streams per workgroup x compute units);
+ * 0 for a handle on another kernel. */
+int pirip_hip_get_launch_resident_blocks(const pirip_hip_demod *h);
+/* The rule itself, as a pure function (no device): a launch of `nblocks` workgroups of `streams_per_block` streams on `cus` compute
+ * units that hold `streams_per_cu` streams each. Returns the first block index that starts at the raised priority (nblocks: none), or a
+ * negative PIRIP_ERR_*. */
+int pirip_hip_launch_first_tail_block(int nblocks, int streams_per_cu, int streams_per_block, int cus);
+
 /* fsk_enable_burst_mode() for every stream of the handle [UPSTREAM-RECALLED fsk.c]: nin is reset to N
  * and no longer follows the timing estimate. */
 int pirip_hip_set_burst_mode(pirip_hip_demod *h, int enable);

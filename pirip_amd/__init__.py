@@ -8,6 +8,6 @@ from .binding import (  # noqa: F401
     PiripError, FskParams, HipDemod, HipDecim, lib, lib_path, build, device_count, selftest_sqrt, selftest_div,
     IN_CU8_FSKDEMOD, IN_CU8_CSDR, IN_CS16, IN_CF32, STATS_PER_FRAME,
     HipTestBits, testframe_payload, HipRepeater, HipPing, PingConfig, PingEntry, PING_ENTRY_DTYPE, HipAir, AirPath, AirPathEx, AirInfo,
-    AirFade, air_fade, air_fade_table,
+    AirFade, air_fade, air_fade_table, launch_first_tail_block,
     HipLdpc, HipRx, HipChan, HipTx, HipMux, HipTxStream, MUX_FIR, MUX_LINEAR, TX_CARRIER_OFF, STANDIN_CODE, RX_TRIAL_SYNC, RX_SYNC, RX_BITS, RX_BIT_ERRORS, LDPC_INFO_PER_CALL,
 )

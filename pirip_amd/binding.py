@@ -316,6 +316,17 @@ def recalled(**overrides):
     return r
 
 
+def launch_first_tail_block(nblocks, streams_per_cu, streams_per_block, cus):
+    """pirip_hip_launch_first_tail_block (no device): the first workgroup of a wave-kernel launch of `nblocks` that starts at the raised
+    priority; nblocks: none does."""
+    L = lib()
+    L.pirip_hip_launch_first_tail_block.argtypes = [C.c_int] * 4
+    first = int(L.pirip_hip_launch_first_tail_block(int(nblocks), int(streams_per_cu), int(streams_per_block), int(cus)))
+    if first < 0:
+        _chk(first, "pirip_hip_launch_first_tail_block")
+    return first
+
+
 class HipDemod:
     """nstreams device-resident demodulators (pirip_hip_create; recalled=dict(field=value, ...): pirip_hip_create_recalled)."""
 
@@ -413,6 +424,17 @@ class HipDemod:
     def set_estimator_band_only(self, enable=True):
         """Opt-in: Sf is maintained only for the FFT bins the peak search can read (include/pirip_hip.h); outputs unchanged."""
         _chk(self.L.pirip_hip_set_estimator_band_only(self.h, 1 if enable else 0), "pirip_hip_set_estimator_band_only")
+
+    def set_launch_tail_first(self, enable=True):
+        """pirip_hip_set_launch_tail_first: the workgroups of a wave-kernel launch's last residency start at a raised wave priority
+        (default on); outputs unchanged."""
+        self.L.pirip_hip_set_launch_tail_first.argtypes = [C.c_void_p, C.c_int]
+        _chk(self.L.pirip_hip_set_launch_tail_first(self.h, 1 if enable else 0), "pirip_hip_set_launch_tail_first")
+
+    def launch_resident_blocks(self):
+        """pirip_hip_get_launch_resident_blocks: workgroups of the handle's wave instance that its device holds at once (0: another kernel)."""
+        self.L.pirip_hip_get_launch_resident_blocks.argtypes = [C.c_void_p]
+        return int(self.L.pirip_hip_get_launch_resident_blocks(self.h))
 
     def set_freq_est_limits(self, est_min, est_max):
         """fsk_set_freq_est_limits() on the live handle; returns the status code (PIRIP_OK = 0) instead of raising."""

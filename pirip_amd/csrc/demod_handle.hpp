@@ -38,6 +38,10 @@ struct pirip_hip_demod {
     int exact0 = 1;                             // pirip_hip_set_exact_first_frame / PIRIP_EXACT0=0 switch it off (A/B, tests)
     int32_t *d_first = nullptr;                 // [nstreams] samples the prologue consumed in the current call
     float *d_eye = nullptr;                     // pirip_hip_enable_eye: [nstreams][8][160] |f_int| eye traces of each stream's latest frame
+    // Launch tail (fsk_plan.cpp: launch_first_tail_block): the device's compute units, read once at create, and whether the workgroups of a
+    // wave-kernel launch's last residency start at a raised priority (pirip_hip_set_launch_tail_first; on by default)
+    int num_cu = 0;
+    int tail_first = 1;
     struct CaptureWork *capture = nullptr;      // capture.hip: work area of pirip_hip_demod_capture, allocated on first use
 };
 #pragma GCC visibility pop

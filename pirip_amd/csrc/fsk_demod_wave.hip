@@ -240,10 +240,15 @@ __device__ __forceinline__ uint32_t spread16(uint32_t x)     // bit t of x -> bi
 // 3: correlator, 4: window sums + timing; anything else: whole frame) behind a run-time test the compiler cannot see through, so the
 // phases before the mark are compiled exactly as in the full frame: differences of SQ_INSTS_VALU between consecutive k are the
 // instructions each phase EXECUTES (tools/phase_valu.sh). Results of a stopped run are wrong by construction.
+// The same builds keep a per-wave launch timeline (tools/wave_drain.py): where pirip_hip_wave_timeline() has named a buffer, every wave
+// that runs frames leaves four 64-bit words at row `sid` -- s_memtime before its first frame and after its last, its frame count, and where
+// it ran (HW_ID in the low word: wave slot, SIMD, CU, shader array and engine; XCC_ID above it).
 #ifdef PIRIP_WAVE_TIMING
 __device__ int g_wave_stop_phase = -1;
+__device__ unsigned long long *g_wave_timeline = nullptr;
+__device__ int g_wave_timeline_rows = 0;
 #define PIRIP_T_DECL long long t_acc_[8] = {0, 0, 0, 0, 0, 0, 0, 0}; long long t_last_ = __builtin_amdgcn_s_memtime(); \
-    const int t_stop_ = __builtin_amdgcn_readfirstlane(g_wave_stop_phase)
+    const int t_stop_ = __builtin_amdgcn_readfirstlane(g_wave_stop_phase); const long long t_first_ = t_last_
 #define PIRIP_T_MARK(i) { const long long t_now_ = __builtin_amdgcn_s_memtime(); t_acc_[i] += t_now_ - t_last_; t_last_ = t_now_; } \
     if (t_stop_ == (i)) { pos += nin; frame++; wave_lds_sync(); continue; } else (void)0
 #else
@@ -333,6 +338,17 @@ constexpr bool wave_locked_paths_instance(int M, int TS, int P, int NDFT, int FM
     return M == 2 && TS == 24 && P == 24 && NDFT == 256 && FMT == PIRIP_IN_CU8_FSKDEMOD && !FFT_FMA && !MASK && BAND == 0;
 }
 
+// Instances whose launches raise the priority of their last residency's workgroups (the "launch tail" block in front of the frame loop):
+// all but those that the register report (tools/kernel_resources.sh, profiles/lt_resources_{parent,result}.txt) shows spilling more SGPRs
+// with the block than without. They keep the prologue they had.
+constexpr bool wave_tail_prio_instance(int M, int TS, int P, int NDFT, int FMT, int WPS, bool FFT_FMA, bool MASK, int BAND)
+{
+    if (TS == 40 && M == 2 && FMT == PIRIP_IN_CS16 && !MASK) return false;      // + 40 (34 -> 74)
+    if (TS == 40 && M == 4 && FMT == PIRIP_IN_CF32 && MASK) return false;       // + 3
+    if (TS == 8 && M == 2 && !MASK) return false;                               // + 1
+    return true;
+}
+
 // Per-wave LDS footprint, also used by the launcher to report occupancy
 template <class C, int M> constexpr int wave_lds_bytes() { return C::RAW_B + C::XP_B; }
 
@@ -361,6 +377,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     constexpr bool INPLACE = TS == 10;
     constexpr bool PLAIN = wave_plain_instance(M, TS, P, NDFT, FMT, WPS, FFT_FMA, MASK, BAND);
     constexpr bool ARGMAX_SINGLE = !PLAIN && !wave_two_pass_argmax_instance(M, TS, FMT, MASK, BAND);
+    constexpr bool TAIL_PRIO = wave_tail_prio_instance(M, TS, P, NDFT, FMT, WPS, FFT_FMA, MASK, BAND);
     static_assert(offsetof(DemodArgs, d) == 0, "the argument block is the first kernel argument");
     auto ap = [&]() {
         if constexpr (INPLACE) return (const __attribute__((address_space(4))) DemodArgs *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -585,6 +602,16 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     constexpr int NBITS = NSYM * (M == 2 ? 1 : 2);
     wave_lds_sync();
     dma_frame(pos);
+    // Launch tail (fsk_plan.cpp: launch_first_tail_block): the workgroups of the launch's last residency run their frames at a raised priority,
+    // so that the waves with the most work left win VALU arbitration against older neighbours that are nearly done. The block index (from
+    // the stream index, which is live here anyway) and the threshold are scalars: one compare and a branch round one s_setprio; a wave
+    // ends with its priority and the next one on its slot starts at 0. The threshold is read here, from the kernarg segment, and is dead
+    // before the first frame. (In front of the state loads the same block turns the loads behind it into vector loads with waterfall
+    // loops round the frame's buffer descriptor: it stays the last thing before the loop.)
+    if constexpr (TAIL_PRIO) {
+        auto tp = (const __attribute__((address_space(4))) DemodArgs *)__builtin_amdgcn_kernarg_segment_ptr();
+        if (sid / WPB >= tp->first_tail_block) __builtin_amdgcn_s_setprio(1);
+    }
     PIRIP_T_DECL;
 
     while (frame < max_frames && pos + nin <= nsamp) {
@@ -1600,6 +1627,11 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
 #ifdef PIRIP_WAVE_TIMING
     if (a.io.stats && lane0 == 0 && sid == nstreams / 2)
         for (int i = 0; i < 8; i++) a.io.stats[(size_t)sid * a.io.stats_stride + i] = (float)t_acc_[i];
+    if (g_wave_timeline && sid < g_wave_timeline_rows && lane0 == 0) {
+        unsigned long long *row = g_wave_timeline + 4 * (size_t)sid;
+        row[0] = (unsigned long long)t_first_; row[1] = (unsigned long long)__builtin_amdgcn_s_memtime(); row[2] = (unsigned long long)(frame - frame_first);
+        row[3] = ((unsigned long long)__builtin_amdgcn_s_getreg(0x1814) << 32) | __builtin_amdgcn_s_getreg(0xF804);   // XCC_ID[3:0] | HW_ID[31:0]
+    }
 #endif
 #pragma unroll
     for (int b = 0; b < NB; b++) if (!BAND || lane0 < 16) a.s.Sf[(size_t)sid * NDFT + own_sfi(lane0, b)] = Sf[b];
@@ -1718,7 +1750,10 @@ hipError_t launch_inst(const DemodArgs &a, int nstreams, hipStream_t stream)
         (void)hipStreamSynchronize(stream);
     }
 #endif
-    hipLaunchKernelGGL((fsk_demod_wave_kernel<M, TS, P, NSYM, NDFT, FMT, WPB, WPS, FMA, MASK, BAND>), g, b, dyn, stream, a, nstreams);
+    // launch tail: which of THIS grid's workgroups start at a raised priority (none in a launch of one residency or less)
+    DemodArgs at = a;
+    at.first_tail_block = launch_first_tail_block((int)g.x, launch_resident_blocks(4 * WPS, WPB, a.tail_cus), a.tail_first != 0);
+    hipLaunchKernelGGL((fsk_demod_wave_kernel<M, TS, P, NSYM, NDFT, FMT, WPB, WPS, FMA, MASK, BAND>), g, b, dyn, stream, at, nstreams);
     return hipGetLastError();
 }
 
@@ -1786,6 +1821,8 @@ bool demod_wave_applicable(const FskDims &d) { return find_inst(d) != nullptr; }
 // streams of this configuration's instance that one CU holds at a time (one wave each: waves per SIMD x 4 SIMDs; 0: no instance)
 int demod_wave_streams_per_cu(const FskDims &d) { const WaveInst *w = find_inst(d); return w ? 4 * w->wps : 0; }
 
+int demod_wave_resident_blocks(const FskDims &d, int cus) { const WaveInst *w = find_inst(d); return w ? launch_resident_blocks(4 * w->wps, w->wpb, cus) : 0; }
+
 bool demod_wave_soft_capable(const FskDims &d) { return find_inst(d) != nullptr && d.P <= 10 && d.Nsym == 50; }
 
 int demod_wave_describe(const FskDims &d, char *buf, size_t n)
@@ -1802,6 +1839,20 @@ int64_t demod_wave_max_samples(const FskDims &d)
     const int bps = d.in_format == PIRIP_IN_CF32 ? 8 : d.in_format == PIRIP_IN_CS16 ? 4 : 2;
     return 0x7fffff00LL / bps * 2 / 2;                      // 32-bit buffer-descriptor range in bytes
 }
+
+#ifdef PIRIP_WAVE_TIMING
+}  // namespace pirip
+// profiling builds only (tools/wave_drain.py): rows x 4 64-bit words of device memory that later launches fill, one row per stream; nullptr: none
+extern "C" int pirip_hip_wave_timeline(void *d_rows, int rows)
+{
+    unsigned long long *p = (unsigned long long *)d_rows;
+    const int n = p ? rows : 0;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(pirip::g_wave_timeline), &p, sizeof(p)) != hipSuccess) return PIRIP_ERR_HIP;
+    if (hipMemcpyToSymbol(HIP_SYMBOL(pirip::g_wave_timeline_rows), &n, sizeof(n)) != hipSuccess) return PIRIP_ERR_HIP;
+    return PIRIP_OK;
+}
+namespace pirip {
+#endif
 
 hipError_t launch_demod_wave(const DemodArgs &a, int nstreams, hipStream_t stream)
 {

@@ -129,6 +129,10 @@ struct DemodArgs {
     DemodState s;
     DemodIO io;
     float tw_s2[18];            // wave-uniform FFT twiddles of the wave kernel (Ndft 256: stage 2; Ndft 512: tw[64], tw[128], tw[192])
+    // Launch tail of the wave kernel (fsk_plan.cpp: launch_first_tail_block). The handle fills tail_first (pirip_hip_set_launch_tail_first)
+    // and tail_cus (its device's compute units); launch_demod_wave derives first_tail_block for the launch's own grid: all the kernel reads.
+    int tail_first, tail_cus;
+    int first_tail_block;       // blocks from here on start at wave priority 1 (the grid's size: none)
 };
 
 // pirip_hip_demod_batch with per-stream segment descriptors (pirip_capi.hip; seg == nullptr: the public call itself)
@@ -163,6 +167,7 @@ hipError_t selftest_atan2(const float *d_y, const float *d_x, float *d_out, int 
 bool demod_wave_applicable(const FskDims &d);
 int demod_wave_describe(const FskDims &d, char *buf, size_t n);   // instance name of the configuration (0 when none applies)
 int demod_wave_streams_per_cu(const FskDims &d);                   // streams of the instance resident on one CU (waves per SIMD x 4)
+int demod_wave_resident_blocks(const FskDims &d, int cus);         // workgroups of the instance resident at once on `cus` compute units (0: no instance)
 bool demod_wave_soft_capable(const FskDims &d);                    // the instance can write SoftOut (bit LLRs + hard words)
 int64_t demod_wave_max_samples(const FskDims &d);
 hipError_t launch_demod_wave(const DemodArgs &a, int nstreams, hipStream_t stream);

@@ -471,4 +471,24 @@ void recalled_defaults(pirip_fsk_recalled *r)
     r->sf_power = 0;
 }
 
+// Launch tail of the wave-per-stream demodulator ("Launch tail"). A launch of more workgroups than the chip holds at once
+// ends with a queue that has run dry: the last-dispatched workgroups still have their whole stream ahead of them while the waves they share
+// a SIMD with are nearly done, lose VALU arbitration to them (priority, then age: oldest first) and then finish alone on a SIMD that one
+// wave cannot fill. The workgroups of the last residency -- the `resident` highest block indices -- therefore start at wave priority 1.
+// Returns the first raised block: nblocks - resident, or nblocks (none) for a launch of one residency or less, an unknown residency
+// (resident <= 0) or the rule switched off. (Measured beside it and dropped: levels 1 / 2 / 3 over the thirds of the window, highest for
+// the latest blocks -- the same gain to within the noise, profiles/lt_ab_candidates.txt.)
+int launch_first_tail_block(int nblocks, int resident, bool enabled)
+{
+    return (enabled && resident > 0 && nblocks > resident) ? nblocks - resident : nblocks;
+}
+
+// workgroups of `streams_per_block` streams resident at once on `cus` compute units that hold `streams_per_cu` streams each
+int launch_resident_blocks(int streams_per_cu, int streams_per_block, int cus)
+{
+    if (streams_per_cu <= 0 || streams_per_block <= 0 || cus <= 0) return 0;
+    const int64_t r = (int64_t)(streams_per_cu / streams_per_block) * cus;
+    return r > 0x7fffffff ? 0x7fffffff : (int)r;
+}
+
 }  // namespace pirip

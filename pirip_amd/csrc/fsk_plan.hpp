@@ -115,6 +115,9 @@ void csdr_lowpass(float *taps, int length, float cutoff_rate, int window);   // 
 // peak-search range of fsk_set_freq_est_limits(): fills est_st / est_en, or returns false where codec2 asserts
 bool fsk_est_range(int Fs, int Ndft, int est_min, int est_max, int *st, int *en);
 void recalled_defaults(pirip_fsk_recalled *r);                     // today's values (pirip_hip_recalled_defaults)
+// launch tail of the wave demodulator (fsk_plan.cpp): which workgroups of a launch start at a raised wave priority
+int launch_resident_blocks(int streams_per_cu, int streams_per_block, int cus);   // workgroups resident at once (0: unknown)
+int launch_first_tail_block(int nblocks, int resident, bool enabled);              // blocks from here on are raised (nblocks: none)
 bool recalled_from_env(pirip_fsk_recalled *r);                     // PIRIP_RECALLED="field=value,..." over what r holds; false: unknown field
 
 }  // namespace pirip

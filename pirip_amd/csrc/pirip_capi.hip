@@ -44,6 +44,8 @@ void fill_args(const pirip_hip_demod *h, DemodArgs *a)
                        h->d_osc_drift, h->d_osc_step, h->d_timing_rec, h->d_fast_tab};
     for (int i = 0; i < 18; i++) a->tw_s2[i] = h->plan.tw_s2[i];
     a->s = DemodState{h->d_Sf, h->d_theta, h->d_hist, h->d_scal, h->d_phic};
+    a->tail_first = h->tail_first; a->tail_cus = h->num_cu;
+    a->first_tail_block = 0x7fffffff;                     // (launch_demod_wave's, per launch)
 }
 
 bool bind(const pirip_hip_demod *h) { return bind_device(h->device); }
@@ -181,6 +183,10 @@ int pirip_hip_create_recalled(const pirip_fsk_params *p, const pirip_fsk_recalle
     if (rc != PIRIP_OK) { delete h; return rc; }
     h->nstreams = nstreams;
     {
+        int cus = 0;                                         // (unknown: launches raise no workgroup's priority)
+        if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, h->device) == hipSuccess && cus > 0) h->num_cu = cus;
+    }
+    {
         const char *k = getenv("PIRIP_KERNEL");
         const bool want_general = getenv("PIRIP_FORCE_GENERAL") || (k && !strcmp(k, "general"));
         if (const char *f = getenv("PIRIP_FFT_FMA")) {
@@ -301,6 +307,25 @@ int pirip_hip_set_exact_first_frame(pirip_hip_demod *h, int enable)
     if (!h) return PIRIP_ERR_BAD_ARG;
     h->exact0 = enable ? 1 : 0;
     return PIRIP_OK;
+}
+
+int pirip_hip_set_launch_tail_first(pirip_hip_demod *h, int enable)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    h->tail_first = enable ? 1 : 0;
+    return PIRIP_OK;
+}
+
+int pirip_hip_get_launch_resident_blocks(const pirip_hip_demod *h)
+{
+    if (!h) return PIRIP_ERR_BAD_ARG;
+    return h->kernel == PIRIP_KERNEL_WAVE ? demod_wave_resident_blocks(h->plan.d, h->num_cu) : 0;
+}
+
+int pirip_hip_launch_first_tail_block(int nblocks, int streams_per_cu, int streams_per_block, int cus)
+{
+    if (nblocks < 0) return PIRIP_ERR_BAD_ARG;
+    return launch_first_tail_block(nblocks, launch_resident_blocks(streams_per_cu, streams_per_block, cus), true);
 }
 
 int pirip_hip_demod_batch(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp,
