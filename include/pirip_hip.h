@@ -27,6 +27,8 @@
  *              counted on the device behind the demodulator or the receiver.
  *   section O  channel (pirip_hip_air_*)                    : T transmitted wideband IQ streams onto R received ones: paths with
  *              gain, delay, carrier offset, sample-clock offset and Rayleigh / Rician fading, AWGN per receiver, block after block.
+ *   section P  band monitor (pirip_hip_spec_*)              : averaged wideband power spectra of a batch of IQ streams and the power,
+ *              peak and peak bin of a list of bands, block after block, exact against kiss_fft.
  *   section D  libcsdr-compatible entry points              : convert_u8_f, convert_f_s16,
  *              firdes_*, fir_decimate_cc
  *              [UPSTREAM-RECALLED csdr libcsdr.h].
@@ -1018,6 +1020,72 @@ int pirip_hip_air_create_fade(int Fs, int in_format, int out_format, int ntx, in
 /* A fade's table, the very integers and floats the kernel reads (fade->path is not looked at). Host only: no device is looked for.
  * PIRIP_ERR_BAD_ARG for a NULL pointer, Fs < 2 and the fade's values refused above; PIRIP_ERR_UNSUPPORTED as above. */
 int pirip_hip_air_fade_table(int Fs, uint64_t seed, const pirip_air_fade *fade, int32_t w[16], uint32_t theta[16], float *scale, float *los);
+
+/* ----------------------------------------------------------------------------------- */
+/* section P : band monitor (averaged wideband spectra and band powers on the device)    */
+/*   The view script/dash.py plots (SfdB with the band limits) and the two figures the    */
+/*   README's "Noise Figure Testing" compares (a tone's power, the floor's density),      */
+/*   one stage in front of section H: on the wideband stream itself, for a batch of      */
+/*   streams, block after block, without host synchronisation.          */
+/*   Only symbols are added: PIRIP_HIP_ABI_VERSION and every entry point above stand.    */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_spec pirip_hip_spec;
+typedef struct pirip_spec_band { int32_t stream, lo_hz, hi_hz; } pirip_spec_band;
+typedef struct pirip_spec_band_row { float power, peak; int32_t peak_bin; } pirip_spec_band_row;
+typedef struct pirip_spec_info { int Fs, in_format, nfft, hop, avg, nstreams, nbands, device; double scale; } pirip_spec_info;
+
+/* nstreams streams at Fs samples/s. in_format PIRIP_IN_CU8_CSDR is read as b / 127.5 - 1 per component (section H's conversion),
+ * PIRIP_IN_CF32 as it is. nfft is one of 256, 1024, 4096 (the powers of 4: kiss_fft's factorisation has radix-4 stages only), hop one of
+ * nfft, nfft / 2, avg = A in 1 .. 65536.
+ * Segments and rows: segment k of a stream covers its samples [k hop, k hop + nfft), counted from the last reset (create counts as one);
+ * row j is the segments j A .. j A + A - 1 and is complete when its last sample has been pushed.
+ * Window: w[i] = 0.5 - 0.5 cos(2 pi i / nfft) for i <= nfft / 2, computed in double and rounded once to float, and w[i] = w[nfft - i] above
+ * (the formula's own symmetry, kept whatever cos() returns); pirip_hip_spec_window returns the very floats the kernel uses.
+ * Per segment, in float: v[i] = (w[i] x.re, w[i] x.im), one product per component; X = the forward kiss_fft of v with the unfused twiddle
+ * multiply on every butterfly operand -- oracle/kiss_fft_oracle.c at its default, twiddles (float) cos / sin of the double -2 pi i / nfft;
+ * the process-wide fused-multiply switch of the demodulator does not reach this section --; p[b] = X.re X.re + X.im X.im, two rounded
+ * products and one rounded add, no fma.
+ * Rows: row[b] starts at +0 and takes its segments in ascending k, row[b] = row[b] + p_k[b]. Rows are stored unscaled, in FFT bin order
+ * (bin 0 = DC, bin b at b Fs / nfft Hz, from nfft / 2 on at (b - nfft) Fs / nfft). info.scale = 1 / (A sum w[i]^2), the sum of the double
+ * products in ascending i, is the factor to a per-bin mean power; the consumer applies it.
+ * Bands: band q = (stream, lo_hz, hi_hz) with -Fs / 2 <= lo <= hi < Fs / 2. bin(f) = floor((2 f nfft + Fs) / (2 Fs)) mod nfft in 64-bit
+ * integers, floor toward minus infinity, the result in [0, nfft). The band is the bins from bin(lo) upward, with wrap-around at nfft, to
+ * bin(hi) inclusive: ((bin(hi) - bin(lo)) mod nfft) + 1 of them; pirip_hip_spec_band_bins returns bin(lo) and that count. Per complete row:
+ * power = the sum of the band's row[b] from +0 in that walking order, plain float adds; peak = the largest of them (the first bin's value,
+ * replaced by each later one that compares greater); peak_bin = its bin, the first in walking order on a tie. Bands may overlap, and
+ * their number per stream is not limited.
+ * State, per stream: the samples of its incomplete segments (fewer than nfft, in in_format), the running row[] of its incomplete row, and
+ * on the host the count of samples pushed. Every output is a function of the stream's own samples since the last reset: any cutting of
+ * the same input into calls gives the one-shot rows and band entries bit for bit (n = 1 and calls that complete no segment included), and
+ * a stream's outputs depend neither on the other streams nor on which bands the handle has.
+ * PIRIP_ERR_BAD_ARG for out NULL, bands NULL with nbands > 0, Fs < 2, nstreams < 1, nbands < 0, avg < 1, an in_format other than the two,
+ * a band's stream outside [0, nstreams), lo > hi or an edge outside [-Fs/2, Fs/2). PIRIP_ERR_UNSUPPORTED for any other nfft or hop,
+ * avg > 65536, Fs > 2^24, nstreams > 65535. Every argument check comes before a device is looked for; no CPU fallback: without a device
+ * PIRIP_ERR_NO_DEVICE. Create sizes everything and synchronises. */
+int pirip_hip_spec_create(int Fs, int in_format, int nfft, int hop, int avg, int nstreams, int nbands, const pirip_spec_band *bands, int device,
+                          pirip_hip_spec **out);
+int pirip_hip_spec_destroy(pirip_hip_spec *spec);
+int pirip_hip_spec_get_info(const pirip_hip_spec *spec, pirip_spec_info *info);
+/* The window of nfft points. Host only: no device is looked for. PIRIP_ERR_BAD_ARG for w NULL, PIRIP_ERR_UNSUPPORTED for another nfft. */
+int pirip_hip_spec_window(int nfft, float *w);
+/* Band q's first bin and number of bins (each pointer may be NULL). PIRIP_ERR_BAD_ARG for a band outside [0, nbands). */
+int pirip_hip_spec_band_bins(const pirip_hip_spec *spec, int band, int32_t *first_bin, int32_t *nbins);
+/* Rows the next push of n samples completes; host arithmetic: with S(t) = 0 for t < nfft, else (t - nfft) / hop + 1, the complete segments
+ * of t samples, and P the samples pushed so far, S(P + n) / A - S(P) / A (integer divisions). n = 0 is allowed. Negative: PIRIP_ERR_*. */
+int64_t pirip_hip_spec_nrows(const pirip_hip_spec *spec, int64_t n);
+/* n more samples of every stream, stream r at d_in + r in_stride_bytes (device memory, in_format). The push that completes the rows
+ * j0 .. j0 + m - 1, m = pirip_hip_spec_nrows(spec, n), writes row j0 + i of stream r at d_rows + r stream_stride + i row_stride (strides in
+ * floats, nfft floats each; d_rows may be NULL: no rows are stored) and band q's entry i at d_bands + q band_stride + i (stride in entries;
+ * d_bands NULL if and only if nbands == 0). A push that completes nothing writes nothing. With d_rows == NULL the band entries are the same
+ * bits. Enqueued on hip_stream (NULL = default stream), one HIP stream per handle; never synchronises, never allocates.
+ * PIRIP_ERR_BAD_ARG for NULL spec or d_in, d_bands NULL with nbands > 0, n < 1, input rows that are not whole samples or overlap (a
+ * pointer or stride that is no multiple of the sample's size, a stride below n samples with nstreams > 1), d_rows or d_bands that is not
+ * 4-byte aligned, row_stride < nfft with m > 1, stream_stride < (m - 1) row_stride + nfft with m > 0 and nstreams > 1, band_stride < m with
+ * nbands > 1. PIRIP_ERR_UNSUPPORTED when the count of samples pushed would reach 2^53. A refused push enqueues nothing and changes no state. */
+int pirip_hip_spec_push(pirip_hip_spec *spec, const void *d_in, size_t in_stride_bytes, int64_t n, float *d_rows, size_t row_stride,
+                        size_t stream_stride, pirip_spec_band_row *d_bands, size_t band_stride, void *hip_stream);
+/* Forget the history: the next sample is sample 0 of segment 0 of row 0. Host state only; nothing is enqueued. */
+int pirip_hip_spec_reset(pirip_hip_spec *spec, void *hip_stream);
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

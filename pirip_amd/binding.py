@@ -98,6 +98,19 @@ class AirInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("Fs", "ntx", "nrx", "npaths", "in_format", "out_format", "max_delay", "device")]
 
 
+class SpecBand(C.Structure):
+    """pirip_spec_band: the stream, and the band's edges in Hz, -Fs/2 <= lo <= hi < Fs/2"""
+    _fields_ = [("stream", C.c_int32), ("lo_hz", C.c_int32), ("hi_hz", C.c_int32)]
+
+
+class SpecInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("Fs", "in_format", "nfft", "hop", "avg", "nstreams", "nbands", "device")] + [("scale", C.c_double)]
+
+
+# pirip_spec_band_row as a numpy structured dtype (12 bytes, the C layout): what HipSpectrum.push's band entries are on the host
+SPEC_BAND_ROW_DTYPE = [("power", "<f4"), ("peak", "<f4"), ("peak_bin", "<i4")]
+
+
 class LdpcInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("n", "k", "bits_per_frame", "data_bytes", "nbits_per_call", "max_iter", "nstreams")] + \
                [("name", C.c_char * 64)]
@@ -264,6 +277,15 @@ def lib():
     L.pirip_hip_air_reset_drift.argtypes = [vp, i64, i64, vp]
     L.pirip_hip_air_create_fade.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, C.c_uint64, C.c_int32, i32, C.POINTER(vp)]
     L.pirip_hip_air_fade_table.argtypes = [i32, C.c_uint64, C.POINTER(AirFade), vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
+    L.pirip_hip_spec_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(vp)]
+    L.pirip_hip_spec_destroy.argtypes = [vp]
+    L.pirip_hip_spec_get_info.argtypes = [vp, C.POINTER(SpecInfo)]
+    L.pirip_hip_spec_window.argtypes = [i32, vp]
+    L.pirip_hip_spec_band_bins.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
+    L.pirip_hip_spec_nrows.restype = i64
+    L.pirip_hip_spec_nrows.argtypes = [vp, i64]
+    L.pirip_hip_spec_push.argtypes = [vp, vp, sz, i64, vp, sz, sz, vp, sz, vp]
+    L.pirip_hip_spec_reset.argtypes = [vp, vp]
     _lib = L
     return L
 
@@ -1138,6 +1160,121 @@ class HipAir:
         ms, left = C.c_int32(0), C.c_int64(0)
         _chk(self.L.pirip_hip_air_get_drift(self.h, C.byref(ms), C.byref(left)), "pirip_hip_air_get_drift")
         return ms.value, left.value
+
+
+class HipSpectrum:
+    """Band monitor (include/pirip_hip.h section P): averaged power spectra of nstreams wideband IQ streams and the power, peak and peak bin
+    of a list of bands, block after block. nfft: 256, 1024 or 4096; hop: nfft (None) or nfft / 2; avg: segments per row; bands: SpecBand
+    entries or tuples (stream, lo_hz, hi_hz); in_format: IN_CU8_CSDR or IN_CF32. The incomplete segments and the running row stay on the
+    device: any cutting of a stream into push() calls gives the same rows and band entries. db() and occupied() work on what push()
+    returned once it is on the host, in numpy and without a device."""
+
+    def __init__(self, Fs, nfft, hop=None, avg=1, nstreams=1, bands=(), in_format=IN_CU8_CSDR, device=-1):
+        self.L = lib()
+        self.bands = [b if isinstance(b, SpecBand) else SpecBand(int(b[0]), int(b[1]), int(b[2])) for b in bands]
+        arr = (SpecBand * max(len(self.bands), 1))(*self.bands)
+        h = C.c_void_p()
+        _chk(self.L.pirip_hip_spec_create(int(Fs), int(in_format), int(nfft), int(nfft if hop is None else hop), int(avg), int(nstreams),
+                                          len(self.bands), C.addressof(arr) if self.bands else None, device, C.byref(h)), "pirip_hip_spec_create")
+        self.h = h
+        self.info = SpecInfo()
+        _chk(self.L.pirip_hip_spec_get_info(self.h, C.byref(self.info)), "pirip_hip_spec_get_info")
+        self.Fs, self.nfft, self.hop, self.avg, self.nstreams, self.nbands = (self.info.Fs, self.info.nfft, self.info.hop, self.info.avg,
+                                                                             self.info.nstreams, self.info.nbands)
+        self.scale = float(self.info.scale)
+        self.in_format = int(in_format)
+        self.bytes_per_sample = 8 if in_format == IN_CF32 else 2
+
+    def close(self):
+        if getattr(self, "h", None):
+            self.L.pirip_hip_spec_destroy(self.h)
+            self.h = None
+
+    __del__ = close
+
+    def window(self):
+        return spec_window(self.nfft)
+
+    def band_bins(self, q):
+        """(first bin, number of bins) of band q: the bins first, first + 1, ... with wrap-around at nfft"""
+        first, count = C.c_int32(0), C.c_int32(0)
+        _chk(self.L.pirip_hip_spec_band_bins(self.h, int(q), C.byref(first), C.byref(count)), "pirip_hip_spec_band_bins")
+        return first.value, count.value
+
+    def nrows(self, n):
+        """rows the next push of n samples completes (host arithmetic)"""
+        m = int(self.L.pirip_hip_spec_nrows(self.h, int(n)))
+        if m < 0:
+            _chk(m, "pirip_hip_spec_nrows")
+        return m
+
+    def push(self, x, rows=None, stream=None):
+        """x: a torch tensor on the device, [nstreams, n, 2] uint8 or float32 (or [n, 2] with one stream), the samples that follow the last
+        call's. Returns (rows, bands): rows a float32 tensor [nstreams, m, nfft] of the m rows the call completed, unscaled, in FFT bin
+        order (None with rows=False), bands a uint8 tensor [nbands, m, 12] of pirip_spec_band_row entries (band_rows() reads it on the
+        host). Does not synchronise."""
+        import torch
+        if x.dim() == 2:
+            x = x.unsqueeze(0)
+        if x.dim() != 3 or x.shape[0] != self.nstreams or x.shape[2] != 2 or x.element_size() * 2 != self.bytes_per_sample or x.stride(2) != 1 or \
+                x.stride(1) != 2:
+            raise ValueError("x: [nstreams, n, 2] in the handle's input format, samples contiguous")
+        n = int(x.shape[1])
+        m = self.nrows(n)
+        want_rows = rows is None or bool(rows)
+        d_rows = torch.empty((self.nstreams, m, self.nfft), dtype=torch.float32, device=x.device) if want_rows else None
+        # (never an empty allocation: a push that completes nothing still hands over a pointer)
+        d_bands = torch.empty((self.nbands, max(m, 1), 12), dtype=torch.uint8, device=x.device)
+        self.push_raw(x, x.stride(0) * x.element_size(), n, d_rows, self.nfft, max(m, 1) * self.nfft, d_bands if self.nbands else None, max(m, 1),
+                      stream)
+        return d_rows, d_bands[:, :m]
+
+    def push_raw(self, d_in, in_stride, n, d_rows, row_stride, stream_stride, d_bands, band_stride, stream=None):
+        """pirip_hip_spec_push on device pointers or tensors: in_stride in bytes, row_stride / stream_stride in floats, band_stride in entries"""
+        _chk(self.L.pirip_hip_spec_push(self.h, _dev(d_in), int(in_stride), int(n), _dev(d_rows), int(row_stride), int(stream_stride),
+                                        _dev(d_bands), int(band_stride), _hip_stream(stream)), "pirip_hip_spec_push")
+
+    def reset(self, stream=None):
+        """forget the history: the next sample starts segment 0 of row 0"""
+        _chk(self.L.pirip_hip_spec_reset(self.h, _hip_stream(stream)), "pirip_hip_spec_reset")
+
+    @staticmethod
+    def band_rows(bands):
+        """push()'s band tensor (or its numpy copy) as a structured array [nbands, m] with the fields power, peak, peak_bin"""
+        import numpy as np
+        b = bands.cpu().numpy() if hasattr(bands, "cpu") else np.asarray(bands)
+        return np.ascontiguousarray(b).view(SPEC_BAND_ROW_DTYPE).reshape(b.shape[0], b.shape[1])
+
+    def db(self, rows):
+        """10 log10(rows scale) of rows [..., nfft] on the host, the bins shifted to dash.py's axis: entry i at -Fs/2 + i Fs/nfft"""
+        return spec_db(rows, self.scale)
+
+    def occupied(self, band_rows, noise_band, ratio_db):
+        """band_rows: band_rows() of a push, [nbands, m]. True where a band's power per bin exceeds that of band `noise_band` by ratio_db"""
+        return spec_occupied(band_rows, [self.band_bins(q)[1] for q in range(self.nbands)], noise_band, ratio_db)
+
+
+def spec_window(nfft):
+    """pirip_hip_spec_window (host only): the nfft floats of the band monitor's window"""
+    import numpy as np
+    w = np.zeros(int(nfft), dtype=np.float32)
+    _chk(lib().pirip_hip_spec_window(int(nfft), w.ctypes.data), "pirip_hip_spec_window")
+    return w
+
+
+def spec_db(rows, scale):
+    """HipSpectrum.db without a handle: rows [..., nfft] (numpy or a tensor), scale = info.scale"""
+    import numpy as np
+    r = rows.cpu().numpy() if hasattr(rows, "cpu") else np.asarray(rows)
+    with np.errstate(divide="ignore"):
+        return np.fft.fftshift(10.0 * np.log10(r.astype(np.float64) * float(scale)), axes=-1)
+
+
+def spec_occupied(band_rows, nbins, noise_band, ratio_db):
+    """HipSpectrum.occupied without a handle: nbins[q] the number of bins of band q"""
+    import numpy as np
+    per_bin = band_rows["power"].astype(np.float64) / np.asarray(nbins, dtype=np.float64)[:, None]
+    return per_bin > per_bin[int(noise_band)][None, :] * 10.0 ** (float(ratio_db) / 10.0)
 
 
 def air_fade(f):

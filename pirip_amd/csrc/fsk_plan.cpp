@@ -17,6 +17,18 @@ struct cf { float re, im; };
 inline cf cmul(cf a, cf b) { return {a.re * b.re - a.im * b.im, a.re * b.im + a.im * b.re}; }
 }  // namespace
 
+// FFT twiddles exactly as kiss_fft_alloc(): float of double cos/sin
+void fft_twiddles(int nfft, std::vector<float> *twiddle)
+{
+    twiddle->resize(2 * (size_t)nfft);
+    for (int i = 0; i < nfft; i++) {
+        const double pi = 3.141592653589793238462643383279502884197169399375105820974944;
+        double phase = -2 * pi * i / nfft;
+        (*twiddle)[2 * i] = (float)std::cos(phase);
+        (*twiddle)[2 * i + 1] = (float)std::sin(phase);
+    }
+}
+
 int FskPlan::init(int Fs, int Rs, int M, int P, int Nsym, int est_min, int est_max,
                   int freq_est_type, int tone_spacing, int in_format, const pirip_fsk_recalled *recalled)
 {
@@ -101,14 +113,7 @@ int FskPlan::init(int Fs, int Rs, int M, int P, int Nsym, int est_min, int est_m
         }
     }
 
-    // FFT twiddles exactly as kiss_fft_alloc(): float of double cos/sin
-    twiddle.resize(2 * (size_t)Ndft);
-    for (int i = 0; i < Ndft; i++) {
-        const double pi = 3.141592653589793238462643383279502884197169399375105820974944;
-        double phase = -2 * pi * i / Ndft;
-        twiddle[2 * i] = (float)std::cos(phase);
-        twiddle[2 * i + 1] = (float)std::sin(phase);
-    }
+    fft_twiddles(Ndft, &twiddle);
 
     // factorisation: 4s first, then a single 2 (Ndft is a power of two)
     int radices[kMaxStages], ms[kMaxStages], nst = 0;

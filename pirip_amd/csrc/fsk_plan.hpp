@@ -85,6 +85,9 @@ struct FskPlan {
              int freq_est_type, int tone_spacing, int in_format, const pirip_fsk_recalled *recalled = nullptr);
 };
 
+// kiss_fft_alloc's forward twiddles for any nfft, [nfft][2]: what FskPlan::twiddle holds for Ndft (the band monitor's transform reads them too)
+void fft_twiddles(int nfft, std::vector<float> *twiddle);
+
 // Tx-side / measurement-instrument helpers shared by the CPU tools (fsk_mod,
 // fsk_get_test_bits, fsk_put_test_bits) -- plain scalar C++, never on the GPU path.
 struct FskMod {
