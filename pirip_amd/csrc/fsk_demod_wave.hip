@@ -338,6 +338,23 @@ constexpr bool wave_locked_paths_instance(int M, int TS, int P, int NDFT, int FM
     return M == 2 && TS == 24 && P == 24 && NDFT == 256 && FMT == PIRIP_IN_CU8_FSKDEMOD && !FFT_FMA && !MASK && BAND == 0;
 }
 
+// Instances whose timing tail issues fewer vector instructions per frame ("packed window powers"):
+//   powers: the tones' window sums are squared as register pairs (v_pk_mul / v_pk_fma: x0^2 + x1^2 .., y0^2 + y1^2 ..) and the two halves
+//           added once, 3 instructions per window start where there were 5 (2-FSK). The four squares are summed in another order: timing,
+//           ppm and fract may move in their last bits (DESIGN.md 5's contract for the wave kernels); the window sums are the same words.
+//           The window starts are handed to hipcc four at a time behind a scheduling fence (a-7 has why).
+//   ppm:    appm = x / Nsym is div_rn_const where x is +0 or |x| >= 2^-125 (one wave-uniform test; tools/div_const_check.c and
+//           pirip_hip_selftest_div cover both signs), else -- and under the test hook FskDims::frame_cache == 0 -- the IEEE divide:
+//           the same word either way.
+// Opt-in by the rule of wave_locked_paths_instance: the register report (profiles/wp_resources_{parent,result}.txt) shows no VGPR
+// spill, the same occupancy and no more spilled SGPRs, AND an interleaved A/B was taken (profiles/wp_ab_headline.txt, wp_ab_band_only.txt):
+// the `fsk_demod -p 24` instance and its band-only twin -- the two go together, the band-only estimator's contract being that it changes
+// no output word of the full one. Every instance not named here compiles the code it had.
+constexpr bool wave_packed_power_instance(int M, int TS, int P, int NDFT, int FMT, bool FFT_FMA, bool MASK, int BAND)
+{
+    return M == 2 && TS == 24 && P == 24 && NDFT == 256 && FMT == PIRIP_IN_CU8_FSKDEMOD && !FFT_FMA && !MASK;
+}
+
 // Instances whose launches raise the priority of their last residency's workgroups (the "launch tail" block in front of the frame loop):
 // all but those that the register report (tools/kernel_resources.sh, profiles/lt_resources_{parent,result}.txt) shows spilling more SGPRs
 // with the block than without. They keep the prologue they had.
@@ -378,6 +395,7 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
     constexpr bool PLAIN = wave_plain_instance(M, TS, P, NDFT, FMT, WPS, FFT_FMA, MASK, BAND);
     constexpr bool ARGMAX_SINGLE = !PLAIN && !wave_two_pass_argmax_instance(M, TS, FMT, MASK, BAND);
     constexpr bool TAIL_PRIO = wave_tail_prio_instance(M, TS, P, NDFT, FMT, WPS, FFT_FMA, MASK, BAND);
+    constexpr bool PACKED_POWER = wave_packed_power_instance(M, TS, P, NDFT, FMT, FFT_FMA, MASK, BAND);
     static_assert(offsetof(DemodArgs, d) == 0, "the argument block is the first kernel argument");
     auto ap = [&]() {
         if constexpr (INPLACE) return (const __attribute__((address_space(4))) DemodArgs *)__builtin_amdgcn_kernarg_segment_ptr();
@@ -1356,8 +1374,18 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
         {
             v2f prpi{0.f, 0.f};
             v2f ft{0.f, 0.f};                                                // .x = sum over tones of |window sum|^2 (.y rides along unused)
+            // PACKED_POWER: hipcc is handed GROUP window starts at a time, fenced in front (the group's first phasor read is issued ahead
+            // of its arithmetic: with the packed squares hipcc otherwise sinks every read to its use and each window start waits out the
+            // LDS latency -- 1.4 % SLOWER than the scalar squares) and tied behind. Inside a group the window starts' chains interleave,
+            // which fills most of the wait states between a DPP add and the packed square that reads it. Interleaved A/B
+            // (profiles/wp_ab_candidates.txt): 1 < 3 < 4; from 6 on the kernel spills VGPRs.
+            constexpr int GROUP = PACKED_POWER ? 4 : 1;
+            static_assert(P % GROUP == 0, "whole groups of window starts");
 #pragma unroll
             for (int q = 0; q < P; q++) {
+                v2f sq;                                                      // PACKED_POWER: (sum over tones of re^2, ... of im^2)
+                const v2f tp = *(const v2f *)&s_tph[q];    // exp(+j 2 pi q / P), uniform LDS read
+                if (PACKED_POWER && q % GROUP == 0) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int m = 0; m < M; m++) {
                     const v2f own = fi[m][q];
@@ -1365,15 +1393,26 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
                     w0.x = add_lane_up(own.x, tot[m].x - own.x);
                     w0.y = add_lane_up(own.y, tot[m].y - own.y);
                     fi[m][q] = w0;
-                    // |w0|^2 (into / onto ft.x) as asm: left to hipcc, the SLP vectoriser pairs these across tones and pays five v_mov per window start
-                    if (m == 0) asm("v_mul_f32 %0, %1, %1\n\tv_fma_f32 %0, %2, %2, %0" : "=&v"(ft.x) : "v"(w0.y), "v"(w0.x));
-                    else { float t2; asm("v_mul_f32 %0, %2, %2\n\tv_fma_f32 %0, %3, %3, %0\n\tv_add_f32 %1, %1, %0" : "=&v"(t2), "+v"(ft.x) : "v"(w0.y), "v"(w0.x)); }
+                    if constexpr (PACKED_POWER) {
+                        // the window sum is a register pair: both squares in one packed instruction per tone, the halves added once below
+                        if (m == 0) asm("v_pk_mul_f32 %0, %1, %1" : "=v"(sq) : "v"(w0));
+                        else asm("v_pk_fma_f32 %0, %1, %1, %0" : "+v"(sq) : "v"(w0));
+                    } else {
+                        // |w0|^2 (into / onto ft.x) as asm: left to hipcc, the SLP vectoriser pairs these across tones and pays five v_mov per window start
+                        if (m == 0) asm("v_mul_f32 %0, %1, %1\n\tv_fma_f32 %0, %2, %2, %0" : "=&v"(ft.x) : "v"(w0.y), "v"(w0.x));
+                        else { float t2; asm("v_mul_f32 %0, %2, %2\n\tv_fma_f32 %0, %3, %3, %0\n\tv_add_f32 %1, %1, %0" : "=&v"(t2), "+v"(ft.x) : "v"(w0.y), "v"(w0.x)); }
+                    }
                 }
-                const v2f tp = *(const v2f *)&s_tph[q];    // exp(+j 2 pi q / P), uniform LDS read
+                if constexpr (PACKED_POWER) asm("v_add_f32 %0, %1, %2" : "=v"(ft.x) : "v"(sq.x), "v"(sq.y));
                 // (pr, pi) += ft1 * (cos, sin): one packed fma, ft1 broadcast from the low half (round 5: was two scalar fma)
                 asm("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[0,1,1]" : "+v"(prpi) : "v"(ft), "v"(tp));
-                // one window start at a time: without this tie hipcc computes all P*M window sums first and spills
-                asm volatile("" : "+v"(prpi), "+v"(fi[0][q]), "+v"(fi[M - 1][q]));
+                // one window start (PACKED_POWER: one group) at a time: without this tie hipcc computes all P*M window sums first and spills
+                if constexpr (GROUP == 1) asm volatile("" : "+v"(prpi), "+v"(fi[0][q]), "+v"(fi[M - 1][q]));
+                else if (q % GROUP == GROUP - 1) {
+                    asm volatile("" : "+v"(prpi));
+#pragma unroll
+                    for (int k = q + 1 - GROUP; k <= q; k++) asm volatile("" : "+v"(fi[0][k]), "+v"(fi[M - 1][k]));
+                }
             }
             const float pr = prpi.x, pi = prpi.y;
             if (lane <= NSYM) {                            // (Nsym+1)*P window starts in all
@@ -1402,7 +1441,12 @@ __global__ __launch_bounds__(kWave * WPB, WPS) void fsk_demod_wave_kernel(DemodA
             const float d_norm = norm_rx_timing - sc_norm_rx_timing;
             sc_norm_rx_timing = norm_rx_timing;
             if (fabsf(d_norm) < 0.2f) {
-                const float appm = (1e6f * d_norm) / (float)NSYM;      // (the expression every kernel and capture.hip's ppm recomputation share)
+                // (the expression every kernel and capture.hip's ppm recomputation share; PACKED_POWER: the quotient by div_rn_const where the
+                // dividend is in its domain -- +0 or |x| >= 2^-125 -- and the test hook is off: 3 instructions + the test for the IEEE sequence's 13)
+                const float x6 = 1e6f * d_norm;
+                float appm;
+                if (PACKED_POWER && !(ninp_fc & kFcNever) && __all(fabsf(x6) >= 0x1p-125f || fbits(x6) == 0u)) appm = div_rn_const<NSYM>(x6);
+                else appm = x6 / (float)NSYM;
                 sc_ppm = (0.9f * sc_ppm) + (0.1f * appm);
             }
             nin_next = N;
@@ -1719,6 +1763,10 @@ hipError_t selftest_div(unsigned long long *mismatches)
         hipLaunchKernelGGL(div_selftest_kernel<3>, dim3(4096), dim3(256), 0, 0, d, 0u, 0x7f7fffffu);                 // every finite x >= 0
         hipLaunchKernelGGL(div_selftest_kernel<50>, dim3(4096), dim3(256), 0, 0, d + 1, 0u, 0u);
         hipLaunchKernelGGL(div_selftest_kernel<50>, dim3(4096), dim3(256), 0, 0, d + 1, 0x01000000u, 0x7f7fffffu);
+        // the negative side (the ppm smoother's dividend has either sign): every finite x < 0 for / 3, x <= -2^-125 for / 50; -0 is in
+        // neither domain (the corrected product gives +0)
+        hipLaunchKernelGGL(div_selftest_kernel<3>, dim3(4096), dim3(256), 0, 0, d, 0x80000001u, 0xff7fffffu);
+        hipLaunchKernelGGL(div_selftest_kernel<50>, dim3(4096), dim3(256), 0, 0, d + 1, 0x81000000u, 0xff7fffffu);
         unsigned long long h[2] = {0, 0};
         e = hipMemcpy(h, d, sizeof(h), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipGetLastError();

@@ -77,7 +77,9 @@ __device__ __forceinline__ float logbesseli0_upstream(float x)
 // float on the CPU (tools/div_const_check.c) and on the device (pirip_hip_selftest_div):
 //   C = 3:  every finite x >= 0, the denormals included;
 //   C = 50: x = 0 and every finite x >= 2^-125 (167 772 denormals and floats below 2^-125 round the other way).
-// Not in either domain: +inf (the residual fma is inf - inf: NaN, where the quotient is +inf) and NaN (NaN either way). Callers guard both
+// Every operation of the form is odd in x, so the negative side mirrors the positive one (every finite x < 0 for C = 3, x <= -2^-125 for
+// C = 50: checked the same way) with one exception: x = -0 gives +0 (the residual fma(+0, c, -0) is +0), where the quotient is -0.
+// Not in either domain: +-inf (the residual fma is inf - inf: NaN, where the quotient is +-inf) and NaN (NaN either way). Callers guard both
 // ends with a wave-uniform range test.
 template <int C>
 __device__ __forceinline__ float div_rn_const(float x)
@@ -185,7 +187,7 @@ const char *demod_wave_source_hash();                              // Makefile: 
 // exhaustive device-side check of the wave kernel's correctly rounded square roots (x = 0 and every float in [2^-96, FLT_MAX])
 hipError_t selftest_sqrt(unsigned long long *mismatches);
 // the fused FSK_LDPC hand-over's x / 3 and x / 50 (x * RN(1/c) corrected once) against the IEEE quotient on their domains (div_rn_const):
-// x / 3 for every finite x >= 0, x / 50 for x = 0 and every float in [2^-125, FLT_MAX]
+// x / 3 for every finite x >= 0, x / 50 for x = 0 and every float in [2^-125, FLT_MAX]; and the same ranges negated, without -0
 hipError_t selftest_div(unsigned long long *mismatches);       // (count for / 50, saturated) << 32 | count for / 3
 
 }  // namespace pirip
