@@ -6,6 +6,7 @@ bench.py and the tests; it never imports the CPU oracle and has no CPU compute p
 """
 from .binding import (  # noqa: F401
     PiripError, FskParams, HipDemod, HipDecim, lib, lib_path, build, device_count, selftest_sqrt, selftest_div,
+    StreamState, kernel_source_hash, selftest_atan2,
     IN_CU8_FSKDEMOD, IN_CU8_CSDR, IN_CS16, IN_CF32, STATS_PER_FRAME,
     HipTestBits, testframe_payload, HipRepeater, HipPing, PingConfig, PingEntry, PING_ENTRY_DTYPE, HipAir, AirPath, AirPathEx, AirInfo,
     AirFade, air_fade, air_fade_table, launch_first_tail_block,

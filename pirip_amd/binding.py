@@ -3,10 +3,16 @@
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
 library is missing or no HIP device is usable the calls raise PiripError.
+
+Every prototype of the header has one entry in SIGNATURES, applied once by lib(); every handle class is a _Handle, which owns the
+library, the C handle and its life cycle. tests/test_binding_abi_cpu.py holds the table and the structures below to the header.
 """
 import ctypes as C
 import os
 import subprocess
+import sys
+
+import numpy as np
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # PIRIP_HIP_LIB: measurement builds only (e.g. the -DPIRIP_WAVE_TIMING library tools/phase_split.py reads its cycle split from)
@@ -31,9 +37,22 @@ class FskInfo(C.Structure):
                 ("nin_max", C.c_int), ("nstreams", C.c_int), ("bytes_per_sample", C.c_int)]
 
 
+class FskRecalled(C.Structure):
+    """pirip_fsk_recalled: the constants held from recall of codec2, as data (include/pirip_hip.h)."""
+    _fields_ = [("hann_denominator_ndft", C.c_int), ("tc", C.c_float), ("est_space_rs", C.c_float), ("nin_threshold", C.c_float),
+                ("nin_step_div", C.c_int), ("s16_scale", C.c_float), ("u8d_offset", C.c_float), ("u8d_scale", C.c_float),
+                ("ndft_rule", C.c_int), ("sf_power", C.c_int)]
+
+
 class CaptureReport(C.Structure):
     _fields_ = [("segments", C.c_int32), ("segment_frames", C.c_int32), ("passes", C.c_int32), ("segments_rerun", C.c_int32),
                 ("frames_demodulated", C.c_int64)]
+
+
+class StreamState(C.Structure):
+    """pirip_stream_state: what codec2 keeps in struct FSK between calls, 13 words (HipDemod.stream_state)"""
+    _fields_ = [("nin", C.c_int)] + [(n, C.c_float) for n in ("norm_rx_timing", "ppm", "snr_est", "SNRest", "EbNodB", "v_est")] + \
+               [("f_est", C.c_float * 4), ("rx_sig_pow", C.c_float), ("rx_nse_pow", C.c_float)]
 
 
 class ChanInfo(C.Structure):
@@ -116,9 +135,188 @@ class LdpcInfo(C.Structure):
                [("name", C.c_char * 64)]
 
 
+class ChainGroup(C.Structure):
+    """struct pirip_chain_group (include/pirip_hip.h)"""
+    _fields_ = [("dem", C.c_void_p), ("ldpc", C.c_void_p), ("d_in", C.c_void_p), ("d_status", C.c_void_p), ("d_payload", C.c_void_p),
+                ("d_info", C.c_void_p), ("d_stats", C.c_void_p), ("d_nframes", C.c_void_p), ("d_consumed", C.c_void_p)]
+
+
 RX_TRIAL_SYNC, RX_SYNC, RX_BITS, RX_BIT_ERRORS = 1, 2, 4, 8
 LDPC_INFO_PER_CALL = 10
 STANDIN_CODE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "standin_256_512_4.code")
+
+
+def _signatures():
+    vp, i32, i64, u64, sz, f32, cs, P = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_size_t, C.c_float, C.c_char_p, C.POINTER
+    return {
+        # section A: batch-of-streams demodulator
+        "pirip_hip_create": (i32, [P(FskParams), i32, i32, P(vp)]),
+        "pirip_hip_recalled_defaults": (None, [P(FskRecalled)]),
+        "pirip_hip_create_recalled": (i32, [P(FskParams), P(FskRecalled), i32, i32, P(vp)]),
+        "pirip_hip_destroy": (i32, [vp]),
+        "pirip_hip_get_info": (i32, [vp, P(FskInfo)]),
+        "pirip_hip_get_kernel": (i32, [vp]),
+        "pirip_hip_set_exact_first_frame": (i32, [vp, i32]),
+        "pirip_hip_get_kernel_name": (i32, [vp, cs, sz]),
+        "pirip_hip_reset": (i32, [vp, vp]),
+        "pirip_hip_clear_estimators": (i32, [vp, vp]),
+        "pirip_hip_demod_batch": (i32, [vp, vp, sz, i64, vp, sz, vp, sz, vp, sz, vp, vp, i64, vp]),
+        "pirip_hip_demod_capture": (i32, [vp, vp, i64, vp, vp, vp, i64, P(i64), P(i64), P(CaptureReport), vp]),
+        "pirip_hip_demod_capture_host": (i32, [vp, vp, i64, vp, vp, vp, i64, P(i64), P(i64), P(CaptureReport)]),
+        "pirip_hip_demod_host": (i32, [vp, vp, i64, vp, vp, vp, i64, P(i64), P(i64)]),
+        "pirip_hip_nin0": (i32, [vp]),
+        "pirip_hip_set_bit_packing": (i32, [vp, i32]),
+        "pirip_hip_set_estimator_band_only": (i32, [vp, i32]),
+        "pirip_hip_set_launch_tail_first": (i32, [vp, i32]),
+        "pirip_hip_get_launch_resident_blocks": (i32, [vp]),
+        "pirip_hip_launch_first_tail_block": (i32, [i32, i32, i32, i32]),
+        "pirip_hip_set_burst_mode": (i32, [vp, i32]),
+        "pirip_hip_get_Sf": (i32, [vp, i32, vp]),
+        "pirip_hip_enable_eye": (i32, [vp, i32]),
+        "pirip_hip_get_eye": (i32, [vp, i32, i32, vp, vp, vp]),
+        "pirip_hip_get_scalars": (i32, [vp, i32, vp]),
+        "pirip_hip_get_stream_state": (i32, [vp, i32, P(StreamState)]),
+        "pirip_hip_set_freq_est_limits": (i32, [vp, i32, i32]),
+        # section B: csdr front end, and B2: synthetic Tx
+        "pirip_hip_decim_create": (i32, [i32, f32, i32, i32, P(vp)]),
+        "pirip_hip_decim_destroy": (i32, [vp]),
+        "pirip_hip_decim_taps": (i32, [vp, vp, P(i32)]),
+        "pirip_hip_decim_set_arith": (i32, [vp, i32]),
+        "pirip_hip_decim_get_arith": (i32, [vp]),
+        "pirip_hip_decim_nout": (i64, [vp, i64]),
+        "pirip_hip_decim_batch": (i32, [vp, vp, sz, i64, vp, sz, i32, vp]),
+        "pirip_hip_synth_cu8": (i32, [i32, i32, i32, i32, vp, i32, vp, vp, sz, i64, vp, sz, i64, f32, f32, u64, vp]),
+        # section E: FSK_LDPC receive
+        "pirip_hip_ldpc_create": (i32, [cs, i32, i32, i32, i32, P(vp)]),
+        "pirip_hip_ldpc_destroy": (i32, [vp]),
+        "pirip_hip_ldpc_get_info": (i32, [vp, P(LdpcInfo)]),
+        "pirip_hip_ldpc_reset": (i32, [vp, vp]),
+        "pirip_hip_ldpc_get_llr_history": (i32, [vp, i32, vp]),
+        "pirip_hip_ldpc_get_layout_conflicts": (i32, [vp, P(i32), P(i32)]),
+        "pirip_hip_ldpc_rx_batch": (i32, [vp, vp, sz, vp, i32, vp, vp, vp, vp]),
+        "pirip_hip_fsk_ldpc_rx_batch": (i32, [vp, vp, vp, sz, i64, vp, vp, vp, vp, sz, vp, vp, i64, vp]),
+        "pirip_hip_fsk_ldpc_last_path": (i32, [vp]),
+        "pirip_hip_fsk_ldpc_rx_batch_groups": (i32, [P(ChainGroup), i32, sz, i64, sz, i64, vp]),
+        "pirip_hip_ldpc_rx_host": (i32, [vp, vp, i32, vp, vp, vp]),
+        "pirip_hip_ldpc_llr": (i32, [vp, vp, i32, vp, vp]),
+        "pirip_hip_ldpc_decode_llr": (i32, [vp, vp, i32, vp, vp, vp]),
+        # section G: streaming receiver
+        "pirip_hip_rx_create": (i32, [vp, vp, vp, i64, P(vp)]),
+        "pirip_hip_rx_destroy": (i32, [vp]),
+        "pirip_hip_rx_max_frames": (i64, [vp]),
+        "pirip_hip_rx_input": (i32, [vp, P(vp), P(sz)]),
+        "pirip_hip_rx_process": (i32, [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
+        "pirip_hip_rx_push": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]),
+        "pirip_hip_rx_get_counters": (i32, [vp, vp, vp]),
+        "pirip_hip_rx_reset": (i32, [vp, vp]),
+        # section H: channelizer
+        "pirip_hip_chan_create": (i32, [i32, i32, f32, i32, i32, i32, vp, vp, i32, P(vp)]),
+        "pirip_hip_chan_destroy": (i32, [vp]),
+        "pirip_hip_chan_get_info": (i32, [vp, P(ChanInfo)]),
+        "pirip_hip_chan_taps": (i32, [vp, vp, P(i32)]),
+        "pirip_hip_chan_nout": (i64, [vp, i64]),
+        "pirip_hip_chan_batch": (i32, [vp, vp, sz, i64, i64, vp, sz, vp]),
+        "pirip_hip_rx_create_chan": (i32, [vp, vp, vp, i64, P(vp)]),
+        # section I: FSK_LDPC transmit
+        "pirip_hip_tx_create": (i32, [cs, i32, i32, i32, i32, i32, P(vp)]),
+        "pirip_hip_tx_destroy": (i32, [vp]),
+        "pirip_hip_tx_get_info": (i32, [vp, P(TxInfo)]),
+        "pirip_hip_tx_set_tones": (i32, [vp, vp, i32]),
+        "pirip_hip_tx_set_gaps": (i32, [vp, vp, vp]),
+        "pirip_hip_tx_reset": (i32, [vp, vp]),
+        "pirip_hip_tx_max_syms": (i64, [vp, i32]),
+        "pirip_hip_tx_frame": (i32, [vp, vp, sz, vp, i32, vp, sz, i64, vp, vp, sz, vp]),
+        "pirip_hip_tx_modulate": (i32, [vp, vp, sz, vp, i64, i32, vp, sz, f32, f32, u64, vp]),
+        "pirip_hip_tx_records_to_iq": (i32, [vp, vp, sz, vp, i32, i64, i32, vp, sz, f32, f32, u64, vp, vp]),
+        "pirip_hip_tx_repeat_max_records": (i32, [vp, i32]),
+        "pirip_hip_tx_repeat_records": (i32, [vp, vp, sz, vp, sz, vp, i32, i32, vp, sz, i32, vp, vp]),
+        # section J: multiplexer
+        "pirip_hip_mux_create": (i32, [i32, i32, i32, f32, i32, i32, i32, vp, vp, vp, i32, P(vp)]),
+        "pirip_hip_mux_destroy": (i32, [vp]),
+        "pirip_hip_mux_get_info": (i32, [vp, P(MuxInfo)]),
+        "pirip_hip_mux_taps": (i32, [vp, vp, P(i32)]),
+        "pirip_hip_mux_nout": (i64, [vp, i64]),
+        "pirip_hip_mux_batch": (i32, [vp, vp, sz, i64, i64, vp, sz, vp]),
+        # section K: streaming transmitter
+        "pirip_hip_txs_create": (i32, [vp, vp, i64, i64, P(vp)]),
+        "pirip_hip_txs_destroy": (i32, [vp]),
+        "pirip_hip_txs_get_info": (i32, [vp, P(TxsInfo)]),
+        "pirip_hip_txs_send": (i32, [vp, vp, sz, vp, i32, vp, vp]),
+        "pirip_hip_txs_process": (i32, [vp, vp, sz, vp, vp]),
+        "pirip_hip_txs_get_counters": (i32, [vp, vp, vp, vp, vp]),
+        "pirip_hip_txs_reset": (i32, [vp, vp]),
+        # section L: test-frame counter
+        "pirip_hip_tbits_create": (i32, [i32, f32, vp, i32, i32, P(vp)]),
+        "pirip_hip_tbits_destroy": (i32, [vp]),
+        "pirip_hip_tbits_push": (i32, [vp, vp, sz, i32, i32, vp, i64, vp]),
+        "pirip_hip_tbits_get_counters": (i32, [vp, vp, vp, vp, vp]),
+        "pirip_hip_tbits_counters_device": (i32, [vp, P(vp)]),
+        "pirip_hip_tbits_reset": (i32, [vp, vp]),
+        "pirip_hip_tbits_testframe_payload": (i32, [i32, vp]),
+        "pirip_hip_tbits_set_payload": (i32, [vp, i32, vp]),
+        "pirip_hip_tbits_push_records": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, i32, vp]),
+        "pirip_hip_tbits_get_record_counters": (i32, [vp, vp, vp, vp, vp, vp]),
+        # section M: streaming repeater
+        "pirip_hip_rpt_create": (i32, [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, P(vp)]),
+        "pirip_hip_rpt_destroy": (i32, [vp]),
+        "pirip_hip_rpt_get_info": (i32, [vp, P(RptInfo)]),
+        "pirip_hip_rpt_push_records": (i32, [vp, vp, sz, vp, sz, vp, i32, vp, sz, vp]),
+        "pirip_hip_rpt_process": (i32, [vp, vp, sz, vp]),
+        "pirip_hip_rpt_push": (i32, [vp, vp, sz, vp, sz, vp]),
+        "pirip_hip_rpt_records": (i32, [vp] + [P(vp), P(sz)] * 3 + [P(vp)]),
+        "pirip_hip_rpt_offered": (i32, [vp, P(vp), P(sz), P(vp)]),
+        "pirip_hip_rpt_get_counters": (i32, [vp] + [vp] * 7),
+        "pirip_hip_rpt_reset": (i32, [vp, vp]),
+        # section N: ping terminal
+        "pirip_hip_ping_create": (i32, [vp, vp, vp, P(PingConfig), P(vp)]),
+        "pirip_hip_ping_destroy": (i32, [vp]),
+        "pirip_hip_ping_get_info": (i32, [vp, P(PingInfo)]),
+        "pirip_hip_ping_push_records": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, i32, vp, sz, vp]),
+        "pirip_hip_ping_process": (i32, [vp, vp, sz, vp]),
+        "pirip_hip_ping_push": (i32, [vp, vp, sz, vp, sz, vp]),
+        "pirip_hip_ping_records": (i32, [vp] + [P(vp), P(sz)] * 4 + [P(vp)]),
+        "pirip_hip_ping_offered": (i32, [vp, P(vp), P(sz), P(vp)]),
+        "pirip_hip_ping_get_counters": (i32, [vp] + [vp] * 9),
+        "pirip_hip_ping_get_log": (i32, [vp, i32, vp, i32, P(i32)]),
+        "pirip_hip_ping_reset": (i32, [vp, vp]),
+        # section O: channel
+        "pirip_hip_air_create": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, u64, i32, P(vp)]),
+        "pirip_hip_air_destroy": (i32, [vp]),
+        "pirip_hip_air_get_info": (i32, [vp, P(AirInfo)]),
+        "pirip_hip_air_set_sigma": (i32, [vp, vp, vp]),
+        "pirip_hip_air_push": (i32, [vp, vp, sz, i64, vp, sz, vp]),
+        "pirip_hip_air_reset": (i32, [vp, i64, vp]),
+        "pirip_hip_air_create_ex": (i32, [i32, i32, i32, i32, i32, i32, vp, vp, u64, C.c_int32, i32, P(vp)]),
+        "pirip_hip_air_interp_table": (i32, [vp, P(i32), P(i32)]),
+        "pirip_hip_air_get_drift": (i32, [vp, P(C.c_int32), P(i64)]),
+        "pirip_hip_air_reset_drift": (i32, [vp, i64, i64, vp]),
+        "pirip_hip_air_create_fade": (i32, [i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, u64, C.c_int32, i32, P(vp)]),
+        "pirip_hip_air_fade_table": (i32, [i32, u64, P(AirFade), vp, vp, P(f32), P(f32)]),
+        # section P: band monitor
+        "pirip_hip_spec_create": (i32, [i32, i32, i32, i32, i32, i32, i32, vp, i32, P(vp)]),
+        "pirip_hip_spec_destroy": (i32, [vp]),
+        "pirip_hip_spec_get_info": (i32, [vp, P(SpecInfo)]),
+        "pirip_hip_spec_window": (i32, [i32, vp]),
+        "pirip_hip_spec_band_bins": (i32, [vp, i32, P(C.c_int32), P(C.c_int32)]),
+        "pirip_hip_spec_nrows": (i64, [vp, i64]),
+        "pirip_hip_spec_push": (i32, [vp, vp, sz, i64, vp, sz, sz, vp, sz, vp]),
+        "pirip_hip_spec_reset": (i32, [vp, vp]),
+        # the library itself
+        "pirip_hip_find_code": (i32, [cs, cs, sz]),
+        "pirip_hip_version": (cs, []),
+        "pirip_hip_abi": (i32, [vp, vp, vp]),
+        "pirip_hip_abi_check": (i32, [i32, i32, sz]),
+        "pirip_hip_kernel_source_hash": (cs, []),
+        "pirip_hip_strerror": (cs, [i32]),
+        "pirip_hip_device_count": (i32, []),
+        "pirip_hip_selftest_sqrt": (i32, [P(u64)]),
+        "pirip_hip_selftest_div": (i32, [P(u64)]),
+        "pirip_hip_selftest_atan2": (i32, [vp, vp, vp, i32]),
+    }
+
+
+# C name -> (restype, argtypes): every prototype of include/pirip_hip.h, in the header's order
+SIGNATURES = _signatures()
 
 
 def lib_path():
@@ -153,166 +351,14 @@ def lib():
         except Exception:
             pass
     L = C.CDLL(_LIB)
-    vp, i32, i64, sz = C.c_void_p, C.c_int, C.c_int64, C.c_size_t
-    L.pirip_hip_version.restype = C.c_char_p
-    L.pirip_hip_strerror.restype = C.c_char_p
-    L.pirip_hip_strerror.argtypes = [i32]
-    L.pirip_hip_device_count.restype = i32
-    L.pirip_hip_create.argtypes = [C.POINTER(FskParams), i32, i32, C.POINTER(vp)]
-    L.pirip_hip_destroy.argtypes = [vp]
-    L.pirip_hip_get_info.argtypes = [vp, C.POINTER(FskInfo)]
-    L.pirip_hip_reset.argtypes = [vp, vp]
-    L.pirip_hip_demod_batch.argtypes = [vp, vp, sz, i64, vp, sz, vp, sz, vp, sz, vp, vp, i64, vp]
-    L.pirip_hip_demod_capture.argtypes = [vp, vp, i64, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64), C.POINTER(CaptureReport), vp]
-    L.pirip_hip_demod_host.argtypes = [vp, vp, i64, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64)]
-    L.pirip_hip_nin0.argtypes = [vp]
-    L.pirip_hip_get_Sf.argtypes = [vp, i32, vp]
-    L.pirip_hip_get_scalars.argtypes = [vp, i32, vp]
-    L.pirip_hip_set_burst_mode.argtypes = [vp, i32]
-    L.pirip_hip_set_bit_packing.argtypes = [vp, i32]
-    L.pirip_hip_set_estimator_band_only.argtypes = [vp, i32]
-    L.pirip_hip_set_freq_est_limits.argtypes = [vp, i32, i32]
-    L.pirip_hip_decim_create.argtypes = [i32, C.c_float, i32, i32, C.POINTER(vp)]
-    L.pirip_hip_decim_destroy.argtypes = [vp]
-    L.pirip_hip_decim_taps.argtypes = [vp, vp, C.POINTER(i32)]
-    L.pirip_hip_decim_nout.restype = i64
-    L.pirip_hip_decim_nout.argtypes = [vp, i64]
-    L.pirip_hip_decim_batch.argtypes = [vp, vp, sz, i64, vp, sz, i32, vp]
-    L.pirip_hip_synth_cu8.argtypes = [i32, i32, i32, i32, vp, i32, vp, vp, sz, i64, vp, sz, i64,
-                                      C.c_float, C.c_float, C.c_uint64, vp]
-    L.pirip_hip_ldpc_create.argtypes = [C.c_char_p, i32, i32, i32, i32, C.POINTER(vp)]
-    L.pirip_hip_ldpc_destroy.argtypes = [vp]
-    L.pirip_hip_ldpc_get_info.argtypes = [vp, C.POINTER(LdpcInfo)]
-    L.pirip_hip_ldpc_reset.argtypes = [vp, vp]
-    L.pirip_hip_ldpc_rx_batch.argtypes = [vp, vp, sz, vp, i32, vp, vp, vp, vp]
-    L.pirip_hip_ldpc_rx_host.argtypes = [vp, vp, i32, vp, vp, vp]
-    L.pirip_hip_fsk_ldpc_rx_batch.argtypes = [vp, vp, vp, sz, C.c_int64, vp, vp, vp, vp, sz, vp, vp, C.c_int64, vp]
-    L.pirip_hip_fsk_ldpc_last_path.argtypes = [vp]
-    L.pirip_hip_ldpc_llr.argtypes = [vp, vp, i32, vp, vp]
-    L.pirip_hip_ldpc_decode_llr.argtypes = [vp, vp, i32, vp, vp, vp]
-    L.pirip_hip_rx_create.argtypes = [vp, vp, vp, i64, C.POINTER(vp)]
-    L.pirip_hip_rx_destroy.argtypes = [vp]
-    L.pirip_hip_rx_max_frames.restype = i64
-    L.pirip_hip_rx_max_frames.argtypes = [vp]
-    L.pirip_hip_rx_input.argtypes = [vp, C.POINTER(vp), C.POINTER(sz)]
-    L.pirip_hip_rx_process.argtypes = [vp, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
-    L.pirip_hip_rx_push.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, vp, vp, vp, sz, vp, vp]
-    L.pirip_hip_rx_get_counters.argtypes = [vp, vp, vp]
-    L.pirip_hip_rx_reset.argtypes = [vp, vp]
-    L.pirip_hip_rx_create_chan.argtypes = [vp, vp, vp, i64, C.POINTER(vp)]
-    L.pirip_hip_chan_create.argtypes = [i32, i32, C.c_float, i32, i32, i32, vp, vp, i32, C.POINTER(vp)]
-    L.pirip_hip_chan_destroy.argtypes = [vp]
-    L.pirip_hip_chan_get_info.argtypes = [vp, C.POINTER(ChanInfo)]
-    L.pirip_hip_chan_taps.argtypes = [vp, vp, C.POINTER(i32)]
-    L.pirip_hip_chan_nout.restype = i64
-    L.pirip_hip_chan_nout.argtypes = [vp, i64]
-    L.pirip_hip_chan_batch.argtypes = [vp, vp, sz, i64, i64, vp, sz, vp]
-    L.pirip_hip_tx_create.argtypes = [C.c_char_p, i32, i32, i32, i32, i32, C.POINTER(vp)]
-    L.pirip_hip_tx_destroy.argtypes = [vp]
-    L.pirip_hip_tx_get_info.argtypes = [vp, C.POINTER(TxInfo)]
-    L.pirip_hip_tx_set_tones.argtypes = [vp, vp, i32]
-    L.pirip_hip_tx_set_gaps.argtypes = [vp, vp, vp]
-    L.pirip_hip_tx_reset.argtypes = [vp, vp]
-    L.pirip_hip_tx_max_syms.restype = i64
-    L.pirip_hip_tx_max_syms.argtypes = [vp, i32]
-    L.pirip_hip_tx_frame.argtypes = [vp, vp, sz, vp, i32, vp, sz, i64, vp, vp, sz, vp]
-    L.pirip_hip_tx_modulate.argtypes = [vp, vp, sz, vp, i64, i32, vp, sz, C.c_float, C.c_float, C.c_uint64, vp]
-    L.pirip_hip_tx_records_to_iq.argtypes = [vp, vp, sz, vp, i32, i64, i32, vp, sz, C.c_float, C.c_float, C.c_uint64, vp, vp]
-    L.pirip_hip_tx_repeat_max_records.argtypes = [vp, i32]
-    L.pirip_hip_tx_repeat_records.argtypes = [vp, vp, sz, vp, sz, vp, i32, i32, vp, sz, i32, vp, vp]
-    L.pirip_hip_mux_create.argtypes = [i32, i32, i32, C.c_float, i32, i32, i32, vp, vp, vp, i32, C.POINTER(vp)]
-    L.pirip_hip_mux_destroy.argtypes = [vp]
-    L.pirip_hip_mux_get_info.argtypes = [vp, C.POINTER(MuxInfo)]
-    L.pirip_hip_mux_taps.argtypes = [vp, vp, C.POINTER(i32)]
-    L.pirip_hip_mux_nout.restype = i64
-    L.pirip_hip_mux_nout.argtypes = [vp, i64]
-    L.pirip_hip_mux_batch.argtypes = [vp, vp, sz, i64, i64, vp, sz, vp]
-    L.pirip_hip_txs_create.argtypes = [vp, vp, i64, i64, C.POINTER(vp)]
-    L.pirip_hip_txs_destroy.argtypes = [vp]
-    L.pirip_hip_txs_get_info.argtypes = [vp, C.POINTER(TxsInfo)]
-    L.pirip_hip_txs_send.argtypes = [vp, vp, sz, vp, i32, vp, vp]
-    L.pirip_hip_txs_process.argtypes = [vp, vp, sz, vp, vp]
-    L.pirip_hip_txs_get_counters.argtypes = [vp, vp, vp, vp, vp]
-    L.pirip_hip_txs_reset.argtypes = [vp, vp]
-    L.pirip_hip_tbits_create.argtypes = [i32, C.c_float, vp, i32, i32, C.POINTER(vp)]
-    L.pirip_hip_tbits_destroy.argtypes = [vp]
-    L.pirip_hip_tbits_push.argtypes = [vp, vp, sz, i32, i32, vp, i64, vp]
-    L.pirip_hip_tbits_get_counters.argtypes = [vp, vp, vp, vp, vp]
-    L.pirip_hip_tbits_counters_device.argtypes = [vp, C.POINTER(vp)]
-    L.pirip_hip_tbits_reset.argtypes = [vp, vp]
-    L.pirip_hip_tbits_testframe_payload.argtypes = [i32, vp]
-    L.pirip_hip_tbits_set_payload.argtypes = [vp, i32, vp]
-    L.pirip_hip_tbits_push_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, i32, vp]
-    L.pirip_hip_tbits_get_record_counters.argtypes = [vp, vp, vp, vp, vp, vp]
-    L.pirip_hip_rpt_create.argtypes = [vp, vp, vp, i32, vp, i32, i32, i32, i32, i32, C.POINTER(vp)]
-    L.pirip_hip_rpt_destroy.argtypes = [vp]
-    L.pirip_hip_rpt_get_info.argtypes = [vp, C.POINTER(RptInfo)]
-    L.pirip_hip_rpt_push_records.argtypes = [vp, vp, sz, vp, sz, vp, i32, vp, sz, vp]
-    L.pirip_hip_rpt_process.argtypes = [vp, vp, sz, vp]
-    L.pirip_hip_rpt_push.argtypes = [vp, vp, sz, vp, sz, vp]
-    L.pirip_hip_rpt_records.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
-    L.pirip_hip_rpt_offered.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
-    L.pirip_hip_rpt_get_counters.argtypes = [vp, vp, vp, vp, vp, vp, vp, vp]
-    L.pirip_hip_rpt_reset.argtypes = [vp, vp]
-    L.pirip_hip_ping_create.argtypes = [vp, vp, vp, C.POINTER(PingConfig), C.POINTER(vp)]
-    L.pirip_hip_ping_destroy.argtypes = [vp]
-    L.pirip_hip_ping_get_info.argtypes = [vp, C.POINTER(PingInfo)]
-    L.pirip_hip_ping_push_records.argtypes = [vp, vp, sz, vp, sz, vp, sz, vp, sz, vp, i32, vp, sz, vp]
-    L.pirip_hip_ping_process.argtypes = [vp, vp, sz, vp]
-    L.pirip_hip_ping_push.argtypes = [vp, vp, sz, vp, sz, vp]
-    L.pirip_hip_ping_records.argtypes = [vp] + [C.POINTER(vp), C.POINTER(sz)] * 4 + [C.POINTER(vp)]
-    L.pirip_hip_ping_offered.argtypes = [vp, C.POINTER(vp), C.POINTER(sz), C.POINTER(vp)]
-    L.pirip_hip_ping_get_counters.argtypes = [vp] + [vp] * 9
-    L.pirip_hip_ping_get_log.argtypes = [vp, i32, vp, i32, C.POINTER(i32)]
-    L.pirip_hip_ping_reset.argtypes = [vp, vp]
-    L.pirip_hip_air_create.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, C.c_uint64, i32, C.POINTER(vp)]
-    L.pirip_hip_air_destroy.argtypes = [vp]
-    L.pirip_hip_air_get_info.argtypes = [vp, C.POINTER(AirInfo)]
-    L.pirip_hip_air_set_sigma.argtypes = [vp, vp, vp]
-    L.pirip_hip_air_push.argtypes = [vp, vp, sz, i64, vp, sz, vp]
-    L.pirip_hip_air_reset.argtypes = [vp, i64, vp]
-    L.pirip_hip_air_create_ex.argtypes = [i32, i32, i32, i32, i32, i32, vp, vp, C.c_uint64, C.c_int32, i32, C.POINTER(vp)]
-    L.pirip_hip_air_interp_table.argtypes = [vp, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-    L.pirip_hip_air_get_drift.argtypes = [vp, C.POINTER(C.c_int32), C.POINTER(C.c_int64)]
-    L.pirip_hip_air_reset_drift.argtypes = [vp, i64, i64, vp]
-    L.pirip_hip_air_create_fade.argtypes = [i32, i32, i32, i32, i32, i32, vp, i32, vp, vp, C.c_uint64, C.c_int32, i32, C.POINTER(vp)]
-    L.pirip_hip_air_fade_table.argtypes = [i32, C.c_uint64, C.POINTER(AirFade), vp, vp, C.POINTER(C.c_float), C.POINTER(C.c_float)]
-    L.pirip_hip_spec_create.argtypes = [i32, i32, i32, i32, i32, i32, i32, vp, i32, C.POINTER(vp)]
-    L.pirip_hip_spec_destroy.argtypes = [vp]
-    L.pirip_hip_spec_get_info.argtypes = [vp, C.POINTER(SpecInfo)]
-    L.pirip_hip_spec_window.argtypes = [i32, vp]
-    L.pirip_hip_spec_band_bins.argtypes = [vp, i32, C.POINTER(C.c_int32), C.POINTER(C.c_int32)]
-    L.pirip_hip_spec_nrows.restype = i64
-    L.pirip_hip_spec_nrows.argtypes = [vp, i64]
-    L.pirip_hip_spec_push.argtypes = [vp, vp, sz, i64, vp, sz, sz, vp, sz, vp]
-    L.pirip_hip_spec_reset.argtypes = [vp, vp]
+    for name, (restype, argtypes) in SIGNATURES.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise PiripError(f"{_LIB} does not export {name} (include/pirip_hip.h declares it): rebuild the library") from None
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
-
-
-def device_count():
-    return int(lib().pirip_hip_device_count())
-
-
-def selftest_sqrt():
-    """Mismatches of the wave kernel's correctly rounded square roots against (float)sqrt((double)x) over x = 0 and every
-    float in [2^-96, FLT_MAX], counted on the device (pirip_hip_selftest_sqrt): (v_sqrt variant << 32) | rsq variant."""
-    L = lib()
-    m = C.c_uint64(0)
-    L.pirip_hip_selftest_sqrt.argtypes = [C.POINTER(C.c_uint64)]
-    _chk(L.pirip_hip_selftest_sqrt(C.byref(m)), "pirip_hip_selftest_sqrt")
-    return int(m.value)
-
-
-def selftest_div():
-    """Mismatches of the fused hand-over's x / 3 and x / 50 (pirip_hip_selftest_div) against the device's IEEE quotient over their measured
-    domains -- x / 3: every finite x >= 0, denormals included; x / 50: x = 0 and every float in [2^-125, FLT_MAX]:
-    (count for / 50 << 32) | count for / 3."""
-    L = lib()
-    m = C.c_uint64(0)
-    L.pirip_hip_selftest_div.argtypes = [C.POINTER(C.c_uint64)]
-    _chk(L.pirip_hip_selftest_div(C.byref(m)), "pirip_hip_selftest_div")
-    return int(m.value)
 
 
 def _chk(rc, what):
@@ -320,11 +366,54 @@ def _chk(rc, what):
         raise PiripError(f"{what}: {lib().pirip_hip_strerror(rc).decode()} ({rc})")
 
 
-class FskRecalled(C.Structure):
-    """pirip_fsk_recalled: the constants held from recall of codec2, as data (include/pirip_hip.h)."""
-    _fields_ = [("hann_denominator_ndft", C.c_int), ("tc", C.c_float), ("est_space_rs", C.c_float), ("nin_threshold", C.c_float),
-                ("nin_step_div", C.c_int), ("s16_scale", C.c_float), ("u8d_offset", C.c_float), ("u8d_scale", C.c_float),
-                ("ndft_rule", C.c_int), ("sf_power", C.c_int)]
+def _dev(x):
+    """a device pointer: None / 0, an int, or anything with data_ptr() (a torch tensor)"""
+    if x is None:
+        return 0
+    return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
+
+
+def _hip_stream(stream):
+    """stream=None: torch's current stream when torch is loaded, else the default stream"""
+    if stream is not None:
+        return int(stream)
+    torch = sys.modules.get("torch")
+    return int(torch.cuda.current_stream().cuda_stream) if torch is not None and torch.cuda.is_available() else 0
+
+
+def device_count():
+    return int(lib().pirip_hip_device_count())
+
+
+def kernel_source_hash():
+    """pirip_hip_kernel_source_hash: 16 hex digits that name the kernel sources the library was built from (profiles/hbm_traffic.json
+    carries the hash its counters were taken on)."""
+    return lib().pirip_hip_kernel_source_hash().decode()
+
+
+def _mismatches(name):
+    m = C.c_uint64(0)
+    _chk(getattr(lib(), name)(C.byref(m)), name)
+    return int(m.value)
+
+
+def selftest_sqrt():
+    """Mismatches of the wave kernel's correctly rounded square roots against (float)sqrt((double)x) over x = 0 and every
+    float in [2^-96, FLT_MAX], counted on the device (pirip_hip_selftest_sqrt): (v_sqrt variant << 32) | rsq variant."""
+    return _mismatches("pirip_hip_selftest_sqrt")
+
+
+def selftest_div():
+    """Mismatches of the fused hand-over's x / 3 and x / 50 (pirip_hip_selftest_div) against the device's IEEE quotient over their measured
+    domains -- x / 3: every finite x >= 0, denormals included; x / 50: x = 0 and every float in [2^-125, FLT_MAX]:
+    (count for / 50 << 32) | count for / 3."""
+    return _mismatches("pirip_hip_selftest_div")
+
+
+def selftest_atan2(d_y, d_x, d_out, n):
+    """pirip_hip_selftest_atan2: the exact prologue's atan2f of n float pairs d_y, d_x into d_out (device pointers or tensors), on the
+    default stream; the caller synchronises."""
+    _chk(lib().pirip_hip_selftest_atan2(_dev(d_y), _dev(d_x), _dev(d_out), int(n)), "pirip_hip_selftest_atan2")
 
 
 def recalled(**overrides):
@@ -341,56 +430,100 @@ def recalled(**overrides):
 def launch_first_tail_block(nblocks, streams_per_cu, streams_per_block, cus):
     """pirip_hip_launch_first_tail_block (no device): the first workgroup of a wave-kernel launch of `nblocks` that starts at the raised
     priority; nblocks: none does."""
-    L = lib()
-    L.pirip_hip_launch_first_tail_block.argtypes = [C.c_int] * 4
-    first = int(L.pirip_hip_launch_first_tail_block(int(nblocks), int(streams_per_cu), int(streams_per_block), int(cus)))
+    first = int(lib().pirip_hip_launch_first_tail_block(int(nblocks), int(streams_per_cu), int(streams_per_block), int(cus)))
     if first < 0:
         _chk(first, "pirip_hip_launch_first_tail_block")
     return first
 
 
-class HipDemod:
+class _Handle:
+    """One object of the library: its C handle h (None once closed, or when create failed), the library L, and the object's life cycle.
+    A class names its C prefix (_c: pirip_hip_<section>, whose _destroy and _get_info are its) and, where it has one, its info structure."""
+    _c = None
+    _Info = None
+    L = h = None
+
+    def _create(self, name, *args):
+        """the create entry point `name`: args, then the handle out; reads self.info where the class has an info structure"""
+        self.L = lib()
+        h = C.c_void_p()
+        _chk(getattr(self.L, name)(*args, C.byref(h)), name)
+        self.h = h
+        if self._Info is not None:
+            self.info = self._Info()
+            self._call(self._c + "_get_info", C.byref(self.info))
+
+    def _ptr(self, name):
+        """the handle for a call of `name`: a closed object raises here, before C sees a NULL"""
+        if self.h is None:
+            raise PiripError(f"{name}: this {type(self).__name__} is closed")
+        return self.h
+
+    def _call(self, name, *args):
+        """name(h, *args), which returns a status (every measured call comes through here: one test, one C call, one compare)"""
+        if self.h is None:
+            self._ptr(name)
+        rc = getattr(self.L, name)(self.h, *args)
+        if rc != 0:
+            _chk(rc, name)
+
+    def _value(self, name, *args):
+        """name(h, *args), which returns a value"""
+        return getattr(self.L, name)(self._ptr(name), *args)
+
+    def _taps(self):
+        """the *_taps protocol: ask for the length, allocate, ask again"""
+        n = C.c_int(0)
+        self._call(self._c + "_taps", None, C.byref(n))
+        t = np.zeros(n.value, dtype=np.float32)
+        self._call(self._c + "_taps", t.ctypes.data, C.byref(n))
+        return t
+
+    def close(self):
+        h, self.h = self.h, None
+        if h is not None:
+            getattr(self.L, self._c + "_destroy")(h)
+
+    def __del__(self):
+        try:       # never raises: at interpreter shutdown the library or this module may be gone before the object
+            self.close()
+        except Exception:
+            pass
+
+
+def _ptr_of(obj, name):
+    """obj's handle for a call of `name`, NULL for no object"""
+    return None if obj is None else obj._ptr(name)
+
+
+class HipDemod(_Handle):
     """nstreams device-resident demodulators (pirip_hip_create; recalled=dict(field=value, ...): pirip_hip_create_recalled)."""
+    _c, _Info = "pirip_hip", FskInfo
 
     def __init__(self, Fs, Rs, M, P=8, Nsym=50, est_min=0, est_max=0, mask=0, in_format=IN_CU8_FSKDEMOD,
                  nstreams=1, device=-1, recalled=None):
-        self.L = lib()
         self.params = FskParams(Fs, Rs, M, P, Nsym, est_min, est_max, 1 if mask else 0, mask if mask else 100, in_format)
-        h = C.c_void_p()
         if recalled is None:
-            _chk(self.L.pirip_hip_create(C.byref(self.params), nstreams, device, C.byref(h)), "pirip_hip_create")
+            self._create("pirip_hip_create", C.byref(self.params), nstreams, device)
         else:
-            rc = globals()["recalled"](**recalled)
-            _chk(self.L.pirip_hip_create_recalled(C.byref(self.params), C.byref(rc), nstreams, device, C.byref(h)), "pirip_hip_create_recalled")
-        self.h = h
-        self.info = FskInfo()
-        _chk(self.L.pirip_hip_get_info(self.h, C.byref(self.info)), "pirip_hip_get_info")
+            self._create("pirip_hip_create_recalled", C.byref(self.params), C.byref(globals()["recalled"](**recalled)), nstreams, device)
         self.nstreams = nstreams
         self.M, self.Nsym, self.Nbits, self.N = M, Nsym, self.info.Nbits, self.info.N
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def kernel(self):
         """'wave' / 'block' (a specialised instance), 'general', or 'exact' (PIRIP_KERNEL=exact: every frame in the CPU algorithm's own
         operation order, the on-device cross-check) -- pirip_hip_get_kernel."""
-        self.L.pirip_hip_get_kernel.argtypes = [C.c_void_p]
-        k = self.L.pirip_hip_get_kernel(self.h)
+        k = self._value("pirip_hip_get_kernel")
         return "wave" if k == 2 else "block" if k == 3 else "exact" if k == 4 else "general"
 
     def kernel_name(self):
         """pirip_hip_get_kernel_name: the instance's template arguments / the general kernel's run-time shape."""
         buf = C.create_string_buffer(256)
-        self.L.pirip_hip_get_kernel_name.argtypes = [C.c_void_p, C.c_char_p, C.c_size_t]
-        _chk(self.L.pirip_hip_get_kernel_name(self.h, buf, 256), "pirip_hip_get_kernel_name")
+        self._call("pirip_hip_get_kernel_name", buf, 256)
         return buf.value.decode()
 
     def reset(self, stream=0):
-        _chk(self.L.pirip_hip_reset(self.h, stream), "pirip_hip_reset")
+        self._call("pirip_hip_reset", stream)
 
     def max_frames_for(self, nsamp):
         return nsamp // (2 * self.N - self.info.nin_max) + 2          # (the shortest frame: N - the nin step)
@@ -400,9 +533,8 @@ class HipDemod:
         """Raw device pointers (ints); enqueues on `stream`, does not synchronise."""
         if max_frames is None:
             max_frames = self.max_frames_for(nsamp)
-        _chk(self.L.pirip_hip_demod_batch(self.h, d_in, in_stride, nsamp, d_bits, bits_stride, d_filt, filt_stride,
-                                          d_stats, stats_stride, d_nframes, d_consumed, max_frames, stream),
-             "pirip_hip_demod_batch")
+        self._call("pirip_hip_demod_batch", d_in, in_stride, nsamp, d_bits, bits_stride, d_filt, filt_stride,
+                   d_stats, stats_stride, d_nframes, d_consumed, max_frames, stream)
 
     def demod_capture(self, d_in, nsamp, d_bits, d_filt=0, d_stats=0, max_frames=None, stream=0):
         """One long capture on the handle's stream slots (pirip_hip_demod_capture): raw device pointers; synchronises.
@@ -410,13 +542,12 @@ class HipDemod:
         if max_frames is None:
             max_frames = self.max_frames_for(nsamp)
         nf, cons, rep = C.c_int64(0), C.c_int64(0), CaptureReport()
-        _chk(self.L.pirip_hip_demod_capture(self.h, d_in, nsamp, d_bits, d_filt, d_stats, max_frames, C.byref(nf), C.byref(cons),
-                                            C.byref(rep), stream), "pirip_hip_demod_capture")
+        self._call("pirip_hip_demod_capture", d_in, nsamp, d_bits, d_filt, d_stats, max_frames, C.byref(nf), C.byref(cons), C.byref(rep),
+                   stream)
         return nf.value, cons.value, {k: getattr(rep, k) for k, _ in CaptureReport._fields_}
 
     def demod_host(self, buf, want_filt=True):
         """numpy buffer [n, 2] in the configured format -> dict (stream 0; uploads/downloads)."""
-        import numpy as np
         buf = np.ascontiguousarray(buf)
         nsamp = buf.shape[0]
         maxf = self.max_frames_for(nsamp)
@@ -425,168 +556,133 @@ class HipDemod:
         filt = np.zeros((maxf, self.M * self.Nsym), dtype=np.float32)
         st = np.zeros((maxf, STATS_PER_FRAME), dtype=np.float32)
         nf, cons = C.c_int64(0), C.c_int64(0)
-        _chk(self.L.pirip_hip_demod_host(self.h, buf.ctypes.data, nsamp, bits.ctypes.data,
-                                         filt.ctypes.data if want_filt else None, st.ctypes.data, maxf,
-                                         C.byref(nf), C.byref(cons)), "pirip_hip_demod_host")
+        self._call("pirip_hip_demod_host", buf.ctypes.data, nsamp, bits.ctypes.data, filt.ctypes.data if want_filt else None,
+                   st.ctypes.data, maxf, C.byref(nf), C.byref(cons))
         n = nf.value
         return {"nframes": n, "consumed": cons.value, "bits": bits[:n], "rx_filt": filt[:n] if want_filt else None,
                 "stats": st[:n]}
 
     def set_bit_packing(self, packed=True):
         """d_bits becomes ceil(Nbits/8) bytes per frame, MSB first (strides in packed bytes)."""
-        _chk(self.L.pirip_hip_set_bit_packing(self.h, 1 if packed else 0), "pirip_hip_set_bit_packing")
+        self._call("pirip_hip_set_bit_packing", 1 if packed else 0)
         self.packed = bool(packed)
 
     def set_exact_first_frame(self, enable=True):
         """pirip_hip_set_exact_first_frame: the prologue that demodulates a created stream's first frame in the CPU restatement's own
         operation order where P == Ts (default on); off: frame 0 comes from the handle's kernel like every other frame (A/B runs)."""
-        self.L.pirip_hip_set_exact_first_frame.argtypes = [C.c_void_p, C.c_int]
-        _chk(self.L.pirip_hip_set_exact_first_frame(self.h, 1 if enable else 0), "pirip_hip_set_exact_first_frame")
+        self._call("pirip_hip_set_exact_first_frame", 1 if enable else 0)
 
     def set_estimator_band_only(self, enable=True):
         """Opt-in: Sf is maintained only for the FFT bins the peak search can read (include/pirip_hip.h); outputs unchanged."""
-        _chk(self.L.pirip_hip_set_estimator_band_only(self.h, 1 if enable else 0), "pirip_hip_set_estimator_band_only")
+        self._call("pirip_hip_set_estimator_band_only", 1 if enable else 0)
 
     def set_launch_tail_first(self, enable=True):
         """pirip_hip_set_launch_tail_first: the workgroups of a wave-kernel launch's last residency start at a raised wave priority
         (default on); outputs unchanged."""
-        self.L.pirip_hip_set_launch_tail_first.argtypes = [C.c_void_p, C.c_int]
-        _chk(self.L.pirip_hip_set_launch_tail_first(self.h, 1 if enable else 0), "pirip_hip_set_launch_tail_first")
+        self._call("pirip_hip_set_launch_tail_first", 1 if enable else 0)
 
     def launch_resident_blocks(self):
         """pirip_hip_get_launch_resident_blocks: workgroups of the handle's wave instance that its device holds at once (0: another kernel)."""
-        self.L.pirip_hip_get_launch_resident_blocks.argtypes = [C.c_void_p]
-        return int(self.L.pirip_hip_get_launch_resident_blocks(self.h))
+        return int(self._value("pirip_hip_get_launch_resident_blocks"))
 
     def set_freq_est_limits(self, est_min, est_max):
         """fsk_set_freq_est_limits() on the live handle; returns the status code (PIRIP_OK = 0) instead of raising."""
-        return int(self.L.pirip_hip_set_freq_est_limits(self.h, int(est_min), int(est_max)))
+        return int(self._value("pirip_hip_set_freq_est_limits", int(est_min), int(est_max)))
 
     def set_burst_mode(self, enable=True):
-        _chk(self.L.pirip_hip_set_burst_mode(self.h, 1 if enable else 0), "pirip_hip_set_burst_mode")
+        self._call("pirip_hip_set_burst_mode", 1 if enable else 0)
 
     def enable_eye(self, enable=True):
         """MODEM_STATS.rx_eye: keep the eye traces of each stream's latest frame (moves the handle to the general kernel, resets state)."""
-        self.L.pirip_hip_enable_eye.argtypes = [C.c_void_p, C.c_int]
-        _chk(self.L.pirip_hip_enable_eye(self.h, 1 if enable else 0), "pirip_hip_enable_eye")
+        self._call("pirip_hip_enable_eye", 1 if enable else 0)
 
     def eye(self, s=0, normalise=True):
-        import numpy as np
         out = np.zeros((8, 160), dtype=np.float32)
         ntr, npt = C.c_int(0), C.c_int(0)
-        self.L.pirip_hip_get_eye.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-        _chk(self.L.pirip_hip_get_eye(self.h, s, 1 if normalise else 0, out.ctypes.data, C.byref(ntr), C.byref(npt)), "pirip_hip_get_eye")
+        self._call("pirip_hip_get_eye", s, 1 if normalise else 0, out.ctypes.data, C.byref(ntr), C.byref(npt))
         return out[:ntr.value, :npt.value].copy()
 
     def get_Sf(self, s=0):
-        import numpy as np
         out = np.zeros(self.info.Ndft, dtype=np.float32)
-        _chk(self.L.pirip_hip_get_Sf(self.h, s, out.ctypes.data), "pirip_hip_get_Sf")
+        self._call("pirip_hip_get_Sf", s, out.ctypes.data)
         return out
 
-
-def _taps(fn, h):
-    """the *_taps protocol: ask for the length, allocate, ask again"""
-    import numpy as np
-    n = C.c_int(0)
-    fn(h, None, C.byref(n))
-    t = np.zeros(n.value, dtype=np.float32)
-    fn(h, t.ctypes.data, C.byref(n))
-    return t
+    def stream_state(self, s=0):
+        """pirip_hip_get_stream_state: the StreamState of stream s after the last call. Synchronises."""
+        st = StreamState()
+        self._call("pirip_hip_get_stream_state", s, C.byref(st))
+        return st
 
 
-class HipDecim:
+class HipDecim(_Handle):
     """csdr convert_u8_f | fir_decimate_cc D | [convert_f_s16] as one device stage."""
+    _c = "pirip_hip_decim"
 
     def __init__(self, D, transition_bw=0.05, out_s16=True, device=-1):
-        self.L = lib()
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_decim_create(D, transition_bw, 1 if out_s16 else 0, device, C.byref(h)),
-             "pirip_hip_decim_create")
-        self.h, self.D, self.out_s16 = h, D, out_s16
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_decim_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self._create("pirip_hip_decim_create", D, transition_bw, 1 if out_s16 else 0, device)
+        self.D, self.out_s16 = D, out_s16
 
     def taps(self):
-        return _taps(self.L.pirip_hip_decim_taps, self.h)
+        return self._taps()
 
     def nout(self, n_in):
-        return int(self.L.pirip_hip_decim_nout(self.h, n_in))
+        return int(self._value("pirip_hip_decim_nout", n_in))
 
     def set_arith(self, mode):
         """0 exact (default: the scalar csdr loop bit for bit), 1 fused accumulate, 2 affine map pulled out of the sum (opt-in measurements)"""
-        _chk(self.L.pirip_hip_decim_set_arith(self.h, int(mode)), "pirip_hip_decim_set_arith")
+        self._call("pirip_hip_decim_set_arith", int(mode))
+
+    def get_arith(self):
+        """pirip_hip_decim_get_arith: the tap-loop arithmetic in use, as set_arith's mode (or PIRIP_DECIM_FMA at create)"""
+        return int(self._value("pirip_hip_decim_get_arith"))
 
     def batch(self, d_in, in_stride, n_in, d_out, out_stride, nstreams, stream=0):
-        _chk(self.L.pirip_hip_decim_batch(self.h, d_in, in_stride, n_in, d_out, out_stride, nstreams, stream),
-             "pirip_hip_decim_batch")
+        self._call("pirip_hip_decim_batch", d_in, in_stride, n_in, d_out, out_stride, nstreams, stream)
 
 
-class HipChan:
+class HipChan(_Handle):
     """Channelizer (include/pirip_hip.h section H): channel c = csdr shift_addition_cc (-offsets[c]/Fs) | fir_decimate_cc D of capture
     inputs[c] (all 0 when inputs is None), for every channel of every capture in one pass over the u8 IQ. out_s16: interleaved s16 IQ out
     (convert_f_s16), else complex float."""
+    _c, _Info = "pirip_hip_chan", ChanInfo
 
     def __init__(self, Fs, D, offsets, inputs=None, transition_bw=0.05, out_s16=False, device=-1):
-        import numpy as np
-        self.L = lib()
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
         inp = np.zeros(off.size, dtype=np.int32) if inputs is None else np.ascontiguousarray(inputs, dtype=np.int32).reshape(-1)
         if inp.size != off.size:
             raise ValueError("inputs and offsets must have the same length")
         ninputs = int(inp.max()) + 1 if inp.size else 1
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_chan_create(int(Fs), int(D), transition_bw, 1 if out_s16 else 0, ninputs, int(off.size),
-                                          inp.ctypes.data if inp.size else None, off.ctypes.data if off.size else None, device, C.byref(h)),
-             "pirip_hip_chan_create")
-        self.h = h
-        self.info = ChanInfo()
-        _chk(self.L.pirip_hip_chan_get_info(self.h, C.byref(self.info)), "pirip_hip_chan_get_info")
+        self._create("pirip_hip_chan_create", int(Fs), int(D), transition_bw, 1 if out_s16 else 0, ninputs, int(off.size),
+                     inp.ctypes.data if inp.size else None, off.ctypes.data if off.size else None, device)
         self.Fs, self.D, self.out_s16 = int(Fs), int(D), bool(out_s16)
         self.offsets, self.inputs = off.copy(), inp.copy()
         self.ninputs, self.nchan, self.Lp = self.info.ninputs, self.info.nchan, self.info.ntaps_padded
         self.bytes_per_sample = 4 if out_s16 else 8
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_chan_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
     def taps(self):
         """the prototype low-pass h (section B's taps for the same D / transition_bw, unpadded)"""
-        return _taps(self.L.pirip_hip_chan_taps, self.h)
+        return self._taps()
 
     def nout(self, n_in):
-        return int(self.L.pirip_hip_chan_nout(self.h, int(n_in)))
+        return int(self._value("pirip_hip_chan_nout", int(n_in)))
 
     def batch(self, d_in, in_stride, n_in, d_out, out_stride, t0=0, stream=0):
         """capture i at d_in + i * in_stride (n_in u8 IQ samples, the first at absolute index t0) -> channel c at d_out + c * out_stride
         (nout(n_in) samples); raw device pointers, enqueued on `stream`, does not synchronise"""
-        _chk(self.L.pirip_hip_chan_batch(self.h, d_in, in_stride, int(n_in), int(t0), d_out, out_stride, stream), "pirip_hip_chan_batch")
+        self._call("pirip_hip_chan_batch", d_in, in_stride, int(n_in), int(t0), d_out, out_stride, stream)
 
 
 TX_CARRIER_OFF = 0xFF
 
 
-class HipTx:
+class HipTx(_Handle):
     """nstreams FSK_LDPC transmitters (include/pirip_hip.h section I): records of rpitx_fsk --code's stdin protocol -> channel symbols ->
     continuous-phase M-FSK IQ. f1: one first-tone frequency for all streams or one per stream (Hz); lead / gap: carrier-off symbols in
     front of a stream's first record and for each of its `2` records (scalars or one per stream)."""
+    _c, _Info = "pirip_hip_tx", TxInfo
 
     def __init__(self, code_path, Fs, Rs, M, nstreams=1, f1=None, shift=None, lead=0, gap=0, device=-1):
-        self.L = lib()
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_tx_create(code_path.encode(), int(Fs), int(Rs), int(M), int(nstreams), device, C.byref(h)), "pirip_hip_tx_create")
-        self.h = h
-        self.info = TxInfo()
-        _chk(self.L.pirip_hip_tx_get_info(self.h, C.byref(self.info)), "pirip_hip_tx_get_info")
+        self._create("pirip_hip_tx_create", code_path.encode(), int(Fs), int(Rs), int(M), int(nstreams), device)
         self.Fs, self.Rs, self.M, self.Ts, self.nstreams = int(Fs), int(Rs), int(M), self.info.Ts, int(nstreams)
         self.k, self.data_bytes, self.record_bytes = self.info.k, self.info.data_bytes, 1 + self.info.data_bytes
         self.bits_per_frame, self.frame_syms, self.preamble_syms = self.info.bits_per_frame, self.info.frame_syms, self.info.preamble_syms
@@ -595,15 +691,7 @@ class HipTx:
             self.set_tones(f1, shift if shift is not None else Rs)
         self.set_gaps(lead, gap)
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_tx_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
     def _per_stream(self, v):
-        import numpy as np
         a = np.ascontiguousarray(v, dtype=np.int32).reshape(-1)
         if a.size == 1:
             a = np.full(self.nstreams, int(a[0]), dtype=np.int32)
@@ -613,59 +701,56 @@ class HipTx:
 
     def set_tones(self, f1, shift):
         a = self._per_stream(f1)
-        _chk(self.L.pirip_hip_tx_set_tones(self.h, a.ctypes.data, int(shift)), "pirip_hip_tx_set_tones")
+        self._call("pirip_hip_tx_set_tones", a.ctypes.data, int(shift))
 
     def set_gaps(self, lead=0, gap=0):
         a, b = self._per_stream(lead), self._per_stream(gap)
-        _chk(self.L.pirip_hip_tx_set_gaps(self.h, a.ctypes.data, b.ctypes.data), "pirip_hip_tx_set_gaps")
+        self._call("pirip_hip_tx_set_gaps", a.ctypes.data, b.ctypes.data)
 
     def reset(self, stream=0):
-        _chk(self.L.pirip_hip_tx_reset(self.h, stream), "pirip_hip_tx_reset")
+        self._call("pirip_hip_tx_reset", stream)
 
     def max_syms(self, max_rec):
-        return int(self.L.pirip_hip_tx_max_syms(self.h, int(max_rec)))
+        return int(self._value("pirip_hip_tx_max_syms", int(max_rec)))
 
     def frame(self, d_records, rec_stride, max_rec, d_syms, sym_stride, max_syms, d_nrec=0, d_nsym=0, d_bits=0, bits_stride=0, stream=0):
         """records -> symbol rows (and the framer's bits); raw device pointers, enqueued on `stream`, does not synchronise"""
-        _chk(self.L.pirip_hip_tx_frame(self.h, d_records, rec_stride, d_nrec, int(max_rec), d_syms, sym_stride, int(max_syms), d_nsym,
-                                       d_bits, bits_stride, stream), "pirip_hip_tx_frame")
+        self._call("pirip_hip_tx_frame", d_records, rec_stride, d_nrec, int(max_rec), d_syms, sym_stride, int(max_syms), d_nsym,
+                   d_bits, bits_stride, stream)
 
     def modulate(self, d_syms, sym_stride, nsym, d_out, out_stride, out_format=IN_CU8_FSKDEMOD, d_nsym=0, amp=32.0, sigma=0.0, seed=1,
                  stream=0):
         """nsym symbol times (nsym * Ts samples) per stream -> IQ rows; continues where the previous call stopped"""
-        _chk(self.L.pirip_hip_tx_modulate(self.h, d_syms, sym_stride, d_nsym, int(nsym), out_format, d_out, out_stride, amp, sigma, seed,
-                                          stream), "pirip_hip_tx_modulate")
+        self._call("pirip_hip_tx_modulate", d_syms, sym_stride, d_nsym, int(nsym), out_format, d_out, out_stride, amp, sigma, seed, stream)
 
     def repeat_max_records(self, ncalls):
-        return int(self.L.pirip_hip_tx_repeat_max_records(self.h, int(ncalls)))
+        return int(self._value("pirip_hip_tx_repeat_max_records", int(ncalls)))
 
     def repeat_records(self, d_status, status_stride, d_payload, payload_stride, ncalls, source_byte, d_records, rec_stride, max_rec,
                        d_ncalls=0, d_nrec=0, stream=0):
         """receiver records (HipLdpc.chain_batch's status / payload rows) -> Tx records by frame_repeater's state machine, on the device;
         a burst still being received waits in the handle for the call in which it ends"""
-        _chk(self.L.pirip_hip_tx_repeat_records(self.h, d_status, status_stride, d_payload, payload_stride, d_ncalls, int(ncalls),
-                                                int(source_byte), d_records, rec_stride, int(max_rec), d_nrec, stream),
-             "pirip_hip_tx_repeat_records")
+        self._call("pirip_hip_tx_repeat_records", d_status, status_stride, d_payload, payload_stride, d_ncalls, int(ncalls),
+                   int(source_byte), d_records, rec_stride, int(max_rec), d_nrec, stream)
 
     def records_to_iq(self, d_records, rec_stride, max_rec, nsym, d_out, out_stride, out_format=IN_CU8_FSKDEMOD, d_nrec=0, d_nsym=0,
                       amp=32.0, sigma=0.0, seed=1, stream=0):
-        _chk(self.L.pirip_hip_tx_records_to_iq(self.h, d_records, rec_stride, d_nrec, int(max_rec), int(nsym), out_format, d_out, out_stride,
-                                               amp, sigma, seed, d_nsym, stream), "pirip_hip_tx_records_to_iq")
+        self._call("pirip_hip_tx_records_to_iq", d_records, rec_stride, d_nrec, int(max_rec), int(nsym), out_format, d_out, out_stride,
+                   amp, sigma, seed, d_nsym, stream)
 
 
 MUX_FIR, MUX_LINEAR = 0, 1
 
 
-class HipMux:
+class HipMux(_Handle):
     """Multiplexer (include/pirip_hip.h section J), the channelizer's mirror image: channel c (complex float at Fs / D) is interpolated
     by D, moved to offsets[c] Hz, scaled by gains[c] (all 1 when gains is None) and added to wideband stream outputs[c] (all 0 when
     outputs is None; noutputs: more streams than the largest index, the others empty). kind: MUX_FIR (D times section B's low-pass) or
     MUX_LINEAR; out_format: IN_CU8_CSDR (u8 IQ) or IN_CF32."""
+    _c, _Info = "pirip_hip_mux", MuxInfo
 
     def __init__(self, Fs, D, offsets, outputs=None, gains=None, kind=MUX_FIR, transition_bw=0.05, out_format=IN_CU8_CSDR, device=-1,
                  noutputs=None):
-        import numpy as np
-        self.L = lib()
         off = np.ascontiguousarray(offsets, dtype=np.int32).reshape(-1)
         outp = np.zeros(off.size, dtype=np.int32) if outputs is None else np.ascontiguousarray(outputs, dtype=np.int32).reshape(-1)
         g = None if gains is None else np.ascontiguousarray(gains, dtype=np.float32).reshape(-1)
@@ -673,13 +758,9 @@ class HipMux:
             raise ValueError("outputs, gains and offsets must have the same length")
         if noutputs is None:
             noutputs = int(outp.max()) + 1 if outp.size else 1
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_mux_create(int(Fs), int(D), int(kind), transition_bw, int(out_format), int(noutputs), int(off.size),
-                                         outp.ctypes.data if outp.size else None, off.ctypes.data if off.size else None,
-                                         g.ctypes.data if g is not None and g.size else None, device, C.byref(h)), "pirip_hip_mux_create")
-        self.h = h
-        self.info = MuxInfo()
-        _chk(self.L.pirip_hip_mux_get_info(self.h, C.byref(self.info)), "pirip_hip_mux_get_info")
+        self._create("pirip_hip_mux_create", int(Fs), int(D), int(kind), transition_bw, int(out_format), int(noutputs), int(off.size),
+                     outp.ctypes.data if outp.size else None, off.ctypes.data if off.size else None,
+                     g.ctypes.data if g is not None and g.size else None, device)
         self.Fs, self.D, self.kind, self.out_format = int(Fs), int(D), int(kind), int(out_format)
         self.offsets, self.outputs = off.copy(), outp.copy()
         self.gains = np.ones(off.size, dtype=np.float32) if g is None else g.copy()
@@ -687,119 +768,72 @@ class HipMux:
         self.nchan, self.noutputs = self.info.nchan, self.info.noutputs
         self.bytes_per_sample = 8 if out_format == IN_CF32 else 2
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_mux_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
     def taps(self):
         """the prototype h (ntaps, unpadded)"""
-        return _taps(self.L.pirip_hip_mux_taps, self.h)
+        return self._taps()
 
     def nout(self, n_in):
-        return int(self.L.pirip_hip_mux_nout(self.h, int(n_in)))
+        return int(self._value("pirip_hip_mux_nout", int(n_in)))
 
     def batch(self, d_in, in_stride, n_in, d_out, out_stride, m0=0, stream=0):
         """channel c at d_in + c * in_stride (n_in complex floats, the first at absolute index m0) -> output i at d_out + i * out_stride
         (nout(n_in) samples, the first at absolute index (m0 + Q - 1) D); raw device pointers, enqueued on `stream`, does not synchronise"""
-        _chk(self.L.pirip_hip_mux_batch(self.h, d_in, in_stride, int(n_in), int(m0), d_out, out_stride, stream), "pirip_hip_mux_batch")
+        self._call("pirip_hip_mux_batch", d_in, in_stride, int(n_in), int(m0), d_out, out_stride, stream)
 
 
-class HipTxStream:
+class HipTxStream(_Handle):
     """Streaming transmitter (include/pirip_hip.h section K): every channel of HipTx `tx` has a symbol queue on the device, and each
     process() turns the next S = block / (D Ts) symbols of every queue into `block` wideband samples per output of HipMux `mux`, with no
     modem-rate IQ in between. queue_syms: each queue's capacity in symbols (>= S). Both handles must outlive the stream."""
+    _c, _Info = "pirip_hip_txs", TxsInfo
 
     def __init__(self, tx, mux, block, queue_syms):
-        self.L = lib()
         self.tx, self.mux = tx, mux
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_txs_create(tx.h, mux.h, int(block), int(queue_syms), C.byref(h)), "pirip_hip_txs_create")
-        self.h = h
-        self.info = TxsInfo()
-        _chk(self.L.pirip_hip_txs_get_info(self.h, C.byref(self.info)), "pirip_hip_txs_get_info")
+        self._create("pirip_hip_txs_create", tx._ptr("pirip_hip_txs_create"), mux._ptr("pirip_hip_txs_create"), int(block), int(queue_syms))
         self.block, self.queue_syms, self.S, self.H = self.info.block, self.info.queue_syms, self.info.S, self.info.H
         self.nchan, self.noutputs, self.bytes_per_sample = self.info.nchan, self.info.noutputs, mux.bytes_per_sample
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_txs_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def send(self, d_records, rec_stride, max_rec, d_nrec=0, d_taken=0, stream=0):
         """offer every channel its records (HipTx.frame's format); per channel all or nothing, d_taken[s] = records taken. Raw device
         pointers, enqueued on `stream`."""
-        _chk(self.L.pirip_hip_txs_send(self.h, d_records, rec_stride, d_nrec, int(max_rec), d_taken, stream), "pirip_hip_txs_send")
+        self._call("pirip_hip_txs_send", d_records, rec_stride, d_nrec, int(max_rec), d_taken, stream)
 
     def process(self, d_out, out_stride, d_sent=0, stream=0):
         """one block: output i gets `block` samples at d_out + i * out_stride; d_sent[s] = symbols dequeued. Does not synchronise."""
-        _chk(self.L.pirip_hip_txs_process(self.h, d_out, out_stride, d_sent, stream), "pirip_hip_txs_process")
+        self._call("pirip_hip_txs_process", d_out, out_stride, d_sent, stream)
 
     def counters(self):
         """dict of int64[nchan]: queued, sent, underrun, refused -- synchronises."""
-        import numpy as np
         out = {k: np.zeros(self.nchan, dtype=np.int64) for k in ("queued", "sent", "underrun", "refused")}
-        _chk(self.L.pirip_hip_txs_get_counters(self.h, *(out[k].ctypes.data for k in ("queued", "sent", "underrun", "refused"))),
-             "pirip_hip_txs_get_counters")
+        self._call("pirip_hip_txs_get_counters", *(a.ctypes.data for a in out.values()))
         return out
 
     def reset(self, stream=0):
-        _chk(self.L.pirip_hip_txs_reset(self.h, stream), "pirip_hip_txs_reset")
+        self._call("pirip_hip_txs_reset", stream)
 
 
 def testframe_payload(k):
     """The --testframes payload of a code with k data bits, packed MSB first: uint8[k / 8] (pirip_hip_tbits_testframe_payload; no device)."""
-    import numpy as np
     out = np.zeros(max(int(k) // 8, 1), dtype=np.uint8)
     _chk(lib().pirip_hip_tbits_testframe_payload(int(k), out.ctypes.data), "pirip_hip_tbits_testframe_payload")
     return out
 
 
-def _dev(x):
-    """a device pointer: None / 0, an int, or anything with data_ptr() (a torch tensor)"""
-    if x is None:
-        return 0
-    return int(x.data_ptr()) if hasattr(x, "data_ptr") else int(x)
-
-
-def _hip_stream(stream):
-    """stream=None: torch's current stream when torch is loaded, else the default stream"""
-    if stream is not None:
-        return int(stream)
-    import sys
-    torch = sys.modules.get("torch")
-    return int(torch.cuda.current_stream().cuda_stream) if torch is not None and torch.cuda.is_available() else 0
-
-
-class HipTestBits:
+class HipTestBits(_Handle):
     """Test-frame counter (include/pirip_hip.h section L): fsk_put_test_bits [-f framesize] [-t valid_thresh] for nstreams streams, counted
     on the device. frame: None for the tool's own frame, else framesize values 0 / 1. push() takes the demodulator's bit rows,
     push_records() the FSK_LDPC receiver's records (rtl_fsk --testframes' ecdd, tallied)."""
+    _c = "pirip_hip_tbits"
 
     def __init__(self, framesize=100, valid_thresh=0.1, frame=None, nstreams=1, device=-1):
-        import numpy as np
-        self.L = lib()
         fb = None
         if frame is not None:
             fb = np.ascontiguousarray(frame, dtype=np.uint8).reshape(-1)
             if fb.size != framesize:
                 raise ValueError("frame must hold framesize bits")
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_tbits_create(int(framesize), float(valid_thresh), None if fb is None else fb.ctypes.data, int(nstreams), device,
-                                           C.byref(h)), "pirip_hip_tbits_create")
-        self.h = h
+        self._create("pirip_hip_tbits_create", int(framesize), float(valid_thresh), None if fb is None else fb.ctypes.data, int(nstreams),
+                     device)
         self.framesize, self.valid_thresh, self.nstreams, self.data_bytes = int(framesize), float(valid_thresh), int(nstreams), 0
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_tbits_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def push(self, bits, nframes=None, row_bits=None, packed=False, stream=None, max_frames=None, bits_stride=None):
         """bits: a uint8 tensor [nstreams, max_frames, row bytes] (the last two dimensions contiguous) or a raw device pointer with
@@ -820,16 +854,15 @@ class HipTestBits:
             bits_stride = int(bits.stride(0)) if bits_stride is None else int(bits_stride)
         elif max_frames is None or bits_stride is None or row_bits is None:
             raise ValueError("a raw pointer needs row_bits, max_frames and bits_stride")
-        _chk(self.L.pirip_hip_tbits_push(self.h, _dev(bits), int(bits_stride), int(row_bits), 1 if packed else 0, _dev(nframes),
-                                         int(max_frames), _hip_stream(stream)), "pirip_hip_tbits_push")
+        self._call("pirip_hip_tbits_push", _dev(bits), int(bits_stride), int(row_bits), 1 if packed else 0, _dev(nframes), int(max_frames),
+                   _hip_stream(stream))
 
     def set_payload(self, data_bytes, payload=None):
         """what push_records compares with: data_bytes bytes, None = testframe_payload(8 * data_bytes)"""
-        import numpy as np
         p = None if payload is None else np.ascontiguousarray(payload, dtype=np.uint8).reshape(-1)
         if p is not None and p.size != data_bytes:
             raise ValueError("payload must hold data_bytes bytes")
-        _chk(self.L.pirip_hip_tbits_set_payload(self.h, int(data_bytes), None if p is None else p.ctypes.data), "pirip_hip_tbits_set_payload")
+        self._call("pirip_hip_tbits_set_payload", int(data_bytes), None if p is None else p.ctypes.data)
         self.data_bytes = int(data_bytes)
 
     def push_records(self, status, payload, info, ncalls=None, max_calls=None, status_stride=None, payload_stride=None, info_stride=None,
@@ -844,65 +877,82 @@ class HipTestBits:
             info_stride = int(info.stride(0)) if info_stride is None else int(info_stride)
         elif None in (max_calls, status_stride, payload_stride, info_stride):
             raise ValueError("raw pointers need max_calls and the three strides")
-        _chk(self.L.pirip_hip_tbits_push_records(self.h, _dev(status), status_stride, _dev(payload), payload_stride, _dev(info), info_stride,
-                                                 _dev(ncalls), int(max_calls), _hip_stream(stream)), "pirip_hip_tbits_push_records")
+        self._call("pirip_hip_tbits_push_records", _dev(status), status_stride, _dev(payload), payload_stride, _dev(info), info_stride,
+                   _dev(ncalls), int(max_calls), _hip_stream(stream))
 
-    def _read(self, fn, names, what):
-        import numpy as np
+    def _read(self, name, names):
         out = {k: np.zeros(self.nstreams, dtype=np.int64) for k in names}
-        _chk(fn(self.h, *(out[k].ctypes.data for k in names)), what)
+        self._call(name, *(out[k].ctypes.data for k in names))
         return out
 
     def counters(self):
         """dict of int64[nstreams]: packets, bits, errors (fsk_put_test_bits' packetcnt, bitcnt, biterr), pushed -- synchronises."""
-        return self._read(self.L.pirip_hip_tbits_get_counters, ("packets", "bits", "errors", "pushed"), "pirip_hip_tbits_get_counters")
+        return self._read("pirip_hip_tbits_get_counters", ("packets", "bits", "errors", "pushed"))
 
     def counters_device(self):
         """device pointer of the int64 [nstreams][4] counters {packets, bits, errors, pushed}"""
         p = C.c_void_p()
-        _chk(self.L.pirip_hip_tbits_counters_device(self.h, C.byref(p)), "pirip_hip_tbits_counters_device")
+        self._call("pirip_hip_tbits_counters_device", C.byref(p))
         return int(p.value)
 
     def record_counters(self):
         """dict of int64[nstreams]: frames (decoded), bits (payload bits compared), errors, frames_in_error, crc_ok -- synchronises."""
-        return self._read(self.L.pirip_hip_tbits_get_record_counters, ("frames", "bits", "errors", "frames_in_error", "crc_ok"),
-                          "pirip_hip_tbits_get_record_counters")
+        return self._read("pirip_hip_tbits_get_record_counters", ("frames", "bits", "errors", "frames_in_error", "crc_ok"))
 
     def reset(self, stream=None):
-        _chk(self.L.pirip_hip_tbits_reset(self.h, _hip_stream(stream)), "pirip_hip_tbits_reset")
+        self._call("pirip_hip_tbits_reset", _hip_stream(stream))
 
 
-class HipRepeater:
+class _Terminal(_Handle):
+    """What the repeater and the ping terminal share: a receiver's block in, a transmitter stream's block out, the C names apart."""
+
+    def process(self, out, out_stride, stream=None):
+        """the block at rx.input() -> one block per output (needs rx)"""
+        self._call(self._c + "_process", _dev(out), int(out_stride), _hip_stream(stream))
+
+    def push(self, d_in, in_stride, out, out_stride, stream=None):
+        """process() after copying the block from d_in (rows in_stride bytes apart) into rx's input"""
+        self._call(self._c + "_push", _dev(d_in), int(in_stride), _dev(out), int(out_stride), _hip_stream(stream))
+
+    def _records(self, rows):
+        """<prefix>_records: a device pointer and a stride in elements for each of `rows`, then the pointer of nframes"""
+        p = [C.c_void_p() for _ in range(len(rows) + 1)]
+        st = [C.c_size_t(0) for _ in rows]
+        self._call(self._c + "_records", *(C.byref(x) for pair in zip(p, st) for x in pair), C.byref(p[-1]))
+        out = {"nframes": int(p[-1].value or 0)}
+        for k, ptr, stride in zip(rows, p, st):
+            out[k], out[k + "_stride"] = int(ptr.value or 0), int(stride.value)
+        return out
+
+    def offered(self):
+        """(device pointer of the records offered in the last call, bytes per channel row, device pointer of the int32 [nchan] counts)"""
+        p, n, st = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
+        self._call(self._c + "_offered", C.byref(p), C.byref(st), C.byref(n))
+        return int(p.value), int(st.value), int(n.value)
+
+    def reset(self, stream=None):
+        self._call(self._c + "_reset", _hip_stream(stream))
+
+
+class HipRepeater(_Terminal):
     """Streaming repeater (include/pirip_hip.h section M): one call per block from received FSK_LDPC records -- or, with a HipRx `rx`
     created with an ldpc, from wideband IQ -- to the repeated wideband IQ of HipTxStream `txs` (created on HipTx `tx`). route[c]: the
     transmit channel of receive channel c, negative = not repeated; source: byte 0 of every repeated frame; filter: None, or the byte 0
     of frames that are not repeated (the repeater's own); holdoff: calls a finished burst waits; max_burst: frames held per burst;
     pending: records of each transmit channel's pending ring (default: two bursts). The handles must outlive the repeater; pointer
     arguments take torch tensors or raw device pointers, streams default to torch's current stream."""
+    _c, _Info = "pirip_hip_rpt", RptInfo
 
     def __init__(self, tx, txs, route, source, filter=None, holdoff=0, max_burst=100, pending=None, rx=None):
-        import numpy as np
-        self.L = lib()
         self.rx, self.tx, self.txs = rx, tx, txs
         rt = np.ascontiguousarray(route, dtype=np.int32).reshape(-1)
         if pending is None:
             pending = 2 * (int(max_burst) + 1)
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_rpt_create(rx.h if rx is not None else None, tx.h, txs.h, int(rt.size), rt.ctypes.data, int(source),
-                                         -1 if filter is None else int(filter), int(holdoff), int(max_burst), int(pending), C.byref(h)),
-             "pirip_hip_rpt_create")
-        self.h = h
-        self.info = RptInfo()
-        _chk(self.L.pirip_hip_rpt_get_info(self.h, C.byref(self.info)), "pirip_hip_rpt_get_info")
+        name = "pirip_hip_rpt_create"
+        self._create(name, _ptr_of(rx, name), tx._ptr(name), txs._ptr(name), int(rt.size), rt.ctypes.data, int(source),
+                     -1 if filter is None else int(filter), int(holdoff), int(max_burst), int(pending))
         self.nrx, self.nchan, self.pending, self.rx_rows = self.info.nrx, self.info.nchan, self.info.pending_records, self.info.rx_rows
         self.data_bytes = tx.data_bytes
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_rpt_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def push_records(self, status, payload, out, out_stride, ncalls=None, max_calls=None, status_stride=None, payload_stride=None, stream=None):
         """status uint8 [nrx, max_calls], payload uint8 [nrx, max_calls, data_bytes] (tensors, per-channel rows contiguous; or raw
@@ -913,45 +963,22 @@ class HipRepeater:
             payload_stride = int(payload.stride(0)) if payload_stride is None else int(payload_stride)
         elif None in (max_calls, status_stride, payload_stride):
             raise ValueError("raw pointers need max_calls and the two strides")
-        _chk(self.L.pirip_hip_rpt_push_records(self.h, _dev(status), status_stride, _dev(payload), payload_stride, _dev(ncalls), int(max_calls),
-                                               _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_rpt_push_records")
-
-    def process(self, out, out_stride, stream=None):
-        """the block at rx.input() -> one block per output (needs rx)"""
-        _chk(self.L.pirip_hip_rpt_process(self.h, _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_rpt_process")
-
-    def push(self, d_in, in_stride, out, out_stride, stream=None):
-        """process() after copying the block from d_in (rows in_stride bytes apart) into rx's input"""
-        _chk(self.L.pirip_hip_rpt_push(self.h, _dev(d_in), int(in_stride), _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_rpt_push")
+        self._call("pirip_hip_rpt_push_records", _dev(status), status_stride, _dev(payload), payload_stride, _dev(ncalls), int(max_calls),
+                   _dev(out), int(out_stride), _hip_stream(stream))
 
     def records(self):
         """dict of the last call's received records: device pointers status, payload, info, nframes and the strides in elements"""
-        p = [C.c_void_p() for _ in range(4)]
-        st = [C.c_size_t(0) for _ in range(3)]
-        _chk(self.L.pirip_hip_rpt_records(self.h, C.byref(p[0]), C.byref(st[0]), C.byref(p[1]), C.byref(st[1]), C.byref(p[2]), C.byref(st[2]),
-                                          C.byref(p[3])), "pirip_hip_rpt_records")
-        return dict(status=int(p[0].value or 0), status_stride=int(st[0].value), payload=int(p[1].value or 0), payload_stride=int(st[1].value),
-                    info=int(p[2].value or 0), info_stride=int(st[2].value), nframes=int(p[3].value or 0))
-
-    def offered(self):
-        """(device pointer of the records offered in the last call, bytes per channel row, device pointer of the int32 [nchan] counts)"""
-        p, n, st = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
-        _chk(self.L.pirip_hip_rpt_offered(self.h, C.byref(p), C.byref(st), C.byref(n)), "pirip_hip_rpt_offered")
-        return int(p.value), int(st.value), int(n.value)
+        return self._records(("status", "payload", "info"))
 
     def counters(self):
         """dict of int64 arrays -- [nrx]: bursts_in, frames_in, filtered, unrouted; [nchan]: bursts_out, pending, dropped. Synchronises."""
-        import numpy as np
         names = ("bursts_in", "frames_in", "filtered", "unrouted", "bursts_out", "pending", "dropped")
         out = {k: np.zeros(self.nrx if i < 4 else self.nchan, dtype=np.int64) for i, k in enumerate(names)}
-        _chk(self.L.pirip_hip_rpt_get_counters(self.h, *(out[k].ctypes.data for k in names)), "pirip_hip_rpt_get_counters")
+        self._call("pirip_hip_rpt_get_counters", *(out[k].ctypes.data for k in names))
         return out
 
-    def reset(self, stream=None):
-        _chk(self.L.pirip_hip_rpt_reset(self.h, _hip_stream(stream)), "pirip_hip_rpt_reset")
 
-
-class HipPing:
+class HipPing(_Terminal):
     """Ping terminal (include/pirip_hip.h section N): per call the received FSK_LDPC records -- the caller's, or with a HipRx `rx` created
     with an ldpc those of the wideband block -- go through the filter into a log ring per receive channel, and on a schedule counted in
     calls a burst of `frames` test frames (source in byte 0, with seq the frame's number in byte 1) goes out through HipTxStream `txs`
@@ -959,14 +986,13 @@ class HipPing:
     per transmit channel (None: 0); period: calls between bursts; max_bursts: per channel, 0 = no limit; log_entries: entries of each
     ring; nin0: what the first demodulator call consumes (taken from rx where given). The handles must outlive the terminal; pointer
     arguments take torch tensors or raw device pointers, streams default to torch's current stream."""
+    _c, _Info = "pirip_hip_ping", PingInfo
 
     RX_COUNTERS = ("frames", "filtered", "decoded", "crc_fail", "bit_errors", "lost")
     TX_COUNTERS = ("bursts_sent", "frames_sent", "skipped")
 
     def __init__(self, rx=None, tx=None, txs=None, nrx=None, source=1, filter=None, frames=3, seq=False, period=1, first_call=None, max_bursts=0,
                  log_entries=256, nin0=0):
-        import numpy as np
-        self.L = lib()
         self.rx, self.tx, self.txs = rx, tx, txs
         if nrx is None:
             nrx = rx.nstreams if rx is not None else 0
@@ -975,22 +1001,11 @@ class HipPing:
             raise ValueError("first_call: one entry per transmit channel")
         cfg = PingConfig(int(nrx), int(source), -1 if filter is None else int(filter), int(frames), 1 if seq else 0, int(period),
                          None if fc is None else fc.ctypes.data_as(C.POINTER(C.c_int32)), int(max_bursts), int(log_entries), int(nin0))
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_ping_create(rx.h if rx is not None else None, tx.h if tx is not None else None,
-                                          txs.h if txs is not None else None, C.byref(cfg), C.byref(h)), "pirip_hip_ping_create")
-        self.h = h
-        self.info = PingInfo()
-        _chk(self.L.pirip_hip_ping_get_info(self.h, C.byref(self.info)), "pirip_hip_ping_get_info")
+        name = "pirip_hip_ping_create"
+        self._create(name, _ptr_of(rx, name), _ptr_of(tx, name), _ptr_of(txs, name), C.byref(cfg))
         i = self.info
         self.nrx, self.nchan, self.rx_rows, self.data_bytes, self.log_entries, self.nin0 = i.nrx, i.nchan, i.rx_rows, i.data_bytes, i.log_entries, i.nin0
         self.frames = i.frames_per_burst
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_ping_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def push_records(self, status, payload, info, stats, out=None, out_stride=0, ncalls=None, max_calls=None, status_stride=None,
                      payload_stride=None, info_stride=None, stats_stride=None, stream=None):
@@ -1005,59 +1020,40 @@ class HipPing:
             stats_stride = int(stats.stride(0)) if stats_stride is None else int(stats_stride)
         elif None in (max_calls, status_stride, payload_stride, info_stride, stats_stride):
             raise ValueError("raw pointers need max_calls and the four strides")
-        _chk(self.L.pirip_hip_ping_push_records(self.h, _dev(status), status_stride, _dev(payload), payload_stride, _dev(info), info_stride,
-                                                _dev(stats), stats_stride, _dev(ncalls), int(max_calls), _dev(out), int(out_stride),
-                                                _hip_stream(stream)), "pirip_hip_ping_push_records")
+        self._call("pirip_hip_ping_push_records", _dev(status), status_stride, _dev(payload), payload_stride, _dev(info), info_stride,
+                   _dev(stats), stats_stride, _dev(ncalls), int(max_calls), _dev(out), int(out_stride), _hip_stream(stream))
 
     def process(self, out=None, out_stride=0, stream=None):
         """the block at rx.input() -> the log, and with tx one block per output (needs rx)"""
-        _chk(self.L.pirip_hip_ping_process(self.h, _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_ping_process")
+        super().process(out, out_stride, stream)
 
     def push(self, d_in, in_stride, out=None, out_stride=0, stream=None):
         """process() after copying the block from d_in (rows in_stride bytes apart) into rx's input"""
-        _chk(self.L.pirip_hip_ping_push(self.h, _dev(d_in), int(in_stride), _dev(out), int(out_stride), _hip_stream(stream)), "pirip_hip_ping_push")
+        super().push(d_in, in_stride, out, out_stride, stream)
 
     def records(self):
         """dict of the last call's rows: device pointers status, payload, info, stats, nframes and the strides in elements"""
-        p = [C.c_void_p() for _ in range(5)]
-        st = [C.c_size_t(0) for _ in range(4)]
-        _chk(self.L.pirip_hip_ping_records(self.h, C.byref(p[0]), C.byref(st[0]), C.byref(p[1]), C.byref(st[1]), C.byref(p[2]), C.byref(st[2]),
-                                           C.byref(p[3]), C.byref(st[3]), C.byref(p[4])), "pirip_hip_ping_records")
-        return dict(status=int(p[0].value or 0), status_stride=int(st[0].value), payload=int(p[1].value or 0), payload_stride=int(st[1].value),
-                    info=int(p[2].value or 0), info_stride=int(st[2].value), stats=int(p[3].value or 0), stats_stride=int(st[3].value),
-                    nframes=int(p[4].value or 0))
-
-    def offered(self):
-        """(device pointer of the records offered in the last call, bytes per channel row, device pointer of the int32 [nchan] counts)"""
-        p, n, st = C.c_void_p(), C.c_void_p(), C.c_size_t(0)
-        _chk(self.L.pirip_hip_ping_offered(self.h, C.byref(p), C.byref(st), C.byref(n)), "pirip_hip_ping_offered")
-        return int(p.value), int(st.value), int(n.value)
+        return self._records(("status", "payload", "info", "stats"))
 
     def counters(self):
         """dict of int64 arrays -- [nrx]: frames, filtered, decoded, crc_fail, bit_errors, lost; [nchan]: bursts_sent, frames_sent, skipped.
         Synchronises."""
-        import numpy as np
         out = {k: np.zeros(self.nrx, dtype=np.int64) for k in self.RX_COUNTERS}
         out.update({k: np.zeros(self.nchan, dtype=np.int64) for k in self.TX_COUNTERS})
-        _chk(self.L.pirip_hip_ping_get_counters(self.h, *(out[k].ctypes.data for k in self.RX_COUNTERS + self.TX_COUNTERS)),
-             "pirip_hip_ping_get_counters")
+        self._call("pirip_hip_ping_get_counters", *(out[k].ctypes.data for k in self.RX_COUNTERS + self.TX_COUNTERS))
         return out
 
     def log(self, chan, max_entries=None):
         """the newest entries of receive channel chan, oldest first: numpy structured array of PING_ENTRY_DTYPE. Synchronises."""
-        import numpy as np
         n = self.log_entries if max_entries is None else int(max_entries)
         out = np.zeros(max(n, 1), dtype=np.dtype(PING_ENTRY_DTYPE))
         assert out.dtype.itemsize == C.sizeof(PingEntry) == 40
         got = C.c_int(0)
-        _chk(self.L.pirip_hip_ping_get_log(self.h, int(chan), out.ctypes.data, n, C.byref(got)), "pirip_hip_ping_get_log")
+        self._call("pirip_hip_ping_get_log", int(chan), out.ctypes.data, n, C.byref(got))
         return out[:got.value].copy()
 
-    def reset(self, stream=None):
-        _chk(self.L.pirip_hip_ping_reset(self.h, _hip_stream(stream)), "pirip_hip_ping_reset")
 
-
-class HipAir:
+class HipAir(_Handle):
     """Channel (include/pirip_hip.h section O): ntx transmitted wideband IQ streams onto nrx received ones. paths: AirPath entries, or
     tuples / dicts of (rx, tx, gain, delay, offset_hz) -- received stream rx hears transmitted stream tx scaled by the real gain, `delay`
     samples late and `offset_hz` Hz up; sigma: the noise per component of every received stream (a number, nrx numbers, or None for none),
@@ -1071,9 +1067,9 @@ class HipAir:
     Fading: fades is a list of AirFade, of tuples (path, doppler_hz, rice_k, key) or of dicts with those keys (rice_k and
     key default to 0) -- the path of that index gets a Rayleigh (rice_k 0) or Rician gain of that Doppler spread, a float in Hz that is
     rounded to whole millihertz. Without fades the handle is the one it was."""
+    _c, _Info = "pirip_hip_air", AirInfo
 
     def __init__(self, Fs, paths, ntx, nrx, sigma=None, seed=1, in_format=IN_CU8_CSDR, out_format=IN_CU8_CSDR, device=-1, max_slip=0, fades=None):
-        self.L = lib()
         rows = []
         for p in paths:
             if isinstance(p, AirPathEx):
@@ -1087,32 +1083,25 @@ class HipAir:
                 rows.append(tuple(p))
         self.paths = rows
         sg = self._sigma(sigma, int(nrx))
-        h = C.c_void_p()
+        d_sg = None if sg is None else sg.ctypes.data
         common = (int(Fs), int(in_format), int(out_format), int(ntx), int(nrx), len(rows))
         self.fades = [air_fade(f) for f in fades or ()]
-        if self.fades:
-            arr = (AirPathEx * max(len(rows), 1))()
-            for i, p in enumerate(rows):
-                arr[i] = AirPathEx(int(p[0]), int(p[1]), int(p[3]), int(p[4]), float(p[2]), int(p[5]) if len(p) > 5 else 0)
-            farr = (AirFade * len(self.fades))(*self.fades)
-            _chk(self.L.pirip_hip_air_create_fade(*common, C.addressof(arr) if rows else None, len(self.fades), C.addressof(farr),
-                                                  None if sg is None else sg.ctypes.data, int(seed), int(max_slip), device, C.byref(h)),
-                 "pirip_hip_air_create_fade")
-        elif int(max_slip) == 0 and not any(len(p) > 5 and int(p[5]) for p in rows):
+        if not self.fades and int(max_slip) == 0 and not any(len(p) > 5 and int(p[5]) for p in rows):
             arr = (AirPath * max(len(rows), 1))()
             for i, (rx, tx, gain, delay, off) in enumerate(p[:5] for p in rows):
                 arr[i] = AirPath(int(rx), int(tx), int(delay), int(off), float(gain))
-            _chk(self.L.pirip_hip_air_create(*common, C.addressof(arr) if rows else None, None if sg is None else sg.ctypes.data, int(seed),
-                                             device, C.byref(h)), "pirip_hip_air_create")
+            self._create("pirip_hip_air_create", *common, C.addressof(arr) if rows else None, d_sg, int(seed), device)
         else:
             arr = (AirPathEx * max(len(rows), 1))()
             for i, p in enumerate(rows):
                 arr[i] = AirPathEx(int(p[0]), int(p[1]), int(p[3]), int(p[4]), float(p[2]), int(p[5]) if len(p) > 5 else 0)
-            _chk(self.L.pirip_hip_air_create_ex(*common, C.addressof(arr) if rows else None, None if sg is None else sg.ctypes.data, int(seed),
-                                                int(max_slip), device, C.byref(h)), "pirip_hip_air_create_ex")
-        self.h = h
-        self.info = AirInfo()
-        _chk(self.L.pirip_hip_air_get_info(self.h, C.byref(self.info)), "pirip_hip_air_get_info")
+            d_arr = C.addressof(arr) if rows else None
+            if self.fades:
+                farr = (AirFade * len(self.fades))(*self.fades)
+                self._create("pirip_hip_air_create_fade", *common, d_arr, len(self.fades), C.addressof(farr), d_sg, int(seed), int(max_slip),
+                             device)
+            else:
+                self._create("pirip_hip_air_create_ex", *common, d_arr, d_sg, int(seed), int(max_slip), device)
         self.Fs, self.ntx, self.nrx, self.seed, self.max_delay = int(Fs), self.info.ntx, self.info.nrx, int(seed), self.info.max_delay
         self.in_format, self.out_format = int(in_format), int(out_format)
         self.in_bytes_per_sample = 8 if in_format == IN_CF32 else 2
@@ -1120,7 +1109,6 @@ class HipAir:
 
     @staticmethod
     def _sigma(sigma, nrx):
-        import numpy as np
         if sigma is None:
             return None
         sg = np.ascontiguousarray(sigma, dtype=np.float32).reshape(-1)
@@ -1130,67 +1118,48 @@ class HipAir:
             raise ValueError("sigma: one value, or one per received stream")
         return sg
 
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_air_destroy(self.h)
-            self.h = None
-
-    __del__ = close
-
     def push(self, d_in, in_stride, n, d_out, out_stride, stream=None):
         """transmitted stream t: n samples at d_in + t * in_stride -> received stream r: n samples at d_out + r * out_stride (strides in
         bytes); the samples follow the last call's. Does not synchronise."""
-        _chk(self.L.pirip_hip_air_push(self.h, _dev(d_in), int(in_stride), int(n), _dev(d_out), int(out_stride), _hip_stream(stream)),
-             "pirip_hip_air_push")
+        self._call("pirip_hip_air_push", _dev(d_in), int(in_stride), int(n), _dev(d_out), int(out_stride), _hip_stream(stream))
 
     def set_sigma(self, sigma, stream=None):
         """new sigma (a number or nrx numbers) for the calls behind this one; does not synchronise"""
         sg = self._sigma(0.0 if sigma is None else sigma, self.nrx)
-        _chk(self.L.pirip_hip_air_set_sigma(self.h, sg.ctypes.data, _hip_stream(stream)), "pirip_hip_air_set_sigma")
+        self._call("pirip_hip_air_set_sigma", sg.ctypes.data, _hip_stream(stream))
 
     def reset(self, n0=0, stream=None, age=0):
         """forget the history: the next sample has absolute index n0 and clock age `age`, every earlier one is zero"""
         if age:
-            _chk(self.L.pirip_hip_air_reset_drift(self.h, int(n0), int(age), _hip_stream(stream)), "pirip_hip_air_reset_drift")
+            self._call("pirip_hip_air_reset_drift", int(n0), int(age), _hip_stream(stream))
         else:
-            _chk(self.L.pirip_hip_air_reset(self.h, int(n0), _hip_stream(stream)), "pirip_hip_air_reset")
+            self._call("pirip_hip_air_reset", int(n0), _hip_stream(stream))
 
     def drift(self):
         """(max_slip, how many more samples push() will take): host state, no synchronisation"""
         ms, left = C.c_int32(0), C.c_int64(0)
-        _chk(self.L.pirip_hip_air_get_drift(self.h, C.byref(ms), C.byref(left)), "pirip_hip_air_get_drift")
+        self._call("pirip_hip_air_get_drift", C.byref(ms), C.byref(left))
         return ms.value, left.value
 
 
-class HipSpectrum:
+class HipSpectrum(_Handle):
     """Band monitor (include/pirip_hip.h section P): averaged power spectra of nstreams wideband IQ streams and the power, peak and peak bin
     of a list of bands, block after block. nfft: 256, 1024 or 4096; hop: nfft (None) or nfft / 2; avg: segments per row; bands: SpecBand
     entries or tuples (stream, lo_hz, hi_hz); in_format: IN_CU8_CSDR or IN_CF32. The incomplete segments and the running row stay on the
     device: any cutting of a stream into push() calls gives the same rows and band entries. db() and occupied() work on what push()
     returned once it is on the host, in numpy and without a device."""
+    _c, _Info = "pirip_hip_spec", SpecInfo
 
     def __init__(self, Fs, nfft, hop=None, avg=1, nstreams=1, bands=(), in_format=IN_CU8_CSDR, device=-1):
-        self.L = lib()
         self.bands = [b if isinstance(b, SpecBand) else SpecBand(int(b[0]), int(b[1]), int(b[2])) for b in bands]
         arr = (SpecBand * max(len(self.bands), 1))(*self.bands)
-        h = C.c_void_p()
-        _chk(self.L.pirip_hip_spec_create(int(Fs), int(in_format), int(nfft), int(nfft if hop is None else hop), int(avg), int(nstreams),
-                                          len(self.bands), C.addressof(arr) if self.bands else None, device, C.byref(h)), "pirip_hip_spec_create")
-        self.h = h
-        self.info = SpecInfo()
-        _chk(self.L.pirip_hip_spec_get_info(self.h, C.byref(self.info)), "pirip_hip_spec_get_info")
+        self._create("pirip_hip_spec_create", int(Fs), int(in_format), int(nfft), int(nfft if hop is None else hop), int(avg), int(nstreams),
+                     len(self.bands), C.addressof(arr) if self.bands else None, device)
         self.Fs, self.nfft, self.hop, self.avg, self.nstreams, self.nbands = (self.info.Fs, self.info.nfft, self.info.hop, self.info.avg,
                                                                              self.info.nstreams, self.info.nbands)
         self.scale = float(self.info.scale)
         self.in_format = int(in_format)
         self.bytes_per_sample = 8 if in_format == IN_CF32 else 2
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_spec_destroy(self.h)
-            self.h = None
-
-    __del__ = close
 
     def window(self):
         return spec_window(self.nfft)
@@ -1198,12 +1167,12 @@ class HipSpectrum:
     def band_bins(self, q):
         """(first bin, number of bins) of band q: the bins first, first + 1, ... with wrap-around at nfft"""
         first, count = C.c_int32(0), C.c_int32(0)
-        _chk(self.L.pirip_hip_spec_band_bins(self.h, int(q), C.byref(first), C.byref(count)), "pirip_hip_spec_band_bins")
+        self._call("pirip_hip_spec_band_bins", int(q), C.byref(first), C.byref(count))
         return first.value, count.value
 
     def nrows(self, n):
         """rows the next push of n samples completes (host arithmetic)"""
-        m = int(self.L.pirip_hip_spec_nrows(self.h, int(n)))
+        m = int(self._value("pirip_hip_spec_nrows", int(n)))
         if m < 0:
             _chk(m, "pirip_hip_spec_nrows")
         return m
@@ -1231,17 +1200,16 @@ class HipSpectrum:
 
     def push_raw(self, d_in, in_stride, n, d_rows, row_stride, stream_stride, d_bands, band_stride, stream=None):
         """pirip_hip_spec_push on device pointers or tensors: in_stride in bytes, row_stride / stream_stride in floats, band_stride in entries"""
-        _chk(self.L.pirip_hip_spec_push(self.h, _dev(d_in), int(in_stride), int(n), _dev(d_rows), int(row_stride), int(stream_stride),
-                                        _dev(d_bands), int(band_stride), _hip_stream(stream)), "pirip_hip_spec_push")
+        self._call("pirip_hip_spec_push", _dev(d_in), int(in_stride), int(n), _dev(d_rows), int(row_stride), int(stream_stride),
+                   _dev(d_bands), int(band_stride), _hip_stream(stream))
 
     def reset(self, stream=None):
         """forget the history: the next sample starts segment 0 of row 0"""
-        _chk(self.L.pirip_hip_spec_reset(self.h, _hip_stream(stream)), "pirip_hip_spec_reset")
+        self._call("pirip_hip_spec_reset", _hip_stream(stream))
 
     @staticmethod
     def band_rows(bands):
         """push()'s band tensor (or its numpy copy) as a structured array [nbands, m] with the fields power, peak, peak_bin"""
-        import numpy as np
         b = bands.cpu().numpy() if hasattr(bands, "cpu") else np.asarray(bands)
         return np.ascontiguousarray(b).view(SPEC_BAND_ROW_DTYPE).reshape(b.shape[0], b.shape[1])
 
@@ -1256,7 +1224,6 @@ class HipSpectrum:
 
 def spec_window(nfft):
     """pirip_hip_spec_window (host only): the nfft floats of the band monitor's window"""
-    import numpy as np
     w = np.zeros(int(nfft), dtype=np.float32)
     _chk(lib().pirip_hip_spec_window(int(nfft), w.ctypes.data), "pirip_hip_spec_window")
     return w
@@ -1264,7 +1231,6 @@ def spec_window(nfft):
 
 def spec_db(rows, scale):
     """HipSpectrum.db without a handle: rows [..., nfft] (numpy or a tensor), scale = info.scale"""
-    import numpy as np
     r = rows.cpu().numpy() if hasattr(rows, "cpu") else np.asarray(rows)
     with np.errstate(divide="ignore"):
         return np.fft.fftshift(10.0 * np.log10(r.astype(np.float64) * float(scale)), axes=-1)
@@ -1272,7 +1238,6 @@ def spec_db(rows, scale):
 
 def spec_occupied(band_rows, nbins, noise_band, ratio_db):
     """HipSpectrum.occupied without a handle: nbins[q] the number of bins of band q"""
-    import numpy as np
     per_bin = band_rows["power"].astype(np.float64) / np.asarray(nbins, dtype=np.float64)[:, None]
     return per_bin > per_bin[int(noise_band)][None, :] * 10.0 ** (float(ratio_db) / 10.0)
 
@@ -1289,7 +1254,6 @@ def air_fade(f):
 
 def air_fade_table(Fs, seed, fade):
     """pirip_hip_air_fade_table (host only): (w int32 [16], theta uint32 [16], scale, los), the integers and floats the kernel reads"""
-    import numpy as np
     f = air_fade(fade)
     w, theta = np.zeros(16, dtype=np.int32), np.zeros(16, dtype=np.uint32)
     scale, los = C.c_float(0), C.c_float(0)
@@ -1302,7 +1266,6 @@ def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, 
               amp=32.0, sigma=0.0, seed=1, skip=None, stream=0):
     """Device-side fsk_mod -c | u8 quantiser [| AWGN] for len(f1_hz) streams (include/pirip_hip.h B2).
     d_bits / d_out are device pointers; f1_hz / skip are host integer sequences."""
-    import numpy as np
     f1 = np.ascontiguousarray(f1_hz, dtype=np.int32)
     sk = None if skip is None else np.ascontiguousarray(skip, dtype=np.int32)
     assert sk is None or sk.size == f1.size
@@ -1311,145 +1274,106 @@ def synth_cu8(Fs, Rs, M, f1_hz, tone_spacing, d_bits, bits_stride, nsym, d_out, 
                                    d_out, out_stride, nsamp, amp, sigma, seed, stream), "pirip_hip_synth_cu8")
 
 
-class ChainGroup(C.Structure):
-    """struct pirip_chain_group (include/pirip_hip.h)"""
-    _fields_ = [("dem", C.c_void_p), ("ldpc", C.c_void_p), ("d_in", C.c_void_p), ("d_status", C.c_void_p), ("d_payload", C.c_void_p),
-                ("d_info", C.c_void_p), ("d_stats", C.c_void_p), ("d_nframes", C.c_void_p), ("d_consumed", C.c_void_p)]
-
-
-class HipLdpc:
+class HipLdpc(_Handle):
     """nstreams FSK_LDPC receivers (include/pirip_hip.h section E): soft decisions -> status / payload records."""
+    _c, _Info = "pirip_hip_ldpc", LdpcInfo
 
     def __init__(self, code_path, M, Nsym=50, nstreams=1, device=-1):
-        self.L = lib()
-        self.h = C.c_void_p()
-        _chk(self.L.pirip_hip_ldpc_create(code_path.encode(), M, Nsym, nstreams, device, C.byref(self.h)), "pirip_hip_ldpc_create")
-        self.info = LdpcInfo()
-        _chk(self.L.pirip_hip_ldpc_get_info(self.h, C.byref(self.info)), "pirip_hip_ldpc_get_info")
+        self._create("pirip_hip_ldpc_create", code_path.encode(), M, Nsym, nstreams, device)
         self.M, self.Nsym, self.nstreams = M, Nsym, nstreams
         self.n, self.k, self.Nbits, self.data_bytes = self.info.n, self.info.k, self.info.nbits_per_call, self.info.data_bytes
 
-    def close(self):
-        if self.h:
-            self.L.pirip_hip_ldpc_destroy(self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def reset(self, stream=0):
-        _chk(self.L.pirip_hip_ldpc_reset(self.h, stream), "pirip_hip_ldpc_reset")
+        self._call("pirip_hip_ldpc_reset", stream)
 
     def llr_history(self, s=0):
         """The 2 * bits_per_frame binary16 soft bits receiver s carries into its next call, oldest first (pirip_hip_ldpc_get_llr_history)."""
-        import numpy as np
         out = np.zeros(2 * self.info.bits_per_frame, dtype=np.float16)
-        self.L.pirip_hip_ldpc_get_llr_history.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        _chk(self.L.pirip_hip_ldpc_get_llr_history(self.h, s, out.ctypes.data), "pirip_hip_ldpc_get_llr_history")
+        self._call("pirip_hip_ldpc_get_llr_history", s, out.ctypes.data)
         return out
 
     def layout_conflicts(self):
         """(identity layout's, layout in use's) bank conflicts per decoder iteration (pirip_hip_ldpc_get_layout_conflicts)."""
         ident, used = C.c_int(0), C.c_int(0)
-        self.L.pirip_hip_ldpc_get_layout_conflicts.argtypes = [C.c_void_p, C.POINTER(C.c_int), C.POINTER(C.c_int)]
-        _chk(self.L.pirip_hip_ldpc_get_layout_conflicts(self.h, C.byref(ident), C.byref(used)), "pirip_hip_ldpc_get_layout_conflicts")
+        self._call("pirip_hip_ldpc_get_layout_conflicts", C.byref(ident), C.byref(used))
         return ident.value, used.value
 
     def rx_batch(self, d_rx_filt, filt_stride, d_ncalls, ncalls, d_status, d_payload, d_info, stream=0):
-        _chk(self.L.pirip_hip_ldpc_rx_batch(self.h, d_rx_filt, filt_stride, d_ncalls, ncalls, d_status, d_payload, d_info, stream),
-             "pirip_hip_ldpc_rx_batch")
+        self._call("pirip_hip_ldpc_rx_batch", d_rx_filt, filt_stride, d_ncalls, ncalls, d_status, d_payload, d_info, stream)
 
     def chain_batch(self, dem, d_in, in_stride, nsamp, d_status, d_payload, d_info, d_nframes, d_consumed, max_frames,
                     d_stats=0, stats_stride=0, stream=0):
         """pirip_hip_fsk_ldpc_rx_batch: IQ of every stream of HipDemod `dem` -> records of this receiver's streams (device pointers)."""
-        _chk(self.L.pirip_hip_fsk_ldpc_rx_batch(dem.h, self.h, d_in, in_stride, nsamp, d_status, d_payload, d_info, d_stats, stats_stride,
-                                                d_nframes, d_consumed, max_frames, stream), "pirip_hip_fsk_ldpc_rx_batch")
+        name = "pirip_hip_fsk_ldpc_rx_batch"
+        _chk(self.L.pirip_hip_fsk_ldpc_rx_batch(dem._ptr(name), self._ptr(name), d_in, in_stride, nsamp, d_status, d_payload, d_info, d_stats,
+                                                stats_stride, d_nframes, d_consumed, max_frames, stream), name)
 
     @staticmethod
     def chain_batch_groups(groups, in_stride, nsamp, max_frames, stats_stride=0, stream=0):
         """pirip_hip_fsk_ldpc_rx_batch_groups: groups = [(HipLdpc, HipDemod, d_in, d_status, d_payload, d_info, d_nframes, d_consumed[, d_stats]), ...]"""
+        name = "pirip_hip_fsk_ldpc_rx_batch_groups"
         arr = (ChainGroup * len(groups))()
         for i, g in enumerate(groups):
             ld, dem, d_in, d_status, d_payload, d_info, d_nframes, d_consumed = g[:8]
-            arr[i] = ChainGroup(dem.h, ld.h, d_in, d_status, d_payload, d_info, g[8] if len(g) > 8 else None, d_nframes, d_consumed)
-        L = lib()
-        L.pirip_hip_fsk_ldpc_rx_batch_groups.argtypes = [C.POINTER(ChainGroup), C.c_int, C.c_size_t, C.c_int64, C.c_size_t, C.c_int64, C.c_void_p]
-        _chk(L.pirip_hip_fsk_ldpc_rx_batch_groups(arr, len(groups), in_stride, nsamp, stats_stride, max_frames, stream), "pirip_hip_fsk_ldpc_rx_batch_groups")
+            arr[i] = ChainGroup(dem._ptr(name), ld._ptr(name), d_in, d_status, d_payload, d_info, g[8] if len(g) > 8 else None, d_nframes,
+                                d_consumed)
+        _chk(lib().pirip_hip_fsk_ldpc_rx_batch_groups(arr, len(groups), in_stride, nsamp, stats_stride, max_frames, stream), name)
 
     def last_path_fused(self):
-        return self.L.pirip_hip_fsk_ldpc_last_path(self.h) == 1
+        return self._value("pirip_hip_fsk_ldpc_last_path") == 1
 
     def rx_host(self, rx_filt_calls):
-        import numpy as np
         r = np.ascontiguousarray(rx_filt_calls, dtype=np.float32).reshape(-1, self.M * self.Nsym)
         n = r.shape[0]
         status = np.zeros(n, dtype=np.uint8)
         payload = np.zeros((n, self.data_bytes), dtype=np.uint8)
         info = np.zeros((n, LDPC_INFO_PER_CALL), dtype=np.int32)
-        _chk(self.L.pirip_hip_ldpc_rx_host(self.h, r.ctypes.data, n, status.ctypes.data, payload.ctypes.data, info.ctypes.data),
-             "pirip_hip_ldpc_rx_host")
+        self._call("pirip_hip_ldpc_rx_host", r.ctypes.data, n, status.ctypes.data, payload.ctypes.data, info.ctypes.data)
         return status, payload, info
 
 
-class HipRx:
+class HipRx(_Handle):
     """Streaming receiver over live channels (include/pirip_hip.h section G): one block per channel per call, each channel's unconsumed
     tail carried on the device. dem: HipDemod; ldpc: HipLdpc or None (records out instead of bits); dec: HipDecim or None (u8 IQ at
     the tuner rate in instead of modem-rate samples); chan: HipChan or None (wideband u8 IQ captures in, one row per capture, each
     channel of the channelizer a channel of dem; exclusive with dec); block: input samples per channel (per capture with chan) per call.
     The handles must outlive the receiver."""
+    _c = "pirip_hip_rx"
 
     def __init__(self, dem, ldpc=None, dec=None, block=None, chan=None):
-        self.L = lib()
         if dec is not None and chan is not None:
             raise ValueError("HipRx: dec and chan are mutually exclusive")
         self.dem, self.ldpc, self.dec, self.chan = dem, ldpc, dec, chan
-        h = C.c_void_p()
-        if chan is not None:
-            _chk(self.L.pirip_hip_rx_create_chan(dem.h, ldpc.h if ldpc is not None else None, chan.h, int(block), C.byref(h)),
-                 "pirip_hip_rx_create_chan")
-        else:
-            _chk(self.L.pirip_hip_rx_create(dem.h, ldpc.h if ldpc is not None else None, dec.h if dec is not None else None, int(block),
-                                            C.byref(h)), "pirip_hip_rx_create")
-        self.h = h
+        name = "pirip_hip_rx_create_chan" if chan is not None else "pirip_hip_rx_create"
+        self._create(name, dem._ptr(name), _ptr_of(ldpc, name), _ptr_of(chan if chan is not None else dec, name), int(block))
         self.block, self.nstreams = int(block), dem.nstreams
         self.ninputs = chan.ninputs if chan is not None else dem.nstreams
-        self.max_frames = int(self.L.pirip_hip_rx_max_frames(self.h))
-
-    def close(self):
-        if getattr(self, "h", None):
-            self.L.pirip_hip_rx_destroy(self.h)
-            self.h = None
-
-    __del__ = close
+        self.max_frames = int(self._value("pirip_hip_rx_max_frames"))
 
     def input(self):
         """(device pointer of channel 0's next block, stride in bytes): the zero-copy landing zone (pirip_hip_rx_input)."""
         p, st = C.c_void_p(), C.c_size_t(0)
-        _chk(self.L.pirip_hip_rx_input(self.h, C.byref(p), C.byref(st)), "pirip_hip_rx_input")
+        self._call("pirip_hip_rx_input", C.byref(p), C.byref(st))
         return int(p.value), int(st.value)
 
     def process(self, d_bits=0, bits_stride=0, d_filt=0, filt_stride=0, d_status=0, d_payload=0, d_info=0, d_stats=0, stats_stride=0,
                 d_nframes=0, stream=0):
         """Raw device pointers (ints); enqueues on `stream`, does not synchronise."""
-        _chk(self.L.pirip_hip_rx_process(self.h, d_bits, bits_stride, d_filt, filt_stride, d_status, d_payload, d_info, d_stats,
-                                         stats_stride, d_nframes, stream), "pirip_hip_rx_process")
+        self._call("pirip_hip_rx_process", d_bits, bits_stride, d_filt, filt_stride, d_status, d_payload, d_info, d_stats,
+                   stats_stride, d_nframes, stream)
 
     def push(self, d_in, in_stride, d_bits=0, bits_stride=0, d_filt=0, filt_stride=0, d_status=0, d_payload=0, d_info=0, d_stats=0,
              stats_stride=0, d_nframes=0, stream=0):
         """process() after copying channel s's block from d_in + s * in_stride (device) into the input."""
-        _chk(self.L.pirip_hip_rx_push(self.h, d_in, in_stride, d_bits, bits_stride, d_filt, filt_stride, d_status, d_payload, d_info,
-                                      d_stats, stats_stride, d_nframes, stream), "pirip_hip_rx_push")
+        self._call("pirip_hip_rx_push", d_in, in_stride, d_bits, bits_stride, d_filt, filt_stride, d_status, d_payload, d_info,
+                   d_stats, stats_stride, d_nframes, stream)
 
     def counters(self):
         """(consumed_total int64[nstreams], backlog int32[nstreams]) -- synchronises."""
-        import numpy as np
         tot = np.zeros(self.nstreams, dtype=np.int64)
         bl = np.zeros(self.nstreams, dtype=np.int32)
-        _chk(self.L.pirip_hip_rx_get_counters(self.h, tot.ctypes.data, bl.ctypes.data), "pirip_hip_rx_get_counters")
+        self._call("pirip_hip_rx_get_counters", tot.ctypes.data, bl.ctypes.data)
         return tot, bl
 
     def reset(self, stream=0):
-        _chk(self.L.pirip_hip_rx_reset(self.h, stream), "pirip_hip_rx_reset")
+        self._call("pirip_hip_rx_reset", stream)

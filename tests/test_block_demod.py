@@ -37,12 +37,8 @@ def _same_result(a, b, what):
 
 
 def _state(h, s=0):
-    """pirip_hip_get_stream_state of stream s (14 words) and its Sf"""
-    import ctypes as C
-    st = np.zeros(14, dtype=np.uint32)
-    h.L.pirip_hip_get_stream_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    assert h.L.pirip_hip_get_stream_state(h.h, s, st.ctypes.data) == 0
-    return st, h.get_Sf(s)
+    """pirip_hip_get_stream_state of stream s (the 13 words of pirip_stream_state) and its Sf"""
+    return np.frombuffer(h.stream_state(s), dtype=np.uint32), h.get_Sf(s)
 
 
 def _scalars(h, s=0):
@@ -259,7 +255,7 @@ def test_stream_scalars_after_a_call_without_stats_output(oracle, built_lib, end
     _same_words(sc1, sc2, "scalars with and without the stats output")
     # (the rest of the state too, but for word 3, snr_est: a running average over the observable frames -- every frame with a stats output, the
     #  call's last one without, as include/pirip_hip.h says of pirip_stream_state)
-    keep = [i for i in range(14) if i != 3]
+    keep = [i for i in range(13) if i != 3]          # (the 13 words of the structure: all the library writes)
     _same_words(st1[keep], st2[keep], "stream state with and without the stats output")
     last = r1["stats"][-1]
     _same_words(sc1[[0, 1, 4, 5, 7]], last[[0, 1, 4, 5, 7]], "scalars against the last stats row")

@@ -67,11 +67,8 @@ def _same_words(a, b, what):
 
 
 def _state(h, s=0):
-    """pirip_hip_get_stream_state: nin, norm_rx_timing, ppm, snr_est, SNRest, EbNodB, v_est, f_est[4], rx_sig_pow, rx_nse_pow as 14 words"""
-    st = np.zeros(14, dtype=np.uint32)
-    h.L.pirip_hip_get_stream_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-    assert h.L.pirip_hip_get_stream_state(h.h, s, st.ctypes.data) == 0
-    return st
+    """pirip_hip_get_stream_state: nin, norm_rx_timing, ppm, snr_est, SNRest, EbNodB, v_est, f_est[4], rx_sig_pow, rx_nse_pow as 13 words"""
+    return np.frombuffer(h.stream_state(s), dtype=np.uint32)
 
 
 def _oracle_Sf(oracle, o, ndft):

@@ -1520,9 +1520,7 @@ def test_device_atan2f_restatement_equals_the_hosts_libm(built_lib):
         want[i] = libm.atan2f(float(y[i]), float(x[i]))
     dy, dx = torch.from_numpy(y).cuda(), torch.from_numpy(x).cuda()
     out = torch.zeros(n, dtype=torch.float32, device="cuda")
-    L = pirip_amd.lib()
-    L.pirip_hip_selftest_atan2.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
-    assert L.pirip_hip_selftest_atan2(dy.data_ptr(), dx.data_ptr(), out.data_ptr(), n) == 0
+    pirip_amd.selftest_atan2(dy.data_ptr(), dx.data_ptr(), out.data_ptr(), n)          # raises unless the status is PIRIP_OK
     torch.cuda.synchronize()
     got = out.cpu().numpy()
     assert np.array_equal(got[idx].view(np.uint32), want[idx].view(np.uint32)), np.nonzero(got[idx].view(np.uint32) != want[idx].view(np.uint32))[0][:5]

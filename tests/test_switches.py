@@ -195,12 +195,6 @@ def _stream(host, off, stride, n_in, s):
     return np.ascontiguousarray(host[off + s * stride: off + s * stride + 2 * n_in]).reshape(n_in, 2)
 
 
-def _get_arith(dec):
-    import ctypes as C
-    dec.L.pirip_hip_decim_get_arith.argtypes = [C.c_void_p]
-    return int(dec.L.pirip_hip_decim_get_arith(dec.h))
-
-
 @pytest.mark.parametrize("form", ["env", "api"])
 @pytest.mark.parametrize("D,tbw,kernel", ss.ARITH_ROWS)
 def test_decimator_opt_in_arithmetics_are_their_formulas_bit_for_bit(oracle, built_lib, monkeypatch, D, tbw, kernel, form):
@@ -223,9 +217,9 @@ def test_decimator_opt_in_arithmetics_are_their_formulas_bit_for_bit(oracle, bui
             else:
                 monkeypatch.delenv("PIRIP_DECIM_FMA", raising=False)
                 dec = pirip_amd.HipDecim(D, tbw, out_s16=s16)
-                assert _get_arith(dec) == 0
+                assert dec.get_arith() == 0
                 dec.set_arith(mode)
-            assert _get_arith(dec) == mode
+            assert dec.get_arith() == mode
             for layout, stride in strides.items():
                 got = _decimate(dec, dev, off, stride, n_in, B, s16)
                 for s in range(B):
@@ -251,7 +245,7 @@ def test_decimator_table_conversion_is_the_exact_oracle(oracle, built_lib, monke
         for mode in (1, 2):
             with pytest.raises(pirip_amd.PiripError, match=r"\(%d\)" % ERR_UNSUPPORTED):
                 dec.set_arith(mode)
-        assert _get_arith(dec) == 0
+        assert dec.get_arith() == 0
         for off in (2, 1):
             got = _decimate(dec, dev, off, stride, n_in, B, s16)
             for s in range(B):

@@ -80,10 +80,6 @@ def test_the_library_exports_the_record_conversion_and_refuses_bad_arguments_wit
         assert name + "(" in hdr and hasattr(built_lib, name), name
     assert "#define PIRIP_TX_REPEAT_MAX_FRAMES 100" in hdr
     mx, rr = built_lib.pirip_hip_tx_repeat_max_records, built_lib.pirip_hip_tx_repeat_records
-    mx.restype, mx.argtypes = C.c_int, [C.c_void_p, C.c_int]
-    rr.restype = C.c_int
-    rr.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p, C.c_size_t, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_size_t, C.c_int,
-                   C.c_void_p, C.c_void_p]
     assert mx(None, 10) == 0 and mx(None, -1) == 0
     buf = (C.c_uint8 * 64)()
     p = C.cast(buf, C.c_void_p)

@@ -118,12 +118,11 @@ def run(c, host, on, watch, packed=False):
         out["nframes"].append(nfr.cpu().numpy()); out["consumed"].append(cons.cpu().numpy())
         pos += out["consumed"][-1]
     assert (out["nframes"][0] == 2).all() and (out["nframes"][1] == 1).all(), "two frames, then the third"
-    h.L.pirip_hip_get_stream_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     per = {}
     for s in watch:
-        sc = np.zeros(8, dtype=np.float32); state = np.zeros(14, dtype=np.uint32)
-        assert h.L.pirip_hip_get_scalars(h.h, s, sc.ctypes.data) == 0 and h.L.pirip_hip_get_stream_state(h.h, s, state.ctypes.data) == 0
-        per[s] = {"Sf": h.get_Sf(s), "scalars": sc, "state": state}
+        sc = np.zeros(8, dtype=np.float32)
+        assert h.L.pirip_hip_get_scalars(h.h, s, sc.ctypes.data) == 0
+        per[s] = {"Sf": h.get_Sf(s), "scalars": sc, "state": np.frombuffer(h.stream_state(s), dtype=np.uint32)}
     h.close()
     return out, per
 

@@ -2,8 +2,6 @@
 through the C-ABI, pirip_hip_launch_first_tail_block -- no device. R = streams per CU / streams per workgroup x compute units workgroups
 are resident at once; a launch of nblocks > R workgroups raises the last R of them, a smaller one none (first raised block = nblocks).
 (One level only: the variant with three levels over the thirds of the window measured the same and was not kept)"""
-import ctypes as C
-
 import pytest
 
 import pirip_amd
@@ -35,15 +33,12 @@ def test_the_headline_launch(built_lib):
 
 def test_bad_arguments_and_unknown_residency(built_lib):
     L = pirip_amd.lib()
-    L.pirip_hip_launch_first_tail_block.argtypes = [C.c_int] * 4
     assert L.pirip_hip_launch_first_tail_block(-1, 12, 4, 256) < 0
     # a device whose CU count could not be read (0), or a shape without an instance: nothing raised
     assert pirip_amd.launch_first_tail_block(5000, 12, 4, 0) == 5000
     assert pirip_amd.launch_first_tail_block(5000, 0, 4, 256) == 5000
     assert pirip_amd.launch_first_tail_block(5000, 12, 0, 256) == 5000
-    L.pirip_hip_set_launch_tail_first.argtypes = [C.c_void_p, C.c_int]
     assert L.pirip_hip_set_launch_tail_first(None, 1) < 0
-    L.pirip_hip_get_launch_resident_blocks.argtypes = [C.c_void_p]
     assert L.pirip_hip_get_launch_resident_blocks(None) < 0
 
 

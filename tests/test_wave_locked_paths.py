@@ -128,11 +128,11 @@ def run(c, host, calls, cache, monkeypatch, limits=None):
             out["bits"][s].append(bits[s].cpu().numpy()); out["rx_filt"][s].append(filt[s].cpu().numpy()); out["stats"][s].append(stats[s].cpu().numpy())
         pos += cons.cpu().numpy()
     res = []
-    h.L.pirip_hip_get_stream_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
     for s in range(B):
-        sc = np.zeros(8, dtype=np.float32); state = np.zeros(14, dtype=np.uint32)
-        assert h.L.pirip_hip_get_scalars(h.h, s, sc.ctypes.data) == 0 and h.L.pirip_hip_get_stream_state(h.h, s, state.ctypes.data) == 0
-        res.append({"nframes": sum(calls), "consumed": int(pos[s]), "Sf": h.get_Sf(s), "scalars": sc, "state": state,
+        sc = np.zeros(8, dtype=np.float32)
+        assert h.L.pirip_hip_get_scalars(h.h, s, sc.ctypes.data) == 0
+        res.append({"nframes": sum(calls), "consumed": int(pos[s]), "Sf": h.get_Sf(s), "scalars": sc,
+                    "state": np.frombuffer(h.stream_state(s), dtype=np.uint32),
                     **{k: np.concatenate(out[k][s]) for k in out}})
     h.close()
     return res

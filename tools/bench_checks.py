@@ -121,11 +121,10 @@ def counter_annotations(h, lib, total_samples, kern_ms, M, TS, P, NSYM):
     """HBM bytes per launch and the VALU side of the headline kernel from the COMMITTED counter passes (profiles/hbm_traffic.json,
     collected in separate rocprofv3 --pmc runs), quoted only while the library that runs carries the kernel code object they were taken
     on. Returns (traffic_bytes_per_launch | None, traffic_source, valu | None, kernel_hash)."""
-    import ctypes as C
+    import pirip_amd
     traffic, traffic_src, valu, khash = None, None, None, None
     try:
-        lib.pirip_hip_kernel_source_hash.restype = C.c_char_p
-        khash = lib.pirip_hip_kernel_source_hash().decode()
+        khash = pirip_amd.kernel_source_hash()          # (of the library `lib`: the binding loads one per process)
         tj = json.load(open(os.path.join(ROOT, "profiles", "hbm_traffic.json")))
         if h.kernel() == "wave" and h.kernel_name() == tj.get("kernel_name", h.kernel_name()):
             fresh = tj.get("kernel_source_hash") == khash

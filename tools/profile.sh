@@ -31,7 +31,7 @@ SQ3="SQ_WAIT_INST_LDS SQ_LDS_ADDR_CONFLICT SQ_LDS_UNALIGNED_STALL SQ_ACTIVE_INST
 SQ4="SQ_INSTS_VMEM_WR SQ_INSTS_SMEM SQ_INST_CYCLES_VMEM SQ_INSTS_BRANCH SQ_INSTS_SENDMSG SQ_ACTIVE_INST_VMEM SQ_ACTIVE_INST_FLAT"
 SETS=("FETCH_SIZE" "WRITE_SIZE" "$SQ1" "$SQ2" "$SQ3")
 case "$PMC_SET" in SQ1) SETS=("$SQ1");; SQ2) SETS=("$SQ2");; SQ3) SETS=("$SQ3");; esac
-khash() { python3 -c "import sys,ctypes; sys.path.insert(0,'$R'); import pirip_amd; L=pirip_amd.lib(); L.pirip_hip_kernel_source_hash.restype=ctypes.c_char_p; print(L.pirip_hip_kernel_source_hash().decode())"; }
+khash() { python3 -c "import sys; sys.path.insert(0,'$R'); import pirip_amd; print(pirip_amd.kernel_source_hash())"; }
 # stats CMD... : one kernel-trace --stats run of CMD into /tmp/pr (+ /tmp/pr.log)
 stats() { rm -rf /tmp/pr; timeout $1 rocprofv3 --kernel-trace --stats -d /tmp/pr -- "${@:2}" > /tmp/pr.log 2>&1; }
 # pmc TIMEOUT "SET" CMD... : one counter run of CMD into /tmp/pm

@@ -44,11 +44,8 @@ m = re.search(r"kernel_source_hash ([0-9a-f]{16})", open(src).read())
 if m:
     out["kernel_source_hash"] = m.group(1)
 else:
-    import ctypes
     import pirip_amd
-    L = pirip_amd.lib()
-    L.pirip_hip_kernel_source_hash.restype = ctypes.c_char_p
-    out["kernel_source_hash"] = L.pirip_hip_kernel_source_hash().decode()
+    out["kernel_source_hash"] = pirip_amd.kernel_source_hash()
 # the opt-in band-only estimator's counter passes of the same tag (tools/profile.sh part "band"), when they were taken
 bsrc = src.replace("_headline_pmc.txt", "_band_only_stats_pmc.txt")
 if bsrc != src and os.path.exists(bsrc):

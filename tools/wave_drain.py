@@ -141,8 +141,7 @@ def main():
     L.pirip_hip_wave_timeline.argtypes = [C.c_void_p, C.c_int]
     x, _ = bench_configs.modulate(L, FS, RS, M, 10000, 10000, NSAMP // (FS // RS) + 50, 7)
     base = np.clip(np.rint(127.0 + 32.0 * x[:NSAMP].astype(np.float64)), 0, 255).astype(np.uint8)
-    L.pirip_hip_kernel_source_hash.restype = C.c_char_p
-    print(f"# tools/wave_drain.py --tail {args.mode}: timing build, kernel code object {L.pirip_hip_kernel_source_hash().decode()}")
+    print(f"# tools/wave_drain.py --tail {args.mode}: timing build, kernel code object {pirip_amd.kernel_source_hash()}")
     for B in args.streams:
         ms, t, R = run(B, args.mode, base)
         if args.dump:
