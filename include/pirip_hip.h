@@ -1088,6 +1088,111 @@ int pirip_hip_spec_push(pirip_hip_spec *spec, const void *d_in, size_t in_stride
 int pirip_hip_spec_reset(pirip_hip_spec *spec, void *hip_stream);
 
 /* ----------------------------------------------------------------------------------- */
+/* section Q : diversity receiver (B branches of one channel, soft bits combined per frame) */
+/*   The receive side of section O's one transmitter onto R received streams: the           */
+/*   receivers of a section E handle in groups of B branches -- tuners, antennas, sites    */
+/*   -- whose soft bits of the same frame are added and decoded once.     */
+/*   Adding LLRs is the optimal combination of independent branches, and the LLR stage      */
+/*   scales each branch by its own SNR estimate: the plain sum weights as maximal-ratio     */
+/*   combining would. The branch receivers write what they write today; this stage runs      */
+/*   behind them and reads what they left. Only symbols are added: PIRIP_HIP_ABI_VERSION    */
+/*   and every entry point above stand.                                                     */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_div pirip_hip_div;
+/* (This section's three structures are written `struct X { ... }; typedef struct X X;`, unlike the `typedef struct X { ... } X;` of every
+ * section above. tests/test_binding_abi_cpu.py finds the header's structures by the second form and holds them to a fixed list of ctypes
+ * twins; these three are held to their twins -- binding.DivConfig, DivEntry, DivInfo, DIV_ENTRY_DTYPE -- by tests/test_diversity_cpu.py
+ * instead. A structure added here in this form has NO layout check until a test names it: add it to that test, or extend the general
+ * guard's list and return to the usual form.) */
+struct pirip_div_config {
+    int branches;               /* B, 2 .. 8: receivers g B .. g B + B - 1 of ldpc are the branches of group g */
+    int samples_per_symbol;     /* Ts, modem-rate samples per symbol (Fs / Rs of the branches' demodulator) */
+    int nin0;                   /* samples the first demodulator call consumes (section N's clock) */
+    int max_skew_samples;       /* frames whose first unique-word bits lie at most this far apart are one frame */
+    int max_rows;               /* rows per receiver and call, 1 .. 4096: sizes every launch and the pending ring */
+    int log_entries;            /* >= 1: entries of each group's ring */
+};
+typedef struct pirip_div_config pirip_div_config;
+struct pirip_div_entry {                    /* 24 bytes */
+    int64_t t_samples;                      /* floor(tau_anchor / bps): the frame's first unique-word bit on the sample timeline */
+    int32_t iters, pcc, eraw;               /* the combined codeword's decode: info[4], info[5], info[8] of section E */
+    uint8_t members, solo_ok, status, pad;  /* bit b: branch b is a member / its own record had PIRIP_RX_BITS; PIRIP_RX_* of the decode */
+};
+typedef struct pirip_div_entry pirip_div_entry;
+struct pirip_div_info {
+    int groups, branches, samples_per_symbol, nin0, max_skew_samples, max_rows, log_entries, pending, slots, n, data_bytes, device;
+};
+typedef struct pirip_div_info pirip_div_info;
+/* The model. bps = log2(M), Ts = samples_per_symbol, bpf = 32 + n, Nbits as in ldpc; tags are int64 in units of 1 / bps sample.
+ * Branch clock, per receiver: {samples = 0, next_nin = nin0}; for every valid row f of a call, in order: samples += next_nin;
+ * next_nin = (int)stats[f][6] (pirip_hip_ping_push_records' clock).
+ * Candidate: every row with info[6] >= 0 (a job of the branch's sync state machine; loc = info[6]) holds the n codeword soft bits
+ * (binary16) its own decode read, its branch, solo_ok = the row's PIRIP_RX_BITS, and the tag
+ *     tau = t_end bps - (2 bpf - loc) Ts,         t_end = the branch clock after that row.
+ * Horizon, after a call's rows: H = min over the group's branches of (samples bps) - 2 bpf Ts; every candidate a branch can still
+ * produce has tau > H.
+ * Clusters, with K = max_skew_samples bps, repeated: the anchor is the pending candidate with the smallest (tau, branch); if
+ * tau_anchor + K <= H the cluster is every pending candidate with tau <= tau_anchor + K, at most one per branch (the earliest; a
+ * later one stays pending); it is emitted and its members leave the pending set; the first anchor that is not closed ends the call.
+ * Membership and order depend on tags alone: the sequence of clusters is the same for any cutting of the rows into calls.
+ * Combination, per soft-bit position: the members' values are added in float in ascending branch order, starting from the first
+ * member's value, and rounded once to binary16; a NaN becomes +0 (an erasure, section E's rule), +-inf stays, a sum beyond binary16's
+ * range is +-inf.
+ * Decode and record: the combined codeword goes through ldpc's own decoder (whichever PIRIP_LDPC_DECODER / auto selects: all three
+ * write the same words) and section E's CRC16; one pirip_div_entry per cluster is appended to the group's ring at written %
+ * log_entries, its data_bytes payload bytes to the payload ring beside it. status = PIRIP_RX_SYNC | PIRIP_RX_BITS (CRC matches) |
+ * PIRIP_RX_BIT_ERRORS (pcc < m); eraw counts against the combined hard decisions.
+ *
+ * Borrows ldpc, which must outlive the handle. PIRIP_ERR_BAD_ARG for NULL pointers, branches outside 2 .. 8, ldpc's nstreams no
+ * multiple of branches, samples_per_symbol < 1, nin0 < 0, log_entries < 1, max_rows < 1, and unless 0 <= K < bpf Ts / 2.
+ * PIRIP_ERR_UNSUPPORTED for max_rows > 4096. The pending ring holds 3 (max_rows Nbits / bpf + 2) + 2 candidates per branch: none is
+ * dropped while every call has at most max_rows rows and the clocks of a group's branches stay within one such call of each other.
+ * Create sizes everything and synchronises. */
+int pirip_hip_div_create(pirip_hip_ldpc *ldpc, const pirip_div_config *cfg, pirip_hip_div **out);
+int pirip_hip_div_destroy(pirip_hip_div *dv);
+int pirip_hip_div_get_info(const pirip_hip_div *dv, pirip_div_info *info);      /* pending, slots: candidates / clusters per group and call */
+/* Clocks, pending set, rings and counters as after create: the next call is call 0. Does not reset ldpc. */
+int pirip_hip_div_reset(pirip_hip_div *dv, void *hip_stream);
+/* In stream order behind a receive call of ldpc with the same ncalls -- pirip_hip_ldpc_rx_batch, pirip_hip_fsk_ldpc_rx_batch,
+ * pirip_hip_rx_process / push (ncalls = pirip_hip_rx_max_frames) -- on that call's rows: status bytes at d_status + r status_stride, info
+ * rows at d_info + r info_stride, stats rows at d_stats + r stats_stride (strides in elements), d_nframes [nstreams] valid rows per
+ * receiver (NULL: ncalls). Reads them and the soft bits and job lists the receive call left in ldpc's work buffers, which stay valid
+ * until ldpc's next receive call. Every receive call gives ldpc a new batch serial number: a collect without a fresh batch of that
+ * ncalls is PIRIP_ERR_BAD_ARG (stale buffers are never read; a batch received before create or reset is not fresh), as are NULL d_status / d_info / d_stats, ncalls < 1 or > max_rows, and
+ * strides below ncalls rows. Enqueued on hip_stream (NULL = default stream); never synchronises, never allocates; every call makes the
+ * same launches, sized from max_rows. A refusal above enqueues nothing and changes no state. Any other error (PIRIP_ERR_HIP:
+ * a launch failed) may come after the clocks have advanced and the batch has been marked as read: the handle is
+ * then out of step with its input, and pirip_hip_div_reset -- with a reset of ldpc and of what feeds it -- is the only way on. The same
+ * holds for push_candidates and flush, and for ldpc's receive calls, which count a batch before the launches that could fail. */
+int pirip_hip_div_collect(pirip_hip_div *dv, const uint8_t *d_status, size_t status_stride, const int32_t *d_info, size_t info_stride,
+                          const float *d_stats, size_t stats_stride, const int32_t *d_nframes, int ncalls, void *hip_stream);
+/* The layer under collect, for callers with soft bits of their own: ncand candidates -- n binary16 values at d_llr_h16 + c n, tag
+ * d_tag[c] (int64), receiver d_group_branch[c] = g B + b (an entry < 0 is skipped), d_solo_ok[c] (0 / 1) -- join the pending sets, then
+ * the clusters that d_clock_units [nstreams] (int64: each branch's clock in tag units, samples bps) closes are emitted, combined, decoded
+ * and recorded. ncand <= nstreams (max_rows Nbits / bpf + 2); ncand == 0 (pointers may be NULL) only moves the horizon.
+ * Cost: the list is in no order, so every group's one lane reads all ncand receiver indices to find its own -- groups x ncand reads
+ * per call. That is nothing for a handful of groups or candidates; with thousands of groups and thousands of candidates it is
+ * the call's largest cost, and collect, whose staging is per branch and read by its own group alone, is the path that scales. */
+int pirip_hip_div_push_candidates(pirip_hip_div *dv, const uint16_t *d_llr_h16, const int64_t *d_tag, const int32_t *d_group_branch,
+                                  const uint8_t *d_solo_ok, int ncand, const int64_t *d_clock_units, void *hip_stream);
+/* The same with H = +inf: everything pending is emitted. */
+int pirip_hip_div_flush(pirip_hip_div *dv, void *hip_stream);
+/* Device pointers to what the last collect / push_candidates / flush emitted, valid in stream order until the next: group g's d_count[g]
+ * entries at d_entries + g entry_stride (in entries) and payloads at d_payload + g payload_stride (bytes). Each pointer may be NULL. */
+int pirip_hip_div_last(pirip_hip_div *dv, const pirip_div_entry **d_entries, size_t *entry_stride, const uint8_t **d_payload,
+                       size_t *payload_stride, const int32_t **d_count);
+/* Host copy (synchronises the device) of the newest min(clusters, log_entries, max) entries of group `group`, oldest first, and their
+ * payloads [max][data_bytes] (may be NULL); *written (may be NULL): how many. */
+int pirip_hip_div_get_log(pirip_hip_div *dv, int group, pirip_div_entry *entries, uint8_t *payloads, int max, int *written);
+/* Host copies (synchronises), per group [groups], each may be NULL: clusters emitted, clusters with PIRIP_RX_BITS, those of them no
+ * member decoded alone (empty solo_ok), members summed, entries the ring overwrote, candidates dropped for want of pending space. */
+int pirip_hip_div_get_counters(pirip_hip_div *dv, int64_t *clusters, int64_t *bits, int64_t *rescued, int64_t *members, int64_t *lost,
+                               int64_t *dropped);
+/* Checking aid (synchronises): the n combined soft bits, binary16, of cluster `slot` of group `group` of the last call. */
+int pirip_hip_div_get_combined(pirip_hip_div *dv, int group, int slot, uint16_t *host_llr);
+/* One HIP stream per handle, the one ldpc's receive calls are enqueued on. */
+
+/* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */
 /*             names and signatures as codec2 src/fsk.h [UPSTREAM-RECALLED]              */
 /* ----------------------------------------------------------------------------------- */

@@ -126,6 +126,26 @@ class SpecInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("Fs", "in_format", "nfft", "hop", "avg", "nstreams", "nbands", "device")] + [("scale", C.c_double)]
 
 
+class DivConfig(C.Structure):
+    """pirip_div_config: branches per group, samples per symbol, the first call's samples, skew in samples, rows per call, ring entries"""
+    _fields_ = [(n, C.c_int) for n in ("branches", "samples_per_symbol", "nin0", "max_skew_samples", "max_rows", "log_entries")]
+
+
+class DivEntry(C.Structure):
+    _fields_ = [("t_samples", C.c_int64), ("iters", C.c_int32), ("pcc", C.c_int32), ("eraw", C.c_int32), ("members", C.c_uint8),
+                ("solo_ok", C.c_uint8), ("status", C.c_uint8), ("pad", C.c_uint8)]
+
+
+# pirip_div_entry as a numpy structured dtype (24 bytes, the C layout): what HipDiversity.log and .last return
+DIV_ENTRY_DTYPE = [("t_samples", "<i8"), ("iters", "<i4"), ("pcc", "<i4"), ("eraw", "<i4"), ("members", "u1"), ("solo_ok", "u1"),
+                   ("status", "u1"), ("pad", "u1")]
+
+
+class DivInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("groups", "branches", "samples_per_symbol", "nin0", "max_skew_samples", "max_rows", "log_entries",
+                                       "pending", "slots", "n", "data_bytes", "device")]
+
+
 # pirip_spec_band_row as a numpy structured dtype (12 bytes, the C layout): what HipSpectrum.push's band entries are on the host
 SPEC_BAND_ROW_DTYPE = [("power", "<f4"), ("peak", "<f4"), ("peak_bin", "<i4")]
 
@@ -301,6 +321,18 @@ def _signatures():
         "pirip_hip_spec_nrows": (i64, [vp, i64]),
         "pirip_hip_spec_push": (i32, [vp, vp, sz, i64, vp, sz, sz, vp, sz, vp]),
         "pirip_hip_spec_reset": (i32, [vp, vp]),
+        # section Q: diversity receiver
+        "pirip_hip_div_create": (i32, [vp, P(DivConfig), P(vp)]),
+        "pirip_hip_div_destroy": (i32, [vp]),
+        "pirip_hip_div_get_info": (i32, [vp, P(DivInfo)]),
+        "pirip_hip_div_reset": (i32, [vp, vp]),
+        "pirip_hip_div_collect": (i32, [vp, vp, sz, vp, sz, vp, sz, vp, i32, vp]),
+        "pirip_hip_div_push_candidates": (i32, [vp, vp, vp, vp, vp, i32, vp, vp]),
+        "pirip_hip_div_flush": (i32, [vp, vp]),
+        "pirip_hip_div_last": (i32, [vp, P(vp), P(sz), P(vp), P(sz), P(vp)]),
+        "pirip_hip_div_get_log": (i32, [vp, i32, vp, vp, i32, P(i32)]),
+        "pirip_hip_div_get_counters": (i32, [vp] + [vp] * 6),
+        "pirip_hip_div_get_combined": (i32, [vp, i32, i32, vp]),
         # the library itself
         "pirip_hip_find_code": (i32, [cs, cs, sz]),
         "pirip_hip_version": (cs, []),

@@ -44,6 +44,7 @@ struct pirip_hip_ldpc {
     // per-batch work buffers (grown on demand)
     uint16_t *d_llr_all = nullptr; uint32_t *d_words = nullptr, *d_best = nullptr; int32_t *d_jobs = nullptr, *d_njobs = nullptr;
     size_t cap_calls = 0;
+    uint64_t batch_serial = 0; int batch_ncalls = 0;   // number and width of the last receive call: what section Q's collect reads must be fresh
     float *d_filt_work = nullptr; size_t filt_cap = 0;   // pirip_hip_fsk_ldpc_rx_batch's magnitudes when the fused hand-over does not apply
     int last_path_fused = 0;
     // host staging for the one-stream convenience entry

@@ -265,6 +265,7 @@ int pirip_hip_ldpc_rx_batch(pirip_hip_ldpc *h, const float *d_rx_filt, size_t fi
     const BatchDims bd = batch_dims(c, ncalls);
     int rc = ensure_work(h, ncalls, st);
     if (rc != PIRIP_OK) return rc;
+    h->batch_serial++; h->batch_ncalls = ncalls;
     const bool fused_words = (2 * c.bpf) % 32 == 0;        // every LLR tile then covers whole hard-decision words
     PIRIP_HIPCHK(launch_llr<h16>(h, h->nstreams, st, d_rx_filt, filt_stride, d_ncalls, ncalls, h->d_llr_all, bd.llr_stride,
                          h->d_llr_hist, fused_words ? h->d_words : (uint32_t *)nullptr, bd.nwords));
@@ -317,6 +318,7 @@ int pirip::fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const 
             return stages_after_llr(h, d_nframes, ncalls, d_status, d_payload, d_info, sg, s0, n, beside, sdec, ev);
         };
         h->last_path_fused = 1;
+        h->batch_serial++; h->batch_ncalls = ncalls;
         // Many streams: two ranges (5/8 and 3/8 of them) on two internal HIP streams, forked from and joined back into the caller's. The
         // FSK_LDPC stages are bound by the LDS pipe and the demodulator by VALU issue: the first range's decode (high priority) runs beside
         // the second range's demodulator instead of after the whole batch's (config 4: 26.9 -> 25.2 ms at 3.5 dB). Same kernels on the same
