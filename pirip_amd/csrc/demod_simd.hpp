@@ -178,13 +178,15 @@ __device__ __forceinline__ void bfly4(v2f &f0, v2f &f1, v2f &f2, v2f &f3)
 // Exact conversions (each checked against the defining expression for every input value in tests/test_boundary_cpu.py):
 //   fsk_demod -d   (x - 127)/128              = fma(x, 2^-7, -127/128)
 //   csdr / rtl_fsk x/127.5 - 1 (double, rounded) = fma(x, c_lo, fma(x, c_hi, -1)), c_hi a multiple of 2^-22
+// (hi, lo, c) of fma(x, lo, fma(x, hi, c)): -d needs no second term
+constexpr float kU8dHi = 0.0078125f, kU8dLo = 0.0f, kU8dC = -0.9921875f;
+constexpr float kCsdrHi = 0.007843255996704102f, kCsdrLo = -1.187418e-07f, kCsdrC = -1.0f;
 // the maps on an (I, Q) pair of byte values: one v_pk_fma_f32 per fma instead of two scalar ones (round 5)
 template <int FMT>
 __device__ __forceinline__ v2f cvt_u8_pair(v2f b)
 {
-    if (FMT == PIRIP_IN_CU8_FSKDEMOD) return __builtin_elementwise_fma(b, v2f{0.0078125f, 0.0078125f}, v2f{-0.9921875f, -0.9921875f});
-    return __builtin_elementwise_fma(b, v2f{-1.187418e-07f, -1.187418e-07f},
-                                     __builtin_elementwise_fma(b, v2f{0.007843255996704102f, 0.007843255996704102f}, v2f{-1.0f, -1.0f}));
+    if (FMT == PIRIP_IN_CU8_FSKDEMOD) return __builtin_elementwise_fma(b, v2f{kU8dHi, kU8dHi}, v2f{kU8dC, kU8dC});
+    return __builtin_elementwise_fma(b, v2f{kCsdrLo, kCsdrLo}, __builtin_elementwise_fma(b, v2f{kCsdrHi, kCsdrHi}, v2f{kCsdrC, kCsdrC}));
 }
 
 }  // namespace pirip

@@ -154,7 +154,7 @@ int demod_handle_shape(const pirip_hip_demod *h, int *M, int *Nsym, int *nstream
 int demod_streams_per_cu(const pirip_hip_demod *h);                     // streams of the handle's wave instance that one CU holds at a time (0: another kernel)
 bool demod_soft_capable(const pirip_hip_demod *h, int64_t nsamp);      // the handle's kernel instance can write the fused hand-over for calls of nsamp samples
 
-// launchers (fsk_demod_kernels.hip)
+// launchers (fsk_demod_general.hip)
 size_t demod_general_lds_bytes(const FskDims &d);
 hipError_t launch_demod_general(const DemodArgs &a, int nstreams, hipStream_t stream);
 // the exact first frame (a variant of the general kernel): applicable when a window can hold a single sample (Ts == P) and the shape fits
@@ -177,11 +177,11 @@ hipError_t launch_demod_wave(const DemodArgs &a, int nstreams, hipStream_t strea
 bool demod_block_applicable(const FskDims &d);
 int demod_block_describe(const FskDims &d, char *buf, size_t n);
 hipError_t launch_demod_block(const DemodArgs &a, int nstreams, hipStream_t stream);
-// the launcher of a handle's kernel kind (PIRIP_KERNEL_GENERAL / _WAVE / _BLOCK)
+// the launcher of a handle's kernel kind (PIRIP_KERNEL_GENERAL / _WAVE / _BLOCK / _EXACT)
 inline hipError_t launch_demod_kind(int kind, const DemodArgs &a, int nstreams, hipStream_t stream)
 {
-    return kind == 2 ? launch_demod_wave(a, nstreams, stream) : kind == 3 ? launch_demod_block(a, nstreams, stream) :
-           kind == 4 ? launch_demod_exact(a, nstreams, stream) : launch_demod_general(a, nstreams, stream);
+    return kind == PIRIP_KERNEL_WAVE ? launch_demod_wave(a, nstreams, stream) : kind == PIRIP_KERNEL_BLOCK ? launch_demod_block(a, nstreams, stream) :
+           kind == PIRIP_KERNEL_EXACT ? launch_demod_exact(a, nstreams, stream) : launch_demod_general(a, nstreams, stream);
 }
 const char *demod_wave_source_hash();                              // Makefile: sha256 prefix of the gfx950 code object in fsk_demod_wave.o
 // exhaustive device-side check of the wave kernel's correctly rounded square roots (x = 0 and every float in [2^-96, FLT_MAX])

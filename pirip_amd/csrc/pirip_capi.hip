@@ -236,7 +236,7 @@ int pirip_hip_get_kernel_name(const pirip_hip_demod *h, char *buf, size_t n)
 {
     if (!h || !buf || !n) return PIRIP_ERR_BAD_ARG;
     buf[0] = 0;
-    if (h->kernel == 2 && demod_wave_describe(h->plan.d, buf, n) > 0) return PIRIP_OK;
+    if (h->kernel == PIRIP_KERNEL_WAVE && demod_wave_describe(h->plan.d, buf, n) > 0) return PIRIP_OK;
     if (h->kernel == PIRIP_KERNEL_BLOCK && demod_block_describe(h->plan.d, buf, n) > 0) return PIRIP_OK;
     const FskDims &d = h->plan.d;
     snprintf(buf, n, "fsk_demod_%s_kernel(M=%d,Ts=%d,P=%d,Nsym=%d,Ndft=%d,format %d%s)", h->kernel == PIRIP_KERNEL_EXACT ? "exact" : "general", d.M, d.Ts, d.P, d.Nsym, d.Ndft, d.in_format,
@@ -357,12 +357,12 @@ int demod_batch_seg(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes
     a.io.seg = seg;
     a.io.eye = (h->kernel == PIRIP_KERNEL_GENERAL || h->kernel == PIRIP_KERNEL_EXACT) ? h->d_eye : nullptr;
     hipError_t e;
-    if (h->kernel == 2 && nsamp > demod_wave_max_samples(a.d)) return PIRIP_ERR_UNSUPPORTED;   // present the batch in smaller pieces (before anything runs)
+    if (h->kernel == PIRIP_KERNEL_WAVE && nsamp > demod_wave_max_samples(a.d)) return PIRIP_ERR_UNSUPPORTED;   // present the batch in smaller pieces (before anything runs)
     {
         const int pr = exact0_prologue(h, &a, (hipStream_t)hip_stream);
         if (pr != PIRIP_OK) return pr;
     }
-    if (h->kernel == 2) {
+    if (h->kernel == PIRIP_KERNEL_WAVE) {
         e = launch_demod_wave(a, h->nstreams, (hipStream_t)hip_stream);
     } else e = launch_demod_kind(h->kernel, a, h->nstreams, (hipStream_t)hip_stream);
     PIRIP_HIPCHK(e);
@@ -376,7 +376,7 @@ int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_byte
                      int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, hipStream_t st, int s0, int n, const SegDesc *seg)
 {
     if (!h || !d_in || nsamp < 0 || max_frames < 0 || !so.llr || !so.words || !so.lnI0 || (so.bit0 & 31)) return PIRIP_ERR_BAD_ARG;
-    if (h->kernel != 2 || !demod_wave_soft_capable(h->plan.d) || nsamp > demod_wave_max_samples(h->plan.d)) return PIRIP_ERR_UNSUPPORTED;
+    if (h->kernel != PIRIP_KERNEL_WAVE || !demod_wave_soft_capable(h->plan.d) || nsamp > demod_wave_max_samples(h->plan.d)) return PIRIP_ERR_UNSUPPORTED;
     if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
     DemodArgs a;
     fill_args(h, &a);
@@ -404,9 +404,9 @@ int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_byte
 }
 bool demod_soft_capable(const pirip_hip_demod *h, int64_t nsamp)
 {
-    return h && h->kernel == 2 && demod_wave_soft_capable(h->plan.d) && nsamp <= demod_wave_max_samples(h->plan.d);
+    return h && h->kernel == PIRIP_KERNEL_WAVE && demod_wave_soft_capable(h->plan.d) && nsamp <= demod_wave_max_samples(h->plan.d);
 }
-int demod_streams_per_cu(const pirip_hip_demod *h) { return h && h->kernel == 2 ? demod_wave_streams_per_cu(h->plan.d) : 0; }
+int demod_streams_per_cu(const pirip_hip_demod *h) { return h && h->kernel == PIRIP_KERNEL_WAVE ? demod_wave_streams_per_cu(h->plan.d) : 0; }
 int demod_handle_shape(const pirip_hip_demod *h, int *M, int *Nsym, int *nstreams, int *device)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;
