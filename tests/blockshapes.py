@@ -3,7 +3,9 @@ tests/test_block_demod.py (the device): the workgroup-per-stream demodulator of 
 240 kS/s -- Ts = 240, P = 15, Ndft = 4096, frames of N = 12000 samples, nin = N - 60, N or N + 60."""
 import numpy as np
 
+import parity
 import sigutil
+from demodrun import resample_at
 
 FS, RS, P, F1, SHIFT, MASK = 240000, 1000, 15, 11000, 2000, 2000
 TS, NSYM = FS // RS, 50
@@ -93,17 +95,12 @@ def _with_Sf(ob, o, u8, fmt):
 
 
 def oracle_Sf(ob, o):
-    import ctypes as C
-    from parity import _oracle_field_Sf
-    return np.ctypeslib.as_array(C.cast(_oracle_field_Sf(ob, o), C.POINTER(C.c_float)), shape=(NDFT,)).copy()
+    return parity.oracle_Sf(ob, o, NDFT)
 
 
 def resample(x, ppm):
     """a sample clock off by ppm, by linear interpolation (test_sample_clock_offset_exercises_nin_feedback's resampler)"""
-    n = x.shape[0]
-    t = np.arange(int(n / (1 + abs(ppm)) - 2)) * (1 + ppm)
-    i0 = np.floor(t).astype(int); fr = (t - i0)[:, None].astype(np.float32)
-    return (1 - fr) * x[i0] + fr * x[np.minimum(i0 + 1, n - 1)]
+    return resample_at(x, np.arange(int(x.shape[0] / (1 + abs(ppm)) - 2)) * (1 + ppm))
 
 
 def clock_stream(ob, M, fmt, ppm):

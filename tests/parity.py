@@ -1,6 +1,6 @@
-"""The comparison every device test of the demodulators shares: tolerances, the oracle / handle pair of one
-configuration, the frame-by-frame comparison and the oracle's smoothed spectrum. Used by tests/test_gpu_parity.py, tests/test_block_demod.py
-and what imports them."""
+"""The comparison with the oracle every device test of the demodulators shares: tolerances, the frame-by-frame comparison
+and the oracle's smoothed spectrum. The harness around it -- handles, runs in calls, the word-for-word comparison of two runs -- is
+tests/demodrun.py."""
 import numpy as np
 
 RX_FILT_TOL = 1e-4        # relative to the peak magnitude of the compared block
@@ -9,12 +9,9 @@ TIMING_TOL = 5e-5         # absolute, norm_rx_timing in symbols: the oracle's re
 
 
 def _pair(ob, c, fmt_o, fmt_h, nstreams=1, mask=0, Nsym=50):
-    import pirip_amd
-    o = ob.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], Nsym=Nsym, est_min=c["est_min"], est_max=c["est_max"],
-                     tone_spacing=mask if mask else 100, mask=bool(mask))
-    h = pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], Nsym=Nsym, est_min=c["est_min"], est_max=c["est_max"],
-                           mask=mask, in_format=fmt_h, nstreams=nstreams)
-    return o, h
+    import demodrun
+    c = dict(c, Nsym=Nsym, mask=mask, fmt=fmt_h, band=False)
+    return demodrun.make_oracle(ob, c), demodrun.make_handle(c, nstreams)
 
 
 def _compare(ro, rh, tol=RX_FILT_TOL, allow_near_tie_flips=False, M=2):
@@ -88,3 +85,9 @@ def _oracle_field_Sf(oracle, o):
     o.l.oracle_fsk_get_Sf.restype = C.c_void_p
     o.l.oracle_fsk_get_Sf.argtypes = [C.c_void_p]
     return o.l.oracle_fsk_get_Sf(o.h)
+
+
+def oracle_Sf(oracle, o, ndft=256):
+    """the oracle's smoothed spectrum after its last frame"""
+    import ctypes as C
+    return np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(ndft,)).copy()

@@ -199,9 +199,8 @@ def fft_input(ob, sigutil, name):
 def oracle_fft_run(ob, sigutil, u8, fused, first_frame_unfused=False, cfg=None):
     """The oracle on u8 with the estimator FFT's multiply unfused or fused; first_frame_unfused: the switch is flipped after frame 0 (the
     product's exact first-frame prologue runs in the general kernel's unfused body). Returns (result, Sf); the switch is left off."""
-    import ctypes as C
     import numpy as np
-    from parity import _oracle_field_Sf
+    from parity import oracle_Sf
     c = cfg or sigutil.CFG1
     o = ob.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"])
     try:
@@ -219,5 +218,5 @@ def oracle_fft_run(ob, sigutil, u8, fused, first_frame_unfused=False, cfg=None):
     finally:
         ob.set_fft_fused(False)
     ndft = 1 << (int(c["Fs"] / (0.1 * c["Rs"])) - 1).bit_length()
-    Sf = np.ctypeslib.as_array(C.cast(_oracle_field_Sf(ob, o), C.POINTER(C.c_float)), shape=(ndft,)).copy()
+    Sf = oracle_Sf(ob, o, ndft)
     return r, Sf

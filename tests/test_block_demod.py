@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 
 import blockshapes as bs
+from demodrun import host_chunks, same_results, same_words, scalars, stream_state
 from parity import RX_FILT_TOL, _compare
 
 pytestmark = pytest.mark.gpu
@@ -20,47 +21,9 @@ FILL = 0xA5
 NFILT = bs.NSYM                  # soft magnitudes per tone and frame
 
 
-def _same_words(a, b, what):
-    """bit for bit, floats compared as words"""
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape)
-    x, y = a.view(np.uint8), b.view(np.uint8)
-    if not np.array_equal(x, y):
-        bad = np.argwhere(a != b)
-        raise AssertionError((what, len(bad), bad[:4].tolist(), a[tuple(bad[0])], b[tuple(bad[0])]))
-
-
-def _same_result(a, b, what):
-    assert a["nframes"] == b["nframes"] and a["consumed"] == b["consumed"], (what, a["nframes"], b["nframes"], a["consumed"], b["consumed"])
-    for k in ("bits", "rx_filt", "stats"):
-        _same_words(a[k], b[k], (what, k))
-
-
 def _state(h, s=0):
-    """pirip_hip_get_stream_state of stream s (the 13 words of pirip_stream_state) and its Sf"""
-    return np.frombuffer(h.stream_state(s), dtype=np.uint32), h.get_Sf(s)
-
-
-def _scalars(h, s=0):
-    sc = np.zeros(8, dtype=np.float32)
-    assert h.L.pirip_hip_get_scalars(h.h, s, sc.ctypes.data) == 0
-    return sc
-
-
-def _chunked(h, u8, sizes):
-    """the read loop in ragged chunks: what a call did not consume goes in front of the next chunk"""
-    pos, carry = 0, np.zeros((0, 2), dtype=np.uint8)
-    parts = []
-    for n in sizes:
-        if pos >= u8.shape[0]:
-            break
-        buf = np.concatenate([carry, u8[pos:pos + n]]); pos += n
-        r = h.demod_host(buf)
-        parts.append(r)
-        carry = buf[r["consumed"]:]
-    assert pos >= u8.shape[0]
-    return {"nframes": sum(r["nframes"] for r in parts), "consumed": u8.shape[0] - carry.shape[0], "bits": np.concatenate([r["bits"] for r in parts]),
-            "rx_filt": np.concatenate([r["rx_filt"] for r in parts]), "stats": np.concatenate([r["stats"] for r in parts])}, len(parts)
+    """the 13 words of stream s's pirip_stream_state and its Sf"""
+    return stream_state(h, s), h.get_Sf(s)
 
 
 class Batch:
@@ -125,14 +88,16 @@ def test_every_instance_one_shot_and_ragged_chunks_equal_the_oracle(oracle, buil
             and ("u8 csdr" if fmt == "csdr" else "u8 -d") in h1.kernel_name(), h1.kernel_name()
         r1 = h1.demod_host(u8)
         nflips = _compare(ro, r1, tol=TOL, allow_near_tie_flips=bool(noisy), M=M)
-        _same_words(h1.get_Sf(0), Sf_o, (name, noisy, "Sf after one shot"))
+        same_words(h1.get_Sf(0), Sf_o, (name, noisy, "Sf after one shot"))
         h2 = bs.handle_of(pirip_amd, M, fmt, mask)
-        r2, ncalls = _chunked(h2, u8, bs.chunk_sizes(sorted(bs.ROWS).index(name) + 10 * noisy, u8.shape[0]))
+        cuts = [int(c) for c in np.cumsum(bs.chunk_sizes(sorted(bs.ROWS).index(name) + 10 * noisy, u8.shape[0])) if c < u8.shape[0]]
+        ncalls = len(cuts) + 1
+        r2 = host_chunks(h2, u8, cuts)
         assert ncalls >= 3
         _compare(ro, r2, tol=TOL, allow_near_tie_flips=bool(noisy), M=M)
-        _same_words(h2.get_Sf(0), Sf_o, (name, noisy, "Sf after chunks"))
-        _same_result(r2, r1, (name, noisy, "chunks against one shot"))
-        _same_words(_state(h2)[0], _state(h1)[0], (name, noisy, "stream state"))
+        same_words(h2.get_Sf(0), Sf_o, (name, noisy, "Sf after chunks"))
+        same_results(r2, r1, (name, noisy, "chunks against one shot"))
+        same_words(_state(h2)[0], _state(h1)[0], (name, noisy, "stream state"))
         print(f"{name} {'9 dB' if noisy else 'clean'}: {ro['nframes']} frames, {ncalls} chunks, {nflips} near-tie flips, "
               f"rx_filt error {np.abs(r1['rx_filt'].astype(np.float64) - ro['rx_filt']).max() / np.abs(ro['rx_filt']).max():.2e} of the peak (bar {TOL:g})")
 
@@ -159,7 +124,7 @@ def test_all_240_start_offsets_in_one_batch(oracle, built_lib, fmt, M):
             _compare(ro, rh, tol=TOL, M=M)
         except AssertionError as e:
             raise AssertionError(f"start offset {off}: {e}") from e
-        _same_words(h.get_Sf(off), ro["Sf"], ("Sf of start offset", off))
+        same_words(h.get_Sf(off), ro["Sf"], ("Sf of start offset", off))
         worst = max(worst, float(np.abs(rh["rx_filt"].astype(np.float64) - ro["rx_filt"]).max() / np.abs(ro["rx_filt"]).max()))
     print(f"{fmt} M = {M}: 240 start offsets, largest rx_filt error {worst:.2e} of the peak (bar {TOL:g})")
 
@@ -178,7 +143,7 @@ def test_sustained_clock_offset(oracle, built_lib, ppm, M, fmt):
     h = bs.handle_of(pirip_amd, M, fmt)
     assert h.kernel() == "block"
     _compare(ro, h.demod_host(u8), tol=TOL, M=M)
-    _same_words(h.get_Sf(0), bs.oracle_Sf(oracle, o), "Sf")
+    same_words(h.get_Sf(0), bs.oracle_Sf(oracle, o), "Sf")
 
 
 # ---- d ---------------------------------------------------------------------------------------------------------------------------------
@@ -201,9 +166,9 @@ def test_packed_bits_equal_packbits_of_the_unpacked_twin(oracle, built_lib, name
         assert twin[s]["nframes"] >= 10 and twin[s]["bits"].max() == 1 and twin[s]["untouched"] and packed[s]["untouched"]
         assert packed[s]["nframes"] == twin[s]["nframes"] and packed[s]["consumed"] == twin[s]["consumed"]
         assert packed[s]["bits"].shape == (twin[s]["nframes"], fb)
-        _same_words(packed[s]["bits"], np.packbits(twin[s]["bits"], axis=1), (name, s, "packed bits"))
-        _same_words(packed[s]["rx_filt"], twin[s]["rx_filt"], (name, s, "rx_filt"))
-        _same_words(packed[s]["stats"], twin[s]["stats"], (name, s, "stats"))
+        same_words(packed[s]["bits"], np.packbits(twin[s]["bits"], axis=1), (name, s, "packed bits"))
+        same_words(packed[s]["rx_filt"], twin[s]["rx_filt"], (name, s, "rx_filt"))
+        same_words(packed[s]["stats"], twin[s]["stats"], (name, s, "stats"))
     # ... and the twin is not wrong in the same way: its first stream against the oracle
     _compare(bs.oracle_of(oracle, M, mask).demod(streams[0][:bt.nsamp], bs.fmt_of(oracle, fmt)), twin[0], tol=TOL, allow_near_tie_flips=True, M=M)
 
@@ -245,20 +210,20 @@ def test_stream_scalars_after_a_call_without_stats_output(oracle, built_lib, end
         assert h.kernel() == "block"
         r = Batch(h, [u8], rows).run(maxf, want_filt=False, want_stats=want_stats).fetch()[0]
         assert r["untouched"]
-        out.append((r, _scalars(h), _state(h)[0]))
+        out.append((r, scalars(h), _state(h)[0]))
     (r1, sc1, st1), (r2, sc2, st2) = out
     assert r1["nframes"] == r2["nframes"] >= 5 and r1["consumed"] == r2["consumed"]
     assert (r1["nframes"] == bs.SCALAR_MAX_FRAMES and u8.shape[0] - r1["consumed"] > bs.N + bs.Q) if ending == "max_frames reached" \
         else u8.shape[0] - r1["consumed"] < bs.N - bs.Q
-    _same_words(r1["bits"], r2["bits"], "bits")
+    same_words(r1["bits"], r2["bits"], "bits")
     assert r2["stats"].shape == (r1["nframes"], 10) and (r2["stats"].view(np.uint8) == FILL).all()       # no stats asked for, none written
-    _same_words(sc1, sc2, "scalars with and without the stats output")
+    same_words(sc1, sc2, "scalars with and without the stats output")
     # (the rest of the state too, but for word 3, snr_est: a running average over the observable frames -- every frame with a stats output, the
     #  call's last one without, as include/pirip_hip.h says of pirip_stream_state)
     keep = [i for i in range(13) if i != 3]          # (the 13 words of the structure: all the library writes)
-    _same_words(st1[keep], st2[keep], "stream state with and without the stats output")
+    same_words(st1[keep], st2[keep], "stream state with and without the stats output")
     last = r1["stats"][-1]
-    _same_words(sc1[[0, 1, 4, 5, 7]], last[[0, 1, 4, 5, 7]], "scalars against the last stats row")
+    same_words(sc1[[0, 1, 4, 5, 7]], last[[0, 1, 4, 5, 7]], "scalars against the last stats row")
     assert sc1[6] == last[6] and sc1[5] > 1.0
 
 
@@ -282,12 +247,12 @@ def test_sample_loads_at_every_16_byte_residue(oracle, built_lib):
         ref = ref or (got[0], h.get_Sf(0))
         for s in range(8):
             assert got[s]["untouched"]
-            _same_result(got[s], ref[0], ("base", base, "stream", s))
-            _same_words(h.get_Sf(s), ref[1], ("Sf, base", base, "stream", s))
+            same_results(got[s], ref[0], ("base", base, "stream", s))
+            same_words(h.get_Sf(s), ref[1], ("Sf, base", base, "stream", s))
     ro = bs.sweep_oracle(oracle, M, fmt)[bs.OFF_LONG]
     assert (ro["stats"][:, 6] == bs.N + bs.Q).any()
     _compare(ro, ref[0], tol=TOL, M=M)
-    _same_words(ref[1], ro["Sf"], "Sf")
+    same_words(ref[1], ro["Sf"], "Sf")
 
 
 # ---- h ---------------------------------------------------------------------------------------------------------------------------------
@@ -307,10 +272,10 @@ def test_reset_gives_a_created_stream(oracle, built_lib, name):
     h.reset()
     assert h.kernel() == "block" and not h.get_Sf(0).any()
     rb, rf = h.demod_host(B), fresh.demod_host(B)
-    _same_result(rb, rf, (name, "after reset against a new handle"))
+    same_results(rb, rf, (name, "after reset against a new handle"))
     for x, y, what in zip(_state(h), _state(fresh), ("stream state", "Sf")):
-        _same_words(x, y, (name, what))
-    _same_words(_scalars(h), _scalars(fresh), (name, "scalars"))
+        same_words(x, y, (name, what))
+    same_words(scalars(h), scalars(fresh), (name, "scalars"))
     _compare(bs.oracle_of(oracle, M, mask).demod(B, bs.fmt_of(oracle, fmt)), rb, tol=TOL, M=M)       # (B is the noise-free one)
     # a batch of three: A, then reset on another HIP stream, then B with each stream a different 0 / 16 / 33 samples in
     hb, twin = bs.handle_of(pirip_amd, M, fmt, mask, nstreams=3), bs.handle_of(pirip_amd, M, fmt, mask, nstreams=3)
@@ -325,9 +290,9 @@ def test_reset_gives_a_created_stream(oracle, built_lib, name):
     want = Batch(twin, second, rows).run(rows).fetch()
     for s in range(3):
         assert got[s]["nframes"] >= 10 and got[s]["untouched"]
-        _same_result(got[s], want[s], (name, "batch after reset, stream", s))
+        same_results(got[s], want[s], (name, "batch after reset, stream", s))
         for x, y, what in zip(_state(hb, s), _state(twin, s), ("stream state", "Sf")):
-            _same_words(x, y, (name, what, s))
+            same_words(x, y, (name, what, s))
 
 
 # ---- i ---------------------------------------------------------------------------------------------------------------------------------
@@ -344,7 +309,7 @@ def test_burst_mode_pins_nin(oracle, built_lib, M, fmt):
     ro, rh = o.demod(u8, bs.fmt_of(oracle, fmt)), h.demod_host(u8)
     assert ro["nframes"] >= 5 and (ro["stats"][:, 6] == bs.N).all() and (np.abs(ro["stats"][:, 4]) > 0.25).any()
     _compare(ro, rh, tol=TOL, M=M)
-    _same_words(h.get_Sf(0), bs.oracle_Sf(oracle, o), "Sf")
+    same_words(h.get_Sf(0), bs.oracle_Sf(oracle, o), "Sf")
 
 
 def test_estimator_limits_set_on_the_live_handle(oracle, built_lib):
@@ -358,11 +323,11 @@ def test_estimator_limits_set_on_the_live_handle(oracle, built_lib):
     assert h.set_freq_est_limits(*bs.LIMITS) == 0
     assert h.kernel() == "block" and made.kernel() == "block"
     r, rm, rd = h.demod_host(u8), made.demod_host(u8), default.demod_host(u8)
-    _same_result(r, rm, "limits set against limits at create")
-    _same_words(h.get_Sf(0), made.get_Sf(0), "Sf")
+    same_results(r, rm, "limits set against limits at create")
+    same_words(h.get_Sf(0), made.get_Sf(0), "Sf")
     o = bs.oracle_of(oracle, M, est_min=bs.LIMITS[0], est_max=bs.LIMITS[1])
     _compare(o.demod(u8, bs.fmt_of(oracle, fmt)), r, tol=TOL, allow_near_tie_flips=True, M=M)
-    _same_words(h.get_Sf(0), bs.oracle_Sf(oracle, o), "Sf against the oracle")
+    same_words(h.get_Sf(0), bs.oracle_Sf(oracle, o), "Sf against the oracle")
     assert rd["nframes"] == r["nframes"] and not np.array_equal(rd["stats"][:, :2], r["stats"][:, :2])
 
 
@@ -382,10 +347,10 @@ def test_capture_on_a_block_handle_equals_the_read_loop(oracle, built_lib, piece
     assert seq["nframes"] == 25
     cap, reports = _capture(pirip_amd, hc, u8, pieces)
     assert len(reports) == pieces and all(r["segments"] == 1 and r["passes"] == 1 for r in reports), reports
-    _same_result(cap, seq, "capture against the read loop")
+    same_results(cap, seq, "capture against the read loop")
     for x, y, what in zip(_state(hc), _state(hs), ("stream state", "Sf")):
-        _same_words(x, y, what)
-    _same_words(_scalars(hc), _scalars(hs), "scalars")
+        same_words(x, y, what)
+    same_words(scalars(hc), scalars(hs), "scalars")
     _compare(bs.oracle_of(oracle, M, mask).demod(u8, bs.fmt_of(oracle, fmt)), cap, tol=TOL, allow_near_tie_flips=True, M=M)
 
 
@@ -412,4 +377,4 @@ def test_two_block_handles_on_two_hip_streams_at_once(oracle, built_lib):
     for name, h, b, rows, alone, st in jobs:
         for s, (g, w) in enumerate(zip(b.fetch(), alone)):
             assert g["untouched"]
-            _same_result(g, w, (name, "stream", s))
+            same_results(g, w, (name, "stream", s))

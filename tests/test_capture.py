@@ -13,18 +13,16 @@ import numpy as np
 import pytest
 
 import sigutil
+from demodrun import make_handle, make_oracle, resample_at, same_results, stream_state
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+_same = same_results                # (the name tools/fuzz_parity.py and other test modules compare a capture under)
 
 
 def _resample(x, ppm):
     """sample-clock offset by linear interpolation (as test_sample_clock_offset_exercises_nin_feedback does)"""
-    n = x.shape[0]
-    t = np.arange(int(n / (1 + abs(ppm)) - 2)) * (1 + ppm)
-    i0 = np.floor(t).astype(int)
-    fr = (t - i0)[:, None].astype(np.float32)
-    return ((1 - fr) * x[i0] + fr * x[np.minimum(i0 + 1, n - 1)]).astype(np.float32)
+    return resample_at(x, np.arange(int(x.shape[0] / (1 + abs(ppm)) - 2)) * (1 + ppm))
 
 
 def _signal(ob, cfg, nbits, seed, ppm=0.0, ebno_db=None, offset=0, fmt="u8"):
@@ -44,14 +42,13 @@ def _signal(ob, cfg, nbits, seed, ppm=0.0, ebno_db=None, offset=0, fmt="u8"):
 
 
 def _mk(pirip_amd, cfg, fmt, nstreams, mask=0):
-    return pirip_amd.HipDemod(cfg["Fs"], cfg["Rs"], cfg["M"], P=cfg["P"], est_min=cfg["est_min"], est_max=cfg["est_max"], mask=mask,
-                              in_format=fmt, nstreams=nstreams)
+    return make_handle(dict(cfg, mask=mask, fmt=fmt), nstreams)
 
 
 def _state(h):
     """everything pirip_hip_get_stream_state reports for stream slot 0 (struct pirip_stream_state: nin, norm_rx_timing, ppm, snr_est, SNRest,
     EbNodB, v_est, f_est[4], rx_sig_pow, rx_nse_pow -- 13 words) and its smoothed spectrum"""
-    return np.frombuffer(h.stream_state(0), dtype=np.float32), h.get_Sf(0)
+    return stream_state(h, 0), h.get_Sf(0)
 
 
 def _capture(pirip_amd, h, buf, pieces=1, maxf=None):
@@ -78,16 +75,6 @@ def _capture(pirip_amd, h, buf, pieces=1, maxf=None):
     torch.cuda.synchronize()
     return {"nframes": frames, "consumed": start, "bits": bits[:frames].cpu().numpy(), "rx_filt": filt[:frames].cpu().numpy(),
             "stats": stats[:frames].cpu().numpy()}, reports
-
-
-def _same(a, b, what):
-    assert a["nframes"] == b["nframes"] and a["consumed"] == b["consumed"], (what, a["nframes"], b["nframes"], a["consumed"], b["consumed"])
-    assert np.array_equal(a["bits"], b["bits"]), what
-    for k in ("rx_filt", "stats"):
-        x, y = a[k].view(np.uint32), b[k].view(np.uint32)
-        if not np.array_equal(x, y):
-            bad = np.argwhere(x != y)
-            raise AssertionError((what, k, bad[:5].tolist(), a[k][tuple(bad[0])], b[k][tuple(bad[0])]))
 
 
 CASES = [
@@ -122,8 +109,7 @@ def test_capture_equals_the_sequential_read_loop(oracle, built_lib, case, monkey
     assert hs.kernel() == "wave"
     # the sequential loop against the oracle on the first frames (pinned in full elsewhere)
     nchk = min(buf.shape[0], 40 * hs.N)
-    o = oracle.OracleFsk(cfg["Fs"], cfg["Rs"], cfg["M"], P=cfg["P"], est_min=cfg["est_min"], est_max=cfg["est_max"],
-                         tone_spacing=mask if mask else 100, mask=bool(mask))
+    o = make_oracle(oracle, dict(cfg, mask=mask))
     ro = o.demod(buf[:nchk], fmts[fmt][1], want_filt=False)
     if ebno is None or ebno >= 6.0:     # (noisier: near-tie flips between the two float32 evaluation orders are possible, test_gpu_parity counts them)
         assert np.array_equal(seq["bits"][:ro["nframes"] - 1], ro["bits"][:ro["nframes"] - 1])
@@ -131,7 +117,7 @@ def test_capture_equals_the_sequential_read_loop(oracle, built_lib, case, monkey
     monkeypatch.setenv("PIRIP_CAPTURE_SEG_FRAMES", str(segf))
     hc = _mk(pirip_amd, cfg, fmts[fmt][0], slots, mask)
     cap, reps = _capture(pirip_amd, hc, buf, pieces)
-    _same(cap, seq, name)
+    same_results(cap, seq, name)
     sc_s, sf_s = _state(hs)
     sc_c, sf_c = _state(hc)
     assert np.array_equal(sf_s.view(np.uint32), sf_c.view(np.uint32)), name
@@ -152,7 +138,7 @@ def test_capture_equals_the_sequential_read_loop(oracle, built_lib, case, monkey
     monkeypatch.setenv("PIRIP_CAPTURE_SEQUENTIAL", "1")
     hq = _mk(pirip_amd, cfg, fmts[fmt][0], 4, mask)
     capq, repq = _capture(pirip_amd, hq, buf, 1)
-    _same(capq, seq, name + " (sequential route)")
+    same_results(capq, seq, name + " (sequential route)")
     assert repq[0]["segments"] == 1
 
 
@@ -186,7 +172,7 @@ def test_capture_stops_at_the_output_capacity_like_the_read_loop(oracle, built_l
         # ... and both continue identically from where they stopped
         rest_s = hs.demod_host(buf[int(cons[0]):])
         rest_c, _ = _capture(pirip_amd, hc, buf[cap["consumed"]:], 1)
-        _same(rest_c, rest_s, ("after the limit", limit))
+        same_results(rest_c, rest_s, ("after the limit", limit))
 
 
 def test_capture_with_frames_the_demodulator_skips(oracle, built_lib, monkeypatch):
@@ -206,7 +192,7 @@ def test_capture_with_frames_the_demodulator_skips(oracle, built_lib, monkeypatc
     hc = _mk(pirip_amd, cfg, pirip_amd.IN_CF32, 16)
     cap, reps = _capture(pirip_amd, hc, buf, 1)
     assert reps[0]["segments"] >= 3
-    _same(cap, seq, "frames with non-finite samples")
+    same_results(cap, seq, "frames with non-finite samples")
     sc_s, sf_s = _state(hs)
     sc_c, sf_c = _state(hc)
     assert np.array_equal(sc_s.view(np.uint32), sc_c.view(np.uint32)), (sc_s, sc_c)
@@ -245,7 +231,7 @@ def test_capture_on_a_general_kernel_handle_takes_the_sequential_route(oracle, b
     seq = hs.demod_host(buf)
     hc = _mk(pirip_amd, cfg, pirip_amd.IN_CU8_FSKDEMOD, 16)
     cap, reps = _capture(pirip_amd, hc, buf, 1)
-    _same(cap, seq, "general kernel")
+    same_results(cap, seq, "general kernel")
     assert reps[0]["segments"] == 1 and reps[0]["passes"] == 1
 
 
@@ -306,7 +292,7 @@ def test_capture_with_the_band_only_estimator(oracle, built_lib, monkeypatch, eb
     hc = _mk(pirip_amd, cfg, pirip_amd.IN_CU8_FSKDEMOD, 64)
     hc.set_estimator_band_only(True)
     cap, reps = _capture(pirip_amd, hc, buf, 1)
-    _same(cap, seq, "band-only capture")
+    same_results(cap, seq, "band-only capture")
     sc_s, sf_s = _state(hs)
     sc_c, sf_c = _state(hc)
     assert np.array_equal(sf_s[128:160].view(np.uint32), sf_c[128:160].view(np.uint32))

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import chanref
+import sigutil
 
 pytestmark = pytest.mark.gpu
 
@@ -259,13 +260,6 @@ def test_stream_equals_one_shot(built_lib, block_outputs):
     assert torch.equal(nfr2, nfr) and torch.equal(bits2, bits)
 
 
-def _framer(args):
-    p = subprocess.run([os.path.join(BIN, "fsk_ldpc_framer"), "--code", os.path.join(ROOT, "pirip_amd", "data", "standin_256_512_4.code")] + args,
-                       capture_output=True)
-    assert p.returncode == 0, p.stderr
-    return np.frombuffer(p.stdout, dtype=np.uint8)
-
-
 # the deployed FSK_LDPC modem (rtl_fsk -a 40000 -r 1000 --code) on four channels of one 240 kS/s capture
 LDPC_MODEM = dict(Fs=40000, Rs=1000, M=2, P=10, f1=1000, shift=2000, est_min=500, est_max=15000, mask=0)
 LDPC_FS, LDPC_D, LDPC_OFFSETS = 240000, 6, [-90000, -30000, 30001, 90000]
@@ -274,7 +268,7 @@ LDPC_FS, LDPC_D, LDPC_OFFSETS = 240000, 6, [-90000, -30000, 30001, 90000]
 def test_stream_fsk_ldpc_bursts_on_four_channels(built_lib):
     import torch
     import pirip_amd
-    burst = _framer(["-m", "2", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
+    burst = sigutil.run_framer(["-m", "2", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
     gap = np.zeros(40, dtype=np.uint8)
     bits = [np.concatenate([gap[:k * 8 + 8], burst, gap, gap, np.zeros(400, np.uint8)]) for k in range(4)]
     ts_w = LDPC_FS // LDPC_MODEM["Rs"]
@@ -393,7 +387,7 @@ def test_rtl_fsk_channels_cli_equals_python(built_lib, tmp_path, coded):
     import pirip_amd
     if coded:
         mc, Fs, D, offs = LDPC_MODEM, LDPC_FS, LDPC_D, LDPC_OFFSETS
-        burst = _framer(["-m", "2", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
+        burst = sigutil.run_framer(["-m", "2", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
         bits = [np.concatenate([np.zeros(8 * k + 8, np.uint8), burst, np.zeros(480, np.uint8)]) for k in range(4)]
         n_raw = (max(len(b) for b in bits) + 200) * (Fs // mc["Rs"])
         host, _ = _composite(mc, n_raw, seed=2, amps=[20.0, 30.0, 20.0, 25.0], bits=bits, offsets=offs, Fs=Fs)

@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import rangeref as rr
-from test_gpu_parity import RX_FILT_TOL, _compare
+from demodrun import same_words
+from parity import RX_FILT_TOL, _compare
 
 pytestmark = pytest.mark.gpu
 
@@ -21,27 +22,19 @@ def _hip(pirip_amd, sh, nstreams=1):
                               in_format=pirip_amd.IN_CF32, nstreams=nstreams)
 
 
-def _same_words(a, b):
-    """Bit-for-bit equality of float arrays (NaN payloads included) / of integer arrays."""
-    a, b = np.asarray(a), np.asarray(b)
-    if a.dtype.kind == "f":
-        return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
-    return np.array_equal(a, b)
-
-
 def _scaled_equal(rk, r0, k, reg):
     s = np.float32(2.0 ** k)
     assert (rk["nframes"], rk["consumed"]) == (r0["nframes"], r0["consumed"]), k
     assert np.array_equal(rk["bits"], r0["bits"]), k
     for col in (0, 1, 2, 3, 4, 6, 7):                                  # f_est, norm_rx_timing, nin, ppm
-        assert _same_words(rk["stats"][:, col], r0["stats"][:, col]), (k, col)
-    assert _same_words(rk["rx_filt"], r0["rx_filt"] * s), k
-    assert _same_words(rk["stats"][:, 8], r0["stats"][:, 8] * s * s), k
+        same_words(rk["stats"][:, col], r0["stats"][:, col], (k, col))
+    same_words(rk["rx_filt"], r0["rx_filt"] * s, k)
+    same_words(rk["stats"][:, 8], r0["stats"][:, 8] * s * s, k)
     if reg.eps_clean(k):
         silent = reg.first_nse == 0                                    # frames without a noise term keep the bare 1e-12 / Nsym
-        assert _same_words(rk["stats"][:, 5], r0["stats"][:, 5]), k   # SNRest
-        assert _same_words(rk["stats"][~silent, 9], r0["stats"][~silent, 9] * s * s), k
-        assert _same_words(rk["stats"][silent, 9], r0["stats"][silent, 9]), k
+        same_words(rk["stats"][:, 5], r0["stats"][:, 5], k)   # SNRest
+        same_words(rk["stats"][~silent, 9], r0["stats"][~silent, 9] * s * s, k)
+        same_words(rk["stats"][silent, 9], r0["stats"][silent, 9], k)
 
 
 def _compare_nse_own(ro, rh, M):
@@ -130,10 +123,12 @@ def test_scaled_recording_gives_scaled_words_and_keeps_parity(oracle, built_lib,
             if first is None:
                 # no split, but every magnitude is zero: the oracle reports the bare 1e-12 / Nsym as noise power, the kernel 0, in the
                 # same frames; every other word agrees
-                assert not rh["rx_filt"].any() and _same_words(rh["rx_filt"], ro["rx_filt"]) and _same_words(rh["bits"], ro["bits"])
+                assert not rh["rx_filt"].any()
+                same_words(rh["rx_filt"], ro["rx_filt"], (what, k, "rx_filt"))
+                same_words(rh["bits"], ro["bits"], (what, k, "bits"))
                 d = rh["stats"][:, 9] != ro["stats"][:, 9]
                 assert d.any() and (rh["stats"][d, 9] == 0).all() and (ro["stats"][d, 9] == np.float32(1e-12) / np.float32(50)).all()
-                assert _same_words(rh["stats"][:, :9], ro["stats"][:, :9]), (what, k)
+                same_words(rh["stats"][:, :9], ro["stats"][:, :9], (what, k))
             continue
         assert (rh["nframes"], rh["consumed"]) == (ro["nframes"], ro["consumed"]), (what, k)
         if kernel == "exact":
@@ -150,7 +145,7 @@ def test_scaled_recording_gives_scaled_words_and_keeps_parity(oracle, built_lib,
     h.reset()
     rh = h.demod_host(x)
     for f in ("bits", "rx_filt", "stats"):
-        assert _same_words(rh[f], rh0[f]), f
+        same_words(rh[f], rh0[f], f)
 
 
 def test_codec2_shim_fsk_demod_is_scale_invariant(oracle, built_lib):
@@ -306,4 +301,4 @@ def test_streams_at_overflow_and_far_below_leave_their_neighbours_alone(oracle, 
             continue
         alone = run(_hip(pirip_amd, sh, nstreams=1), host[s:s + 1])
         for i, (a, b) in enumerate(zip(batch, alone)):
-            assert _same_words(a[s], b[0]), (s, k, i)
+            same_words(a[s], b[0], (s, k, i))

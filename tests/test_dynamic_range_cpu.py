@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import rangeref as rr
+from parity import oracle_Sf
 
 
 def _ldpc(oracle, M):
@@ -81,7 +82,7 @@ def test_ladder_brackets_every_boundary(oracle, name):
     assert np.isfinite(rr.demod(oracle, sh, rr.scaled(x, hi))["stats"]).all()
     o = rr.oracle_fsk(oracle, sh)
     o.demod(rr.scaled(x, L["X2_overflow"]), oracle.IN_CF32)
-    assert not np.isfinite(_oracle_Sf(oracle, o, sh["Ndft"])).all()
+    assert not np.isfinite(oracle_Sf(oracle, o, sh["Ndft"])).all()
     # the hand-over's sums-only overflow k: the frame power overflows, the soft magnitudes and the timing do not
     ko = rr.sums_overflow_k(oracle, x, sh, reg, x2_finite=False)
     assert ko is not None and ko > hi
@@ -89,9 +90,3 @@ def test_ladder_brackets_every_boundary(oracle, name):
     assert np.isinf(ro["stats"][:, 8]).any() and np.isfinite(ro["rx_filt"]).all() and np.isfinite(ro["stats"][:, 4]).all()
     assert not np.isinf(rr.demod(oracle, sh, rr.scaled(x, ko - 1))["stats"][:, 8]).any()
 
-
-def _oracle_Sf(oracle, o, ndft):
-    import ctypes as C
-    o.l.oracle_fsk_get_Sf.restype = C.c_void_p
-    o.l.oracle_fsk_get_Sf.argtypes = [C.c_void_p]
-    return np.ctypeslib.as_array(C.cast(o.l.oracle_fsk_get_Sf(o.h), C.POINTER(C.c_float)), shape=(ndft,)).copy()

@@ -12,7 +12,8 @@ import pytest
 
 import nsymshapes as ns
 import sigutil
-from parity import RX_FILT_TOL, TIMING_TOL, _compare, _oracle_field_Sf
+from demodrun import host_chunks, same_results, same_words, stream_state
+from parity import RX_FILT_TOL, TIMING_TOL, _compare, oracle_Sf
 
 pytestmark = pytest.mark.gpu
 
@@ -44,37 +45,6 @@ def _handle(r, nstreams=1):
                               in_format=ns.formats(ob, pirip_amd, r)[1], nstreams=nstreams)
 
 
-def _join(parts, consumed):
-    return {"nframes": sum(p["nframes"] for p in parts), "consumed": consumed, "bits": np.concatenate([p["bits"] for p in parts]),
-            "rx_filt": np.concatenate([p["rx_filt"] for p in parts]), "stats": np.concatenate([p["stats"] for p in parts])}
-
-
-def _in_chunks(h, buf, cuts):
-    """the recording in host calls cut at `cuts`, the unconsumed tail carried in front of the next piece as a reader does"""
-    parts, carry, last = [], buf[:0], 0
-    for cpos in list(cuts) + [buf.shape[0]]:
-        piece = np.concatenate([carry, buf[last:cpos]]); last = cpos
-        p = h.demod_host(piece)
-        parts.append(p); carry = piece[p["consumed"]:]
-    return _join(parts, buf.shape[0] - carry.shape[0])
-
-
-def _same_words(a, b, what):
-    assert a["nframes"] == b["nframes"] and a["consumed"] == b["consumed"], (what, a["nframes"], b["nframes"], a["consumed"], b["consumed"])
-    assert np.array_equal(a["bits"], b["bits"]), (what, "bits")
-    for k in ("rx_filt", "stats"):
-        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), (what, k)
-
-
-def _state(h, s=0):
-    """pirip_hip_get_stream_state: nin, norm_rx_timing, ppm, snr_est, SNRest, EbNodB, v_est, f_est[4], rx_sig_pow, rx_nse_pow as 13 words"""
-    return np.frombuffer(h.stream_state(s), dtype=np.uint32)
-
-
-def _oracle_Sf(oracle, o, ndft):
-    return np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(ndft,)).copy()
-
-
 # ---- 1. parity on every row ---------------------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("r", ns.DEVICE_ROWS, ids=lambda r: r.name)
 def test_every_frame_length_row_equals_the_oracle_one_shot_and_in_ragged_chunks(oracle, built_lib, r):
@@ -94,12 +64,12 @@ def test_every_frame_length_row_equals_the_oracle_one_shot_and_in_ragged_chunks(
               f"timing err {np.abs(rh['stats'][:, 4] - ro['stats'][:, 4]).max() if rh['nframes'] == ro['nframes'] else 'n/a'}")
         nfl = _compare(ro, rh, tol=_tol(r), allow_near_tie_flips=ebno is not None, M=r.M)
         # the smoothed spectrum after the last frame: one FFT more or fewer in any frame shows here even where the peaks stay put
-        assert np.array_equal(Sf.view(np.uint32), _oracle_Sf(oracle, o, ns.dims(r)["Ndft"]).view(np.uint32)), "Sf differs"
+        same_words(Sf, oracle_Sf(oracle, o, ns.dims(r)["Ndft"]), "Sf")
         h = _handle(r)
-        rc = _in_chunks(h, buf, [n // 3 + 17, (2 * n) // 3 + 5])
+        rc = host_chunks(h, buf, [n // 3 + 17, (2 * n) // 3 + 5])
         h.close()
         assert _compare(ro, rc, tol=_tol(r), allow_near_tie_flips=ebno is not None, M=r.M) == nfl
-        _same_words(rc, rh, "chunked against one-shot")
+        same_results(rc, rh, "chunked against one-shot")
 
 
 # ---- 2. frames where no FFT fits ----------------------------------------------------------------------------------------------------
@@ -143,7 +113,7 @@ def test_neighbours_of_the_compiled_length_leave_the_specialised_instances(oracl
     hg = mk(Nsym)
     rg = hg.demod_host(u8)
     hg.close()
-    _same_words(rh, rg, "PIRIP_KERNEL=general")
+    same_results(rh, rg, "PIRIP_KERNEL=general")
     o = oracle.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], Nsym=Nsym, est_min=c["est_min"], est_max=c["est_max"])
     ro = o.demod(u8, oracle.IN_CU8_FSKDEMOD)
     assert ro["nframes"] >= 20
@@ -225,7 +195,7 @@ def test_stop_after_three_frames_resume_and_reset(oracle, built_lib, name):
     nsamp, bps = buf.shape[0], buf.itemsize * 2
     dev = torch.from_numpy(buf).cuda()
     h = _handle(r)
-    created = _state(h).copy()
+    created = stream_state(h).copy()
     maxf, nb, nf_ = h.max_frames_for(nsamp), h.Nbits, r.M * r.Nsym
     st = torch.cuda.current_stream().cuda_stream
 
@@ -242,20 +212,21 @@ def test_stop_after_three_frames_resume_and_reset(oracle, built_lib, name):
 
     a = call(dev.data_ptr(), nsamp, 3)
     assert a["nframes"] == 3 and a["consumed"] == d["N"] + int(ro["stats"][:2, 6].sum())
-    s3 = _state(h)
+    s3 = stream_state(h)
     sf = s3.view(np.float32)
     assert int(s3.view(np.int32)[0]) == int(ro["stats"][2, 6])                                  # nin the fourth frame will take
     assert np.array_equal(sf[7:11], ro["stats"][2, :4])                                          # tone estimates
     assert abs(sf[1] - ro["stats"][2, 4]) < TIMING_TOL * max(1.0, _tol(r) / RX_FILT_TOL)
     assert np.array_equal(s3[[1, 2, 4, 11, 12]], a["stats"][2, [4, 7, 5, 8, 9]].view(np.uint32))   # ... and the third row's own words
     b = call(dev.data_ptr() + a["consumed"] * bps, nsamp - a["consumed"], maxf)
-    both = _join([a, b], a["consumed"] + b["consumed"])
+    both = {"nframes": a["nframes"] + b["nframes"], "consumed": a["consumed"] + b["consumed"],
+            **{k: np.concatenate([a[k], b[k]]) for k in ("bits", "rx_filt", "stats")}}
     _compare(ro, both, tol=_tol(r), M=r.M)
     h.reset()
     torch.cuda.synchronize()
-    assert np.array_equal(_state(h), created) and not h.get_Sf(0).any()
+    assert np.array_equal(stream_state(h), created) and not h.get_Sf(0).any()
     one = call(dev.data_ptr(), nsamp, maxf)
-    _same_words(both, one, "stopped + resumed against one shot after reset")
+    same_results(both, one, "stopped + resumed against one shot after reset")
     h.close()
 
 
@@ -276,7 +247,7 @@ def test_exact_kernel_is_the_oracle_bit_for_bit_at_other_frame_lengths(oracle, b
     if packed:
         h.set_bit_packing(True)
     n = buf.shape[0]
-    rh = _in_chunks(h, buf, [n // 3 + 17, (2 * n) // 3 + 5])
+    rh = host_chunks(h, buf, [n // 3 + 17, (2 * n) // 3 + 5])
     h.close()
     assert rh["nframes"] == ro["nframes"] >= 14 and rh["consumed"] == ro["consumed"]
     if name not in ns.DEGENERATE:
@@ -307,9 +278,9 @@ def test_eye_diagram_and_spectrum_of_short_frames(oracle, built_lib, name):
     assert eo_raw.max() > 0 and np.abs(eh_raw - eo_raw).max() <= RX_FILT_TOL * eo_raw.max()
     eo, eh = o.eye(), h.eye()
     assert eh.max() == 1.0 and np.abs(eh - eo).max() <= 2 * RX_FILT_TOL
-    Sf_o = _oracle_Sf(oracle, o, ns.dims(r)["Ndft"])
+    Sf_o = oracle_Sf(oracle, o, ns.dims(r)["Ndft"])
     assert (Sf_o.any()) == (name not in ns.DEGENERATE)
-    assert np.array_equal(h.get_Sf(0).view(np.uint32), Sf_o.view(np.uint32))
+    same_words(h.get_Sf(0), Sf_o, "Sf")
     h.close()
 
 

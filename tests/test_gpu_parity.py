@@ -10,7 +10,8 @@ import numpy as np
 import pytest
 
 import sigutil
-from parity import RX_FILT_TOL, SNR_TOL, TIMING_TOL, _compare, _oracle_field_Sf, _pair    # noqa: F401 (tests and tools read them from this module too)
+from demodrun import host_chunks
+from parity import RX_FILT_TOL, SNR_TOL, TIMING_TOL, _compare, _oracle_field_Sf, _pair, oracle_Sf    # noqa: F401 (tests and tools read them from this module too)
 
 pytestmark = pytest.mark.gpu
 
@@ -82,8 +83,7 @@ def test_cfg1_600k_bit_vector_bit_exact(oracle, built_lib, kernel_choice):
     res = oracle.put_test_bits(rh["bits"], packet_pass=5990)
     assert res["errors"] == 0 and res["pass"], res
     # the smoothed spectrum after 12000 frames x 8 FFTs is bit-identical (exact FFT path)
-    import ctypes as C
-    Sf_o = np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(256,)).copy()
+    Sf_o = oracle_Sf(oracle, o)
     assert np.array_equal(h.get_Sf(0), Sf_o)
 
 
@@ -94,7 +94,6 @@ def test_estimator_root_tiers_silence_signal_and_denormal_magnitudes(oracle, bui
     127 to exactly 0), sqrtf for anything else (magnitudes whose squares are denormal). A stream that is silent, then carries a signal, then is
     silent again -- frames of both kinds and frames that straddle the edges -- and a complex-float stream scaled to 1e-17 (|X|^2 ~ 1e-30: normal, below 2^-96) walk all three:
     Sf bit for bit, tone estimates, frame and sample counts exact, as everywhere else."""
-    import ctypes as C
     import pirip_amd
     if shape == "block_u8":
         c = dict(Fs=240000, Rs=1000, M=2, P=15, f1=11000, shift=2000, est_min=500, est_max=119000)
@@ -124,7 +123,7 @@ def test_estimator_root_tiers_silence_signal_and_denormal_magnitudes(oracle, bui
     assert rh["nframes"] == ro["nframes"] and rh["consumed"] == ro["consumed"]
     assert np.array_equal(rh["stats"][:, :4], ro["stats"][:, :4]), "tone estimates differ"
     assert np.array_equal(rh["stats"][:, 6], ro["stats"][:, 6]), "nin sequence differs"
-    Sf_o = np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(ndft,)).copy()
+    Sf_o = oracle_Sf(oracle, o, ndft)
     assert np.array_equal(h.get_Sf(0), Sf_o)
     if shape != "wave_f32_tiny":
         assert np.array_equal(rh["bits"], ro["bits"])
@@ -164,16 +163,10 @@ def test_chunked_streaming_equals_one_shot(oracle, built_lib, kernel_choice):
     o, h = _pair(oracle, c, 0, 0)
     ro = o.demod(u8, oracle.IN_CU8_FSKDEMOD)
     rng = np.random.default_rng(0)
-    pos, carry = 0, np.zeros((0, 2), dtype=np.uint8)
-    bits, filt, stats = [], [], []
-    while pos < u8.shape[0]:
-        n = int(rng.integers(1, 5000))
-        buf = np.concatenate([carry, u8[pos:pos + n]]); pos += n
-        r = h.demod_host(buf)
-        bits.append(r["bits"]); filt.append(r["rx_filt"]); stats.append(r["stats"])
-        carry = buf[r["consumed"]:]
-    rh = {"nframes": sum(len(b) for b in bits), "consumed": u8.shape[0] - carry.shape[0],
-          "bits": np.concatenate(bits), "rx_filt": np.concatenate(filt), "stats": np.concatenate(stats)}
+    cuts = [0]
+    while cuts[-1] < u8.shape[0]:
+        cuts.append(cuts[-1] + int(rng.integers(1, 5000)))
+    rh = host_chunks(h, u8, cuts[1:-1])
     _compare(ro, rh)
 
 
@@ -445,7 +438,6 @@ def test_wave_instances_for_rtl_fsk_shapes_and_mask_estimator(oracle, built_lib,
     (P = 6 / 10), 4-FSK at Ts = 40 (s16 behind the decimator, f32 inside rtl_fsk) and the `--mask` comb estimator on all of
     them (README.md:239-297). The handle must be on the wave kernel; clean, noisy (near-tie flips counted) and
     sample-clock-offset inputs against the oracle, the smoothed spectrum bit-identical."""
-    import ctypes as C
     import pirip_amd
     Fs, Rs, M, P, fmtname, mask, f1, shift, est_max = shape
     c = dict(Fs=Fs, Rs=Rs, M=M, P=P, f1=f1, shift=shift, est_min=500, est_max=est_max)
@@ -465,7 +457,7 @@ def test_wave_instances_for_rtl_fsk_shapes_and_mask_estimator(oracle, built_lib,
     ro = o.demod(conv(x), fmt_o); rh = h.demod_host(conv(x))
     assert ro["nframes"] >= 120
     _compare(ro, rh)
-    Sf_o = np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(Ndft,)).copy()
+    Sf_o = oracle_Sf(oracle, o, Ndft)
     assert np.array_equal(h.get_Sf(0), Sf_o)
     y = sigutil.add_awgn(x, 10.0 if M == 4 else 9.0, c, rng)
     o, h = _pair(oracle, c, fmt_o, fmt_h, mask=mask)
@@ -551,8 +543,7 @@ def test_ts40_ndft512_wave_instances(oracle, built_lib, kernel_choice, fmtname, 
     assert ro["nframes"] >= 115
     _compare(ro, rh)
     # the smoothed spectrum after ~700 512-point FFTs is bit-identical (kiss_fft's 4,4,4,4,2 dataflow across the wave)
-    import ctypes as C
-    Sf_o = np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(512,)).copy()
+    Sf_o = oracle_Sf(oracle, o, 512)
     assert np.array_equal(h.get_Sf(0), Sf_o)
     y = sigutil.add_awgn(x, 9.0, c, rng)
     o, h = _pair(oracle, c, fmt_o, fmt_h)
@@ -1450,16 +1441,10 @@ def test_block_instance_serves_rtl_fsk_r1000_and_carries_state(oracle, built_lib
     rz, oz = hz.demod_host(z), mk().demod(z, oracle.IN_CU8_CSDR)
     assert rz["nframes"] == oz["nframes"] == 3 and np.array_equal(rz["bits"], oz["bits"]) and np.array_equal(rz["stats"][:, :4], oz["stats"][:, :4])
     h2 = pirip_amd.HipDemod(Fs, Rs, M, P=P, est_min=c["est_min"], est_max=c["est_max"], mask=mask, in_format=pirip_amd.IN_CU8_CSDR, nstreams=1)
-    pos, carry = 0, np.zeros((0, 2), dtype=np.uint8)
-    bits_l, filt_l, stats_l = [], [], []
-    while pos < u8.shape[0]:
-        n = int(rng.integers(1, 40000))
-        buf = np.concatenate([carry, u8[pos:pos + n]]); pos += n
-        r = h2.demod_host(buf)
-        bits_l.append(r["bits"]); filt_l.append(r["rx_filt"]); stats_l.append(r["stats"])
-        carry = buf[r["consumed"]:]
-    rh = {"nframes": sum(len(b) for b in bits_l), "consumed": u8.shape[0] - carry.shape[0], "bits": np.concatenate(bits_l),
-          "rx_filt": np.concatenate(filt_l), "stats": np.concatenate(stats_l)}
+    cuts = [0]
+    while cuts[-1] < u8.shape[0]:
+        cuts.append(cuts[-1] + int(rng.integers(1, 40000)))
+    rh = host_chunks(h2, u8, cuts[1:-1])
     _compare(ro, rh, tol=tol, allow_near_tie_flips=True, M=M)
     # a batch: three streams at a stride that is only sample-aligned, stopped after 7 frames and resumed
     nsamp = min(x.shape[0] for x in streams)
@@ -1671,7 +1656,6 @@ def test_band_only_estimator_changes_no_output(oracle, built_lib, fmt):
     edge of the search range, handed over in uneven pieces: every output word (bits, soft magnitudes, all stats columns,
     frame / sample counts) is IDENTICAL, Sf inside the band is bit-identical (and equal to the oracle's), Sf outside the band is
     not maintained; a search range that leaves the band is refused, one inside it is honoured like the full estimator honours it."""
-    import ctypes as C
     import pirip_amd
     c = dict(sigutil.CFG1)
     fo, fh = (oracle.IN_CU8_FSKDEMOD, pirip_amd.IN_CU8_FSKDEMOD) if fmt == "fskdemod" else (oracle.IN_CU8_CSDR, pirip_amd.IN_CU8_CSDR)
@@ -1704,7 +1688,7 @@ def test_band_only_estimator_changes_no_output(oracle, built_lib, fmt):
         if k == 1:
             o = oracle.OracleFsk(c["Fs"], c["Rs"], 2, P=24, est_min=c["est_min"], est_max=c["est_max"])
             ro = o.demod(u8, fo)
-            Sf_o = np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(256,)).copy()
+            Sf_o = oracle_Sf(oracle, o)
             assert ro["nframes"] == sum(r["nframes"] for r in rb)
             assert np.array_equal(Sf_b[128:160], Sf_o[128:160])
             assert np.array_equal(np.concatenate([r["stats"][:, :4] for r in rb]), ro["stats"][:, :4])
@@ -1793,8 +1777,8 @@ def test_recalled_constant_at_its_alternative_value_hip_equals_oracle(oracle, bu
     # the field does something: the oracle at the alternative differs from the oracle at the default somewhere it can be seen
     r0 = o0.demod(buf, fmt_o)
     n = min(r0["nframes"], ro["nframes"])
-    Sf_a = np.ctypeslib.as_array(__import__("ctypes").cast(_oracle_field_Sf(oracle, o), __import__("ctypes").POINTER(__import__("ctypes").c_float)), shape=(h.info.Ndft,)).copy()
-    Sf_0 = np.ctypeslib.as_array(__import__("ctypes").cast(_oracle_field_Sf(oracle, o0), __import__("ctypes").POINTER(__import__("ctypes").c_float)), shape=(h0.info.Ndft,)).copy()
+    Sf_a = oracle_Sf(oracle, o, h.info.Ndft)
+    Sf_0 = oracle_Sf(oracle, o0, h0.info.Ndft)
     differs = (ro["nframes"] != r0["nframes"] or Sf_a.shape != Sf_0.shape or not np.array_equal(Sf_a, Sf_0) or
                not np.array_equal(ro["rx_filt"][:n], r0["rx_filt"][:n]) or not np.array_equal(ro["stats"][:n], r0["stats"][:n]))
     assert differs, field

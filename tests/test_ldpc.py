@@ -21,12 +21,6 @@ CODE = os.path.join(ROOT, "pirip_amd", "data", "standin_256_512_4.code")
 RX_SYNC, RX_BITS, RX_BIT_ERRORS = 2, 4, 8
 
 
-def _framer(args, stdin=b""):
-    p = subprocess.run([os.path.join(BIN, "fsk_ldpc_framer"), "--code", CODE] + args, input=stdin, capture_output=True)
-    assert p.returncode == 0, p.stderr
-    return np.frombuffer(p.stdout, dtype=np.uint8)
-
-
 def _bursts(ob, cfg, M, bursts, ebno_db, seed, silence=4000, amp=14.0):
     """bursts: list of bit arrays (framer output, preamble included). Returns u8 IQ with noise-only gaps, and sigma."""
     rng = np.random.default_rng(seed)
@@ -55,7 +49,7 @@ def test_code_file_framer_crc_and_parity_checks(oracle, built_lib):
     # public known-answer: CRC-16/CCITT-FALSE("123456789") = 0x29B1
     assert o.crc16(np.frombuffer(b"123456789", dtype=np.uint8)) == 0x29B1
     # test-frame mode of the Tx (rpitx_fsk.cpp:366-421): 2 bursts x 3 frames, source byte 0x5 and sequence numbers
-    bits = _framer(["--testframes", "3", "--bursts", "2", "--source", "0x5", "--seq", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["--testframes", "3", "--bursts", "2", "--source", "0x5", "--seq", "/dev/zero", "-"])
     pre, bpf = 50, 32 + 512
     assert bits.size == 2 * (pre + 3 * bpf)
     assert np.array_equal(bits[:8], [0, 0, 0, 1, 1, 0, 1, 1])        # preamble cycles symbols 0,1,2,3 (rpitx_fsk.cpp:329-335)
@@ -75,7 +69,7 @@ def test_code_file_framer_crc_and_parity_checks(oracle, built_lib):
     rng = np.random.default_rng(1)
     pay = rng.integers(0, 256, (3, 32)).astype(np.uint8)
     rec = b"".join(bytes([bc]) + pay[i].tobytes() for i, bc in enumerate([1, 0, 0])) + bytes([2]) + bytes(32)
-    bits2 = _framer(["--packed", "-", "-"], stdin=rec)
+    bits2 = sigutil.run_framer(["--packed", "-", "-"], stdin=rec)
     assert bits2.size == pre + 3 * bpf
     for f in range(3):
         by = np.packbits(bits2[pre + f * bpf + 32:][:256])
@@ -87,7 +81,7 @@ def test_oracle_loopback_decodes_at_eight_percent_raw_ber(oracle, built_lib):
     FSK_LDPC rx: every frame of both bursts decodes with 0 coded errors, SYNC drops between bursts."""
     code = oracle.parse_code_file(CODE)
     c = dict(sigutil.CFG1, P=6)
-    bits = _framer(["--testframes", "3", "--bursts", "1", "--seq", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["--testframes", "3", "--bursts", "1", "--seq", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, 2, [bits, bits], ebno_db=5.6, seed=3)
     dem = oracle.OracleFsk(c["Fs"], c["Rs"], 2, P=6, est_min=500, est_max=25000)
     r = dem.demod(u8, oracle.IN_CU8_CSDR)
@@ -179,7 +173,7 @@ def test_gpu_receiver_records_equal_oracle_on_the_same_soft_decisions(oracle, bu
     monkeypatch.setenv("PIRIP_LDPC_DECODER", decoder)
     code = oracle.parse_code_file(CODE)
     c = dict(sigutil.CFG1 if M == 2 else sigutil.CFG4, P=6 if M == 2 else 8)
-    bits = _framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x2", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x2", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits[: (50 * M // 2) + 544], bits], ebno_db=ebno, seed=5 + M)
     dem = pirip_amd.HipDemod(c["Fs"], c["Rs"], M, P=c["P"], est_min=500, est_max=c["est_max"], in_format=pirip_amd.IN_CU8_CSDR, nstreams=1)
     r = dem.demod_host(u8)
@@ -211,8 +205,8 @@ def test_rtl_fsk_code_records_drive_a_frame_repeater(oracle, built_lib):
     at ~8 % raw BER, frames from the filtered source address are dropped, -v prints the reference's columns; without -b
     the payload bytes alone come out (README.md:297)."""
     c = dict(sigutil.CFG1, P=6)
-    b_a = _framer(["--testframes", "3", "--seq", "--source", "0x1", "/dev/zero", "-"])
-    b_b = _framer(["--testframes", "2", "--seq", "--source", "0x2", "/dev/zero", "-"])
+    b_a = sigutil.run_framer(["--testframes", "3", "--seq", "--source", "0x1", "/dev/zero", "-"])
+    b_b = sigutil.run_framer(["--testframes", "2", "--seq", "--source", "0x2", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, 2, [b_a, b_b], ebno_db=5.6, seed=11)
     exe = os.path.join(BIN, "rtl_fsk")
     env = dict(os.environ, PIRIP_IQ_FILE="/dev/stdin", PIRIP_CODE_DIR=os.path.join(ROOT, "pirip_amd", "data"))
@@ -266,7 +260,7 @@ def test_ldpc_batch_of_streams_on_device(oracle, built_lib):
     B = 5
     streams, bits_tx = [], []
     for s in range(B):
-        b = _framer(["--testframes", str(1 + s % 3), "--seq", "--source", hex(s + 1), "/dev/zero", "-"])
+        b = sigutil.run_framer(["--testframes", str(1 + s % 3), "--seq", "--source", hex(s + 1), "/dev/zero", "-"])
         bits_tx.append(b)
         streams.append(_bursts(oracle, c, 2, [b], ebno_db=9.0, seed=20 + s))
     nsamp = min(len(x) for x in streams)
@@ -305,7 +299,7 @@ def test_ldpc_batches_with_ragged_call_counts_carry_state_like_the_oracle(oracle
     code = oracle.parse_code_file(CODE)
     c = dict(sigutil.CFG4, P=8)
     M, per = 4, 200
-    bits = _framer(["-m", "4", "--testframes", "4", "--bursts", "1", "--seq", "--source", "0x3", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", "4", "--testframes", "4", "--bursts", "1", "--seq", "--source", "0x3", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits, bits, bits], ebno_db=6.0, seed=31)
     dem = pirip_amd.HipDemod(c["Fs"], c["Rs"], M, P=8, est_min=500, est_max=c["est_max"], in_format=pirip_amd.IN_CU8_CSDR, nstreams=1)
     filt = dem.demod_host(u8)["rx_filt"].reshape(-1, per)
@@ -364,7 +358,7 @@ def test_unique_word_search_under_awkward_call_sizes(oracle, built_lib, M, Nsym)
     import pirip_amd
     code = oracle.parse_code_file(CODE)
     Nbits = Nsym * (1 if M == 2 else 2)
-    bits = _framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
     rng = np.random.default_rng(100 * M + Nsym)
     lead = rng.integers(0, 2, 977, dtype=np.uint8)
     allbits = np.concatenate([lead, np.frombuffer(bits, dtype=np.uint8), rng.integers(0, 2, 1500, dtype=np.uint8)])
@@ -477,7 +471,7 @@ def test_fused_demod_to_ldpc_chain_equals_oracle_on_the_same_magnitudes(oracle, 
         "cf32": (pirip_amd.IN_CF32, lambda x: np.ascontiguousarray(x * np.float32(0.37)), 8),
         "cf32tiny": (pirip_amd.IN_CF32, lambda x: np.ascontiguousarray(x * np.float32(1e-17)), 8),
     }[fmtname]
-    bits = _framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
     rng = np.random.default_rng(77 + P + M)
     gap = 40 * Ts
     segs = [np.zeros((gap, 2), dtype=np.float32)]
@@ -565,7 +559,7 @@ def test_freedv_api_c_program_records_equal_rtl_fsk_and_the_oracle_chain(oracle,
                            "-Wl,-rpath," + libdir, "-lm"])
     code = oracle.parse_code_file(CODE)
     c = dict(sigutil.CFG1 if M == 2 else sigutil.CFG4, P=6)                 # Ts = 24 -> P = 6: the FSK_LDPC oversample rule
-    bits = _framer(["-m", str(M), "--testframes", "4", "--bursts", "1", "--seq", "--source", "0x3", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", str(M), "--testframes", "4", "--bursts", "1", "--seq", "--source", "0x3", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits], ebno_db=ebno, seed=90 + M)
     lo, hi = 5000, c["est_max"]
     p = subprocess.run([exe, CODE, str(M), "240000", "10000", str(lo), str(hi), "v"], input=u8.tobytes(), capture_output=True)
@@ -641,7 +635,7 @@ def test_independent_receiver_agrees_with_the_mirror_oracle(oracle, built_lib, M
     tolerance, every frame delivered by one delivered by the other with the same bytes, iteration counts within one."""
     code = oracle.parse_code_file(CODE)
     c = dict(sigutil.CFG1 if M == 2 else sigutil.CFG4, P=6 if M == 2 else 8)
-    bits = _framer(["-m", str(M), "--testframes", "5", "--bursts", "1", "--seq", "--source", "0x2", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", str(M), "--testframes", "5", "--bursts", "1", "--seq", "--source", "0x2", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits], ebno_db=ebno, seed=40 + M)
     r = oracle.OracleFsk(c["Fs"], c["Rs"], M, P=c["P"], est_min=500, est_max=c["est_max"]).demod(u8, oracle.IN_CU8_CSDR)
     mir, ind = oracle.OracleLdpc(code, M, llr_map=llr_map), oracle.IndepLdpc(code, M, mode=3 if llr_map == "upstream" else 1)
@@ -667,7 +661,7 @@ def test_gpu_receiver_against_the_independent_float32_receiver(oracle, built_lib
     import pirip_amd
     code = oracle.parse_code_file(CODE)
     c = dict(sigutil.CFG1 if M == 2 else sigutil.CFG4, P=6 if M == 2 else 8)
-    bits = _framer(["-m", str(M), "--testframes", "5", "--bursts", "1", "--seq", "--source", "0x2", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", str(M), "--testframes", "5", "--bursts", "1", "--seq", "--source", "0x2", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits, bits], ebno_db=ebno, seed=50 + M)
     dem = pirip_amd.HipDemod(c["Fs"], c["Rs"], M, P=c["P"], est_min=500, est_max=c["est_max"], in_format=pirip_amd.IN_CU8_CSDR, nstreams=1)
     filt = dem.demod_host(u8)["rx_filt"]
@@ -697,7 +691,7 @@ def test_chain_in_groups_on_prioritised_streams_writes_the_same_records(oracle, 
     import pirip_amd
     c = dict(sigutil.CFG4, P=8)
     M = 4
-    bits = _framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x5", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x5", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits, bits], ebno_db=6.5, seed=41)
     B, nsamp = 5, 2 * ((u8.shape[0] - 40) // 4)
     host = np.stack([u8[3 * s: 3 * s + 2 * nsamp] for s in range(B)])                     # every channel its own start offset
@@ -735,7 +729,7 @@ def test_chain_split_into_two_stream_ranges_writes_the_same_records(oracle, buil
     import pirip_amd
     c = dict(sigutil.CFG4, P=8)
     M, B = 4, 7
-    bits = _framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x6", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x6", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits, bits], ebno_db=6.5, seed=43)
     nsamp = 2 * ((u8.shape[0] - 60) // 4)
     host = np.stack([u8[5 * s: 5 * s + 2 * nsamp] for s in range(B)])
@@ -788,7 +782,7 @@ def test_chain_split_joins_the_callers_stream_when_a_range_fails(oracle, built_l
     import pirip_amd
     c = dict(sigutil.CFG4, P=8)
     M, B = 4, 7
-    bits = _framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x7", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x7", "/dev/zero", "-"])
     u8 = _bursts(oracle, c, M, [bits, bits], ebno_db=6.5, seed=47)
     nsamp = (u8.shape[0] - 60) // 2
     host = np.stack([u8[5 * s: 5 * s + nsamp] for s in range(B)])
@@ -836,7 +830,7 @@ def test_two_chain_receivers_of_4096_streams_on_two_hip_streams_concurrently(ora
     pairs = []
     data = []
     for k, (seed, ebno) in enumerate(((51, 6.0), (53, 4.5))):
-        bits = _framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", hex(8 + k), "/dev/zero", "-"])
+        bits = sigutil.run_framer(["-m", "4", "--testframes", "3", "--bursts", "1", "--seq", "--source", hex(8 + k), "/dev/zero", "-"])
         u8 = _bursts(oracle, c, M, [bits, bits], ebno_db=ebno, seed=seed)
         nsamp = u8.shape[0] - 64
         d = torch.from_numpy(u8).cuda()

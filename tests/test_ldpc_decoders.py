@@ -134,7 +134,7 @@ def test_generic_decoder_records(oracle, built_lib, monkeypatch):
     import test_ldpc as tl
     code = oracle.parse_code_file(CODE)
     c = dict(sigutil.CFG1, P=6)
-    bits = tl._framer(["--testframes", "4", "--bursts", "1", "--seq", "--source", "0x6", "/dev/zero", "-"])
+    bits = sigutil.run_framer(["--testframes", "4", "--bursts", "1", "--seq", "--source", "0x6", "/dev/zero", "-"])
     u8 = tl._bursts(oracle, c, 2, [bits, bits], ebno_db=6.0, seed=61)
     dem = pirip_amd.HipDemod(c["Fs"], c["Rs"], 2, P=6, est_min=500, est_max=c["est_max"], in_format=pirip_amd.IN_CU8_CSDR, nstreams=1)
     filt = dem.demod_host(u8)["rx_filt"]

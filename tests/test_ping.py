@@ -16,6 +16,7 @@ import pytest
 import muxshapes as ms
 import pingref
 import rptref
+import sigutil
 
 pytestmark = pytest.mark.gpu
 
@@ -24,19 +25,6 @@ BAD_ARG, UNSUPPORTED = -1, -6
 LOOP_S, LOOP_GAP, LOOP_CALLS = 100, 64, 90
 ROUTE = [1, 0, 3, 2]
 FIRST = [2, 3, 4, 5]
-
-
-def _hip():
-    """the HIP runtime this process has loaded (device-to-device copies out of the handle's rows)"""
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    rt = C.CDLL(path)
-    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    return rt
-
-
-def _d2d(rt, dst, src, n):
-    assert rt.hipMemcpyAsync(dst, src, n, 3, None) == 0
 
 
 def _want():
@@ -173,7 +161,7 @@ def test_scheduler_equals_the_model_and_a_host_driven_transmitter(built_lib, nam
     burst = pingref.burst_records(_want(), 3, 1, True)
     offered, m = pingref.run_schedule(s, burst)
     K, blk, rl = s["calls"], block * 2, 1 + pingref.KB
-    rt = _hip()
+    rt = sigutil.hip_runtime()
     p_rec, stride, p_n = ping.offered()
     assert stride == 4 * rl
     out = torch.full((K * blk + 64,), CANARY, dtype=torch.uint8, device="cuda")
@@ -183,8 +171,8 @@ def test_scheduler_equals_the_model_and_a_host_driven_transmitter(built_lib, nam
     for n in range(K):
         ping.push_records(none[0], none[1], none[2], none[3], out=out.data_ptr() + 32 + n * blk, out_stride=blk, max_calls=0, status_stride=0,
                           payload_stride=0, info_stride=0, stats_stride=0)
-        _d2d(rt, off[n].data_ptr(), p_rec, 4 * stride)
-        _d2d(rt, cnt[n].data_ptr(), p_n, 4 * 4)
+        sigutil.d2d(rt, off[n].data_ptr(), p_rec, 4 * stride)
+        sigutil.d2d(rt, cnt[n].data_ptr(), p_n, 4 * 4)
     torch.cuda.synchronize()
     assert (out[:32] == CANARY).all() and (out[32 + K * blk:] == CANARY).all()
     off, cnt = off.cpu().numpy(), cnt.cpu().numpy()
@@ -285,7 +273,7 @@ def _run_loop(term, rep, tbits=None, K=LOOP_CALLS):
     """the two handles step block by block, each fed the other's previous output (silence first) -> dict of the terminal's and the
     repeater's blocks and copies of the terminal's records() of every call"""
     import torch
-    rt = _hip()
+    rt = sigutil.hip_runtime()
     blk = term.block * 2
     R, kb = term.ping.rx_rows, pingref.KB
     silence = torch.full((blk,), 128, dtype=torch.uint8, device="cuda")
@@ -303,11 +291,11 @@ def _run_loop(term, rep, tbits=None, K=LOOP_CALLS):
         if tbits is not None:
             tbits.push_records(r["status"], r["payload"], r["info"], ncalls=r["nframes"], max_calls=R, status_stride=R, payload_stride=R * kb,
                                info_stride=R * 10)
-        _d2d(rt, st[k].data_ptr(), r["status"], 4 * R)
-        _d2d(rt, pl[k].data_ptr(), r["payload"], 4 * R * kb)
-        _d2d(rt, info[k].data_ptr(), r["info"], 4 * R * 10 * 4)
-        _d2d(rt, stats[k].data_ptr(), r["stats"], 4 * R * 10 * 4)
-        _d2d(rt, nfr[k].data_ptr(), r["nframes"], 4 * 4)
+        sigutil.d2d(rt, st[k].data_ptr(), r["status"], 4 * R)
+        sigutil.d2d(rt, pl[k].data_ptr(), r["payload"], 4 * R * kb)
+        sigutil.d2d(rt, info[k].data_ptr(), r["info"], 4 * R * 10 * 4)
+        sigutil.d2d(rt, stats[k].data_ptr(), r["stats"], 4 * R * 10 * 4)
+        sigutil.d2d(rt, nfr[k].data_ptr(), r["nframes"], 4 * 4)
         rep.rpt.push(t_out[k - 1] if k else silence, blk, r_out[k], blk)
     torch.cuda.synchronize()
     return dict(t_out=t_out, r_out=r_out, seen=[x.cpu().numpy() for x in (st, pl, info, stats, nfr)], logs=[term.ping.log(c) for c in range(4)],

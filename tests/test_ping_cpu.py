@@ -1,24 +1,14 @@
 """include/pirip_hip.h section N without a GPU: the host model tests/pingref.py that tests/test_ping.py holds the device to. Its burst
 records are what fsk_ldpc_framer --testframes sends, and its tables reach the corners they claim."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
-import muxshapes as ms
 import pingref
 import rptref
+import sigutil
 
-FRAMER = os.path.join(ms.BIN, "fsk_ldpc_framer")
 MODEM = {2: (50, 544), 4: (100, 272)}         # preamble and frame of the stand-in code, in symbols
 GAP = 64
-
-
-def _framer(args, stdin=b""):
-    p = subprocess.run([FRAMER, "--code", ms.CODE] + args, input=stdin, capture_output=True)
-    assert p.returncode == 0, p.stderr.decode()
-    return np.frombuffer(p.stdout, dtype=np.uint8)
 
 
 @pytest.mark.parametrize("M", [2, 4])
@@ -29,8 +19,8 @@ def test_burst_records_are_the_framers_test_frames(built_lib, M, frames, seq):
     source = 0xA7
     rec = pingref.burst_records(pirip_amd.testframe_payload(8 * pingref.KB), frames, source, seq)
     assert rec.shape == (frames + 1, 1 + pingref.KB) and rec[:, 0].tolist() == [1] + [0] * (frames - 1) + [2]
-    got = _framer(["-m", str(M), "--packed", "--gap", "7", "-", "-"], rec.tobytes())
-    want = _framer(["-m", str(M), "--testframes", str(frames), "--bursts", "1", "--source", hex(source), "--gap", "7"] + (["--seq"] if seq else []) +
+    got = sigutil.run_framer(["-m", str(M), "--packed", "--gap", "7", "-", "-"], rec.tobytes())
+    want = sigutil.run_framer(["-m", str(M), "--testframes", str(frames), "--bursts", "1", "--source", hex(source), "--gap", "7"] + (["--seq"] if seq else []) +
                    ["/dev/zero", "-"])
     assert got.size == want.size > 0 and np.array_equal(got, want)
     if seq:

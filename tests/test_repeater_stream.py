@@ -4,7 +4,6 @@ Every check is exact. The records offered per call and the counters come from th
 tests/test_repeater_stream_cpu.py pins to frame_repeater's own output and whose schedules it shows to reach every corner; the IQ must be
 what a fresh HipTxStream makes when the host sends it the model's records call by call. The closed loop runs a terminal's bursts through
 the repeater and a checking receiver, and feeds the repeater its own output to see that it repeats none of it."""
-import ctypes as C
 import os
 import subprocess
 
@@ -13,25 +12,13 @@ import pytest
 
 import muxshapes as ms
 import rptref
+import sigutil
 
 pytestmark = pytest.mark.gpu
 
 CANARY = 0xA5
 BAD_ARG, UNSUPPORTED = -1, -6
 MFS, RS = 40000, 5000                          # Ts = 8, the smallest of tests/test_txs.py's shapes; D = 1, linear: wideband = modem rate
-
-
-def _hip():
-    """the HIP runtime this process has loaded (device-to-device copies out of the handle's rows)"""
-    with open("/proc/self/maps") as f:
-        path = next(line.split()[-1] for line in f if "libamdhip64" in line)
-    rt = C.CDLL(path)
-    rt.hipMemcpyAsync.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int, C.c_void_p]
-    return rt
-
-
-def _d2d(rt, dst, src, n):
-    assert rt.hipMemcpyAsync(dst, src, n, 3, None) == 0
 
 
 def _modem(M):
@@ -78,7 +65,7 @@ class _Run:
     def go(self, upto=None):
         """the first `upto` calls (None: all) -> (IQ uint8 [calls * block * 2], offered uint8 [calls, ntx, P, rl], counts int32 [calls, ntx])"""
         import torch
-        rt = _hip()
+        rt = sigutil.hip_runtime()
         ntx = self.s["ntx"]
         ncalls = self.ncalls if upto is None else upto
         out = torch.full((ncalls * self.blk + 64,), CANARY, dtype=torch.uint8, device="cuda")
@@ -88,8 +75,8 @@ class _Run:
         assert stride == self.P * self.rl
         for n in range(ncalls):
             self.rpt.push_records(self.d_st[n], self.d_pl[n], out.data_ptr() + 32 + n * self.blk, self.blk, ncalls=self.d_nc[n])
-            _d2d(rt, off[n].data_ptr(), p_rec, ntx * stride)
-            _d2d(rt, cnt[n].data_ptr(), p_n, ntx * 4)
+            sigutil.d2d(rt, off[n].data_ptr(), p_rec, ntx * stride)
+            sigutil.d2d(rt, cnt[n].data_ptr(), p_n, ntx * 4)
         torch.cuda.synchronize()
         assert (out[:32] == CANARY).all() and (out[32 + ncalls * self.blk:] == CANARY).all()
         assert np.array_equal(self.d_st.cpu().numpy(), self.hst) and np.array_equal(self.d_pl.cpu().numpy(), self.hpl)   # the records are only read
@@ -297,7 +284,7 @@ def test_the_intake_writes_the_records_of_the_record_conversion(built_lib, tmp_p
     block = 2 * tx.Ts
     txs = pirip_amd.HipTxStream(tx, mux, block, max(max(syms), rptref.burst_cost(100, tx.preamble_syms, tx.frame_syms, rptref.GAP_SYMS)))
     rpt = pirip_amd.HipRepeater(tx, txs, list(range(B)), src, filter=None, holdoff=0, max_burst=100, pending=P)
-    rt = _hip()
+    rt = sigutil.hip_runtime()
     rl = 1 + kb
     p_rec, stride, p_n = rpt.offered()
     assert stride == P * rl
@@ -312,8 +299,8 @@ def test_the_intake_writes_the_records_of_the_record_conversion(built_lib, tmp_p
             hst[s, :st[s].size], hpl[s, :st[s].size] = st[s], pl[s]
         staged.append([torch.from_numpy(x).cuda() for x in (hst, hpl, np.array([x.size for x in st], np.int32))])
         rpt.push_records(staged[n][0], staged[n][1], out, block * 2, ncalls=staged[n][2])
-        _d2d(rt, off[n].data_ptr(), p_rec, B * stride)
-        _d2d(rt, cnt[n].data_ptr(), p_n, B * 4)
+        sigutil.d2d(rt, off[n].data_ptr(), p_rec, B * stride)
+        sigutil.d2d(rt, cnt[n].data_ptr(), p_n, B * 4)
     torch.cuda.synchronize()
     off, cnt = off.cpu().numpy(), cnt.cpu().numpy()
     compared = 0
@@ -385,7 +372,7 @@ class _Repeater:
         out = torch.zeros_like(blocks)
         K, R, kb = blocks.shape[0], self.rpt.rx_rows, rptref.KB
         if tbits is not None:
-            rt = _hip()
+            rt = sigutil.hip_runtime()
             st = torch.zeros((K, 4, R), dtype=torch.uint8, device="cuda")
             pl = torch.zeros((K, 4, R, kb), dtype=torch.uint8, device="cuda")
             info = torch.zeros((K, 4, R, 10), dtype=torch.int32, device="cuda")
@@ -397,10 +384,10 @@ class _Repeater:
                 assert (r["status_stride"], r["payload_stride"], r["info_stride"]) == (R, R * kb, R * 10)
                 tbits.push_records(r["status"], r["payload"], r["info"], ncalls=r["nframes"], max_calls=R,
                                    status_stride=r["status_stride"], payload_stride=r["payload_stride"], info_stride=r["info_stride"])
-                _d2d(rt, st[k].data_ptr(), r["status"], 4 * R)
-                _d2d(rt, pl[k].data_ptr(), r["payload"], 4 * R * kb)
-                _d2d(rt, info[k].data_ptr(), r["info"], 4 * R * 10 * 4)
-                _d2d(rt, nfr[k].data_ptr(), r["nframes"], 4 * 4)
+                sigutil.d2d(rt, st[k].data_ptr(), r["status"], 4 * R)
+                sigutil.d2d(rt, pl[k].data_ptr(), r["payload"], 4 * R * kb)
+                sigutil.d2d(rt, info[k].data_ptr(), r["info"], 4 * R * 10 * 4)
+                sigutil.d2d(rt, nfr[k].data_ptr(), r["nframes"], 4 * 4)
         torch.cuda.synchronize()
         if tbits is not None:
             self.seen = [x.cpu().numpy() for x in (st, pl, info, nfr)]

@@ -3,9 +3,6 @@
 A recording of many live channels -- each with its own timing offset and sample-clock error, so that every channel follows its own nin
 sequence -- is fed block after block through the receiver and compared, bit for bit, with ONE batch call over the whole recording: same
 kernels, same samples, same carried state, so bits, soft magnitudes, statistics rows, frame counts and consumed samples must be equal."""
-import os
-import subprocess
-
 import numpy as np
 import pytest
 
@@ -13,8 +10,6 @@ import sigutil
 
 pytestmark = pytest.mark.gpu
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-BIN = os.path.join(ROOT, "pirip_amd", "bin")
 
 # rtl_fsk -r 1000 at 240 kS/s (the block kernel's Ts = 240 / Ndft = 4096 shape)
 CFG_R1000 = dict(Fs=240000, Rs=1000, M=2, P=15, f1=11000, shift=2000, est_min=500, est_max=119000)
@@ -235,16 +230,9 @@ def test_stream_front_end_equals_decimator_then_demod(oracle, built_lib, front):
     assert np.array_equal(tot, cons_want) and np.array_equal(tot + backlog, np.full(nch, n_mod))
 
 
-def _framer(args):
-    p = subprocess.run([os.path.join(BIN, "fsk_ldpc_framer"), "--code", os.path.join(ROOT, "pirip_amd", "data", "standin_256_512_4.code")] + args,
-                       capture_output=True)
-    assert p.returncode == 0, p.stderr
-    return np.frombuffer(p.stdout, dtype=np.uint8)
-
-
 def _bursts(M):
     """framer output (preamble, unique word, codeword) behind gaps of different lengths, one per base waveform (repeated to length)"""
-    b = _framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
+    b = sigutil.run_framer(["-m", str(M), "--testframes", "3", "--bursts", "1", "--seq", "--source", "0x4", "/dev/zero", "-"])
     gap = np.zeros(40 * (1 if M == 2 else 2), dtype=np.uint8)
     return [np.concatenate([gap[:k * 8 + 8], b, gap, gap]) for k in range(4)]
 

@@ -20,7 +20,8 @@ import ldpcshapes as ls
 import nsymshapes as ns
 import sigutil
 import switchshapes as ss
-from parity import RX_FILT_TOL, _compare
+from demodrun import host_chunks, make_handle, same_results, same_words, stream_state, words
+from parity import RX_FILT_TOL, _compare, oracle_Sf
 
 pytestmark = pytest.mark.gpu
 
@@ -37,30 +38,9 @@ def _once(key, make):
     return _memo[key]
 
 
-def _words(a):
-    a = np.ascontiguousarray(a)
-    return a.view({1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
-
-
-def _same_words(a, b, what):
-    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
-    assert a.shape == b.shape and a.dtype == b.dtype, (what, a.shape, b.shape, a.dtype, b.dtype)
-    if not np.array_equal(_words(a), _words(b)):
-        bad = np.argwhere(_words(a) != _words(b))
-        raise AssertionError((what, "%d of %d words differ" % (len(bad), a.size), bad[:4].tolist(), a[tuple(bad[0])], b[tuple(bad[0])]))
-
-
-def _same_result(a, b, what):
-    assert a["nframes"] == b["nframes"] and a["consumed"] == b["consumed"], (what, a["nframes"], b["nframes"], a["consumed"], b["consumed"])
-    for k in ("bits", "rx_filt", "stats"):
-        _same_words(a[k], b[k], (what, k))
-
-
 # ======== the fused FFT multiply ===========================================================================================================
 def _cfg1_handle(nstreams=1):
-    import pirip_amd
-    c = sigutil.CFG1
-    return pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"], in_format=0, nstreams=nstreams)
+    return make_handle(sigutil.CFG1, nstreams)
 
 
 def _fused_oracle(oracle, name, first_frame_unfused=True, n=None):
@@ -89,19 +69,13 @@ def test_fused_fft_multiply_equals_the_fused_oracle(oracle, built_lib, monkeypat
     assert h.kernel() == "wave" and "fused FFT multiply" in h.kernel_name(), h.kernel_name()
     rh = h.demod_host(u8)
     _compare_fused(name, ro, rh)
-    _same_words(h.get_Sf(0), Sf_o, (name, "Sf, one call"))
+    same_words(h.get_Sf(0), Sf_o, (name, "Sf, one call"))
     h = _cfg1_handle()
     n = u8.shape[0]
-    parts, carry, last = [], u8[:0], 0
-    for cut in (n // 3 + 17, (2 * n) // 3 + 5, n):
-        piece = np.concatenate([carry, u8[last:cut]]); last = cut
-        p = h.demod_host(piece)
-        parts.append(p); carry = piece[p["consumed"]:]
-    rc = {k: np.concatenate([p[k] for p in parts]) for k in ("bits", "rx_filt", "stats")}
-    rc["nframes"], rc["consumed"] = sum(p["nframes"] for p in parts), n - carry.shape[0]
+    rc = host_chunks(h, u8, (n // 3 + 17, (2 * n) // 3 + 5))
     _compare_fused(name, ro, rc)
-    _same_words(h.get_Sf(0), Sf_o, (name, "Sf, three calls"))
-    _same_result(rc, rh, (name, "three calls against one"))
+    same_words(h.get_Sf(0), Sf_o, (name, "Sf, three calls"))
+    same_results(rc, rh, (name, "three calls against one"))
 
 
 def test_fused_fft_multiply_five_streams(oracle, built_lib, monkeypatch):
@@ -129,7 +103,7 @@ def test_fused_fft_multiply_five_streams(oracle, built_lib, monkeypatch):
         rh = {"nframes": k, "consumed": int(cons[s]), "bits": bits[s, :k].cpu().numpy(), "rx_filt": filt[s, :k].cpu().numpy(),
               "stats": stats[s, :k].cpu().numpy()}
         _compare_fused(nm, ro, rh)
-        _same_words(h.get_Sf(s), Sf_o, (nm, "Sf of stream %d" % s))
+        same_words(h.get_Sf(s), Sf_o, (nm, "Sf of stream %d" % s))
 
 
 def test_fused_fft_multiply_without_the_exact_prologue(oracle, built_lib, monkeypatch):
@@ -148,18 +122,18 @@ def test_fused_fft_multiply_without_the_exact_prologue(oracle, built_lib, monkey
     err0 = sigutil.rel_err(rh["rx_filt"][0], ro["rx_filt"][0])             # (relative to frame 0's own peak)
     print(f"frame 0 without the prologue: rx_filt error {err0:.2e} of its peak (bar {3 * RX_FILT_TOL:g})")
     assert err0 < 3 * RX_FILT_TOL
-    _same_words(rh["stats"][0, :4], ro["stats"][0, :4], "tone estimates of frame 0")
+    same_words(rh["stats"][0, :4], ro["stats"][0, :4], "tone estimates of frame 0")
     assert rh["stats"][0, 6] == ro["stats"][0, 6] and np.array_equal(rh["bits"][0], ro["bits"][0])
     n0 = 1200                                               # (frame 0 of a created stream takes nin = N samples)
     rest = lambda r: dict({k: r[k][1:] for k in ("bits", "rx_filt", "stats")}, nframes=r["nframes"] - 1, consumed=r["consumed"] - n0,
                           **({"timing_cond": r["timing_cond"][1:]} if "timing_cond" in r else {}))
     _compare(rest(ro), rest(rh))
-    _same_words(h.get_Sf(0), Sf_o, "Sf, fused from frame 0")
+    same_words(h.get_Sf(0), Sf_o, "Sf, fused from frame 0")
     h1 = _cfg1_handle()
     h1.set_exact_first_frame(False)
     r1 = h1.demod_host(u8[:1200])
     assert r1["nframes"] == 1 and r1["consumed"] == 1200
-    _same_words(h1.get_Sf(0), ss.oracle_fft_run(oracle, sigutil, u8[:1200], True)[1], "Sf after frame 0 alone")
+    same_words(h1.get_Sf(0), ss.oracle_fft_run(oracle, sigutil, u8[:1200], True)[1], "Sf after frame 0 alone")
 
 
 def test_fused_switch_changes_nothing_without_a_fused_instance(oracle, built_lib, monkeypatch):
@@ -167,7 +141,7 @@ def test_fused_switch_changes_nothing_without_a_fused_instance(oracle, built_lib
     import pirip_amd
     c = sigutil.CFG4
     u8 = sigutil.make_u8_stream(oracle, c, 12000, seed=5, ebno_db=9.0, random_bits=True, amp=14.0)[0]
-    mk = lambda: pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"], in_format=0, nstreams=1)
+    mk = lambda: make_handle(c)
     monkeypatch.delenv("PIRIP_FFT_FMA", raising=False)
     h0 = mk()
     r0 = h0.demod_host(u8)
@@ -176,8 +150,8 @@ def test_fused_switch_changes_nothing_without_a_fused_instance(oracle, built_lib
     assert h1.kernel() == "wave" and h1.kernel_name() == h0.kernel_name() and "fused" not in h1.kernel_name()
     r1 = h1.demod_host(u8)
     assert r0["nframes"] >= 100
-    _same_result(r1, r0, "4-FSK under PIRIP_FFT_FMA=1")
-    _same_words(h1.get_Sf(0), h0.get_Sf(0), "Sf")
+    same_results(r1, r0, "4-FSK under PIRIP_FFT_FMA=1")
+    same_words(h1.get_Sf(0), h0.get_Sf(0), "Sf")
 
 
 # ======== the decimator ====================================================================================================================
@@ -225,7 +199,7 @@ def test_decimator_opt_in_arithmetics_are_their_formulas_bit_for_bit(oracle, bui
                 for s in range(B):
                     m = 0 if (off + s * stride) % 2 else mode
                     want = _once(("arith", D, layout, s, m, s16), lambda: oracle.decim_u8(ss.arith_stream(host, D, layout, s), D, tbw, mode=m, out_s16=s16))
-                    _same_words(got[s], want, (D, form, "mode %d" % mode, "s16" if s16 else "f32", layout, "stream %d in arithmetic %d" % (s, m)))
+                    same_words(got[s], want, (D, form, "mode %d" % mode, "s16" if s16 else "f32", layout, "stream %d in arithmetic %d" % (s, m)))
             dec.close()
 
 
@@ -250,7 +224,7 @@ def test_decimator_table_conversion_is_the_exact_oracle(oracle, built_lib, monke
             got = _decimate(dec, dev, off, stride, n_in, B, s16)
             for s in range(B):
                 want = _once(("lut", D, off, s, s16), lambda: oracle.decim_u8(_stream(host, off, stride, n_in, s), D, 0.05, mode=0, out_s16=s16))
-                _same_words(got[s], want, (D, "s16" if s16 else "f32", "offset %d" % off, "stream %d" % s))
+                same_words(got[s], want, (D, "s16" if s16 else "f32", "offset %d" % off, "stream %d" % s))
         dec.close()
 
 
@@ -310,7 +284,7 @@ def _general_run(r, buf, monkeypatch, value):
     h = fl._handle(r)
     assert h.kernel() == "general"
     rh = h.demod_host(buf)
-    Sf, st = h.get_Sf(0), fl._state(h)
+    Sf, st = h.get_Sf(0), stream_state(h)
     h.close()
     return rh, Sf, st
 
@@ -318,7 +292,7 @@ def _general_run(r, buf, monkeypatch, value):
 def _state_is_the_last_frames(st, rh, what):
     """pirip_stream_state after a call repeats the last frame's statistics: norm_rx_timing, ppm, SNRest, f_est[4], rx_sig_pow, rx_nse_pow"""
     last = rh["stats"][-1]
-    _same_words(st.view(np.float32)[[1, 2, 4, 7, 8, 9, 10, 11, 12]], last[[4, 7, 5, 0, 1, 2, 3, 8, 9]], (what, "state against the last stats row"))
+    same_words(st.view(np.float32)[[1, 2, 4, 7, 8, 9, 10, 11, 12]], last[[4, 7, 5, 0, 1, 2, 3, 8, 9]], (what, "state against the last stats row"))
 
 
 @pytest.mark.parametrize("r", THREAD_ROWS, ids=lambda r: "%s_default%d" % (r.name, r.threads))
@@ -334,21 +308,21 @@ def test_general_kernel_thread_counts_equal_the_oracle(oracle, built_lib, monkey
     import test_frame_lengths as fl
     for ebno in (None, 9.0):
         buf, ro, o = fl._reference(oracle, r, ebno)
-        Sf_o = fl._oracle_Sf(oracle, o, ns.dims(r)["Ndft"])
+        Sf_o = oracle_Sf(oracle, o, ns.dims(r)["Ndft"])
         base, base_Sf, base_st = _general_run(r, buf, monkeypatch, None)
         _compare(ro, base, tol=fl._tol(r), allow_near_tie_flips=ebno is not None, M=r.M)
         differ = {}
         for nt in GENERAL_THREADS:
             rh, Sf, st = _general_run(r, buf, monkeypatch, str(nt))
             _compare(ro, rh, tol=fl._tol(r), allow_near_tie_flips=ebno is not None, M=r.M)
-            _same_words(Sf, Sf_o, (r.name, ebno, nt, "Sf"))
+            same_words(Sf, Sf_o, (r.name, ebno, nt, "Sf"))
             _state_is_the_last_frames(st, rh, (r.name, ebno, nt))
-            _same_words(st[[0, 7, 8, 9, 10]], base_st[[0, 7, 8, 9, 10]], (r.name, ebno, nt, "nin and tone estimates of the state"))
+            same_words(st[[0, 7, 8, 9, 10]], base_st[[0, 7, 8, 9, 10]], (r.name, ebno, nt, "nin and tone estimates of the state"))
             if nt == r.threads:
-                _same_result(rh, base, (r.name, ebno, "the default count set explicitly"))
-                _same_words(st, base_st, (r.name, ebno, nt, "stream state"))
+                same_results(rh, base, (r.name, ebno, "the default count set explicitly"))
+                same_words(st, base_st, (r.name, ebno, nt, "stream state"))
             else:
-                differ[nt] = int((_words(rh["rx_filt"]) != _words(base["rx_filt"])).sum())
+                differ[nt] = int((words(rh["rx_filt"]) != words(base["rx_filt"])).sum())
         print(f"{r.name} Eb/N0 {ebno}: rx_filt words that differ from the default launch ({r.threads} threads), by thread count: {differ}")
         if ebno is not None:
             assert any(differ.values()), differ
@@ -363,12 +337,12 @@ def test_general_kernel_refused_thread_counts_keep_the_default(oracle, built_lib
     buf, ro, o = fl._reference(oracle, r, 9.0)
     base, base_Sf, base_st = _general_run(r, buf, monkeypatch, None)
     other = _general_run(r, buf, monkeypatch, "128")[0]
-    assert (_words(other["rx_filt"]) != _words(base["rx_filt"])).any(), "128 threads and the default count give the same words on this row"
+    assert (words(other["rx_filt"]) != words(base["rx_filt"])).any(), "128 threads and the default count give the same words on this row"
     for value in ("100", "63", "576", "0", "-128", "wide", ""):
         rh, Sf, st = _general_run(r, buf, monkeypatch, value)
-        _same_result(rh, base, (r.name, "PIRIP_GENERAL_THREADS=%r" % value))
-        _same_words(st, base_st, (r.name, value, "stream state"))
-        _same_words(Sf, base_Sf, (r.name, value, "Sf"))
+        same_results(rh, base, (r.name, "PIRIP_GENERAL_THREADS=%r" % value))
+        same_words(st, base_st, (r.name, value, "stream state"))
+        same_words(Sf, base_Sf, (r.name, value, "Sf"))
 
 
 # ======== switches that move no output word ==================================================================================================
@@ -396,9 +370,9 @@ def test_block_stagger_changes_no_output_word(oracle, built_lib, monkeypatch, st
     nsamp = min(x.shape[0] for x in streams)
     for s in range(3):
         assert base[s]["nframes"] >= 10 and base[s]["untouched"] and got[s]["untouched"]
-        tb._same_result(got[s], base[s], (stagger, "stream %d" % s))
-        _same_words(got_state[s][0], base_state[s][0], (stagger, s, "stream state"))
-        _same_words(got_state[s][1], base_state[s][1], (stagger, s, "Sf"))
+        same_results(got[s], base[s], (stagger, "stream %d" % s))
+        same_words(got_state[s][0], base_state[s][0], (stagger, s, "stream state"))
+        same_words(got_state[s][1], base_state[s][1], (stagger, s, "Sf"))
         ro = _once(("stagger oracle", s), lambda: bs.oracle_of(oracle, M, mask).demod(streams[s][:nsamp], bs.fmt_of(oracle, fmt)))
         _compare(ro, base[s], tol=tb.TOL, allow_near_tie_flips=s != 1, M=M)
 
@@ -435,8 +409,8 @@ def test_capture_replicas_and_pinned_frames_change_no_output_word(oracle, built_
     print(name, switch, value, reps)
     tc._same(cap, seq, (name, switch, value))
     sc_c, sf_c = tc._state(hc)
-    _same_words(sf_c, sf_s, (name, switch, value, "Sf"))
-    _same_words(sc_c, sc_s, (name, switch, value, "stream state"))
+    same_words(sf_c, sf_s, (name, switch, value, "Sf"))
+    same_words(sc_c, sc_s, (name, switch, value, "stream state"))
     assert all(rp["segments"] >= 3 for rp in reps), reps
 
 
@@ -475,6 +449,7 @@ def test_ldpc_storage_layouts_decode_the_same_words(oracle, built_lib, tmp_path,
 def test_env_forms_equal_the_api_forms(oracle, built_lib, monkeypatch):
     """PIRIP_EST_BAND=1 is pirip_hip_set_estimator_band_only(1) and PIRIP_EXACT0=0 is pirip_hip_set_exact_first_frame(0) for programs
     that only call create (the command-line tools): the same kernel and the same output words as the handle that made the call."""
+    import pirip_amd
     u8 = ss.fft_input(oracle, sigutil, "awgn9")
     monkeypatch.delenv("PIRIP_EST_BAND", raising=False); monkeypatch.delenv("PIRIP_EXACT0", raising=False)
     plain = _cfg1_handle()
@@ -483,14 +458,15 @@ def test_env_forms_equal_the_api_forms(oracle, built_lib, monkeypatch):
     api.set_estimator_band_only(True)
     r_api = api.demod_host(u8)
     monkeypatch.setenv("PIRIP_EST_BAND", "1")
-    env = _cfg1_handle()
+    c = sigutil.CFG1                      # (created bare: make_handle holds a handle to what its shape says, and this one's estimator comes from the environment)
+    env = pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"], in_format=0, nstreams=1)
     monkeypatch.delenv("PIRIP_EST_BAND")
     assert env.kernel_name() == api.kernel_name() != plain.kernel_name() and "band-only estimator" in env.kernel_name(), env.kernel_name()
     r_env = env.demod_host(u8)
     assert r_env["nframes"] >= 100
-    _same_result(r_env, r_api, "PIRIP_EST_BAND=1 against set_estimator_band_only")
-    _same_words(env.get_Sf(0), api.get_Sf(0), "Sf, band-only")
-    _same_result(r_env, r_plain, "the band-only estimator against the full one")          # (its own contract: outputs unchanged)
+    same_results(r_env, r_api, "PIRIP_EST_BAND=1 against set_estimator_band_only")
+    same_words(env.get_Sf(0), api.get_Sf(0), "Sf, band-only")
+    same_results(r_env, r_plain, "the band-only estimator against the full one")          # (its own contract: outputs unchanged)
 
     api = _cfg1_handle()
     api.set_exact_first_frame(False)
@@ -499,13 +475,13 @@ def test_env_forms_equal_the_api_forms(oracle, built_lib, monkeypatch):
     env = _cfg1_handle()
     monkeypatch.delenv("PIRIP_EXACT0")
     r_env = env.demod_host(u8)
-    _same_result(r_env, r_api, "PIRIP_EXACT0=0 against set_exact_first_frame(0)")
-    _same_words(env.get_Sf(0), api.get_Sf(0), "Sf, no prologue")
+    same_results(r_env, r_api, "PIRIP_EXACT0=0 against set_exact_first_frame(0)")
+    same_words(env.get_Sf(0), api.get_Sf(0), "Sf, no prologue")
     # the switch does something on this input: without the prologue frame 0 is the wave kernel's rounding of the soft magnitudes
-    assert not np.array_equal(_words(r_api["rx_filt"][0]), _words(r_plain["rx_filt"][0]))
+    assert not np.array_equal(words(r_api["rx_filt"][0]), words(r_plain["rx_filt"][0]))
     monkeypatch.setenv("PIRIP_EXACT0", "1")
     env = _cfg1_handle()
-    _same_result(env.demod_host(u8), r_plain, "PIRIP_EXACT0=1 against the default")
+    same_results(env.demod_host(u8), r_plain, "PIRIP_EXACT0=1 against the default")
 
 
 # ======== the tools' call sizes ================================================================================================================

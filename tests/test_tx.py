@@ -25,13 +25,6 @@ MOD_SHAPES = [
 ]
 
 
-def _framer_tool(code, M, rec, gap_bits):
-    p = subprocess.run([os.path.join(BIN, "fsk_ldpc_framer"), "--code", code, "-m", str(M), "--packed", "--gap", str(gap_bits), "-", "-"],
-                       input=rec.tobytes(), capture_output=True)
-    assert p.returncode == 0, p.stderr
-    return np.frombuffer(p.stdout, dtype=np.uint8)
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("variant", [None, "rician"])
 @pytest.mark.parametrize("M", [2, 4])
@@ -66,7 +59,7 @@ def test_framer_equals_fsk_ldpc_framer_byte_for_byte(built_lib, tmp_path, M, var
     torch.cuda.synchronize()
     syms, bits, nsym = syms.cpu().numpy(), bits.cpu().numpy(), nsym.cpu().numpy()
     for s in range(B):
-        want = _framer_tool(code, M, recs[s], gap[s] * bps)
+        want = sigutil.run_framer(["-m", str(M), "--packed", "--gap", str(gap[s] * bps), "-", "-"], recs[s].tobytes(), code)
         want = np.concatenate([np.zeros(lead[s] * bps, dtype=np.uint8), want])
         assert nsym[s] * bps == want.size, (s, nsym[s], want.size)
         assert np.array_equal(bits[s, :want.size], want), s                                # the framer tool's output, exactly
@@ -274,7 +267,7 @@ def test_loopback_into_the_receive_chain(oracle, built_lib, M, P):
 
     # the existing path: host framer, upload, pirip_hip_synth_cu8 for the burst; the silence around it spliced in on the host
     rows = np.zeros((B, nsamp, 2), dtype=np.uint8)
-    bits = np.stack([_framer_tool(CODE, M, host[s], 0) for s in range(B)])
+    bits = np.stack([sigutil.run_framer(["-m", str(M), "--packed", "--gap", "0", "-", "-"], host[s].tobytes(), CODE) for s in range(B)])
     assert bits.shape[1] == burst * bps
     d_bits = torch.from_numpy(bits).cuda()
     seg = torch.zeros((B, burst * Ts * 2), dtype=torch.uint8, device="cuda")

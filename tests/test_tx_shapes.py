@@ -10,6 +10,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import sigutil
 import txref
 from test_ldpc import _write_random_code
 
@@ -62,13 +63,6 @@ def check_frames(bits, plan, recs, lead_bits, gap_bits, pre_bits, n, k, uw, H, c
     return frames
 
 
-def _framer_tool(code, M, rec, gap_bits):
-    p = subprocess.run([os.path.join(BIN, "fsk_ldpc_framer"), "--code", code, "-m", str(M), "--packed", "--gap", str(gap_bits), "-", "-"],
-                       input=rec.tobytes(), capture_output=True)
-    assert p.returncode == 0, p.stderr
-    return np.frombuffer(p.stdout, dtype=np.uint8)
-
-
 def framer_case(oracle, code, M, n, k, rng, B=6):
     """mixed-control record plans through pirip_hip_tx_frame: the device bits equal fsk_ldpc_framer --packed, every frame satisfies H,
     carries the CRC16 and the file's UW, the symbols are the bits' -> number of frames checked"""
@@ -103,7 +97,7 @@ def framer_case(oracle, code, M, n, k, rng, B=6):
     crc16 = oracle.OracleLdpc(oracle.parse_code_file(code), M).crc16
     frames = 0
     for s in range(B):
-        want = np.concatenate([np.zeros(lead[s] * bps, dtype=np.uint8), _framer_tool(code, M, recs[s], gap[s] * bps)])
+        want = np.concatenate([np.zeros(lead[s] * bps, dtype=np.uint8), sigutil.run_framer(["-m", str(M), "--packed", "--gap", str(gap[s] * bps), "-", "-"], recs[s].tobytes(), code)])
         assert nsym[s] * bps == want.size, (s, nsym[s], want.size)
         assert np.array_equal(bits[s, :want.size], want), (s, np.flatnonzero(bits[s, :want.size] != want)[:8])
         assert (bits[s, want.size:] == 0xAA).all() and (syms[s, nsym[s]:] == 0xAA).all()

@@ -7,13 +7,12 @@ Every case runs 5 streams (a partial workgroup) of about ten frames and compares
   * bits, per-frame stats, rx_filt, Sf, the stream scalars and `consumed` with the oracle (tests/parity.py's rules), and
   * every word of every output with the same library whose cache misses on every frame (PIRIP_FRAME_CACHE=0, read at create time).
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import sigutil
-from parity import _compare, _oracle_field_Sf
+from demodrun import make_handle, make_oracle, run_calls, same_results
+from parity import _compare, oracle_Sf
 
 pytestmark = pytest.mark.gpu
 
@@ -23,119 +22,46 @@ SHAPES = {"2fsk_p24": sigutil.CFG1, "2fsk_p8": CFG1_P8, "4fsk_p8": sigutil.CFG4,
           "2fsk_p8_mask": dict(CFG1_P8, mask=10000), "4fsk_p8_mask": dict(sigutil.CFG4, mask=10000)}
 BIN_HZ = 937.5                      # Fs / Ndft of every shape here
 NFRAMES = 13                        # frames of input per stream (the runs stop a few frames short: F below)
-
-
-def _nbits(c):
-    return 50 * (1 if c["M"] == 2 else 2)
-
-
-def _mod(oracle, c, nframes, seed, tone_bins=0):
-    bits = np.random.default_rng(seed).integers(0, 2, nframes * _nbits(c)).astype(np.uint8)
-    return sigutil.mod_complex(oracle, c, bits, f1=c["f1"] + int(round(tone_bins * BIN_HZ)))
-
-
-def steady(oracle, c, seed, offset, tone_bins):
-    return oracle.quantise_cu8(_mod(oracle, c, NFRAMES + 1, seed, tone_bins))[offset:]
-
-
-def mover(oracle, c, seed):
-    """tones one FFT bin up in the middle of the call, and back"""
-    x = np.concatenate([_mod(oracle, c, 4, seed), _mod(oracle, c, 4, seed + 1, tone_bins=1), _mod(oracle, c, NFRAMES - 7, seed + 2)])
-    return oracle.quantise_cu8(x)[3:]
-
-
-def clock_offset(oracle, c, seed, ppm=2500e-6):
-    """a sample clock that runs fast, then slow: the timing estimate crosses -1/4 and +1/4 symbol, nin takes N - Ts/4 and N + Ts/4"""
-    x = _mod(oracle, c, NFRAMES + 2, seed)
-    n = x.shape[0]
-    step = np.where(np.arange(n) < n // 3, 1.0 + ppm, 1.0 - ppm)
-    t = np.concatenate([[0.0], np.cumsum(step)[:-1]])
-    t = t[t < n - 2]
-    i0 = np.floor(t).astype(int); fr = (t - i0)[:, None].astype(np.float32)
-    return oracle.quantise_cu8((1 - fr) * x[i0] + fr * x[i0 + 1])
+PPM = 2500e-6
 
 
 def mixed_batch(oracle, c):
-    """[steady, mover, steady on other bins, clock offset, steady at another timing phase]: each wave's cache key is its own"""
-    rows = [steady(oracle, c, 1, 0, 0), mover(oracle, c, 10), steady(oracle, c, 2, 7, -1), clock_offset(oracle, c, 20), steady(oracle, c, 3, 17, 2)]
-    n = min(r.shape[0] for r in rows)
-    return np.stack([r[:n] for r in rows])
-
-
-def _oracle(oracle, c, est=None):
-    lo, hi = est or (c["est_min"], c["est_max"])
-    mask = c.get("mask", 0)
-    return oracle.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=lo, est_max=hi, tone_spacing=mask if mask else 100, mask=bool(mask))
-
-
-def _oracle_Sf(oracle, o):
-    return np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(256,)).copy()
+    """[steady, mover, steady on other bins, clock offset, steady at another timing phase]: each wave's cache key is its own. The mover's
+    tones go one FFT bin up in the middle of the call, and back; the sample clock runs fast, then slow: the timing estimate crosses
+    -1/4 and +1/4 symbol, nin takes N - Ts/4 and N + Ts/4"""
+    return sigutil.mixed_batch(oracle, c, NFRAMES, (4, 4, NFRAMES - 7), lambda n: np.where(np.arange(n) < n // 3, 1.0 + PPM, 1.0 - PPM))
 
 
 def run(c, host, F, per_call=None, cache=True, exact0=True, est=None, monkeypatch=None, reset_first=False):
-    """All B streams through pirip_hip_demod_batch until every stream has made F frames, per_call frames per call (None: one call).
-    Between calls every stream's unconsumed samples are presented again from its own position. Returns per-stream outputs and state."""
+    """All B streams until every stream has made F frames, per_call frames per call (None: one call), on a handle created with the frame
+    cache on or off. Returns per-stream outputs and state."""
     import torch
-    import pirip_amd
     monkeypatch.setenv("PIRIP_FRAME_CACHE", "1" if cache else "0")
-    B, L = host.shape[0], host.shape[1]
     lo, hi = est or (c["est_min"], c["est_max"])
-    h = pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=lo, est_max=hi, mask=c.get("mask", 0), in_format=0, nstreams=B)
+    h = make_handle(c, host.shape[0], est_min=lo, est_max=hi)
     assert h.kernel() == "wave"
     if not exact0:
         h.set_exact_first_frame(False)
-    st = torch.cuda.current_stream().cuda_stream
-    nb, nf = h.Nbits, c["M"] * 50
     if reset_first:
         # a used handle, then reset: the state a created handle starts from (ninp == 0)
+        st = torch.cuda.current_stream().cuda_stream
         dev = torch.from_numpy(host).cuda()
-        h.demod_batch(dev.data_ptr(), L * 2, L, 0, 0, 0, 0, 0, 0, 0, 0, 3, st)
+        h.demod_batch(dev.data_ptr(), host.shape[1] * 2, host.shape[1], 0, 0, 0, 0, 0, 0, 0, 0, 3, st)
         h.reset(st)
-    pos = np.zeros(B, dtype=np.int64)
-    done = 0
-    out = {k: [[] for _ in range(B)] for k in ("bits", "rx_filt", "stats")}
-    while done < F:
-        k = F - done if per_call is None else min(per_call, F - done)
-        n = int(L - pos.max())
-        dev = torch.from_numpy(np.stack([host[s, pos[s]:pos[s] + n] for s in range(B)])).cuda()
-        bits = torch.zeros((B, k, nb), dtype=torch.uint8, device="cuda")
-        filt = torch.zeros((B, k, nf), dtype=torch.float32, device="cuda")
-        stats = torch.zeros((B, k, pirip_amd.STATS_PER_FRAME), dtype=torch.float32, device="cuda")
-        nfr = torch.zeros(B, dtype=torch.int32, device="cuda"); cons = torch.zeros(B, dtype=torch.int64, device="cuda")
-        h.demod_batch(dev.data_ptr(), n * 2, n, bits.data_ptr(), k * nb, filt.data_ptr(), k * nf, stats.data_ptr(),
-                      k * pirip_amd.STATS_PER_FRAME, nfr.data_ptr(), cons.data_ptr(), k, st)
-        torch.cuda.synchronize()
-        assert (nfr.cpu().numpy() == k).all(), (nfr, k, done)
-        for s in range(B):
-            out["bits"][s].append(bits[s].cpu().numpy()); out["rx_filt"][s].append(filt[s].cpu().numpy()); out["stats"][s].append(stats[s].cpu().numpy())
-        pos += cons.cpu().numpy()
-        done += k
-    res = []
-    for s in range(B):
-        sc = np.zeros(8, dtype=np.float32)
-        assert h.L.pirip_hip_get_scalars(h.h, s, sc.ctypes.data) == 0
-        res.append({"nframes": F, "consumed": int(pos[s]), "Sf": h.get_Sf(s), "scalars": sc,
-                    **{k: np.concatenate(out[k][s]) for k in out}})
+    k = per_call or F
+    res = run_calls(h, host, [min(k, F - done) for done in range(0, F, k)])
     h.close()
     return res
-
-
-def same_words(a, b, what):
-    for s, (x, y) in enumerate(zip(a, b)):
-        assert x["consumed"] == y["consumed"], (what, s)
-        for k in ("bits", "rx_filt", "stats", "Sf", "scalars"):
-            assert np.array_equal(x[k].view(np.uint8 if x[k].dtype == np.uint8 else np.uint32),
-                                  y[k].view(np.uint8 if y[k].dtype == np.uint8 else np.uint32)), (what, s, k)
 
 
 def against_oracle(oracle, c, host, res, est=None):
     """Each stream against its own oracle run over exactly the samples the device consumed. Returns the oracle results."""
     ros = []
     for s, rh in enumerate(res):
-        o = _oracle(oracle, c, est)
+        o = make_oracle(oracle, c, est)
         ro = o.demod(host[s, :rh["consumed"]], oracle.IN_CU8_FSKDEMOD)
         _compare(ro, rh, M=c["M"])
-        assert np.array_equal(rh["Sf"], _oracle_Sf(oracle, o)), s
+        assert np.array_equal(rh["Sf"], oracle_Sf(oracle, o)), s
         # the stream scalars are the last frame's stats row (f_est, timing, SNRest, nin, ppm), which _compare has just held to the oracle's
         last = rh["stats"][-1]
         assert np.array_equal(rh["scalars"][[0, 1, 2, 3, 4, 5, 7]], last[[0, 1, 2, 3, 4, 5, 7]]) and rh["scalars"][6] == last[6] == o.nin(), s
@@ -145,7 +71,7 @@ def against_oracle(oracle, c, host, res, est=None):
 
 def frames_for(oracle, c, host, est=None):
     """F: one frame fewer than the shortest oracle run, so that every stream has the samples for F frames in every call pattern"""
-    return min(_oracle(oracle, c, est).demod(host[s], oracle.IN_CU8_FSKDEMOD, want_filt=False)["nframes"] for s in range(host.shape[0])) - 1
+    return min(make_oracle(oracle, c, est).demod(host[s], oracle.IN_CU8_FSKDEMOD, want_filt=False)["nframes"] for s in range(host.shape[0])) - 1
 
 
 @pytest.fixture(scope="module")
@@ -171,7 +97,7 @@ def test_steady_moving_tones_and_nin_steps_hit_and_miss_alike(oracle, built_lib,
     assert len(moves) >= 2 and moves[0] >= 2 and f1[-1] == f1[moves[0]], f1
     nin = ros[3]["stats"][:, 6]
     assert (nin == N - Q).any() and (nin == N + Q).any() and (nin == N).any(), nin
-    same_words(hit, run(c, host, F, cache=False, monkeypatch=monkeypatch), "cache off")
+    same_results(hit, run(c, host, F, cache=False, monkeypatch=monkeypatch), "cache off")
 
 
 @pytest.mark.parametrize("shape,per_call", [("2fsk_p24", 1), ("2fsk_p24", 2), ("2fsk_p24", 3), ("2fsk_p8", 2), ("4fsk_p8", 3), ("2fsk_p8_mask", 2), ("4fsk_p8_mask", 1)])
@@ -181,9 +107,9 @@ def test_cache_does_not_survive_a_call_boundary(oracle, built_lib, batches, monk
     F = frames_for(oracle, c, host)
     one = run(c, host, F, monkeypatch=monkeypatch)
     parts = run(c, host, F, per_call=per_call, monkeypatch=monkeypatch)
-    same_words(one, parts, f"calls of {per_call}")
+    same_results(one, parts, f"calls of {per_call}")
     against_oracle(oracle, c, host, parts)
-    same_words(parts, run(c, host, F, per_call=per_call, cache=False, monkeypatch=monkeypatch), "cache off")
+    same_results(parts, run(c, host, F, per_call=per_call, cache=False, monkeypatch=monkeypatch), "cache off")
 
 
 @pytest.mark.parametrize("exact0", [True, False])
@@ -194,8 +120,8 @@ def test_first_call_after_reset_with_and_without_the_exact_prologue(oracle, buil
     F = frames_for(oracle, c, host)
     fresh = run(c, host, F, exact0=exact0, monkeypatch=monkeypatch)
     against_oracle(oracle, c, host, fresh)
-    same_words(fresh, run(c, host, F, exact0=exact0, reset_first=True, monkeypatch=monkeypatch), "after reset")
-    same_words(fresh, run(c, host, F, exact0=exact0, cache=False, monkeypatch=monkeypatch), "cache off")
+    same_results(fresh, run(c, host, F, exact0=exact0, reset_first=True, monkeypatch=monkeypatch), "after reset")
+    same_results(fresh, run(c, host, F, exact0=exact0, cache=False, monkeypatch=monkeypatch), "cache off")
 
 
 def test_all_neutral_input_takes_the_tie_path(oracle, built_lib, monkeypatch):
@@ -208,7 +134,7 @@ def test_all_neutral_input_takes_the_tie_path(oracle, built_lib, monkeypatch):
     for s, ro in enumerate(against_oracle(oracle, c, host, hit)):
         # (nothing exceeds best = 0: both tones end on index 0 of the shifted spectrum, -Fs/2)
         assert not hit[s]["Sf"].any() and (ro["stats"][:, :2] == -c["Fs"] / 2).all() and (hit[s]["stats"][:, :2] == -c["Fs"] / 2).all()
-    same_words(hit, run(c, host, F, cache=False, monkeypatch=monkeypatch), "cache off")
+    same_results(hit, run(c, host, F, cache=False, monkeypatch=monkeypatch), "cache off")
 
 
 def test_bit_equal_maxima_in_two_lanes_smaller_bin_wins(oracle, built_lib, monkeypatch):
@@ -223,7 +149,7 @@ def test_bit_equal_maxima_in_two_lanes_smaller_bin_wins(oracle, built_lib, monke
     est = (-4000, 25000)
     rows = []
     for s in range(5):
-        x = _mod(oracle, c, NFRAMES + 1, 40 + s)
+        x = sigutil.mod_frames(oracle, c, NFRAMES + 1, 40 + s)
         x[:, 1] = 0.0
         rows.append(oracle.quantise_cu8(x)[5 * s:])
     n = min(r.shape[0] for r in rows)
@@ -237,4 +163,4 @@ def test_bit_equal_maxima_in_two_lanes_smaller_bin_wins(oracle, built_lib, monke
         assert Sf[125] == Sf[131] == Sf[118:139].max()         # the lower tone's peak sits in two bins, both inside the search range
         assert (ro["stats"][2:, 0] == -3 * BIN_HZ).all() and (ro["stats"][2:, 1] > 0).all(), ro["stats"][:, :2]
         assert np.array_equal(hit[s]["stats"][:, :2], ro["stats"][:, :2])
-    same_words(hit, run(c, host, F, est=est, cache=False, monkeypatch=monkeypatch), "cache off")
+    same_results(hit, run(c, host, F, est=est, cache=False, monkeypatch=monkeypatch), "cache off")

@@ -9,13 +9,12 @@ ragged calls, which is how the state block a call leaves behind (raw tail, tone 
 The instances that have not taken the locked paths run the same code under both settings apart from the frame cache itself; they are
 here so that taking them later is tested from the start.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 
 import sigutil
-from parity import _compare, _oracle_field_Sf
+from demodrun import make_handle, make_oracle, run_calls, same_results
+from parity import _compare, oracle_Sf
 
 pytestmark = pytest.mark.gpu
 
@@ -37,113 +36,25 @@ SHAPES = {
 }
 
 
-def _nbits(c):
-    return 50 * (1 if c["M"] == 2 else 2)
-
-
-def _bin_hz(c):
-    return c["Fs"] / 256.0
-
-
-def _mod(oracle, c, nframes, seed, tone_bins=0):
-    bits = np.random.default_rng(seed).integers(0, 2, nframes * _nbits(c)).astype(np.uint8)
-    return sigutil.mod_complex(oracle, c, bits, f1=c["f1"] + int(round(tone_bins * _bin_hz(c))))
-
-
-def _conv(oracle, c, x):
-    if c["fmt"] == CF32:
-        return np.ascontiguousarray(x.astype(np.float32) * np.float32(0.37))
-    return oracle.quantise_cu8(x)
-
-
-def _resample(x, step):
-    """x read at positions 0, step[0], step[0] + step[1], ... (linear interpolation)"""
-    t = np.concatenate([[0.0], np.cumsum(step)[:-1]])
-    t = t[t < x.shape[0] - 2]
-    i0 = np.floor(t).astype(int); fr = (t - i0)[:, None].astype(np.float32)
-    return ((1 - fr) * x[i0] + fr * x[i0 + 1]).astype(np.float32)
-
-
-def clock_offset(oracle, c, seed, ppm):
-    x = _mod(oracle, c, NFRAMES + 2, seed)
-    return _resample(x, np.full(x.shape[0], 1.0 + ppm * 1e-6))
-
-
-def mover(oracle, c, seed):
-    """tones one FFT bin up half-way through"""
-    h = (NFRAMES + 1) // 2
-    return np.concatenate([_mod(oracle, c, h, seed), _mod(oracle, c, NFRAMES + 1 - h, seed + 1, tone_bins=1)])[3:]
-
-
-def batch(oracle, c, rows):
-    rows = [_conv(oracle, c, r) for r in rows]
-    n = min(r.shape[0] for r in rows)
-    return np.stack([r[:n] for r in rows])
-
-
 def mixed_batch(oracle, c):
-    return batch(oracle, c, [_mod(oracle, c, NFRAMES + 1, 1), mover(oracle, c, 10), _mod(oracle, c, NFRAMES + 1, 2, tone_bins=-1)[7:],
-                             clock_offset(oracle, c, 20, 2500.0), _mod(oracle, c, NFRAMES + 1, 3, tone_bins=2)[17:]])
-
-
-def _oracle(oracle, c, est=None):
-    lo, hi = est or (c["est_min"], c["est_max"])
-    return oracle.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=lo, est_max=hi)
-
-
-def _oracle_Sf(oracle, o):
-    return np.ctypeslib.as_array(C.cast(_oracle_field_Sf(oracle, o), C.POINTER(C.c_float)), shape=(256,)).copy()
+    """the mover's tones go one FFT bin up half-way through; the sample clock is 2500 ppm fast"""
+    h = (NFRAMES + 1) // 2
+    return sigutil.mixed_batch(oracle, c, NFRAMES, (h, NFRAMES + 1 - h), lambda n: np.full(n, 1.0 + 2500.0 * 1e-6))
 
 
 def run(c, host, calls, cache, monkeypatch, limits=None):
-    """All B streams through pirip_hip_demod_batch, calls[i] frames in call i; every stream's unconsumed samples are presented again
-    from its own position. limits[i] (when given and not None): pirip_hip_set_freq_est_limits before call i. Returns per-stream results."""
-    import torch
-    import pirip_amd
+    """run_calls on a wave handle created with the frame cache on or off. limits[i] (when given and not None):
+    pirip_hip_set_freq_est_limits before call i. Returns per-stream results."""
     monkeypatch.setenv("PIRIP_FRAME_CACHE", "1" if cache else "0")
-    B, L = host.shape[0], host.shape[1]
-    bps = host.dtype.itemsize * 2
-    h = pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"], in_format=c["fmt"], nstreams=B)
-    if c["band"]:
-        h.set_estimator_band_only(True)
-    assert h.kernel() == "wave" and ("band-only" in h.kernel_name()) == c["band"]
-    st = torch.cuda.current_stream().cuda_stream
-    nb, nf = h.Nbits, c["M"] * 50
-    pos = np.zeros(B, dtype=np.int64)
-    out = {k: [[] for _ in range(B)] for k in ("bits", "rx_filt", "stats")}
-    for i, k in enumerate(calls):
+    h = make_handle(c, host.shape[0])
+    assert h.kernel() == "wave"
+
+    def set_limits(i, h):
         if limits and limits[i]:
             assert h.set_freq_est_limits(*limits[i]) == 0
-        n = int(L - pos.max())
-        dev = torch.from_numpy(np.stack([host[s, pos[s]:pos[s] + n] for s in range(B)])).cuda()
-        bits = torch.zeros((B, k, nb), dtype=torch.uint8, device="cuda")
-        filt = torch.zeros((B, k, nf), dtype=torch.float32, device="cuda")
-        stats = torch.zeros((B, k, pirip_amd.STATS_PER_FRAME), dtype=torch.float32, device="cuda")
-        nfr = torch.zeros(B, dtype=torch.int32, device="cuda"); cons = torch.zeros(B, dtype=torch.int64, device="cuda")
-        h.demod_batch(dev.data_ptr(), n * bps, n, bits.data_ptr(), k * nb, filt.data_ptr(), k * nf, stats.data_ptr(),
-                      k * pirip_amd.STATS_PER_FRAME, nfr.data_ptr(), cons.data_ptr(), k, st)
-        torch.cuda.synchronize()
-        assert (nfr.cpu().numpy() == k).all(), (nfr, k, i)
-        for s in range(B):
-            out["bits"][s].append(bits[s].cpu().numpy()); out["rx_filt"][s].append(filt[s].cpu().numpy()); out["stats"][s].append(stats[s].cpu().numpy())
-        pos += cons.cpu().numpy()
-    res = []
-    for s in range(B):
-        sc = np.zeros(8, dtype=np.float32)
-        assert h.L.pirip_hip_get_scalars(h.h, s, sc.ctypes.data) == 0
-        res.append({"nframes": sum(calls), "consumed": int(pos[s]), "Sf": h.get_Sf(s), "scalars": sc,
-                    "state": np.frombuffer(h.stream_state(s), dtype=np.uint32),
-                    **{k: np.concatenate(out[k][s]) for k in out}})
+    res = run_calls(h, host, calls, before_call=set_limits)
     h.close()
     return res
-
-
-def same_words(a, b, what):
-    for s, (x, y) in enumerate(zip(a, b)):
-        assert x["consumed"] == y["consumed"], (what, s)
-        for k in ("bits", "rx_filt", "stats", "Sf", "scalars", "state"):
-            assert np.array_equal(x[k].view(np.uint8 if x[k].dtype == np.uint8 else np.uint32),
-                                  y[k].view(np.uint8 if y[k].dtype == np.uint8 else np.uint32)), (what, s, k)
 
 
 def against_oracle(oracle, c, host, res, limits=None, calls=None):
@@ -151,7 +62,7 @@ def against_oracle(oracle, c, host, res, limits=None, calls=None):
     Returns the oracle's stats per stream."""
     ros = []
     for s, rh in enumerate(res):
-        o = _oracle(oracle, c)
+        o = make_oracle(oracle, c)
         if limits and calls:
             parts, pos = [], 0
             for i, k in enumerate(calls):
@@ -171,13 +82,13 @@ def against_oracle(oracle, c, host, res, limits=None, calls=None):
         _compare(ro, rh, M=c["M"])
         assert np.array_equal(rh["stats"][:, :4], ro["stats"][:, :4]), s           # f_est frame by frame
         lo_hi = slice(128, 160) if c["band"] else slice(0, 256)
-        assert np.array_equal(rh["Sf"][lo_hi], _oracle_Sf(oracle, o)[lo_hi]), s
+        assert np.array_equal(rh["Sf"][lo_hi], oracle_Sf(oracle, o)[lo_hi]), s
         ros.append(ro["stats"])
     return ros
 
 
 def frames_for(oracle, c, host):
-    return min(_oracle(oracle, c).demod(host[s], c["fmt"], want_filt=False)["nframes"] for s in range(host.shape[0])) - 1
+    return min(make_oracle(oracle, c).demod(host[s], c["fmt"], want_filt=False)["nframes"] for s in range(host.shape[0])) - 1
 
 
 @pytest.fixture(scope="module")
@@ -195,10 +106,10 @@ def test_hook_off_equals_hook_on_equals_oracle(oracle, built_lib, batches, monke
     N, Q = c["Fs"] // c["Rs"] * 50, c["Fs"] // c["Rs"] // 4
     assert (st[0][2:, 0] == st[0][2, 0]).all() and (np.diff(st[1][:, 0]) != 0).any()      # stream 0 stays on its bins, stream 1 moves
     assert (st[3][:, 6] == N - Q).any() and (st[3][:, 6] == N).any()                       # stream 3 steps nin between hit frames
-    same_words(on, run(c, host, [F], False, monkeypatch), "hook off")
+    same_results(on, run(c, host, [F], False, monkeypatch), "hook off")
     ragged = [3, 1, F - 6, 2]
-    same_words(on, run(c, host, ragged, True, monkeypatch), "ragged calls")
-    same_words(on, run(c, host, ragged, False, monkeypatch), "ragged calls, hook off")
+    same_results(on, run(c, host, ragged, True, monkeypatch), "ragged calls")
+    same_results(on, run(c, host, ragged, False, monkeypatch), "ragged calls, hook off")
 
 
 # (est_min, est_max, f1, shift): the tones stay inside the range (checked on the oracle's f_est below); live slot sets by
@@ -213,7 +124,7 @@ RANGES = {
 
 
 def _range_batch(oracle, c):
-    return batch(oracle, c, [_mod(oracle, c, NFRAMES + 1, 30 + s)[5 * s:] for s in range(5)])
+    return sigutil.batch(oracle, c, [sigutil.mod_frames(oracle, c, NFRAMES + 1, 30 + s)[5 * s:] for s in range(5)])
 
 
 @pytest.mark.parametrize("name", list(RANGES))
@@ -231,7 +142,7 @@ def test_search_range_set_on_the_live_handle(oracle, built_lib, monkeypatch, nam
         f = st[s][2:, :2]
         assert (f >= lo).all() and (f < hi).all() and (np.abs(f[:, 0] - f1) <= 1875).all(), (s, f)
         assert (((np.rint(f[:, 1] / 937.5).astype(int) >> 4) & 3) == top_slot).all(), (s, f)
-    same_words(on, run(c, host, [F], False, monkeypatch, limits=limits), "hook off")
+    same_results(on, run(c, host, [F], False, monkeypatch, limits=limits), "hook off")
 
 
 def test_search_range_changes_between_two_calls(oracle, built_lib, monkeypatch):
@@ -241,7 +152,7 @@ def test_search_range_changes_between_two_calls(oracle, built_lib, monkeypatch):
     calls, limits = [4, 4, 3], [(500, 25000), (500, 40000), (2000, 28000)]
     on = run(c, host, calls, True, monkeypatch, limits=limits)
     against_oracle(oracle, c, host, on, limits=limits, calls=calls)
-    same_words(on, run(c, host, calls, False, monkeypatch, limits=limits), "hook off")
+    same_results(on, run(c, host, calls, False, monkeypatch, limits=limits), "hook off")
 
 
 @pytest.mark.parametrize("name", ["headline_u8", "4fsk_p8"])
@@ -252,11 +163,11 @@ def test_hit_path_exits_in_the_middle_of_a_call(oracle, built_lib, monkeypatch, 
     long_frames = 2 * NFRAMES
     rows = []
     for s, ppm in enumerate([300.0, -300.0, 300.0, -300.0]):
-        x = sigutil.mod_complex(oracle, c, np.random.default_rng(50 + s).integers(0, 2, long_frames * _nbits(c)).astype(np.uint8))
+        x = sigutil.mod_complex(oracle, c, np.random.default_rng(50 + s).integers(0, 2, long_frames * sigutil.frame_bits(c)).astype(np.uint8))
         # a start phase near the nin threshold, so that the slow drift (0.36 samples per frame) crosses it inside the run
-        rows.append(_resample(x, np.full(x.shape[0], 1.0 + ppm * 1e-6))[(6 if ppm > 0 else 17) + s:])
-    rows.append(np.concatenate([_mod(oracle, c, NFRAMES, 60), _mod(oracle, c, NFRAMES, 61, tone_bins=1)])[3:])
-    host = batch(oracle, c, rows)
+        rows.append(sigutil.resample_steps(x, np.full(x.shape[0], 1.0 + ppm * 1e-6))[(6 if ppm > 0 else 17) + s:])
+    rows.append(sigutil.mover(oracle, c, 60, (NFRAMES, NFRAMES)))
+    host = sigutil.batch(oracle, c, rows)
     F = frames_for(oracle, c, host)
     assert 22 <= F <= 27
     on = run(c, host, [F], True, monkeypatch)
@@ -267,6 +178,6 @@ def test_hit_path_exits_in_the_middle_of_a_call(oracle, built_lib, monkeypatch, 
     assert (np.diff(st[4][:, 0]) != 0).any()
     ragged = [5, 1, 2, F - 11, 3]
     parts = run(c, host, ragged, True, monkeypatch)
-    same_words(on, parts, "ragged calls")
-    same_words(on, run(c, host, [F], False, monkeypatch), "hook off")
-    same_words(parts, run(c, host, ragged, False, monkeypatch), "ragged calls, hook off")
+    same_results(on, parts, "ragged calls")
+    same_results(on, run(c, host, [F], False, monkeypatch), "hook off")
+    same_results(parts, run(c, host, ragged, False, monkeypatch), "ragged calls, hook off")

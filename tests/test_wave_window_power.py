@@ -23,8 +23,8 @@ import numpy as np
 import pytest
 
 import wpshapes as wp
-from parity import TIMING_TOL, _compare
-from test_wave_locked_paths import _oracle_Sf, run, same_words
+from demodrun import make_handle, make_oracle, run_calls, same_results
+from parity import TIMING_TOL, _compare, oracle_Sf
 
 pytestmark = pytest.mark.gpu
 
@@ -41,6 +41,16 @@ def batches(oracle):
     shapes = {**wp.PACKED, **wp.UNCHANGED}
     return {(name, case): make(oracle, shapes[name]) for name in shapes for case, make in wp.CASES.items()
             if name in wp.PACKED or (name, case) in PARENT_SHA256}
+
+
+def run(c, host, calls, cache, monkeypatch):
+    """run_calls on a wave handle created with the frame cache on or off"""
+    monkeypatch.setenv("PIRIP_FRAME_CACHE", "1" if cache else "0")
+    h = make_handle(c, host.shape[0])
+    assert h.kernel() == "wave"
+    res = run_calls(h, host, calls)
+    h.close()
+    return res
 
 
 def frames_of(case):
@@ -62,11 +72,11 @@ def digest(res):
 
 def check_against_oracle(oracle, c, host, res, noisy):
     for s, rh in enumerate(res):
-        o = wp.make_oracle(oracle, c)
+        o = make_oracle(oracle, c)
         ro = o.demod(host[s, :rh["consumed"]], c["fmt"])
         flips = _compare(ro, rh, allow_near_tie_flips=noisy, M=c["M"])       # exact: frames, consumed, f_est, nin, (noise-free) bits
         band = slice(128, 160) if c["band"] else slice(0, 256)               # (band-only: Sf is kept for FFT bins 0 .. 31)
-        assert np.array_equal(rh["Sf"][band], _oracle_Sf(oracle, o)[band]), s
+        assert np.array_equal(rh["Sf"][band], oracle_Sf(oracle, o)[band]), s
         dp = np.abs(rh["stats"][:, 7].astype(np.float64) - ro["stats"][:, 7].astype(np.float64))
         print(f"stream {s}: timing max diff {np.abs(rh['stats'][:, 4] - ro['stats'][:, 4]).max():.2e} symbols, ppm max diff {dp.max():.2e}, "
               f"near-tie bit flips {flips}")
@@ -87,12 +97,12 @@ def test_packed_instance_against_the_oracle_and_itself(oracle, built_lib, batche
         d = np.concatenate([np.diff(r["stats"][:, 4]) for r in one])
         assert (d < 0).sum() >= 20 and (d > 0).sum() >= 20                   # dividends of both signs reach the divide
     ragged = [3, 1, F - 6, 2]
-    same_words(one, run(c, host, ragged, True, monkeypatch), "ragged calls")
+    same_results(one, run(c, host, ragged, True, monkeypatch), "ragged calls")
     hook = run(c, host, [F], False, monkeypatch)
-    same_words(one, hook, "frame cache off, IEEE divide")
+    same_results(one, hook, "frame cache off, IEEE divide")
     for s in range(len(one)):
         assert np.array_equal(one[s]["stats"][:, 7].view(np.uint32), hook[s]["stats"][:, 7].view(np.uint32)), s
-    same_words(hook, run(c, host, ragged, False, monkeypatch), "ragged calls, frame cache off")
+    same_results(hook, run(c, host, ragged, False, monkeypatch), "ragged calls, frame cache off")
 
 
 def test_band_only_twin_computes_the_full_instances_words(oracle, built_lib, batches, monkeypatch):
@@ -100,25 +110,19 @@ def test_band_only_twin_computes_the_full_instances_words(oracle, built_lib, bat
     for case in ("clean", "drifting"):
         full = run(wp.PACKED["headline_u8"], batches["headline_u8", case], [frames_of(case)], True, monkeypatch)
         band = run(wp.PACKED["band_only"], batches["band_only", case], [frames_of(case)], True, monkeypatch)
-        for s, (x, y) in enumerate(zip(full, band)):
-            assert x["consumed"] == y["consumed"]
-            for k in ("bits", "rx_filt", "stats"):
-                assert np.array_equal(x[k].view(np.uint8 if k == "bits" else np.uint32), y[k].view(np.uint8 if k == "bits" else np.uint32)), (case, s, k)
+        same_results(full, band, case, keys=("bits", "rx_filt", "stats"))
 
 
 @pytest.mark.parametrize("name", list(wp.PACKED))
 def test_packed_bit_output_equals_unpacked(oracle, built_lib, batches, name):
     import torch
-    import pirip_amd
     c, host = wp.PACKED[name], batches[name, "clean"]
     B, n, F = host.shape[0], host.shape[1], wp.CLEAN_FRAMES
     dev = torch.from_numpy(host).cuda()
     out = []
     for packed in (False, True):
-        h = pirip_amd.HipDemod(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"], in_format=c["fmt"], nstreams=B)
+        h = make_handle(c, B)
         h.set_bit_packing(packed)
-        if c["band"]:
-            h.set_estimator_band_only(True)
         fb = (h.Nbits + 7) // 8 if packed else h.Nbits
         bits = torch.zeros((B, F, fb), dtype=torch.uint8, device="cuda")
         nfr = torch.zeros(B, dtype=torch.int32, device="cuda"); cons = torch.zeros(B, dtype=torch.int64, device="cuda")

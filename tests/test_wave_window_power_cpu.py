@@ -19,6 +19,7 @@ import numpy as np
 import pytest
 
 import wpshapes as wp
+from demodrun import make_oracle
 
 f32 = np.float32
 
@@ -95,7 +96,7 @@ def oracle_runs(oracle):
             host = make(oracle, c)
             per_stream = []
             for s in range(host.shape[0]):
-                o = wp.make_oracle(oracle, c)
+                o = make_oracle(oracle, c)
                 pos, stats, ab = 0, [], []
                 while pos + o.nin() <= host.shape[1]:
                     r = o.demod(host[s, pos:pos + o.nin()], c["fmt"], want_filt=False)

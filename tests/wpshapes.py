@@ -8,6 +8,7 @@ the device test demands the oracle's nin sequence exactly and exempts no stream.
 import numpy as np
 
 import sigutil
+from demodrun import resample_at
 
 U8D, CSDR = 0, 1                                  # pirip_amd.IN_* == oracle.IN_*
 NSYM = 50
@@ -31,47 +32,26 @@ EBNO_DB = 9.0
 TIMING_MARGIN = 5e-4
 
 
-def _nbits(c):
-    return NSYM * (1 if c["M"] == 2 else 2)
-
-
-def _mod(oracle, c, nframes, seed):
-    bits = np.random.default_rng(seed).integers(0, 2, nframes * _nbits(c)).astype(np.uint8)
-    return sigutil.mod_complex(oracle, c, bits)
-
-
 def _resample(x, ratio):
     """x read at positions 0, ratio, 2 ratio, ... (linear interpolation)"""
-    t = np.arange(int((x.shape[0] - 2) / ratio)) * ratio
-    i0 = np.floor(t).astype(int); fr = (t - i0)[:, None].astype(np.float32)
-    return ((1 - fr) * x[i0] + fr * x[i0 + 1]).astype(np.float32)
-
-
-def _batch(oracle, rows):
-    rows = [oracle.quantise_cu8(r) for r in rows]
-    n = min(r.shape[0] for r in rows)
-    return np.stack([r[:n] for r in rows])
+    return resample_at(x, np.arange(int((x.shape[0] - 2) / ratio)) * ratio)
 
 
 def clean(oracle, c):
     """noise-free, every stream at its own start offset"""
-    return _batch(oracle, [_mod(oracle, c, CLEAN_FRAMES + 2, 100 + s)[off:] for s, off in enumerate(CLEAN_OFFSETS)])
+    return sigutil.batch(oracle, c, [sigutil.mod_frames(oracle, c, CLEAN_FRAMES + 2, 100 + s)[off:] for s, off in enumerate(CLEAN_OFFSETS)])
 
 
 def drifting(oracle, c):
     """+ 300 / - 300 ppm of sample-clock offset over 40 frames: 0.36 samples per frame, so nin steps at least once in each direction"""
-    return _batch(oracle, [_resample(_mod(oracle, c, PPM_FRAMES + 2, 200 + s), 1.0 + ppm * 1e-6)[off:]
-                           for s, (ppm, off) in enumerate(zip(PPM, PPM_OFFSETS))])
+    return sigutil.batch(oracle, c, [_resample(sigutil.mod_frames(oracle, c, PPM_FRAMES + 2, 200 + s), 1.0 + ppm * 1e-6)[off:]
+                                  for s, (ppm, off) in enumerate(zip(PPM, PPM_OFFSETS))])
 
 
 def noisy(oracle, c):
     rng = np.random.default_rng(300)
-    return _batch(oracle, [sigutil.add_awgn(_mod(oracle, c, CLEAN_FRAMES + 2, 300 + s), EBNO_DB, c, rng)[off:] * np.float32(0.5)
-                           for s, off in enumerate(CLEAN_OFFSETS)])
+    return sigutil.batch(oracle, c, [sigutil.add_awgn(sigutil.mod_frames(oracle, c, CLEAN_FRAMES + 2, 300 + s), EBNO_DB, c, rng)[off:] * np.float32(0.5)
+                                  for s, off in enumerate(CLEAN_OFFSETS)])
 
 
 CASES = {"clean": clean, "drifting": drifting, "noisy": noisy}
-
-
-def make_oracle(oracle, c):
-    return oracle.OracleFsk(c["Fs"], c["Rs"], c["M"], P=c["P"], est_min=c["est_min"], est_max=c["est_max"])
