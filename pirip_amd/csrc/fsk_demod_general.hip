@@ -30,6 +30,7 @@
 #include <cmath>
 
 #include "../../include/pirip_hip.h"
+#include "demod_frame.hpp"
 #include "demod_simd.hpp"
 #include "fsk_device.hpp"
 #include "glibc_atan2f.hpp"
@@ -237,10 +238,7 @@ struct Stream {
     uint32_t theta[kMaxTones]; // oscillator phase of every tone, 2^32 = one turn
     float2 phc[kMaxTones];     // oracle order, every frame: phi_c of every tone, carried frame to frame by thread 0
 };
-struct Tones { float f_est[kMaxTones]; uint32_t dtheta[kMaxTones]; int drift_ix[kMaxTones]; };   // a frame's tone estimates: Hz, phase step, oscillator-table row
 struct FrameOut { uint8_t *bits; float *filt; float *stats; int frame_bytes; };                  // a frame's output rows (nullptr: not requested)
-struct Timing { int nin_next, low_sample, high_sample; float fract; };
-struct SymbolSums { float sig, nse, mean_e, std_e; };
 
 __device__ __forceinline__ void open_stream(Stream &c, char *smem, int64_t seg_in)
 {
@@ -662,10 +660,7 @@ __device__ __forceinline__ SymbolSums decide_symbols(const Stream &c, const Timi
         for (int m = 0; m < kMaxTones; m++) if (m < M) {
             const float2 lo = c.L.fint[m * nint + st + t.low_sample];
             const float2 hi = c.L.fint[m * nint + st + t.high_sample];
-            float2 r;
-            r.x = (1 - fract) * lo.x; r.y = (1 - fract) * lo.y;
-            r.x = r.x + fract * hi.x; r.y = r.y + fract * hi.y;
-            tmax[m] = (r.x * r.x) + (r.y * r.y);
+            tmax[m] = tone_power(lo, hi, fract);
             sum += tmax[m];
         }
         float mx = tmax[0]; int sym = 0;
@@ -724,17 +719,6 @@ __device__ __forceinline__ SymbolSums sum_symbols_serial(Stream &c, const float 
     __syncthreads();
     return s;
 }
-__device__ __forceinline__ void update_snr(StreamScalars &sc, SymbolSums s, int Nsym)
-{
-    const float sig = s.sig / (float)Nsym, nse = s.nse / (float)Nsym, mean_e = s.mean_e / (float)Nsym;
-    sc.v_est = sqrtf(sig - nse);
-    sc.SNRest = sig / nse;
-    sc.rx_sig_pow = sig; sc.rx_nse_pow = nse;
-    float std_e = (s.std_e / (float)Nsym) - (mean_e * mean_e);
-    std_e = std_e > 0.0f ? sqrtf(std_e) : 0.0f;
-    sc.EbNodB = -6.0f + (20.0f * log10f((1e-6f + mean_e) / (1e-6f + std_e)));
-    sc.snr_est = (0.5f * sc.snr_est) + (0.5f * sc.EbNodB);
-}
 // the frame's stats row; with a NaN timing estimate (upstream returns before touching the outputs) zeroed bits and magnitudes
 __device__ __forceinline__ void finish_frame(const Stream &c, const FrameOut &o, int nin, bool bad)
 {
@@ -744,9 +728,7 @@ __device__ __forceinline__ void finish_frame(const Stream &c, const FrameOut &o,
         for (int i = c.tid; i < c.a.d.M * c.a.d.Nsym; i += c.NT) if (o.filt) o.filt[i] = 0.f;
     }
     if (!o.stats || c.tid != 0) return;
-    o.stats[0] = sc.f_est[0]; o.stats[1] = sc.f_est[1]; o.stats[2] = sc.f_est[2]; o.stats[3] = sc.f_est[3];
-    o.stats[4] = sc.norm_rx_timing; o.stats[5] = sc.SNRest; o.stats[6] = (float)nin; o.stats[7] = sc.ppm;
-    o.stats[8] = sc.rx_sig_pow; o.stats[9] = sc.rx_nse_pow;
+    write_stats_row(o.stats, sc.f_est, sc.norm_rx_timing, sc.SNRest, nin, sc.ppm, sc.rx_sig_pow, sc.rx_nse_pow);
 }
 
 }  // namespace

@@ -22,12 +22,22 @@ if len(sys.argv) > 1 and sys.argv[1] == "child":
     e1.record(st); torch.cuda.synchronize()
     print("RATE", float(cons.sum()) / (e0.elapsed_time(e1) / 20) / 1e6, hb.kernel())
 else:
-    # variants: "TAG=ENVNAME=VALUE" (environment of that variant's processes) on the command line, default: the start-up stagger experiment
+    # variants: "TAG=ENVNAME=VALUE" (environment of that variant's processes) on the command line, default: the start-up stagger experiment.
+    # Two builds of the library: "A parent=PIRIP_HIP_LIB=<path>" "B result=PIRIP_HIP_LIB=<path>" (pirip_amd/binding.py loads what it names).
+    # Every pass is a process of its own under a time limit; the first one that exits non-zero or runs out of time ends the run, non-zero.
+    CHILD_TIMEOUT = 180
     variants = [v.split("=", 1) for v in sys.argv[1:]] or [["A default", ""], ["B stagger 3", "PIRIP_BLOCK_STAGGER=3"], ["C stagger 6", "PIRIP_BLOCK_STAGGER=6"]]
     for M in (2, 4):
         for rep in range(3):
             for tag, envs in variants:
                 env = dict(os.environ)
                 env.update(kv.split("=", 1) for kv in envs.split(",") if "=" in kv)
-                r = subprocess.run([sys.executable, __file__, "child", str(M)], env=env, capture_output=True, text=True)
-                print(M, tag, [l for l in r.stdout.splitlines() if l.startswith("RATE")] or r.stderr[-300:], flush=True)
+                try:
+                    r = subprocess.run([sys.executable, __file__, "child", str(M)], env=env, capture_output=True, text=True, timeout=CHILD_TIMEOUT)
+                except subprocess.TimeoutExpired:
+                    print(M, tag, "no result after %d s: stopping" % CHILD_TIMEOUT, flush=True)
+                    sys.exit(124)
+                if r.returncode != 0:
+                    print(M, tag, "exit status %d: stopping" % r.returncode, r.stderr[-300:], flush=True)
+                    sys.exit(1)
+                print(M, tag, [l for l in r.stdout.splitlines() if l.startswith("RATE")], flush=True)
