@@ -1193,6 +1193,126 @@ int pirip_hip_div_get_combined(pirip_hip_div *dv, int group, int slot, uint16_t 
 /* One HIP stream per handle, the one ldpc's receive calls are enqueued on. */
 
 /* ----------------------------------------------------------------------------------- */
+/* section R : packet link (datagrams cut into FSK_LDPC frames and reassembled)         */
+/*   The layer between a datagram and the frames every section above moves: the open     */
+/*   milestone of the reference's plan ("TAP/TUN integration and demo IP link | What       */
+/*   protocol?"). The reference fixes no protocol; this section fixes one. Composes, as     */
+/*   section N does, a streaming receiver (section G, optional) and a transmitter with its   */
+/*   streaming transmitter (sections I and K, optional): packets handed to send are cut      */
+/*   into bursts that wait in section M's pending rings and go into section K's queue whole,  */
+/*   received records are put back together into packets in a ring per receive channel       */
+/*   (DESIGN.md 4.18). No call synchronises or allocates; every call enqueues the same         */
+/*   launches. Only symbols are added: PIRIP_HIP_ABI_VERSION and every entry point above      */
+/*   stand.                                                                                   */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_pkt pirip_hip_pkt;
+/* Wire format. kb = data_bytes (>= 16); the framer overwrites bytes kb - 2 and kb - 1 with the CRC16. cap = kb - 8.
+ *   byte 0 src    the sender's address (where rtl_fsk's --filter and the repeater's rewrite look)
+ *   byte 1 dst    the destination's address, 0xFF = everyone
+ *   byte 2 id     the sender's packet counter of the channel, mod 256
+ *   byte 3 idx    fragment index, 0 .. nfrag - 1
+ *   byte 4 nfrag  fragments of the packet, 1 .. max_frags
+ *   byte 5 len    body bytes in this fragment, 1 .. cap; every fragment but the last has len == cap
+ *   bytes 6 .. kb - 3: cap body bytes, zero padded
+ * The body of a packet of L bytes, 1 <= L <= max_packet = max_frags * cap - 4, is the L bytes and their CRC-32 (IEEE 802.3, zlib's crc32)
+ * as four bytes, least significant first; nfrag = ceil((L + 4) / cap). One packet is one burst: the records pirip_hip_tx_frame reads, with
+ * burst control 1, 0, ..., 0, then the `2` record of zeros.
+ * (This section's three structures are written as section Q's are and are held to their twins -- binding.PktConfig, PktEntry, PktInfo,
+ * PKT_ENTRY_DTYPE -- by tests/test_packet_cpu.py.) */
+struct pirip_pkt_config {
+    int nrx;                    /* receive channels (== rx's channels when rx is given) */
+    int source_byte;            /* 0..255: src of every frame sent */
+    int filter_byte;            /* -1, or 0..255 = rtl_fsk --filter: such a frame loses PIRIP_RX_BITS before it is looked at */
+    int address;                /* -1: every frame is accepted; 0..255: only frames whose dst is this or 0xFF */
+    int max_frags;              /* 1..PIRIP_TX_REPEAT_MAX_FRAMES: a section M repeater can repeat any packet whole */
+    int pending_records;        /* >= max_frags + 1: records of each transmit channel's pending ring */
+    int ring_entries;           /* >= 1: packets of each receive channel's ring */
+};
+typedef struct pirip_pkt_config pirip_pkt_config;
+struct pirip_pkt_entry {                    /* 24 bytes */
+    int64_t seq;                            /* packets delivered on the channel before this one */
+    int32_t call, row, length;              /* n and f of the packet's last fragment; L */
+    uint8_t src, dst, id, nfrag;            /* of the last fragment */
+};
+typedef struct pirip_pkt_entry pirip_pkt_entry;
+struct pirip_pkt_info {
+    int nrx, nchan, source_byte, filter_byte, address, max_frags, pending_records, ring_entries, cap, max_packet, has_rx, rx_rows, data_bytes,
+        device;
+};
+typedef struct pirip_pkt_info pirip_pkt_info;
+/* rx, tx and txs as in pirip_hip_ping_create, with its error codes: rx NULL or a streaming receiver created with an ldpc, of cfg->nrx
+ * channels, at most 4096 rows per call (PIRIP_ERR_UNSUPPORTED above) and, with tx, of tx's data_bytes; tx and txs both NULL -- the handle
+ * only receives, nchan = 0 and every call's d_out must be NULL -- or a transmitter and the streaming transmitter created on it. One of tx /
+ * txs without the other, all three NULL, handles on different devices, cfg or out NULL, nrx < 1 or not rx's channels, source_byte outside
+ * 0 .. 255, filter_byte or address outside -1 .. 255, max_frags outside 1 .. PIRIP_TX_REPEAT_MAX_FRAMES, pending_records < max_frags + 1,
+ * ring_entries < 1, data_bytes < 16, and a txs whose queue_syms does not hold one burst of max_frags frames (preamble_syms + max_frags *
+ * frame_syms + tx's largest gap) are PIRIP_ERR_BAD_ARG. Every work row is sized here with tx's gaps as they are: set the gaps first.
+ * Create synchronises the device. */
+int pirip_hip_pkt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, const pirip_pkt_config *cfg, pirip_hip_pkt **out);
+int pirip_hip_pkt_destroy(pirip_hip_pkt *pkt);
+int pirip_hip_pkt_get_info(const pirip_hip_pkt *pkt, pirip_pkt_info *info);
+/* Transmit channel t hands over d_npk[t] (NULL = max_pk; clamped to [0, max_pk]) packets: packet j's bytes at d_bytes + t * chan_stride +
+ * j * pkt_stride, its length d_len[t * max_pk + j] (int32) and its destination d_dst[t * max_pk + j] (uint8). They are taken in order: a
+ * length outside 1 .. max_packet stops the channel and raises `bad`; a packet whose nfrag + 1 records do not fit the free space of the
+ * channel's pending ring stops the channel and raises `refused`. Each packet taken gets id = (packets sent on the channel) mod 256 and is
+ * written as its burst into the pending ring, from where the next calls' offers take it. d_taken[t] (may be NULL): packets taken, always
+ * a prefix. Needs tx; NULL d_bytes / d_len / d_dst, max_pk < 0: PIRIP_ERR_BAD_ARG. Enqueued on hip_stream; never synchronises. */
+int pirip_hip_pkt_send(pirip_hip_pkt *pkt, const uint8_t *d_bytes, size_t chan_stride, size_t pkt_stride, const int32_t *d_npk, int max_pk,
+                       const int32_t *d_len, const uint8_t *d_dst, int32_t *d_taken, void *hip_stream);
+/* Call n (n = 0, 1, ... since create / reset), in stream order:
+ * 1. reassemble, per receive channel c over its d_ncalls[c] (NULL = ncalls; clamped to [0, ncalls]) rows in row order -- status bytes at
+ *    d_status + c * status_stride, payloads of data_bytes bytes at d_payload + c * payload_stride, as pirip_hip_fsk_ldpc_rx_batch writes
+ *    them; they are only read. The channel carries an open packet {src, id, nfrag, next, nbytes} and an assembly buffer of max_frags * cap
+ *    bytes on the device, so a packet may straddle any number of calls. Every row goes through these rules, in this order:
+ *    a. a row without PIRIP_RX_SYNC closes an open packet (incomplete);
+ *    b. a row with PIRIP_RX_BITS whose byte 0 is filter_byte loses BITS (filtered);
+ *    c. a row without BITS is done;
+ *    d. a bad header -- nfrag outside 1 .. max_frags, idx >= nfrag, len outside 1 .. cap, or len != cap on a fragment that is not the
+ *       last -- closes an open packet (incomplete), counts malformed, and the row is done;
+ *    e. with address >= 0, a dst that is neither address nor 0xFF counts foreign, and the row is done: nothing else changes;
+ *    f. idx == 0 closes an open packet (incomplete), opens {src, id, nfrag, next = 1, nbytes = len} and copies the len body bytes;
+ *    g. idx > 0 with a packet open whose src, id and nfrag are the row's and whose next == idx appends the len body bytes: next += 1,
+ *       nbytes += len; any other idx > 0 closes an open packet (incomplete), counts orphan, and the row is done;
+ *    h. when next == nfrag the packet closes: nbytes < 5 or a CRC-32 that does not match counts crc_fail, else the packet is delivered.
+ *    Delivery writes one pirip_pkt_entry at slot delivered % ring_entries of the channel's ring and the packet's length bytes at the same
+ *    slot of a data ring with max_packet bytes per slot: the ring overwrites its oldest entry (lost).
+ * 2. offer: section M's step 2 with a hold-off of 0 over the pending rings that pirip_hip_pkt_send fills.
+ * 3. pirip_hip_txs_process into d_out (its rules for d_out / out_stride_bytes).
+ * A handle without tx runs step 1 alone and wants d_out == NULL (else PIRIP_ERR_BAD_ARG); a handle with tx wants d_out. d_status and
+ * d_payload are required (PIRIP_ERR_BAD_ARG), as are strides that hold ncalls rows when nrx > 1. ncalls <= 4096 (PIRIP_ERR_UNSUPPORTED
+ * above), ncalls < 0 is PIRIP_ERR_BAD_ARG. Works with and without rx (with rx it changes nothing of the receiver). Enqueued on
+ * hip_stream (NULL = default stream); never synchronises. */
+int pirip_hip_pkt_push_records(pirip_hip_pkt *pkt, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                               const int32_t *d_ncalls, int ncalls, void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* Need rx (PIRIP_ERR_BAD_ARG without): pirip_hip_rx_process on the block at pirip_hip_rx_input (push: after copying it from d_in as
+ * pirip_hip_rx_push does; d_in == NULL is PIRIP_ERR_BAD_ARG) into the handle's own record rows, then the steps above over them. */
+int pirip_hip_pkt_process(pirip_hip_pkt *pkt, void *d_out, size_t out_stride_bytes, void *hip_stream);
+int pirip_hip_pkt_push(pirip_hip_pkt *pkt, const void *d_in, size_t in_stride_bytes, void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* The rows the last call read, as received: after process / push the handle's own -- rx_rows rows per channel, strides in elements,
+ * d_nframes [nrx] --, after push_records the caller's. Valid in stream order; each pointer may be NULL. PIRIP_ERR_BAD_ARG before the
+ * first call. */
+int pirip_hip_pkt_records(pirip_hip_pkt *pkt, const uint8_t **d_status, size_t *status_stride, const uint8_t **d_payload, size_t *payload_stride,
+                          const int32_t **d_nframes);
+/* The records offered to the streaming transmitter in the last call: channel t's d_nrec[t] records at d_records + t * rec_stride.
+ * PIRIP_ERR_BAD_ARG on a handle without tx. */
+int pirip_hip_pkt_offered(pirip_hip_pkt *pkt, const uint8_t **d_records, size_t *rec_stride, const int32_t **d_nrec);
+/* Host copies (synchronises the device), each may be NULL. Per receive channel [nrx]: packets delivered, frames the filter removed, frames
+ * for another address, frames with a bad header, fragments that fitted no open packet, packets closed before their last fragment, packets
+ * whose body failed its check, entries the ring overwrote. Per transmit channel [nchan]: packets sent, sends stopped by a full ring,
+ * sends stopped by a bad length, records waiting in the ring. */
+int pirip_hip_pkt_get_counters(pirip_hip_pkt *pkt, int64_t *delivered, int64_t *filtered, int64_t *foreign, int64_t *malformed, int64_t *orphan,
+                               int64_t *incomplete, int64_t *crc_fail, int64_t *lost, int64_t *sent, int64_t *refused, int64_t *bad,
+                               int64_t *pending);
+/* Host copy (synchronises the device) of the newest min(delivered, ring_entries, max) entries of receive channel chan, oldest first, and
+ * their bytes at bytes + i * max_packet (bytes may be NULL); *written (may be NULL): how many. PIRIP_ERR_BAD_ARG for chan outside
+ * [0, nrx), max < 0 or entries == NULL with max > 0. */
+int pirip_hip_pkt_get_packets(pirip_hip_pkt *pkt, int chan, pirip_pkt_entry *entries, uint8_t *bytes, int max, int *written);
+/* Forgets open packets, the rings and the counters and resets txs, and rx where present: the next call is n = 0, the next id 0. */
+int pirip_hip_pkt_reset(pirip_hip_pkt *pkt, void *hip_stream);
+/* One HIP stream per handle: open packets, rings and counters are device state advanced in stream order, the call index is host state
+ * advanced when a call is enqueued. */
+
+/* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */
 /*             names and signatures as codec2 src/fsk.h [UPSTREAM-RECALLED]              */
 /* ----------------------------------------------------------------------------------- */

@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J, K, L, M, N and O).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J, K, L, M, N, O, P, Q and R).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -144,6 +144,26 @@ DIV_ENTRY_DTYPE = [("t_samples", "<i8"), ("iters", "<i4"), ("pcc", "<i4"), ("era
 class DivInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("groups", "branches", "samples_per_symbol", "nin0", "max_skew_samples", "max_rows", "log_entries",
                                        "pending", "slots", "n", "data_bytes", "device")]
+
+
+class PktConfig(C.Structure):
+    """pirip_pkt_config: receive channels, src of frames sent, filtered byte 0 or -1, accepted dst or -1, fragments per packet, records of
+    a pending ring, packets of a receive ring"""
+    _fields_ = [(n, C.c_int) for n in ("nrx", "source_byte", "filter_byte", "address", "max_frags", "pending_records", "ring_entries")]
+
+
+class PktEntry(C.Structure):
+    _fields_ = [("seq", C.c_int64), ("call", C.c_int32), ("row", C.c_int32), ("length", C.c_int32), ("src", C.c_uint8), ("dst", C.c_uint8),
+                ("id", C.c_uint8), ("nfrag", C.c_uint8)]
+
+
+# pirip_pkt_entry as a numpy structured dtype (24 bytes, the C layout): what HipPacket.packets returns
+PKT_ENTRY_DTYPE = [("seq", "<i8"), ("call", "<i4"), ("row", "<i4"), ("length", "<i4"), ("src", "u1"), ("dst", "u1"), ("id", "u1"), ("nfrag", "u1")]
+
+
+class PktInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nrx", "nchan", "source_byte", "filter_byte", "address", "max_frags", "pending_records", "ring_entries",
+                                       "cap", "max_packet", "has_rx", "rx_rows", "data_bytes", "device")]
 
 
 # pirip_spec_band_row as a numpy structured dtype (12 bytes, the C layout): what HipSpectrum.push's band entries are on the host
@@ -333,6 +353,19 @@ def _signatures():
         "pirip_hip_div_get_log": (i32, [vp, i32, vp, vp, i32, P(i32)]),
         "pirip_hip_div_get_counters": (i32, [vp] + [vp] * 6),
         "pirip_hip_div_get_combined": (i32, [vp, i32, i32, vp]),
+        # section R: packet link
+        "pirip_hip_pkt_create": (i32, [vp, vp, vp, P(PktConfig), P(vp)]),
+        "pirip_hip_pkt_destroy": (i32, [vp]),
+        "pirip_hip_pkt_get_info": (i32, [vp, P(PktInfo)]),
+        "pirip_hip_pkt_send": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp, vp]),
+        "pirip_hip_pkt_push_records": (i32, [vp, vp, sz, vp, sz, vp, i32, vp, sz, vp]),
+        "pirip_hip_pkt_process": (i32, [vp, vp, sz, vp]),
+        "pirip_hip_pkt_push": (i32, [vp, vp, sz, vp, sz, vp]),
+        "pirip_hip_pkt_records": (i32, [vp] + [P(vp), P(sz)] * 2 + [P(vp)]),
+        "pirip_hip_pkt_offered": (i32, [vp, P(vp), P(sz), P(vp)]),
+        "pirip_hip_pkt_get_counters": (i32, [vp] + [vp] * 12),
+        "pirip_hip_pkt_get_packets": (i32, [vp, i32, vp, vp, i32, P(i32)]),
+        "pirip_hip_pkt_reset": (i32, [vp, vp]),
         # the library itself
         "pirip_hip_find_code": (i32, [cs, cs, sz]),
         "pirip_hip_version": (cs, []),

@@ -5,16 +5,12 @@
 
 #include <cstdint>
 
+#include "burst_ring.hpp"
 #include "hip_host.hpp"
 
 #pragma GCC visibility push(hidden)
 namespace pirip {
 
-// a transmit channel's pending ring: records [head, tail), counted since create / reset
-struct RptRing {
-    uint64_t head, tail;
-    int64_t bursts_out, dropped;
-};
 // a receive channel's counters
 struct RptRxCount {
     int64_t bursts, frames, filtered, unrouted;
@@ -41,12 +37,7 @@ struct pirip_hip_rpt {
     int32_t *d_state = nullptr;            // [nrx][2] receiving, frames held
     uint8_t *d_held = nullptr;             // [nrx][max_burst][kb] the frames of a burst that is still being received
     pirip::RptRxCount *d_cnt = nullptr;    // [nrx]
-    pirip::RptRing *d_ring_state = nullptr;   // [ntx]
-    uint8_t *d_ring = nullptr;             // [ntx][pending][1 + kb]
-    int64_t *d_ready = nullptr;            // [ntx][pending] at a burst's first record: the call from which it may be offered
-    int32_t *d_blen = nullptr;             // [ntx][pending] at a burst's first record: its records
-    uint8_t *d_offered = nullptr;          // [ntx][pending][1 + kb] the records offered in the last call
-    int32_t *d_noffered = nullptr;         // [ntx]
+    pirip::BurstRings rings;               // [ntx] the pending rings (burst_ring.hpp), pending records of 1 + kb bytes each
     // with rx: the records of the last call
     uint8_t *d_status = nullptr, *d_payload = nullptr;       // [nrx][rx_rows], [nrx][rx_rows][kb]
     int32_t *d_info = nullptr, *d_nframes = nullptr;         // [nrx][rx_rows][PIRIP_LDPC_INFO_PER_CALL], [nrx]

@@ -6,10 +6,8 @@
 //   offer:   pending ring --rpt_offer_kernel (one wave per transmit channel)--> record rows --section K's send path--> symbol queue
 //   process: pirip_hip_txs_process
 //
-// Pending ring of a transmit channel: `pending` records of 1 + kb bytes, head and tail 64-bit record counts on the device. A burst is the
-// records 1, 0, ..., 0, 2; at the slot of its first record lie its length in records and its ready tag (the call from which it may be
-// offered). route's non-negative entries are distinct, so a ring has one writer; the offer of call n runs behind the intake of call n and
-// in front of the intake of call n + 1 (stream order), so head and tail are never written while they are read.
+// The pending rings and the offer step are burst_ring.hpp's, shared with the packet link (section R). route's non-negative entries are
+// distinct, so a ring has one writer: the intake.
 // The call index n is host state advanced when a call is enqueued, as the sample index of section K.
 #include <hip/hip_runtime.h>
 
@@ -22,6 +20,7 @@
 #include "hip_host.hpp"
 #include "ldpc_handle.hpp"
 #include "mux_handle.hpp"
+#include "burst_ring.hpp"
 #include "repeat_device.hpp"
 #include "rpt_handle.hpp"
 #include "tx_handle.hpp"
@@ -35,9 +34,8 @@ struct IntakeArgs {
     RepeatIn in;
     const int32_t *route;                  // [nrx]
     RptRxCount *cnt;                       // [nrx]
-    RptRing *rs;                           // [ntx]
-    uint8_t *ring; int64_t *ready; int32_t *blen;
-    int pending, filter;
+    BurstRingView v;
+    int filter;
     int64_t ready_at;                      // n + holdoff
 };
 
@@ -48,8 +46,6 @@ __global__ __launch_bounds__(64) void rpt_intake_kernel(IntakeArgs a)
 {
     __shared__ int32_t s_start;                              // the ring slot of the tail
     const int c = blockIdx.x, t = a.route[c];
-    const int rl = 1 + a.in.kb;
-    uint8_t *ring = a.ring + (size_t)(t >= 0 ? t : 0) * a.pending * rl;
     int nfilt = 0;
     auto status = [&](uint8_t v, const uint8_t *frame) {     // rtl_fsk --filter: a frame of the repeater's own is no frame
         if ((v & PIRIP_RX_BITS) && a.filter >= 0 && frame[0] == (uint8_t)a.filter) { v = (uint8_t)(v & ~PIRIP_RX_BITS); nfilt++; }
@@ -59,98 +55,45 @@ __global__ __launch_bounds__(64) void rpt_intake_kernel(IntakeArgs a)
         int64_t frames = 0, unrouted = 0, dropped = 0;
         int off = 0, start = 0;
         if (t >= 0) {
-            const uint64_t head = a.rs[t].head, tail = a.rs[t].tail;
-            int64_t room = (int64_t)a.pending - (int64_t)(tail - head);
-            start = (int)(tail % (uint64_t)a.pending);
+            const uint64_t head = a.v.rs[t].head, tail = a.v.rs[t].tail;
+            int64_t room = (int64_t)a.v.pending - (int64_t)(tail - head);
+            start = (int)(tail % (uint64_t)a.v.pending);
             for (int b = 0; b < nb; b++) {
-                const int len = nfr[b] + 1;
                 frames += nfr[b];
-                if (len <= room) {
-                    const int slot = ring_slot(start, off, a.pending);
-                    a.ready[(size_t)t * a.pending + slot] = a.ready_at;
-                    a.blen[(size_t)t * a.pending + slot] = len;
-                    base[b] = off; off += len; room -= len;
-                } else {
-                    base[b] = -2; dropped++;
-                }
+                base[b] = burst_ring_place(a.v, t, nfr[b] + 1, a.ready_at, start, off, room);
+                dropped += base[b] < 0;
             }
-            a.rs[t].tail = tail + (uint64_t)off;
-            a.rs[t].dropped += dropped;
+            a.v.rs[t].tail = tail + (uint64_t)off;
+            a.v.rs[t].dropped += dropped;
         } else {
             for (int b = 0; b < nb; b++) { frames += nfr[b]; base[b] = -2; unrouted++; }
         }
         s_start = start;
         a.cnt[c].bursts += nb; a.cnt[c].frames += frames; a.cnt[c].unrouted += unrouted;
     };
-    repeat_stream(a.in, c, status, place, [&](int base, int j) { return base >= 0 ? ring + (size_t)ring_slot(s_start, base + j, a.pending) * rl : nullptr; });
+    repeat_stream(a.in, c, status, place, [&](int base, int j) { return base >= 0 ? burst_ring_record(a.v, t, s_start, base + j) : nullptr; });
     nfilt = wave_sum(nfilt);
     if (threadIdx.x == 0) a.cnt[c].filtered += nfilt;
-}
-
-struct OfferArgs {
-    RptRing *rs;                           // [ntx]
-    const uint8_t *ring; const int64_t *ready; const int32_t *blen;
-    const TxsChanState *queue; int64_t queue_syms;           // section K's queues: free space = queue_syms - (tail - head)
-    const int32_t *gap;                    // [ntx] tx's gaps (device)
-    uint8_t *rec; int32_t *nrec;           // [ntx][pending][1 + kb] and [ntx]: what section K's send path reads
-    int pending, rl, psyms, fsyms;
-    int64_t now;                           // n
-};
-
-// Every lane walks the ring's bursts from the head (the same loads and the same decisions in all of them: no divergence), then the wave
-// copies the taken records out of the ring, across its wrap, into the channel's row.
-__global__ __launch_bounds__(64) void rpt_offer_kernel(OfferArgs a)
-{
-    const int t = blockIdx.x, lane = threadIdx.x;
-    const uint64_t head = a.rs[t].head, tail = a.rs[t].tail;
-    int64_t room = a.queue_syms - (int64_t)(a.queue[t].tail - a.queue[t].head);
-    const int gap = a.gap[t] > 0 ? a.gap[t] : 0;              // tx_layout_kernel's rule
-    const int64_t first_syms = tx_record_syms(1, a.psyms, a.fsyms, gap), next_syms = tx_record_syms(0, a.psyms, a.fsyms, gap);
-    const int start = (int)(head % (uint64_t)a.pending);
-    int take = 0, bursts = 0;
-    while (head + (uint64_t)take < tail) {
-        const int slot = ring_slot(start, take, a.pending);
-        const int len = a.blen[(size_t)t * a.pending + slot];
-        if (len < 2 || take + len > a.pending || a.ready[(size_t)t * a.pending + slot] > a.now) break;
-        const int64_t cost = first_syms + (len - 2) * next_syms + tx_record_syms(2, a.psyms, a.fsyms, gap);     // records 1, 0, ..., 0, 2
-        if (cost > room) break;                              // head of the line: the bursts behind it wait
-        room -= cost; take += len; bursts++;
-    }
-    const uint8_t *ring = a.ring + (size_t)t * a.pending * a.rl;
-    uint8_t *out = a.rec + (size_t)t * a.pending * a.rl;
-    const int first = (a.pending - start) * a.rl;            // bytes up to the end of the ring
-    for (int i = lane; i < take * a.rl; i += 64) out[i] = i < first ? ring[(size_t)start * a.rl + i] : ring[i - first];
-    if (lane == 0) {
-        a.rs[t].head = head + (uint64_t)take;
-        a.rs[t].bursts_out += bursts;
-        a.nrec[t] = take;
-    }
 }
 
 int rpt_clear(pirip_hip_rpt *r, hipStream_t st)
 {
     PIRIP_HIPCHK(hipMemsetAsync(r->d_state, 0, sizeof(int32_t) * 2 * (size_t)r->nrx, st));
     PIRIP_HIPCHK(hipMemsetAsync(r->d_cnt, 0, sizeof(RptRxCount) * (size_t)r->nrx, st));
-    PIRIP_HIPCHK(hipMemsetAsync(r->d_ring_state, 0, sizeof(RptRing) * (size_t)r->ntx, st));
-    PIRIP_HIPCHK(hipMemsetAsync(r->d_noffered, 0, sizeof(int32_t) * (size_t)r->ntx, st));
+    PIRIP_TRY(r->rings.clear(st));
     r->calls = 0;
     return PIRIP_OK;
 }
 
 int rpt_alloc(pirip_hip_rpt *r, const int32_t *route)
 {
-    const size_t nrx = (size_t)r->nrx, ntx = (size_t)r->ntx, P = (size_t)r->pending, rl = 1 + (size_t)r->kb;
+    const size_t nrx = (size_t)r->nrx;
     DevMem &m = r->mem;
     PIRIP_TRY(m.upload(&r->d_route, route, sizeof(int32_t) * nrx));
     PIRIP_TRY(m.alloc(&r->d_state, sizeof(int32_t) * 2 * nrx));
     PIRIP_TRY(m.alloc_filled(&r->d_held, 0, nrx * (size_t)r->max_burst * (size_t)r->kb));
     PIRIP_TRY(m.alloc(&r->d_cnt, sizeof(RptRxCount) * nrx));
-    PIRIP_TRY(m.alloc(&r->d_ring_state, sizeof(RptRing) * ntx));
-    PIRIP_TRY(m.alloc_filled(&r->d_ring, 0, ntx * P * rl));
-    PIRIP_TRY(m.alloc_filled(&r->d_ready, 0, sizeof(int64_t) * ntx * P));
-    PIRIP_TRY(m.alloc_filled(&r->d_blen, 0, sizeof(int32_t) * ntx * P));
-    PIRIP_TRY(m.alloc_filled(&r->d_offered, 0, ntx * P * rl));
-    PIRIP_TRY(m.alloc(&r->d_noffered, sizeof(int32_t) * ntx));
+    PIRIP_TRY(r->rings.alloc(m, r->ntx, r->pending, 1 + r->kb));
     if (r->rx) {
         const size_t R = (size_t)r->rx_rows;
         PIRIP_TRY(m.alloc_filled(&r->d_status, 0, nrx * R));
@@ -168,24 +111,13 @@ int rpt_alloc(pirip_hip_rpt *r, const int32_t *route)
 int rpt_run(pirip_hip_rpt *r, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride, const int32_t *d_ncalls,
             int ncalls, void *d_out, size_t out_stride_bytes, hipStream_t st)
 {
-    const pirip_hip_tx *tx = r->tx;
     IntakeArgs ia{};
     ia.in = RepeatIn{d_status, status_stride, d_payload, payload_stride, d_ncalls, ncalls, r->d_state, r->d_held, r->kb, r->max_burst, r->source};
-    ia.route = r->d_route; ia.cnt = r->d_cnt; ia.rs = r->d_ring_state;
-    ia.ring = r->d_ring; ia.ready = r->d_ready; ia.blen = r->d_blen;
-    ia.pending = r->pending; ia.filter = r->filter;
+    ia.route = r->d_route; ia.cnt = r->d_cnt; ia.v = r->rings.view();
+    ia.filter = r->filter;
     ia.ready_at = r->calls + r->holdoff;
     hipLaunchKernelGGL(rpt_intake_kernel, dim3((unsigned)r->nrx), dim3(64), repeat_lds_bytes(ncalls), st, ia);
-    OfferArgs oa{};
-    oa.rs = r->d_ring_state; oa.ring = r->d_ring; oa.ready = r->d_ready; oa.blen = r->d_blen;
-    oa.queue = r->txs->d_state; oa.queue_syms = r->txs->queue_syms; oa.gap = tx->d_gap;
-    oa.rec = r->d_offered; oa.nrec = r->d_noffered;
-    oa.pending = r->pending; oa.rl = 1 + r->kb; oa.psyms = tx_pre_syms(tx); oa.fsyms = tx_frame_syms(tx);
-    oa.now = r->calls;
-    hipLaunchKernelGGL(rpt_offer_kernel, dim3((unsigned)r->ntx), dim3(64), 0, st, oa);
-    PIRIP_HIPCHK(hipGetLastError());
-    PIRIP_TRY(pirip_hip_txs_send(r->txs, r->d_offered, (size_t)r->pending * (size_t)(1 + r->kb), r->d_noffered, r->pending, nullptr, st));
-    PIRIP_TRY(pirip_hip_txs_process(r->txs, d_out, out_stride_bytes, nullptr, st));
+    PIRIP_TRY(r->rings.offer_and_process(r->tx, r->txs, r->calls, d_out, out_stride_bytes, st));
     r->calls++;
     return PIRIP_OK;
 }
@@ -227,10 +159,7 @@ int pirip_hip_rpt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs,
         if (rows > kRepeatMaxCalls) return PIRIP_ERR_UNSUPPORTED;
         rx_rows = (int)rows;
     }
-    // what section K's send path asks of rows of pending_records records
-    int64_t cap = tx_row_syms(tx, pending_records, 0);
-    if (cap < 1) cap = 1;
-    PIRIP_TRY(tx_frame_check(tx, (size_t)pending_records * (size_t)(1 + kb), pending_records, (size_t)cap, cap, false, 0));
+    PIRIP_TRY(burst_rings_check(tx, pending_records));
     if (!bind_device(tx->device)) return PIRIP_ERR_NO_DEVICE;
     pirip_hip_rpt *r = new (std::nothrow) pirip_hip_rpt();
     if (!r) return PIRIP_ERR_NOMEM;
@@ -310,9 +239,9 @@ int pirip_hip_rpt_records(pirip_hip_rpt *r, const uint8_t **d_status, size_t *st
 int pirip_hip_rpt_offered(pirip_hip_rpt *r, const uint8_t **d_records, size_t *rec_stride, const int32_t **d_nrec)
 {
     if (!r) return PIRIP_ERR_BAD_ARG;
-    if (d_records) *d_records = r->d_offered;
-    if (rec_stride) *rec_stride = (size_t)r->pending * (size_t)(1 + r->kb);
-    if (d_nrec) *d_nrec = r->d_noffered;
+    if (d_records) *d_records = r->rings.d_offered;
+    if (rec_stride) *rec_stride = r->rings.row_bytes();
+    if (d_nrec) *d_nrec = r->rings.d_noffered;
     return PIRIP_OK;
 }
 
@@ -321,9 +250,9 @@ int pirip_hip_rpt_get_counters(pirip_hip_rpt *r, int64_t *bursts_in, int64_t *fr
 {
     if (!r) return PIRIP_ERR_BAD_ARG;
     std::vector<RptRxCount> rc((size_t)r->nrx);
-    std::vector<RptRing> rs((size_t)r->ntx);
+    std::vector<BurstRing> rs((size_t)r->ntx);
     PIRIP_TRY(read_back(r->device, r->d_cnt, rc));
-    PIRIP_TRY(read_back(r->device, r->d_ring_state, rs));
+    PIRIP_TRY(read_back(r->device, r->rings.d_state, rs));
     for (size_t c = 0; c < rc.size(); c++) {
         if (bursts_in) bursts_in[c] = rc[c].bursts;
         if (frames_in) frames_in[c] = rc[c].frames;
