@@ -1312,6 +1312,75 @@ int pirip_hip_pkt_reset(pirip_hip_pkt *pkt, void *hip_stream);
 /* One HIP stream per handle: open packets, rings and counters are device state advanced in stream order, the call index is host state
  * advanced when a call is enqueued. */
 
+/* Parity fragments (opt-in, per handle). The link loses frames, and a plain handle loses the packet with any of them.
+ * A handle created with pirip_hip_pkt_create_fec sends, behind the k = nfrag data fragments of a packet, r(k) = max(1, min(max_parity,
+ * ceil(k * parity_pct / 100))) parity fragments, and puts a packet together from any k of its k + r fragments. Both ends are configured
+ * alike. There is still no acknowledgement and no retransmission.
+ *   Data fragments are a plain handle's, header and body, except that the padding behind the CRC-32 in the last fragment is not zeros:
+ *   body byte q of the packet (q counted over its k * cap body bytes, q >= L + 4) is pad(id, q), in uint32 arithmetic
+ *       x = ((id << 16) | q) * 2654435761u; x ^= x >> 16; x *= 2246822519u; x ^= x >> 13; pad = x >> 24
+ *   so that a short last fragment is no run of equal symbols. No reader looks at these bytes.
+ *   Parity fragment j (0 <= j < r) has idx = k + j, nfrag = k, the packet's src, dst and id, and len = the last data fragment's len: the
+ *   packet's length is known whenever one parity fragment is. Its cap body bytes are P_j[b] = XOR_i C[j][i] * D_i[b], b = 0 .. cap - 1,
+ *   over the full cap-byte bodies D_i of the data fragments as sent, CRC-32 and padding included, in GF(2^8) with the polynomial
+ *   x^8 + x^4 + x^3 + x^2 + 1 (0x11D). C is the Cauchy matrix C[j][i] = 1 / (j XOR (max_parity + i)), 0 <= j < max_parity, 0 <= i <
+ *   max_frags, of which a packet uses the first r(k) rows and k columns: every square submatrix of it is regular. The header bytes
+ *   are not covered: a repeater rewrites src and the parity stays valid.
+ *   One packet is one burst of k + r frames and the `2` record, placed whole: k + r + 1 records of room, else `refused`.
+ * A plain handle receives an undamaged burst of an FEC handle as before and then counts its r parity frames malformed; an FEC handle
+ * receives a plain sender's burst, for which no parity is needed when nothing is lost.
+ *
+ * Step 1 of a call on an FEC handle. The channel carries the key {src, id, nfrag} of one packet, a phase (none / collecting / closed),
+ * a bitmap of the k + r fragments seen and their count, lastlen (the last data fragment's len, 0 = not yet stated) and an assembly
+ * buffer of (max_frags + max_parity) * cap bytes with fragment idx at idx * cap. Every row goes through these rules, in this order:
+ *    A. a row without PIRIP_RX_SYNC changes nothing and counts nothing (unlike rule a: a fade that drops sync in the middle of a burst is
+ *       what the parity is for);
+ *    B. a row with PIRIP_RX_BITS whose byte 0 is filter_byte loses BITS (filtered);
+ *    C. a row without BITS is done;
+ *    D. a bad header counts malformed and the row is done, nothing else changes: nfrag outside 1 .. max_frags; idx >= nfrag + r(nfrag);
+ *       a data fragment (idx < nfrag) with len outside 1 .. cap, or with len != cap when it is not the last; a parity fragment with len
+ *       outside 1 .. cap; a fragment that states lastlen (the last data fragment or a parity fragment) differently from the lastlen that
+ *       the packet being collected, if the fragment's key is its key, already holds;
+ *    E. with address >= 0, a dst that is neither address nor 0xFF counts foreign, and the row is done;
+ *    F. the key is the channel's and the phase is closed: surplus, done. The key is the channel's, the phase collecting and the
+ *       fragment's bit set: duplicate, done. The key is the channel's, the phase collecting and the bit clear: store. Any other key:
+ *       a packet being collected is counted incomplete, the channel's state opens on this fragment -- any fragment may open a packet
+ *       -- and stores it. Store: all cap body bytes go to the buffer, the bit is set, the count goes up, and the last data fragment
+ *       or a parity fragment sets lastlen;
+ *    G. when the count reaches k the phase becomes closed. The m missing data fragments are rebuilt from the m parity fragments present
+ *       (there are exactly m): S_p = P_p XOR XOR_{i present} C[p][i] * D_i per parity row p, then the m x m system over the missing
+ *       columns is solved by Gauss-Jordan elimination. L = (k - 1) * cap + lastlen - 4; L < 1 or a CRC-32 that does not match counts
+ *       crc_fail, else the packet is delivered exactly as by rule h (entry, data ring, row = this row), and with m > 0 recovered
+ *       goes up by 1 and repaired by m.
+ * One packet is open per channel: fragments of two senders interleaved on one channel throw each other out, which is counted
+ * incomplete. A packet whose key is that of the packet before it on the channel (the same sender, nfrag and id, 256 packets on with
+ * nothing heard between) is taken for surplus.
+ * The two structures are written as the three above are and are held to their twins -- binding.PktFecConfig, PktFecInfo -- by
+ * tests/test_packet_fec_cpu.py. */
+struct pirip_pkt_fec_config {
+    int max_parity;             /* R, 1..16: parity fragments of a packet at most */
+    int parity_pct;             /* 1..100: parity fragments per 100 data fragments, rounded up */
+};
+typedef struct pirip_pkt_fec_config pirip_pkt_fec_config;
+struct pirip_pkt_fec_info {
+    int enabled, max_parity, parity_pct;
+    int max_burst_frames;       /* max_frags + r(max_frags); max_frags on a plain handle */
+};
+typedef struct pirip_pkt_fec_info pirip_pkt_fec_info;
+/* pirip_hip_pkt_create with parity fragments: every rule of it, and fec NULL, max_parity outside 1 .. 16, parity_pct outside 1 .. 100,
+ * max_frags + max_parity > PIRIP_TX_REPEAT_MAX_FRAMES (a repeater can hold any burst whole, and idx stays a byte), pending_records <
+ * max_burst_frames + 1 and a txs whose queue_syms does not hold one burst of max_burst_frames frames (preamble_syms + max_burst_frames *
+ * frame_syms + tx's largest gap) are PIRIP_ERR_BAD_ARG. max_packet is max_frags * cap - 4 as before. Every other entry point of this
+ * section works on the handle unchanged; pirip_hip_pkt_get_counters reports orphan = 0 on it, always. */
+int pirip_hip_pkt_create_fec(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, const pirip_pkt_config *cfg,
+                             const pirip_pkt_fec_config *fec, pirip_hip_pkt **out);
+/* enabled = 0 on a plain handle (max_parity = parity_pct = 0, max_burst_frames = max_frags). */
+int pirip_hip_pkt_get_fec_info(const pirip_hip_pkt *pkt, pirip_pkt_fec_info *info);
+/* Host copies (synchronises the device), each may be NULL, per receive channel [nrx]: packets delivered that needed a decode, data
+ * fragments rebuilt in them, fragments seen twice while their packet was collected, fragments of a packet that was closed already.
+ * PIRIP_ERR_BAD_ARG on a plain handle. */
+int pirip_hip_pkt_get_fec_counters(pirip_hip_pkt *pkt, int64_t *recovered, int64_t *repaired, int64_t *duplicate, int64_t *surplus);
+
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */
 /*             names and signatures as codec2 src/fsk.h [UPSTREAM-RECALLED]              */

@@ -166,6 +166,15 @@ class PktInfo(C.Structure):
                                        "cap", "max_packet", "has_rx", "rx_rows", "data_bytes", "device")]
 
 
+class PktFecConfig(C.Structure):
+    """pirip_pkt_fec_config: parity fragments of a packet at most (1 .. 16), parity fragments per 100 data fragments (1 .. 100)"""
+    _fields_ = [(n, C.c_int) for n in ("max_parity", "parity_pct")]
+
+
+class PktFecInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("enabled", "max_parity", "parity_pct", "max_burst_frames")]
+
+
 # pirip_spec_band_row as a numpy structured dtype (12 bytes, the C layout): what HipSpectrum.push's band entries are on the host
 SPEC_BAND_ROW_DTYPE = [("power", "<f4"), ("peak", "<f4"), ("peak_bin", "<i4")]
 
@@ -366,6 +375,9 @@ def _signatures():
         "pirip_hip_pkt_get_counters": (i32, [vp] + [vp] * 12),
         "pirip_hip_pkt_get_packets": (i32, [vp, i32, vp, vp, i32, P(i32)]),
         "pirip_hip_pkt_reset": (i32, [vp, vp]),
+        "pirip_hip_pkt_create_fec": (i32, [vp, vp, vp, P(PktConfig), P(PktFecConfig), P(vp)]),
+        "pirip_hip_pkt_get_fec_info": (i32, [vp, P(PktFecInfo)]),
+        "pirip_hip_pkt_get_fec_counters": (i32, [vp] + [vp] * 4),
         # the library itself
         "pirip_hip_find_code": (i32, [cs, cs, sz]),
         "pirip_hip_version": (cs, []),

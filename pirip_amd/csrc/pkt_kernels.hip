@@ -5,6 +5,8 @@
 //   reassemble: records --pkt_rx_kernel (one wave per receive channel)--> open packet, assembly buffer --> entry ring, data ring, counters
 //   offer:      pending ring --burst_offer_kernel--> record rows --section K's send path--> symbol queue
 //   process:    pirip_hip_txs_process
+// A handle with parity fragments (pirip_hip_pkt_create_fec) has pkt_fec_kernels.hip's two kernels in the places of the first two; the
+// host code here is the same for both kinds.
 //
 // Both kernels make their decisions in every lane alike (the values they decide on are read into scalars: every branch on them is a
 // scalar branch) and spread the bytes over the lanes: a fragment's body, a burst's records, a packet's CRC-32 (pkt_device.hpp). The call index n is host state advanced
@@ -18,6 +20,7 @@
 
 #include "../../include/pirip_hip.h"
 #include "burst_ring.hpp"
+#include "gf256_device.hpp"
 #include "hip_host.hpp"
 #include "ldpc_handle.hpp"
 #include "mux_handle.hpp"
@@ -34,19 +37,9 @@ namespace {
 
 constexpr int kPktMaxRows = kRepeatMaxCalls;                 // rows per channel and call, section M's limit
 
-struct SendArgs {
-    const uint8_t *bytes; size_t chan_stride, pkt_stride;    // packet j of channel t at bytes + t * chan_stride + j * pkt_stride
-    const int32_t *npk; int max_pk;        // packets per channel (NULL: max_pk), at most max_pk
-    const int32_t *len; const uint8_t *dst;                  // [ntx][max_pk]
-    int32_t *taken;                        // [ntx] or NULL
-    PktTxState *state;                     // [ntx]
-    BurstRingView v;
-    int kb, cap, max_packet, source;
-};
-
 // One wave per transmit channel, packet after packet: every lane decides alike, the wave computes the CRC-32 and writes the burst's
 // records into the ring, across its wrap. A packet that is refused ends the channel's call: what was taken is a prefix.
-__global__ __launch_bounds__(64) void pkt_send_kernel(SendArgs a)
+__global__ __launch_bounds__(64) void pkt_send_kernel(PktSendArgs a)
 {
     const int t = blockIdx.x, lane = threadIdx.x;
     const int n = __builtin_amdgcn_readfirstlane(row_count(a.npk, (size_t)t, a.max_pk)), rl = a.v.rl;
@@ -92,25 +85,11 @@ __global__ __launch_bounds__(64) void pkt_send_kernel(SendArgs a)
     }
 }
 
-struct RxArgs {
-    const uint8_t *status; size_t status_stride; const uint8_t *payload; size_t payload_stride;      // [nrx][rows], [nrx][rows][kb]
-    const int32_t *nrows; int max_rows;    // rows per channel (NULL: max_rows), at most max_rows
-    int kb, cap, max_frags, max_packet, filter, address, ring_entries;
-    int32_t call;                          // n
-    PktRxState *state;                     // [nrx]
-    uint8_t *assembly;                     // [nrx][max_frags * cap]
-    pirip_pkt_entry *entries;              // [nrx][ring_entries]
-    uint8_t *data;                         // [nrx][ring_entries][max_packet]
-};
-
-// dynamic LDS of a launch over max_rows rows: two words per row, the status byte and the six header bytes
-constexpr size_t pkt_rx_lds_bytes(int max_rows) { return 8 * (size_t)max_rows; }
-
 // One wave per receive channel. The rows' status and header bytes are staged in LDS by all lanes; then every lane walks the rows through
 // the rules of the header alike, and where a rule moves bytes -- a fragment's body into the assembly buffer, a finished packet into the
 // data ring -- or checks them -- the CRC-32 -- the wave does it together. The assembly buffer is global memory that this wave alone
 // writes and reads: the barrier in front of the check makes the fragments' stores visible to the lanes that read them.
-__global__ __launch_bounds__(64) void pkt_rx_kernel(RxArgs a)
+__global__ __launch_bounds__(64) void pkt_rx_kernel(PktRxArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) uint32_t s_rows[];
     const size_t c = blockIdx.x;
@@ -189,6 +168,7 @@ __global__ __launch_bounds__(64) void pkt_rx_kernel(RxArgs a)
 int pkt_clear(pirip_hip_pkt *p, hipStream_t st)
 {
     PIRIP_HIPCHK(hipMemsetAsync(p->d_rx_state, 0, sizeof(PktRxState) * (size_t)p->nrx, st));
+    if (p->max_parity) PIRIP_HIPCHK(hipMemsetAsync(p->d_fec_state, 0, sizeof(PktFecState) * (size_t)p->nrx, st));
     PIRIP_HIPCHK(hipMemsetAsync(p->d_entries, 0, sizeof(pirip_pkt_entry) * (size_t)p->nrx * (size_t)p->ring_entries, st));
     if (p->tx) {
         PIRIP_HIPCHK(hipMemsetAsync(p->d_tx_state, 0, sizeof(PktTxState) * (size_t)p->ntx, st));
@@ -203,7 +183,15 @@ int pkt_alloc(pirip_hip_pkt *p)
     const size_t nrx = (size_t)p->nrx, kb = (size_t)p->kb, E = (size_t)p->ring_entries;
     DevMem &m = p->mem;
     PIRIP_TRY(m.alloc(&p->d_rx_state, sizeof(PktRxState) * nrx));
-    PIRIP_TRY(m.alloc_filled(&p->d_asm, 0, nrx * (size_t)p->max_frags * (size_t)p->cap));
+    PIRIP_TRY(m.alloc_filled(&p->d_asm, 0, nrx * (size_t)(p->max_frags + p->max_parity) * (size_t)p->cap));
+    if (p->max_parity) {
+        PIRIP_TRY(m.alloc(&p->d_fec_state, sizeof(PktFecState) * nrx));
+        std::vector<uint8_t> cm((size_t)p->max_parity * (size_t)p->max_frags);
+        for (int j = 0; j < p->max_parity; j++)
+            for (int i = 0; i < p->max_frags; i++) cm[(size_t)j * p->max_frags + i] = gf256_cauchy(p->max_parity, j, i);
+        PIRIP_TRY(m.alloc(&p->d_cauchy, cm.size()));
+        PIRIP_HIPCHK(hipMemcpy(p->d_cauchy, cm.data(), cm.size(), hipMemcpyHostToDevice));
+    }
     PIRIP_TRY(m.alloc(&p->d_entries, sizeof(pirip_pkt_entry) * nrx * E));
     PIRIP_TRY(m.alloc_filled(&p->d_data, 0, nrx * E * (size_t)p->max_packet));
     if (p->tx) {
@@ -235,15 +223,20 @@ int pkt_check_out(const pirip_hip_pkt *p, const void *d_out, size_t out_stride_b
 int pkt_run(pirip_hip_pkt *p, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride, const int32_t *d_ncalls,
             int ncalls, void *d_out, size_t out_stride_bytes, hipStream_t st)
 {
-    RxArgs ra{};
+    PktRxArgs ra{};
     ra.status = d_status; ra.status_stride = status_stride; ra.payload = d_payload; ra.payload_stride = payload_stride;
     ra.nrows = d_ncalls; ra.max_rows = ncalls;
     ra.kb = p->kb; ra.cap = p->cap; ra.max_frags = p->max_frags; ra.max_packet = p->max_packet; ra.filter = p->filter; ra.address = p->address;
     ra.ring_entries = p->ring_entries;
     ra.call = (int32_t)p->calls;
     ra.state = p->d_rx_state; ra.assembly = p->d_asm; ra.entries = p->d_entries; ra.data = p->d_data;
-    hipLaunchKernelGGL(pkt_rx_kernel, dim3((unsigned)p->nrx), dim3(64), pkt_rx_lds_bytes(ncalls), st, ra);
-    PIRIP_HIPCHK(hipGetLastError());
+    ra.max_parity = p->max_parity; ra.parity_pct = p->parity_pct; ra.fec = p->d_fec_state; ra.cauchy = p->d_cauchy;
+    if (p->max_parity) {
+        PIRIP_TRY(pkt_fec_launch_rx(ra, p->nrx, st));
+    } else {
+        hipLaunchKernelGGL(pkt_rx_kernel, dim3((unsigned)p->nrx), dim3(64), pkt_rx_lds_bytes(ncalls), st, ra);
+        PIRIP_HIPCHK(hipGetLastError());
+    }
     if (p->tx) PIRIP_TRY(p->rings.offer_and_process(p->tx, p->txs, p->calls, d_out, out_stride_bytes, st));
     p->calls++;
     return PIRIP_OK;
@@ -267,9 +260,9 @@ int pkt_receive(pirip_hip_pkt *p, const void *d_in, size_t in_stride_bytes, void
 
 }  // namespace
 
-extern "C" {
-
-int pirip_hip_pkt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, const pirip_pkt_config *cfg, pirip_hip_pkt **out)
+// fec == NULL: a plain handle, whose largest burst is max_frags frames; else max_frags + r(max_frags)
+int pirip::pkt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, const pirip_pkt_config *cfg, const pirip_pkt_fec_config *fec,
+                      pirip_hip_pkt **out)
 {
     if (!out) return PIRIP_ERR_BAD_ARG;
     *out = nullptr;
@@ -278,11 +271,15 @@ int pirip_hip_pkt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs,
     if (cfg->nrx < 1 || cfg->source_byte < 0 || cfg->source_byte > 255 || cfg->filter_byte < -1 || cfg->filter_byte > 255 || cfg->address < -1 ||
         cfg->address > 255)
         return PIRIP_ERR_BAD_ARG;
-    if (cfg->max_frags < 1 || cfg->max_frags > PIRIP_TX_REPEAT_MAX_FRAMES || cfg->pending_records < cfg->max_frags + 1 || cfg->ring_entries < 1)
+    if (cfg->max_frags < 1 || cfg->max_frags > PIRIP_TX_REPEAT_MAX_FRAMES || cfg->ring_entries < 1) return PIRIP_ERR_BAD_ARG;
+    if (fec && (fec->max_parity < 1 || fec->max_parity > kPktMaxParity || fec->parity_pct < 1 || fec->parity_pct > 100 ||
+                cfg->max_frags + fec->max_parity > PIRIP_TX_REPEAT_MAX_FRAMES))
         return PIRIP_ERR_BAD_ARG;
+    const int burst_frames = cfg->max_frags + (fec ? pkt_fec_r(cfg->max_frags, fec->max_parity, fec->parity_pct) : 0);
+    if (cfg->pending_records < burst_frames + 1) return PIRIP_ERR_BAD_ARG;
     const int ntx = tx ? tx->nstreams : 0;
     int kb = tx ? tx->code.data_bytes() : 0, device = tx ? tx->device : 0, rx_rows = 0;
-    if (tx && tx_pre_syms(tx) + (int64_t)cfg->max_frags * tx_frame_syms(tx) + tx->max_gap > txs->queue_syms) return PIRIP_ERR_BAD_ARG;
+    if (tx && tx_pre_syms(tx) + (int64_t)burst_frames * tx_frame_syms(tx) + tx->max_gap > txs->queue_syms) return PIRIP_ERR_BAD_ARG;
     if (rx) {
         int ns = 0, dev = 0;
         const pirip_hip_ldpc *ldpc = nullptr;
@@ -302,10 +299,18 @@ int pirip_hip_pkt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs,
     p->source = cfg->source_byte; p->filter = cfg->filter_byte; p->address = cfg->address; p->max_frags = cfg->max_frags;
     p->pending = cfg->pending_records; p->ring_entries = cfg->ring_entries; p->cap = pkt_cap(kb); p->max_packet = pkt_max_packet(kb, cfg->max_frags);
     p->rx_rows = rx_rows;
+    if (fec) { p->max_parity = fec->max_parity; p->parity_pct = fec->parity_pct; }
     const int rc = pkt_alloc(p);
     if (rc != PIRIP_OK) { delete p; return rc; }
     *out = p;
     return PIRIP_OK;
+}
+
+extern "C" {
+
+int pirip_hip_pkt_create(pirip_hip_rx *rx, pirip_hip_tx *tx, pirip_hip_txs *txs, const pirip_pkt_config *cfg, pirip_hip_pkt **out)
+{
+    return pkt_create(rx, tx, txs, cfg, nullptr, out);
 }
 
 int pirip_hip_pkt_destroy(pirip_hip_pkt *p) { return destroy_handle(p, p ? p->device : 0); }
@@ -323,10 +328,12 @@ int pirip_hip_pkt_send(pirip_hip_pkt *p, const uint8_t *d_bytes, size_t chan_str
 {
     if (!p || !p->tx || !d_bytes || !d_len || !d_dst || max_pk < 0) return PIRIP_ERR_BAD_ARG;
     if (!bind_device(p->device)) return PIRIP_ERR_NO_DEVICE;
-    SendArgs sa{};
+    PktSendArgs sa{};
     sa.bytes = d_bytes; sa.chan_stride = chan_stride; sa.pkt_stride = pkt_stride; sa.npk = d_npk; sa.max_pk = max_pk; sa.len = d_len; sa.dst = d_dst;
     sa.taken = d_taken; sa.state = p->d_tx_state; sa.v = p->rings.view();
     sa.kb = p->kb; sa.cap = p->cap; sa.max_packet = p->max_packet; sa.source = p->source;
+    sa.max_frags = p->max_frags; sa.max_parity = p->max_parity; sa.parity_pct = p->parity_pct; sa.cauchy = p->d_cauchy;
+    if (p->max_parity) return pkt_fec_launch_send(sa, p->ntx, (hipStream_t)hip_stream);
     hipLaunchKernelGGL(pkt_send_kernel, dim3((unsigned)p->ntx), dim3(64), 0, (hipStream_t)hip_stream, sa);
     PIRIP_HIPCHK(hipGetLastError());
     return PIRIP_OK;

@@ -4,7 +4,7 @@ import ctypes as C
 
 import numpy as np
 
-from .binding import PKT_ENTRY_DTYPE, PktConfig, PktEntry, PktInfo, _dev, _hip_stream, _ptr_of, _Terminal
+from .binding import PKT_ENTRY_DTYPE, PktConfig, PktEntry, PktFecConfig, PktFecInfo, PktInfo, _dev, _hip_stream, _ptr_of, _Terminal
 
 
 class HipPacket(_Terminal):
@@ -26,15 +26,22 @@ class HipPacket(_Terminal):
         if nrx is None:
             nrx = rx.nstreams if rx is not None else 0
         if pending is None:
-            pending = 2 * (int(max_frags) + 1)
+            pending = 2 * (self._burst_frames(int(max_frags)) + 1)
         cfg = PktConfig(int(nrx), int(source), -1 if filter is None else int(filter), -1 if address is None else int(address), int(max_frags),
                         int(pending), int(ring_entries))
-        name = "pirip_hip_pkt_create"
-        self._create(name, _ptr_of(rx, name), _ptr_of(tx, name), _ptr_of(txs, name), C.byref(cfg))
+        self._create_link(rx, tx, txs, cfg)
         i = self.info
         self.nrx, self.nchan, self.rx_rows, self.data_bytes, self.ring_entries = i.nrx, i.nchan, i.rx_rows, i.data_bytes, i.ring_entries
         self.cap, self.max_packet, self.max_frags, self.pending = i.cap, i.max_packet, i.max_frags, i.pending_records
         self._staged = None
+
+    def _burst_frames(self, max_frags):
+        """frames of the largest burst"""
+        return max_frags
+
+    def _create_link(self, rx, tx, txs, cfg):
+        name = "pirip_hip_pkt_create"
+        self._create(name, _ptr_of(rx, name), _ptr_of(tx, name), _ptr_of(txs, name), C.byref(cfg))
 
     def send(self, packets, dst, lengths=None, npk=None, taken=None, stream=None):
         """Hand packets to the transmit channels. Either packets is a list with one list of bytes objects per channel and dst an int or a
@@ -110,3 +117,38 @@ class HipPacket(_Terminal):
         self._call("pirip_hip_pkt_get_packets", int(chan), ent.ctypes.data, data.ctypes.data, n, C.byref(got))
         ent = ent[:got.value].copy()
         return ent, [data[i, :int(e["length"])].tobytes() for i, e in enumerate(ent)]
+
+
+class HipPacketFec(HipPacket):
+    """HipPacket with parity fragments (include/pirip_hip.h section R, pirip_hip_pkt_create_fec): behind the k data fragments of a packet
+    go r(k) = max(1, min(max_parity, ceil(k * parity_pct / 100))) parity fragments, and any k of the k + r put the packet together. Both
+    ends are created alike. pending defaults to two bursts of max_frags + r(max_frags) frames; txs must hold one such burst."""
+
+    FEC_COUNTERS = ("recovered", "repaired", "duplicate", "surplus")
+
+    def __init__(self, rx=None, tx=None, txs=None, nrx=None, source=1, filter=None, address=None, max_frags=84, pending=None, ring_entries=64,
+                 max_parity=16, parity_pct=20):
+        self._fec = PktFecConfig(int(max_parity), int(parity_pct))
+        super().__init__(rx, tx, txs, nrx, source, filter, address, max_frags, pending, ring_entries)
+        self.max_parity, self.parity_pct, self.max_burst_frames = int(max_parity), int(parity_pct), self.fec_info().max_burst_frames
+
+    def _burst_frames(self, max_frags):
+        r = -(-max_frags * self._fec.parity_pct // 100)
+        return max_frags + max(1, min(self._fec.max_parity, r))
+
+    def _create_link(self, rx, tx, txs, cfg):
+        name = "pirip_hip_pkt_create_fec"
+        self._create(name, _ptr_of(rx, name), _ptr_of(tx, name), _ptr_of(txs, name), C.byref(cfg), C.byref(self._fec))
+
+    def fec_info(self):
+        """PktFecInfo: enabled, max_parity, parity_pct, max_burst_frames"""
+        info = PktFecInfo()
+        self._call("pirip_hip_pkt_get_fec_info", C.byref(info))
+        return info
+
+    def fec_counters(self):
+        """dict of int64 arrays [nrx]: recovered (packets delivered that needed a decode), repaired (data fragments rebuilt in them),
+        duplicate, surplus. Synchronises."""
+        out = {k: np.zeros(self.nrx, dtype=np.int64) for k in self.FEC_COUNTERS}
+        self._call("pirip_hip_pkt_get_fec_counters", *(out[k].ctypes.data for k in self.FEC_COUNTERS))
+        return out
