@@ -1315,7 +1315,7 @@ int pirip_hip_pkt_reset(pirip_hip_pkt *pkt, void *hip_stream);
 /* Parity fragments (opt-in, per handle). The link loses frames, and a plain handle loses the packet with any of them.
  * A handle created with pirip_hip_pkt_create_fec sends, behind the k = nfrag data fragments of a packet, r(k) = max(1, min(max_parity,
  * ceil(k * parity_pct / 100))) parity fragments, and puts a packet together from any k of its k + r fragments. Both ends are configured
- * alike. There is still no acknowledgement and no retransmission.
+ * alike. There is still no acknowledgement and no retransmission in this section: section S adds them above it.
  *   Data fragments are a plain handle's, header and body, except that the padding behind the CRC-32 in the last fragment is not zeros:
  *   body byte q of the packet (q counted over its k * cap body bytes, q >= L + 4) is pad(id, q), in uint32 arithmetic
  *       x = ((id << 16) | q) * 2654435761u; x ^= x >> 16; x *= 2246822519u; x ^= x >> 13; pad = x >> 24
@@ -1380,6 +1380,121 @@ int pirip_hip_pkt_get_fec_info(const pirip_hip_pkt *pkt, pirip_pkt_fec_info *inf
  * fragments rebuilt in them, fragments seen twice while their packet was collected, fragments of a packet that was closed already.
  * PIRIP_ERR_BAD_ARG on a plain handle. */
 int pirip_hip_pkt_get_fec_counters(pirip_hip_pkt *pkt, int64_t *recovered, int64_t *repaired, int64_t *duplicate, int64_t *surplus);
+
+/* ----------------------------------------------------------------------------------- */
+/* section S : ARQ sessions (acknowledged in-order delivery with retransmission)        */
+/*   Section R loses a packet with a lost fragment and asks nobody again; parity raises   */
+/*   the threshold and does not close the loop. This section closes it: a selective-repeat */
+/*   session per channel over one packet handle, plain or FEC, whose every terminal both    */
+/*   sends and receives. ARQ segments travel as the payload of section R packets: R's wire   */
+/*   format, its src byte, --filter, parity and whitening apply unchanged.   */
+/*   No call synchronises or allocates; time is counted in calls; every byte and counter is a  */
+/*   function of the inputs. Only symbols are added: PIRIP_HIP_ABI_VERSION stands.             */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_arq pirip_hip_arq;
+/* Wire format: the payload bytes of a section R packet.
+ *   byte 0  type   0xD0 DATA, 0xA0 ACK
+ *   byte 1  seq    DATA: the segment's sequence number mod 256
+ *                  ACK:  base = the next sequence number the receiver wants in order, mod 256
+ *   DATA:   bytes 2 .. : 1 .. max_payload user bytes, max_payload = pkt's max_packet - 2
+ *   ACK:    bytes 2 .. 5: bitmap, least significant byte first; bit i set = segment base + 1 + i is held out of order
+ *           bytes 6 .. acklen - 1: filler, byte q = (31 * base + 73 * q + 0x5A) & 0xFF
+ *           acklen = max(6, min(cap - 4, max_packet)): an ACK fills its one fragment up to the CRC-32, so that it is no run of equal
+ *           symbols on a plain handle (section R). A receiver accepts an ACK of any length >= 6 and reads six bytes.
+ * The window W is 1 .. 32, so sequence numbers mod 256 are unambiguous; the state keeps absolute int64 counters.
+ * (This section's three structures are written as section R's are and are held to their twins -- binding.ArqConfig, ArqEntry, ArqInfo,
+ * ARQ_ENTRY_DTYPE -- by tests/test_arq_cpu.py.) */
+struct pirip_arq_config {
+    int window;                 /* W, 1..32: segments in flight per channel */
+    int rto_calls;              /* >= 1: calls after which an unacknowledged segment is sent again */
+    int max_tries;              /* >= 1: transmissions of one segment before the session is broken */
+    int queue_entries;          /* >= window: segments of each channel's submit queue, which is its retransmission store */
+    int out_entries;            /* >= 1: segments of each channel's output ring */
+};
+typedef struct pirip_arq_config pirip_arq_config;
+struct pirip_arq_entry {                    /* 16 bytes */
+    int64_t seq;                            /* the segment's absolute sequence number */
+    int32_t call, length;                   /* n of the call that delivered it; user bytes */
+};
+typedef struct pirip_arq_entry pirip_arq_entry;
+struct pirip_arq_info {
+    int nchan, window, rto_calls, max_tries, queue_entries, out_entries, max_payload, acklen, device;
+};
+typedef struct pirip_arq_info pirip_arq_info;
+/* A handle over one packet handle, which it borrows as the packet handle borrows rx / tx / txs: pkt must outlive it, and WHILE AN ARQ
+ * HANDLE LIVES ITS PACKET HANDLE MUST NOT BE DRIVEN DIRECTLY (send, push_records, process, push, reset); that is not enforced. Transmit
+ * channel t and receive channel t of pkt form one session with the peer address peers[t] (host int[nchan]): 0 .. 255, or -1 for "whoever
+ * answers". DATA and ACK go to dst = peers[t], or 0xFF when it is -1. PIRIP_ERR_BAD_ARG: pkt, cfg, peers or out NULL; a packet handle
+ * without tx or with nrx != nchan; window outside 1 .. 32; rto_calls < 1; max_tries < 1; queue_entries < window; out_entries < 1; a peer
+ * outside -1 .. 255; pkt's max_packet < 6. Create synchronises the device.
+ * Sessions through a section M repeater are out of scope: it rewrites src, so a terminal's own DATA would come back as the peer's. */
+int pirip_hip_arq_create(pirip_hip_pkt *pkt, const pirip_arq_config *cfg, const int *peers, pirip_hip_arq **out);
+int pirip_hip_arq_destroy(pirip_hip_arq *arq);
+int pirip_hip_arq_get_info(const pirip_hip_arq *arq, pirip_arq_info *info);
+/* Sender state of a channel: sub_nxt (segments accepted from the user), snd_nxt (segments sent at least once), snd_una (the oldest
+ * unacknowledged segment), broken, per window slot (segment s at s % W) acked, tries, due, and a segment ring of queue_entries slots of
+ * max_payload bytes with its lengths: segment s lives at slot s % queue_entries from submit until snd_una passes it.
+ * Channel t hands over d_nseg[t] (NULL = max_seg; clamped to [0, max_seg]) segments: segment j's bytes at d_bytes + t * chan_stride +
+ * j * seg_stride, its length d_len[t * max_seg + j] (int32). They are taken in order, and what is taken is a prefix: a length outside
+ * 1 .. max_payload stops the channel and raises `bad`; a full ring (sub_nxt - snd_una == queue_entries) or a broken session stops the
+ * channel and raises `refused`. d_taken[t] (may be NULL): segments taken. NULL d_bytes / d_len, max_seg < 0: PIRIP_ERR_BAD_ARG. Enqueued
+ * on hip_stream; never synchronises. */
+int pirip_hip_arq_submit(pirip_hip_arq *arq, const uint8_t *d_bytes, size_t chan_stride, size_t seg_stride, const int32_t *d_nseg, int max_seg,
+                         const int32_t *d_len, int32_t *d_taken, void *hip_stream);
+/* Call n (n = 0, 1, ... since create / reset), in stream order:
+ * 1. stage. From the session state as call n - 1 left it, each channel lists what it sends now, into a device staging area of 1 + W
+ *    packets per channel, in this order:
+ *    (a) one ACK {base = rcv_nxt, bitmap of the reorder buffer} if ack_pending;
+ *    (b) if any in-flight slot (snd_una <= s < snd_nxt) has !acked, due <= n and tries == max_tries, the session becomes broken, counted
+ *        once; a broken session stages nothing but (a);
+ *    (c) otherwise every in-flight slot with !acked and due <= n, ascending;
+ *    (d) then new segments snd_nxt .. while snd_nxt - snd_una < W and snd_nxt < sub_nxt, ascending.
+ * 2. send. pirip_hip_pkt_send from the staging area; what it takes is a prefix (section R's contract).
+ * 3. commit. The state changes of the staged items that were taken, and of those only; `deferred` goes up by the count of the others.
+ *    ACK: ack_pending = 0, acks_sent += 1. Retransmission: tries += 1, due = n + rto_calls, retransmitted += 1. New segment: tries = 1,
+ *    due = n + rto_calls, snd_nxt += 1, sent += 1.
+ * 4. the packet handle's own call of the same name with the same arguments and rules: reassemble, offer, pirip_hip_txs_process into
+ *    d_out.
+ * 5. receive. The packets step 4 delivered on each channel, in the packet ring's seq order; the handle keeps seen[c], the count of packets
+ *    it has consumed, and when delivered - seen > pkt's ring_entries the overwritten packets are skipped and counted `overrun`
+ *    (retransmission recovers them). Receiver state: rcv_nxt, a held bitmap and a reorder buffer of W slots (segment s at s % W),
+ *    ack_pending, and an output ring of out_entries slots of max_payload bytes with pirip_arq_entry entries, which overwrites its oldest
+ *    entry (lost). Each packet of length L from source src goes through these rules, in this order:
+ *    R1. L < 2, or a type that is neither 0xD0 nor 0xA0: alien, done (plain datagrams may share the channel; pkt's ring still holds them).
+ *    R2. peer[c] >= 0 and src != peer[c]: stranger, done.
+ *    R3. DATA. L < 3: malformed, done. Let d = (seq - rcv_nxt) & 255. d == 0: deliver with entry seq = rcv_nxt, call = n, and
+ *        rcv_nxt += 1, then deliver held successors while the next one is held; ack_pending = 1. 0 < d < W: a held segment counts
+ *        duplicate, another is held; ack_pending = 1. Else let back = (rcv_nxt - seq) & 255: 1 <= back <= min(W, rcv_nxt) counts
+ *        duplicate, ack_pending = 1. Else outside, done.
+ *    R4. ACK. L < 6: malformed, done. Let a = (base - snd_una) & 255. a > snd_nxt - snd_una: stale, done. Otherwise snd_una += a;
+ *        every bit i with base + 1 + i < snd_nxt sets that slot's acked; `acked` goes up by the number of segments acknowledged for the
+ *        first time, cumulatively or by bit, each once.
+ * Section R's checks of the handle, of d_status / d_payload, their strides and ncalls, of d_in and of d_out / out_stride_bytes are made
+ * before anything is enqueued; the packet handle needs rx for process / push as there. Enqueued on hip_stream; never synchronises. */
+int pirip_hip_arq_push_records(pirip_hip_arq *arq, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride,
+                               const int32_t *d_ncalls, int ncalls, void *d_out, size_t out_stride_bytes, void *hip_stream);
+int pirip_hip_arq_process(pirip_hip_arq *arq, void *d_out, size_t out_stride_bytes, void *hip_stream);
+int pirip_hip_arq_push(pirip_hip_arq *arq, const void *d_in, size_t in_stride_bytes, void *d_out, size_t out_stride_bytes, void *hip_stream);
+/* Host copies (synchronises the device), each may be NULL, per channel [nchan]. Sender: segments sent for the first time, sent again,
+ * acknowledged, ACKs sent, staged items pirip_hip_pkt_send did not take, submits stopped by a full ring or a broken session, submits
+ * stopped by a bad length, broken (0 / 1), waiting = sub_nxt - snd_nxt, inflight = snd_nxt - snd_una. Receiver: segments delivered, DATA
+ * seen before, DATA outside the window, ACKs outside the window, packets that are no segment, packets of another source, segments too
+ * short, packets the packet ring overwrote unseen, entries the output ring overwrote. */
+int pirip_hip_arq_get_counters(pirip_hip_arq *arq, int64_t *sent, int64_t *retransmitted, int64_t *acked, int64_t *acks_sent, int64_t *deferred,
+                               int64_t *refused, int64_t *bad, int64_t *broken, int64_t *waiting, int64_t *inflight, int64_t *delivered,
+                               int64_t *duplicate, int64_t *outside, int64_t *stale, int64_t *alien, int64_t *stranger, int64_t *malformed,
+                               int64_t *overrun, int64_t *lost);
+/* Host copy (synchronises the device) of the newest min(delivered, out_entries, max) entries of channel chan, oldest first, and their
+ * bytes at bytes + i * max_payload (bytes may be NULL); *written (may be NULL): how many. PIRIP_ERR_BAD_ARG as pirip_hip_pkt_get_packets. */
+int pirip_hip_arq_get_delivered(pirip_hip_arq *arq, int chan, pirip_arq_entry *entries, uint8_t *bytes, int max, int *written);
+/* Checking aid (synchronises), each pointer may be NULL: the absolute counters of channel chan, the held bitmap (bit i: segment
+ * rcv_nxt + 1 + i) and ack_pending. */
+int pirip_hip_arq_get_state(pirip_hip_arq *arq, int chan, int64_t *sub_nxt, int64_t *snd_nxt, int64_t *snd_una, int64_t *rcv_nxt,
+                            uint32_t *held, int *ack_pending);
+/* Forgets the sessions, the rings and the counters and resets the packet handle too: the next call is n = 0, the next segment 0. */
+int pirip_hip_arq_reset(pirip_hip_arq *arq, void *hip_stream);
+/* One HIP stream per handle, the packet handle's: the sessions are device state advanced in stream order, the call index is host state
+ * advanced when a call is enqueued. */
 
 /* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */

@@ -1,4 +1,4 @@
-"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J, K, L, M, N, O, P, Q and R).
+"""ctypes binding of libpirip_hip.so (include/pirip_hip.h, sections A, B, E, G, H, I, J, K, L, M, N, O, P, Q, R and S).
 
 Device buffers are passed as raw device pointers (ints): with PyTorch, ``tensor.data_ptr()``
 and ``torch.cuda.current_stream().cuda_stream``. Nothing here computes on the CPU; if the
@@ -173,6 +173,25 @@ class PktFecConfig(C.Structure):
 
 class PktFecInfo(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("enabled", "max_parity", "parity_pct", "max_burst_frames")]
+
+
+class ArqConfig(C.Structure):
+    """pirip_arq_config: segments in flight, calls until a segment is sent again, transmissions before the session is broken, segments of
+    a submit queue, segments of an output ring"""
+    _fields_ = [(n, C.c_int) for n in ("window", "rto_calls", "max_tries", "queue_entries", "out_entries")]
+
+
+class ArqEntry(C.Structure):
+    _fields_ = [("seq", C.c_int64), ("call", C.c_int32), ("length", C.c_int32)]
+
+
+# pirip_arq_entry as a numpy structured dtype (16 bytes, the C layout): what HipArq.delivered returns
+ARQ_ENTRY_DTYPE = [("seq", "<i8"), ("call", "<i4"), ("length", "<i4")]
+
+
+class ArqInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("nchan", "window", "rto_calls", "max_tries", "queue_entries", "out_entries", "max_payload", "acklen",
+                                       "device")]
 
 
 # pirip_spec_band_row as a numpy structured dtype (12 bytes, the C layout): what HipSpectrum.push's band entries are on the host
@@ -378,6 +397,18 @@ def _signatures():
         "pirip_hip_pkt_create_fec": (i32, [vp, vp, vp, P(PktConfig), P(PktFecConfig), P(vp)]),
         "pirip_hip_pkt_get_fec_info": (i32, [vp, P(PktFecInfo)]),
         "pirip_hip_pkt_get_fec_counters": (i32, [vp] + [vp] * 4),
+        # section S: ARQ sessions
+        "pirip_hip_arq_create": (i32, [vp, P(ArqConfig), vp, P(vp)]),
+        "pirip_hip_arq_destroy": (i32, [vp]),
+        "pirip_hip_arq_get_info": (i32, [vp, P(ArqInfo)]),
+        "pirip_hip_arq_submit": (i32, [vp, vp, sz, sz, vp, i32, vp, vp, vp]),
+        "pirip_hip_arq_push_records": (i32, [vp, vp, sz, vp, sz, vp, i32, vp, sz, vp]),
+        "pirip_hip_arq_process": (i32, [vp, vp, sz, vp]),
+        "pirip_hip_arq_push": (i32, [vp, vp, sz, vp, sz, vp]),
+        "pirip_hip_arq_get_counters": (i32, [vp] + [vp] * 19),
+        "pirip_hip_arq_get_delivered": (i32, [vp, i32, vp, vp, i32, P(i32)]),
+        "pirip_hip_arq_get_state": (i32, [vp, i32, P(i64), P(i64), P(i64), P(i64), P(C.c_uint32), P(i32)]),
+        "pirip_hip_arq_reset": (i32, [vp, vp]),
         # the library itself
         "pirip_hip_find_code": (i32, [cs, cs, sz]),
         "pirip_hip_version": (cs, []),
