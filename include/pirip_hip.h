@@ -1497,6 +1497,97 @@ int pirip_hip_arq_reset(pirip_hip_arq *arq, void *hip_stream);
  * advanced when a call is enqueued. */
 
 /* ----------------------------------------------------------------------------------- */
+/* section T : half-duplex medium access (carrier sense, backoff, T/R mute)             */
+/*   The reference radio is half duplex on one frequency: a terminal that transmits      */
+/*   hears itself, and two that start together destroy each other's bursts. Sections R    */
+/*   and S offer a burst in the first call in which it is due and fits. This section       */
+/*   attaches to a packet handle and decides, per call and on the device: whether a         */
+/*   receive channel carries somebody's carrier, whether the rows it brought are the own     */
+/*   transmitter's (they lose PIRIP_RX_BITS), and how many bursts the offer may take after a  */
+/*   slotted random backoff. No call synchronises or allocates; time is       */
+/*   counted in calls; every decision is a function of the inputs and the key. A packet handle  */
+/*   without this layer makes the launches and the bytes it made before. Only symbols are       */
+/*   added: PIRIP_HIP_ABI_VERSION stands.                                                        */
+/* ----------------------------------------------------------------------------------- */
+typedef struct pirip_hip_mac pirip_hip_mac;
+/* (This section's two structures are written as section R's are and are held to their twins -- binding.MacConfig, MacInfo -- by
+ * tests/test_mac_cpu.py.) */
+struct pirip_mac_config {
+    int sense_mask;             /* 1..3: bit 0 = a row with PIRIP_RX_SYNC is carrier; bit 1 = a row whose stats[5] (SNRest) >= sense_snr is carrier */
+    float sense_snr;            /* compared as the float it is; a NaN row is no carrier */
+    int slot_calls;             /* 1..2^20: calls per backoff slot */
+    int cw;                     /* 1..1024: every access draws b in [0, cw) slots */
+    int ifs_calls;              /* 0..2^30 - 1: the countdown runs only in a call that ends a run of more than ifs_calls idle calls */
+    int mute_calls;             /* 0..2^30: see step 1 */
+    int txop_bursts;            /* 1..2^30: bursts one access may put on air */
+    uint32_t key;               /* seeds the draws; the two ends of a link take different keys */
+};
+typedef struct pirip_mac_config pirip_mac_config;
+struct pirip_mac_info {
+    int ntx, nrx, sense_mask;
+    float sense_snr;
+    int slot_calls, cw, ifs_calls, mute_calls, txop_bursts;
+    uint32_t key;
+    int device;
+};
+typedef struct pirip_mac_info pirip_mac_info;
+#define PIRIP_MAC_IDLE    0
+#define PIRIP_MAC_CONTEND 1
+#define PIRIP_MAC_HOLD    2
+/* Attaches a medium-access layer to pkt, which it borrows: pkt must outlive it, must have a transmitter, and has at most one such layer.
+ * rx_of_tx (host int32 [pkt's transmit channels]): -1 for an ungated transmit channel, which is offered exactly as without the layer, or
+ * the receive channel 0 .. nrx - 1 that the transmit channel listens on and whose rows its own bursts come back in. While attached every
+ * call of pkt -- push_records, process, push, driven directly or by a section S handle -- runs steps 0 - 2 below in front of its own, in
+ * stream order; on a pkt with rx and bit 1 of sense_mask, process / push also ask the receiver for its stats rows, into a buffer this
+ * handle owns. PIRIP_ERR_BAD_ARG: pkt, cfg, rx_of_tx or out NULL; a pkt without tx or with a layer already; a configuration value outside
+ * the limits stated at pirip_mac_config; an rx_of_tx outside -1 .. nrx - 1; two transmit channels that name one receive channel. Create
+ * synchronises the device.
+ *
+ * Call n (pkt's n), per channel:
+ * 0. air, per transmit channel t: air = 1 iff section K dequeued at least one symbol of t in call n - 1's process (PIRIP_TX_CARRIER_OFF
+ *    symbols inside a burst count: the antenna switch stays on Tx); 0 in this layer's first call. quiet[t] = 0 if air, else
+ *    min(quiet[t] + 1, 2^30); it starts at 2^30.
+ * 1. sense and mute, per receive channel c, in front of section R's reassembly; t = the transmit channel with rx_of_tx[t] == c, if any.
+ *    own = t exists and quiet[t] < mute_calls. If own: every row of the call loses PIRIP_RX_BITS before rule a / A reads it and keeps
+ *    PIRIP_RX_SYNC (the caller's rows are only read: the reassembly reads a copy), `muted` goes up by the rows that had BITS, carrier = 0.
+ *    Otherwise carrier = 1 iff some row f < nf has PIRIP_RX_SYNC with bit 0 of sense_mask, or stats[f][5] >= sense_snr with bit 1 and
+ *    stats rows given. idle[c] = 0 if own or carrier, else min(idle[c] + 1, 2^30); it starts at 0. `own` and `carrier` count the calls.
+ * 2. gate, per transmit channel t with c = rx_of_tx[t] >= 0. State: phase (PIRIP_MAC_IDLE at first), counter, run, accesses. due = the
+ *    pending ring's head burst exists and its ready tag <= n; queued = section K's queue of t is not empty before the offer. In this order:
+ *    1. HOLD and not queued: phase = IDLE.
+ *    2. IDLE and due: phase = CONTEND, counter = slot_calls * draw(key, t, accesses), accesses += 1.
+ *    3. CONTEND: if idle[c] > ifs_calls and counter == 0: phase = HOLD, run = 0, won += 1; if idle[c] > ifs_calls and counter > 0:
+ *       counter -= 1, backoff += 1; otherwise deferred += 1.
+ *    4. limit = HOLD ? txop_bursts - run : 0: section R's offer takes at most `limit` bursts beside its own rules; run and `bursts` go up
+ *       by what it took.
+ *    draw(key, t, a), in uint32 with a truncated to 32 bits:
+ *        x = key ^ t * 0x9E3779B9 ^ a * 0x85EBCA6B;  x ^= x >> 16;  x *= 0x7FEB352D;  x ^= x >> 15;  x *= 0x846CA68B;  x ^= x >> 16;
+ *        draw = ((uint64_t)x * cw) >> 32.
+ *    There is no exponential window: this layer sees no ACKs. */
+int pirip_hip_mac_create(pirip_hip_pkt *pkt, const pirip_mac_config *cfg, const int32_t *rx_of_tx, pirip_hip_mac **out);
+/* Detaches (synchronises the device): pkt then behaves as if no layer had ever been attached. */
+int pirip_hip_mac_destroy(pirip_hip_mac *mac);
+int pirip_hip_mac_get_info(const pirip_hip_mac *mac, pirip_mac_info *info);
+/* pirip_hip_pkt_push_records only: the stats rows that go with the status rows of the calls that follow, PIRIP_STATS_PER_FRAME floats per
+ * row, channel c's at d_stats + c * stats_stride (device, stride in floats, as pirip_hip_rx_process writes them; only read). NULL (the
+ * state after create): bit 1 senses nothing. PIRIP_ERR_BAD_ARG on a pkt with rx when bit 1 of sense_mask is set: the layer owns them. */
+int pirip_hip_mac_set_stats(pirip_hip_mac *mac, const float *d_stats, size_t stats_stride);
+/* The stats rows the next call's step 1 reads, as pirip_hip_pkt_records gives the status rows: what pirip_hip_mac_set_stats named, or on
+ * a pkt with rx and bit 1 the handle's own buffer, which holds the rows of the last process / push. *d_stats NULL: none. Each may be NULL. */
+int pirip_hip_mac_stats(pirip_hip_mac *mac, const float **d_stats, size_t *stats_stride);
+/* Host copies (synchronises the device), each may be NULL. Per transmit channel [ntx]: accesses, accesses won, calls counted down, calls
+ * deferred, bursts offered through the gate. Per receive channel [nrx]: calls with carrier, calls that were the own transmitter's, rows
+ * that lost PIRIP_RX_BITS. */
+int pirip_hip_mac_get_counters(pirip_hip_mac *mac, int64_t *accesses, int64_t *won, int64_t *backoff, int64_t *deferred, int64_t *bursts,
+                               int64_t *carrier, int64_t *own, int64_t *muted);
+/* Checking aid (synchronises), each pointer may be NULL: transmit channel t's phase, counter, run and quiet, and the idle run of the
+ * receive channel it listens on (-1 for an ungated channel). PIRIP_ERR_BAD_ARG for a t outside 0 .. ntx - 1. */
+int pirip_hip_mac_get_state(pirip_hip_mac *mac, int t, int *phase, int *counter, int *run, int *quiet, int *idle);
+/* Forgets the state and the counters: the next call is the layer's first. pirip_hip_pkt_reset (and with it pirip_hip_arq_reset) does the
+ * same to an attached layer. Enqueued on hip_stream. */
+int pirip_hip_mac_reset(pirip_hip_mac *mac, void *hip_stream);
+
+/* ----------------------------------------------------------------------------------- */
 /* section C : libcodec2-compatible single-stream API (host buffers)                    */
 /*             names and signatures as codec2 src/fsk.h [UPSTREAM-RECALLED]              */
 /* ----------------------------------------------------------------------------------- */

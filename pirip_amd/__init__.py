@@ -13,8 +13,10 @@ from .binding import (  # noqa: F401
     HipSpectrum, SpecBand, SpecInfo, SPEC_BAND_ROW_DTYPE, spec_window, spec_db, spec_occupied,
     DivConfig, DivEntry, DivInfo, DIV_ENTRY_DTYPE,
     PktConfig, PktEntry, PktInfo, PKT_ENTRY_DTYPE, PktFecConfig, PktFecInfo, ArqConfig, ArqEntry, ArqInfo, ARQ_ENTRY_DTYPE,
+    MacConfig, MacInfo, MAC_IDLE, MAC_CONTEND, MAC_HOLD,
     HipLdpc, HipRx, HipChan, HipTx, HipMux, HipTxStream, MUX_FIR, MUX_LINEAR, TX_CARRIER_OFF, STANDIN_CODE, RX_TRIAL_SYNC, RX_SYNC, RX_BITS, RX_BIT_ERRORS, LDPC_INFO_PER_CALL,
 )
 from .diversity import HipDiversity  # noqa: F401
 from .packet import HipPacket, HipPacketFec  # noqa: F401
 from .arq import HipArq  # noqa: F401
+from .mac import HipMac  # noqa: F401

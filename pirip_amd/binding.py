@@ -194,6 +194,21 @@ class ArqInfo(C.Structure):
                                        "device")]
 
 
+class MacConfig(C.Structure):
+    """pirip_mac_config: what counts as carrier and from which SNRest on, calls per backoff slot, slots to draw from, idle calls in front
+    of the countdown, calls muted behind the own transmitter, bursts per access, the key of the draws"""
+    _fields_ = [("sense_mask", C.c_int), ("sense_snr", C.c_float)] + \
+               [(n, C.c_int) for n in ("slot_calls", "cw", "ifs_calls", "mute_calls", "txop_bursts")] + [("key", C.c_uint32)]
+
+
+class MacInfo(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("ntx", "nrx", "sense_mask")] + [("sense_snr", C.c_float)] + \
+               [(n, C.c_int) for n in ("slot_calls", "cw", "ifs_calls", "mute_calls", "txop_bursts")] + [("key", C.c_uint32), ("device", C.c_int)]
+
+
+MAC_IDLE, MAC_CONTEND, MAC_HOLD = 0, 1, 2
+
+
 # pirip_spec_band_row as a numpy structured dtype (12 bytes, the C layout): what HipSpectrum.push's band entries are on the host
 SPEC_BAND_ROW_DTYPE = [("power", "<f4"), ("peak", "<f4"), ("peak_bin", "<i4")]
 
@@ -409,6 +424,15 @@ def _signatures():
         "pirip_hip_arq_get_delivered": (i32, [vp, i32, vp, vp, i32, P(i32)]),
         "pirip_hip_arq_get_state": (i32, [vp, i32, P(i64), P(i64), P(i64), P(i64), P(C.c_uint32), P(i32)]),
         "pirip_hip_arq_reset": (i32, [vp, vp]),
+        # section T: medium access
+        "pirip_hip_mac_create": (i32, [vp, P(MacConfig), vp, P(vp)]),
+        "pirip_hip_mac_destroy": (i32, [vp]),
+        "pirip_hip_mac_get_info": (i32, [vp, P(MacInfo)]),
+        "pirip_hip_mac_set_stats": (i32, [vp, vp, sz]),
+        "pirip_hip_mac_stats": (i32, [vp, P(vp), P(sz)]),
+        "pirip_hip_mac_get_counters": (i32, [vp] + [vp] * 8),
+        "pirip_hip_mac_get_state": (i32, [vp, i32, P(i32), P(i32), P(i32), P(i32), P(i32)]),
+        "pirip_hip_mac_reset": (i32, [vp, vp]),
         # the library itself
         "pirip_hip_find_code": (i32, [cs, cs, sz]),
         "pirip_hip_version": (cs, []),

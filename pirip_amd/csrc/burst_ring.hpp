@@ -60,6 +60,13 @@ __device__ __forceinline__ uint8_t *burst_ring_record(const BurstRingView &v, in
     return v.ring + ((size_t)t * v.pending + (size_t)ring_slot(start, j, v.pending)) * v.rl;
 }
 
+// a channel's limit on one offer (section T's gate): the offer takes at most `limit` bursts and adds what it took to run and bursts;
+// limit < 0: this channel has none, and nothing is added
+struct BurstLimit {
+    int32_t limit, run;
+    int64_t bursts;
+};
+
 struct BurstOfferArgs {
     BurstRingView v;
     const TxsChanState *queue; int64_t queue_syms;           // section K's queues: free space = queue_syms - (tail - head)
@@ -67,6 +74,7 @@ struct BurstOfferArgs {
     uint8_t *rec; int32_t *nrec;           // [ntx][pending][rl] and [ntx]: what section K's send path reads
     int psyms, fsyms;
     int64_t now;                           // n
+    BurstLimit *limit;                     // [ntx], or NULL: no limit beside the rules below
 };
 
 // One wave per transmit channel. Every lane walks the ring's bursts from the head (the same loads and the same decisions in all of them: no
@@ -81,8 +89,9 @@ static __global__ __launch_bounds__(64) void burst_offer_kernel(BurstOfferArgs a
     const int gap = a.gap[t] > 0 ? a.gap[t] : 0;              // tx_layout_kernel's rule
     const int64_t first_syms = tx_record_syms(1, a.psyms, a.fsyms, gap), next_syms = tx_record_syms(0, a.psyms, a.fsyms, gap);
     const int start = (int)(head % (uint64_t)pending);
+    const int lim = a.limit ? a.limit[t].limit : -1, most = lim < 0 ? INT32_MAX : lim;
     int take = 0, bursts = 0;
-    while (head + (uint64_t)take < tail) {
+    while (head + (uint64_t)take < tail && bursts < most) {
         const int slot = ring_slot(start, take, pending);
         const int len = a.v.blen[(size_t)t * pending + slot];
         if (len < 2 || take + len > pending || a.v.ready[(size_t)t * pending + slot] > a.now) break;
@@ -98,6 +107,7 @@ static __global__ __launch_bounds__(64) void burst_offer_kernel(BurstOfferArgs a
         a.v.rs[t].head = head + (uint64_t)take;
         a.v.rs[t].bursts_out += bursts;
         a.nrec[t] = take;
+        if (lim >= 0) { a.limit[t].run += bursts; a.limit[t].bursts += bursts; }
     }
 }
 
@@ -135,14 +145,16 @@ struct BurstRings {
     }
     // Call `now`'s offer and what follows it: whole bursts from every ring's head into txs's queues while they are due and fit, through
     // pirip_hip_txs_send's path, then pirip_hip_txs_process into d_out. The handle's device is current.
-    int offer_and_process(pirip_hip_tx *tx, pirip_hip_txs *txs, int64_t now, void *d_out, size_t out_stride_bytes, hipStream_t st)
+    // limit: section T's per-channel limits (device), NULL for none.
+    int offer_and_process(pirip_hip_tx *tx, pirip_hip_txs *txs, int64_t now, void *d_out, size_t out_stride_bytes, hipStream_t st,
+                          BurstLimit *limit = nullptr)
     {
         BurstOfferArgs oa{};
         oa.v = view();
         oa.queue = txs->d_state; oa.queue_syms = txs->queue_syms; oa.gap = tx->d_gap;
         oa.rec = d_offered; oa.nrec = d_noffered;
         oa.psyms = tx_pre_syms(tx); oa.fsyms = tx_frame_syms(tx);
-        oa.now = now;
+        oa.now = now; oa.limit = limit;
         hipLaunchKernelGGL(burst_offer_kernel, dim3((unsigned)ntx), dim3(64), 0, st, oa);
         PIRIP_HIPCHK(hipGetLastError());
         PIRIP_TRY(pirip_hip_txs_send(txs, d_offered, row_bytes(), d_noffered, pending, nullptr, st));

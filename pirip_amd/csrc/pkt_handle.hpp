@@ -78,6 +78,7 @@ struct pirip_hip_pkt {
     int rx_rows = 0;                       // with rx: record rows per channel and call (pirip_hip_rx_max_frames)
     int max_parity = 0, parity_pct = 0;    // an FEC handle (pirip_hip_pkt_create_fec): max_parity > 0
     int64_t calls = 0;                     // calls since create / reset: the n of the entries and of the offers
+    pirip_hip_mac *mac = nullptr;          // section T's layer while one is attached (mac_handle.hpp): it borrows this handle
     pirip::DevMem mem;
     pirip::PktRxState *d_rx_state = nullptr;        // [nrx]
     uint8_t *d_asm = nullptr;              // [nrx][(max_frags + max_parity) * cap] the open packet's body so far

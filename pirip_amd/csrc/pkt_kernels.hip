@@ -23,6 +23,7 @@
 #include "gf256_device.hpp"
 #include "hip_host.hpp"
 #include "ldpc_handle.hpp"
+#include "mac_handle.hpp"
 #include "mux_handle.hpp"
 #include "pkt_device.hpp"
 #include "pkt_handle.hpp"
@@ -174,6 +175,7 @@ int pkt_clear(pirip_hip_pkt *p, hipStream_t st)
         PIRIP_HIPCHK(hipMemsetAsync(p->d_tx_state, 0, sizeof(PktTxState) * (size_t)p->ntx, st));
         PIRIP_TRY(p->rings.clear(st));
     }
+    if (p->mac) PIRIP_TRY(mac_clear(p->mac, st));
     p->calls = 0;
     return PIRIP_OK;
 }
@@ -219,10 +221,14 @@ int pkt_check_out(const pirip_hip_pkt *p, const void *d_out, size_t out_stride_b
     return iq_rows_check(d_out, out_stride_bytes, p->txs->mux->bs, p->txs->mux->noutputs, p->txs->block);
 }
 
-// steps 1 - 3 over rows that are on the device; the handle's device is current
+// steps 1 - 3 over rows that are on the device; the handle's device is current. With section T's layer attached its steps come first:
+// the reassembly then reads that layer's copy of the status rows and the offer takes its limits (d_stats: the rows' stats, or NULL).
 int pkt_run(pirip_hip_pkt *p, const uint8_t *d_status, size_t status_stride, const uint8_t *d_payload, size_t payload_stride, const int32_t *d_ncalls,
-            int ncalls, void *d_out, size_t out_stride_bytes, hipStream_t st)
+            int ncalls, const float *d_stats, size_t stats_stride, void *d_out, size_t out_stride_bytes, hipStream_t st)
 {
+    BurstLimit *limit = nullptr;
+    if (p->mac)
+        PIRIP_TRY(mac_before(p->mac, d_status, status_stride, d_stats, stats_stride, d_ncalls, ncalls, p->calls, &d_status, &status_stride, &limit, st));
     PktRxArgs ra{};
     ra.status = d_status; ra.status_stride = status_stride; ra.payload = d_payload; ra.payload_stride = payload_stride;
     ra.nrows = d_ncalls; ra.max_rows = ncalls;
@@ -237,7 +243,7 @@ int pkt_run(pirip_hip_pkt *p, const uint8_t *d_status, size_t status_stride, con
         hipLaunchKernelGGL(pkt_rx_kernel, dim3((unsigned)p->nrx), dim3(64), pkt_rx_lds_bytes(ncalls), st, ra);
         PIRIP_HIPCHK(hipGetLastError());
     }
-    if (p->tx) PIRIP_TRY(p->rings.offer_and_process(p->tx, p->txs, p->calls, d_out, out_stride_bytes, st));
+    if (p->tx) PIRIP_TRY(p->rings.offer_and_process(p->tx, p->txs, p->calls, d_out, out_stride_bytes, st, limit));
     p->calls++;
     return PIRIP_OK;
 }
@@ -248,14 +254,18 @@ int pkt_receive(pirip_hip_pkt *p, const void *d_in, size_t in_stride_bytes, void
     PIRIP_TRY(pkt_check_out(p, d_out, out_stride_bytes));
     if (!bind_device(p->device)) return PIRIP_ERR_NO_DEVICE;
     const size_t R = (size_t)p->rx_rows, kb = (size_t)p->kb;
+    float *stats = p->mac ? p->mac->d_stats : nullptr;           // section T senses on the receiver's stats rows when its bit 1 asks
+    const size_t stats_stride = stats ? R * PIRIP_STATS_PER_FRAME : 0;
     if (d_in)
-        PIRIP_TRY(pirip_hip_rx_push(p->rx, d_in, in_stride_bytes, nullptr, 0, nullptr, 0, p->d_status, p->d_payload, p->d_info, nullptr, 0, p->d_nframes,
-                                    hip_stream));
+        PIRIP_TRY(pirip_hip_rx_push(p->rx, d_in, in_stride_bytes, nullptr, 0, nullptr, 0, p->d_status, p->d_payload, p->d_info, stats, stats_stride,
+                                    p->d_nframes, hip_stream));
     else
-        PIRIP_TRY(pirip_hip_rx_process(p->rx, nullptr, 0, nullptr, 0, p->d_status, p->d_payload, p->d_info, nullptr, 0, p->d_nframes, hip_stream));
+        PIRIP_TRY(pirip_hip_rx_process(p->rx, nullptr, 0, nullptr, 0, p->d_status, p->d_payload, p->d_info, stats, stats_stride, p->d_nframes,
+                                       hip_stream));
     p->last_status = p->d_status; p->last_status_stride = R; p->last_payload = p->d_payload; p->last_payload_stride = R * kb;
     p->last_nframes = p->d_nframes;
-    return pkt_run(p, p->d_status, R, p->d_payload, R * kb, p->d_nframes, p->rx_rows, d_out, out_stride_bytes, (hipStream_t)hip_stream);
+    return pkt_run(p, p->d_status, R, p->d_payload, R * kb, p->d_nframes, p->rx_rows, stats, stats_stride, d_out, out_stride_bytes,
+                   (hipStream_t)hip_stream);
 }
 
 }  // namespace
@@ -347,7 +357,8 @@ int pirip_hip_pkt_push_records(pirip_hip_pkt *p, const uint8_t *d_status, size_t
     if (ncalls > kPktMaxRows) return PIRIP_ERR_UNSUPPORTED;
     PIRIP_TRY(pkt_check_out(p, d_out, out_stride_bytes));
     if (!bind_device(p->device)) return PIRIP_ERR_NO_DEVICE;
-    PIRIP_TRY(pkt_run(p, d_status, status_stride, d_payload, payload_stride, d_ncalls, ncalls, d_out, out_stride_bytes, (hipStream_t)hip_stream));
+    PIRIP_TRY(pkt_run(p, d_status, status_stride, d_payload, payload_stride, d_ncalls, ncalls, p->mac ? p->mac->user_stats : nullptr,
+                      p->mac ? p->mac->user_stats_stride : 0, d_out, out_stride_bytes, (hipStream_t)hip_stream));
     p->last_status = d_status; p->last_status_stride = status_stride; p->last_payload = d_payload; p->last_payload_stride = payload_stride;
     p->last_nframes = d_ncalls;
     return PIRIP_OK;
