@@ -156,10 +156,12 @@ int pirip_hip_set_exact_first_frame(pirip_hip_demod *h, int enable);
 /* The same as text: the instance (template arguments, streams per workgroup, waves per SIMD) or the general kernel with its
  * run-time shape -- what bench.py prints as config.kernel. */
 int pirip_hip_get_kernel_name(const pirip_hip_demod *h, char *buf, size_t n);
-/* Back to the state fsk_create_hbr() leaves (Sf = 0, oscillators at phase 0, nin = N). */
+/* Back to the state fsk_create_hbr() leaves (Sf = 0, oscillators at phase 0, nin = N). Enqueued on hip_stream (NULL = default stream);
+ * never synchronises -- the streaming handles' resets (sections G, M, N, R, S) come through here. */
 int pirip_hip_reset(pirip_hip_demod *h, void *hip_stream);
 /* fsk_clear_estimators() for every stream [UPSTREAM-RECALLED codec2 fsk.c]: the smoothed spectrum Sf back to zero and nin back
- * to N -- oscillator phases, integrator memory, timing and ppm estimates stay, as upstream leaves them. */
+ * to N -- oscillator phases, integrator memory, timing and ppm estimates stay, as upstream leaves them. Enqueued on hip_stream; never
+ * synchronises. */
 int pirip_hip_clear_estimators(pirip_hip_demod *h, void *hip_stream);
 
 /* Demodulate one batch. Stream s reads complex samples from
@@ -382,7 +384,9 @@ int pirip_hip_ldpc_get_layout_conflicts(const pirip_hip_ldpc *h, int *identity, 
  *   d_status  [s][ncalls]                 rx_status byte (PIRIP_RX_*)
  *   d_payload [s][ncalls][k/8]            packed payload bytes, zeros when the call produced no frame
  *   d_info    [s][ncalls][PIRIP_LDPC_INFO_PER_CALL]
- * i.e. the `rtl_fsk -b` record stream. Sync state and the last two frames of soft bits carry to the next call. */
+ * i.e. the `rtl_fsk -b` record stream. Sync state and the last two frames of soft bits carry to the next call.
+ * This call and the ones below are enqueued on hip_stream and do not synchronise, except that a call with more ncalls (max_frames, ncw)
+ * than any before it grows the handle's work rows and waits for hip_stream first; pirip_hip_rx_create sizes them for its receiver. */
 int pirip_hip_ldpc_rx_batch(pirip_hip_ldpc *h, const float *d_rx_filt, size_t filt_stride, const int32_t *d_ncalls, int ncalls,
                             uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, void *hip_stream);
 /* The whole receive chain of one batch in one call -- what `rtl_fsk --code NAME` does per block of IQ: stream s of `dem` (created

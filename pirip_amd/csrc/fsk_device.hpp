@@ -146,6 +146,7 @@ int fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const void *d
                           uint8_t *d_status, uint8_t *d_payload, int32_t *d_info, float *d_stats, size_t stats_stride,
                           int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, const SegDesc *seg, hipStream_t st);
 int ldpc_handle_shape(const pirip_hip_ldpc *h, int *M, int *Nsym, int *nstreams, int *device);   // (ldpc_rx.hip)
+int ldpc_reserve(pirip_hip_demod *dem, pirip_hip_ldpc *h, int64_t nsamp, int64_t max_frames);   // (ldpc_rx.hip) the chain's work rows, sized ahead of the calls
 // pirip_capi.hip: the demodulator's side of the fused hand-over
 int demod_batch_soft(pirip_hip_demod *h, const void *d_in, size_t in_stride_bytes, int64_t nsamp, const SoftOut &so, float *d_stats, size_t stats_stride,
                      int32_t *d_nframes, int64_t *d_consumed, int64_t max_frames, hipStream_t st, int s0 = 0, int n = -1,

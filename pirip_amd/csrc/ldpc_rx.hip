@@ -401,6 +401,23 @@ int pirip::fsk_ldpc_rx_batch_seg(pirip_hip_demod *dem, pirip_hip_ldpc *h, const 
     return pirip_hip_ldpc_rx_batch(h, h->d_filt_work, (size_t)ncalls * per, d_nframes, ncalls, d_status, d_payload, d_info, hip_stream);
 }
 
+// The work rows of chain calls of max_frames frames over nsamp samples, sized now: a streaming receiver asks at create, where it waits
+// for the device anyway, so that none of its calls meets the growth (and the wait for the stream that comes with it).
+int pirip::ldpc_reserve(pirip_hip_demod *dem, pirip_hip_ldpc *h, int64_t nsamp, int64_t max_frames)
+{
+    if (!dem || !h || max_frames <= 0 || max_frames > (1 << 24)) return PIRIP_ERR_BAD_ARG;
+    if (!bind_device(h->device)) return PIRIP_ERR_NO_DEVICE;
+    const LdpcDev &c = h->dev;
+    const int ncalls = (int)max_frames;
+    PIRIP_HIPCHK(hipDeviceSynchronize());                  // (calls in flight may still use the rows that are replaced)
+    PIRIP_TRY(ensure_work(h, ncalls, nullptr));
+    if ((2 * c.bpf) % 32 == 0 && demod_soft_capable(dem, nsamp)) return PIRIP_OK;
+    if ((size_t)ncalls > h->filt_cap)
+        PIRIP_TRY(grow_dev(h->mem, &h->filt_cap, (size_t)ncalls, GrowSync::none, nullptr,
+                           {grow_buf(&h->d_filt_work, sizeof(float) * (size_t)h->nstreams * ncalls * (size_t)c.M * c.Nsym)}));
+    return PIRIP_OK;
+}
+
 int pirip::ldpc_handle_shape(const pirip_hip_ldpc *h, int *M, int *Nsym, int *nstreams, int *device)
 {
     if (!h) return PIRIP_ERR_BAD_ARG;

@@ -26,13 +26,18 @@ int reset_state(pirip_hip_demod *h, hipStream_t st)
     PIRIP_HIPCHK(hipMemsetAsync(h->d_theta, 0, sizeof(uint32_t) * ns * kMaxTones, st));
     PIRIP_HIPCHK(hipMemsetAsync(h->d_hist, 0, sizeof(float2) * ns * d.M * d.hist_len, st));
     PIRIP_HIPCHK(hipMemsetAsync(h->d_phic, 0, sizeof(float2) * ns * kMaxTones, st));
-    std::vector<StreamScalars> sc(ns);
-    std::memset(sc.data(), 0, sizeof(StreamScalars) * ns);
-    for (auto &s : sc) s.nin = d.N;
-    PIRIP_HIPCHK(hipMemcpyAsync(h->d_scal, sc.data(), sizeof(StreamScalars) * ns, hipMemcpyHostToDevice, st));
-    PIRIP_HIPCHK(hipStreamSynchronize(st));   // sc goes out of scope
+    // the scalars as create leaves them come from the device copy made at create: nothing here waits for the stream
+    PIRIP_HIPCHK(hipMemcpyAsync(h->d_scal, h->d_scal0, sizeof(StreamScalars) * ns, hipMemcpyDeviceToDevice, st));
     h->nin0 = d.N;
     h->fresh = true;
+    return PIRIP_OK;
+}
+
+// create and the setters that move a handle to another kernel: on the default stream, and done when the call returns
+int reset_state_now(pirip_hip_demod *h)
+{
+    PIRIP_TRY(reset_state(h, nullptr));
+    PIRIP_HIPCHK(hipStreamSynchronize(nullptr));
     return PIRIP_OK;
 }
 
@@ -72,6 +77,10 @@ int alloc_tables_and_state(pirip_hip_demod *h)
     PIRIP_TRY(m.alloc(&h->d_theta, sizeof(uint32_t) * ns * kMaxTones));
     PIRIP_TRY(m.alloc(&h->d_hist, sizeof(float2) * ns * d.M * d.hist_len));
     PIRIP_TRY(m.alloc(&h->d_scal, sizeof(StreamScalars) * ns));
+    std::vector<StreamScalars> sc0(ns);
+    std::memset(sc0.data(), 0, sizeof(StreamScalars) * ns);
+    for (auto &s : sc0) s.nin = d.N;
+    PIRIP_TRY(m.upload(&h->d_scal0, sc0.data(), sizeof(StreamScalars) * ns));
     PIRIP_TRY(m.alloc(&h->d_first, sizeof(int32_t) * ns));
     PIRIP_TRY(m.alloc(&h->d_phic, sizeof(float2) * ns * kMaxTones));
     return PIRIP_OK;
@@ -214,7 +223,7 @@ int pirip_hip_create_recalled(const pirip_fsk_params *p, const pirip_fsk_recalle
     rc = alloc_tables_and_state(h);
     if (rc != PIRIP_OK) { delete h; return rc; }
     if (const char *e = getenv("PIRIP_EXACT0")) h->exact0 = atoi(e) ? 1 : 0;
-    rc = reset_state(h, nullptr);
+    rc = reset_state_now(h);
     if (rc != PIRIP_OK) { delete h; return rc; }
     *out = h;
     return PIRIP_OK;
@@ -252,10 +261,9 @@ int pirip_hip_clear_estimators(pirip_hip_demod *h, void *hip_stream)
     const FskDims &d = h->plan.d;
     const size_t ns = (size_t)h->nstreams;
     PIRIP_HIPCHK(hipMemsetAsync(h->d_Sf, 0, sizeof(float) * ns * d.Ndft, st));
-    // nin = N in every stream's scalars: a strided copy of one int per stream
-    std::vector<int32_t> nin(ns, d.N);
-    PIRIP_HIPCHK(hipMemcpy2DAsync(&h->d_scal->nin, sizeof(StreamScalars), nin.data(), sizeof(int32_t), sizeof(int32_t), ns, hipMemcpyHostToDevice, st));
-    PIRIP_HIPCHK(hipStreamSynchronize(st));   // nin goes out of scope
+    // nin = N in every stream's scalars: a strided copy of one int per stream, from the device copy of the created scalars
+    PIRIP_HIPCHK(hipMemcpy2DAsync(&h->d_scal->nin, sizeof(StreamScalars), &h->d_scal0->nin, sizeof(StreamScalars), sizeof(int32_t), ns,
+                                  hipMemcpyDeviceToDevice, st));
     h->nin0 = d.N;
     return PIRIP_OK;
 }
@@ -488,7 +496,7 @@ int pirip_hip_enable_eye(pirip_hip_demod *h, int enable)
     PIRIP_HIPCHK(hipMemset(h->d_eye, 0, bytes));
     if (h->kernel != PIRIP_KERNEL_GENERAL && h->kernel != PIRIP_KERNEL_EXACT) {
         h->kernel = PIRIP_KERNEL_GENERAL;
-        return reset_state(h, nullptr);
+        return reset_state_now(h);
     }
     return PIRIP_OK;
 }
@@ -548,7 +556,8 @@ int pirip_hip_set_estimator_band_only(pirip_hip_demod *h, int enable)
     }
     if (!h->plan.d.est_band) return PIRIP_OK;
     h->plan.d.est_band = 0;
-    return pirip_hip_reset(h, nullptr);
+    if (!bind(h)) return PIRIP_ERR_NO_DEVICE;
+    return reset_state_now(h);
 }
 
 // fsk_enable_burst_mode() for every stream of the handle: nin is pinned to N from now on

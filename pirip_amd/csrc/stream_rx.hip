@@ -248,7 +248,9 @@ int rx_create_impl(pirip_hip_demod *dem, pirip_hip_ldpc *ldpc, pirip_hip_decim *
         rx->raw_pre = round_up((size_t)rx->H * 2, 256);
         rx->raw_row_bytes = round_up(rx->raw_pre + (size_t)block * 2, 256);
     }
-    const int rc = rx_alloc(rx);
+    int rc = rx_alloc(rx);
+    // the FSK_LDPC receiver grows its work rows with the largest call it has seen: every call of this receiver has the same size, known now
+    if (rc == PIRIP_OK && ldpc) rc = ldpc_reserve(dem, ldpc, rx->c_pre + rx->m, rx->budget);
     if (rc != PIRIP_OK) { delete rx; return rc; }
     *out = rx;
     return PIRIP_OK;
